@@ -6,6 +6,11 @@ HBM (packed 2-bit), against the BASELINE C2 database (DNA k=10, 999 branches, ~1
 Multi-GPU: reads shard across ranks, DB replicated per GPU, no collective on the data path ("weak" scaling:
 every rank places its own `--reads`).  The CPU oracle is used here ONLY as the cpu_baseline leg and as the
 pre-timing checker of a sample; the timed path is the HIP engine through the C ABI.
+
+A plain run sets up, warms up, times `--steps` steps, writes the last step's outputs if `--dump-outputs DIR` is
+given, and prints the one JSON line.  Everything else the line can carry (the oracle check of a sample, roofline
+and work counters, the clade-shaped, PCIe-inclusive, FASTA-to-jplace and single-process legs, the CPU baselines)
+runs only with `--full`.
 """
 import argparse
 import json
@@ -33,7 +38,17 @@ def parse():
     ap.add_argument("--reads", type=int, default=0, help="reads per GPU per step (default: the config's count)")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per read (0=auto, 8/16/32/64)")
     ap.add_argument("--table", default="auto", choices=["auto", "direct", "direct8", "hash"])
-    ap.add_argument("--verify", type=int, default=2000, help="reads checked against the oracle before timing")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg of the line besides the timed steps: the oracle check of a sample before timing (--verify), roofline and "
+                         "work counters, the clade-shaped, PCIe-inclusive, FASTA-to-jplace and single-process legs, the CPU baselines (each still "
+                         "switched off by its own --no-* option).  Off by default: a plain run only sets up, warms up, times --steps steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64): n_rows, branch, score, "
+                         "lwr and flags of a fixed, seeded sample of at most 262 144 reads, their indices in the batch as read_index (rank r > 0 "
+                         "adds .rank<r> to the names).  Every value is finite: the -inf score of an unused row (past n_rows) is written as "
+                         "the lowest float32")
+    ap.add_argument("--verify", type=int, default=2000, help="--full: reads checked against the oracle before timing")
     ap.add_argument("--cpu-sample", type=int, default=100000, help="reads timed on the CPU oracle (rank 0, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-clade", action="store_true", help="C2 and T4k ... T64k: skip the clade-shaped variant of the line (reads cut from a genome whose k-mers "
@@ -48,7 +63,7 @@ def parse():
     ap.add_argument("--force-device", type=int, default=-1, help="rehearsal only: put every rank on this device")
     ap.add_argument("--single-process", action="store_true",
                     help="add the mode RAPPAS itself would use -- ONE host process driving the GPUs: rk_db_clone to every device, one rk_place_batch_multi call per "
-                         "step over page-locked buffers -- as the field `single_process` (never `value`).  On by default when --gpus > 1 (rank 0 measures it after "
+                         "step over page-locked buffers -- as the field `single_process` (never `value`).  On by default with --full when --gpus > 1 (rank 0 measures it after "
                          "the ranks' timed region); with --gpus 1 it runs --sp-handles handles on the one device")
     ap.add_argument("--sp-handles", type=int, default=0, help="--single-process: handles (default: --gpus; on fewer visible devices they share them round-robin)")
     ap.add_argument("--sp-reads", type=int, default=2_000_000, help="--single-process: reads per handle and step")
@@ -133,6 +148,36 @@ def unpack_to_ascii(alphabet, packed_np, length):
         out[:, i] = letters[(v & np.uint64((1 << bits) - 1)).astype(np.int64)]
     off = (np.arange(n + 1, dtype=np.uint64) * np.uint64(length))
     return out.reshape(-1), off
+
+
+DUMP_READS = 262_144  # reads in the --dump-outputs sample: 132 bytes each in the files, about 35 MB in all
+UNUSED_SCORE = np.finfo(np.float32).min  # --dump-outputs: the score of an unused row (-inf from the engine), as a finite number
+
+
+def dump_outputs(torch, d, out, n_reads, rank):
+    """--dump-outputs: the placement arrays of the last timed step, as a caller of place_packed receives them, for a fixed, seeded sample
+    of reads (all of them up to DUMP_READS), each as d/<name>.npy in float32 (n_rows, branch, score) or float64 (lwr, flags, read_index).
+    Rows past a read's n_rows are unused (include/rappas_place.h: branch 0xFFFF, score -inf, lwr 0); their score is written as UNUSED_SCORE
+    so that every value in the files is finite."""
+    if n_reads <= DUMP_READS:
+        idx = np.arange(n_reads, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(20240607).choice(n_reads, DUMP_READS, replace=False)).astype(np.int64)
+    sel = torch.from_numpy(idx).to(out["n_rows"].device)
+    take = lambda name: out[name].index_select(0, sel).cpu().numpy()
+    n_rows = take("n_rows")
+    score = take("score").astype(np.float32)
+    score[np.arange(score.shape[1])[None, :] >= n_rows[:, None]] = UNUSED_SCORE
+    arrays = {"read_index": idx.astype(np.float64),
+              "n_rows": n_rows.astype(np.float32),
+              "branch": take("branch").view(np.uint16).astype(np.float32),   # 0xFFFF = unused row
+              "score": score,
+              "lwr": take("lwr").astype(np.float64),
+              "flags": take("flags").view(np.uint32).astype(np.float64)}
+    os.makedirs(d, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for name, arr in arrays.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), arr)
 
 
 def row_length_table(sdb):
@@ -629,13 +674,15 @@ def main():
     def step():
         pp.place_packed(packed, fixed_len=rlen, out=out, keepAtMost=K)
 
-    # ---- correctness gate on a sample before any timing (oracle = checker only) ----
+    # the first launch (code object load, the engine's lazy set-up) stays out of the warm-up and the timed steps
+    step()
+    torch.cuda.synchronize()
+
+    # ---- --full: correctness gate on a sample before any timing (oracle = checker only) ----
     verified = None
-    if a.verify and rank == 0:
+    if a.full and a.verify and rank == 0:
         from tests.util import compare_with_oracle
         nv = min(a.verify, n_reads, 48 if spec is not None else a.verify)
-        step()
-        torch.cuda.synchronize()
         seq, off = unpack_to_ascii(alphabet, packed[:nv].cpu().numpy().view(np.uint32), rlen)
         odb = oracle_db_for(seq, off)
         ref = odb.place(seq, off, keep_at_most=K)
@@ -645,17 +692,18 @@ def main():
         st = compare_with_oracle(got, ref, odb, seq, off)
         verified = dict(reads=nv, ties=st["ties"], max_lwr_rel=st["max_lwr_rel"])
 
-    # ---- algorithmic bytes: B = ceil(R*b/8) + Q*8 + H*6 + (2 + K*14)   ----
+    # ---- --full: algorithmic bytes: B = ceil(R*b/8) + Q*8 + H*6 + (2 + K*14)   ----
     Q = rlen - k + 1
-    H_total, hit_kmers = count_entries_torch(torch, lens_table, alphabet, k, bits, packed, rlen)
-    H_mean = H_total / n_reads
-    B = math.ceil(rlen * bits / 8) + Q * 8 + H_mean * 6 + (2 + K * 14)
-    # the engine's own count of the same quantities (rk_count_work_device: a kernel of its own) next to the torch count above
-    try:
-        work = pp.count_work(packed, fixed_len=rlen)
-        work["equals_independent_count"] = bool(work["entries"] == H_total and work["kmers_hit"] == hit_kmers and work["kmers_probed"] == n_reads * Q)
-    except AttributeError:  # (RK_LIB pointing at a build older than the entry point)
-        work = None
+    if a.full:
+        H_total, hit_kmers = count_entries_torch(torch, lens_table, alphabet, k, bits, packed, rlen)
+        H_mean = H_total / n_reads
+        B = math.ceil(rlen * bits / 8) + Q * 8 + H_mean * 6 + (2 + K * 14)
+        # the engine's own count of the same quantities (rk_count_work_device: a kernel of its own) next to the torch count above
+        try:
+            work = pp.count_work(packed, fixed_len=rlen)
+            work["equals_independent_count"] = bool(work["entries"] == H_total and work["kmers_hit"] == hit_kmers and work["kmers_probed"] == n_reads * Q)
+        except AttributeError:  # (RK_LIB pointing at a build older than the entry point)
+            work = None
 
     for _ in range(a.warmup):
         step()
@@ -679,24 +727,12 @@ def main():
     elapsed, per_rank = sync.finish(t0, t1, dict(reads_per_s=n_reads * a.steps / (t_own - t0), kernel_ms=kern_avg_s * 1e3,
                                                   device=torch.cuda.get_device_name(local_rank), device_index=local_rank,
                                                   pci_bus_id=pci_bus_id(local_rank)))
+    if a.dump_outputs:
+        dump_outputs(torch, a.dump_outputs, out, n_reads, rank)
 
     if rank == 0:
         value = n_gpus * n_reads * a.steps / elapsed
-        achieved = (B * n_reads / kern_avg_s) / 1e9  # GB/s, algorithmic bytes / average kernel duration
         peak = 8000.0
-        traffic = None
-        # HBM-side bytes per launch from the committed rocprofv3 --pmc passes of THIS configuration and batch size
-        # (profiles/pmc_traffic_<config>.json, written by scripts/profile.sh + prof_summary.py; null when none matches)
-        pmc_path = os.path.join(ROOT, "profiles", f"pmc_traffic_{a.config}.json")
-        if not os.path.exists(pmc_path):
-            pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc_path):
-            try:
-                pj = json.load(open(pmc_path))
-                if pj.get("config") == a.config and pj.get("reads") == n_reads:
-                    traffic = pj.get("hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
         sym = "bp DNA" if alphabet == 4 else "aa"
         metric = {"C2": "reads placed/sec (whole node), 150 bp DNA vs 10^7-kmer DB",
                   "C3": "reads placed/sec (whole node), 150 bp DNA vs 10^7-kmer DB"}.get(
@@ -711,16 +747,31 @@ def main():
                                    f"{n_reads} x {rlen} symbol reads per GPU per step (uniform, seed 1+rank), keep_at_most=7",
                        "table": {ra.RK_TABLE_DIRECT: "direct (compact blocks: 0.67 B/k-mer with 4-bit unit counts, 1.33 B/k-mer with bytes; see config.kernel)", ra.RK_TABLE_DIRECT8: "direct8", ra.RK_TABLE_HASH: "hash"}[db.info.table_mode],
                        "kernel": db.kernel_name(), "reads_per_gpu": n_reads, "sharding": f"reads x{n_gpus}, DB replicated"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
-                         "traffic": traffic, "bytes_per_read": B, "entries_per_read": H_mean,
-                         "kernel_ms": kern_avg_s * 1e3, "kernel": db.kernel_name().split("<")[0]},
-            "verified_vs_oracle": verified,
-            "work_counters": work,
         }
+        if a.full:
+            achieved = (B * n_reads / kern_avg_s) / 1e9  # GB/s, algorithmic bytes / average kernel duration
+            traffic = None
+            # HBM-side bytes per launch from the committed rocprofv3 --pmc passes of THIS configuration and batch size
+            # (profiles/pmc_traffic_<config>.json, written by scripts/profile.sh + prof_summary.py; null when none matches)
+            pmc_path = os.path.join(ROOT, "profiles", f"pmc_traffic_{a.config}.json")
+            if not os.path.exists(pmc_path):
+                pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc_path):
+                try:
+                    pj = json.load(open(pmc_path))
+                    if pj.get("config") == a.config and pj.get("reads") == n_reads:
+                        traffic = pj.get("hbm_bytes_per_launch")
+                except Exception:
+                    traffic = None
+            line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
+                                "traffic": traffic, "bytes_per_read": B, "entries_per_read": H_mean,
+                                "kernel_ms": kern_avg_s * 1e3, "kernel": db.kernel_name().split("<")[0]}
+            line["verified_vs_oracle"] = verified
+            line["work_counters"] = work
         line.update(per_rank_fields(sync, per_rank))
         line["n_gpus_visible"] = torch.cuda.device_count()
         line["device_pci_bus_id"] = pci_bus_id(local_rank)
-        if (a.single_process or n_gpus > 1) and alphabet == 4 and spec is None:
+        if (a.single_process or (a.full and n_gpus > 1)) and alphabet == 4 and spec is None:
             # ---- ONE process over all GPUs (what a single JVM would do), after every rank's timed region; never `value` ----
             sync.close()  # (the other ranks leave now: their processes must not sit in a barrier on the GPUs this leg is about to use)
             try:
@@ -730,7 +781,7 @@ def main():
             except Exception as e:
                 line["single_process"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         pinned_bufs = None
-        if not a.no_pcie and n_gpus == 1:
+        if a.full and not a.no_pcie and n_gpus == 1:
             # the page-locked caller buffers of the boundary legs below, allocated here, as a caller would at start-up.  (Allocated after
             # the clade leg -- seconds of numpy on the host in between -- the same leg ran at 1.0 - 1.9e8 reads/s instead of 3.0e8, five
             # runs of five: wherever the thread was by then, its page-locked memory landed further from the GPU.)
@@ -738,7 +789,7 @@ def main():
             pinned_bufs = (ra.host_alloc((npc_, wpr), np.uint32),
                            ra.Placements(ra.host_alloc(npc_, np.uint8), ra.host_alloc((npc_, K), np.uint16), ra.host_alloc((npc_, K), np.float32),
                                          ra.host_alloc((npc_, K), np.float64), ra.host_alloc(npc_, np.uint32), {}))
-        if a.config in ("C2", "T4k", "T8k", "T20k", "T40k", "T64k") and not a.no_clade and n_gpus == 1:
+        if a.full and a.config in ("C2", "T4k", "T8k", "T20k", "T40k", "T64k") and not a.no_clade and n_gpus == 1:
             # ---- the same tree and row statistics with clade-shaped reads (what real placements look like): never `value` ----
             cdb_s, genome = synth.make_clade_db(k=k, n_branches=n_branches)
             nc = min(2_000_000, n_reads)
@@ -769,7 +820,7 @@ def main():
                                          f"stretch of a 700 kbp genome share a neighbourhood of the tree; {nc} x {rlen} bp reads cut from the genome "
                                          "(every k-mer present: a third more row entries per read than the uniform reads of `value`)"}
             cdb.close()
-        if not a.no_pcie and n_gpus == 1:
+        if a.full and not a.no_pcie and n_gpus == 1:
             # ---- the boundary RAPPAS would call: host buffers in, host buffers out (never `value`) ----
             # pageable numpy arrays (what a JVM heap array looks like to the library), result arrays allocated once and reused
             npc = min(a.pcie_reads, n_reads)
@@ -810,7 +861,7 @@ def main():
                                 "threads": min(os.cpu_count() or 1, 16)},
                 "sample": f"first {npc} reads of the batch, pageable host arrays unless named page-locked, result arrays reused, 5 calls after two warm-ups",
                 "equals_device_path": same}
-        if not a.no_pcie and n_gpus == 1 and a.config == "C2" and alphabet == 4:
+        if a.full and not a.no_pcie and n_gpus == 1 and a.config == "C2" and alphabet == 4:
             # ---- the stand-alone tool around the kernel: FASTA bytes (page cache) -> .jplace bytes written, through rappas_amd/bin/rk_place
             #      (scan + dedup + gather + rk_place_batch + the jplace text, every pass on all of the tool's host threads; DB image
             #      loading and process start-up are outside the figure).  Never `value`. ----
@@ -818,7 +869,7 @@ def main():
                 line["fasta_to_jplace"] = fasta_to_jplace_leg(ra, db, h_seq, h_off, npc, rlen, n_branches, K)
             except Exception as e:  # the leg must not take the bench line down
                 line["fasta_to_jplace"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if not a.no_cpu_baseline and n_gpus == 1:
+        if a.full and not a.no_cpu_baseline and n_gpus == 1:
             # bounded sample: about 10 s of single-thread work (the oracle does ~1.6e7 row entries per second)
             ns = min(a.cpu_sample, n_reads, max(64 if spec is not None else 2000, int(1.6e8 / max(1.0, H_mean))))
             seq, off = unpack_to_ascii(alphabet, packed[:ns].cpu().numpy().view(np.uint32), rlen)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Authoring script of the known-answer vectors in tests/golden/build/ (phylo-kmer DB construction).
+"""Authoring script of the known-answer vectors in tests/golden/construction/ (phylo-kmer DB construction).
 
 The reference ships no fixtures for this path and cannot run here, so the vectors are derived from its source:
 tests/pyref_build.py replays src/core/algos/WordExplorer_v3.java:98-199 and its callers in plain Python (every float32
@@ -62,7 +62,8 @@ def make(name, alphabet, k, omega, node_probs, node_branch, align_rows=None, lim
                gaps=gaps, limit_to_1_jump=limit1,
                expected=dict(key_codes=codes.tolist(), row_offsets=off.tolist(), branch_ids=br.tolist(),
                              score_bits=sc.view(np.uint32).tolist(), tuples=tuples, visits=visits))
-    with open(os.path.join(HERE, "build", name + ".json"), "w") as f:
+    os.makedirs(os.path.join(HERE, "construction"), exist_ok=True)
+    with open(os.path.join(HERE, "construction", name + ".json"), "w") as f:
         json.dump(doc, f, indent=1)
     print(name, "keys", len(codes), "entries", len(br), "tuples", tuples, "visits", visits)
 

@@ -62,11 +62,11 @@ def has_tie(e):
 
 
 def build_cases():
-    return sorted(glob.glob(os.path.join(HERE, "golden", "build", "*.json")))
+    return sorted(glob.glob(os.path.join(HERE, "golden", "construction", "*.json")))
 
 
 def load_build(path):
-    """tests/golden/build/*.json (make_golden_build.py) -> kwargs for the builders + expected CSR."""
+    """tests/golden/construction/*.json (make_golden_build.py) -> kwargs for the builders + expected CSR."""
     with open(path) as f:
         g = json.load(f)
     states = np.array(g["states"], np.uint8)

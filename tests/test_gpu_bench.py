@@ -1,10 +1,12 @@
 """GPU (-m gpu): bench.py's contract -- `--gpus N` really starts N ranks (one process per GPU), every config named in
-BASELINE.json has a bench leg, and the JSON line carries roofline + cpu_baseline."""
+BASELINE.json has a bench leg, the JSON line carries roofline + cpu_baseline with --full, and a plain run times the steps it is
+asked for and can write what its last step computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +27,7 @@ def run_bench(*args, timeout=900, **extra_env):
 def test_gpus_2_starts_two_ranks_and_reports_the_whole_job(backend):
     """two ranks rehearsed on the one GPU of this box: gloo for the barrier / max-over-ranks (RCCL needs one GPU per rank), and
     with no process group at all (file rendezvous + monotonic stamps)"""
-    common = ["--reads", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", "--verify", "300"]
+    common = ["--full", "--reads", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", "--verify", "300"]
     one = run_bench("--gpus", "1", *common)
     two = run_bench("--gpus", "2", "--force-device", "0", "--dist-backend", backend, *common)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
@@ -57,7 +59,7 @@ def test_world_size_mismatch_is_an_error():
 
 @pytest.mark.parametrize("config,reads", [("C1", "1000"), ("C4", "100000"), ("C3", "2000000"), ("T4k", "200000"), ("T40k", "100000"), ("T64k", "100000"), ("P20k", "100000")])
 def test_other_configs_have_a_bench_leg(config, reads):
-    line = run_bench("--config", config, "--reads", reads, "--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--verify", "500")
+    line = run_bench("--full", "--config", config, "--reads", reads, "--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--verify", "500")
     assert line["config"]["workload"].startswith(config + ":")
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["value"] > 0
     assert line["verified_vs_oracle"]["reads"] == 500
@@ -67,7 +69,8 @@ def test_single_process_mode_and_device_identity_fields():
     """what the first real multi-GPU record needs in order to prove N distinct GPUs (PCI bus ids per rank, visible-device count) and the
     mode RAPPAS itself would use -- ONE process, rk_db_clone to every device, rk_place_batch_multi per step -- here with three
     handles on the one GPU of this box; with two ranks on it, rank 0 measures the single-process mode after the ranks' timed region"""
-    common = ["--reads", "300000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", "--no-clade", "--verify", "200", "--sp-reads", "150000"]
+    common = ["--full", "--reads", "300000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pcie", "--no-clade", "--verify", "200",
+              "--sp-reads", "150000"]
     one = run_bench("--gpus", "1", "--single-process", "--sp-handles", "3", *common)
     assert one["n_gpus_visible"] >= 1 and len(one["device_pci_bus_id"].split(":")) == 3
     sp = one["single_process"]
@@ -98,3 +101,38 @@ def test_device_ordinals_follow_hip_visible_devices():
         outs.append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]))
     assert outs[0]["placed"] == outs[1]["placed"] > 400 and outs[0]["pci"] == outs[1]["pci"] and outs[1]["info_device"] == 0
     assert outs[1]["second"] == -1   # RK_ERR_INVALID: device 1 is out of range when one device is visible
+
+
+def test_plain_run_times_the_steps_asked_for_and_dumps_the_last_step(tmp_path):
+    """a plain run: the result line without the --full legs, `steps` as asked, ms_per_step of one timed step; --dump-outputs writes
+    the last step's arrays (a seeded sample when the batch is larger than it), the same from run to run with the same arguments"""
+    args = ["--gpus", "1", "--reads", "300000", "--steps", "4", "--warmup", "1"]
+    one = run_bench(*args, "--dump-outputs", str(tmp_path / "one"))
+    two = run_bench(*args, "--dump-outputs", str(tmp_path / "two"))
+    for line in (one, two):
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["unit"] == "reads/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["value"] > 0
+        assert abs(line["value"] - 300000 / (line["ms_per_step"] / 1e3)) / line["value"] < 1e-6
+        for leg in ("roofline", "verified_vs_oracle", "work_counters", "clade", "pcie_inclusive", "fasta_to_jplace", "cpu_baseline",
+                    "cpu_baseline_all_cores", "single_process"):
+            assert leg not in line, leg
+    names = {"read_index": np.float64, "n_rows": np.float32, "branch": np.float32, "score": np.float32, "lwr": np.float64, "flags": np.float64}
+    assert sorted(os.listdir(tmp_path / "one")) == sorted(n + ".npy" for n in names)
+    got = {}
+    for name, dt in names.items():
+        x, y = np.load(tmp_path / "one" / (name + ".npy")), np.load(tmp_path / "two" / (name + ".npy"))
+        assert x.dtype == dt and x.shape[0] == 262144 and np.array_equal(x, y, equal_nan=True), name
+        got[name] = x
+    assert sum(os.path.getsize(tmp_path / "one" / (n + ".npy")) for n in names) < 64 << 20
+    idx = got["read_index"]
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 300000
+    assert got["branch"].shape == got["score"].shape == got["lwr"].shape == (262144, 7)
+    n_rows = got["n_rows"].astype(np.int64)
+    placed = (got["flags"].astype(np.uint32) & 1) != 0
+    assert np.all(placed[n_rows > 0]) and placed.sum() > 0 and n_rows.max() <= 7
+    used = np.arange(7)[None, :] < n_rows[:, None]      # rows past n_rows: branch 0xFFFF, score -inf, lwr 0 (include/rappas_place.h)
+    assert np.all(got["branch"][~used] == 0xFFFF) and np.all(got["branch"][used] < 0xFFFF)
+    assert np.all(got["score"][~used] == np.finfo(np.float32).min) and np.all(got["score"][used] > np.finfo(np.float32).min)
+    for name, x in got.items():
+        assert np.all(np.isfinite(x)), name
+    assert np.all(got["lwr"][~used] == 0) and np.all(got["lwr"][used] > 0)
