@@ -28,6 +28,14 @@ struct __attribute__((aligned(8))) Entry {
 #endif
 constexpr u32 ROWS_FIT32_LIMIT = RK_FIT32_LIMIT;  // blobs below this use 32-bit offsets (ITEM_FILLER must stay outside the buffer)
 constexpr u32 ROW_UNIT = 16;  // entries per 128-byte unit; rows are unit-aligned and padded to whole units
+// Dense view of a small-tree image (<= 1 023 branches, compact table, 32-bit offsets, no windows; built on the device from the
+// canonical image, which stays as it is): 128-byte units of 24 entries, dwords w[0..31], lane li of a 16-lane group loading
+// w[2li], w[2li + 1] as today.  w[2li] = d of entry li; li < 8: w[2li + 1] = d of entry 16 + li; li >= 8, j = li - 8:
+// w[2li + 1] = slot(j) | slot(j + 8) << 10 | slot(16 + j) << 20.  d = fl(score - T), the increment apply_slot computes; slot =
+// word index in the score vector (branch + 1, 0 = scratch).  Padding is all zero.  Rows stay unit-aligned in dense k-mer order
+// and unit 0 stays reserved; the view's compact table (same form as the canonical one) counts dense units.
+constexpr u32 ROW_UNIT24 = 24;
+constexpr u32 SLOT24_BITS = 10, SLOT24_MAX = (1u << SLOT24_BITS) - 1;
 
 // k-mer -> row lookup flavours (template parameter of the kernels)
 constexpr int TM_HASH = 0, TM_DIRECT8 = 1, TM_COMPACT = 2;

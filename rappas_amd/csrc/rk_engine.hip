@@ -539,6 +539,9 @@ struct rk_db {
     bool windowed = false;
     bool has_pos = false;              // d_winspec holds position keys only (dense kernels)
     bool compact_nib = false;          // the compact table holds 4-bit unit counts
+    void *d_dense_table = nullptr;     // dense view (rk_device.h, ROW_UNIT24) for place_packed16_kernel, or nullptr: build_dense_view
+    void *d_dense_rows = nullptr;
+    uint64_t dense_rows_bytes = 0;
     WindowPlan wp;
     uint32_t lanes_per_read = 0;       // 0 = auto
     uint32_t waves_per_block = 1;
@@ -580,6 +583,8 @@ extern "C" void rk_db_destroy(rk_db *db) {
     (void)hipSetDevice(db->info.device);
     if (db->d_table) (void)hipFree(db->d_table);
     if (db->d_rows) (void)hipFree(db->d_rows);
+    if (db->d_dense_table) (void)hipFree(db->d_dense_table);
+    if (db->d_dense_rows) (void)hipFree(db->d_dense_rows);
     if (db->d_alpha) (void)hipFree(db->d_alpha);
     if (db->d_winspec) (void)hipFree(db->d_winspec);
     if (db->stream) (void)hipStreamDestroy(db->stream);
@@ -633,6 +638,136 @@ static int open_db(const DbMeta &m, int device, rk_db **out) {
     return RK_OK;
 }
 
+// ---- the dense view of a small-tree image (rk_device.h, ROW_UNIT24): 24 entries per 128-byte unit instead of 16, so a read of C2
+//      pulls 123 row lines from the Infinity Cache instead of 145.  Built on the device from the canonical image,
+//      which stays as it is (save / load, clone, the ambiguity kernel, rk_db_fetch_row and every other kernel read that one) ----
+__device__ __forceinline__ u32 compact_count(const unsigned char *blk, u32 j, bool nib) {
+    return nib ? (blk[4 + j / 2] >> (4 * (j & 1))) & 15u : blk[4 + j];
+}
+// dense units of a canonical row of `units` units from unit cu: its entries end where the padding (slot 0) of its last unit starts;
+// a row keeps at least one unit, so a k-mer has a row in the dense view exactly when it has one in the canonical image
+__device__ __forceinline__ u32 dense_units_of(const Entry *rows, u32 cu, u32 units, u32 &n) {
+    const Entry *last = rows + (u64)(cu + units - 1) * ROW_UNIT;
+    u32 m = ROW_UNIT;
+    while (m > 0 && last[m - 1].branch == 0) m--;
+    n = (units - 1) * ROW_UNIT + m;
+    const u32 du = (n + ROW_UNIT24 - 1) / ROW_UNIT24;
+    return du ? du : 1u;
+}
+
+// pass 1, one thread per 16-byte table block: the dense unit counts of its k-mers (into the dense table, base left for pass 2) and their sum
+__global__ void dense_count_kernel(const uint4 *ctab, uint4 *dtab, u64 n_blocks, u32 per, bool nib, const Entry *rows, u32 *sums) {
+    for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b < n_blocks; b += (u64)gridDim.x * blockDim.x) {
+        const uint4 cblk = ctab[b];
+        const unsigned char *cb = (const unsigned char *)&cblk;
+        u32 ow[4] = {0u, 0u, 0u, 0u};
+        u32 cu = cblk.x, sum = 0, n;
+        for (u32 j = 0; j < per; j++) {
+            const u32 units = compact_count(cb, j, nib);
+            if (!units) continue;
+            const u32 du = dense_units_of(rows, cu, units, n);
+            if (nib) ow[1 + j / 8] |= du << (4 * (j % 8));
+            else ow[1 + j / 4] |= du << (8 * (j % 4));
+            sum += du;
+            cu += units;
+        }
+        dtab[b] = make_uint4(0u, ow[1], ow[2], ow[3]);
+        sums[b] = sum;
+    }
+}
+
+// pass 2, one thread per table block: its dense base (1 + the units of every block before it) and its rows in the dense layout
+__global__ void dense_fill_kernel(const uint4 *ctab, uint4 *dtab, u64 n_blocks, u32 per, bool nib, const Entry *rows, const u32 *bases,
+                                  float T, uint4 *drows) {
+    for (u64 b = (u64)blockIdx.x * blockDim.x + threadIdx.x; b < n_blocks; b += (u64)gridDim.x * blockDim.x) {
+        const uint4 cblk = ctab[b];
+        const unsigned char *cb = (const unsigned char *)&cblk;
+        u32 cu = cblk.x, du0 = bases[b], n;
+        ((u32 *)dtab)[4 * b] = du0;
+        for (u32 j = 0; j < per; j++) {
+            const u32 units = compact_count(cb, j, nib);
+            if (!units) continue;
+            const u32 du = dense_units_of(rows, cu, units, n);
+            const Entry *src = rows + (u64)cu * ROW_UNIT;
+            for (u32 q = 0; q < du; q++) {
+                u32 s[ROW_UNIT24], d[ROW_UNIT24];
+#pragma unroll
+                for (u32 t = 0; t < ROW_UNIT24; t++) {
+                    const u32 e = q * ROW_UNIT24 + t;
+                    const Entry x = e < n ? src[e] : Entry{0u, 0.0f};
+                    s[t] = x.branch >> 2;  // byte offset of the branch's word -> word index (<= SLOT24_MAX: n_branches <= 1 023)
+                    d[t] = s[t] ? __float_as_uint(x.score - T) : 0u;  // = apply_slot's fl(v - T), bit for bit
+                }
+                u32 w[32];
+#pragma unroll
+                for (u32 i = 0; i < 16; i++) w[2 * i] = d[i];
+#pragma unroll
+                for (u32 i = 0; i < 8; i++) {
+                    w[2 * i + 1] = d[16 + i];
+                    w[2 * (8 + i) + 1] = s[i] | s[i + 8] << SLOT24_BITS | s[16 + i] << (2 * SLOT24_BITS);
+                }
+                uint4 *dst = drows + (u64)(du0 + q) * 8;
+#pragma unroll
+                for (u32 i = 0; i < 8; i++) dst[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+            }
+            du0 += du;
+            cu += units;
+        }
+    }
+}
+
+// Every small-tree image place_packed16_kernel serves gets the view (the canonical layout stays in use when it cannot be made: out of
+// device memory, or the developer knob RK_NO_DENSE_UNITS, read per handle, for A/B runs and tests).  Needs the canonical image complete
+// on the current device.
+static void build_dense_view(rk_db *db) {
+    if (db->info.table_mode != RK_TABLE_DIRECT || db->info.n_branches > SLOT24_MAX || db->indexed || db->windowed ||
+        db->info.rows_bytes >= ROWS_FIT32_LIMIT || db->info.table_bytes < 16 || rk_knob("RK_NO_DENSE_UNITS"))
+        return;
+    // ... where rows stream (the nibble form's rule, build_table): a dense step costs more VALU and LDS work per unit, which only fewer row
+    // lines pay back.  C4 (0.13 row units per k-mer code) placed 7.97e8 reads/s with the view against 8.26e8 without; C2 (1.03): 3.78e8
+    // against 3.66e8
+    if (2 * (db->info.rows_bytes / 128) < db->info.table_slots) return;
+    const u64 n_blocks = db->info.table_bytes / 16;
+    const u32 per = db->compact_nib ? 2 * COMPACT_KMERS : COMPACT_KMERS;
+    const unsigned grid = (unsigned)std::min<u64>((n_blocks + 255) / 256, (u64)db->cu_count * 8);
+    u32 *d_sums = nullptr;
+    bool ok = false;
+    do {
+        std::vector<u32> sums(n_blocks);
+        if (hipMalloc((void **)&d_sums, n_blocks * 4) != hipSuccess || hipMalloc(&db->d_dense_table, n_blocks * 16) != hipSuccess) break;
+        hipLaunchKernelGGL(dense_count_kernel, dim3(grid), dim3(256), 0, db->stream, (const uint4 *)db->d_table, (uint4 *)db->d_dense_table,
+                           (u64)n_blocks, per, db->compact_nib, (const Entry *)db->d_rows, d_sums);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(sums.data(), d_sums, n_blocks * 4, hipMemcpyDeviceToHost, db->stream) != hipSuccess ||
+            hipStreamSynchronize(db->stream) != hipSuccess)
+            break;
+        u64 next = 1;  // unit 0: reserved, all zero
+        for (u64 b = 0; b < n_blocks; b++) {
+            const u64 c = sums[b];
+            sums[b] = (u32)next;
+            next += c;
+        }
+        const u64 bytes = next * 128;
+        if (bytes > db->info.rows_bytes) break;  // (cannot happen: a dense row never has more units than its canonical one)
+        if (hipMalloc(&db->d_dense_rows, bytes) != hipSuccess || hipMemsetAsync(db->d_dense_rows, 0, 128, db->stream) != hipSuccess ||
+            hipMemcpyAsync(d_sums, sums.data(), n_blocks * 4, hipMemcpyHostToDevice, db->stream) != hipSuccess)
+            break;
+        hipLaunchKernelGGL(dense_fill_kernel, dim3(grid), dim3(256), 0, db->stream, (const uint4 *)db->d_table, (uint4 *)db->d_dense_table,
+                           (u64)n_blocks, per, db->compact_nib, (const Entry *)db->d_rows, (const u32 *)d_sums, db->info.thr_log10,
+                           (uint4 *)db->d_dense_rows);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(db->stream) != hipSuccess) break;
+        db->dense_rows_bytes = bytes;
+        ok = true;
+    } while (false);
+    if (d_sums) (void)hipFree(d_sums);
+    if (!ok) {
+        if (db->d_dense_table) (void)hipFree(db->d_dense_table);
+        if (db->d_dense_rows) (void)hipFree(db->d_dense_rows);
+        db->d_dense_table = db->d_dense_rows = nullptr;
+        db->dense_rows_bytes = 0;
+        (void)hipGetLastError();
+    }
+}
+
 // info + device view once d_table / d_rows hold the image
 static void finish_db(rk_db *db, const DbMeta &m, uint32_t mode, bool indexed, bool mono, uint64_t n_keys, uint64_t n_entries,
                       uint64_t slots, uint64_t hash_mask, uint64_t table_bytes, uint64_t blob_bytes, uint32_t max_len) {
@@ -658,6 +793,7 @@ static void finish_db(rk_db *db, const DbMeta &m, uint32_t mode, bool indexed, b
     db->view.winspec = (db->windowed || db->has_pos) ? db->d_winspec : nullptr;
     db->view.win_w = db->windowed ? db->wp.W : 0u;
     db->view.n_win = db->windowed ? db->wp.n_win : 0u;
+    build_dense_view(db);
 }
 
 static int check_launchable(const rk_db *db);
@@ -1292,28 +1428,55 @@ static int launch_variant(const rk_db *db, const Geometry &g, const PlaceArgs &a
     constexpr int PU = G <= 16 ? (BITS == 5 && G == 16 ? 7 : 9) : (G == 32 ? 5 : 3);  // (= probe_unroll)
     constexpr int U = G == 64 ? RK_RING64 : RK_RING;
     auto kern = place_packed_kernel<G, BITS, TM, WIDE, U, PU>;
+    decltype(kern) clade_kern = nullptr;
+    PlaceArgs la = args;
     if constexpr (G == 16 && !WIDE && TM != TM_HASH) {
         if (use_pipelined16(db, g, args)) {
-            kern = place_packed16_kernel<BITS, TM, U, PU>;
+            auto k16 = place_packed16_kernel<BITS, TM, U, PU>;
+            auto k24 = place_packed16_kernel<BITS, TM, U, PU, TM == TM_COMPACT>;
             if constexpr (BITS == 5) {
                 // every read of the batch has the same, known length and at most 96 k-mers (C4: 100 residues, k = 5): six rounds
-                if (!args.lens && args.fixed_len >= db->info.k && args.fixed_len - db->info.k + 1 <= 96u) kern = place_packed16_kernel<BITS, TM, U, 6>;
+                if (!args.lens && args.fixed_len >= db->info.k && args.fixed_len - db->info.k + 1 <= 96u) {
+                    k16 = place_packed16_kernel<BITS, TM, U, 6>;
+                    k24 = place_packed16_kernel<BITS, TM, U, 6, TM == TM_COMPACT>;
+                }
+            }
+            kern = k16;
+            if (TM == TM_COMPACT && db->d_dense_rows) {  // the dense view: its own table and row blob, for this kernel only
+                kern = k24;
+                la.db.compact = (const uint4 *)db->d_dense_table;
+                la.db.rows = (const unsigned char *)db->d_dense_rows;
+                la.db.rows_bytes = db->dense_rows_bytes;
+                // Reads of a clade find most of their row lines in the L2 already, so the lines the view saves do not pay for its longer
+                // step (C2's clade line: 3.14e8 reads/s with the view against 3.27e8 without).  Where the re-tiling pre-pass judged the
+                // batch on the device, both kernels are launched and the one the batch is not for returns at once (PlaceArgs::only_if).
+                if (args.perm) {
+                    clade_kern = k16;
+                    la.only_if = 3u;  // bits 0, 1: uniform reads (batch_is_mine)
+                }
             }
         }
     }
     const uint32_t wpb = db->waves_per_block;
     const size_t lds = g.lds_per_wave * wpb;
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const uint64_t n_tiles = (args.n_reads + g.NG - 1) / g.NG;
-    uint64_t per_cu = 0;
-    if (int rc = resident_blocks(kern, 64 * (int)wpb, lds, (g.waves_per_cu + wpb - 1) / wpb, per_cu)) return rc;
-    uint64_t blocks = (uint64_t)db->cu_count * per_cu;
-    const uint64_t need = (n_tiles + wpb - 1) / wpb;
-    if (blocks > need) blocks = need;
-    if (blocks == 0) return RK_OK;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, args);
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
+    auto go = [&](decltype(kern) k, const PlaceArgs &pa) -> int {
+        HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        uint64_t per_cu = 0;
+        if (int rc = resident_blocks(k, 64 * (int)wpb, lds, (g.waves_per_cu + wpb - 1) / wpb, per_cu)) return rc;
+        uint64_t blocks = (uint64_t)db->cu_count * per_cu;
+        const uint64_t need = (n_tiles + wpb - 1) / wpb;
+        if (blocks > need) blocks = need;
+        if (blocks == 0) return RK_OK;
+        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, pa);
+        HIP_TRY(hipGetLastError());
+        return RK_OK;
+    };
+    if (int rc = go(kern, la)) return rc;
+    if (!clade_kern) return RK_OK;
+    PlaceArgs ca = args;
+    ca.only_if = 4u;  // bit 2: reads of a clade
+    return go(clade_kern, ca);
 }
 
 template <int G, int BITS, int TM>
@@ -1947,9 +2110,11 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
     probe.words_per_read = 16;
     // (the tile-pipelined variant serves packed records of <= 16 words, i.e. reads of <= 256 bases / 102 residues; longer
     // records take place_packed_kernel with the same geometry)
-    snprintf(buf, sizeof(buf), "%s<G=%u,BITS=%u,%s,%s,U=%d,PU=%u> lds/wave=%zuB cap=%u waves/CU<=%u (LDS; registers may allow fewer)",
-             use_pipelined16(db, g, probe) ? "place_packed16_kernel" : "place_packed_kernel", g.G, db->info.bits_per_symbol, db->info.table_mode == RK_TABLE_DIRECT ? (db->compact_nib ? "DIRECT4" : "DIRECT") : (db->info.table_mode == RK_TABLE_DIRECT8 ? "DIRECT8" : "HASH"),
-             db->info.rows_bytes < ROWS_FIT32_LIMIT ? "ITEM32" : "ITEM64", g.G == 64 ? RK_RING64 : RK_RING, g.pu, g.lds_per_wave, g.list_cap, g.waves_per_cu);
+    const bool pipe = use_pipelined16(db, g, probe);
+    snprintf(buf, sizeof(buf), "%s<G=%u,BITS=%u,%s,%s%s,U=%d,PU=%u> lds/wave=%zuB cap=%u waves/CU<=%u (LDS; registers may allow fewer)%s",
+             pipe ? "place_packed16_kernel" : "place_packed_kernel", g.G, db->info.bits_per_symbol, db->info.table_mode == RK_TABLE_DIRECT ? (db->compact_nib ? "DIRECT4" : "DIRECT") : (db->info.table_mode == RK_TABLE_DIRECT8 ? "DIRECT8" : "HASH"),
+             pipe && db->d_dense_rows ? "ROW24," : "", db->info.rows_bytes < ROWS_FIT32_LIMIT ? "ITEM32" : "ITEM64", g.G == 64 ? RK_RING64 : RK_RING, g.pu, g.lds_per_wave, g.list_cap, g.waves_per_cu,
+             pipe && db->d_dense_rows && db->view.winspec ? "; batches of 32 768 reads or more that the device judges clade-shaped: 16-entry units" : "");
     m->kernel_name = buf;
     return m->kernel_name.c_str();
 }

@@ -369,20 +369,26 @@ __device__ __forceinline__ void apply_entry(u32 *S, u32 nb, u32 br, float sc, fl
 // word x + 1, and `sb` is the word's byte offset as the row entries carry it (0 for padding).
 // MONO (every score of the database is >= the threshold, so every increment is >= 0 and a touched word never drops
 // below Q*T): the first-touch test is one v_max with the -inf marker.
-template <bool MONO = false>
-__device__ __forceinline__ void apply_slot(u32 *S, u32 sb, float sc, float QT, float T) {
-    if (RK_ABLATE & 8) {
-        asm volatile("" ::"v"(sb), "v"(sc));
-        return;
-    }
-    u32 *p = (u32 *)((unsigned char *)S + sb);
-    const u32 old = *p;
+// what S + d starts from: fl(Q*T) on the first touch of the word, else the word
+template <bool MONO>
+__device__ __forceinline__ float touch_base(u32 old, float QT) {
     float base;
     if (MONO) asm("v_max_f32 %0, %1, %2" : "=v"(base) : "v"(old), "v"(QT));  // plain max: no NaNs here, no canonicalize
     else base = (old == S_UNTOUCHED) ? QT : __uint_as_float(old);
-    const float d = sc - T;
-    const float nw = base + d;
-    *p = __float_as_uint(nw);
+    return base;
+}
+// apply_delta: the same update with the increment d = fl(sc - T) given (the dense 24-entry units store it).
+template <bool MONO = false>
+__device__ __forceinline__ void apply_delta(u32 *p, float d, float QT) {
+    if (RK_ABLATE & 8) {
+        asm volatile("" ::"v"(p), "v"(d));
+        return;
+    }
+    *p = __float_as_uint(touch_base<MONO>(*p, QT) + d);
+}
+template <bool MONO = false>
+__device__ __forceinline__ void apply_slot(u32 *S, u32 sb, float sc, float QT, float T) {
+    apply_delta<MONO>((u32 *)((unsigned char *)S + sb), sc - T, QT);
 }
 template <int G, int U, bool WIDE, bool SOA = false>
 __device__ __forceinline__ void accumulate_list(u32 *S, u32 nb, const u64 *list, int cnt, u32 li,
@@ -501,11 +507,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_resource(const DbView &db
     return __builtin_amdgcn_make_buffer_rsrc((void *)db.rows, (short)0, (int)(u32)db.rows_bytes, 0x00020000);
 }
 
-template <int G, int U, bool MONO, bool WIN = false>
+// D24: the units are the dense 24-entry units of rk_device.h (G == 16): the same load, then lanes 0..7 take the slot word of
+// lane li + 8 (one DPP row_ror:8) and apply two entries, lanes 8..15 one.  The 24 slots of a unit belong to one row, so they are
+// distinct and the two read-modify-writes of a step never meet (except on the scratch word); steps stay in list order.
+template <int G, int U, bool MONO, bool WIN = false, bool D24 = false>
 __device__ __forceinline__ void accumulate_units(u32 *S, const u32 *items, int wcnt, u32 li,
                                                  __amdgpu_buffer_rsrc_t rs, float QT, float T, u32 wlo4p4 = 4u, u32 w4 = 0xFFFFFFFFu) {
+    static_assert(!D24 || (G == 16 && !WIN), "dense units: 16-lane groups, whole trees");
     const u32 li8 = li * 8;
     const u32 my_unit = li >> 4;  // which 128-byte unit of the chunk this lane reads
+    const bool two = li < 8;                 // D24: the lanes that also apply entry 16 + li
+    const u32 sh_a = two ? 0u : SLOT24_BITS;  // D24: where this lane's first slot sits in the slot word
     u32 sb[U], it[U];
     float sc[U];
     auto issue = [&](u32 item, u32 &b, float &v) {
@@ -521,6 +533,26 @@ __device__ __forceinline__ void accumulate_units(u32 *S, const u32 *items, int w
         const u32 t = b - wlo4p4;
         return (t < w4) ? t + 4u : 0u;
     };
+    auto apply = [&](u32 b, float v) {
+        if (!D24) {
+            apply_slot<MONO>(S, slot_of(b), v, QT, T);
+            return;
+        }
+        // b = w[2li] (d of entry li), v = w[2li + 1] (lanes 0..7: d of entry 16 + li; lanes 8..15: the slot word)
+        // Both words are read before either is written (one LDS round trip per step, as with 16-entry units): the two slots of a
+        // lane, and those of different lanes, differ unless both are the scratch word.  Lanes 8..15 send their second update there.
+        const u32 w = __float_as_uint(v);
+        const u32 r = (u32)__builtin_amdgcn_update_dpp(0, (int)w, 0x128, 0xF, 0xF, false);  // row_ror:8: lane li + 8's word
+        u32 *pa = S + (((two ? r : w) >> sh_a) & SLOT24_MAX);
+        u32 *pb = S + (two ? (r >> (2 * SLOT24_BITS)) & SLOT24_MAX : 0u);
+        if (RK_ABLATE & 8) {
+            asm volatile("" ::"v"(pa), "v"(pb), "v"(b), "v"(v));
+            return;
+        }
+        const u32 oa = *pa, ob = *pb;
+        *pa = __float_as_uint(touch_base<MONO>(oa, QT) + __uint_as_float(b));
+        *pb = __float_as_uint(touch_base<MONO>(ob, QT) + v);
+    };
 #pragma unroll
     for (int u = 0; u < U; u++) issue(items[u], sb[u], sc[u]);
 #pragma unroll
@@ -529,7 +561,7 @@ __device__ __forceinline__ void accumulate_units(u32 *S, const u32 *items, int w
     while (true) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            apply_slot<MONO>(S, slot_of(sb[u]), sc[u], QT, T);
+            apply(sb[u], sc[u]);
             issue(it[u], sb[u], sc[u]);
             it[u] = items[s0 + 2 * U + u];
         }
@@ -1301,10 +1333,14 @@ __device__ __forceinline__ void record_codes(u32 recw, u32 pos, u32 li, u32 k, u
     }
 }
 
-template <int BITS, int TM, int U, int PU>
+// D24: a.db is the image's dense view (rk_device.h: 24-entry units, its own compact table); everything but the accumulate step and
+// the wide-row fallback is the same.
+template <int BITS, int TM, int U, int PU, bool D24 = false>
 __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
     constexpr int G = 16, NG = 4;
     static_assert(TM != TM_HASH, "direct tables only");
+    static_assert(!D24 || TM == TM_COMPACT, "the dense view carries a compact table");
+    if (!batch_is_mine(a)) return;  // (launched beside the other layout's kernel: the pre-pass gave the batch to that one)
     extern __shared__ u32 lds[];
     const bool perm_given = tile_order_given(a);
     const u32 lane = threadIdx.x & 63;
@@ -1405,8 +1441,8 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             wcnt = max(wcnt, __builtin_amdgcn_readlane(cnt, 48));
             for (int i = cnt + (int)li; i < wcnt + 2 * U; i += G) items[i] = ITEM_FILLER;
             wave_lds_fence();
-            if (a.db.mono) accumulate_units<G, U, true>(S, items, wcnt, li, rows_rs, QT, T);
-            else accumulate_units<G, U, false>(S, items, wcnt, li, rows_rs, QT, T);
+            if (a.db.mono) accumulate_units<G, U, true, false, D24>(S, items, wcnt, li, rows_rs, QT, T);
+            else accumulate_units<G, U, false, false, D24>(S, items, wcnt, li, rows_rs, QT, T);
             wave_lds_fence();
             cnt = 0;
         };
@@ -1458,7 +1494,25 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
                 }
             }
             if (__any(more && cnt + total > cap_items)) flush();
-            if (__any(more && total > cap_items)) {
+            if (D24 && __any(more && total > cap_items)) {
+                // the batch's units do not fit an empty list: they go through it in parts, still in k-mer order (a part may
+                // end inside a row); unit c of position u is unit excl[u] + c of the batch
+                for (u32 done = 0; __any(done < (u32)total);) {
+                    const u32 room = (u32)(cap_items - cnt);
+#pragma unroll
+                    for (int u = 0; u < PU; u++) {
+                        const u32 rb = (u32)(desc[u] >> DESC_LEN_BITS) * 8u;
+                        for (u32 c = 0; __any(c < nch[u]); c++) {
+                            const u32 x = excl[u] + c - done;  // (wraps for units before the part: then >= room)
+                            if (c < nch[u] && x < room) items[cnt + (int)x] = rb + c * 128u;
+                        }
+                    }
+                    const u32 take = min((u32)total - done, room);
+                    cnt += (int)take;
+                    done += take;
+                    if (__any(done < (u32)total)) flush();
+                }
+            } else if (__any(more && total > cap_items)) {
                 const int per_part = cap_rows / G;
                 for (int u_lo = 0; u_lo < PU; u_lo += per_part) {
                     int rc = 0;
