@@ -94,6 +94,8 @@ struct PlaceArgs {
     u32 only_if;             // first kernels launched side by side: 0 = run; else the classes of batches this launch is for, as the pre-pass judged the
                              // batch on the device -- bit 0: uniform reads (*keep_order != 0) whose sampled k-mers have a row more often than a random
                              // read's, bit 1: uniform reads that hit no more often than that (keep_order[3] != 0), bit 2: reads of a clade (re-tiled)
+    u32 marked_if;           // with only_marked and the pre-pass's verdicts: the classes of batches (bits as only_if; 0 = all three) whose tiles a first
+                             // kernel was launched for -- place_packed16w_kernel takes only their marked tiles, and every tile of a batch of another class
     unsigned char *tile_marks;  // [ceil(n_reads / 4)] scratch of the launch (zeroed before the first kernel): tile t -- the reads at slots 4t .. 4t+3 of the
                                 // batch's order -- is left to place_packed16w_kernel by the kernel launched ahead of it (never the caller's flag array:
                                 // d_flags_in may be the same buffer as the output flags)

@@ -4,6 +4,7 @@
 #include "rk_kernels.hip"
 #include "rk_internal.h"
 #include "rk_pack_host.h"
+#include "rk_plan.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -457,13 +458,7 @@ struct WindowPlan {
 #ifndef RK_WSTREAM_MIN_BRANCHES
 #define RK_WSTREAM_MIN_BRANCHES 4500u
 #endif
-// Row units a 150-symbol read brings (its ~150 k-mers x the row units per k-mer CODE of the image) beyond which the sorted list of
-// place_packed16s_kernel stops fitting and place_packed16w_kernel alone is ahead: scripts/long_rows_big_tree.py, 9 001 branches,
-// a quarter of the 9-mers present, rows of 70 / 150 / 300 entries (~170 / 350 / 680 units a read): 73 / 35 / 15 Mreads/s with the
-// second kernel first, 77 / 46 / 21 without (profiles/r03_long_rows_big_tree.txt)
-#ifndef RK_WSTREAM_MAX_UNITS
-#define RK_WSTREAM_MAX_UNITS 220.0
-#endif
+// (RK_WSTREAM_MAX_UNITS: rk_plan.h)
 static bool wstream_tree(uint32_t nb, uint32_t bits, double units_per_code, double units_per_row) {  // images whose tiles go to place_packed16s_kernel first
     if (rk_knob("RK_WSTREAM_ALWAYS")) return true;  // developer / test knob: the sorted-stream kernel on every windowed tree
     if (150.0 * units_per_code > RK_WSTREAM_MAX_UNITS) return false;
@@ -1616,155 +1611,59 @@ struct TileOrder {
     }
 };
 
-// place_hash64_kernel's geometry: NS = 2 048 slots (16 KB) + a word per lane + a list of 320 items = 17 920 B per wave, nine waves per CU
-#ifndef RK_HASH_LOGS
-#define RK_HASH_LOGS 11
-#endif
-constexpr uint32_t RK_HASH_LOG_SLOTS = RK_HASH_LOGS, RK_HASH_MAIN_CAP = 320;
-#ifndef RK_HASH_KEY_SLACK
-#define RK_HASH_KEY_SLACK 48u  // slots kept free: a read's table takes NS - this many keys (the kernel counts a step's entries before it takes the step)
-#endif
-// From this many branches on place_hash64_kernel is ahead of place_packed16s_kernel, whose cost grows with the windows a tree is cut
-// into (profiles/r04_hash_crossover.txt and DESIGN.md 4.1d; C2-like rows, Mreads/s hash / sorted-stream: uniform reads 19 999 branches
-// 94 / 108, 28 001: 95 / 95, 39 999: 95 / 71, 65 535: 94 / 35; clade-shaped reads 82 / 119 at 28 001, 81 / 95 at 39 999, 82 / 47 at
-// 65 535; 92 / 81 at 50 001, 84 / 81 at 55 001, 48 / 81 at 60 001).  Uniform reads cross at ~28 000 branches, clade-shaped ones at ~56 000: in between BOTH kernels are launched and the
-// batch's shape -- what the re-tiling pre-pass found, on the device -- says which of them runs (PlaceArgs::only_if); a batch without
-// the pre-pass (fewer than 32 768 reads) goes by the single rule in the middle.
-#ifndef RK_HASH_MIN_BRANCHES_CLADE
-#define RK_HASH_MIN_BRANCHES_CLADE 56000u
-#endif
-// amino acids (k = 5, 100 residues, C4-like rows: a quarter of the k-mers present, ~300 entries a read): the hash kernel runs 196 Mreads/s
-// at any size, place_packed16s_kernel 231 / 205 / 177 / 119 / 51 at 9 001 / 12 001 / 15 999 / 33 001 / 65 535 branches -- they cross at
-// ~13 500; reads cut from the sequence the k-mers come from 107 against 198 / 168 / 136 / 65 at 9 001 / 25 001 / 46 001 / 60 001: ~56 000
-// as for DNA (profiles/r04_hash_crossover_aa.txt).
-// The hash kernel's cost follows a read's row units, place_packed16s_kernel's the units AND the windows: through the two measured
-// crossings -- 145 units a read (C2, 150 bp) at 28 000 branches, 33 (C4-like, 100 residues) at 13 500 -- the uniform crossing is taken as
-// 130 branches per unit + 9 250 for other row densities and read lengths; batches too small for the pre-pass go by that + 8 000
-// (36 000 for C2-like rows).  -DRK_HASH_MIN_BRANCHES_UNIFORM_FIXED=n replaces the fit by a constant.
-// Reads that bring few row entries even when every k-mer of theirs has a row take the table of 1 024 slots (hash_small_table): sixteen waves
-// per CU, half the reset and the scan.  Forced onto the protein sweep above (RK_HASH_SMALL_TABLE; its reads hit a quarter of their k-mers, a real
-// read would overflow that table) it gives 310 Mreads/s on uniform reads and 170 on clade-shaped ones at every size, and the crossings move to ~2 600 branches
-// (place_packed16s_kernel: 329 / 297 at 2 001 / 3 100) and ~24 000 (181 / 168 / 151 at 15 999 / 25 001 / 33 001).  One measured crossing only in
-// this regime: 19 branches per unit + 2 000 (a tree of four windows: the table's reset and scan do not shrink with the read) passes through it.
-// (clade-shaped batches through the 1 024-slot table with the large one behind it: DNA 96 - 100 Mreads/s at any size against place_packed16s_kernel's
-//  128 / 106 / 95 / 92 / 84 / 48 at 19 999 / 33 001 / 46 001 / 50 001 / 55 001 / 60 001 branches -- they cross at ~42 000; amino acids 170 against
-//  181 / 168 / 151 at 15 999 / 25 001 / 33 001: ~24 000.  Through both: 160 branches per row unit of a read + 18 700)
-static uint32_t hash_min_clade_small(double est_units) {
-#ifdef RK_HASH_MIN_BRANCHES_CLADE_SMALL
-    (void)est_units;
-    return RK_HASH_MIN_BRANCHES_CLADE_SMALL;
-#else
-    const double nb = 160.0 * est_units + 18700.0;
-    return nb > 65535.0 ? 65535u : (uint32_t)nb;
-#endif
+// place_hash64_kernel's geometry (rk_plan.h: RK_HASH_LOG_SLOTS, RK_HASH_KEY_SLACK): a list of 320 items a lane
+constexpr uint32_t RK_HASH_MAIN_CAP = 320;
+using rk_plan::F_NONE;
+using rk_plan::F_SORTED;
+using rk_plan::F_HASH_BIG;
+using rk_plan::F_HASH_SMALL;
+static rk_plan::Knobs plan_knobs() {  // (developer knobs: the product library reads none)
+    rk_plan::Knobs kn;
+    kn.hash_always = rk_knob("RK_HASH_ALWAYS") != nullptr;
+    kn.hash_big_table = rk_knob("RK_HASH_BIG_TABLE") != nullptr;
+    kn.hash_small_table = rk_knob("RK_HASH_SMALL_TABLE") != nullptr;
+    kn.hash_clade_small = rk_knob("RK_HASH_CLADE_SMALL") != nullptr;
+    kn.wstream_always = rk_knob("RK_WSTREAM_ALWAYS") != nullptr;
+    kn.no_wstream = rk_knob("RK_NO_WSTREAM") != nullptr;
+    if (const char *e = rk_knob("RK_HASH_KEY_SLACK")) kn.key_slack = (uint32_t)atoi(e);
+    return kn;
 }
-static uint32_t hash_min_clade(bool small_table) { return small_table ? 24000u : RK_HASH_MIN_BRANCHES_CLADE; }
-static uint32_t hash_min_uniform(double est_units, bool small_table) {
-#ifdef RK_HASH_MIN_BRANCHES_UNIFORM_FIXED
-    (void)est_units;
-    return RK_HASH_MIN_BRANCHES_UNIFORM_FIXED;
-#else
-    const double nb = small_table ? 19.0 * est_units + 2000.0 : 130.0 * est_units + 9250.0;
-    return nb > (double)hash_min_clade(small_table) ? hash_min_clade(small_table) : (uint32_t)nb;
-#endif
-}
-static uint32_t hash_min_single(double est_units, bool small_table) {
-    const uint32_t u = hash_min_uniform(est_units, small_table) + 8000u;
-    return u > hash_min_clade(small_table) ? hash_min_clade(small_table) : u;
-}
+static uint32_t hash_key_limit(uint32_t log_slots = RK_HASH_LOG_SLOTS) { return rk_plan::hash_key_limit(plan_knobs(), log_slots); }
 static bool hash_capable(const rk_db *db) {  // images whose tiles can go to place_hash64_kernel first
     if (rk_knob("RK_NO_HASH") || rk_knob("RK_NO_WSTREAM") || db->info.rows_bytes >= ROWS_FIT32_LIMIT) return false;
     return rk_knob("RK_HASH_ALWAYS") || db->wp.stream;
 }
-static bool hash_tree(const rk_db *db, double est_units, bool small_table) {  // ... by the single rule
-    if (!hash_capable(db)) return false;
-    return rk_knob("RK_HASH_ALWAYS") || db->info.n_branches > hash_min_single(est_units, small_table);
-}
-static uint32_t hash_key_limit(uint32_t log_slots);
-// The table of 1 024 slots: est_units < 0 asks "in no case"; otherwise est_units holds the row ENTRIES of a read all of whose k-mers have a
-// row (mean row length x its k-mers) -- what a read from an organism of the reference brings, four times the uniform estimate of C4-like
-// rows -- and the small table is taken only when even that fits: a read that overflows costs a tile of place_packed16w_kernel.
-static bool hash_small_table(double full_hit_entries) {
-    if (rk_knob("RK_HASH_BIG_TABLE") || full_hit_entries < 0.0) return false;  // (developer knob: A/B)
-    return rk_knob("RK_HASH_SMALL_TABLE") != nullptr || full_hit_entries <= 0.8 * hash_key_limit(RK_HASH_LOG_SLOTS - 1);
-}
-static double full_hit_entries(const rk_db *db, uint32_t symbols) {
-    const double kmers = symbols > db->info.k ? (double)(symbols - db->info.k + 1) : 0.0;
-    return db->info.n_keys ? kmers * (double)db->info.n_entries / (double)db->info.n_keys : 0.0;
-}
-static uint32_t hash_key_limit(uint32_t log_slots = RK_HASH_LOG_SLOTS) {
-    uint32_t slack = RK_HASH_KEY_SLACK;
-    if (const char *e = rk_knob("RK_HASH_KEY_SLACK")) slack = (uint32_t)atoi(e);  // developer knob
-    const uint32_t ns = 1u << log_slots;
-    if (slack < 16u) slack = 16u;
-    if (slack > ns - 64u) slack = ns - 64u;
-    return ns - slack;
-}
-
-// ---- which kernel goes first on a windowed tree with short rows, per class of batch ----
-enum First { F_NONE, F_SORTED, F_HASH_BIG, F_HASH_SMALL };
-struct FirstPlan { First for_uniform, for_sparse, for_clade; };
-static FirstPlan first_kernel_plan(const rk_db *db, double est_units, bool hash_small, bool hash_fits, bool sorted_fits, bool verdict) {
-    const uint32_t nb_tree = db->info.n_branches;
-    const bool forced = rk_knob("RK_HASH_ALWAYS") != nullptr;
-    const First table_u = hash_small ? F_HASH_SMALL : F_HASH_BIG;
-    FirstPlan p;
-    if (forced && hash_fits) {
-        p.for_uniform = p.for_sparse = p.for_clade = table_u;
-        return p;
-    }
-    const uint32_t min_u = verdict ? hash_min_uniform(est_units, hash_small) : hash_min_single(est_units, hash_small);
-    p.for_uniform = hash_fits && nb_tree > min_u ? table_u : sorted_fits ? F_SORTED : hash_fits && hash_tree(db, est_units, hash_small) ? table_u : F_NONE;
-    p.for_clade = p.for_sparse = p.for_uniform;
-    if (verdict) {
-        // reads of a clade touch a third of the branches uniform reads do (profiles/r04_lsize_hist.txt: ~500 against ~1 300; max 1 135): their
-        // tables fit the 1 024-slot instantiation -- sixteen waves per CU -- and the few that do not are placed by the large one, launched
-        // behind it on the tiles it hands over
-        const bool clade_small = hash_fits && !hash_small && (rk_knob("RK_HASH_CLADE_SMALL") || nb_tree > hash_min_clade_small(est_units)) && !rk_knob("RK_HASH_BIG_TABLE");
-        p.for_clade = clade_small ? F_HASH_SMALL : hash_fits && nb_tree > hash_min_clade(hash_small) ? table_u : sorted_fits ? F_SORTED : p.for_uniform;
-        // uniform batches whose k-mers hit no more often than a random read's (the pre-pass's second verdict): the uniform estimate of a read's
-        // entries holds, and where that fits the 1 024-slot table the small instantiation serves them (the large one behind it, as for clades)
-        if (hash_fits && !hash_small && !rk_knob("RK_HASH_BIG_TABLE") && est_units * 9.3 <= 0.6 * hash_key_limit(RK_HASH_LOG_SLOTS - 1) && nb_tree > hash_min_uniform(est_units, true))
-            p.for_sparse = F_HASH_SMALL;
-    }
-    return p;
+// the plan's inputs for reads of this shape on this image (the launch's own: verdict, first_ok, marked_list, left false)
+static rk_plan::In plan_in(const rk_db *db, const rk_plan::ReadShape &rs, uint32_t words_per_read) {
+    rk_plan::In in;
+    in.n_branches = db->info.n_branches;
+    in.est_units = rs.est_units;
+    in.full_hit_entries = rk_plan::full_hit_entries(rs.max_syms, db->info.k, db->info.n_keys, db->info.n_entries);
+    in.hash_capable = hash_capable(db);
+    in.words_per_read = words_per_read;
+    in.one_batch = rs.one_batch;
+    in.stream = db->wp.stream;
+    in.knobs = plan_knobs();
+    return in;
 }
 
 static int launch_windowed(const rk_db *db, PlaceArgs a, hipStream_t stream) {
     WindowPlan wp = db->wp;
     const uint64_t n_tiles = (a.n_reads + 3) / 4;
     if (!n_tiles) return RK_OK;
-    static const bool no_stream = rk_knob("RK_NO_WSTREAM") != nullptr;  // developer knob: place_packed16w_kernel alone (A/B)
-    // (the reads of this batch may be longer than the 150 symbols the image was judged for: their k-mers x the image's row units per code)
-    const uint32_t max_syms = a.lens ? a.words_per_read * 32 / db->info.bits_per_symbol : a.fixed_len;
-    const double est_units = (max_syms > db->info.k ? max_syms - db->info.k + 1 : 0) * wp.units_per_code;
-    // (reads of one known length whose k-mers do not fit its single probe batch would all be handed over: not launched for those)
-    const uint32_t probe_cap = (db->info.bits_per_symbol == 5 ? 7u : 9u) * 16u;
-    const bool one_batch = a.lens != nullptr || a.fixed_len < db->info.k || a.fixed_len - db->info.k + 1 <= probe_cap;
-    // place_hash64_kernel first: images of short rows (the rule place_packed16s_kernel had), reads whose distinct branches -- at most
-    // their entries, ~9.3 a unit with C2-like rows -- fit the table (profiles/r04_lsize_hist.txt)
-    const bool hash_fits = !no_stream && hash_capable(db) && (est_units * 9.3 <= 0.8 * hash_key_limit() || rk_knob("RK_HASH_ALWAYS"));
-    // reads of few row units (a protein database: ~300 entries a read): a table of 1 024 slots -- half the reset and the scan, 9.7 KB a
-    // wave, sixteen waves per CU instead of nine
-    const bool hash_small = hash_small_table(full_hit_entries(db, max_syms));
-    const bool sorted_fits = a.words_per_read <= 16 && !no_stream && wp.stream && one_batch && (est_units <= 1.25 * RK_WSTREAM_MAX_UNITS || rk_knob("RK_WSTREAM_ALWAYS"));
+    // (the reads of this batch may be longer than the 150 symbols the image was judged for: rk_plan::read_shape)
+    const rk_plan::ReadShape rs = rk_plan::read_shape(db->info.bits_per_symbol, db->info.k, a.words_per_read, a.lens != nullptr, a.fixed_len, wp.units_per_code);
+    rk_plan::In in = plan_in(db, rs, a.words_per_read);
     TileOrder order;
-    if (int rc = order.prepare(db, a, stream, hash_fits || sorted_fits)) return rc;
-    const bool first_ok = a.tile_marks != nullptr;  // (no scratch to be had for the marks: place_packed16w_kernel alone)
-    // Which kernel goes first for each class of batch (first_kernel_plan); when the batch went through the re-tiling pre-pass (a.perm) its
+    if (int rc = order.prepare(db, a, stream, rk_plan::plan_fit(in).want_marks())) return rc;
+    in.first_ok = a.tile_marks != nullptr;  // (no scratch to be had for the marks: place_packed16w_kernel alone)
+    in.marked_list = a.marked_list != nullptr;
+    // Which kernel goes first for each class of batch (rk_plan.h); when the batch went through the re-tiling pre-pass (a.perm) its
     // verdicts are on the device: the kernels that differ between the classes are launched side by side and return at once when the batch
-    // is not theirs (PlaceArgs::only_if).  Without the verdicts (small batches) one rule serves all.
-    const bool verdict = a.perm != nullptr;
-    const FirstPlan plan = first_kernel_plan(db, est_units, hash_small, hash_fits, sorted_fits, verdict);
-    const First for_uniform = plan.for_uniform, for_sparse = plan.for_sparse, for_clade = plan.for_clade;
-    // every distinct kernel once, with the classes of batches it serves (PlaceArgs::only_if: bit 0 uniform reads that hit often, bit 1
-    // uniform reads that hit like random ones, bit 2 reads of a clade; all three = unconditional)
-    const First by_class[3] = {for_uniform, for_sparse, for_clade};
-    auto class_mask = [&](First f) -> uint32_t {
-        uint32_t m = 0;
-        for (int c = 0; c < 3; c++) m |= by_class[c] == f ? 1u << c : 0u;
-        return m;
-    };
+    // is not theirs (PlaceArgs::only_if), and place_packed16w_kernel takes every tile of a batch whose class has no first kernel
+    // (PlaceArgs::marked_if).  Without the verdicts (small batches) one rule serves all.
+    in.verdict = a.perm != nullptr;
+    const rk_plan::Plan plan = rk_plan::launch_plan(in);
     auto launch_hash = [&](uint32_t log_slots, uint32_t only_if, uint32_t only_marked) -> int {
         PlaceArgs b = a;
         b.only_if = only_if;
@@ -1796,30 +1695,20 @@ static int launch_windowed(const rk_db *db, PlaceArgs a, hipStream_t stream) {
         HIP_TRY(hipGetLastError());
         return RK_OK;
     };
-    bool any_first = false, small_on_trust = false;
-    if (first_ok) {
-        for (First f : {F_HASH_SMALL, F_HASH_BIG}) {
-            const uint32_t m = class_mask(f);
-            if (!m) continue;
-            if (int rc = launch_hash(f == F_HASH_SMALL ? RK_HASH_LOG_SLOTS - 1 : RK_HASH_LOG_SLOTS, m == 7u ? 0u : m, 0u)) return rc;
-            any_first = true;
-            small_on_trust = small_on_trust || (f == F_HASH_SMALL && !hash_small);
-        }
-        if (small_on_trust && a.marked_list) {  // the tiles the small table handed over: the large one next, then place_packed16w_kernel for what is left
-            if (int rc = compact_marks()) return rc;
-            const uint32_t m = class_mask(F_HASH_SMALL);  // (only for the batches the small table took)
-            if (int rc = launch_hash(RK_HASH_LOG_SLOTS, m == 7u ? 0u : m, 1u)) return rc;
-        }
+    if (plan.hash_small.run)
+        if (int rc = launch_hash(RK_HASH_LOG_SLOTS - 1, plan.hash_small.only_if, 0u)) return rc;
+    if (plan.hash_big.run)
+        if (int rc = launch_hash(RK_HASH_LOG_SLOTS, plan.hash_big.only_if, 0u)) return rc;
+    if (plan.hash_behind.run) {  // the tiles the small table handed over: the large one next, then place_packed16w_kernel for what is left
+        if (int rc = compact_marks()) return rc;
+        if (int rc = launch_hash(RK_HASH_LOG_SLOTS, plan.hash_behind.only_if, 1u)) return rc;
     }
-    const bool sorted_first = first_ok && class_mask(F_SORTED) != 0u;
-    const uint32_t sorted_only_if = class_mask(F_SORTED) == 7u ? 0u : class_mask(F_SORTED);
-    const bool hash_first = any_first;
-    if (sorted_first) {
+    if (plan.sorted.run) {
         // ---- place_packed16s_kernel: the sorted list of a tile's four reads + their touched bitmaps.  Seven waves per CU on
         //      the largest windows, eight otherwise; the list holds a C2-like read (145 units, 250 at the tail) with the padding of
         //      its window segments ----
         PlaceArgs b = a;
-        b.only_if = sorted_only_if;  // (when another kernel takes batches of the other shape)
+        b.only_if = plan.sorted.only_if;  // (when another kernel takes batches of the other shape)
         const uint32_t work_min = 96u;  // scratch of the second pass: 48 candidate keys
         // ring of row loads: eight deep, a window's segment padded to half turns of it (four deep it left the stream waiting
         // on HBM: ~280 cycles a step; segments padded to whole turns of eight made the largest trees' lists half filler)
@@ -1863,7 +1752,8 @@ static int launch_windowed(const rk_db *db, PlaceArgs a, hipStream_t stream) {
         HIP_TRY(hipGetLastError());
     }
     // ---- place_packed16w_kernel: every tile (records of more than 16 words), or the tiles the first kernel handed over ----
-    a.only_marked = ((hash_first || sorted_first) && first_ok) ? 1u : 0u;
+    a.only_marked = plan.only_marked ? 1u : 0u;
+    a.marked_if = plan.marked_if;
     if (a.only_marked)
         if (int rc = compact_marks()) return rc;
     // 88 words = the 44 keys the exact select of a window needs as scratch for keep_at_most <= 8 (K + 16 candidates + 16 winners); 96 beyond
@@ -2076,13 +1966,14 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
     if (use_windowed(db, 7, 16)) {
         // (for the reads of BASELINE's configs -- 150 bases / 100 residues -- and a batch large enough for the pre-pass's verdicts)
         const uint32_t syms_name = db->info.bits_per_symbol == 5 ? 100u : 150u;
-        const double est_name = (double)(syms_name - db->info.k + 1) * db->wp.units_per_code;
-        const bool hash_fits = hash_capable(db) && (rk_knob("RK_HASH_ALWAYS") || est_name * 9.3 <= 0.8 * hash_key_limit());
-        const bool small_name = hash_small_table(full_hit_entries(db, syms_name));
-        const bool sorted_name = db->wp.stream && !rk_knob("RK_NO_WSTREAM") && (est_name <= 1.25 * RK_WSTREAM_MAX_UNITS || rk_knob("RK_WSTREAM_ALWAYS"));
-        const FirstPlan pl = first_kernel_plan(db, est_name, small_name, hash_fits, sorted_name, true);
-        auto what = [](First f) { return f == F_HASH_SMALL ? "place_hash64_kernel with 1 024 slots (the 2 048-slot one behind it)" : f == F_HASH_BIG ? "place_hash64_kernel" : f == F_SORTED ? "place_packed16s_kernel" : "place_packed16w_kernel"; };
-        const First shown = pl.for_uniform == F_HASH_BIG || pl.for_uniform == F_HASH_SMALL ? pl.for_uniform : (pl.for_sparse == F_HASH_SMALL || pl.for_clade == F_HASH_SMALL || pl.for_clade == F_HASH_BIG) && pl.for_uniform == F_NONE ? pl.for_clade : pl.for_uniform;
+        const uint32_t wpr_name = (syms_name * db->info.bits_per_symbol + 31) / 32;
+        rk_plan::ReadShape rs = rk_plan::read_shape(db->info.bits_per_symbol, db->info.k, wpr_name, false, syms_name, db->wp.units_per_code);
+        rs.one_batch = true;  // (reads of these lengths in records of their own length: the probe batch is the record's)
+        rk_plan::In in = plan_in(db, rs, wpr_name);
+        in.verdict = true;
+        const rk_plan::FirstPlan pl = rk_plan::first_kernel_plan(in, rk_plan::plan_fit(in));
+        auto what = [](rk_plan::First f) { return f == F_HASH_SMALL ? "place_hash64_kernel with 1 024 slots (the 2 048-slot one behind it)" : f == F_HASH_BIG ? "place_hash64_kernel" : f == F_SORTED ? "place_packed16s_kernel" : "place_packed16w_kernel"; };
+        const rk_plan::First shown = pl.for_uniform == F_HASH_BIG || pl.for_uniform == F_HASH_SMALL ? pl.for_uniform : (pl.for_sparse == F_HASH_SMALL || pl.for_clade == F_HASH_SMALL || pl.for_clade == F_HASH_BIG) && pl.for_uniform == F_NONE ? pl.for_clade : pl.for_uniform;
         if (shown == F_HASH_BIG || shown == F_HASH_SMALL) {
             const uint32_t ls = shown == F_HASH_SMALL ? RK_HASH_LOG_SLOTS - 1 : RK_HASH_LOG_SLOTS;
             char other[360] = "";

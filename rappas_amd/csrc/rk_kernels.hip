@@ -88,10 +88,17 @@ __device__ __forceinline__ double shfl_f64(double v, int src, int width) {
 __device__ __forceinline__ bool tile_order_given(const PlaceArgs &a) { return a.perm != nullptr && *a.keep_order == 0u; }  // (once per wave)
 // the verdicts of the pre-pass on the batch (retile_decide_kernel: keep_order[0] = the batch keeps its order, keep_order[3] = its sampled
 // k-mers have a row no more often than a random read's) against what this launch was made for (PlaceArgs::only_if)
+__device__ __forceinline__ u32 batch_class(const PlaceArgs &a) { return a.keep_order[0] == 0u ? 2u : (a.keep_order[3] != 0u ? 1u : 0u); }
 __device__ __forceinline__ bool batch_is_mine(const PlaceArgs &a) {
     if (!a.only_if || !a.perm) return true;
-    const u32 cls = a.keep_order[0] == 0u ? 2u : (a.keep_order[3] != 0u ? 1u : 0u);
-    return ((a.only_if >> cls) & 1u) != 0u;
+    return ((a.only_if >> batch_class(a)) & 1u) != 0u;
+}
+// place_packed16w_kernel behind the first kernels: only the tiles they handed over when one of them was launched for this batch's class
+// (PlaceArgs::marked_if), every tile otherwise (once per wave)
+__device__ __forceinline__ bool takes_only_marked(const PlaceArgs &a) {
+    if (!a.only_marked) return false;
+    if (!a.marked_if || !a.perm) return true;
+    return ((a.marked_if >> batch_class(a)) & 1u) != 0u;
 }
 __device__ __forceinline__ u64 tile_read(const PlaceArgs &a, u64 slot, bool given) { return given ? (u64)a.perm[slot] : slot; }
 // LDS data exchanged between lanes of ONE wave: DS operations of a wave execute in order, so only the
@@ -1840,7 +1847,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
     // Second launch behind place_packed16s_kernel / place_hash64_kernel: only the tiles they handed over.  With a list of them
     // (compact_marks_kernel) the waves take the next tile from one queue -- a handful of tiles of ~0.4 ms each on a 65 535-branch tree,
     // which a fixed tile -> wave assignment left to a few waves; every wave ends when the queue's head passes the list's length.
-    const bool queued = a.only_marked != 0u && a.marked_list != nullptr;
+    const bool only_marked = takes_only_marked(a);
+    const bool queued = only_marked && a.marked_list != nullptr;
     auto take_marked = [&]() -> u64 {
         u32 i = 0;
         if (lane == 0) i = atomicAdd(&a.marked_ctl[1], 1u);
@@ -1852,7 +1860,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
     load_tile(tile, c_recw, c_R, c_fin, c_have);
 
     while (tile < n_tiles) {
-        if (a.only_marked && !queued) {  // (no list: every wave looks at the marks of its own tiles)
+        if (only_marked && !queued) {  // (no list: every wave looks at the marks of its own tiles)
             const u32 mark = a.tile_marks[tile];
             if (!__builtin_amdgcn_readfirstlane((int)mark)) {
                 tile += wave_count;
