@@ -18,6 +18,7 @@
 //     K rounds of group arg-max, LWR in fp64 on the first K lanes; the scan also resets S for the next read.
 // No MFMA: this is a gather/accumulate bounded by the memory system, not a contraction.
 #include "rk_device.h"
+#include "rk_slots24.h"
 
 #include <type_traits>
 #ifndef RK_ROW_NT
@@ -514,17 +515,22 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rows_resource(const DbView &db
     return __builtin_amdgcn_make_buffer_rsrc((void *)db.rows, (short)0, (int)(u32)db.rows_bytes, 0x00020000);
 }
 
-// D24: the units are the dense 24-entry units of rk_device.h (G == 16): the same load, then lanes 0..7 take the slot word of
-// lane li + 8 (one DPP row_ror:8) and apply two entries, lanes 8..15 one.  The 24 slots of a unit belong to one row, so they are
-// distinct and the two read-modify-writes of a step never meet (except on the scratch word); steps stay in list order.
+// D24: the units are the dense 24-entry units of rk_device.h (G == 16): the same load, then a step of rk_slots24.h -- one masked DPP
+// row_ror:8 (lanes 0..7 take the slot word of lane li + 8, lanes 8..15 keep their own) and two ten-bit fields at per-lane offsets --
+// gives every lane two words of S: lanes 0..7 apply entries li and 16 + li, lanes 8..15 entry li and a second update that lands on
+// the scratch word.  The 24 slots of a unit belong to one row, so they are distinct and the two read-modify-writes of a step never
+// meet (except on the scratch word); steps stay in list order.
+// A step is cut in two: PREPARE (wait for the ring entry, DPP, fields, LDS addresses) and COMMIT (both LDS words read, first touch,
+// add, both written -- one LDS round trip, as with 16-entry units).  A wave issues in order, so step n + 1 is prepared between the
+// LDS reads of step n and the wait for them: the unpacking is off the read -> write -> read chain of the score vector.
 template <int G, int U, bool MONO, bool WIN = false, bool D24 = false>
 __device__ __forceinline__ void accumulate_units(u32 *S, const u32 *items, int wcnt, u32 li,
                                                  __amdgpu_buffer_rsrc_t rs, float QT, float T, u32 wlo4p4 = 4u, u32 w4 = 0xFFFFFFFFu) {
     static_assert(!D24 || (G == 16 && !WIN), "dense units: 16-lane groups, whole trees");
+    static_assert(rk_slots24::SLOT_BITS == SLOT24_BITS, "rk_slots24.h unpacks the slot words rk_device.h defines");
     const u32 li8 = li * 8;
     const u32 my_unit = li >> 4;  // which 128-byte unit of the chunk this lane reads
-    const bool two = li < 8;                 // D24: the lanes that also apply entry 16 + li
-    const u32 sh_a = two ? 0u : SLOT24_BITS;  // D24: where this lane's first slot sits in the slot word
+    const rk_slots24::Shifts sh24 = rk_slots24::lane_shifts(li);  // D24: where this lane's two slots sit in the word the DPP leaves it
     u32 sb[U], it[U];
     float sc[U];
     auto issue = [&](u32 item, u32 &b, float &v) {
@@ -540,35 +546,52 @@ __device__ __forceinline__ void accumulate_units(u32 *S, const u32 *items, int w
         const u32 t = b - wlo4p4;
         return (t < w4) ? t + 4u : 0u;
     };
-    auto apply = [&](u32 b, float v) {
-        if (!D24) {
-            apply_slot<MONO>(S, slot_of(b), v, QT, T);
-            return;
-        }
-        // b = w[2li] (d of entry li), v = w[2li + 1] (lanes 0..7: d of entry 16 + li; lanes 8..15: the slot word)
-        // Both words are read before either is written (one LDS round trip per step, as with 16-entry units): the two slots of a
-        // lane, and those of different lanes, differ unless both are the scratch word.  Lanes 8..15 send their second update there.
-        const u32 w = __float_as_uint(v);
-        const u32 r = (u32)__builtin_amdgcn_update_dpp(0, (int)w, 0x128, 0xF, 0xF, false);  // row_ror:8: lane li + 8's word
-        u32 *pa = S + (((two ? r : w) >> sh_a) & SLOT24_MAX);
-        u32 *pb = S + (two ? (r >> (2 * SLOT24_BITS)) & SLOT24_MAX : 0u);
-        if (RK_ABLATE & 8) {
-            asm volatile("" ::"v"(pa), "v"(pb), "v"(b), "v"(v));
-            return;
-        }
-        const u32 oa = *pa, ob = *pb;
-        *pa = __float_as_uint(touch_base<MONO>(oa, QT) + __uint_as_float(b));
-        *pb = __float_as_uint(touch_base<MONO>(ob, QT) + v);
+    // D24, a ring entry is b = w[2li] (d of entry li), v = w[2li + 1] (lanes 0..7: d of entry 16 + li; lanes 8..15: the slot word)
+    auto prepare = [&](float v, u32 *&pa, u32 *&pb) {
+        const int w = (int)__float_as_uint(v);
+        // row_ror:8, bank_mask 0x3 = lanes 0..7 of each row are written, lanes 8..15 keep `old` = their own word: no v_mov 0, no select
+        const u32 r = (u32)__builtin_amdgcn_update_dpp(w, w, 0x128, 0xF, 0x3, false);
+        const rk_slots24::Slots s = rk_slots24::lane_slots(sh24, r);
+        pa = S + s.a;
+        pb = S + s.b;
     };
 #pragma unroll
     for (int u = 0; u < U; u++) issue(items[u], sb[u], sc[u]);
 #pragma unroll
     for (int u = 0; u < U; u++) it[u] = items[U + u];
     int s0 = 0;
+    if (D24) {
+        u32 *pa, *pb;
+        prepare(sc[0], pa, pb);
+        while (true) {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                u32 *na, *nb;
+                if (RK_ABLATE & 8) {  // timing-only: keep the loads and the unpacking alive, skip the LDS update
+                    asm volatile("" ::"v"(pa), "v"(pb), "v"(sb[u]), "v"(sc[u]));
+                    prepare(sc[(u + 1) % U], na, nb);
+                } else {
+                    // Both words are read before either is written: the two slots of a lane, and those of different lanes, differ
+                    // unless both are the scratch word.
+                    const u32 oa = *pa, ob = *pb;
+                    prepare(sc[(u + 1) % U], na, nb);  // the next step's entry (after the last step: a filler's zeros)
+                    *pa = __float_as_uint(touch_base<MONO>(oa, QT) + __uint_as_float(sb[u]));
+                    *pb = __float_as_uint(touch_base<MONO>(ob, QT) + sc[u]);
+                }
+                issue(it[u], sb[u], sc[u]);
+                it[u] = items[s0 + 2 * U + u];
+                pa = na;
+                pb = nb;
+            }
+            s0 += U;
+            if (s0 >= wcnt) break;  // what is left in the ring are fillers
+        }
+        return;
+    }
     while (true) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            apply(sb[u], sc[u]);
+            apply_slot<MONO>(S, slot_of(sb[u]), sc[u], QT, T);
             issue(it[u], sb[u], sc[u]);
             it[u] = items[s0 + 2 * U + u];
         }
