@@ -924,6 +924,192 @@ __device__ __forceinline__ int heads_rounds(const Heads4 &h, int K, u32 li, u32 
     win_key = ((int)li < num) ? (((u64)win_o << 32) | (u64)(0xFFFFu - (win_i - 1u))) : 0ull;
     return num;
 }
+// ---- the fast select of select_topk for 16-lane groups: the scan keeps SCORES only (three VALU a word against eight with the quads
+//      carried along), the rounds name the winning streams, and each winner's slot is found afterwards by reading its one stream
+//      again (S is intact until select_topk resets it).  Kernels that reset or leave S window by window keep Heads4 above. ----
+struct Heads3 {
+    float s0[4], s1[4], dr[4];  // per stream: the two best scores (s0 >= s1) and the best dropped one
+};
+__device__ __forceinline__ void heads3_clear(Heads3 &h) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) h.s0[c] = h.s1[c] = h.dr[c] = -INFINITY;
+}
+__device__ __forceinline__ float max_as_is(float a, float b) {  // one v_max_f32: fmaxf, and fmed3f(a, b, +inf) which the optimiser turns into it, put a canonicalising v_max v, v, v in front of each operand
+    float r;
+    asm("v_max_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+template <int C>
+__device__ __forceinline__ void heads3_feed(Heads3 &h, float v) {  // v_med3_f32, v_med3_f32, v_max_f32
+    h.dr[C] = __builtin_amdgcn_fmed3f(v, h.s1[C], h.dr[C]);
+    h.s1[C] = __builtin_amdgcn_fmed3f(v, h.s0[C], h.s1[C]);
+    h.s0[C] = max_as_is(v, h.s0[C]);
+}
+__device__ __forceinline__ void heads3_feed_quad(Heads3 &h, const uint4 v4) {
+    heads3_feed<0>(h, __uint_as_float(v4.x));
+    heads3_feed<1>(h, __uint_as_float(v4.y));
+    heads3_feed<2>(h, __uint_as_float(v4.z));
+    heads3_feed<3>(h, __uint_as_float(v4.w));
+}
+// the order of heads_scan: 16-byte reads with the next quad in flight, the partial last quad masked
+template <int G>
+__device__ __forceinline__ void heads3_scan(const u32 *S, u32 ns, u32 li, Heads3 &h) {
+    const uint4 *S4 = (const uint4 *)S;
+    const u32 n4_full = ns / 4;
+    if (li < n4_full) {
+        uint4 a = S4[li];
+        u32 q = li + G;
+        for (; q + G < n4_full; q += 2 * G) {  // two quads a turn, each fed while the next is on its way: no test around a read, no copy of a quad
+            const uint4 b = S4[q];
+            heads3_feed_quad(h, a);
+            a = S4[q + G];
+            heads3_feed_quad(h, b);
+        }
+        if (q < n4_full) {
+            const uint4 b = S4[q];
+            heads3_feed_quad(h, a);
+            a = b;
+        }
+        heads3_feed_quad(h, a);
+    }
+    if ((ns & 3u) && (n4_full % G) == li) {
+        uint4 v4 = S4[n4_full];
+        const u32 i = 4 * n4_full;
+        if (i >= ns) v4.x = S_UNTOUCHED;
+        if (i + 1 >= ns) v4.y = S_UNTOUCHED;
+        if (i + 2 >= ns) v4.z = S_UNTOUCHED;
+        if (i + 3 >= ns) v4.w = S_UNTOUCHED;
+        heads3_feed_quad(h, v4);
+    }
+}
+template <int S>
+__device__ __forceinline__ u32 row_shr32(u32 v) {  // value of lane li - S of the row, 0 for the first S lanes
+    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + S, 0xF, 0xF, true);  // row_shr:S
+}
+// K rounds over the 4 * G heads, on scores and stream tags.  A head's tag is its stream id 4 * li + c, plus one, plus HEADS3_SECOND once
+// the stream has been popped: among equal heads the largest tag is popped, so the second pop of a stream whose two best are equal
+// follows its first at once.  Lane r gets rank r's ordered score and tag.  doubt: a dropped score that could belong to the answer
+// (as heads_rounds_raw) or a head left behind that equals the K-th winner -- which of the equal ones belong is a matter of branch
+// ids nobody has looked up.  Without doubt every entry >= the K-th winner is a winner, and the order among equal scores is all
+// that is left open.
+constexpr u32 HEADS3_SECOND = 128u;
+template <int G>
+__device__ __forceinline__ int heads3_rounds(const Heads3 &h, int K, u32 li, u32 gi, u32 &win_o, u32 &win_t, bool &doubt) {
+    static_assert(4 * G < (int)HEADS3_SECOND, "stream tags");
+    constexpr u32 ORD_NEG_INF = 0x007FFFFFu;  // ord_f32(-inf)
+    u32 o0[4], o1[4], t0[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        o0[c] = ord_f32(h.s0[c]); o1[c] = ord_f32(h.s1[c]);
+        t0[c] = 4u * li + (u32)c + 1u;
+    }
+    u32 last = ORD_NEG_INF;
+    int num = 0;
+    win_o = 0; win_t = 0;
+    for (int r = 0; r < K; r++) {
+        const u32 m = group_max_u32<G>(max(max(o0[0], o0[1]), max(o0[2], o0[3])));
+        const bool valid = m != ORD_NEG_INF;  // group-uniform: something is left
+        u32 cand = 0;
+#pragma unroll
+        for (int c = 0; c < 4; c++) cand = max(cand, (o0[c] == m) ? t0[c] : 0u);
+        const u32 w = group_max_u32<G>(valid ? cand : 0u);  // one holder among equals
+        const bool mine = (int)li == r && valid;
+        win_o = mine ? m : win_o;
+        win_t = mine ? w : win_t;
+        num += valid ? 1 : 0;
+        last = valid ? m : last;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            const bool pop = valid && t0[c] == w;  // exactly one stream of one lane (tags are unique)
+            o0[c] = pop ? o1[c] : o0[c];
+            o1[c] = pop ? ORD_NEG_INF : o1[c];
+            t0[c] = pop ? (t0[c] | HEADS3_SECOND) : t0[c];
+        }
+    }
+    u32 od = max(max(ord_f32(h.dr[0]), ord_f32(h.dr[1])), max(ord_f32(h.dr[2]), ord_f32(h.dr[3])));
+    od = max(od, max(max(o0[0], o0[1]), max(o0[2], o0[3])));  // heads left behind (none while fewer than K were found)
+    const bool d = (num == K) ? (od >= last) : (od != ORD_NEG_INF);
+    doubt = group_bits<G>(__ballot(d), gi) != 0;  // group-uniform
+    return num;
+}
+// The slot of a winner: the smallest index of stream `stream` (words S[stream + 4 * G * i]) whose bits are `bits`, or the second
+// smallest (`second`: the stream's two best are equal and this is the later pop).  The words are read from the top, eight at a time;
+// a match moves the one found before to second place.  Only the top eight can reach beyond the stream's end (there the read is
+// turned to the scratch word S[0], UNTOUCHED, which equals no winner).  Returns 0 when there is no such word.
+template <int G>
+__device__ __forceinline__ u32 heads3_locate(const u32 *S, u32 ns, u32 stream, u32 bits, bool second) {
+    constexpr u32 NONE = 0x40000000u;
+    constexpr int CH = 8;
+    const u32 n4 = (ns + 3) / 4;
+    const int trip = (int)((n4 + G - 1) / G);                           // words of the longest stream (uniform)
+    const int cnt = (int)((ns - stream + 4u * G - 1u) / (4u * G));      // words of this one (stream < ns)
+    int k = (trip - 1) / CH;
+    const u32 *p = S + stream + (u32)(4 * G * CH) * (u32)k;
+    u32 first = NONE, sec = NONE;
+    {
+        const int jv = cnt - CH * k;
+        u32 w[CH];
+#pragma unroll
+        for (int j = 0; j < CH; j++) {
+            const u32 *pj = (j < jv) ? p + 4 * G * j : S;
+            w[j] = *pj;
+        }
+#pragma unroll
+        for (int j = CH - 1; j >= 0; j--) {
+            const bool eq = w[j] == bits;
+            sec = eq ? first : sec;
+            first = eq ? (u32)j : first;
+        }
+    }
+    for (k--; k >= 0; k--) {
+        p -= 4 * G * CH;
+        first += (u32)CH; sec += (u32)CH;  // (indices count from the chunk at hand)
+        u32 w[CH];
+#pragma unroll
+        for (int j = 0; j < CH; j++) w[j] = p[4 * G * j];
+#pragma unroll
+        for (int j = CH - 1; j >= 0; j--) {
+            const bool eq = w[j] == bits;
+            sec = eq ? first : sec;
+            first = eq ? (u32)j : first;
+        }
+    }
+    const u32 i = second ? sec : first;
+    return i < NONE ? stream + 4u * G * i : 0u;
+}
+// scan, rounds and locate for one read; the rank-r key in lane r as heads_rounds leaves it
+template <int G>
+__device__ __forceinline__ int heads3_select(u32 *S, u32 ns, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key, bool &doubt RK_STAMP_PARAMS) {
+    Heads3 h;
+    heads3_clear(h);
+    heads3_scan<G>(S, ns, li, h);
+    RK_STAMP(8);
+    u32 win_o, win_t;
+    const int num = heads3_rounds<G>(h, K, li, gi, win_o, win_t, doubt);
+    RK_STAMP(9);
+    const bool won = (int)li < num;
+    const u32 prev_o = row_shr32<1>(win_o), prev_t = row_shr32<1>(win_t);
+    const bool tie = won && li > 0 && prev_o == win_o;                   // equal scores in neighbouring ranks
+    const bool second = tie && (prev_t | HEADS3_SECOND) == win_t;        // ... both of one stream
+    const u32 stream = won ? (win_t & (HEADS3_SECOND - 1u)) - 1u : 0u;
+    const u32 slot = heads3_locate<G>(S, ns, stream, __float_as_uint(unord_f32(win_o)), second);
+    if (group_bits<G>(__ballot(won && slot == 0u), gi) != 0) doubt = true;  // (never met: the exact path would put it right)
+    win_key = won ? (((u64)win_o << 32) | (u64)(0xFFFFu - (slot - 1u))) : 0ull;
+    if (__ballot(tie && !doubt) != 0) {  // rare, wave-uniform: the order among equal scores is the branch's -- rank the K keys as a whole
+#ifdef RK_STAMPS
+        st_[15] += 1;  // (diagnostic: tiles that re-rank)
+#endif
+        wave_lds_fence();
+        if (won) list[li] = win_key;
+        wave_lds_fence();
+        u64 *win = list + (cap - 16);
+        rank_candidates<G>(list, num, win, K, li);
+        win_key = won ? win[li] : 0ull;
+        wave_lds_fence();
+    }
+    RK_STAMP(13);
+    return num;
+}
 template <int G>
 __device__ __forceinline__ int select_topk(u32 *S, u32 n_branches, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key RK_STAMP_PARAMS) {
     // slot layout: the scratch word S[0] leaves the competition, then the scan runs over ns = n_branches + 1 slots and
@@ -932,12 +1118,20 @@ __device__ __forceinline__ int select_topk(u32 *S, u32 n_branches, u32 li, u32 g
     wave_lds_fence();
     const u32 nb = n_branches + 1;
     if (K > RK_HEADS_MAX_K || K > G) return select_topk_scan<G>(S, nb, li, gi, K, list, cap, win_key RK_STAMP_ARGS);
-    Heads4 h;
-    heads_clear(h);
-    heads_scan<G>(S, nb, li, 0u, h);
-    RK_STAMP(8);
     bool doubt;
-    const int num = heads_rounds<G>(h, K, li, gi, win_key, doubt);
+    int num;
+    if constexpr (G == 16) {  // a group is one DPP row: scores only in the scan, the winners' slots looked up afterwards
+        num = heads3_select<G>(S, nb, li, gi, K, list, cap, win_key, doubt RK_STAMP_ARGS);
+    } else {
+        Heads4 h;
+        heads_clear(h);
+        heads_scan<G>(S, nb, li, 0u, h);
+        RK_STAMP(8);
+        num = heads_rounds<G>(h, K, li, gi, win_key, doubt);
+    }
+#ifdef RK_STAMPS
+    st_[14] += doubt ? 1 : 0;  // (diagnostic: reads sent to the exact scan)
+#endif
     if (doubt) return select_topk_scan<G>(S, nb, li, gi, K, list, cap, win_key RK_STAMP_ARGS);
     RK_STAMP(9);
     uint4 *S4w = (uint4 *)S;
@@ -1598,7 +1792,9 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         RK_STAMP(1);  // next tile's codes + gather issue
 
         u64 win_key;
-        const int numBest = select_topk<G>(S, nb, li, gi, (int)a.keep_at_most, list, (int)a.list_cap, win_key RK_STAMP_ARGS);
+        int numBest = 0;
+        if (RK_ABLATE & 2) { win_key = list[0]; for (u32 i = li; i <= nb; i += G) S[i] = S_UNTOUCHED; }  // (timing only)
+        else numBest = select_topk<G>(S, nb, li, gi, (int)a.keep_at_most, list, (int)a.list_cap, win_key RK_STAMP_ARGS);
         wave_lds_fence();
         RK_STAMP(5);  // select (rest: reset)
         decode_batch(ncode, nraw, 0u, nQ, desc0);  // (before this tile's stores, so that the wait covers loads only)

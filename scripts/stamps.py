@@ -2,7 +2,7 @@
 import ctypes as C, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-so = os.path.join(ROOT, "rappas_amd", "variants", "librk_stamps.so")
+so = os.environ.get("RK_STAMPS_LIB") or os.path.join(ROOT, "rappas_amd", "variants", "librk_stamps.so")  # (RK_STAMPS_LIB: a stamps build of another revision)
 extra = sys.argv[1:]
 flags = [a for a in extra if a.startswith("-D")]
 table = next((a.split("=")[1] for a in extra if a.startswith("--table=")), "auto")
@@ -23,7 +23,15 @@ mode = {"auto": ra.RK_TABLE_AUTO, "direct": ra.RK_TABLE_DIRECT, "direct8": ra.RK
 db = ra.PhyloKmerDB.from_synth(sdb, table_mode=mode)
 pp = ra.PlacementProcess(db)
 n = 4_000_000
-if bits == 2:
+clade = "--clade" in extra  # C2's tree with clade-shaped reads (bench.py --full's clade leg) instead of uniform ones
+if clade:
+    sdb, genome = synth.make_clade_db(k=10, n_branches=999)
+    db = ra.PhyloKmerDB.from_synth(sdb, table_mode=mode)
+    pp = ra.PlacementProcess(db)
+    n = 2_000_000
+    seq, off = synth.make_clade_reads(genome, n, rlen)
+    packed = torch.from_numpy(pp.pack_reads_host(seq, off)[0].view(np.int32)).cuda()
+elif bits == 2:
     wpr = db.packed_words(rlen)
     packed = torch.randint(-2**31, 2**31, (n, wpr), dtype=torch.int64, device="cuda").to(torch.int32)
     packed[:, wpr - 1] &= (1 << (2 * rlen - 32 * (wpr - 1))) - 1
@@ -53,6 +61,9 @@ if windowed:
     tot = a[:, :10].sum(1)
 for i, nm in enumerate(names):
     print(f"  {nm:24s} {100 * np.median(a[:, i] / tot):5.1f} %   {np.median(a[:, i]) / (n / 4 / nw):8.0f} cycles/tile")
+if not windowed:  # select_topk: the locate pass of 16-lane groups, and counters (of the wave's first read / of the wave)
+    print(f"  {'select: locate + re-rank':24s} {100 * np.median(a[:, 13] / tot):5.1f} %   {np.median(a[:, 13]) / (n / 4 / nw):8.0f} cycles/tile")
+    print(f"  reads sent to the exact scan: {100 * a[:, 14].sum() / (n / 4):.4f} %   tiles that re-rank equal scores: {100 * a[:, 15].sum() / (n / 4):.4f} %")
 if windowed:
     tiles = n / 4 / nw
     print(f"  accumulate calls/tile {np.median(a[:, 11]) / tiles:.2f}, steps/call {np.median(a[:, 10] / a[:, 11]):.1f}, "
