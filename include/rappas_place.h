@@ -57,7 +57,13 @@ extern "C" {
 #define RK_FLAG_TOO_SHORT 4u      /* R < k : no k-mer (the reference crashes for R < k-1) */
 #define RK_FLAG_AMBIGUOUS 8u      /* read contains an ambiguity character */
 #define RK_FLAG_BELOW_NSBOUND 16u /* best score < ns_bound: no jplace record (PlacementProcess.java:974) */
+#define RK_FLAG_REVERSE 32u       /* the reported result of this read comes from its reverse complement (rk_place_*_strands) */
 #define RK_FLAG_TOO_LONG 64u      /* device pack only: read longer than the packed record; not placed */
+
+/* strand(s) a DNA read is placed on (rk_place_packed_device_strands / rk_place_batch_strands; the reference knows forward only) */
+#define RK_STRAND_FORWARD 0 /* as given: the orientation of the reference alignment */
+#define RK_STRAND_REVERSE 1 /* the reverse complement of every read */
+#define RK_STRAND_BOTH 2    /* both, and per read the result with the better best score */
 
 /* error codes */
 #define RK_OK 0
@@ -240,6 +246,58 @@ int rk_place_packed_device(rk_db *db, const rk_params *p, uint64_t n_reads, cons
                            uint32_t words_per_read, const uint32_t *d_lens, uint32_t fixed_len,
                            const uint32_t *d_flags_in, const uint8_t *d_seq_ascii, const uint64_t *d_seq_off,
                            const rk_result *d_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * DNA reads on either strand.  The reference places a read in the orientation it arrives in only
+ * (src/core/algos/PlacementProcess.java:645-1025 walks the query as given); shotgun and amplicon reads arrive in either.  With
+ * A=0 T=1 C=2 G=3 (src/core/DNAStatesShifted.java:182-209) the complement of a state is state ^ 1, so the other strand of a packed
+ * record is made on the device, and reads being independent (PlacementProcess.java:1067-1075) the better strand is a per-read
+ * choice.  DNA only: on an amino-acid handle every entry point below fails with RK_ERR_UNSUPPORTED.  Device pointers and `stream`
+ * as for rk_place_packed_device.
+ *   rk_revcomp_packed_device  records [n_reads][words_per_read] -> d_packed_out (same geometry; must not alias d_packed): for a read
+ *                             of R symbols (d_lens[r], or fixed_len when d_lens is NULL) output symbol j = input symbol R-1-j xor 1,
+ *                             every bit from 2R on is zero (the packer's padding).  Lengths and flags do not depend on the strand
+ *                             and are not rewritten.
+ *   rk_revcomp_ascii_device   the same for characters, offsets unchanged: read r's bytes reversed and complemented -- A<->T, U->A,
+ *                             C<->G, R<->Y, K<->M, B<->V, D<->H; S W N . - stay; case is kept; any other byte is copied (an
+ *                             unsupported character stays one).  d_out_ascii must not alias d_seq_ascii.
+ *   rk_merge_strands_device   d_fwd (in/out) and d_rev: two result sets of the same reads and keep_at_most.  Per read the reverse
+ *                             result is taken if and only if n_rows_rev > 0 and (n_rows_fwd == 0 or score_rev[0] > score_fwd[0] as
+ *                             float32); a tie keeps forward.  Taking it copies n_rows, all keep_at_most rows of branch / score / lwr
+ *                             and the flags, and sets RK_FLAG_REVERSE.
+ *   rk_strands_work_bytes     bytes of caller-owned device workspace rk_place_packed_device_strands needs for such a batch: the
+ *                             reverse records, a second result set and -- ascii_bytes > 0: the total length of the reads' characters,
+ *                             d_seq_off[n_reads] -- the reversed characters.  0 (and a message) on a bad argument.
+ *   rk_place_packed_device_strands
+ *                             rk_place_packed_device on the strand(s) asked for.  RK_STRAND_FORWARD is exactly that call (d_work may
+ *                             be NULL).  RK_STRAND_REVERSE makes the reverse records in the workspace, places them into d_out and sets
+ *                             RK_FLAG_REVERSE on every read.  RK_STRAND_BOTH places the reverse records into the workspace's result
+ *                             set and the reads as given into d_out, then merges into d_out.  Two placement passes: a fused kernel is
+ *                             not part of this version.  Allocates nothing; a workspace smaller than rk_strands_work_bytes(...,
+ *                             ascii_bytes = 0) or an unknown strand is RK_ERR_INVALID, and nothing is launched.  The reversed
+ *                             characters (made only for the reads the ambiguity kernel takes, and only when d_flags_in, d_seq_ascii
+ *                             and d_seq_off are all given) go behind that part: the call cannot see d_seq_off[n_reads] without
+ *                             waiting for the stream, so what the workspace holds beyond it is their room -- none at all is
+ *                             RK_ERR_INVALID, no byte is written past it.  Asynchronous on `stream`; the one-stream rule of
+ *                             rk_place_packed_device holds (the handle's launch scratch is used through that call).
+ *   rk_place_batch_strands    rk_place_batch on the strand(s) asked for: the same chunked host path, the workspace part of the
+ *                             handle's host-path buffers (grow-only, freed by rk_db_destroy); a chunk's characters are reversed only
+ *                             if it holds a read flagged AMBIGUOUS.  counters are taken from the final flags.  Results equal
+ *                             rk_place_packed_device_strands over the whole batch, whatever the chunking.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int rk_revcomp_packed_device(rk_db *db, uint64_t n_reads, const uint32_t *d_packed, uint32_t words_per_read, const uint32_t *d_lens,
+                             uint32_t fixed_len, uint32_t *d_packed_out, void *stream);
+int rk_revcomp_ascii_device(rk_db *db, uint64_t n_reads, const uint8_t *d_seq_ascii, const uint64_t *d_seq_off, uint8_t *d_out_ascii,
+                            void *stream);
+int rk_merge_strands_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_fwd, const rk_result *d_rev,
+                            void *stream);
+uint64_t rk_strands_work_bytes(const rk_db *db, uint64_t n_reads, uint32_t words_per_read, uint32_t keep_at_most, uint64_t ascii_bytes);
+int rk_place_packed_device_strands(rk_db *db, const rk_params *p, uint32_t strand, uint64_t n_reads, const uint32_t *d_packed,
+                                   uint32_t words_per_read, const uint32_t *d_lens, uint32_t fixed_len, const uint32_t *d_flags_in,
+                                   const uint8_t *d_seq_ascii, const uint64_t *d_seq_off, const rk_result *d_out, void *d_work,
+                                   uint64_t work_bytes, void *stream);
+int rk_place_batch_strands(rk_db *db, const rk_params *p, uint32_t strand, uint64_t n_reads, const uint8_t *seq_ascii,
+                           const uint64_t *seq_off, rk_result *out, rk_counters *counters);
 
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the

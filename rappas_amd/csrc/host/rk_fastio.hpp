@@ -730,12 +730,13 @@ inline FastWriteStats write_jplace_fast(const std::string &path, const Tree &t, 
 }
 
 // notplaced_<query>.tsv of rk_hostio.hpp: notplaced_log over the scan's records
-inline std::string notplaced_log_fast(const FastaScan &sc, const FastDedup &d, const uint32_t *flags) {
+inline std::string flagged_log_fast(const FastaScan &sc, const FastDedup &d, const uint32_t *flags, uint32_t mask, uint32_t want) {
     std::string out;
     for (size_t i = 0; i < sc.recs.size(); i++)
-        if (!(flags[d.uniq_of_rec[i]] & 1u)) { out.append(sc.recs[i].hdr, sc.recs[i].hdr_len); out.push_back('\n'); }
+        if ((flags[d.uniq_of_rec[i]] & mask) == want) { out.append(sc.recs[i].hdr, sc.recs[i].hdr_len); out.push_back('\n'); }
     return out;
 }
+inline std::string notplaced_log_fast(const FastaScan &sc, const FastDedup &d, const uint32_t *flags) { return flagged_log_fast(sc, d, flags, 1u, 0u); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // the reference tree as the `user` blob of a database image (rk_db_save): exact, line based

@@ -196,14 +196,17 @@ inline void dedup_reads(const std::vector<Fasta> &recs, std::vector<Fasta> &uniq
     names = dedup_names(recs, d);
 }
 
-// notplaced_<query>.tsv (Main_PLACEMENT_v07.java:214, PlacementProcess.java:797-806): the full header of every read that hits
-// nothing in the database, every occurrence (the reference registers checksums of placed reads only, :1046), in file order
-inline std::string notplaced_log(const std::vector<Fasta> &recs, const Dedup &d, const uint32_t *flags) {
+// the full header of every record whose unique read has (flags & mask) == want, one per line, in file order, every occurrence
+inline std::string flagged_log(const std::vector<Fasta> &recs, const Dedup &d, const uint32_t *flags, uint32_t mask, uint32_t want) {
     std::string out;
     for (size_t i = 0; i < recs.size(); i++)
-        if (!(flags[d.uniq_of_rec[i]] & 1u)) { out += recs[i].header; out += "\n"; }
+        if ((flags[d.uniq_of_rec[i]] & mask) == want) { out += recs[i].header; out += "\n"; }
     return out;
 }
+// notplaced_<query>.tsv (Main_PLACEMENT_v07.java:214, PlacementProcess.java:797-806): the full header of every read that hits
+// nothing in the database, every occurrence (the reference registers checksums of placed reads only, :1046), in file order.
+// (reversed_<query>.tsv of --strand rev | both follows the same rules with RK_FLAG_REVERSE.)
+inline std::string notplaced_log(const std::vector<Fasta> &recs, const Dedup &d, const uint32_t *flags) { return flagged_log(recs, d, flags, 1u, 0u); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // N1: tree

@@ -23,18 +23,20 @@ static std::string slurp(const std::string &path) {
     return ss.str();
 }
 
-static int usage() {
-    std::cerr << "usage: rk_place (--jsondb DB.json | --uniondb DB.union | --dbimage DB.rkimg) --fasta READS.fa --out OUT.jplace [--keep-at-most 7]\n"
+static int usage(std::ostream &os = std::cerr, int rc = 2) {
+    os << "usage: rk_place (--jsondb DB.json | --uniondb DB.union | --dbimage DB.rkimg) --fasta READS.fa --out OUT.jplace [--keep-at-most 7]\n"
                  "                [--keep-factor 0.01] [--amb mean|max|skip] [--nsbound X] [--guppy-compat] [--device 0] [--logs DIR]\n"
-                 "                [--threads N] [--md5-dedup] [--classic-io] [--timing] [--save-dbimage DB.rkimg]\n"
+                 "                [--threads N] [--md5-dedup] [--classic-io] [--timing] [--save-dbimage DB.rkimg] [--strand fwd|rev|both]\n"
+                 "                (--strand, DNA: the reads as given = the reference's behaviour | their reverse complements | both, the better\n"
+                 "                 strand per read; rev / both also write logs/reversed_<query>.tsv)\n"
                  "       rk_place (--jsondb DB.json | --uniondb DB.union) --save-dbimage DB.rkimg      (no GPU needed)\n"
                  "       rk_place --emit-tree TREE.nwk | --format-float X | --format-double X | --dedup READS.fa | --md5 TEXT\n";
-    return 2;
+    return rc;
 }
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd";
         bool logs_given = false, md5_dedup = false, classic = false, timing = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7;
@@ -59,6 +61,8 @@ int main(int argc, char **argv) {
             else if (a == "--keep-at-most") keep_at_most = (uint32_t)std::stoul(val());
             else if (a == "--keep-factor") keep_factor = std::stof(val());
             else if (a == "--amb") amb = val();
+            else if (a == "--strand") strand_name = val();
+            else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
             else if (a == "--guppy-compat") guppy = true;
             else if (a == "--device") device = std::stoi(val());
@@ -243,6 +247,14 @@ int main(int argc, char **argv) {
         uint32_t amb_mode;
         if (amb == "mean") amb_mode = RK_AMB_MEAN; else if (amb == "max") amb_mode = RK_AMB_MAX; else if (amb == "skip") amb_mode = RK_AMB_SKIP;
         else return usage();
+        uint32_t strand;
+        if (strand_name == "fwd") strand = RK_STRAND_FORWARD; else if (strand_name == "rev") strand = RK_STRAND_REVERSE; else if (strand_name == "both") strand = RK_STRAND_BOTH;
+        else return usage();
+        // (fwd is rk_place_batch itself: the reference's behaviour, and this driver's before it knew about strands)
+        auto place = [&](rk_db *h, const rk_params *pp, uint64_t m, const uint8_t *sq, const uint64_t *so, rk_result *rs, rk_counters *c) {
+            const int rc = strand == RK_STRAND_FORWARD ? rk_place_batch(h, pp, m, sq, so, rs, c) : rk_place_batch_strands(h, pp, strand, m, sq, so, rs, c);
+            if (rc != RK_OK) throw std::runtime_error(std::string(strand == RK_STRAND_FORWARD ? "rk_place_batch: " : "rk_place_batch_strands: ") + rk_last_error());
+        };
         auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_start = now();
 
@@ -293,6 +305,7 @@ int main(int argc, char **argv) {
         namespace fs = std::filesystem;
         const fs::path log_dir = logs_given ? fs::path(logs) : fs::absolute(fs::path(out)).parent_path() / "logs";
         const std::string notplaced_name = "notplaced_" + fs::path(fasta).filename().string() + ".tsv";
+        const std::string reversed_name = "reversed_" + fs::path(fasta).filename().string() + ".tsv";  // (--strand rev | both only)
 
         if (!classic) {
             // ---- every host thread on every pass (rk_fastio.hpp) ----
@@ -330,7 +343,7 @@ int main(int argc, char **argv) {
             const double t3b = now();
             rk_result res{n_rows.data(), branch.data(), score.data(), lwr.data(), flags.data()};
             rk_counters ct;
-            if (rk_place_batch(db, &p, n, (const uint8_t *)seq.data(), off.data(), &res, &ct) != RK_OK) throw std::runtime_error(std::string("rk_place_batch: ") + rk_last_error());
+            place(db, &p, n, (const uint8_t *)seq.data(), off.data(), &res, &ct);
             const double t4 = now();
             const rkh::FastWriteStats ws = rkh::write_jplace_fast(out, tree, sc, dd, K, n_rows.data(), branch.data(), score.data(), lwr.data(), call, guppy, team);
             const double t5 = now();
@@ -339,6 +352,11 @@ int main(int argc, char **argv) {
                 std::ofstream nf(log_dir / notplaced_name, std::ios::binary);
                 if (!nf) throw std::runtime_error("cannot write the notplaced log under " + log_dir.string());
                 nf << rkh::notplaced_log_fast(sc, dd, flags.data());
+            }
+            if (strand != RK_STRAND_FORWARD) {
+                std::ofstream rf(log_dir / reversed_name, std::ios::binary);
+                if (!rf) throw std::runtime_error("cannot write the reversed log under " + log_dir.string());
+                rf << rkh::flagged_log_fast(sc, dd, flags.data(), RK_FLAG_REVERSE, RK_FLAG_REVERSE);
             }
             const double t6 = now();
             std::cerr << n << " unique reads, " << ws.placed << " placed -> " << out << "\n";
@@ -373,8 +391,7 @@ int main(int argc, char **argv) {
         std::vector<uint32_t> flags(n);
         rk_result res{n_rows.data(), branch.data(), score.data(), lwr.data(), flags.data()};
         rk_counters ct;
-        const int rc = rk_place_batch(db, &p, n, (const uint8_t *)seq.data(), off.data(), &res, &ct);
-        if (rc != RK_OK) throw std::runtime_error(std::string("rk_place_batch: ") + rk_last_error());
+        place(db, &p, n, (const uint8_t *)seq.data(), off.data(), &res, &ct);
 
         const auto pl = rkh::jplace_placements(tree, names, n, K, n_rows.data(), branch.data(), score.data(), lwr.data(), guppy);
         std::ofstream of(out, std::ios::binary);
@@ -385,6 +402,11 @@ int main(int argc, char **argv) {
             std::ofstream nf(log_dir / notplaced_name, std::ios::binary);
             if (!nf) throw std::runtime_error("cannot write the notplaced log under " + log_dir.string());
             nf << rkh::notplaced_log(records, dd, flags.data());
+            if (strand != RK_STRAND_FORWARD) {
+                std::ofstream rf(log_dir / reversed_name, std::ios::binary);
+                if (!rf) throw std::runtime_error("cannot write the reversed log under " + log_dir.string());
+                rf << rkh::flagged_log(records, dd, flags.data(), RK_FLAG_REVERSE, RK_FLAG_REVERSE);
+            }
         }
         std::cerr << n << " unique reads, " << pl.size() << " placed -> " << out << "\n";
         if (timing) std::cout << "{\"reads\": " << records.size() << ", \"unique\": " << n << ", \"db_s\": " << (t_db - t_start) << ", \"fasta_to_jplace_s\": " << (now() - tc0) << ", \"classic\": true}" << std::endl;

@@ -415,6 +415,7 @@ unsigned host_threads(uint64_t n_reads, unsigned asked) {
 
 struct rk_workspace {
     GrowBuf ascii, off, packed, lens, flags, nrows, branch, score, lwr, oflags;
+    GrowBuf strands;  // rk_place_batch_strands: the workspace of rk_place_packed_device_strands for a chunk
     // page-locked staging for callers that hand over pageable memory (a JVM heap array, a numpy array): copies to / from
     // it run on a few host threads, the DMA itself is then asynchronous and overlaps the other workspace's chunk
     PinBuf h_ascii, h_off, h_packed, h_nrows, h_branch, h_score, h_lwr, h_oflags;
@@ -422,7 +423,7 @@ struct rk_workspace {
     uint64_t pend_r0 = 0, pend_n = 0;
     hipStream_t stream = nullptr;
     void release() {
-        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &nrows, &branch, &score, &lwr, &oflags}) b->release();
+        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &nrows, &branch, &score, &lwr, &oflags, &strands}) b->release();
         for (PinBuf *b : {&h_ascii, &h_off, &h_packed, &h_nrows, &h_branch, &h_score, &h_lwr, &h_oflags}) b->release();
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;
@@ -2084,6 +2085,152 @@ extern "C" int rk_place_packed_device(rk_db *db, const rk_params *p, uint64_t n_
     return RK_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// DNA reads on either strand: the reverse complement of packed records / characters on the device, the per-read
+// merge of two result sets, and rk_place_packed_device composed over them.  Two placement passes; nothing here touches a placement
+// kernel or the launch plan.
+// ------------------------------------------------------------------------------------------------
+static int strands_handle(const rk_db *db, const char *who) {
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (db->info.alphabet != RK_ALPHABET_DNA) return fail(RK_ERR_UNSUPPORTED, "%s: reverse complement is defined for DNA databases only (this one holds amino acids)", who);
+    return RK_OK;
+}
+
+static unsigned strand_blocks(const rk_db *db, uint64_t threads) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((threads + 255) / 256, (uint64_t)db->cu_count * 16));
+}
+
+extern "C" int rk_revcomp_packed_device(rk_db *db, uint64_t n_reads, const uint32_t *d_packed, uint32_t words_per_read, const uint32_t *d_lens,
+                                        uint32_t fixed_len, uint32_t *d_packed_out, void *stream) {
+    int rc = strands_handle(db, "rk_revcomp_packed_device");
+    if (rc) return rc;
+    if (n_reads == 0) return RK_OK;
+    if (!d_packed || !d_packed_out || words_per_read == 0) return fail(RK_ERR_INVALID, "rk_revcomp_packed_device: null/zero argument");
+    if (d_packed == d_packed_out) return fail(RK_ERR_INVALID, "rk_revcomp_packed_device: the output must not alias the input");
+    if (!d_lens && (uint64_t)fixed_len * 2 > (uint64_t)words_per_read * 32)
+        return fail(RK_ERR_INVALID, "rk_revcomp_packed_device: fixed_len=%u does not fit %u words", fixed_len, words_per_read);
+    HIP_TRY(hipSetDevice(db->info.device));
+    hipLaunchKernelGGL(revcomp_packed_kernel, dim3(strand_blocks(db, n_reads * words_per_read)), dim3(256), 0, (hipStream_t)stream, d_packed, (u64)n_reads,
+                       words_per_read, d_lens, fixed_len, d_packed_out);
+    HIP_TRY(hipGetLastError());
+    return RK_OK;
+}
+
+// only_flags / out_cap: the composed call reverses the reads the ambiguity kernel takes, into the room its workspace has
+static int launch_revcomp_ascii(rk_db *db, uint64_t n_reads, const uint8_t *d_seq_ascii, const uint64_t *d_seq_off, const uint32_t *only_flags,
+                                uint8_t *d_out, uint64_t out_cap, hipStream_t s) {
+    hipLaunchKernelGGL(revcomp_ascii_kernel, dim3(strand_blocks(db, n_reads * 64)), dim3(256), 0, s, d_seq_ascii, (const u64 *)d_seq_off, (u64)n_reads,
+                       only_flags, d_out, (u64)out_cap);
+    HIP_TRY(hipGetLastError());
+    return RK_OK;
+}
+
+extern "C" int rk_revcomp_ascii_device(rk_db *db, uint64_t n_reads, const uint8_t *d_seq_ascii, const uint64_t *d_seq_off, uint8_t *d_out_ascii,
+                                       void *stream) {
+    int rc = strands_handle(db, "rk_revcomp_ascii_device");
+    if (rc) return rc;
+    if (n_reads == 0) return RK_OK;
+    if (!d_seq_ascii || !d_seq_off || !d_out_ascii) return fail(RK_ERR_INVALID, "rk_revcomp_ascii_device: null argument");
+    if (d_seq_ascii == d_out_ascii) return fail(RK_ERR_INVALID, "rk_revcomp_ascii_device: the output must not alias the input");
+    HIP_TRY(hipSetDevice(db->info.device));
+    return launch_revcomp_ascii(db, n_reads, d_seq_ascii, d_seq_off, nullptr, d_out_ascii, ~0ull, (hipStream_t)stream);
+}
+
+static bool result_complete(const rk_result *r) { return r && r->n_rows && r->branch && r->score && r->lwr && r->flags; }
+
+extern "C" int rk_merge_strands_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_fwd, const rk_result *d_rev,
+                                       void *stream) {
+    int rc = strands_handle(db, "rk_merge_strands_device");
+    if (rc) return rc;
+    if (keep_at_most < 1 || keep_at_most > 16) return fail(RK_ERR_INVALID, "keep_at_most=%u outside 1..16", keep_at_most);
+    if (n_reads == 0) return RK_OK;
+    if (!result_complete(d_fwd) || !result_complete(d_rev)) return fail(RK_ERR_INVALID, "rk_merge_strands_device: null result array");
+    HIP_TRY(hipSetDevice(db->info.device));
+    hipLaunchKernelGGL(merge_strands_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, (hipStream_t)stream, (u64)n_reads, keep_at_most, d_fwd->n_rows,
+                       d_fwd->branch, d_fwd->score, d_fwd->lwr, d_fwd->flags, (const unsigned char *)d_rev->n_rows, (const unsigned short *)d_rev->branch,
+                       (const float *)d_rev->score, (const double *)d_rev->lwr, (const uint32_t *)d_rev->flags);
+    HIP_TRY(hipGetLastError());
+    return RK_OK;
+}
+
+// The workspace of rk_place_packed_device_strands: reverse records | second result set (n_rows, branch, score, lwr, flags) |
+// reversed characters; every part starts on a 256-byte boundary of the block.
+struct StrandWork {
+    uint64_t rec, nrows, branch, score, lwr, flags, ascii;  // byte offsets; `ascii` = size of everything before the characters
+};
+static StrandWork strand_work(uint64_t n, uint32_t wpr, uint32_t K) {
+    auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
+    StrandWork w{};
+    w.rec = 0;
+    w.nrows = up(n * wpr * 4);
+    w.branch = w.nrows + up(n);
+    w.score = w.branch + up(n * K * 2);
+    w.lwr = w.score + up(n * K * 4);
+    w.flags = w.lwr + up(n * K * 8);
+    w.ascii = w.flags + up(n * 4);
+    return w;
+}
+
+extern "C" uint64_t rk_strands_work_bytes(const rk_db *db, uint64_t n_reads, uint32_t words_per_read, uint32_t keep_at_most, uint64_t ascii_bytes) {
+    if (strands_handle(db, "rk_strands_work_bytes")) return 0;
+    if (words_per_read == 0 || keep_at_most < 1 || keep_at_most > 16) { (void)fail(RK_ERR_INVALID, "rk_strands_work_bytes: words_per_read=%u, keep_at_most=%u", words_per_read, keep_at_most); return 0; }
+    if (n_reads >= (1ull << 40)) { (void)fail(RK_ERR_INVALID, "rk_strands_work_bytes: n_reads too large"); return 0; }
+    return strand_work(n_reads, words_per_read, keep_at_most).ascii + ascii_bytes;
+}
+
+extern "C" int rk_place_packed_device_strands(rk_db *db, const rk_params *p, uint32_t strand, uint64_t n_reads, const uint32_t *d_packed,
+                                              uint32_t words_per_read, const uint32_t *d_lens, uint32_t fixed_len, const uint32_t *d_flags_in,
+                                              const uint8_t *d_seq_ascii, const uint64_t *d_seq_off, const rk_result *d_out, void *d_work,
+                                              uint64_t work_bytes, void *stream) {
+    int rc = strands_handle(db, "rk_place_packed_device_strands");
+    if (rc) return rc;
+    if (strand > RK_STRAND_BOTH) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: strand=%u (0 forward, 1 reverse, 2 both)", strand);
+    if (strand == RK_STRAND_FORWARD)
+        return rk_place_packed_device(db, p, n_reads, d_packed, words_per_read, d_lens, fixed_len, d_flags_in, d_seq_ascii, d_seq_off, d_out, stream);
+    // every test the placement call would make, before the first launch: an error leaves the caller's arrays as they are
+    if (!d_out) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: null argument");
+    rc = check_params(p);
+    if (rc) return rc;
+    if (n_reads == 0) return RK_OK;
+    if (!d_packed || words_per_read == 0) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: null packed reads");
+    if (!result_complete(d_out)) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: null result array");
+    if (!d_lens && (uint64_t)fixed_len * 2 > (uint64_t)words_per_read * 32)
+        return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: fixed_len=%u does not fit %u words", fixed_len, words_per_read);
+    if (n_reads >= (1ull << 40)) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: n_reads too large");
+    const StrandWork L = strand_work(n_reads, words_per_read, p->keep_at_most);
+    if (!d_work || work_bytes < L.ascii)
+        return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: workspace of %llu bytes, %llu needed (rk_strands_work_bytes)", (unsigned long long)(d_work ? work_bytes : 0),
+                    (unsigned long long)L.ascii);
+    const bool ascii = d_flags_in && d_seq_ascii && d_seq_off;
+    if (ascii && work_bytes == L.ascii)
+        return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: the workspace has no room for the reversed characters (rk_strands_work_bytes with ascii_bytes)");
+    HIP_TRY(hipSetDevice(db->info.device));
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)d_work;
+    uint32_t *rev = (uint32_t *)(base + L.rec);
+    uint8_t *rev_ascii = ascii ? (uint8_t *)(base + L.ascii) : nullptr;
+    rc = rk_revcomp_packed_device(db, n_reads, d_packed, words_per_read, d_lens, fixed_len, rev, s);
+    if (rc) return rc;
+    if (ascii) {
+        rc = launch_revcomp_ascii(db, n_reads, d_seq_ascii, d_seq_off, d_flags_in, rev_ascii, work_bytes - L.ascii, s);
+        if (rc) return rc;
+    }
+    if (strand == RK_STRAND_REVERSE) {
+        rc = rk_place_packed_device(db, p, n_reads, rev, words_per_read, d_lens, fixed_len, d_flags_in, rev_ascii, d_seq_off, d_out, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(mark_reverse_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, s, d_out->flags, (u64)n_reads);
+        HIP_TRY(hipGetLastError());
+        return RK_OK;
+    }
+    // the reverse strand first: d_flags_in may be the output flag array itself, which the forward pass then overwrites
+    const rk_result rres{(uint8_t *)(base + L.nrows), (uint16_t *)(base + L.branch), (float *)(base + L.score), (double *)(base + L.lwr), (uint32_t *)(base + L.flags)};
+    rc = rk_place_packed_device(db, p, n_reads, rev, words_per_read, d_lens, fixed_len, d_flags_in, rev_ascii, d_seq_off, &rres, s);
+    if (rc) return rc;
+    rc = rk_place_packed_device(db, p, n_reads, d_packed, words_per_read, d_lens, fixed_len, d_flags_in, d_seq_ascii, d_seq_off, d_out, s);
+    if (rc) return rc;
+    return rk_merge_strands_device(db, p->keep_at_most, n_reads, d_out, &rres, s);
+}
+
 // rk_count_work_device: the work a batch asks of the database (count_work_kernel), for callers that want the reference's own
 // diagnostics -- k-mers looked up, k-mers found, row entries walked -- next to the placements.  Opt-in and separate: the placement
 // kernels carry no counters.
@@ -2138,7 +2285,7 @@ static rk::PackSpec pack_spec(const Alphabet &A, uint32_t alphabet, uint32_t bit
 }
 
 static int place_host(rk_db *db, const rk_params *p, uint64_t n_reads, const HostInput &in, rk_result *out, rk_counters *counters,
-                      const char *who) {
+                      const char *who, uint32_t strand = RK_STRAND_FORWARD) {
     const bool packed_in = in.packed != nullptr;
     const uint8_t *seq_ascii = in.ascii;
     const uint64_t *seq_off = in.off;
@@ -2442,8 +2589,18 @@ static int place_host(rk_db *db, const rk_params *p, uint64_t n_reads, const Hos
             rk_result dres{w.nrows.as<uint8_t>(), w.branch.as<uint16_t>(), w.score.as<float>(), w.lwr.as<double>(), w.oflags.as<uint32_t>()};
             const uint32_t *d_lens = (!packed_in || in.lens) ? w.lens.as<uint32_t>() : nullptr;   // (host-packed chunks carry both)
             const uint32_t *d_flags = (!packed_in || in.flags) ? w.flags.as<uint32_t>() : nullptr;
-            WS_TRY(rk_place_packed_device(db, p, n, w.packed.as<uint32_t>(), wpr, d_lens, packed_in ? in.fixed_len : 0, d_flags,
-                                          need_ascii ? w.ascii.as<uint8_t>() : nullptr, need_ascii ? w.off.as<uint64_t>() : nullptr, &dres, s));
+            if (strand == RK_STRAND_FORWARD) {
+                WS_TRY(rk_place_packed_device(db, p, n, w.packed.as<uint32_t>(), wpr, d_lens, packed_in ? in.fixed_len : 0, d_flags,
+                                              need_ascii ? w.ascii.as<uint8_t>() : nullptr, need_ascii ? w.off.as<uint64_t>() : nullptr, &dres, s));
+            } else {
+                // the other strand's records, its result set and -- a chunk whose characters travel -- their reverse complement: part
+                // of the workspace (a chunk of empty reads has characters of length 0: one byte of room keeps the call's test quiet)
+                const uint64_t wb = rk_strands_work_bytes(db, n, wpr, K, need_ascii ? std::max<uint64_t>(nbytes, 1) : 0);
+                WS_TRY(w.strands.reserve(wb));
+                WS_TRY(rk_place_packed_device_strands(db, p, strand, n, w.packed.as<uint32_t>(), wpr, d_lens, packed_in ? in.fixed_len : 0, d_flags,
+                                                      need_ascii ? w.ascii.as<uint8_t>() : nullptr, need_ascii ? w.off.as<uint64_t>() : nullptr, &dres,
+                                                      w.strands.p, wb, s));
+            }
         }
         if (out_pinned) {
             WS_HIP(hipMemcpyAsync(out->n_rows + r0, w.nrows.p, n, hipMemcpyDeviceToHost, s));
@@ -2556,6 +2713,22 @@ extern "C" int rk_place_batch(rk_db *db, const rk_params *p, uint64_t n_reads, c
     RK_GUARD_BEGIN
     return place_host(db, p, n_reads, in, out, counters, "rk_place_batch");
     RK_GUARD_END("rk_place_batch")
+}
+
+extern "C" int rk_place_batch_strands(rk_db *db, const rk_params *p, uint32_t strand, uint64_t n_reads, const uint8_t *seq_ascii,
+                                      const uint64_t *seq_off, rk_result *out, rk_counters *counters) {
+    int rc = strands_handle(db, "rk_place_batch_strands");
+    if (rc) return rc;
+    if (strand > RK_STRAND_BOTH) return fail(RK_ERR_INVALID, "rk_place_batch_strands: strand=%u (0 forward, 1 reverse, 2 both)", strand);
+    if (!out) return fail(RK_ERR_INVALID, "rk_place_batch_strands: null argument");
+    rc = check_params(p);
+    if (rc) return rc;
+    if (n_reads && (!seq_ascii || !seq_off)) return fail(RK_ERR_INVALID, "rk_place_batch_strands: null reads");
+    HostInput in;
+    in.ascii = seq_ascii; in.off = seq_off;
+    RK_GUARD_BEGIN
+    return place_host(db, p, n_reads, in, out, counters, "rk_place_batch_strands", strand);
+    RK_GUARD_END("rk_place_batch_strands")
 }
 
 extern "C" int rk_place_batch_packed(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *packed, uint32_t words_per_read,

@@ -4213,4 +4213,129 @@ __global__ void __launch_bounds__(256) pack_reads_kernel(const unsigned char *as
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// the other strand of a DNA read.  States are A=0 T=1 C=2 G=3, so the complement of a state is state ^ 1 and the
+// reverse complement of a 2-bit record is register work: output symbol j = input symbol R-1-j, xor 1.  The reference places a read
+// in the orientation it arrives in only; nothing of it stands behind these kernels.
+//
+// revcomp_packed_kernel: one thread per output word, as pack_reads_kernel.  Output word w holds the output symbols 16w .. 16w+15 =
+// the input symbols R-16(w+1) .. R-1-16w in reverse order: the 32 input bits from bit 2(R-16(w+1)) on -- two words and one 32-bit
+// funnel shift (v_alignbit_b32; no 64-bit shift by a per-lane count) --, bit-reversed, the two bits of every pair swapped back, xor
+// 0b01 per symbol.  Where the window starts below symbol 0 (the read's last word, reads of fewer than 16 symbols) the input's first
+// word is shifted up instead and the symbols at or beyond R are masked: every bit from 2R on is zero, the packer's padding.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) revcomp_packed_kernel(const u32 *packed, u64 n_reads, u32 words_per_read, const u32 *lens, u32 fixed_len,
+                                                             u32 *out) {
+    const u64 total = n_reads * words_per_read;
+    const u32 cap_syms = words_per_read * 16u;
+    for (u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (u64)gridDim.x * blockDim.x) {
+        const u64 r = t / words_per_read;
+        const u32 w = (u32)(t - r * words_per_read);
+        u32 R = lens ? lens[r] : fixed_len;
+        R = R < cap_syms ? R : cap_syms;
+        const u32 done = 16u * w;  // output symbols in the words before this one
+        u32 v = 0;
+        if (R > done) {
+            const u32 *rec = packed + r * words_per_read;
+            const u32 left = R - done;  // output symbols from this word on
+            u32 x;
+            if (left >= 16u) {
+                const u32 bit = 2u * (left - 16u);  // first input bit of the window
+                const u32 wi = bit >> 5, sh = bit & 31u;
+                const u32 w0 = rec[wi];
+                const u32 w1 = wi + 1 < words_per_read ? rec[wi + 1] : 0u;  // (wi + 1 == words_per_read only with sh == 0)
+                x = __builtin_amdgcn_alignbit(w1, w0, sh);
+            } else {
+                x = rec[0] << (32u - 2u * left);  // input symbols 0 .. left-1 at the top of the window (left >= 1: a 32-bit shift by 2 .. 30)
+            }
+            x = __builtin_bitreverse32(x);
+            x = ((x & 0x55555555u) << 1) | ((x >> 1) & 0x55555555u);
+            v = x ^ 0x55555555u;
+            if (left < 16u) v &= (1u << (2u * left)) - 1u;
+        }
+        out[t] = v;
+    }
+}
+
+// complement of an IUPAC nucleotide code, case kept; every other byte is itself (so an unsupported character stays one)
+__device__ __forceinline__ unsigned char complement_char(unsigned char c) {
+    const unsigned char up = (c >= 'a' && c <= 'z') ? (unsigned char)(c - 32) : c;
+    unsigned char o;
+    switch (up) {
+    case 'A': o = 'T'; break;
+    case 'T': case 'U': o = 'A'; break;
+    case 'C': o = 'G'; break;
+    case 'G': o = 'C'; break;
+    case 'R': o = 'Y'; break;
+    case 'Y': o = 'R'; break;
+    case 'K': o = 'M'; break;
+    case 'M': o = 'K'; break;
+    case 'B': o = 'V'; break;
+    case 'V': o = 'B'; break;
+    case 'D': o = 'H'; break;
+    case 'H': o = 'D'; break;
+    default: return c;
+    }
+    return up == c ? o : (unsigned char)(o + 32);
+}
+
+// revcomp_ascii_kernel: the same for the characters (the ambiguity kernel works on characters).  One wave per read, a lane per
+// output byte: the stores of a wave are consecutive bytes, its loads the mirrored run.  The complement table sits in the LDS.
+// only_flags (or nullptr = every read): only the reads place_ascii_kernel will take -- flagged AMBIGUOUS, neither BAD_CHAR nor
+// TOO_LONG -- are written.  No byte at or beyond out_cap is written.
+__global__ void __launch_bounds__(256) revcomp_ascii_kernel(const unsigned char *ascii, const u64 *seq_off, u64 n_reads, const u32 *only_flags,
+                                                            unsigned char *out, u64 out_cap) {
+    __shared__ unsigned char comp[256];
+    comp[threadIdx.x & 255] = complement_char((unsigned char)(threadIdx.x & 255));
+    __syncthreads();
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 r = wave; r < n_reads; r += n_waves) {
+        if (only_flags) {
+            const u32 f = only_flags[r];
+            if (!(f & RK_FLAG_AMBIGUOUS) || (f & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG))) continue;
+        }
+        const u64 o0 = seq_off[r], o1 = seq_off[r + 1];
+        const u64 end = o1 < out_cap ? o1 : out_cap;
+        for (u64 o = o0 + lane; o < end; o += 64) out[o] = comp[ascii[o1 - 1 - (o - o0)]];
+    }
+}
+
+// merge_strands_kernel: per read the better of the two strands' results, in place in the forward set.  A wave takes 64 reads: every
+// lane decides one of them (reverse iff it has rows and forward has none or a smaller best score; a tie keeps forward) BEFORE any
+// row of these reads is written, then the wave copies the K rows of the reads that switch, lane after lane along the arrays.
+__global__ void __launch_bounds__(256) merge_strands_kernel(u64 n_reads, u32 K, unsigned char *f_nrows, unsigned short *f_branch, float *f_score,
+                                                            double *f_lwr, u32 *f_flags, const unsigned char *r_nrows, const unsigned short *r_branch,
+                                                            const float *r_score, const double *r_lwr, const u32 *r_flags) {
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    for (u64 r0 = wave * 64; r0 < n_reads; r0 += n_waves * 64) {
+        const u64 r = r0 + lane;
+        int take = 0;
+        if (r < n_reads) {
+            const u32 nr = r_nrows[r], nf = f_nrows[r];
+            take = nr > 0 && (nf == 0 || r_score[r * K] > f_score[r * K]);
+        }
+        for (u32 e = lane; e < 64u * K; e += 64) {  // (uniform trip count: the shuffle below is executed by the whole wave)
+            const u32 rr = e / K;
+            const int t = __shfl(take, (int)rr, 64);
+            const u64 g = r0 * K + e;
+            if (t && r0 + rr < n_reads) {
+                f_branch[g] = r_branch[g];
+                f_score[g] = r_score[g];
+                f_lwr[g] = r_lwr[g];
+            }
+        }
+        if (take) {
+            f_nrows[r] = r_nrows[r];
+            f_flags[r] = r_flags[r] | RK_FLAG_REVERSE;
+        }
+    }
+}
+
+// a batch placed from its reverse complement only: every read's result says so
+__global__ void __launch_bounds__(256) mark_reverse_kernel(u32 *flags, u64 n_reads) {
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (u64)gridDim.x * blockDim.x) flags[r] |= RK_FLAG_REVERSE;
+}
+
 }  // namespace rk

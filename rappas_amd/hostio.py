@@ -76,6 +76,40 @@ def notplaced_log(records, unique, placed):
     return "".join(h + "\n" for h in lines)
 
 
+def reversed_log(records, unique, flags):
+    """Text of `reversed_<query>.tsv` (written next to the not-placed log when reads are placed on the reverse or on both strands):
+    the FULL header of every read whose reported result comes from its reverse complement (RK_FLAG_REVERSE, bit 32 of the unique
+    read's flags), one per line, in file order, every occurrence -- the not-placed log's rules."""
+    return notplaced_log(records, unique, (np.asarray(flags) & 32) == 0)
+
+
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+for _a, _b in ("AT", "TA", "UA", "CG", "GC", "RY", "YR", "KM", "MK", "BV", "VB", "DH", "HD"):
+    _COMPLEMENT[ord(_a)] = ord(_b)
+    _COMPLEMENT[ord(_a.lower())] = ord(_b.lower())
+
+
+def revcomp(seq_bytes):
+    """Reverse complement of one DNA read (bytes / str / uint8 array -> the same type), the numpy twin of rk_revcomp_ascii_device:
+    A<->T, U->A, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W, N, '.' and '-' are their own complements; case is kept; every other byte
+    is copied as it is."""
+    if isinstance(seq_bytes, str):
+        return revcomp(seq_bytes.encode("latin-1")).decode("latin-1")
+    if isinstance(seq_bytes, (bytes, bytearray)):
+        return _COMPLEMENT[np.frombuffer(bytes(seq_bytes), np.uint8)[::-1]].tobytes()
+    return _COMPLEMENT[np.asarray(seq_bytes, np.uint8)[::-1]]
+
+
+def revcomp_batch(seq, seq_off):
+    """revcomp of every read of a batch (uint8 concatenation, uint64 offsets [n + 1]) -> uint8 array under the same offsets"""
+    seq = np.asarray(seq, np.uint8)
+    off = np.asarray(seq_off).astype(np.int64)
+    lens = np.diff(off)
+    # output byte i of read r (at off[r] + i) comes from off[r + 1] - 1 - i
+    src = np.repeat(off[1:] - 1 + off[:-1], lens) - np.arange(int(off[-1]) - int(off[0]), dtype=np.int64) - int(off[0])
+    return _COMPLEMENT[seq[src]] if len(src) else np.zeros(0, np.uint8)
+
+
 def pack_batch(seqs):
     """list of str -> (uint8 concatenation, uint64 offsets) as rk_place_batch takes them."""
     off = np.zeros(len(seqs) + 1, np.uint64)

@@ -20,6 +20,15 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _strand(strand):
+    """"forward" | "reverse" | "both" (or the drivers' fwd / rev, or an RK_STRAND_* value) -> RK_STRAND_*"""
+    if isinstance(strand, str):
+        if strand not in _lib.STRANDS:
+            raise ValueError(f"strand must be 'forward', 'reverse' or 'both', not {strand!r}")
+        return _lib.STRANDS[strand]
+    return int(strand)
+
+
 @dataclass
 class Placements:
     """Rows best -> worse per read; unused rows are branch 0xFFFF / score -inf / lwr 0."""
@@ -224,9 +233,12 @@ class PlacementProcess:
         return rk_params(keepAtMost, keepFactor, amb, self.ns_bound)
 
     def processQueries(self, seq, seq_off, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
-                       treatAmbiguitiesWithMax=False, out=None):
+                       treatAmbiguitiesWithMax=False, out=None, strand="forward"):
         """seq: uint8 ASCII of all reads concatenated (no gap stripping, as FASTAPointer(q,false) delivers them);
-        seq_off: uint64 [n+1].  Defaults = src/main_v2/ArgumentsParser_v2.java:87-91.  `out`: a Placements to reuse."""
+        seq_off: uint64 [n+1].  Defaults = src/main_v2/ArgumentsParser_v2.java:87-91.  `out`: a Placements to reuse.
+        strand (DNA databases): "forward" = the reads as given (rk_place_batch, the reference's behaviour), "reverse" = their reverse
+        complements, "both" = per read the strand with the better best score (rk_place_batch_strands; RK_FLAG_REVERSE marks the
+        results that come from the reverse complement)."""
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
         seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
         n = seq_off.shape[0] - 1
@@ -237,8 +249,13 @@ class PlacementProcess:
         res = rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
         p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
         ct = rk_counters()
-        _lib.check(self._lib.rk_place_batch(self.db.handle, C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res),
-                                            C.byref(ct)))
+        st = _strand(strand)
+        if st == _lib.RK_STRAND_FORWARD:
+            _lib.check(self._lib.rk_place_batch(self.db.handle, C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res),
+                                                C.byref(ct)))
+        else:
+            _lib.check(self._lib.rk_place_batch_strands(self.db.handle, C.byref(p), st, n, _ptr(seq), _ptr(seq_off), C.byref(res),
+                                                        C.byref(ct)))
         out.counters = {f: getattr(ct, f) for f, _ in rk_counters._fields_}
         return out
 
@@ -305,7 +322,9 @@ class PlacementProcess:
     # ---- device-resident variant (torch tensors only carry the memory and the stream) ----
     def place_packed(self, packed, fixed_len=0, lens=None, flags_in=None, seq_ascii=None, seq_off=None, out=None,
                      keepAtMost=7, keepFactor=0.01, treatAmbiguities=True, treatAmbiguitiesWithMax=False,
-                     stream=None):
+                     stream=None, strand="forward"):
+        """rk_place_packed_device; with strand "reverse" / "both" rk_place_packed_device_strands, whose device workspace (the
+        reverse records, a second result set, the reversed characters) is a tensor this object owns and grows as batches ask."""
         import torch
         n, wpr = packed.shape
         dev = packed.device
@@ -321,9 +340,43 @@ class PlacementProcess:
         p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
         dp = lambda t: None if t is None else t.data_ptr()
-        _lib.check(self._lib.rk_place_packed_device(self.db.handle, C.byref(p), n, packed.data_ptr(), wpr, dp(lens),
-                                                    fixed_len, dp(flags_in), dp(seq_ascii), dp(seq_off),
-                                                    C.byref(res), C.c_void_p(st)))
+        sd = _strand(strand)
+        if sd == _lib.RK_STRAND_FORWARD:
+            _lib.check(self._lib.rk_place_packed_device(self.db.handle, C.byref(p), n, packed.data_ptr(), wpr, dp(lens),
+                                                        fixed_len, dp(flags_in), dp(seq_ascii), dp(seq_off),
+                                                        C.byref(res), C.c_void_p(st)))
+            return out
+        chars = seq_ascii is not None and seq_off is not None and flags_in is not None
+        need = int(self._lib.rk_strands_work_bytes(self.db.handle, n, wpr, K, max(1, seq_ascii.numel()) if chars else 0))
+        if n and not need:
+            _lib.check(_lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_DNA else _lib.RK_ERR_UNSUPPORTED)
+        work = getattr(self, "_strand_work", None)
+        if work is None or work.device != dev or work.numel() < need:
+            # (grow-only; the old block goes back to the allocator of the stream it was used on, in stream order)
+            work = self._strand_work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _lib.check(self._lib.rk_place_packed_device_strands(self.db.handle, C.byref(p), sd, n, packed.data_ptr(), wpr, dp(lens),
+                                                            fixed_len, dp(flags_in), dp(seq_ascii), dp(seq_off),
+                                                            C.byref(res), work.data_ptr(), work.numel(), C.c_void_p(st)))
+        return out
+
+    def revcomp_packed(self, packed, fixed_len=0, lens=None, stream=None):
+        """rk_revcomp_packed_device: the reverse complement of 2-bit records [n, wpr] (int32 tensor on the database's device) ->
+        a new tensor of the same shape; lengths and flags are the same for both strands."""
+        import torch
+        n, wpr = packed.shape
+        out = torch.empty_like(packed)
+        st = stream if stream is not None else torch.cuda.current_stream(packed.device).cuda_stream
+        _lib.check(self._lib.rk_revcomp_packed_device(self.db.handle, n, packed.data_ptr(), wpr, None if lens is None else lens.data_ptr(),
+                                                      fixed_len, out.data_ptr(), C.c_void_p(st)))
+        return out
+
+    def revcomp_ascii(self, seq_ascii, seq_off, stream=None):
+        """rk_revcomp_ascii_device: every read's characters reversed and complemented (hostio.revcomp is the numpy twin), same offsets."""
+        import torch
+        out = torch.empty_like(seq_ascii)
+        st = stream if stream is not None else torch.cuda.current_stream(seq_ascii.device).cuda_stream
+        _lib.check(self._lib.rk_revcomp_ascii_device(self.db.handle, seq_off.shape[0] - 1, seq_ascii.data_ptr(), seq_off.data_ptr(),
+                                                     out.data_ptr(), C.c_void_p(st)))
         return out
 
     def count_work(self, packed, fixed_len=0, lens=None, flags_in=None, stream=None):

@@ -15,9 +15,11 @@ from ..placement import PhyloKmerDB, PlacementProcess
 
 
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
-               call_string="", device=0, union=False, dbimage=None, save_dbimage=None):
+               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd"):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
-    engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob)"""
+    engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
+    behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
+    reversed_<query>.tsv)"""
     if dbimage is not None:
         from ..placement import db_image_info
         _, blob = db_image_info(dbimage)
@@ -40,11 +42,12 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
         seq, off = hostio.pack_batch([s for _, s in unique])
         res = PlacementProcess(db, ns_bound).processQueries(
             seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
-            treatAmbiguitiesWithMax=(amb == "max"))
+            treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
     finally:
         db.close()
     pl = hostio.jplace_placements(tree, names, res.n_rows, res.branch, res.score, res.lwr, guppy)
     res.notplaced = hostio.notplaced_log(records, unique, (res.flags & 1) != 0)
+    res.reversed = hostio.reversed_log(records, unique, res.flags) if strand != "fwd" else None
     return hostio.jplace_document(tree, pl, call_string, guppy), res
 
 
@@ -61,6 +64,9 @@ def main(argv=None):
     ap.add_argument("--keep-factor", type=float, default=0.01)
     ap.add_argument("--amb", choices=["mean", "max", "skip"], default="mean", help="--ambwithmax / --noamb")
     ap.add_argument("--nsbound", type=float, default=float("-inf"))
+    ap.add_argument("--strand", choices=["fwd", "rev", "both"], default="fwd",
+                    help="DNA: place the reads as given (default, the reference's behaviour), their reverse complements, or both and keep "
+                         "the better strand per read; rev / both also write logs/reversed_<query>.tsv")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--logs", default=None, help="directory of notplaced_<query>.tsv (default: logs/ next to --out, like the reference's workdir/logs)")
@@ -73,13 +79,16 @@ def main(argv=None):
         fasta_text = f.read()
     call = "".join(" " + x for x in (argv if argv is not None else sys.argv[1:]))
     doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
-                          a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage)
+                          a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand)
     with open(a.out, "w") as f:
         f.write(doc)
     logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.out)), "logs")
     os.makedirs(logs, exist_ok=True)
     with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
         f.write(res.notplaced)
+    if res.reversed is not None:
+        with open(os.path.join(logs, "reversed_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
+            f.write(res.reversed)
     placed = int(np.count_nonzero(res.n_rows))
     print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
     return 0
