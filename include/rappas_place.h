@@ -57,7 +57,7 @@ extern "C" {
 #define RK_FLAG_TOO_SHORT 4u      /* R < k : no k-mer (the reference crashes for R < k-1) */
 #define RK_FLAG_AMBIGUOUS 8u      /* read contains an ambiguity character */
 #define RK_FLAG_BELOW_NSBOUND 16u /* best score < ns_bound: no jplace record (PlacementProcess.java:974) */
-#define RK_FLAG_REVERSE 32u       /* the reported result of this read comes from its reverse complement (rk_place_*_strands) */
+#define RK_FLAG_REVERSE 32u       /* the reported result of this read comes from its reverse complement (rk_place_*_strands; *_translated: frames 3..5) */
 #define RK_FLAG_TOO_LONG 64u      /* device pack only: read longer than the packed record; not placed */
 
 /* strand(s) a DNA read is placed on (rk_place_packed_device_strands / rk_place_batch_strands; the reference knows forward only) */
@@ -298,6 +298,67 @@ int rk_place_packed_device_strands(rk_db *db, const rk_params *p, uint32_t stran
                                    uint64_t work_bytes, void *stream);
 int rk_place_batch_strands(rk_db *db, const rk_params *p, uint32_t strand, uint64_t n_reads, const uint8_t *seq_ascii,
                            const uint64_t *seq_off, rk_result *out, rk_counters *counters);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * DNA reads on amino-acid databases: six-frame translation on the device.  The reference places a read as given
+ * (src/core/algos/PlacementProcess.java:645-1025), so a DNA read meets a protein database only after the caller has translated it;
+ * here the 2-bit record is translated on the device, each frame is placed, and the best frame is a per-read merge, as for strands.
+ * Amino-acid databases only: on a DNA handle every entry point below that takes one fails with RK_ERR_UNSUPPORTED and launches
+ * nothing.  These entry points were added without a bump of RK_VERSION (no struct changed).
+ *   Input      2-bit DNA records as rk_pack_reads(RK_ALPHABET_DNA, ...) writes them (A=0 T=1 C=2 G=3, symbol i at bits [2i, 2i+2)),
+ *              their lengths (or fixed_len) and, optionally, the packer's flags.
+ *   Frames     0, 1, 2: the record as given from base offset 0, 1, 2; 3, 4, 5: its reverse complement (state ^ 1,
+ *              src/core/DNAStatesShifted.java:182-209) from offset 0, 1, 2, read straight from the forward record: codon j of frame
+ *              3+o is bases R-1-o-3j, R-2-o-3j, R-3-o-3j, each xor 1.  A frame has floor((R - o) / 3) codons, none when R < o + 3.
+ *   Code       the standard genetic code (NCBI table 1) only; residue states in the order of src/core/AAStates.java:48-197 (R=0 H=1
+ *              K=2 D=3 E=4 S=5 T=6 N=7 Q=8 C=9 G=10 P=11 A=12 I=13 L=14 M=15 F=16 W=17 Y=18 V=19); convert_uo plays no part.
+ *   Stops      the reference reads '*' as a fully ambiguous residue (AAStates.java:103) and a packed record cannot carry ambiguity,
+ *              so a frame's record is its LONGEST STOP-FREE RUN of residues (TAA, TAG, TGA end a run; of runs of equal length the
+ *              first): 5 bits a residue from bit 0, every bit from 5 * len on zero (the packer's padding), len 0 for a frame without
+ *              residues.  A frame shorter than k comes back RK_FLAG_TOO_SHORT from the placement itself.
+ *   Flags      RK_FLAG_BAD_CHAR / RK_FLAG_AMBIGUOUS / RK_FLAG_TOO_LONG of the DNA read are handed to every frame's placement as
+ *              d_flags_in: such reads come back unplaced with the flag set (rk_place_packed_device without characters).  Translating
+ *              ambiguous bases into ambiguous residues is NOT part of this version.  The packer's RK_FLAG_TOO_SHORT speaks of bases,
+ *              not residues, and is dropped.
+ *   rk_translate_packed_device   one frame of every read: records -> d_aa_out [n_reads][aa_words] and d_aa_lens_out [n_reads].
+ *                                aa_words >= rk_packed_words(db, L / 3), L = fixed_len when d_dna_lens is NULL, else the 16 * dna_words
+ *                                bases a record holds (lengths beyond it are cut to it); anything smaller, or frame > 5, is
+ *                                RK_ERR_INVALID.  Words beyond the run are written as zero.
+ *   rk_translate_packed_host     the same words and lengths in plain C++ on the host: no handle, no GPU (the alphabet is implied).
+ *   rk_merge_frames_device       d_best (in/out, with its frame bytes d_best_frame) and d_cand, the result set of frame cand_frame
+ *                                (0..5): per read the candidate is taken if and only if n_rows_c > 0 and (n_rows_best == 0 or
+ *                                score_c[0] > score_best[0] as float32); a tie keeps the earlier frame.  Taking it copies n_rows, all
+ *                                keep_at_most rows of branch / score / lwr and the flags, writes cand_frame into d_best_frame[r] and,
+ *                                for cand_frame >= 3, sets RK_FLAG_REVERSE.
+ *   rk_translated_work_bytes     bytes of caller-owned device workspace rk_place_packed_device_translated needs: one amino-acid
+ *                                record set, one array of lengths, one result set -- frames are processed one after the other, so it
+ *                                does not grow with their number.  0 (and a message) on a bad argument.
+ *   rk_place_packed_device_translated
+ *                                frame 0 is placed straight into d_out, frames 1..5 one at a time into the workspace's result set and
+ *                                merged into d_out; d_frame[r] is the frame the reported result comes from, 0xFF for a read with
+ *                                n_rows == 0.  ns_bound gates each frame on its own.  Six placement passes: a fused kernel is not part
+ *                                of this version.  d_dna_flags may be NULL but must not be d_out->flags.  Allocates nothing; a
+ *                                workspace smaller than rk_translated_work_bytes is RK_ERR_INVALID and nothing is launched.
+ *                                Asynchronous on `stream`; the one-stream rule of rk_place_packed_device holds.
+ *   rk_place_batch_translated    DNA characters from the host: packed there (rk_pack_reads), then the device call, chunk by chunk, in
+ *                                buffers that are part of the handle's host-path block (grow-only, freed by rk_db_destroy); counters
+ *                                are taken from the final flags (too_short: the reported frame has fewer than k residues).  Results
+ *                                equal one rk_place_packed_device_translated call over the whole batch, whatever the chunking.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_FRAME_NONE 0xFFu /* d_frame of a read without a result */
+int rk_translate_packed_device(rk_db *db, uint32_t frame, uint64_t n_reads, const uint32_t *d_dna, uint32_t dna_words,
+                               const uint32_t *d_dna_lens, uint32_t fixed_len, uint32_t *d_aa_out, uint32_t aa_words, uint32_t *d_aa_lens_out,
+                               void *stream);
+int rk_translate_packed_host(uint32_t frame, uint64_t n_reads, const uint32_t *dna, uint32_t dna_words, const uint32_t *dna_lens,
+                             uint32_t fixed_len, uint32_t *aa_out, uint32_t aa_words, uint32_t *aa_lens_out);
+int rk_merge_frames_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_best, uint8_t *d_best_frame,
+                           const rk_result *d_cand, uint32_t cand_frame, void *stream);
+uint64_t rk_translated_work_bytes(const rk_db *db, uint64_t n_reads, uint32_t dna_words, uint32_t keep_at_most);
+int rk_place_packed_device_translated(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *d_dna, uint32_t dna_words,
+                                      const uint32_t *d_dna_lens, uint32_t fixed_len, const uint32_t *d_dna_flags, const rk_result *d_out,
+                                      uint8_t *d_frame, void *d_work, uint64_t work_bytes, void *stream);
+int rk_place_batch_translated(rk_db *db, const rk_params *p, uint64_t n_reads, const uint8_t *seq_ascii, const uint64_t *seq_off,
+                              rk_result *out, uint8_t *frame_out, rk_counters *counters);
 
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the

@@ -11,6 +11,7 @@ RK_AMB_SKIP, RK_AMB_MEAN, RK_AMB_MAX = 0, 1, 2
 RK_TABLE_AUTO, RK_TABLE_HASH, RK_TABLE_DIRECT, RK_TABLE_DIRECT8 = 0, 1, 2, 4
 RK_FLAG_PLACED, RK_FLAG_BAD_CHAR, RK_FLAG_TOO_SHORT, RK_FLAG_AMBIGUOUS, RK_FLAG_BELOW_NSBOUND, RK_FLAG_TOO_LONG = 1, 2, 4, 8, 16, 64
 RK_FLAG_REVERSE = 32
+RK_FRAME_NONE = 0xFF  # d_frame of a read without a result (rk_place_*_translated)
 RK_STRAND_FORWARD, RK_STRAND_REVERSE, RK_STRAND_BOTH = 0, 1, 2
 STRANDS = {"forward": RK_STRAND_FORWARD, "fwd": RK_STRAND_FORWARD, "reverse": RK_STRAND_REVERSE, "rev": RK_STRAND_REVERSE, "both": RK_STRAND_BOTH}
 RK_OK, RK_ERR_INVALID, RK_ERR_NO_DEVICE, RK_ERR_HIP, RK_ERR_NOMEM, RK_ERR_UNSUPPORTED, RK_ERR_IO = 0, -1, -2, -3, -4, -5, -6
@@ -116,6 +117,15 @@ EXPORTS = {
                                                  C.POINTER(rk_result), C.c_void_p, C.c_uint64, C.c_void_p]),
     "rk_place_batch_strands": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.POINTER(rk_result), C.POINTER(rk_counters)]),
+    "rk_translate_packed_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.c_void_p, C.c_void_p]),
+    "rk_translate_packed_host": (C.c_int, [C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rk_merge_frames_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.POINTER(rk_result), C.c_uint32, C.c_void_p]),
+    "rk_translated_work_bytes": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "rk_place_packed_device_translated": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                    C.c_void_p, C.POINTER(rk_result), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rk_place_batch_translated": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(rk_result), C.c_void_p,
+                                            C.POINTER(rk_counters)]),
     "rk_count_work_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_set_lanes_per_read": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rk_kernel_name": (C.c_char_p, [C.c_void_p]),

@@ -737,6 +737,15 @@ inline std::string flagged_log_fast(const FastaScan &sc, const FastDedup &d, con
     return out;
 }
 inline std::string notplaced_log_fast(const FastaScan &sc, const FastDedup &d, const uint32_t *flags) { return flagged_log_fast(sc, d, flags, 1u, 0u); }
+// frames_<query>.tsv of rk_hostio.hpp: frames_log over the scan's records
+inline std::string frames_log_fast(const FastaScan &sc, const FastDedup &d, const uint8_t *frame) {
+    std::string out;
+    for (size_t i = 0; i < sc.recs.size(); i++) {
+        const uint8_t f = frame[d.uniq_of_rec[i]];
+        if (f <= 5) { out.append(sc.recs[i].hdr, sc.recs[i].hdr_len); append_frame(out, f); }
+    }
+    return out;
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // the reference tree as the `user` blob of a database image (rk_db_save): exact, line based

@@ -208,6 +208,24 @@ inline std::string flagged_log(const std::vector<Fasta> &recs, const Dedup &d, c
 // (reversed_<query>.tsv of --strand rev | both follows the same rules with RK_FLAG_REVERSE.)
 inline std::string notplaced_log(const std::vector<Fasta> &recs, const Dedup &d, const uint32_t *flags) { return flagged_log(recs, d, flags, 1u, 0u); }
 
+// frames_<query>.tsv of --translate: `header<TAB>frame` for every record whose unique read has a result (frame byte 0..5; 0xFF =
+// none), in file order, every occurrence; the frame is written +1 +2 +3 (the read as given from base 0, 1, 2) / -1 -2 -3 (its
+// reverse complement)
+inline void append_frame(std::string &out, uint8_t f) {
+    out.push_back('\t');
+    out.push_back(f < 3 ? '+' : '-');
+    out.push_back((char)('1' + f % 3));
+    out.push_back('\n');
+}
+inline std::string frames_log(const std::vector<Fasta> &recs, const Dedup &d, const uint8_t *frame) {
+    std::string out;
+    for (size_t i = 0; i < recs.size(); i++) {
+        const uint8_t f = frame[d.uniq_of_rec[i]];
+        if (f <= 5) { out += recs[i].header; append_frame(out, f); }
+    }
+    return out;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // N1: tree
 // ------------------------------------------------------------------------------------------------------------------

@@ -29,6 +29,9 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                [--threads N] [--md5-dedup] [--classic-io] [--timing] [--save-dbimage DB.rkimg] [--strand fwd|rev|both]\n"
                  "                (--strand, DNA: the reads as given = the reference's behaviour | their reverse complements | both, the better\n"
                  "                 strand per read; rev / both also write logs/reversed_<query>.tsv)\n"
+                 "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
+                 "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
+                 "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
                  "       rk_place (--jsondb DB.json | --uniondb DB.union) --save-dbimage DB.rkimg      (no GPU needed)\n"
                  "       rk_place --emit-tree TREE.nwk | --format-float X | --format-double X | --dedup READS.fa | --md5 TEXT\n";
     return rc;
@@ -37,7 +40,7 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 int main(int argc, char **argv) {
     try {
         std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd";
-        bool logs_given = false, md5_dedup = false, classic = false, timing = false;
+        bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7;
         float keep_factor = 0.01f, nsbound = -INFINITY;
@@ -62,6 +65,7 @@ int main(int argc, char **argv) {
             else if (a == "--keep-factor") keep_factor = std::stof(val());
             else if (a == "--amb") amb = val();
             else if (a == "--strand") strand_name = val();
+            else if (a == "--translate") translate = true;
             else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
             else if (a == "--guppy-compat") guppy = true;
@@ -250,8 +254,18 @@ int main(int argc, char **argv) {
         uint32_t strand;
         if (strand_name == "fwd") strand = RK_STRAND_FORWARD; else if (strand_name == "rev") strand = RK_STRAND_REVERSE; else if (strand_name == "both") strand = RK_STRAND_BOTH;
         else return usage();
+        if (translate && strand != RK_STRAND_FORWARD) {
+            std::cerr << "rk_place: --translate places every read in all six reading frames, both strands included: it cannot be combined with --strand rev | both\n";
+            return 2;
+        }
+        std::vector<uint8_t> frame;  // (--translate only) the reading frame of every unique read's result
         // (fwd is rk_place_batch itself: the reference's behaviour, and this driver's before it knew about strands)
         auto place = [&](rk_db *h, const rk_params *pp, uint64_t m, const uint8_t *sq, const uint64_t *so, rk_result *rs, rk_counters *c) {
+            if (translate) {
+                frame.assign(m, (uint8_t)RK_FRAME_NONE);
+                if (rk_place_batch_translated(h, pp, m, sq, so, rs, frame.data(), c) != RK_OK) throw std::runtime_error(std::string("rk_place_batch_translated: ") + rk_last_error());
+                return;
+            }
             const int rc = strand == RK_STRAND_FORWARD ? rk_place_batch(h, pp, m, sq, so, rs, c) : rk_place_batch_strands(h, pp, strand, m, sq, so, rs, c);
             if (rc != RK_OK) throw std::runtime_error(std::string(strand == RK_STRAND_FORWARD ? "rk_place_batch: " : "rk_place_batch_strands: ") + rk_last_error());
         };
@@ -299,6 +313,12 @@ int main(int argc, char **argv) {
             if (rk_db_create(&d, &db) != RK_OK) throw std::runtime_error(std::string("rk_db_create: ") + rk_last_error());
         }
         struct DbGuard { rk_db *p; ~DbGuard() { if (p) rk_db_destroy(p); } } db_guard{db};
+        if (translate) {
+            rk_db_info info;
+            if (rk_db_get_info(db, &info) != RK_OK) throw std::runtime_error(std::string("rk_db_get_info: ") + rk_last_error());
+            if (info.alphabet != RK_ALPHABET_AA)
+                throw std::runtime_error("--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)");
+        }
         const double t_db = now();
         const uint32_t K = keep_at_most;
         rk_params p{K, keep_factor, amb_mode, nsbound};
@@ -306,6 +326,7 @@ int main(int argc, char **argv) {
         const fs::path log_dir = logs_given ? fs::path(logs) : fs::absolute(fs::path(out)).parent_path() / "logs";
         const std::string notplaced_name = "notplaced_" + fs::path(fasta).filename().string() + ".tsv";
         const std::string reversed_name = "reversed_" + fs::path(fasta).filename().string() + ".tsv";  // (--strand rev | both only)
+        const std::string frames_name = "frames_" + fs::path(fasta).filename().string() + ".tsv";      // (--translate only)
 
         if (!classic) {
             // ---- every host thread on every pass (rk_fastio.hpp) ----
@@ -358,6 +379,11 @@ int main(int argc, char **argv) {
                 if (!rf) throw std::runtime_error("cannot write the reversed log under " + log_dir.string());
                 rf << rkh::flagged_log_fast(sc, dd, flags.data(), RK_FLAG_REVERSE, RK_FLAG_REVERSE);
             }
+            if (translate) {
+                std::ofstream ff(log_dir / frames_name, std::ios::binary);
+                if (!ff) throw std::runtime_error("cannot write the frames log under " + log_dir.string());
+                ff << rkh::frames_log_fast(sc, dd, frame.data());
+            }
             const double t6 = now();
             std::cerr << n << " unique reads, " << ws.placed << " placed -> " << out << "\n";
             if (timing) {  // one JSON line (bench.py's fasta_to_jplace leg reads it): seconds per pass, FASTA bytes in -> jplace bytes out
@@ -406,6 +432,11 @@ int main(int argc, char **argv) {
                 std::ofstream rf(log_dir / reversed_name, std::ios::binary);
                 if (!rf) throw std::runtime_error("cannot write the reversed log under " + log_dir.string());
                 rf << rkh::flagged_log(records, dd, flags.data(), RK_FLAG_REVERSE, RK_FLAG_REVERSE);
+            }
+            if (translate) {
+                std::ofstream ff(log_dir / frames_name, std::ios::binary);
+                if (!ff) throw std::runtime_error("cannot write the frames log under " + log_dir.string());
+                ff << rkh::frames_log(records, dd, frame.data());
             }
         }
         std::cerr << n << " unique reads, " << pl.size() << " placed -> " << out << "\n";

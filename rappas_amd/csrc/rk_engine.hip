@@ -4,6 +4,7 @@
 #include "rk_kernels.hip"
 #include "rk_internal.h"
 #include "rk_pack_host.h"
+#include "rk_translate_host.h"
 #include "rk_plan.h"
 
 #include <cmath>
@@ -416,6 +417,7 @@ unsigned host_threads(uint64_t n_reads, unsigned asked) {
 struct rk_workspace {
     GrowBuf ascii, off, packed, lens, flags, nrows, branch, score, lwr, oflags;
     GrowBuf strands;  // rk_place_batch_strands: the workspace of rk_place_packed_device_strands for a chunk
+    GrowBuf translated, frames;  // rk_place_batch_translated: the workspace of rk_place_packed_device_translated and the frame bytes
     // page-locked staging for callers that hand over pageable memory (a JVM heap array, a numpy array): copies to / from
     // it run on a few host threads, the DMA itself is then asynchronous and overlaps the other workspace's chunk
     PinBuf h_ascii, h_off, h_packed, h_nrows, h_branch, h_score, h_lwr, h_oflags;
@@ -423,7 +425,7 @@ struct rk_workspace {
     uint64_t pend_r0 = 0, pend_n = 0;
     hipStream_t stream = nullptr;
     void release() {
-        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &nrows, &branch, &score, &lwr, &oflags, &strands}) b->release();
+        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &nrows, &branch, &score, &lwr, &oflags, &strands, &translated, &frames}) b->release();
         for (PinBuf *b : {&h_ascii, &h_off, &h_packed, &h_nrows, &h_branch, &h_score, &h_lwr, &h_oflags}) b->release();
         if (stream) (void)hipStreamDestroy(stream);
         stream = nullptr;
@@ -2231,6 +2233,147 @@ extern "C" int rk_place_packed_device_strands(rk_db *db, const rk_params *p, uin
     return rk_merge_strands_device(db, p->keep_at_most, n_reads, d_out, &rres, s);
 }
 
+// ------------------------------------------------------------------------------------------------
+// DNA reads on an amino-acid database: one reading frame of packed DNA records translated on the device, the per-read
+// merge of a frame's result set into the best so far, and rk_place_packed_device composed over the six frames.  Six placement passes,
+// one after the other through one record set; nothing here touches a placement kernel or the launch plan.
+// ------------------------------------------------------------------------------------------------
+static int translated_handle(const rk_db *db, const char *who) {
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (db->info.alphabet != RK_ALPHABET_AA) return fail(RK_ERR_UNSUPPORTED, "%s: translated placement needs an amino-acid database (this one holds DNA)", who);
+    return RK_OK;
+}
+
+// 32-bit words of the amino-acid record of a frame of `bases` bases (rk_packed_words of an amino-acid handle)
+static uint32_t translated_words(uint64_t bases) {
+    const uint64_t w = (bases / 3 * 5 + 31) / 32;
+    return w ? (uint32_t)w : 1u;
+}
+
+// the argument tests the device and the host translation share; 0x7FFFFFFF / 16 words: 16 * dna_words must not wrap
+static int translate_args(const char *who, uint32_t frame, const void *dna, uint32_t dna_words, const void *dna_lens, uint32_t fixed_len, const void *aa,
+                          uint32_t aa_words, const void *aa_lens) {
+    if (frame > 5) return fail(RK_ERR_INVALID, "%s: frame=%u (0..2 as given, 3..5 the reverse complement)", who, frame);
+    if (!dna || !aa || !aa_lens || dna_words == 0 || dna_words > 0x7FFFFFFu) return fail(RK_ERR_INVALID, "%s: null/zero argument", who);
+    if (!dna_lens && (uint64_t)fixed_len * 2 > (uint64_t)dna_words * 32) return fail(RK_ERR_INVALID, "%s: fixed_len=%u does not fit %u words", who, fixed_len, dna_words);
+    const uint32_t need = translated_words(dna_lens ? (uint64_t)dna_words * 16 : fixed_len);
+    if (aa_words < need) return fail(RK_ERR_INVALID, "%s: aa_words=%u, %u needed for the longest frame of these records", who, aa_words, need);
+    return RK_OK;
+}
+
+extern "C" int rk_translate_packed_device(rk_db *db, uint32_t frame, uint64_t n_reads, const uint32_t *d_dna, uint32_t dna_words,
+                                          const uint32_t *d_dna_lens, uint32_t fixed_len, uint32_t *d_aa_out, uint32_t aa_words,
+                                          uint32_t *d_aa_lens_out, void *stream) {
+    int rc = translated_handle(db, "rk_translate_packed_device");
+    if (rc) return rc;
+    if (n_reads == 0) return frame > 5 ? fail(RK_ERR_INVALID, "rk_translate_packed_device: frame=%u", frame) : RK_OK;
+    rc = translate_args("rk_translate_packed_device", frame, d_dna, dna_words, d_dna_lens, fixed_len, d_aa_out, aa_words, d_aa_lens_out);
+    if (rc) return rc;
+    if ((const void *)d_dna == (const void *)d_aa_out) return fail(RK_ERR_INVALID, "rk_translate_packed_device: the output must not alias the input");
+    HIP_TRY(hipSetDevice(db->info.device));
+    hipLaunchKernelGGL(translate_frame_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, (hipStream_t)stream, d_dna, (u64)n_reads, dna_words, d_dna_lens,
+                       fixed_len, frame, d_aa_out, aa_words, d_aa_lens_out);
+    HIP_TRY(hipGetLastError());
+    return RK_OK;
+}
+
+extern "C" int rk_translate_packed_host(uint32_t frame, uint64_t n_reads, const uint32_t *dna, uint32_t dna_words, const uint32_t *dna_lens,
+                                        uint32_t fixed_len, uint32_t *aa_out, uint32_t aa_words, uint32_t *aa_lens_out) {
+    if (n_reads == 0) return frame > 5 ? fail(RK_ERR_INVALID, "rk_translate_packed_host: frame=%u", frame) : RK_OK;
+    int rc = translate_args("rk_translate_packed_host", frame, dna, dna_words, dna_lens, fixed_len, aa_out, aa_words, aa_lens_out);
+    if (rc) return rc;
+    rk::translate_range(frame, dna, dna_words, dna_lens, fixed_len, 0, n_reads, aa_out, aa_words, aa_lens_out);
+    return RK_OK;
+}
+
+extern "C" int rk_merge_frames_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_best, uint8_t *d_best_frame,
+                                      const rk_result *d_cand, uint32_t cand_frame, void *stream) {
+    int rc = translated_handle(db, "rk_merge_frames_device");
+    if (rc) return rc;
+    if (keep_at_most < 1 || keep_at_most > 16) return fail(RK_ERR_INVALID, "keep_at_most=%u outside 1..16", keep_at_most);
+    if (cand_frame > 5) return fail(RK_ERR_INVALID, "rk_merge_frames_device: cand_frame=%u outside 0..5", cand_frame);
+    if (n_reads == 0) return RK_OK;
+    if (!result_complete(d_best) || !result_complete(d_cand) || !d_best_frame) return fail(RK_ERR_INVALID, "rk_merge_frames_device: null result array");
+    HIP_TRY(hipSetDevice(db->info.device));
+    hipLaunchKernelGGL(merge_frames_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, (hipStream_t)stream, (u64)n_reads, keep_at_most, d_best->n_rows,
+                       d_best->branch, d_best->score, d_best->lwr, d_best->flags, d_best_frame, (const unsigned char *)d_cand->n_rows,
+                       (const unsigned short *)d_cand->branch, (const float *)d_cand->score, (const double *)d_cand->lwr, (const uint32_t *)d_cand->flags,
+                       cand_frame);
+    HIP_TRY(hipGetLastError());
+    return RK_OK;
+}
+
+// The workspace of rk_place_packed_device_translated: amino-acid records of one frame | their lengths | one result set (n_rows,
+// branch, score, lwr, flags); every part starts on a 256-byte boundary of the block.
+struct TranslatedWork {
+    uint32_t aa_words;
+    uint64_t rec, lens, nrows, branch, score, lwr, flags, total;  // byte offsets
+};
+static TranslatedWork translated_work(uint64_t n, uint32_t dna_words, uint32_t K) {
+    auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
+    TranslatedWork w{};
+    w.aa_words = translated_words((uint64_t)dna_words * 16);
+    w.rec = 0;
+    w.lens = up(n * w.aa_words * 4);
+    w.nrows = w.lens + up(n * 4);
+    w.branch = w.nrows + up(n);
+    w.score = w.branch + up(n * K * 2);
+    w.lwr = w.score + up(n * K * 4);
+    w.flags = w.lwr + up(n * K * 8);
+    w.total = w.flags + up(n * 4);
+    return w;
+}
+
+extern "C" uint64_t rk_translated_work_bytes(const rk_db *db, uint64_t n_reads, uint32_t dna_words, uint32_t keep_at_most) {
+    if (translated_handle(db, "rk_translated_work_bytes")) return 0;
+    if (dna_words == 0 || dna_words > 0x7FFFFFFu || keep_at_most < 1 || keep_at_most > 16) { (void)fail(RK_ERR_INVALID, "rk_translated_work_bytes: dna_words=%u, keep_at_most=%u", dna_words, keep_at_most); return 0; }
+    if (n_reads >= (1ull << 32)) { (void)fail(RK_ERR_INVALID, "rk_translated_work_bytes: n_reads too large"); return 0; }
+    return translated_work(n_reads, dna_words, keep_at_most).total;
+}
+
+extern "C" int rk_place_packed_device_translated(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *d_dna, uint32_t dna_words,
+                                                 const uint32_t *d_dna_lens, uint32_t fixed_len, const uint32_t *d_dna_flags, const rk_result *d_out,
+                                                 uint8_t *d_frame, void *d_work, uint64_t work_bytes, void *stream) {
+    const char *who = "rk_place_packed_device_translated";
+    int rc = translated_handle(db, who);
+    if (rc) return rc;
+    // every test the calls below would make, before the first launch: an error leaves the caller's arrays as they are
+    if (!d_out) return fail(RK_ERR_INVALID, "%s: null argument", who);
+    rc = check_params(p);
+    if (rc) return rc;
+    if (n_reads == 0) return RK_OK;
+    if (!d_dna || dna_words == 0 || dna_words > 0x7FFFFFFu) return fail(RK_ERR_INVALID, "%s: null packed reads", who);
+    if (!result_complete(d_out) || !d_frame) return fail(RK_ERR_INVALID, "%s: null result array", who);
+    if (!d_dna_lens && (uint64_t)fixed_len * 2 > (uint64_t)dna_words * 32) return fail(RK_ERR_INVALID, "%s: fixed_len=%u does not fit %u words", who, fixed_len, dna_words);
+    if (d_dna_flags && d_dna_flags == d_out->flags) return fail(RK_ERR_INVALID, "%s: d_dna_flags must not be the output flag array (every frame reads it)", who);
+    if (n_reads >= (1ull << 32)) return fail(RK_ERR_INVALID, "%s: n_reads too large", who);
+    const TranslatedWork L = translated_work(n_reads, dna_words, p->keep_at_most);
+    if (!d_work || work_bytes < L.total)
+        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_translated_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0),
+                    (unsigned long long)L.total);
+    HIP_TRY(hipSetDevice(db->info.device));
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)d_work;
+    uint32_t *aa = (uint32_t *)(base + L.rec), *aa_lens = (uint32_t *)(base + L.lens);
+    const rk_result cres{(uint8_t *)(base + L.nrows), (uint16_t *)(base + L.branch), (float *)(base + L.score), (double *)(base + L.lwr), (uint32_t *)(base + L.flags)};
+    for (uint32_t f = 0; f < 6; f++) {
+        rc = rk_translate_packed_device(db, f, n_reads, d_dna, dna_words, d_dna_lens, fixed_len, aa, L.aa_words, aa_lens, s);
+        if (rc) return rc;
+        // (the placement kernels take BAD_CHAR / AMBIGUOUS / TOO_LONG from d_flags_in and nothing else: the DNA packer's TOO_SHORT,
+        //  which speaks of bases, ends here; TOO_SHORT of the result is the frame's own, R < k residues)
+        rc = rk_place_packed_device(db, p, n_reads, aa, L.aa_words, aa_lens, 0, d_dna_flags, nullptr, nullptr, f == 0 ? d_out : &cres, s);
+        if (rc) return rc;
+        if (f == 0) {
+            hipLaunchKernelGGL(init_frame_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, s, (const unsigned char *)d_out->n_rows, d_frame, (u64)n_reads);
+            HIP_TRY(hipGetLastError());
+        } else {
+            rc = rk_merge_frames_device(db, p->keep_at_most, n_reads, d_out, d_frame, &cres, f, s);
+            if (rc) return rc;
+        }
+    }
+    return RK_OK;
+}
+
 // rk_count_work_device: the work a batch asks of the database (count_work_kernel), for callers that want the reference's own
 // diagnostics -- k-mers looked up, k-mers found, row entries walked -- next to the placements.  Opt-in and separate: the placement
 // kernels carry no counters.
@@ -2784,6 +2927,80 @@ extern "C" int rk_pack_reads(uint32_t alphabet, int convert_uo, uint32_t k, uint
     return pack_reads_threads(pack_spec(A, alphabet, alphabet == RK_ALPHABET_DNA ? 2u : 5u, k, words_per_read), n_reads, seq_ascii, seq_off, packed,
                               lens, flags, n_threads);
     RK_GUARD_END("rk_pack_reads")
+}
+
+// DNA characters from the host onto an amino-acid database: packed here (rk_pack_reads), then rk_place_packed_device_translated chunk
+// by chunk through the first workspace of the handle's host path.  One chunk in flight -- six placement passes a chunk are the cost,
+// not the copies around them.
+extern "C" int rk_place_batch_translated(rk_db *db, const rk_params *p, uint64_t n_reads, const uint8_t *seq_ascii, const uint64_t *seq_off,
+                                         rk_result *out, uint8_t *frame_out, rk_counters *counters) {
+    const char *who = "rk_place_batch_translated";
+    int rc = translated_handle(db, who);
+    if (rc) return rc;
+    if (!out) return fail(RK_ERR_INVALID, "%s: null argument", who);
+    rc = check_params(p);
+    if (rc) return rc;
+    if (n_reads && (!seq_ascii || !seq_off)) return fail(RK_ERR_INVALID, "%s: null reads", who);
+    RK_GUARD_BEGIN
+    rk_counters ct{};
+    if (n_reads == 0) { if (counters) *counters = ct; return RK_OK; }
+    if (!out->n_rows || !out->branch || !out->score || !out->lwr || !out->flags || !frame_out) return fail(RK_ERR_INVALID, "%s: null result array", who);
+    uint64_t max_len = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        if (seq_off[r + 1] < seq_off[r]) return fail(RK_ERR_INVALID, "%s: seq_off not monotone at read %llu", who, (unsigned long long)r);
+        max_len = std::max(max_len, seq_off[r + 1] - seq_off[r]);
+    }
+    if (max_len > 0x7FFFFFFFull / 8) return fail(RK_ERR_UNSUPPORTED, "%s: read longer than 2^28 symbols", who);
+    const uint32_t dna_words = (uint32_t)std::max<uint64_t>(1, (max_len * 2 + 31) / 32);  // one record width for the whole batch
+    const uint32_t K = p->keep_at_most;
+    uint64_t max_chunk_reads = 1ull << 18;  // (place_host's chunk)
+    if (const char *e = rk_knob("RK_CHUNK_READS")) {  // developer knob
+        const long v = atol(e);
+        if (v >= 1024) max_chunk_reads = (uint64_t)v;
+    }
+    std::lock_guard<std::mutex> lock(db->host_mutex);  // the workspaces belong to the db: one host call at a time
+    HIP_TRY(hipSetDevice(db->info.device));
+    rk_workspace &w = db->ws[0];
+    if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    hipStream_t s = w.stream;
+    std::vector<uint32_t> h_packed, h_lens, h_flags;
+    for (uint64_t r0 = 0; r0 < n_reads; r0 += max_chunk_reads) {
+        const uint64_t n = std::min(max_chunk_reads, n_reads - r0);
+        h_packed.resize(n * dna_words); h_lens.resize(n); h_flags.resize(n);
+        rc = rk_pack_reads(RK_ALPHABET_DNA, 0, 1, n, seq_ascii, seq_off + r0, dna_words, h_packed.data(), h_lens.data(), h_flags.data(), 0);
+        if (rc) return rc;
+        const uint64_t wb = rk_translated_work_bytes(db, n, dna_words, K);
+        if (!wb) return RK_ERR_INVALID;
+        if ((rc = w.packed.reserve(n * dna_words * 4)) || (rc = w.lens.reserve(n * 4)) || (rc = w.flags.reserve(n * 4)) || (rc = w.nrows.reserve(n)) ||
+            (rc = w.branch.reserve(n * K * 2)) || (rc = w.score.reserve(n * K * 4)) || (rc = w.lwr.reserve(n * K * 8)) || (rc = w.oflags.reserve(n * 4)) ||
+            (rc = w.frames.reserve(n)) || (rc = w.translated.reserve(wb)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(w.packed.p, h_packed.data(), n * dna_words * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.lens.p, h_lens.data(), n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(w.flags.p, h_flags.data(), n * 4, hipMemcpyHostToDevice, s));
+        const rk_result dres{w.nrows.as<uint8_t>(), w.branch.as<uint16_t>(), w.score.as<float>(), w.lwr.as<double>(), w.oflags.as<uint32_t>()};
+        rc = rk_place_packed_device_translated(db, p, n, w.packed.as<uint32_t>(), dna_words, w.lens.as<uint32_t>(), 0, w.flags.as<uint32_t>(), &dres,
+                                               w.frames.as<uint8_t>(), w.translated.p, wb, s);
+        if (rc) { (void)hipStreamSynchronize(s); return rc; }
+        HIP_TRY(hipMemcpyAsync(out->n_rows + r0, w.nrows.p, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out->branch + r0 * K, w.branch.p, n * K * 2, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out->score + r0 * K, w.score.p, n * K * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out->lwr + r0 * K, w.lwr.p, n * K * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out->flags + r0, w.oflags.p, n * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(frame_out + r0, w.frames.p, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));  // (the host vectors are packed again for the next chunk)
+        for (uint64_t r = r0; r < r0 + n; r++) {
+            const uint32_t f = out->flags[r];
+            ct.reads++;
+            if (f & RK_FLAG_PLACED) ct.placed++; else ct.unplaced++;
+            if (f & RK_FLAG_BAD_CHAR) ct.bad_char++;
+            if (f & RK_FLAG_TOO_SHORT) ct.too_short++;
+            if (f & RK_FLAG_AMBIGUOUS) ct.ambiguous++;
+        }
+    }
+    if (counters) *counters = ct;
+    return RK_OK;
+    RK_GUARD_END("rk_place_batch_translated")
 }
 
 #include "rk_synth_impl.h"

@@ -19,6 +19,7 @@
 // No MFMA: this is a gather/accumulate bounded by the memory system, not a contraction.
 #include "rk_device.h"
 #include "rk_slots24.h"
+#include "rk_translate.h"
 
 #include <type_traits>
 #ifndef RK_ROW_NT
@@ -4336,6 +4337,114 @@ __global__ void __launch_bounds__(256) merge_strands_kernel(u64 n_reads, u32 K, 
 // a batch placed from its reverse complement only: every read's result says so
 __global__ void __launch_bounds__(256) mark_reverse_kernel(u32 *flags, u64 n_reads) {
     for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (u64)gridDim.x * blockDim.x) flags[r] |= RK_FLAG_REVERSE;
+}
+
+// ------------------------------------------------------------------------------------------------
+// DNA reads on an amino-acid database: one reading frame of a 2-bit record -> a 5-bit record.  The reference places a
+// read as given; nothing of it stands behind these kernels beyond the two alphabets (DNAStatesShifted.java:182-209, AAStates.java:48-197).
+//
+// translate_frame_kernel: a lane per read.  What a lane writes depends on the whole read -- the record of a frame is its longest
+// stop-free run of residues, the first of equal ones -- so a thread per output word would scan all of the read's codons once per word
+// (16 times for 300 bases); a lane scans them once, keeps (start, length) of the best run, then walks that run again and packs it.
+// A codon is six consecutive bits of the record: two words and one 32-bit funnel shift (v_alignbit_b32), then a byte of the LDS table.
+// Forward frames take the six bits at base o + 3j as the table index.  Reverse frames take the six bits at base R-3-o-3j: the codon's
+// bases in reverse order, uncomplemented -- the table of these frames is filled through the permutation (swap the outer pairs, xor
+// 0b010101), so no reverse record is made and the loop is the same.  Residues are appended to a 32-bit word with 32-bit shifts and
+// a carry word (5-bit residues straddle words; no 64-bit shift by a per-lane count).
+// ------------------------------------------------------------------------------------------------
+__device__ const unsigned char codon_table[64] = RK_CODON_TABLE;
+
+__global__ void __launch_bounds__(256) translate_frame_kernel(const u32 *dna, u64 n_reads, u32 dna_words, const u32 *lens, u32 fixed_len, u32 frame,
+                                                              u32 *aa, u32 aa_words, u32 *aa_lens) {
+    __shared__ unsigned char tab[64];
+    const bool rev = frame >= 3u;
+    if (threadIdx.x < 64u) {
+        u32 x = threadIdx.x;
+        if (rev) x = (((x & 3u) << 4) | (x & 12u) | (x >> 4)) ^ 21u;
+        tab[threadIdx.x] = codon_table[x];
+    }
+    __syncthreads();
+    const u32 o = rev ? frame - 3u : frame;
+    const u32 cap = dna_words * 16u;
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (u64)gridDim.x * blockDim.x) {
+        u32 R = lens ? lens[r] : fixed_len;
+        R = R < cap ? R : cap;  // never read past the packed record
+        const u32 n_codons = R >= o + 3u ? (R - o) / 3u : 0u;
+        const u32 *rec = dna + r * dna_words;
+        // residue state (or RK_CODON_STOP) of codon j < n_codons: its lowest base is o + 3j (forward) / R-3-o-3j (reverse), >= 0 and
+        // <= R - 3, so the six bits end at or below bit 2R <= 32 * dna_words: word wi exists, word wi + 1 is needed only if it does
+        auto residue = [&](u32 j) -> u32 {
+            const u32 base = rev ? R - 3u - o - 3u * j : o + 3u * j;
+            const u32 bit = 2u * base, wi = bit >> 5, sh = bit & 31u;
+            const u32 w0 = rec[wi];
+            const u32 w1 = rec[wi + 1u < dna_words ? wi + 1u : wi];  // (wi + 1 == dna_words only with sh <= 26: its bits are not used)
+            return tab[__builtin_amdgcn_alignbit(w1, w0, sh) & 63u];
+        };
+        u32 best_s = 0, best_l = 0, cur_s = 0;
+        for (u32 j = 0; j < n_codons; j++) {
+            if (residue(j) == RK_CODON_STOP) {
+                const u32 l = j - cur_s;
+                if (l > best_l) { best_l = l; best_s = cur_s; }  // (a tie keeps the first run)
+                cur_s = j + 1u;
+            }
+        }
+        if (n_codons - cur_s > best_l) { best_l = n_codons - cur_s; best_s = cur_s; }  // (cur_s <= n_codons)
+        u32 *out = aa + r * aa_words;
+        u32 w = 0, lo = 0, have = 0;
+        for (u32 i = 0; i < best_l; i++) {
+            const u32 st = residue(best_s + i);
+            lo |= st << have;  // have < 32
+            have += 5u;
+            if (have >= 32u) {
+                if (w < aa_words) out[w] = lo;
+                w++;
+                have -= 32u;
+                lo = st >> (5u - have);  // the bits of st that did not fit (have <= 4: a shift by 1 .. 5; by 5 leaves none)
+            }
+        }
+        for (; w < aa_words; w++, lo = 0) out[w] = lo;  // the last, partial word, then the padding
+        aa_lens[r] = best_l;
+    }
+}
+
+// frame 0's results are the first `best`: its frame byte is 0 where it has rows, RK_FRAME_NONE elsewhere
+__global__ void __launch_bounds__(256) init_frame_kernel(const unsigned char *nrows, unsigned char *frame, u64 n_reads) {
+    for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (u64)gridDim.x * blockDim.x) frame[r] = nrows[r] ? 0 : (unsigned char)RK_FRAME_NONE;
+}
+
+// merge_frames_kernel: merge_strands_kernel with a frame id -- per read the candidate frame's result replaces the best so far iff it
+// has rows and the best has none or a smaller best score (a tie keeps the earlier frame); the read's frame byte says where its
+// result comes from, and frames 3..5 are the reverse strand.  The same order of work: a wave decides its 64 reads before it writes.
+__global__ void __launch_bounds__(256) merge_frames_kernel(u64 n_reads, u32 K, unsigned char *b_nrows, unsigned short *b_branch, float *b_score,
+                                                           double *b_lwr, u32 *b_flags, unsigned char *b_frame, const unsigned char *c_nrows,
+                                                           const unsigned short *c_branch, const float *c_score, const double *c_lwr,
+                                                           const u32 *c_flags, u32 cand_frame) {
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    const u32 mark = cand_frame >= 3u ? RK_FLAG_REVERSE : 0u;
+    for (u64 r0 = wave * 64; r0 < n_reads; r0 += n_waves * 64) {
+        const u64 r = r0 + lane;
+        int take = 0;
+        if (r < n_reads) {
+            const u32 nc = c_nrows[r], nb = b_nrows[r];
+            take = nc > 0 && (nb == 0 || c_score[r * K] > b_score[r * K]);
+        }
+        for (u32 e = lane; e < 64u * K; e += 64) {  // (uniform trip count: the shuffle below is executed by the whole wave)
+            const u32 rr = e / K;
+            const int t = __shfl(take, (int)rr, 64);
+            const u64 g = r0 * K + e;
+            if (t && r0 + rr < n_reads) {
+                b_branch[g] = c_branch[g];
+                b_score[g] = c_score[g];
+                b_lwr[g] = c_lwr[g];
+            }
+        }
+        if (take) {
+            b_nrows[r] = c_nrows[r];
+            b_flags[r] = c_flags[r] | mark;
+            b_frame[r] = (unsigned char)cand_frame;
+        }
+    }
 }
 
 }  // namespace rk

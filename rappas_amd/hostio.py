@@ -83,6 +83,78 @@ def reversed_log(records, unique, flags):
     return notplaced_log(records, unique, (np.asarray(flags) & 32) == 0)
 
 
+def frames_log(records, unique, frame):
+    """Text of `frames_<query>.tsv` (written next to the not-placed log by --translate): one line `header<TAB>frame` for every read
+    with a jplace record, in file order, every occurrence (a duplicate follows its representative, the reversed log's rules).
+    `frame[i]`: the reading frame unique read i's result comes from (0..5, 0xFF = none), written +1 +2 +3 for the read as given
+    from base 0, 1, 2 and -1 -2 -3 for its reverse complement."""
+    index = {hashlib.md5(seq.replace("-", "").encode()).digest(): i for i, (_, seq) in enumerate(unique)}
+    out = []
+    for header, seq in records:
+        f = int(frame[index[hashlib.md5(seq.replace("-", "").encode()).digest()]])
+        if f <= 5:
+            out.append(f"{header}\t{'+' if f < 3 else '-'}{f % 3 + 1}\n")
+    return "".join(out)
+
+
+# The standard genetic code (NCBI table 1) over the engine's states: index = b0 | b1 << 2 | b2 << 4 with A=0 T=1 C=2 G=3, value =
+# residue state in the order R H K D E S T N Q C G P A I L M F W Y V, 31 = stop.  Spelled from the textbook TCAG table here (the
+# engine holds the same table as numbers, rappas_amd/csrc/rk_translate.h).
+CODON_STOP = 31
+_AA_ORDER = "RHKDESTNQCGPAILMFWYV"
+_TCAG_TABLE = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
+CODON_TABLE = np.zeros(64, np.uint8)
+for _i, _aa in enumerate(_TCAG_TABLE):
+    _b = ["ATCG".index("TCAG"[(_i >> s) & 3]) for s in (4, 2, 0)]
+    CODON_TABLE[_b[0] | _b[1] << 2 | _b[2] << 4] = CODON_STOP if _aa == "*" else _AA_ORDER.index(_aa)
+
+
+def translate_frames(dna, lens=None, fixed_len=0, aa_words=None):
+    """The numpy twin of rk_translate_packed_device over all six reading frames: 2-bit DNA records u32 [n, dna_words] (A=0 T=1 C=2
+    G=3, base i at bits [2i, 2i+2)) -> (aa u32 [6, n, aa_words], aa_lens u32 [6, n]).  Frame f < 3 reads the record from base f,
+    frame 3 + o its reverse complement (base i of that = base R-1-i, state ^ 1) from base o; per read and frame the longest stop-free
+    run of residues (the first of equal ones), 5 bits a residue from bit 0, zero beyond."""
+    dna = np.ascontiguousarray(dna, dtype=np.uint32)
+    n, dna_words = dna.shape
+    cap = dna_words * 16
+    R = np.minimum(np.asarray(lens, np.int64), cap) if lens is not None else np.full(n, min(int(fixed_len), cap), np.int64)
+    if aa_words is None:
+        aa_words = max(1, ((cap if lens is not None else int(fixed_len)) // 3 * 5 + 31) // 32)
+    pos = np.arange(cap)
+    states = ((dna[:, pos >> 4] >> (2 * (pos & 15)).astype(np.uint32)) & 3).astype(np.int64)  # [n, cap]
+    aa = np.zeros((6, n, aa_words), np.uint32)
+    aa_lens = np.zeros((6, n), np.uint32)
+    rows = np.arange(n)
+    max_codons = cap // 3
+    for f in range(6):
+        o = f % 3
+        n_codons = np.where(R >= o + 3, (R - o) // 3, 0)
+        j = np.arange(max_codons)
+        code = np.zeros((n, max_codons), np.int64)
+        for t in range(3):
+            i = o + 3 * j[None, :] + t  # base of the frame's strand
+            src = i if f < 3 else R[:, None] - 1 - i
+            b = states[rows[:, None], np.clip(src, 0, max(cap - 1, 0))] if cap else np.zeros((n, max_codons), np.int64)
+            code |= (b ^ (1 if f >= 3 else 0)) << (2 * t)
+        res = CODON_TABLE[code].astype(np.int64)
+        ok = (j[None, :] < n_codons[:, None]) & (res != CODON_STOP)
+        run = np.zeros((n, max_codons + 1), np.int64)  # run[:, j + 1] = residues of the stop-free run that ends at codon j
+        for c in range(max_codons):
+            run[:, c + 1] = np.where(ok[:, c], run[:, c] + 1, 0)
+        end = np.argmax(run, axis=1)  # (the first maximum: of runs of equal length the first)
+        length = run[rows, end]
+        start = end - length
+        for i in range(int(length.max()) if n else 0):
+            st = np.where(i < length, res[rows, np.minimum(start + i, max(max_codons - 1, 0))], 0).astype(np.uint64)
+            w, sh = (5 * i) >> 5, (5 * i) & 31
+            if w < aa_words:
+                aa[f, :, w] |= ((st << np.uint64(sh)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+            if sh > 27 and w + 1 < aa_words:
+                aa[f, :, w + 1] |= (st >> np.uint64(32 - sh)).astype(np.uint32)
+        aa_lens[f] = length
+    return aa, aa_lens
+
+
 _COMPLEMENT = np.arange(256, dtype=np.uint8)
 for _a, _b in ("AT", "TA", "UA", "CG", "GC", "RY", "YR", "KM", "MK", "BV", "VB", "DH", "HD"):
     _COMPLEMENT[ord(_a)] = ord(_b)

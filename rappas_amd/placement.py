@@ -38,6 +38,7 @@ class Placements:
     lwr: np.ndarray      # f64 [n, K]
     flags: np.ndarray    # u32 [n]
     counters: dict
+    frame: np.ndarray = None  # u8 [n], processQueriesTranslated only: the reading frame of the result (0..5, 0xFF = none)
 
 
 def pack_reads(alphabet, k, seq, seq_off, words_per_read=None, convert_uo=False, threads=0):
@@ -56,6 +57,29 @@ def pack_reads(alphabet, k, seq, seq_off, words_per_read=None, convert_uo=False,
     flags = np.zeros(n, np.uint32)
     _lib.check(lib.rk_pack_reads(alphabet, int(bool(convert_uo)), k, n, _ptr(seq), _ptr(seq_off), words_per_read, _ptr(packed), _ptr(lens), _ptr(flags), threads))
     return packed, lens, flags
+
+
+def translated_words(dna_len):
+    """32-bit words of the amino-acid record of one reading frame of a DNA read of dna_len bases (5 bits a residue)"""
+    return max(1, (dna_len // 3 * 5 + 31) // 32)
+
+
+def translate_packed_host(dna, frame, lens=None, fixed_len=0, aa_words=None):
+    """rk_translate_packed_host (no GPU): reading frame `frame` (0..2 the read as given from base 0, 1, 2; 3..5 its reverse complement)
+    of 2-bit DNA records u32 [n, dna_words] -> (aa u32 [n, aa_words], aa_lens u32 [n]): per read the longest stop-free run of
+    residues under the standard genetic code, 5 bits a residue -- the records the device kernel writes."""
+    lib = _lib.load()
+    dna = np.ascontiguousarray(dna, dtype=np.uint32)
+    n, dna_words = dna.shape
+    if lens is not None:
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    if aa_words is None:
+        aa_words = translated_words(dna_words * 16 if lens is not None else fixed_len)
+    aa = np.zeros((n, aa_words), np.uint32)
+    aa_lens = np.zeros(n, np.uint32)
+    _lib.check(lib.rk_translate_packed_host(frame, n, _ptr(dna), dna_words, None if lens is None else _ptr(lens), fixed_len, _ptr(aa), aa_words,
+                                            _ptr(aa_lens)))
+    return aa, aa_lens
 
 
 def host_alloc(shape, dtype):
@@ -259,6 +283,28 @@ class PlacementProcess:
         out.counters = {f: getattr(ct, f) for f, _ in rk_counters._fields_}
         return out
 
+    def processQueriesTranslated(self, seq, seq_off, keepAtMost=7, keepFactor=0.01, out=None):
+        """rk_place_batch_translated (amino-acid databases): DNA reads as characters, every read translated in its six reading frames
+        on the device and placed on the database; per read the frame with the best score is reported.  Returns a Placements with one
+        more array, `frame` (u8 [n]: 0..2 forward from base 0, 1, 2; 3..5 the reverse complement; 0xFF = no result).  Reads with an
+        ambiguity code or an unsupported character come back unplaced with their flag."""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+        n = seq_off.shape[0] - 1
+        K = keepAtMost
+        if out is None:
+            out = Placements(np.zeros(n, np.uint8), np.zeros((n, K), np.uint16), np.zeros((n, K), np.float32),
+                             np.zeros((n, K), np.float64), np.zeros(n, np.uint32), {})
+        if getattr(out, "frame", None) is None or out.frame.shape != (n,):
+            out.frame = np.full(n, _lib.RK_FRAME_NONE, np.uint8)
+        res = rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
+        p = self._params(keepAtMost, keepFactor, True, False)
+        ct = rk_counters()
+        _lib.check(self._lib.rk_place_batch_translated(self.db.handle, C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res), _ptr(out.frame),
+                                                       C.byref(ct)))
+        out.counters = {f: getattr(ct, f) for f, _ in rk_counters._fields_}
+        return out
+
     def pack_reads_host(self, seq, seq_off, max_len=None, threads=0, out=None):
         """rk_pack_reads_host: ASCII reads -> (packed u32 [n, wpr], lens u32 [n], flags u32 [n]) on the host, the records the
         device packer would produce (AmbigSequenceKnife.java:103-130 char -> state).  `out` = (packed, lens, flags) to reuse."""
@@ -358,6 +404,54 @@ class PlacementProcess:
                                                             fixed_len, dp(flags_in), dp(seq_ascii), dp(seq_off),
                                                             C.byref(res), work.data_ptr(), work.numel(), C.c_void_p(st)))
         return out
+
+    def place_translated(self, dna, fixed_len=0, lens=None, flags_in=None, out=None, keepAtMost=7, keepFactor=0.01, stream=None):
+        """rk_place_packed_device_translated (amino-acid databases): 2-bit DNA records [n, dna_words] (int32 tensor on the database's
+        device, as rk_pack_reads(RK_ALPHABET_DNA) writes them) placed in their six reading frames; `out` gains "frame" (uint8 [n]).
+        The device workspace (one frame's amino-acid records and lengths, a second result set) is a tensor this object owns and
+        grows as batches ask."""
+        import torch
+        n, wpr = dna.shape
+        dev = dna.device
+        K = keepAtMost
+        if out is None:
+            out = dict(n_rows=torch.empty(n, dtype=torch.uint8, device=dev),
+                       branch=torch.empty((n, K), dtype=torch.int16, device=dev),
+                       score=torch.empty((n, K), dtype=torch.float32, device=dev),
+                       lwr=torch.empty((n, K), dtype=torch.float64, device=dev),
+                       flags=torch.empty(n, dtype=torch.int32, device=dev))
+        if "frame" not in out:
+            out["frame"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), out["score"].data_ptr(),
+                        out["lwr"].data_ptr(), out["flags"].data_ptr())
+        p = self._params(keepAtMost, keepFactor, True, False)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        dp = lambda t: None if t is None else t.data_ptr()
+        need = int(self._lib.rk_translated_work_bytes(self.db.handle, n, wpr, K))
+        if n and not need:
+            _lib.check(_lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_AA else _lib.RK_ERR_UNSUPPORTED)
+        work = getattr(self, "_translated_work", None)
+        if work is None or work.device != dev or work.numel() < need:
+            # (grow-only; the old block goes back to the allocator of the stream it was used on, in stream order)
+            work = self._translated_work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        _lib.check(self._lib.rk_place_packed_device_translated(self.db.handle, C.byref(p), n, dna.data_ptr(), wpr, dp(lens), fixed_len,
+                                                               dp(flags_in), C.byref(res), out["frame"].data_ptr(), work.data_ptr(),
+                                                               work.numel(), C.c_void_p(st)))
+        return out
+
+    def translate_packed(self, dna, frame, fixed_len=0, lens=None, aa_words=None, stream=None):
+        """rk_translate_packed_device: one reading frame of 2-bit DNA records [n, dna_words] -> (amino-acid records [n, aa_words],
+        their lengths [n]) as new int32 tensors (translate_packed_host is the host twin)."""
+        import torch
+        n, wpr = dna.shape
+        if aa_words is None:
+            aa_words = translated_words(wpr * 16 if lens is not None else fixed_len)
+        aa = torch.empty((n, aa_words), dtype=torch.int32, device=dna.device)
+        aa_lens = torch.empty(n, dtype=torch.int32, device=dna.device)
+        st = stream if stream is not None else torch.cuda.current_stream(dna.device).cuda_stream
+        _lib.check(self._lib.rk_translate_packed_device(self.db.handle, frame, n, dna.data_ptr(), wpr, None if lens is None else lens.data_ptr(),
+                                                        fixed_len, aa.data_ptr(), aa_words, aa_lens.data_ptr(), C.c_void_p(st)))
+        return aa, aa_lens
 
     def revcomp_packed(self, packed, fixed_len=0, lens=None, stream=None):
         """rk_revcomp_packed_device: the reverse complement of 2-bit records [n, wpr] (int32 tensor on the database's device) ->

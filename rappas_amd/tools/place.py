@@ -14,12 +14,19 @@ from .. import hostio
 from ..placement import PhyloKmerDB, PlacementProcess
 
 
+TRANSLATE_WITH_STRAND = "--translate places every read in all six reading frames, both strands included: it cannot be combined with --strand rev | both"
+TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
+
+
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
-               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd"):
+               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
-    reversed_<query>.tsv)"""
+    reversed_<query>.tsv).  translate: DNA reads on an amino-acid database, six reading frames translated on the device and the best
+    one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both"."""
+    if translate and strand != "fwd":
+        raise ValueError(TRANSLATE_WITH_STRAND)
     if dbimage is not None:
         from ..placement import db_image_info
         _, blob = db_image_info(dbimage)
@@ -37,17 +44,23 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
         db = PhyloKmerDB(d["alphabet"], d["k"], d["n_branches"], d["thr_log10"], d["thr"], d["key_codes"], d["row_offsets"],
                          d["branch_ids"], d["scores"], device=device, convert_uo=d.get("convert_uo", False))
     try:
+        if translate and db.info.alphabet != 20:
+            raise ValueError(TRANSLATE_NEEDS_AA)
         records = hostio.read_fasta(fasta_text)
         unique, names = hostio.dedup_reads(records)
         seq, off = hostio.pack_batch([s for _, s in unique])
-        res = PlacementProcess(db, ns_bound).processQueries(
-            seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
-            treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
+        if translate:
+            res = PlacementProcess(db, ns_bound).processQueriesTranslated(seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor)
+        else:
+            res = PlacementProcess(db, ns_bound).processQueries(
+                seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
+                treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
     finally:
         db.close()
     pl = hostio.jplace_placements(tree, names, res.n_rows, res.branch, res.score, res.lwr, guppy)
     res.notplaced = hostio.notplaced_log(records, unique, (res.flags & 1) != 0)
     res.reversed = hostio.reversed_log(records, unique, res.flags) if strand != "fwd" else None
+    res.frames = hostio.frames_log(records, unique, res.frame) if translate else None
     return hostio.jplace_document(tree, pl, call_string, guppy), res
 
 
@@ -67,10 +80,16 @@ def main(argv=None):
     ap.add_argument("--strand", choices=["fwd", "rev", "both"], default="fwd",
                     help="DNA: place the reads as given (default, the reference's behaviour), their reverse complements, or both and keep "
                          "the better strand per read; rev / both also write logs/reversed_<query>.tsv")
+    ap.add_argument("--translate", action="store_true",
+                    help="amino-acid database, DNA reads: translate every read in its six reading frames on the device (standard genetic "
+                         "code, longest stop-free run per frame) and report the best frame; also writes logs/frames_<query>.tsv "
+                         "(header<TAB>+1|+2|+3|-1|-2|-3); not with --strand rev | both")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--logs", default=None, help="directory of notplaced_<query>.tsv (default: logs/ next to --out, like the reference's workdir/logs)")
     a = ap.parse_args(argv)
+    if a.translate and a.strand != "fwd":
+        ap.error(TRANSLATE_WITH_STRAND)
     db_text = None
     if a.dbimage is None:
         with open(a.jsondb or a.uniondb, "rb") as f:
@@ -78,8 +97,15 @@ def main(argv=None):
     with open(a.fasta, "rb") as f:
         fasta_text = f.read()
     call = "".join(" " + x for x in (argv if argv is not None else sys.argv[1:]))
-    doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
-                          a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand)
+    try:
+        doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
+                              a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
+                              translate=a.translate)
+    except ValueError as e:
+        if str(e) != TRANSLATE_NEEDS_AA:
+            raise
+        print("rappas_amd.tools.place: " + TRANSLATE_NEEDS_AA, file=sys.stderr)
+        return 1
     with open(a.out, "w") as f:
         f.write(doc)
     logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.out)), "logs")
@@ -89,6 +115,9 @@ def main(argv=None):
     if res.reversed is not None:
         with open(os.path.join(logs, "reversed_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
             f.write(res.reversed)
+    if res.frames is not None:
+        with open(os.path.join(logs, "frames_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
+            f.write(res.frames)
     placed = int(np.count_nonzero(res.n_rows))
     print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
     return 0
