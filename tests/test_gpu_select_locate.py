@@ -12,112 +12,11 @@ import numpy as np
 import pytest
 
 import rappas_amd as ra
-from rappas_amd import synth
 from oracle import oracle as O
+from tests.planted import place_prefilled, planted_db, planted_reads, shapes_met, sorted_vectors  # (shared with tests/test_gpu_tie_order.py)
 from tests.util import compare_with_oracle
 
 pytestmark = pytest.mark.gpu
-
-STREAMS = 64  # 4 streams in each of a group's 16 lanes
-
-
-def planted_db(alphabet, k, nb, n_keys, seed):
-    """rows of up to 24 entries: branches 64 apart (one stream), runs of neighbours, random sets and mixtures; scores drawn from
-    1, 2, 3 or 8 dyadic fractions of the threshold, so that equal sums are everywhere.  Returns the database and the keys' digits."""
-    rng = np.random.default_rng(seed)
-    digits = rng.integers(0, alphabet, (n_keys, k))
-    dense = (digits.astype(np.uint64) * (np.uint64(alphabet) ** np.arange(k, dtype=np.uint64))).sum(1).astype(np.uint64)
-    _, first = np.unique(dense, return_index=True)
-    first.sort()
-    digits, dense = digits[first], dense[first]
-    thr, thr_log10 = synth.thresholds(1.5, alphabet, k)
-    rows_b, rows_s = [], []
-    for _ in range(len(dense)):
-        m = int(rng.integers(1, min(24, nb - 1) + 1))
-        kind = int(rng.integers(0, 4))
-        b = set()
-        if kind in (0, 3) and nb > STREAMS + 2:  # one stream: b, b + 64, b + 128 ...
-            b0 = int(rng.integers(1, min(STREAMS, nb - STREAMS - 1) + 1))
-            same = np.arange(b0, nb, STREAMS)
-            b.update(rng.choice(same, size=min(len(same), m if kind == 0 else 3), replace=False).tolist())
-        if kind == 1:  # neighbours
-            b0 = int(rng.integers(1, nb - m + 1))
-            b.update(range(b0, b0 + m))
-        if len(b) < m:  # anywhere
-            b.update(rng.choice(np.arange(1, nb), size=m - len(b), replace=False).tolist())
-        b = np.array(sorted(b), dtype=np.uint16)
-        palette = int(rng.choice([1, 2, 3, 8]))
-        s = (rng.integers(1, palette + 1, len(b)).astype(np.float32) / np.float32(8.0)) * np.float32(thr_log10)
-        rows_b.append(b)
-        rows_s.append(s.astype(np.float32))
-    off = np.zeros(len(dense) + 1, dtype=np.uint64)
-    np.cumsum([len(b) for b in rows_b], out=off[1:])
-    sdb = synth.SynthDB(alphabet, k, nb, thr, thr_log10, synth.dense_to_code(alphabet, k, dense), off,
-                        np.concatenate(rows_b).astype(np.uint16), np.concatenate(rows_s).astype(np.float32), seed)
-    return sdb, digits
-
-
-def planted_reads(alphabet, k, digits, n, L, seed):
-    """random reads of L symbols carrying none, one, two or three of the keys"""
-    rng = np.random.default_rng(seed)
-    letters = synth.AA_LETTERS if alphabet == 20 else synth.DNA_LETTERS
-    st = rng.integers(0, alphabet, (n, L))
-    how_many = rng.choice([0, 1, 2, 3], size=n, p=[0.06, 0.5, 0.3, 0.14])
-    slots = [0, L // 3, 2 * L // 3]
-    for r in range(n):
-        for j in range(how_many[r]):
-            at = slots[j] + int(rng.integers(0, L // 3 - k))
-            st[r, at:at + k] = digits[int(rng.integers(0, len(digits)))]
-    seq = np.ascontiguousarray(letters[st.reshape(-1)])
-    return seq, (np.arange(n + 1, dtype=np.uint64) * np.uint64(L))
-
-
-def place_prefilled(pp, packed, n, L, K):
-    """rk_place_packed_device into result tensors pre-filled with 0xFF bytes; every read must have been written"""
-    import torch
-    dev = torch.device("cuda", 0)
-    out = dict(n_rows=torch.full((n,), 0xFF, dtype=torch.uint8, device=dev),
-               branch=torch.full((n, K), -1, dtype=torch.int16, device=dev),
-               score=torch.full((n, K), -1, dtype=torch.int32, device=dev).view(torch.float32),
-               lwr=torch.full((n, K), -1, dtype=torch.int64, device=dev).view(torch.float64),
-               flags=torch.full((n,), -1, dtype=torch.int32, device=dev))
-    pp.place_packed(torch.from_numpy(packed.view(np.int32)).to(dev), fixed_len=L, out=out, keepAtMost=K)
-    torch.cuda.synchronize()
-    o = {f: t.cpu().numpy() for f, t in out.items()}
-    unwritten = np.nonzero((o["n_rows"] == 0xFF) | (o["flags"] == -1))[0]
-    assert len(unwritten) == 0, f"{len(unwritten)} of {n} reads never written (first: {unwritten[:8]})"
-    return ra.Placements(o["n_rows"], o["branch"].view(np.uint16), o["score"], o["lwr"], o["flags"].view(np.uint32), {})
-
-
-def sorted_vectors(odb, seq, off):
-    """per read: the touched branches by (score descending, branch ascending) and their scores' bits"""
-    res = []
-    for r in range(len(off) - 1):
-        S, touched, _ = odb.score_vector(bytes(seq[int(off[r]):int(off[r + 1])]))
-        touched = np.sort(touched.astype(np.int64))
-        order = touched[np.argsort(-S[touched].astype(np.float64), kind="stable")]
-        res.append((order, S[order].view(np.uint32)))
-    return res
-
-
-def shapes_met(vectors, K, seen):
-    """which of the cases this file is about the reads' score vectors hold, for keep_at_most K"""
-    for order, bits in vectors:
-        if len(order) == 0:
-            seen["none"] += 1
-            continue
-        if len(order) < K:
-            seen["fewer"] += 1
-        if len(order) > K and bits[K - 1] == bits[K]:
-            seen["straddle"] += 1
-        top, tb = order[:K], bits[:K]
-        stream = (top + 1) % STREAMS
-        for i in range(len(top)):
-            for j in range(i + 1, len(top)):
-                if stream[i] == stream[j]:
-                    seen["stream_equal" if tb[i] == tb[j] else "stream_differ"] += 1
-                elif tb[i] == tb[j]:  # top is sorted: top[i] < top[j] here
-                    seen["tie_ids_along" if stream[i] < stream[j] else "tie_ids_against"] += 1
 
 
 def check_tree(alphabet, k, nb, L, n_reads, seed, need):
