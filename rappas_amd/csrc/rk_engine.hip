@@ -1951,6 +1951,12 @@ static int check_params(const rk_params *p) {
     if (std::isnan(p->keep_factor) || std::isnan(p->ns_bound)) return fail(RK_ERR_INVALID, "NaN in rk_params");
     return RK_OK;
 }
+// without a length array every record holds fixed_len symbols of `bits` bits: they must be there
+static int check_fixed_len(const char *who, const void *lens, uint32_t fixed_len, uint32_t bits, uint32_t words) {
+    if (!lens && (uint64_t)fixed_len * bits > (uint64_t)words * 32) return fail(RK_ERR_INVALID, "%s: fixed_len=%u does not fit %u words", who, fixed_len, words);
+    return RK_OK;
+}
+static bool result_complete(const rk_result *r) { return r && r->n_rows && r->branch && r->score && r->lwr && r->flags; }
 
 extern "C" const char *rk_kernel_name(const rk_db *db) {
     if (!db) return "";
@@ -2048,10 +2054,9 @@ extern "C" int rk_place_packed_device(rk_db *db, const rk_params *p, uint64_t n_
     if (rc) return rc;
     if (n_reads == 0) return RK_OK;
     if (!d_packed || words_per_read == 0) return fail(RK_ERR_INVALID, "rk_place_packed_device: null packed reads");
-    if (!d_out->n_rows || !d_out->branch || !d_out->score || !d_out->lwr || !d_out->flags)
-        return fail(RK_ERR_INVALID, "rk_place_packed_device: null result array");
-    if (!d_lens && (uint64_t)fixed_len * db->info.bits_per_symbol > (uint64_t)words_per_read * 32)
-        return fail(RK_ERR_INVALID, "rk_place_packed_device: fixed_len=%u does not fit %u words", fixed_len, words_per_read);
+    if (!result_complete(d_out)) return fail(RK_ERR_INVALID, "rk_place_packed_device: null result array");
+    rc = check_fixed_len("rk_place_packed_device", d_lens, fixed_len, db->info.bits_per_symbol, words_per_read);
+    if (rc) return rc;
     const bool use_wg = db->indexed && db->lanes_per_read == 0;  // an explicit lanes_per_read forces the single-wave kernel
     const bool use_win = !use_wg && use_windowed(db, p->keep_at_most, words_per_read);
     Geometry g{};
@@ -2109,8 +2114,8 @@ extern "C" int rk_revcomp_packed_device(rk_db *db, uint64_t n_reads, const uint3
     if (n_reads == 0) return RK_OK;
     if (!d_packed || !d_packed_out || words_per_read == 0) return fail(RK_ERR_INVALID, "rk_revcomp_packed_device: null/zero argument");
     if (d_packed == d_packed_out) return fail(RK_ERR_INVALID, "rk_revcomp_packed_device: the output must not alias the input");
-    if (!d_lens && (uint64_t)fixed_len * 2 > (uint64_t)words_per_read * 32)
-        return fail(RK_ERR_INVALID, "rk_revcomp_packed_device: fixed_len=%u does not fit %u words", fixed_len, words_per_read);
+    rc = check_fixed_len("rk_revcomp_packed_device", d_lens, fixed_len, 2, words_per_read);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(db->info.device));
     hipLaunchKernelGGL(revcomp_packed_kernel, dim3(strand_blocks(db, n_reads * words_per_read)), dim3(256), 0, (hipStream_t)stream, d_packed, (u64)n_reads,
                        words_per_read, d_lens, fixed_len, d_packed_out);
@@ -2138,7 +2143,15 @@ extern "C" int rk_revcomp_ascii_device(rk_db *db, uint64_t n_reads, const uint8_
     return launch_revcomp_ascii(db, n_reads, d_seq_ascii, d_seq_off, nullptr, d_out_ascii, ~0ull, (hipStream_t)stream);
 }
 
-static bool result_complete(const rk_result *r) { return r && r->n_rows && r->branch && r->score && r->lwr && r->flags; }
+// merge_results_kernel: `cand` replaces `best` read by read where it is the better one
+static int launch_merge(rk_db *db, uint32_t K, uint64_t n_reads, const rk_result *best, uint8_t *best_frame, const rk_result *cand, uint32_t mark,
+                        uint32_t frame_id, hipStream_t s) {
+    hipLaunchKernelGGL(merge_results_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, s, (u64)n_reads, K, best->n_rows, best->branch, best->score,
+                       best->lwr, best->flags, best_frame, (const unsigned char *)cand->n_rows, (const unsigned short *)cand->branch,
+                       (const float *)cand->score, (const double *)cand->lwr, (const uint32_t *)cand->flags, mark, frame_id);
+    HIP_TRY(hipGetLastError());
+    return RK_OK;
+}
 
 extern "C" int rk_merge_strands_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_fwd, const rk_result *d_rev,
                                        void *stream) {
@@ -2148,36 +2161,29 @@ extern "C" int rk_merge_strands_device(rk_db *db, uint32_t keep_at_most, uint64_
     if (n_reads == 0) return RK_OK;
     if (!result_complete(d_fwd) || !result_complete(d_rev)) return fail(RK_ERR_INVALID, "rk_merge_strands_device: null result array");
     HIP_TRY(hipSetDevice(db->info.device));
-    hipLaunchKernelGGL(merge_strands_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, (hipStream_t)stream, (u64)n_reads, keep_at_most, d_fwd->n_rows,
-                       d_fwd->branch, d_fwd->score, d_fwd->lwr, d_fwd->flags, (const unsigned char *)d_rev->n_rows, (const unsigned short *)d_rev->branch,
-                       (const float *)d_rev->score, (const double *)d_rev->lwr, (const uint32_t *)d_rev->flags);
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
+    return launch_merge(db, keep_at_most, n_reads, d_fwd, nullptr, d_rev, RK_FLAG_REVERSE, 0, (hipStream_t)stream);
 }
 
-// The workspace of rk_place_packed_device_strands: reverse records | second result set (n_rows, branch, score, lwr, flags) |
-// reversed characters; every part starts on a 256-byte boundary of the block.
-struct StrandWork {
-    uint64_t rec, nrows, branch, score, lwr, flags, ascii;  // byte offsets; `ascii` = size of everything before the characters
-};
-static StrandWork strand_work(uint64_t n, uint32_t wpr, uint32_t K) {
-    auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
-    StrandWork w{};
-    w.rec = 0;
-    w.nrows = up(n * wpr * 4);
-    w.branch = w.nrows + up(n);
-    w.score = w.branch + up(n * K * 2);
-    w.lwr = w.score + up(n * K * 4);
-    w.flags = w.lwr + up(n * K * 8);
-    w.ascii = w.flags + up(n * 4);
-    return w;
+// A second result set in a workspace, from byte offset `at` on: n_rows | branch | score | lwr | flags, each on a 256-byte boundary of
+// the block.  Returns the offset behind it and, given a block, the arrays at those offsets of it.
+static uint64_t up256(uint64_t v) { return (v + 255) & ~255ull; }
+static uint64_t work_result(char *base, uint64_t at, uint64_t n, uint32_t K, rk_result *out) {
+    const uint64_t branch = at + up256(n), score = branch + up256(n * K * 2), lwr = score + up256(n * K * 4), flags = lwr + up256(n * K * 8);
+    if (base && out) *out = rk_result{(uint8_t *)(base + at), (uint16_t *)(base + branch), (float *)(base + score), (double *)(base + lwr), (uint32_t *)(base + flags)};
+    return flags + up256(n * 4);
+}
+
+// The workspace of rk_place_packed_device_strands: reverse records | second result set | reversed characters.  Returns the size of
+// everything before the characters.
+static uint64_t strand_work(uint64_t n, uint32_t wpr, uint32_t K, char *base = nullptr, rk_result *second = nullptr) {
+    return work_result(base, up256(n * wpr * 4), n, K, second);
 }
 
 extern "C" uint64_t rk_strands_work_bytes(const rk_db *db, uint64_t n_reads, uint32_t words_per_read, uint32_t keep_at_most, uint64_t ascii_bytes) {
     if (strands_handle(db, "rk_strands_work_bytes")) return 0;
     if (words_per_read == 0 || keep_at_most < 1 || keep_at_most > 16) { (void)fail(RK_ERR_INVALID, "rk_strands_work_bytes: words_per_read=%u, keep_at_most=%u", words_per_read, keep_at_most); return 0; }
     if (n_reads >= (1ull << 40)) { (void)fail(RK_ERR_INVALID, "rk_strands_work_bytes: n_reads too large"); return 0; }
-    return strand_work(n_reads, words_per_read, keep_at_most).ascii + ascii_bytes;
+    return strand_work(n_reads, words_per_read, keep_at_most) + ascii_bytes;
 }
 
 extern "C" int rk_place_packed_device_strands(rk_db *db, const rk_params *p, uint32_t strand, uint64_t n_reads, const uint32_t *d_packed,
@@ -2196,25 +2202,26 @@ extern "C" int rk_place_packed_device_strands(rk_db *db, const rk_params *p, uin
     if (n_reads == 0) return RK_OK;
     if (!d_packed || words_per_read == 0) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: null packed reads");
     if (!result_complete(d_out)) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: null result array");
-    if (!d_lens && (uint64_t)fixed_len * 2 > (uint64_t)words_per_read * 32)
-        return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: fixed_len=%u does not fit %u words", fixed_len, words_per_read);
+    rc = check_fixed_len("rk_place_packed_device_strands", d_lens, fixed_len, 2, words_per_read);
+    if (rc) return rc;
     if (n_reads >= (1ull << 40)) return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: n_reads too large");
-    const StrandWork L = strand_work(n_reads, words_per_read, p->keep_at_most);
-    if (!d_work || work_bytes < L.ascii)
+    char *base = (char *)d_work;
+    rk_result rres{};
+    const uint64_t before_ascii = strand_work(n_reads, words_per_read, p->keep_at_most, base, &rres);
+    if (!d_work || work_bytes < before_ascii)
         return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: workspace of %llu bytes, %llu needed (rk_strands_work_bytes)", (unsigned long long)(d_work ? work_bytes : 0),
-                    (unsigned long long)L.ascii);
+                    (unsigned long long)before_ascii);
     const bool ascii = d_flags_in && d_seq_ascii && d_seq_off;
-    if (ascii && work_bytes == L.ascii)
+    if (ascii && work_bytes == before_ascii)
         return fail(RK_ERR_INVALID, "rk_place_packed_device_strands: the workspace has no room for the reversed characters (rk_strands_work_bytes with ascii_bytes)");
     HIP_TRY(hipSetDevice(db->info.device));
     hipStream_t s = (hipStream_t)stream;
-    char *base = (char *)d_work;
-    uint32_t *rev = (uint32_t *)(base + L.rec);
-    uint8_t *rev_ascii = ascii ? (uint8_t *)(base + L.ascii) : nullptr;
+    uint32_t *rev = (uint32_t *)base;
+    uint8_t *rev_ascii = ascii ? (uint8_t *)(base + before_ascii) : nullptr;
     rc = rk_revcomp_packed_device(db, n_reads, d_packed, words_per_read, d_lens, fixed_len, rev, s);
     if (rc) return rc;
     if (ascii) {
-        rc = launch_revcomp_ascii(db, n_reads, d_seq_ascii, d_seq_off, d_flags_in, rev_ascii, work_bytes - L.ascii, s);
+        rc = launch_revcomp_ascii(db, n_reads, d_seq_ascii, d_seq_off, d_flags_in, rev_ascii, work_bytes - before_ascii, s);
         if (rc) return rc;
     }
     if (strand == RK_STRAND_REVERSE) {
@@ -2225,7 +2232,6 @@ extern "C" int rk_place_packed_device_strands(rk_db *db, const rk_params *p, uin
         return RK_OK;
     }
     // the reverse strand first: d_flags_in may be the output flag array itself, which the forward pass then overwrites
-    const rk_result rres{(uint8_t *)(base + L.nrows), (uint16_t *)(base + L.branch), (float *)(base + L.score), (double *)(base + L.lwr), (uint32_t *)(base + L.flags)};
     rc = rk_place_packed_device(db, p, n_reads, rev, words_per_read, d_lens, fixed_len, d_flags_in, rev_ascii, d_seq_off, &rres, s);
     if (rc) return rc;
     rc = rk_place_packed_device(db, p, n_reads, d_packed, words_per_read, d_lens, fixed_len, d_flags_in, d_seq_ascii, d_seq_off, d_out, s);
@@ -2255,7 +2261,7 @@ static int translate_args(const char *who, uint32_t frame, const void *dna, uint
                           uint32_t aa_words, const void *aa_lens) {
     if (frame > 5) return fail(RK_ERR_INVALID, "%s: frame=%u (0..2 as given, 3..5 the reverse complement)", who, frame);
     if (!dna || !aa || !aa_lens || dna_words == 0 || dna_words > 0x7FFFFFFu) return fail(RK_ERR_INVALID, "%s: null/zero argument", who);
-    if (!dna_lens && (uint64_t)fixed_len * 2 > (uint64_t)dna_words * 32) return fail(RK_ERR_INVALID, "%s: fixed_len=%u does not fit %u words", who, fixed_len, dna_words);
+    if (check_fixed_len(who, dna_lens, fixed_len, 2, dna_words)) return RK_ERR_INVALID;
     const uint32_t need = translated_words(dna_lens ? (uint64_t)dna_words * 16 : fixed_len);
     if (aa_words < need) return fail(RK_ERR_INVALID, "%s: aa_words=%u, %u needed for the longest frame of these records", who, aa_words, need);
     return RK_OK;
@@ -2295,32 +2301,21 @@ extern "C" int rk_merge_frames_device(rk_db *db, uint32_t keep_at_most, uint64_t
     if (n_reads == 0) return RK_OK;
     if (!result_complete(d_best) || !result_complete(d_cand) || !d_best_frame) return fail(RK_ERR_INVALID, "rk_merge_frames_device: null result array");
     HIP_TRY(hipSetDevice(db->info.device));
-    hipLaunchKernelGGL(merge_frames_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, (hipStream_t)stream, (u64)n_reads, keep_at_most, d_best->n_rows,
-                       d_best->branch, d_best->score, d_best->lwr, d_best->flags, d_best_frame, (const unsigned char *)d_cand->n_rows,
-                       (const unsigned short *)d_cand->branch, (const float *)d_cand->score, (const double *)d_cand->lwr, (const uint32_t *)d_cand->flags,
-                       cand_frame);
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
+    return launch_merge(db, keep_at_most, n_reads, d_best, d_best_frame, d_cand, cand_frame >= 3 ? RK_FLAG_REVERSE : 0u, cand_frame, (hipStream_t)stream);
 }
 
-// The workspace of rk_place_packed_device_translated: amino-acid records of one frame | their lengths | one result set (n_rows,
-// branch, score, lwr, flags); every part starts on a 256-byte boundary of the block.
+// The workspace of rk_place_packed_device_translated: amino-acid records of one frame | their lengths | one result set; every part
+// starts on a 256-byte boundary of the block.
 struct TranslatedWork {
     uint32_t aa_words;
-    uint64_t rec, lens, nrows, branch, score, lwr, flags, total;  // byte offsets
+    uint64_t lens, total;  // byte offsets (the records are at 0)
+    rk_result cand;        // with a block given: the result set in it
 };
-static TranslatedWork translated_work(uint64_t n, uint32_t dna_words, uint32_t K) {
-    auto up = [](uint64_t v) { return (v + 255) & ~255ull; };
+static TranslatedWork translated_work(uint64_t n, uint32_t dna_words, uint32_t K, char *base = nullptr) {
     TranslatedWork w{};
     w.aa_words = translated_words((uint64_t)dna_words * 16);
-    w.rec = 0;
-    w.lens = up(n * w.aa_words * 4);
-    w.nrows = w.lens + up(n * 4);
-    w.branch = w.nrows + up(n);
-    w.score = w.branch + up(n * K * 2);
-    w.lwr = w.score + up(n * K * 4);
-    w.flags = w.lwr + up(n * K * 8);
-    w.total = w.flags + up(n * 4);
+    w.lens = up256(n * w.aa_words * 4);
+    w.total = work_result(base, w.lens + up256(n * 4), n, K, &w.cand);
     return w;
 }
 
@@ -2344,30 +2339,30 @@ extern "C" int rk_place_packed_device_translated(rk_db *db, const rk_params *p, 
     if (n_reads == 0) return RK_OK;
     if (!d_dna || dna_words == 0 || dna_words > 0x7FFFFFFu) return fail(RK_ERR_INVALID, "%s: null packed reads", who);
     if (!result_complete(d_out) || !d_frame) return fail(RK_ERR_INVALID, "%s: null result array", who);
-    if (!d_dna_lens && (uint64_t)fixed_len * 2 > (uint64_t)dna_words * 32) return fail(RK_ERR_INVALID, "%s: fixed_len=%u does not fit %u words", who, fixed_len, dna_words);
+    rc = check_fixed_len(who, d_dna_lens, fixed_len, 2, dna_words);
+    if (rc) return rc;
     if (d_dna_flags && d_dna_flags == d_out->flags) return fail(RK_ERR_INVALID, "%s: d_dna_flags must not be the output flag array (every frame reads it)", who);
     if (n_reads >= (1ull << 32)) return fail(RK_ERR_INVALID, "%s: n_reads too large", who);
-    const TranslatedWork L = translated_work(n_reads, dna_words, p->keep_at_most);
+    char *base = (char *)d_work;
+    const TranslatedWork L = translated_work(n_reads, dna_words, p->keep_at_most, base);
     if (!d_work || work_bytes < L.total)
         return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_translated_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0),
                     (unsigned long long)L.total);
     HIP_TRY(hipSetDevice(db->info.device));
     hipStream_t s = (hipStream_t)stream;
-    char *base = (char *)d_work;
-    uint32_t *aa = (uint32_t *)(base + L.rec), *aa_lens = (uint32_t *)(base + L.lens);
-    const rk_result cres{(uint8_t *)(base + L.nrows), (uint16_t *)(base + L.branch), (float *)(base + L.score), (double *)(base + L.lwr), (uint32_t *)(base + L.flags)};
+    uint32_t *aa = (uint32_t *)base, *aa_lens = (uint32_t *)(base + L.lens);
     for (uint32_t f = 0; f < 6; f++) {
         rc = rk_translate_packed_device(db, f, n_reads, d_dna, dna_words, d_dna_lens, fixed_len, aa, L.aa_words, aa_lens, s);
         if (rc) return rc;
         // (the placement kernels take BAD_CHAR / AMBIGUOUS / TOO_LONG from d_flags_in and nothing else: the DNA packer's TOO_SHORT,
         //  which speaks of bases, ends here; TOO_SHORT of the result is the frame's own, R < k residues)
-        rc = rk_place_packed_device(db, p, n_reads, aa, L.aa_words, aa_lens, 0, d_dna_flags, nullptr, nullptr, f == 0 ? d_out : &cres, s);
+        rc = rk_place_packed_device(db, p, n_reads, aa, L.aa_words, aa_lens, 0, d_dna_flags, nullptr, nullptr, f == 0 ? d_out : &L.cand, s);
         if (rc) return rc;
         if (f == 0) {
             hipLaunchKernelGGL(init_frame_kernel, dim3(strand_blocks(db, n_reads)), dim3(256), 0, s, (const unsigned char *)d_out->n_rows, d_frame, (u64)n_reads);
             HIP_TRY(hipGetLastError());
         } else {
-            rc = rk_merge_frames_device(db, p->keep_at_most, n_reads, d_out, d_frame, &cres, f, s);
+            rc = rk_merge_frames_device(db, p->keep_at_most, n_reads, d_out, d_frame, &L.cand, f, s);
             if (rc) return rc;
         }
     }
@@ -2396,8 +2391,7 @@ extern "C" int rk_count_work_device(rk_db *db, uint64_t n_reads, const uint32_t 
     HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(rk_work), s));
     if (n_reads == 0) return RK_OK;
     if (!d_packed || words_per_read == 0) return fail(RK_ERR_INVALID, "rk_count_work_device: null packed reads");
-    if (!d_lens && (uint64_t)fixed_len * db->info.bits_per_symbol > (uint64_t)words_per_read * 32)
-        return fail(RK_ERR_INVALID, "rk_count_work_device: fixed_len=%u does not fit %u words", fixed_len, words_per_read);
+    if (check_fixed_len("rk_count_work_device", d_lens, fixed_len, db->info.bits_per_symbol, words_per_read)) return RK_ERR_INVALID;
     if (db->info.bits_per_symbol == 2) launch_count<2>(db, d_packed, words_per_read, d_lens, fixed_len, d_flags_in, n_reads, (unsigned long long *)d_out, s);
     else launch_count<5>(db, d_packed, words_per_read, d_lens, fixed_len, d_flags_in, n_reads, (unsigned long long *)d_out, s);
     HIP_TRY(hipGetLastError());
@@ -2881,8 +2875,8 @@ extern "C" int rk_place_batch_packed(rk_db *db, const rk_params *p, uint64_t n_r
     int rc = check_params(p);
     if (rc) return rc;
     if (n_reads && (!packed || words_per_read == 0)) return fail(RK_ERR_INVALID, "rk_place_batch_packed: null packed reads");
-    if (!lens && (uint64_t)fixed_len * db->info.bits_per_symbol > (uint64_t)words_per_read * 32)
-        return fail(RK_ERR_INVALID, "rk_place_batch_packed: fixed_len=%u does not fit %u words", fixed_len, words_per_read);
+    rc = check_fixed_len("rk_place_batch_packed", lens, fixed_len, db->info.bits_per_symbol, words_per_read);
+    if (rc) return rc;
     if ((seq_ascii == nullptr) != (seq_off == nullptr)) return fail(RK_ERR_INVALID, "rk_place_batch_packed: seq_ascii and seq_off go together");
     HostInput in;
     in.ascii = seq_ascii; in.off = seq_off; in.packed = packed; in.wpr = words_per_read; in.lens = lens; in.fixed_len = fixed_len; in.flags = flags;

@@ -38,8 +38,9 @@
 
 namespace rk {
 
+// Per-wave cycle sums of the kernel phases (slots 0..15) for the diagnostic build of scripts/stamps.py.  A kernel owns one Stamps and
+// hands it by reference to the functions that stamp; the product build's Stamps is empty and every call on it compiles to nothing.
 #ifdef RK_STAMPS
-// Diagnostic build only (scripts/stamps.py): per-wave cycle sums of the kernel phases. Never compiled into the product.
 __device__ unsigned long long rk_stamp_buf[2 * 4096 * 16];  // second half: place_packed16w_kernel launched behind place_packed16s_kernel
 __device__ __forceinline__ unsigned long long rk_now() {
     unsigned long long t;
@@ -48,13 +49,25 @@ __device__ __forceinline__ unsigned long long rk_now() {
     __builtin_amdgcn_sched_barrier(0);
     return t;
 }
-#define RK_STAMP(slot) do { unsigned long long n_ = rk_now(); st_[slot] += n_ - t_; t_ = n_; } while (0)
-#define RK_STAMP_PARAMS , unsigned long long *st_, unsigned long long &t_
-#define RK_STAMP_ARGS , st_, t_
+struct Stamps {
+    unsigned long long st_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long t_ = rk_now();
+    __device__ __forceinline__ void mark(int slot) {  // the cycles since the last mark go to `slot`
+        const unsigned long long n_ = rk_now();
+        st_[slot] += n_ - t_;
+        t_ = n_;
+    }
+    __device__ __forceinline__ void add(int slot, unsigned long long n) { st_[slot] += n; }  // (slots used as event counters)
+    __device__ __forceinline__ void store(unsigned long long index) const {                   // row `index` of rk_stamp_buf
+        for (int i = 0; i < 16; i++) rk_stamp_buf[index * 16 + i] = st_[i];
+    }
+};
 #else
-#define RK_STAMP(slot) do {} while (0)
-#define RK_STAMP_PARAMS
-#define RK_STAMP_ARGS
+struct Stamps {
+    __device__ __forceinline__ void mark(int) {}
+    __device__ __forceinline__ void add(int, unsigned long long) {}
+    __device__ __forceinline__ void store(unsigned long long) const {}
+};
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -103,6 +116,42 @@ __device__ __forceinline__ bool takes_only_marked(const PlaceArgs &a) {
     return ((a.marked_if >> batch_class(a)) & 1u) != 0u;
 }
 __device__ __forceinline__ u64 tile_read(const PlaceArgs &a, u64 slot, bool given) { return given ? (u64)a.perm[slot] : slot; }
+// What a packed read's inputs mean, for every kernel that takes packed reads: read_head is the definition.  (count_work_kernel, which
+// has no PlaceArgs, shares clamp_len and skips the same reads by its own test.)
+//   R      the length, never past what the record's words hold;
+//   flags  BAD_CHAR | AMBIGUOUS | TOO_LONG of flags_in and nothing else (callers pass an output flag array, or another alphabet's
+//          packer flags), TOO_SHORT added when R < k;
+//   Q      sk.getMerCount() (AmbigSequenceKnife.java:191); 0 for a read that is ambiguous (place_ascii_kernel's), rejected, shorter
+//          than k, or not there (`have`: a tile slot behind the batch's last read);
+//   QT     int * float (PlacementProcess.java:728).
+struct ReadHead {
+    u32 R, flags, Q;
+    float QT;
+    bool is_amb, rejected;
+};
+// (in place, not a returned value: the compiler attaches the range it infers for a function's result to the min that produces it, and
+// the kernels' schedules and register counts then move away from what they were with these lines written inside them)
+template <int BITS>
+__device__ __forceinline__ void clamp_len(u32 &R, u32 words_per_read) {
+    const u32 cap_syms = (words_per_read * 32u) / BITS;
+    R = R < cap_syms ? R : cap_syms;
+}
+template <int BITS>
+__device__ __forceinline__ ReadHead read_head(const PlaceArgs &a, u32 R_raw, u32 fin, bool have) {
+    const u32 k = a.db.k;
+    ReadHead h;
+    h.R = R_raw;
+    clamp_len<BITS>(h.R, a.words_per_read);
+    h.flags = fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG);
+    h.is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
+    h.rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
+    if (h.R < k) h.flags |= RK_FLAG_TOO_SHORT;
+    h.Q = (have && !h.is_amb && !h.rejected && h.R >= k) ? (h.R - k + 1) : 0u;
+    h.QT = (float)(int)h.Q * a.db.T;
+    return h;
+}
+// the read's result is written by place_ascii_kernel, not by the packed kernel that met it
+__device__ __forceinline__ bool deferred(const PlaceArgs &a, const ReadHead &h) { return h.is_amb && a.has_ascii && !h.rejected; }
 // LDS data exchanged between lanes of ONE wave: DS operations of a wave execute in order, so only the
 // compiler has to be stopped from reordering / caching.
 __device__ __forceinline__ void wave_lds_fence() {
@@ -680,7 +729,7 @@ __device__ __forceinline__ int rank_candidates(const u64 *list, int c, u64 *win,
 // `list` has `cap` u64 slots; the last 16 are the winners' scratch.  S must be 16-byte aligned with s_stride % 4 == 0
 // (slots in [nb, s_stride) are scratch).  Returns numBest (group-uniform).
 template <int G>
-__device__ __forceinline__ int select_topk_scan(u32 *S, u32 ns, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key RK_STAMP_PARAMS) {
+__device__ __forceinline__ int select_topk_scan(u32 *S, u32 ns, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key, Stamps &stamps) {
     // slot layout: S[0] is the scratch word (the caller has set it to UNTOUCHED), branch x is S[x + 1], ns = n_branches + 1
     const u32 nb = ns;
     u64 *win = list + (cap - 16);
@@ -1080,14 +1129,14 @@ __device__ __forceinline__ u32 heads3_locate(const u32 *S, u32 ns, u32 stream, u
 }
 // scan, rounds and locate for one read; the rank-r key in lane r as heads_rounds leaves it
 template <int G>
-__device__ __forceinline__ int heads3_select(u32 *S, u32 ns, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key, bool &doubt RK_STAMP_PARAMS) {
+__device__ __forceinline__ int heads3_select(u32 *S, u32 ns, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key, bool &doubt, Stamps &stamps) {
     Heads3 h;
     heads3_clear(h);
     heads3_scan<G>(S, ns, li, h);
-    RK_STAMP(8);
+    stamps.mark(8);
     u32 win_o, win_t;
     const int num = heads3_rounds<G>(h, K, li, gi, win_o, win_t, doubt);
-    RK_STAMP(9);
+    stamps.mark(9);
     const bool won = (int)li < num;
     const u32 prev_o = row_shr32<1>(win_o), prev_t = row_shr32<1>(win_t);
     const bool tie = won && li > 0 && prev_o == win_o;                   // equal scores in neighbouring ranks
@@ -1097,9 +1146,7 @@ __device__ __forceinline__ int heads3_select(u32 *S, u32 ns, u32 li, u32 gi, int
     if (group_bits<G>(__ballot(won && slot == 0u), gi) != 0) doubt = true;  // (never met: the exact path would put it right)
     win_key = won ? (((u64)win_o << 32) | (u64)(0xFFFFu - (slot - 1u))) : 0ull;
     if (__ballot(tie && !doubt) != 0) {  // rare, wave-uniform: the order among equal scores is the branch's -- rank the K keys as a whole
-#ifdef RK_STAMPS
-        st_[15] += 1;  // (diagnostic: tiles that re-rank)
-#endif
+        stamps.add(15, 1);  // (diagnostic: tiles that re-rank)
         wave_lds_fence();
         if (won) list[li] = win_key;
         wave_lds_fence();
@@ -1108,33 +1155,31 @@ __device__ __forceinline__ int heads3_select(u32 *S, u32 ns, u32 li, u32 gi, int
         win_key = won ? win[li] : 0ull;
         wave_lds_fence();
     }
-    RK_STAMP(13);
+    stamps.mark(13);
     return num;
 }
 template <int G>
-__device__ __forceinline__ int select_topk(u32 *S, u32 n_branches, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key RK_STAMP_PARAMS) {
+__device__ __forceinline__ int select_topk(u32 *S, u32 n_branches, u32 li, u32 gi, int K, u64 *list, int cap, u64 &win_key, Stamps &stamps) {
     // slot layout: the scratch word S[0] leaves the competition, then the scan runs over ns = n_branches + 1 slots and
     // slot i stands for branch i - 1
     if (li == 0) S[0] = S_UNTOUCHED;
     wave_lds_fence();
     const u32 nb = n_branches + 1;
-    if (K > RK_HEADS_MAX_K || K > G) return select_topk_scan<G>(S, nb, li, gi, K, list, cap, win_key RK_STAMP_ARGS);
+    if (K > RK_HEADS_MAX_K || K > G) return select_topk_scan<G>(S, nb, li, gi, K, list, cap, win_key, stamps);
     bool doubt;
     int num;
     if constexpr (G == 16) {  // a group is one DPP row: scores only in the scan, the winners' slots looked up afterwards
-        num = heads3_select<G>(S, nb, li, gi, K, list, cap, win_key, doubt RK_STAMP_ARGS);
+        num = heads3_select<G>(S, nb, li, gi, K, list, cap, win_key, doubt, stamps);
     } else {
         Heads4 h;
         heads_clear(h);
         heads_scan<G>(S, nb, li, 0u, h);
-        RK_STAMP(8);
+        stamps.mark(8);
         num = heads_rounds<G>(h, K, li, gi, win_key, doubt);
     }
-#ifdef RK_STAMPS
-    st_[14] += doubt ? 1 : 0;  // (diagnostic: reads sent to the exact scan)
-#endif
-    if (doubt) return select_topk_scan<G>(S, nb, li, gi, K, list, cap, win_key RK_STAMP_ARGS);
-    RK_STAMP(9);
+    stamps.add(14, doubt ? 1 : 0);  // (diagnostic: reads sent to the exact scan)
+    if (doubt) return select_topk_scan<G>(S, nb, li, gi, K, list, cap, win_key, stamps);
+    stamps.mark(9);
     uint4 *S4w = (uint4 *)S;
     const u32 n4 = (nb + 3) / 4;
     const uint4 reset4 = make_uint4(S_UNTOUCHED, S_UNTOUCHED, S_UNTOUCHED, S_UNTOUCHED);
@@ -1280,10 +1325,7 @@ __global__ void __launch_bounds__(256) place_packed_kernel(PlaceArgs a) {
     const u64 n_tiles = (a.n_reads + NG - 1) / NG;
     const u64 wave_global = (u64)blockIdx.x * waves_per_block + wave;
     const u64 wave_count = (u64)gridDim.x * waves_per_block;
-#ifdef RK_STAMPS
-    unsigned long long st_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_ = rk_now();
-#endif
+    Stamps stamps;
     for (u64 tile = wave_global; tile < n_tiles; tile += wave_count) {
         const bool have = tile * NG + gi < a.n_reads;
         const u64 r = have ? tile_read(a, tile * NG + gi, perm_given) : 0ull;
@@ -1291,16 +1333,10 @@ __global__ void __launch_bounds__(256) place_packed_kernel(PlaceArgs a) {
         if (have) {
             R = a.lens ? a.lens[r] : a.fixed_len;
             fin = a.flags_in ? a.flags_in[r] : 0u;
-            const u32 cap_syms = (a.words_per_read * 32u) / BITS;  // never read past the packed record
-            R = R < cap_syms ? R : cap_syms;
         }
-        u32 flags = fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG);
-        const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-        const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-        if (R < k) flags |= RK_FLAG_TOO_SHORT;
-        // Q = sk.getMerCount() (AmbigSequenceKnife.java:191)
-        const u32 Q = (have && !is_amb && !rejected && R >= k) ? (R - k + 1) : 0u;
-        const float QT = (float)(int)Q * T;  // int * float (PlacementProcess.java:728)
+        const ReadHead h = read_head<BITS>(a, R, fin, have);
+        const u32 Q = h.Q;
+        const float QT = h.QT;
         const u32 *rec = a.packed + (have ? r : 0ull) * a.words_per_read;  // in-bounds for idle groups too
         // warm the cache with the NEXT tile's packed records (streamed from HBM, ~2 us if met cold by the probe)
         u32 warm = 0;
@@ -1322,24 +1358,24 @@ __global__ void __launch_bounds__(256) place_packed_kernel(PlaceArgs a) {
                 }
                 for (int i = cnt + (int)li; i < wcnt + 2 * U; i += G) ((u32 *)items)[i] = ITEM_FILLER;
                 wave_lds_fence();
-                RK_STAMP(3);
+                stamps.mark(3);
                 if (!(RK_ABLATE & 1)) {
                     if (a.db.mono) accumulate_units<G, U, true>(S, (const u32 *)items, wcnt, li, rows_rs, QT, T);
                     else accumulate_units<G, U, false>(S, (const u32 *)items, wcnt, li, rows_rs, QT, T);
                 }
                 wave_lds_fence();
-                RK_STAMP(4);
+                stamps.mark(4);
                 cnt = 0;
                 return;
             }
             wave_lds_fence();
-            RK_STAMP(3);
+            stamps.mark(3);
             if (!(RK_ABLATE & 1)) accumulate_chunks<G, U, WIDE>(S, nb, items, cnt, li, a.db.rows, QT, T);
             wave_lds_fence();
-            RK_STAMP(4);
+            stamps.mark(4);
             cnt = 0;
         };
-        RK_STAMP(0);  // tile setup
+        stamps.mark(0);  // tile setup
         while (true) {
             const bool more = pos < Q;
             if (!__any(more)) break;
@@ -1392,7 +1428,7 @@ __global__ void __launch_bounds__(256) place_packed_kernel(PlaceArgs a) {
                 }
             }
             asm volatile("" ::"v"((u32)desc[0]), "v"((u32)desc[PU - 1]));
-            RK_STAMP(1);  // probe: codes + descriptor gathers (includes their latency)
+            stamps.mark(1);  // probe: codes + descriptor gathers (includes their latency)
             // ---- chunks per row and their exclusive prefix sums in k-mer order (lane order inside a sub-batch) ----
             u32 nch[PU], excl[PU];
             int total = 0;
@@ -1476,7 +1512,7 @@ __global__ void __launch_bounds__(256) place_packed_kernel(PlaceArgs a) {
                 cnt += total;
             }
             if (more) pos += PU * G;
-            RK_STAMP(2);  // scans + item emission
+            stamps.mark(2);  // scans + item emission
         }
         if (__any(cnt > 0)) flush();
 
@@ -1484,18 +1520,14 @@ __global__ void __launch_bounds__(256) place_packed_kernel(PlaceArgs a) {
         u64 win_key;
         int numBest = 0;
         if (RK_ABLATE & 2) { win_key = list[0]; for (u32 i = li; i <= nb; i += G) S[i] = S_UNTOUCHED; }
-        else numBest = select_topk<G>(S, nb, li, gi, (int)a.keep_at_most, list, (int)a.list_cap, win_key RK_STAMP_ARGS);
+        else numBest = select_topk<G>(S, nb, li, gi, (int)a.keep_at_most, list, (int)a.list_cap, win_key, stamps);
         wave_lds_fence();
-        RK_STAMP(5);  // select
-        const bool deferred = is_amb && a.has_ascii && !rejected;  // the ASCII kernel writes these
-        if (have && !deferred) weigh_and_store<G>(a, r, li, numBest, win_key, flags);
+        stamps.mark(5);  // select
+        if (have && !deferred(a, h)) weigh_and_store<G>(a, r, li, numBest, win_key, h.flags);
         asm volatile("" ::"v"(warm));  // keep the warming load alive
-        RK_STAMP(6);  // weigh + store
+        stamps.mark(6);  // weigh + store
     }
-#ifdef RK_STAMPS
-    if (lane == 0 && wave_global < 4096)
-        for (int i = 0; i < 16; i++) rk_stamp_buf[wave_global * 16 + i] = st_[i];
-#endif
+    if (lane == 0 && wave_global < 4096) stamps.store(wave_global);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1604,13 +1636,6 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             fin = a.flags_in ? a.flags_in[r] : 0u;
         }
     };
-    auto mer_count = [&](u32 R, u32 fin, bool have) -> u32 {  // Q = sk.getMerCount() (AmbigSequenceKnife.java:191)
-        const u32 cap_syms = (wpr * 32u) / BITS;
-        R = R < cap_syms ? R : cap_syms;
-        const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-        const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-        return (have && !is_amb && !rejected && R >= k) ? (R - k + 1) : 0u;
-    };
     auto fetch_batch = [&](u32 recw, u32 pos, u32 Q, u64 (&code)[PU], RawSlot (&raw)[PU]) {
         record_codes<BITS, PU>(recw, pos, li, k, Q, code);
 #pragma unroll
@@ -1625,10 +1650,7 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         }
     };
 
-#ifdef RK_STAMPS
-    unsigned long long st_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_ = rk_now();
-#endif
+    Stamps stamps;
     // prologue: the first tile's inputs and its first batch of descriptors
     u32 c_recw, c_R, c_fin;
     bool c_have;
@@ -1637,7 +1659,7 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         load_tile(wave_global, c_recw, c_R, c_fin, c_have);
         u64 code[PU];
         RawSlot raw[PU];
-        const u32 Q0 = mer_count(c_R, c_fin, c_have);
+        const u32 Q0 = read_head<BITS>(a, c_R, c_fin, c_have).Q;
         fetch_batch(c_recw, 0u, Q0, code, raw);
         decode_batch(code, raw, 0u, Q0, desc0);
     }
@@ -1646,17 +1668,9 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         const bool have = c_have;
         const u64 r = have ? tile_read(a, tile * NG + gi, perm_given) : 0ull;
         const u32 fin = c_fin;
-        u32 R = c_R;
-        {
-            const u32 cap_syms = (wpr * 32u) / BITS;
-            R = R < cap_syms ? R : cap_syms;
-        }
-        u32 flags = fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG);
-        const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-        const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-        if (R < k) flags |= RK_FLAG_TOO_SHORT;
-        const u32 Q = mer_count(c_R, fin, have);
-        const float QT = (float)(int)Q * T;  // int * float (PlacementProcess.java:728)
+        const ReadHead h = read_head<BITS>(a, c_R, fin, have);
+        const u32 Q = h.Q;
+        const float QT = h.QT;
 
         int cnt = 0;  // chunk items waiting in the list
         auto flush = [&]() {
@@ -1769,7 +1783,7 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             }
         };
 
-        RK_STAMP(0);  // tile setup
+        stamps.mark(0);  // tile setup
         emit_batch(desc0, Q > 0);
         for (u32 pos = PU * G; __any(pos < Q); pos += PU * G) {  // reads longer than PU*16 + k - 1 symbols
             u64 code[PU], desc[PU];
@@ -1779,36 +1793,32 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             decode_batch(code, raw, pos, Q, desc);
             emit_batch(desc, pos < Q);
         }
-        RK_STAMP(2);  // scans + item emission
+        stamps.mark(2);  // scans + item emission
         // next tile's inputs: in flight during this tile's accumulate phase
         load_tile(tile + wave_count, c_recw, c_R, c_fin, c_have);
         if (__any(cnt > 0)) flush();
-        RK_STAMP(4);  // accumulate (incl. its fences)
+        stamps.mark(4);  // accumulate (incl. its fences)
         // next tile's first batch of table gathers: in flight during this tile's select phase
         u64 ncode[PU];
         RawSlot nraw[PU];
-        const u32 nQ = mer_count(c_R, c_fin, c_have);
+        const u32 nQ = read_head<BITS>(a, c_R, c_fin, c_have).Q;
         fetch_batch(c_recw, 0u, nQ, ncode, nraw);
         __builtin_amdgcn_sched_barrier(0);
-        RK_STAMP(1);  // next tile's codes + gather issue
+        stamps.mark(1);  // next tile's codes + gather issue
 
         u64 win_key;
         int numBest = 0;
         if (RK_ABLATE & 2) { win_key = list[0]; for (u32 i = li; i <= nb; i += G) S[i] = S_UNTOUCHED; }  // (timing only)
-        else numBest = select_topk<G>(S, nb, li, gi, (int)a.keep_at_most, list, (int)a.list_cap, win_key RK_STAMP_ARGS);
+        else numBest = select_topk<G>(S, nb, li, gi, (int)a.keep_at_most, list, (int)a.list_cap, win_key, stamps);
         wave_lds_fence();
-        RK_STAMP(5);  // select (rest: reset)
+        stamps.mark(5);  // select (rest: reset)
         decode_batch(ncode, nraw, 0u, nQ, desc0);  // (before this tile's stores, so that the wait covers loads only)
         __builtin_amdgcn_sched_barrier(0);
-        RK_STAMP(3);  // decode of the next tile's descriptors (waits for its gathers)
-        const bool deferred = is_amb && a.has_ascii && !rejected;  // the ASCII kernel writes these
-        if (have && !deferred) weigh_and_store<G>(a, r, li, numBest, win_key, flags);
-        RK_STAMP(6);  // weigh + store
+        stamps.mark(3);  // decode of the next tile's descriptors (waits for its gathers)
+        if (have && !deferred(a, h)) weigh_and_store<G>(a, r, li, numBest, win_key, h.flags);
+        stamps.mark(6);  // weigh + store
     }
-#ifdef RK_STAMPS
-    if (lane == 0 && wave_global < 4096)
-        for (int i = 0; i < 16; i++) rk_stamp_buf[wave_global * 16 + i] = st_[i];
-#endif
+    if (lane == 0 && wave_global < 4096) stamps.store(wave_global);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1840,15 +1850,11 @@ constexpr int RETILE_BINS = 64;
 template <int BITS>
 __device__ __forceinline__ u32 retile_read_key(const PlaceArgs &a, u64 r, u32 &spread, u32 *with_row = nullptr) {
     const u32 k = a.db.k, wpr = a.words_per_read;
-    u32 R = a.lens ? a.lens[r] : a.fixed_len;
-    const u32 cap_syms = (wpr * 32u) / BITS;
-    R = R < cap_syms ? R : cap_syms;
-    const u32 fin = a.flags_in ? a.flags_in[r] : 0u;
-    const bool plain = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG)) == 0 && R >= k;
+    const ReadHead h = read_head<BITS>(a, a.lens ? a.lens[r] : a.fixed_len, a.flags_in ? a.flags_in[r] : 0u, true);
     u32 key = 0;
     spread = 0;
-    if (plain) {
-        const u32 Q = R - k + 1;
+    if (h.flags == 0u) {  // a read the packed kernels probe: not flagged, at least k symbols
+        const u32 Q = h.Q;
         const u32 *rec = a.packed + r * wpr;
         constexpr int NS = 7;
         u32 w[NS];
@@ -1994,9 +2000,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
 
     for (u32 i = li; i < a.s_stride; i += G) S[i] = S_UNTOUCHED;
     wave_lds_fence();
-#ifdef RK_STAMPS
-    unsigned long long st_[16] = {0}, t_ = rk_now();
-#endif
+    Stamps stamps;
 
     const u64 n_tiles = (a.n_reads + NG - 1) / NG;
     const u64 wave_global = (u64)blockIdx.x * waves_per_block + wave;
@@ -2012,13 +2016,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
             R = a.lens ? a.lens[r] : a.fixed_len;
             fin = a.flags_in ? a.flags_in[r] : 0u;
         }
-    };
-    auto mer_count = [&](u32 R, u32 fin, bool have) -> u32 {
-        const u32 cap_syms = (wpr * 32u) / BITS;
-        R = R < cap_syms ? R : cap_syms;
-        const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-        const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-        return (have && !is_amb && !rejected && R >= k) ? (R - k + 1) : 0u;
     };
     const u32 *c_rec = a.packed;  // the current tile's record in memory (records of more than 16 words do not fit one word per lane)
     auto fetch_batch = [&](u32 recw, u32 pos, u32 Q, u64 (&code)[PU], RawSlot (&raw)[PU], u32 (&wsr)[PU]) {
@@ -2092,18 +2089,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
         const u64 r = have ? tile_read(a, tile * NG + gi, perm_given) : 0ull;
         c_rec = a.packed + r * wpr;
         const u32 fin = c_fin;
-        u32 R = c_R;
-        {
-            const u32 cap_syms = (wpr * 32u) / BITS;
-            R = R < cap_syms ? R : cap_syms;
-        }
-        u32 flags = fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG);
-        const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-        const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-        if (R < k) flags |= RK_FLAG_TOO_SHORT;
-        const u32 Q = mer_count(c_R, fin, have);
-        const float QT = (float)(int)Q * T;
-        RK_STAMP(0);  // tile setup
+        const ReadHead h = read_head<BITS>(a, c_R, fin, have);
+        const u32 Q = h.Q;
+        const float QT = h.QT;
+        stamps.mark(0);  // tile setup
 
         // ---- emit: every row unit of the read whose row reaches a window of [wa, wb) -> one tagged item of the main list, k-mer
         //      order.  Called with all windows first; if some read of the tile does not fit its main list, the window range is cut
@@ -2175,16 +2164,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
                     const int wcnt = wave_max4(wc);
                     for (int i = wc + (int)li; i < wcnt + 2 * U; i += G) work[i] = ITEM_FILLER;
                     wave_lds_fence();
-                    RK_STAMP(2);  // window compaction
+                    stamps.mark(2);  // window compaction
                     if (!(RK_ABLATE & 512)) {
                         if (a.db.mono) accumulate_units<G, U, true, true>(S, work, wcnt, li, rows_rs, QT, T, wlo4p4, w4);
                         else accumulate_units<G, U, false, true>(S, work, wcnt, li, rows_rs, QT, T, wlo4p4, w4);
                     }
                     wave_lds_fence();
-                    RK_STAMP(3);  // window accumulate
-#ifdef RK_STAMPS
-                    st_[10] += (unsigned long long)wcnt; st_[11] += 1; st_[12] += (unsigned long long)wc;
-#endif
+                    stamps.mark(3);  // window accumulate
+                    stamps.add(10, wcnt); stamps.add(11, 1); stamps.add(12, wc);
                     wc = 0;
                 };
                 // (one item per lane and chunk: ranks inside a group by ballot + mbcnt; the next chunk's items are read ahead so that
@@ -2205,7 +2192,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
                     wc += __builtin_popcount((u32)mg) + __builtin_popcount((u32)(mg >> 32));
                 }
                 if (__any(wc > 0)) flushw();
-                RK_STAMP(2);
+                stamps.mark(2);
             } else {
                 // ---- fallback: probe the read again for this window; rows that touch it go through the row cursor ----
                 int rc = 0;
@@ -2268,7 +2255,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
                     tile_windows = ((u64)group_or((u32)(touched >> 32)) << 32) | group_or((u32)touched);
                     if (RK_ABLATE & 4096) tile_windows = ~0ull;
                     load_tile(tile + wave_count, n_recw, n_R, n_fin, n_have);
-                    RK_STAMP(1);  // probe + emit
+                    stamps.mark(1);  // probe + emit
                     if (overflow) {  // the whole tree does not fit: start over in as many ranges as the largest read needs (part becomes 0 again)
                         u32 n = all_items + row_ror32<8>(all_items);
                         n += row_ror32<4>(n);
@@ -2291,12 +2278,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
                     if (phase == 0) {
                         heads_scan_reset<G>(S, win_n, li, wlo, hd);
                         wave_lds_fence();
-                        RK_STAMP(4);  // window scan + reset
+                        stamps.mark(4);  // window scan + reset
                         continue;
                     }
                     // ---- exact select over the window, merged into the K best so far ----
                     u64 win_key = 0;
-                    if (!(RK_ABLATE & 1024) || w + 1 == NWIN) select_topk<G>(S, win_n, li, gi, K, work64, (int)(a.work_cap / 2), win_key RK_STAMP_ARGS);  // (timing only)
+                    if (!(RK_ABLATE & 1024) || w + 1 == NWIN) select_topk<G>(S, win_n, li, gi, K, work64, (int)(a.work_cap / 2), win_key, stamps);  // (timing only)
                     wave_lds_fence();
                     if (win_key != 0ull) win_key -= (u64)wlo;  // window-relative branch -> tree id (low 16 bits hold 0xFFFF - branch)
                     if (K <= 8) {  // both sets fit the 16 lanes: ranks by counting over lane rotations
@@ -2332,13 +2319,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
             }
             if (phase == 0) {
                 heads_rounds<G>(hd, K, li, gi, acc_key, doubt);
-                RK_STAMP(5);  // rounds
+                stamps.mark(5);  // rounds
             }
         }
         const int numBest = __builtin_popcountll(group_bits<G>(__ballot(acc_key != 0ull), gi));
-        const bool deferred = is_amb && a.has_ascii && !rejected;  // the ASCII kernel writes these
-        RK_STAMP(6);  // redo of tiles in doubt
-        if (have && !deferred) weigh_and_store<G>(a, r, li, numBest, acc_key, flags);
+        stamps.mark(6);  // redo of tiles in doubt
+        if (have && !deferred(a, h)) weigh_and_store<G>(a, r, li, numBest, acc_key, h.flags);
         if (queued) {
             tile = take_marked();
             load_tile(tile, c_recw, c_R, c_fin, c_have);
@@ -2346,12 +2332,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
             tile += wave_count;
             c_recw = n_recw; c_R = n_R; c_fin = n_fin; c_have = n_have;  // (loaded behind this tile's probe)
         }
-        RK_STAMP(7);  // weigh + store
+        stamps.mark(7);  // weigh + store
     }
-#ifdef RK_STAMPS
-    if (lane == 0 && wave_global < 4096)
-        for (int i = 0; i < 16; i++) rk_stamp_buf[(a.only_marked ? 4096 * 16 : 0) + wave_global * 16 + i] = st_[i];
-#endif
+    if (lane == 0 && wave_global < 4096) stamps.store((a.only_marked ? 4096u : 0u) + wave_global);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2405,9 +2388,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
     const int list_usable = (int)a.main_cap - 3 * U;
     u32 *bm = tlw;  // the current window's touched bitmap (words li and, windows over 512 slots, G + li are lane li's)
 
-#ifdef RK_STAMPS
-    unsigned long long st_[16] = {0}, t_ = rk_now();
-#endif
+    Stamps stamps;
 
     const u64 n_tiles = (a.n_reads + NG - 1) / NG;
     const u64 wave_global = (u64)blockIdx.x * waves_per_block + wave;
@@ -2440,20 +2421,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
         const bool have = c_have;
         const u64 r = have ? tile_read(a, tile * NG + gi, perm_given) : 0ull;
         const u32 fin = c_fin, recw = c_recw;
-        u32 R = c_R;
-        {
-            const u32 cap_syms = (wpr * 32u) / BITS;
-            R = R < cap_syms ? R : cap_syms;
-        }
-        u32 flags = fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG);
-        const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-        const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-        if (R < k) flags |= RK_FLAG_TOO_SHORT;
-        const u32 Q = (have && !is_amb && !rejected && R >= k) ? (R - k + 1) : 0u;
-        const float QT = (float)(int)Q * T;
+        const ReadHead h = read_head<BITS>(a, c_R, fin, have);
+        const u32 Q = h.Q;
+        const float QT = h.QT;
         // the next tile's inputs travel while this one is worked on
         load_tile(tile + wave_count, c_recw, c_R, c_fin, c_have);
-        RK_STAMP(0);  // tile setup
+        stamps.mark(0);  // tile setup
 
         // ---- probe: one batch holds the whole read ----
         bool defer = __any(Q > (u32)(PU * G));
@@ -2485,7 +2458,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
             }
         }
         defer = __any(defer);
-        RK_STAMP(4);  // (diagnostic split of the emit: probe)
+        stamps.mark(4);  // (diagnostic split of the emit: probe)
         // ---- units per window and read: tlw[w], w < 64 ----
         *(uint4 *)(tlw + 4 * li) = make_uint4(0u, 0u, 0u, 0u);
         u32 *idle = tlw + 64 + li;  // a word of the lane's own, always 0: where the lanes whose turn it is not add nothing
@@ -2521,17 +2494,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
         }
         defer = defer || total > list_usable;
         if (defer) {  // wave-uniform
-#ifdef RK_STAMPS
-            st_[10] += 1;
-#endif
+            stamps.add(10, 1);
             if (lane == 0) a.tile_marks[tile] = 1;
             wave_lds_fence();
             continue;
         }
         const u64 nonempty = __ballot(seg_len != 0u);
-#ifdef RK_STAMPS
-        st_[11] += 1; st_[12] += (unsigned long long)total;
-#endif
+        stamps.add(11, 1); stamps.add(12, total);
         wave_lds_fence();  // (every lane has read the counters)
         {   // running place of every window, per read: starts at the segment's start
             u32 *t0 = wbase + NG * (a.s_stride + a.main_cap);
@@ -2540,7 +2509,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
         }
         for (int i = (int)li; i < total + 3 * U; i += G) items[i] = ITEM_FILLER;
         wave_lds_fence();
-        RK_STAMP(8);  // (counts, segments, fillers)
+        stamps.mark(8);  // (counts, segments, fillers)
         // ---- places: one returning add per row and window, in k-mer order (u-major, then the lanes of the group in turn: LDS
         //      operations of a wave execute in program order).  Every turn has a result register of its own, so that the sixteen
         //      adds of a slot are issued back to back (one register for all of them made every add wait for the one before);
@@ -2592,7 +2561,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
             }
         }
         wave_lds_fence();
-        RK_STAMP(9);  // (places + items)
+        stamps.mark(9);  // (places + items)
         // the counters have done their work: their first words become the touched bitmap; every slot of S starts from this read's Q * T
         const u32 QTbits = __float_as_uint(QT);
         bm[li] = 0u;
@@ -2603,7 +2572,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
             for (u32 q = li; q < a.s_stride / 4u; q += G) S4[q] = q4;
         }
         wave_lds_fence();
-        RK_STAMP(1);  // probe + emit + sort
+        stamps.mark(1);  // probe + emit + sort
 
         // ---- the stream ----
         const u32 li8 = li * 8, li4 = li * 4;
@@ -2751,17 +2720,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
                 }
                 if (s0 < bound) {  // the window ends in the middle of a turn: the next one (never empty) starts with the other half
                     half_turn(std::true_type());
-                    RK_STAMP(3);  // stream steps
+                    stamps.mark(3);  // stream steps
                     finish_window();
                     asm volatile("; window end, ring at its half turn");  // (two different markers: the copies must not be merged again)
-                    RK_STAMP(2);  // touched-slot select of the window
+                    stamps.mark(2);  // touched-slot select of the window
                     half_turn(std::false_type());  // (after the last window: four fillers -- an early way out of the loop here would be one
                                                    //  more path into its head with the ring in another order, and the waits would be for that)
                 } else {
-                    RK_STAMP(3);
+                    stamps.mark(3);
                     finish_window();
                     asm volatile("; window end, ring at its start");
-                    RK_STAMP(2);
+                    stamps.mark(2);
                 }
             }
         };
@@ -2786,15 +2755,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
                 acc_key = ((int)li < num) ? (((u64)win_o << 32) | (u64)(0xFFFFu - (win_i - 1u))) : 0ull;
                 const bool tie = tie_v != -INFINITY && ord_f32(tie_v) >= kth_o;
                 doubt = d0 || group_bits<G>(__ballot(tie), gi) != 0;
-#ifdef RK_STAMPS
-                st_[13] += __any(d0) ? 1 : 0;   // (diagnostic: tiles in doubt because of a dropped candidate, as against a tie)
-#endif
-                RK_STAMP(5);  // rounds
+                stamps.add(13, __any(d0) ? 1 : 0);   // (diagnostic: tiles in doubt because of a dropped candidate, as against a tie)
+                stamps.mark(5);  // rounds
         }
         if (__any(doubt)) {
-#ifdef RK_STAMPS
-            st_[15] += 1;
-#endif
+            stamps.add(15, 1);
             {
                 const int num0 = __builtin_popcountll(group_bits<G>(__ballot(acc_key != 0ull), gi));
                 u32 t_o = acc_key != 0ull ? ~(u32)(acc_key >> 32) : 0u;  // smallest ordered score among the winners = largest complement
@@ -2833,21 +2798,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BITS =
         }
         if (__any(cand_over)) {  // (wave-uniform) rare twice over: the tile is left to place_packed16w_kernel; S is in its reset state
             if (lane == 0) a.tile_marks[tile] = 1;
-#ifdef RK_STAMPS
-            st_[10] += 1;
-#endif
+            stamps.add(10, 1);
             continue;
         }
         const int numBest = __builtin_popcountll(group_bits<G>(__ballot(acc_key != 0ull), gi));
-        const bool deferred = is_amb && a.has_ascii && !rejected;  // the ASCII kernel writes these
-        RK_STAMP(6);  // redo of tiles in doubt
-        if (have && !deferred) weigh_and_store<G>(a, r, li, numBest, acc_key, flags);
-        RK_STAMP(7);  // weigh + store
+        stamps.mark(6);  // redo of tiles in doubt
+        if (have && !deferred(a, h)) weigh_and_store<G>(a, r, li, numBest, acc_key, h.flags);
+        stamps.mark(7);  // weigh + store
     }
-#ifdef RK_STAMPS
-    if (lane == 0 && wave_global < 4096)
-        for (int i = 0; i < 16; i++) rk_stamp_buf[wave_global * 16 + i] = st_[i];
-#endif
+    if (lane == 0 && wave_global < 4096) stamps.store(wave_global);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2896,9 +2855,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
     const int cap_items = (int)a.main_cap - 12 * U * NPL - 8;  // fillers behind the last step + the read-ahead of the ring
     const int capc = (int)(a.main_cap / 2) - 16;         // candidate keys of a read in doubt (u64), the last 16 = the winners
     const u32 key_limit = a.work_cap;                    // keys the table may hold (< NS: a probe always finds an empty slot)
-#ifdef RK_STAMPS
-    unsigned long long st_[16] = {0}, t_ = rk_now();
-#endif
+    Stamps stamps;
     auto wave_scan = [&](u32 v, u32 &tot) {  // inclusive prefix sum over the wave's 64 lanes + the total
         v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
         v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
@@ -2935,16 +2892,9 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
             r = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(r >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)r);
             u32 R = (u32)__builtin_amdgcn_readfirstlane((int)(a.lens ? a.lens[r] : a.fixed_len));  // (wave-uniform: one read per wave)
             const u32 fin = (u32)__builtin_amdgcn_readfirstlane((int)(a.flags_in ? a.flags_in[r] : 0u));
-            {
-                const u32 cap_syms = (wpr * 32u) / BITS;
-                R = R < cap_syms ? R : cap_syms;
-            }
-            u32 flags = fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG);
-            const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-            const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-            if (R < k) flags |= RK_FLAG_TOO_SHORT;
-            const u32 Q = (!is_amb && !rejected && R >= k) ? (R - k + 1) : 0u;  // sk.getMerCount() (AmbigSequenceKnife.java:191)
-            const float QT = (float)(int)Q * T;                                  // int * float (PlacementProcess.java:728)
+            const ReadHead h = read_head<BITS>(a, R, fin, true);
+            const u32 Q = h.Q;
+            const float QT = h.QT;
             const u32 *rec = a.packed + r * wpr;
             // ---- the table: empty keys, every value the read's Q * T ----
             {
@@ -2959,7 +2909,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                 keys[NS + lane] = 0u;
             }
             wave_lds_fence();
-            RK_STAMP(0);  // read setup + table reset
+            stamps.mark(0);  // read setup + table reset
 
             bool over = false;  // (wave-uniform) the read does not fit: table, list or candidates
             u32 n_keys = 0;     // (wave-uniform) an upper bound of the keys in the table: the entries applied so far (recounted when it matters)
@@ -3005,9 +2955,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                     }
                     n_keys += n_act;
                 }
-#ifdef RK_STAMPS
-                st_[15] += 1;
-#endif
+                stamps.add(15, 1);
                 // Every lane that is still looking has failed in every round so far, so the distance of its next hop -- triangular
                 // probing: 1, 2, 3 ... slots, every slot is visited -- is the round's number: one scalar for the wave.
                 // Two rounds with all of the step's 64 * NPL entries; the few that are still looking after those (a table at 0.33 mean /
@@ -3018,9 +2966,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                 u64 pend[NPL], pending = 0ull;
 #pragma unroll
                 for (int r = 0; r < 2; r++) {
-#ifdef RK_STAMPS
-                    st_[14] += 1;
-#endif
+                    stamps.add(14, 1);
                     hop4 += 4u;
                     u32 old[NPL];
 #pragma unroll
@@ -3051,9 +2997,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                     u32 hopm = 8u;
                     u64 pm;
                     do {
-#ifdef RK_STAMPS
-                        st_[9] += 1;
-#endif
+                        stamps.add(9, 1);
                         hopm += 4u;
                         u32 oldm[1];
                         oldm[0] = lds_cas_issue(hm, 0u, km);
@@ -3097,9 +3041,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
 #pragma unroll
                     for (int p = 0; p < NPL; p++) *(u32 *)((unsigned char *)lds + at[p]) = mask_select(0u, __float_as_uint(v[p] + d[p]), act[p]);
                 } else {  // the step's units one after the other: k-mer order per branch
-#ifdef RK_STAMPS
-                    st_[12] += 1;
-#endif
+                    stamps.add(12, 1);
                     // (a round under the row's exec mask: the other rows issue nothing, padding lanes of the row add 0 to their own word)
 #pragma unroll
                     for (int p = 0; p < NPL; p++) {
@@ -3126,7 +3068,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                 const int steps = (cnt + 4 * NPL - 1) / (4 * NPL);
                 for (int i = cnt + (int)lane; i < 4 * NPL * (steps + 2 * U); i += 64) items[i] = ITEM_FILLER;
                 wave_lds_fence();
-                RK_STAMP(2);  // emit
+                stamps.mark(2);  // emit
                 const u32 *my = items + gi;  // entry p of this lane in step s: unit my[4 (NPL s + p)]
                 u32 sb[U][NPL], it[U][NPL];
                 float sc[U][NPL];
@@ -3154,7 +3096,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                 }
                 wave_lds_fence();
                 cnt = 0;
-                RK_STAMP(3);  // accumulate
+                stamps.mark(3);  // accumulate
             };
 
             // ---- probe + emit, PU * 64 k-mers at a time ----
@@ -3178,7 +3120,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                     nch[u] = (((u32)d & DESC_LEN_MASK) + 15u) >> 4;
                     rb[u] = (u32)(d >> DESC_LEN_BITS) * 8u;  // byte offset of the row's first 128-byte unit
                 }
-                RK_STAMP(1);  // probe
+                stamps.mark(1);  // probe
                 u32 incl[PU], tot[PU];
 #pragma unroll
                 for (int u = 0; u < PU; u++) incl[u] = wave_scan(nch[u], tot[u]);
@@ -3219,7 +3161,7 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                     heads_feed<2>(hd, kq.z ? __uint_as_float(vq.z) : -INFINITY, kq.z & KEY_MASK);
                     heads_feed<3>(hd, kq.w ? __uint_as_float(vq.w) : -INFINITY, kq.w & KEY_MASK);
                 }
-                RK_STAMP(4);  // table scan
+                stamps.mark(4);  // table scan
                 // equal scores inside one stream arrive in table order, not in branch order: seen at the end (place_packed16s_kernel)
                 float tie_v = -INFINITY;
 #pragma unroll
@@ -3232,13 +3174,11 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                 const int num = heads_rounds_raw<64, true>(hd, K, lane, 0u, win_o, win_i, d0, &kth_o);
                 acc_key = ((int)lane < num) ? (((u64)win_o << 32) | (u64)(0xFFFFu - (win_i - 1u))) : 0ull;
                 const bool tie = tie_v != -INFINITY && ord_f32(tie_v) >= kth_o;
-                RK_STAMP(5);  // rounds
+                stamps.mark(5);  // rounds
                 if (d0 || __any(tie)) {
                     // ---- a read in doubt: every entry at or above the K-th score is a candidate (the true K best are among them),
                     //      ranked exactly (keys are unique: they embed the branch) ----
-#ifdef RK_STAMPS
-                    st_[13] += 1;
-#endif
+                    stamps.add(13, 1);
                     u64 *cl = (u64 *)items, *win = cl + capc;
                     if (lane < 16u) win[lane] = 0ull;
                     int c = 0;
@@ -3268,31 +3208,23 @@ __global__ void __launch_bounds__(64) place_hash64_kernel(PlaceArgs a) {
                         acc_key = (int)lane < K ? win[lane] : 0ull;
                         wave_lds_fence();
                     }
-                    RK_STAMP(6);  // exact ranking of a read in doubt
+                    stamps.mark(6);  // exact ranking of a read in doubt
                 }
             }
             if (over) {
-#ifdef RK_STAMPS
-                st_[10] += 1;
-#endif
+                stamps.add(10, 1);
                 handed = true;
                 continue;
             }
-#ifdef RK_STAMPS
-            st_[11] += 1;
-#endif
+            stamps.add(11, 1);
             const int numBest = __builtin_popcountll(__ballot(acc_key != 0ull));
-            const bool deferred = is_amb && a.has_ascii && !rejected;  // the ASCII kernel writes these
             // (keep_at_most <= 16: the winners sit in the wave's first 16-lane row -- the DPP form of the weighing; the other rows idle)
-            if (!deferred) weigh_and_store<16>(a, r, lane, numBest, acc_key, flags);
-            RK_STAMP(7);  // weigh + store
+            if (!deferred(a, h)) weigh_and_store<16>(a, r, lane, numBest, acc_key, h.flags);
+            stamps.mark(7);  // weigh + store
         }
         if (handed && lane == 0) a.tile_marks[tile] = 1;
     }
-#ifdef RK_STAMPS
-    if (lane == 0 && blockIdx.x < 4096)
-        for (int i = 0; i < 16; i++) rk_stamp_buf[(u64)blockIdx.x * 16 + i] = st_[i];
-#endif
+    if (lane == 0 && blockIdx.x < 4096) stamps.store(blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3483,21 +3415,14 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
     const uint4 reset4 = make_uint4(S_UNTOUCHED, S_UNTOUCHED, S_UNTOUCHED, S_UNTOUCHED);
     for (u32 i = tid; i < a.s_stride; i += blockDim.x) S[i] = S_UNTOUCHED;
     wg_barrier_lds();
-#ifdef RK_STAMPS
-    unsigned long long st_[16] = {0}, t_ = rk_now();
-#endif
+    Stamps stamps;
 
     for (u64 r = blockIdx.x; r < a.n_reads; r += gridDim.x) {
         u32 R = a.lens ? a.lens[r] : a.fixed_len;
-        const u32 cap_syms = (a.words_per_read * 32u) / BITS;  // never read past the packed record
-        R = R < cap_syms ? R : cap_syms;
         const u32 fin = a.flags_in ? a.flags_in[r] : 0u;
-        u32 flags = fin & (RK_FLAG_BAD_CHAR | RK_FLAG_AMBIGUOUS | RK_FLAG_TOO_LONG);
-        const bool is_amb = (fin & RK_FLAG_AMBIGUOUS) != 0;
-        const bool rejected = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG)) != 0;
-        if (R < k) flags |= RK_FLAG_TOO_SHORT;
-        const u32 Q = (!is_amb && !rejected && R >= k) ? (R - k + 1) : 0u;
-        const float QT = (float)(int)Q * T;
+        const ReadHead h = read_head<BITS>(a, R, fin, true);
+        const u32 Q = h.Q;
+        const float QT = h.QT;
         const u32 *rec = a.packed + r * a.words_per_read;
 
         for (u32 pass = 0; pass < P; pass++) {
@@ -3522,7 +3447,7 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
                     desc = lookup_desc<BITS, TM>(a.db, extract_code<BITS>(rec, a.words_per_read, j, k));
                 }
                 const bool hit = ((u32)desc & DESC_LEN_MASK) != 0;
-                RK_STAMP(0);  // probe (record words, table)
+                stamps.mark(0);  // probe (record words, table)
                 const u64 bal = __ballot(hit);
                 if (lane == 0) wcnt[wave] = (u32)__builtin_popcountll(bal);
                 wg_barrier_lds();
@@ -3534,7 +3459,7 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
                 }
                 if (hit) list[hbase + count_below<64>(bal, lane)] = desc;
                 wg_barrier_lds();
-                RK_STAMP(1);  // compaction of the hits (two barriers)
+                stamps.mark(1);  // compaction of the hits (two barriers)
                 // ---- accumulate: every wave applies its branch range of every row, rows in k-mer order ----
                 // every wave's slices of the batch's rows first (the only reads of the hit list), then a barrier: from here on the list
                 // is free -- a wave that is through with its range leaves its winners there while others still stream
@@ -3542,9 +3467,9 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
                 WaveSlices<WIDE> ws;
                 if (work) wave_slices<WIDE>(ws, list, (int)cnt, lane, q_lo, q_hi, a.db.rows);
                 wg_barrier_lds();
-                RK_STAMP(3);  // slices of the batch's rows (index lines)
+                stamps.mark(3);  // slices of the batch's rows (index lines)
                 if (work) wave_accumulate<WIDE, U>(S, win, base, ws, lane, a.db.rows, QT, T);
-                RK_STAMP(2);  // accumulate (this wave's branch range)
+                stamps.mark(2);  // accumulate (this wave's branch range)
                 if (pos0 + batch < Q) wg_barrier_lds();  // (the list is rewritten by the next batch's probe)
             }
 
@@ -3558,9 +3483,7 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
             int num = heads_rounds_raw<64>(hd, K, lane, 0u, win_o, win_i, doubt);
             u64 wkey = ((int)lane < num) ? (((u64)win_o << 32) | (u64)(0xFFFFu - (win_i + base))) : 0ull;
             if (__any(doubt)) {
-#ifdef RK_STAMPS
-                st_[12] += 1;
-#endif
+                stamps.add(12, 1);
                 // A stream dropped an entry that could be among the K best.  The K-th key the heads did find is a lower bound of the
                 // true K-th (it is a real entry), so every true winner is at or above it: one more pass over the segment keeps those
                 // entries -- two a lane, in registers -- and K rounds of wave maxima rank them exactly.  A lane with more than two (or
@@ -3587,9 +3510,7 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
                     }
                 }
                 if (__any(over)) {
-#ifdef RK_STAMPS
-                    st_[13] += 1;
-#endif
+                    stamps.add(13, 1);
                     num = select_rounds64(S, base, s0, s1, lane, K, wkey);
                 } else {
                     num = 0;
@@ -3612,9 +3533,9 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
                     for (u32 e = 0; e < 4; e++)
                         if (4 * q + e >= s0 && 4 * q + e < s1) S[4 * q + e] = S_UNTOUCHED;
             }
-            RK_STAMP(4);  // level-1 select of this wave's segment
+            stamps.mark(4);  // level-1 select of this wave's segment
             wg_barrier_lds();
-            RK_STAMP(5);  // barrier behind it
+            stamps.mark(5);  // barrier behind it
         }
         // ---- select, level 2 (wave 0): exact top-K of the n_pass*NW*K wave winners, then weights and output rows ----
         if (wave == 0) {
@@ -3646,22 +3567,16 @@ __global__ void __launch_bounds__(1024) place_wg_kernel(PlaceArgs a) {
                 win_key = ((int)lane < K) ? win[lane] : 0ull;
                 numBest = __builtin_popcountll(__ballot(win_key != 0));
             }
-            const bool deferred = is_amb && a.has_ascii && !rejected;  // the ASCII kernel writes these
-            RK_STAMP(8);  // level-2 select (wave 0)
+            stamps.mark(8);  // level-2 select (wave 0)
             // (keep_at_most <= 16: the winners sit in the wave's first 16-lane row -- the DPP form of the weighing)
-            if (!deferred) weigh_and_store<16>(a, r, lane, numBest, win_key, flags);
+            if (!deferred(a, h)) weigh_and_store<16>(a, r, lane, numBest, win_key, h.flags);
         }
-        RK_STAMP(6);  // weights + store (wave 0)
+        stamps.mark(6);  // weights + store (wave 0)
         wg_barrier_lds();
-        RK_STAMP(7);  // the other waves waiting for it
-#ifdef RK_STAMPS
-        st_[11] += 1;
-#endif
+        stamps.mark(7);  // the other waves waiting for it
+        stamps.add(11, 1);
     }
-#ifdef RK_STAMPS
-    if (lane == 0 && blockIdx.x < 512 && (wave == 0 || wave == NW - 1))
-        for (int i = 0; i < 16; i++) rk_stamp_buf[((u64)blockIdx.x * 2 + (wave ? 1 : 0)) * 16 + i] = st_[i];
-#endif
+    if (lane == 0 && blockIdx.x < 512 && (wave == 0 || wave == NW - 1)) stamps.store((u64)blockIdx.x * 2 + (wave ? 1 : 0));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3932,9 +3847,7 @@ __global__ void __launch_bounds__(64) place_ascii_kernel(PlaceArgs a, AmbArgs m_
     m.alt_count = alt_l + 320;
     m.char_table = alt_l + 336;
     wave_lds_fence();
-#ifdef RK_STAMPS
-    unsigned long long st_[16] = {0}, t_ = rk_now();
-#endif
+    Stamps stamps;
 
     for (u64 r0 = (u64)blockIdx.x * 64; r0 < a.n_reads; r0 += (u64)gridDim.x * 64) {
         // each lane inspects one read's flag; the wave then serves the flagged ones in turn
@@ -4042,7 +3955,7 @@ __global__ void __launch_bounds__(64) place_ascii_kernel(PlaceArgs a, AmbArgs m_
                     u64 amb_b = __ballot(inr && ambmask != 0);
                     const u64 hit_b = __ballot(hit);
                     u32 p0 = 0;
-                    RK_STAMP(1);  // decode + probes of the batch
+                    stamps.mark(1);  // decode + probes of the batch
                     while (true) {  // wave-uniform: runs of unambiguous positions separated by ambiguous ones
                         const u32 na = amb_b ? (u32)__builtin_ctzll(amb_b) : 64u;
                         const u64 hb = hit_b & bits_below((u32)na) & ~bits_below((u32)p0);
@@ -4051,10 +3964,10 @@ __global__ void __launch_bounds__(64) place_ascii_kernel(PlaceArgs a, AmbArgs m_
                         if (lane_bit(hb, lane)) clist[cnt + count_below<64>(hb, lane)] = desc;
                         cnt += nh;
                         any_long = any_long || __any(lane_bit(hb, lane) && ((u32)desc & DESC_LEN_MASK) > 64u);
-                        RK_STAMP(2);  // list building
+                        stamps.mark(2);  // list building
                         if (na >= 64) break;
                         flush();  // everything before the ambiguous k-mer must be applied first
-                        RK_STAMP(3);  // flush (accumulate)
+                        stamps.mark(3);  // flush (accumulate)
                         const u32 maskA = (u32)__builtin_amdgcn_readlane((int)ambmask, (int)na);
                         const u32 clo = (u32)__builtin_amdgcn_readlane((int)(u32)code, (int)na);
                         const u32 chi = (u32)__builtin_amdgcn_readlane((int)(u32)(code >> 32), (int)na);
@@ -4073,7 +3986,7 @@ __global__ void __launch_bounds__(64) place_ascii_kernel(PlaceArgs a, AmbArgs m_
                                          (u32)__builtin_amdgcn_readlane((int)(u32)alt_d[w], (int)na);
                             if (!(RK_ABLATE & 128)) amb_position<BITS, TM>(a, m, S, Samb, Camb, chunk, codeA, p, cls, lane, QT, have_pre, pre, s_lo, nb, p2, cls2);
                         }
-                        RK_STAMP(4);  // ambiguous position
+                        stamps.mark(4);  // ambiguous position
                         amb_b &= amb_b - 1;
                         p0 = na + 1;
                         if (p0 >= 64) break;
@@ -4082,9 +3995,9 @@ __global__ void __launch_bounds__(64) place_ascii_kernel(PlaceArgs a, AmbArgs m_
                 flush();
                 wave_lds_fence();
                 u64 win_key;
-                RK_STAMP(3);  // last flush
-                select_topk<64>(S, nb, lane, 0u, K, clist, ASCII_LIST_CAP, win_key RK_STAMP_ARGS);
-                RK_STAMP(5);
+                stamps.mark(3);  // last flush
+                select_topk<64>(S, nb, lane, 0u, K, clist, ASCII_LIST_CAP, win_key, stamps);
+                stamps.mark(5);
                 wave_lds_fence();
                 if (win_key != 0) win_key -= s_lo;  // the key's low 16 bits hold 0xFFFF - branch: window-relative -> tree id
                 if (n_win == 1) {
@@ -4100,17 +4013,12 @@ __global__ void __launch_bounds__(64) place_ascii_kernel(PlaceArgs a, AmbArgs m_
             }
             const int numBest = __builtin_popcountll(__ballot(acc_key != 0));
             weigh_and_store<64>(a, r, lane, numBest, acc_key, flags);
-            RK_STAMP(6);
-#ifdef RK_STAMPS
-            st_[10] += 1;
-#endif
+            stamps.mark(6);
+            stamps.add(10, 1);
         }
-        RK_STAMP(0);  // flag inspection, idle lanes
+        stamps.mark(0);  // flag inspection, idle lanes
     }
-#ifdef RK_STAMPS
-    if (lane == 0 && blockIdx.x < 4096)
-        for (int i = 0; i < 16; i++) rk_stamp_buf[blockIdx.x * 16 + i] = st_[i];
-#endif
+    if (lane == 0 && blockIdx.x < 4096) stamps.store(blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -4129,8 +4037,7 @@ __global__ void __launch_bounds__(256) count_work_kernel(DbView db, const u32 *p
     unsigned long long probed = 0, hits = 0, entries = 0;  // (per lane; summed over the wave at the end)
     for (u64 r = wave_global; r < n_reads; r += wave_count) {
         u32 R = lens ? lens[r] : fixed_len;
-        const u32 cap_syms = (wpr * 32u) / BITS;
-        R = R < cap_syms ? R : cap_syms;
+        clamp_len<BITS>(R, wpr);
         const u32 fin = flags_in ? flags_in[r] : 0u;
         const bool skip = (fin & (RK_FLAG_BAD_CHAR | RK_FLAG_TOO_LONG | RK_FLAG_AMBIGUOUS)) != 0 || R < k;
         const u32 Q = skip ? 0u : R - k + 1;
@@ -4302,34 +4209,38 @@ __global__ void __launch_bounds__(256) revcomp_ascii_kernel(const unsigned char 
     }
 }
 
-// merge_strands_kernel: per read the better of the two strands' results, in place in the forward set.  A wave takes 64 reads: every
-// lane decides one of them (reverse iff it has rows and forward has none or a smaller best score; a tie keeps forward) BEFORE any
-// row of these reads is written, then the wave copies the K rows of the reads that switch, lane after lane along the arrays.
-__global__ void __launch_bounds__(256) merge_strands_kernel(u64 n_reads, u32 K, unsigned char *f_nrows, unsigned short *f_branch, float *f_score,
-                                                            double *f_lwr, u32 *f_flags, const unsigned char *r_nrows, const unsigned short *r_branch,
-                                                            const float *r_score, const double *r_lwr, const u32 *r_flags) {
+// merge_results_kernel: per read the better of two result sets, in place in `best` -- the two strands and the frames of a
+// translated read (4.6) alike.  A wave takes 64 reads: every lane decides one of them (the candidate iff it has rows and the best has
+// none or a smaller best score; a tie keeps the best so far: forward, the earlier frame) BEFORE any row of these reads is written,
+// then the wave copies the K rows of the reads that switch, lane after lane along the arrays.  A read that switches gets `mark`
+// (RK_FLAG_REVERSE or nothing) in its flags and, where the caller keeps a frame byte per read, `frame_id` there.
+__global__ void __launch_bounds__(256) merge_results_kernel(u64 n_reads, u32 K, unsigned char *b_nrows, unsigned short *b_branch, float *b_score,
+                                                            double *b_lwr, u32 *b_flags, unsigned char *b_frame, const unsigned char *c_nrows,
+                                                            const unsigned short *c_branch, const float *c_score, const double *c_lwr,
+                                                            const u32 *c_flags, u32 mark, u32 frame_id) {
     const u32 lane = threadIdx.x & 63;
     const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
     for (u64 r0 = wave * 64; r0 < n_reads; r0 += n_waves * 64) {
         const u64 r = r0 + lane;
         int take = 0;
         if (r < n_reads) {
-            const u32 nr = r_nrows[r], nf = f_nrows[r];
-            take = nr > 0 && (nf == 0 || r_score[r * K] > f_score[r * K]);
+            const u32 nc = c_nrows[r], nb = b_nrows[r];
+            take = nc > 0 && (nb == 0 || c_score[r * K] > b_score[r * K]);
         }
         for (u32 e = lane; e < 64u * K; e += 64) {  // (uniform trip count: the shuffle below is executed by the whole wave)
             const u32 rr = e / K;
             const int t = __shfl(take, (int)rr, 64);
             const u64 g = r0 * K + e;
             if (t && r0 + rr < n_reads) {
-                f_branch[g] = r_branch[g];
-                f_score[g] = r_score[g];
-                f_lwr[g] = r_lwr[g];
+                b_branch[g] = c_branch[g];
+                b_score[g] = c_score[g];
+                b_lwr[g] = c_lwr[g];
             }
         }
         if (take) {
-            f_nrows[r] = r_nrows[r];
-            f_flags[r] = r_flags[r] | RK_FLAG_REVERSE;
+            b_nrows[r] = c_nrows[r];
+            b_flags[r] = c_flags[r] | mark;
+            if (b_frame) b_frame[r] = (unsigned char)frame_id;
         }
     }
 }
@@ -4410,41 +4321,6 @@ __global__ void __launch_bounds__(256) translate_frame_kernel(const u32 *dna, u6
 // frame 0's results are the first `best`: its frame byte is 0 where it has rows, RK_FRAME_NONE elsewhere
 __global__ void __launch_bounds__(256) init_frame_kernel(const unsigned char *nrows, unsigned char *frame, u64 n_reads) {
     for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (u64)gridDim.x * blockDim.x) frame[r] = nrows[r] ? 0 : (unsigned char)RK_FRAME_NONE;
-}
-
-// merge_frames_kernel: merge_strands_kernel with a frame id -- per read the candidate frame's result replaces the best so far iff it
-// has rows and the best has none or a smaller best score (a tie keeps the earlier frame); the read's frame byte says where its
-// result comes from, and frames 3..5 are the reverse strand.  The same order of work: a wave decides its 64 reads before it writes.
-__global__ void __launch_bounds__(256) merge_frames_kernel(u64 n_reads, u32 K, unsigned char *b_nrows, unsigned short *b_branch, float *b_score,
-                                                           double *b_lwr, u32 *b_flags, unsigned char *b_frame, const unsigned char *c_nrows,
-                                                           const unsigned short *c_branch, const float *c_score, const double *c_lwr,
-                                                           const u32 *c_flags, u32 cand_frame) {
-    const u32 lane = threadIdx.x & 63;
-    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
-    const u32 mark = cand_frame >= 3u ? RK_FLAG_REVERSE : 0u;
-    for (u64 r0 = wave * 64; r0 < n_reads; r0 += n_waves * 64) {
-        const u64 r = r0 + lane;
-        int take = 0;
-        if (r < n_reads) {
-            const u32 nc = c_nrows[r], nb = b_nrows[r];
-            take = nc > 0 && (nb == 0 || c_score[r * K] > b_score[r * K]);
-        }
-        for (u32 e = lane; e < 64u * K; e += 64) {  // (uniform trip count: the shuffle below is executed by the whole wave)
-            const u32 rr = e / K;
-            const int t = __shfl(take, (int)rr, 64);
-            const u64 g = r0 * K + e;
-            if (t && r0 + rr < n_reads) {
-                b_branch[g] = c_branch[g];
-                b_score[g] = c_score[g];
-                b_lwr[g] = c_lwr[g];
-            }
-        }
-        if (take) {
-            b_nrows[r] = c_nrows[r];
-            b_flags[r] = c_flags[r] | mark;
-            b_frame[r] = (unsigned char)cand_frame;
-        }
-    }
 }
 
 }  // namespace rk

@@ -82,8 +82,8 @@ r1, r2 = res(out), res(out2)
 ms = timed(lambda: _lib.check(lib.rk_revcomp_packed_device(db.handle, n, packed.data_ptr(), wpr, None, rlen, rev_rec.data_ptr(), st)))
 print(f"revcomp_packed_kernel alone: median {statistics.median(ms):.3f} ms ({2 * n * wpr * 4 / statistics.median(ms) / 1e6:.0f} GB/s read + written)")
 ms = timed(lambda: _lib.check(lib.rk_merge_strands_device(db.handle, K, n, C.byref(r1), C.byref(r2), st)))
-print(f"merge_strands_kernel alone (second set = a copy: ties, nothing switches): median {statistics.median(ms):.3f} ms")
+print(f"merge_results_kernel alone (second set = a copy: ties, nothing switches): median {statistics.median(ms):.3f} ms")
 out2["score"] += 1.0
 ms = timed(lambda: _lib.check(lib.rk_merge_strands_device(db.handle, K, n, C.byref(r1), C.byref(r2), st)))
-print(f"merge_strands_kernel alone (every placed read switches on the first call, later calls tie): median {statistics.median(ms):.3f} ms")
+print(f"merge_results_kernel alone (every placed read switches on the first call, later calls tie): median {statistics.median(ms):.3f} ms")
 db.close()

@@ -110,6 +110,6 @@ def five_merges():
         _lib.check(lib.rk_merge_frames_device(db.handle, K, n, C.byref(best), outs[0]["frame"].data_ptr(), C.byref(rs[f]), f, st))
 
 
-t_d = line("(d) merge_frames_kernel alone, five merges (later calls tie)", timed(five_merges))
+t_d = line("(d) merge_results_kernel alone, five merges (later calls tie)", timed(five_merges))
 print(f"(a) - (b) = {t_a - t_b:.3f} ms per {n} reads; (c) + (d) = {t_c + t_d:.3f} ms; (a) / (b) = {t_a / t_b:.3f}")
 db.close()

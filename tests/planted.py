@@ -124,10 +124,10 @@ def with_ambiguity_code(alphabet, seq, off):
     return seq
 
 
-def place_prefilled(pp, packed, n, L, K, keep_factor=0.01, amb=None, flags=None, seq=None, off=None):
+def place_prefilled(pp, packed, n, L, K, keep_factor=0.01, amb=None, flags=None, seq=None, off=None, lens=None):
     """rk_place_packed_device into result tensors pre-filled with 0xFF bytes; every read must have been written.  amb ("skip" / "max" /
     "mean") with the packer's flags and the reads' characters: reads with an ambiguity code go through place_ascii_kernel (without the
-    characters nobody places them)."""
+    characters nobody places them).  lens: a length per read instead of the one length L."""
     import torch
     import rappas_amd as ra
     dev = torch.device("cuda", 0)
@@ -141,6 +141,9 @@ def place_prefilled(pp, packed, n, L, K, keep_factor=0.01, amb=None, flags=None,
         kw = dict(flags_in=torch.from_numpy(flags.view(np.int32)).to(dev), treatAmbiguities=amb != "skip", treatAmbiguitiesWithMax=amb == "max")
         if seq is not None:
             kw.update(seq_ascii=torch.from_numpy(seq).to(dev), seq_off=torch.from_numpy(off.astype(np.int64)).to(dev))
+    if lens is not None:
+        kw.update(lens=torch.from_numpy(lens.view(np.int32)).to(dev))
+        L = 0
     pp.place_packed(torch.from_numpy(packed.view(np.int32)).to(dev), fixed_len=L, out=out, keepAtMost=K, keepFactor=keep_factor, **kw)
     torch.cuda.synchronize()
     o = {f: t.cpu().numpy() for f, t in out.items()}

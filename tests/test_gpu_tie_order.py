@@ -10,6 +10,7 @@ result buffers pre-filled with 0xFF and asserts: the parity bar of tests/util.py
 sort, branch for branch and bit for bit; no read left unwritten; the kernel the case is meant for in kernel_name(); and that every
 shape that can occur on the tree was met by a read (tests/test_planted_shapes.py asserts the same census without a GPU).  The kernels
 that can serve one tree must also agree with each other exactly (n_rows, branch, flags, score bits, LWR)."""
+import contextlib
 import re
 
 import numpy as np
@@ -52,22 +53,33 @@ ROUTES = {
 KEEP_FACTORS = (0.0, 0.01)
 
 
-def run_route(name, route, Ks, monkeypatch, amb=None):
-    """the reads of planted tree `name` through the kernel of `route`: {(K, keep_factor): Placements}, and the kernel's family"""
+@contextlib.contextmanager
+def route_db(name, route, monkeypatch):
+    """the database of planted tree `name`, opened for the kernel of `route`; the route's developer knobs hold while it is open"""
     env, lanes, says = ROUTES[route]
     for knob in KNOBS:
         monkeypatch.delenv(knob, raising=False)
     for knob, v in env.items():
         monkeypatch.setenv(knob, v)
+    db = ra.PhyloKmerDB.from_synth(P.tree(name)[0], device=0)
+    try:
+        db.set_lanes_per_read(lanes)
+        assert says in db.kernel_name(), (route, db.kernel_name())
+        yield db
+    finally:
+        db.close()
+        for knob in env:
+            monkeypatch.delenv(knob, raising=False)
+
+
+def run_route(name, route, Ks, monkeypatch, amb=None):
+    """the reads of planted tree `name` through the kernel of `route`: {(K, keep_factor): Placements}, and the kernel's family"""
     sdb, odb, seq, off, _ = P.tree(name)
     if amb is not None:
         seq, _ = P.ambiguous(name, amb)
     n, L = len(off) - 1, int(off[1])
-    db = ra.PhyloKmerDB.from_synth(sdb, device=0)
-    try:
-        db.set_lanes_per_read(lanes)
+    with route_db(name, route, monkeypatch) as db:
         kn = db.kernel_name()
-        assert says in kn, (route, kn)
         fam = P.family(route, sdb.n_branches, sdb.bits)
         if fam.windows:  # the windows the census counts with are the image's
             got_w = tuple(int(x) for x in re.search(r"windows=(\d+) x (\d+)", kn).groups())
@@ -86,10 +98,6 @@ def run_route(name, route, Ks, monkeypatch, amb=None):
             for kf in KEEP_FACTORS:
                 res[K, kf] = P.place_prefilled(pp, packed, n, L, K, keep_factor=kf, amb=amb, flags=flags, seq=seq, off=off)
         return res, fam
-    finally:
-        db.close()
-        for knob in env:
-            monkeypatch.delenv(knob, raising=False)
 
 
 def check_route(name, route, Ks, monkeypatch, amb=None):

@@ -98,7 +98,7 @@ def test_header_constants_and_binding_agree():
 def test_new_kernels_hold_no_64_bit_shift_by_a_per_lane_count():
     build.build_engine()
     census = check_isa.variable_shift_census(build.ENGINE_SO)
-    for kern in ("revcomp_packed_kernel", "revcomp_ascii_kernel", "merge_strands_kernel", "mark_reverse_kernel"):
+    for kern in ("revcomp_packed_kernel", "revcomp_ascii_kernel", "merge_results_kernel", "mark_reverse_kernel"):
         found = {k: n for k, n in census.items() if re.match(r"^_ZN2rk\d+" + kern + r"E", k)}
         assert found, f"{kern} is not in the library"
         assert all(n == 0 for n in found.values()), found

@@ -191,7 +191,7 @@ def test_native_driver_names_the_flag_and_refuses_it_with_strand():
 def test_new_kernels_hold_no_64_bit_shift_by_a_per_lane_count():
     build.build_engine()
     census = check_isa.variable_shift_census(build.ENGINE_SO)
-    for kern in ("translate_frame_kernel", "merge_frames_kernel", "init_frame_kernel"):
+    for kern in ("translate_frame_kernel", "merge_results_kernel", "init_frame_kernel"):
         found = {k: n for k, n in census.items() if re.match(r"^_ZN2rk\d+" + kern + r"E", k)}
         assert found, f"{kern} is not in the library"
         assert all(n == 0 for n in found.values()), found
