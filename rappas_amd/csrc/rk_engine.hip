@@ -1428,8 +1428,15 @@ static int launch_variant(const rk_db *db, const Geometry &g, const PlaceArgs &a
     auto kern = place_packed_kernel<G, BITS, TM, WIDE, U, PU>;
     decltype(kern) clade_kern = nullptr;
     PlaceArgs la = args;
+    bool whole_simds = false;
     if constexpr (G == 16 && !WIDE && TM != TM_HASH) {
         if (use_pipelined16(db, g, args)) {
+            // The waves of this kernel take their tiles at a fixed stride, so each does the same share of the batch and a CU's four
+            // SIMDs finish together only if they hold the same number of waves.  C4: 14 592 B of LDS a wave allow ten waves a CU; at
+            // 201 VGPRs the registers held it to eight, at 163 (round 8) ten were resident, three on two SIMDs and two on the others,
+            // and the batch took 1.45 ms instead of 1.14 -- the 0.25 / 0.30 of the uneven split.  Nine to eleven resident waves of a
+            // compact-table instance go back to the eight (two a SIMD) that every such instance had before; nothing else changes.
+            whole_simds = TM == TM_COMPACT;
             auto k16 = place_packed16_kernel<BITS, TM, U, PU>;
             auto k24 = place_packed16_kernel<BITS, TM, U, PU, TM == TM_COMPACT>;
             if constexpr (BITS == 5) {
@@ -1462,6 +1469,7 @@ static int launch_variant(const rk_db *db, const Geometry &g, const PlaceArgs &a
         HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         uint64_t per_cu = 0;
         if (int rc = resident_blocks(k, 64 * (int)wpb, lds, (g.waves_per_cu + wpb - 1) / wpb, per_cu)) return rc;
+        if (whole_simds && wpb == 1 && per_cu > 8 && per_cu < 12) per_cu = 8;
         uint64_t blocks = (uint64_t)db->cu_count * per_cu;
         const uint64_t need = (n_tiles + wpb - 1) / wpb;
         if (blocks > need) blocks = need;

@@ -19,6 +19,7 @@
 // No MFMA: this is a gather/accumulate bounded by the memory system, not a contraction.
 #include "rk_device.h"
 #include "rk_slots24.h"
+#include "rk_compact32.h"
 #include "rk_translate.h"
 
 #include <type_traits>
@@ -1590,6 +1591,55 @@ __device__ __forceinline__ void record_codes(u32 recw, u32 pos, u32 li, u32 k, u
     }
 }
 
+// the same positions' dense table indices as 32-bit values (direct tables: sigma^k <= 2^31); a DNA code IS its index and never
+// becomes a 64-bit value here
+template <int BITS, int PU>
+__device__ __forceinline__ void record_indices(u32 recw, u32 pos, u32 li, u32 k, u32 Q, u32 (&idx)[PU]) {
+    if (BITS == 2) {
+        const u32 mask = (k >= 16) ? 0xFFFFFFFFu : ((1u << (2 * k)) - 1u);
+        if (PU <= 15 && pos == 0) {  // (as record_codes)
+            u32 w[PU + 1];
+            Batch0Words<PU, 0>::run(recw, w);
+#pragma unroll
+            for (int u = 0; u < PU; u++) idx[u] = __builtin_amdgcn_alignbit(w[u + 1], w[u], 2 * li) & mask;
+            return;
+        }
+#pragma unroll
+        for (int u = 0; u < PU; u++) {
+            const u32 j0 = pos + u * 16 + li;
+            const u32 j = j0 < Q ? j0 : 0u;
+            const u32 wi = j >> 4, sh = (j & 15u) * 2u;
+            const u32 w0 = __shfl(recw, (int)(wi & 15u), 16);
+            u32 w1 = __shfl(recw, (int)((wi + 1) & 15u), 16);
+            w1 = wi + 1 < 16 ? w1 : 0u;
+            idx[u] = __builtin_amdgcn_alignbit(w1, w0, sh) & mask;
+        }
+        return;
+    }
+    u64 code[PU];
+    record_codes<BITS, PU>(recw, pos, li, k, Q, code);
+#pragma unroll
+    for (int u = 0; u < PU; u++) idx[u] = (u32)dense_index<BITS>(code[u], k);
+}
+
+// One batch of probes in flight, and the rows it found.  C32 (TM_COMPACT): the 32-bit path of rk_compact32.h -- a probe is its gathered
+// block and the k-mer's position in it, a row its first unit and its number of units.  Otherwise (TM_DIRECT8) the k-mer code and the
+// 64-bit descriptor are carried as well.
+template <int PU, bool C32>
+struct ProbeBatch {
+    RawSlot raw[PU];
+    u32 j[C32 ? PU : 1];
+    u64 code[C32 ? 1 : PU];
+};
+template <int PU, bool C32>
+struct RowBatch {
+    u32 unit[C32 ? PU : 1], n[C32 ? PU : 1];
+    u64 desc[C32 ? 1 : PU];
+};
+// the descriptor of such a row, for the rare paths that walk a row by its descriptor.  32-bit products: the kernel that calls it
+// runs on row blobs below ROWS_FIT32_LIMIT only (rb = unit * 128 is a u32 there too), so unit < 2^25, and n <= 255
+__device__ __forceinline__ u64 unit_desc(u32 unit, u32 n) { return n ? ((u64)(unit * ROW_UNIT) << DESC_LEN_BITS) | (u64)(n * ROW_UNIT) : 0ull; }
+
 // D24: a.db is the image's dense view (rk_device.h: 24-entry units, its own compact table); everything but the accumulate step and
 // the wide-row fallback is the same.
 template <int BITS, int TM, int U, int PU, bool D24 = false>
@@ -1636,17 +1686,41 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             fin = a.flags_in ? a.flags_in[r] : 0u;
         }
     };
-    auto fetch_batch = [&](u32 recw, u32 pos, u32 Q, u64 (&code)[PU], RawSlot (&raw)[PU]) {
-        record_codes<BITS, PU>(recw, pos, li, k, Q, code);
+    constexpr bool C32 = TM == TM_COMPACT;
+    const bool nib = a.db.compact_nib != 0;
+    auto fetch_batch = [&](u32 recw, u32 pos, u32 Q, ProbeBatch<PU, C32> &pb) {
+        if constexpr (C32) {
+            u32 idx[PU];
+            record_indices<BITS, PU>(recw, pos, li, k, Q, idx);
+            const unsigned char *table = (const unsigned char *)a.db.compact;  // (< 4 GiB: one base and a 32-bit byte offset per gather)
 #pragma unroll
-        for (int u = 0; u < PU; u++) raw[u] = lookup_fetch<BITS, TM>(a.db, code[u]);
+            for (int u = 0; u < PU; u++) {
+                const rk_compact32::Pos p = nib ? rk_compact32::locate_nib(idx[u]) : rk_compact32::locate_byte(idx[u]);
+                pb.j[u] = p.j;
+                pb.raw[u].v = *(const uint4 *)(table + p.blk * 16u);
+            }
+        } else {
+            record_codes<BITS, PU>(recw, pos, li, k, Q, pb.code);
+#pragma unroll
+            for (int u = 0; u < PU; u++) pb.raw[u] = lookup_fetch<BITS, TM>(a.db, pb.code[u]);
+        }
     };
-    auto decode_batch = [&](const u64 (&code)[PU], const RawSlot (&raw)[PU], u32 pos, u32 Q, u64 (&desc)[PU]) {
+    auto decode_batch = [&](const ProbeBatch<PU, C32> &pb, u32 pos, u32 Q, RowBatch<PU, C32> &rows) {
+        if constexpr (C32) {
 #pragma unroll
-        for (int u = 0; u < PU; u++) {
-            const u32 j = pos + u * G + li;
-            const u64 d = lookup_decode<BITS, TM>(a.db, raw[u], code[u]);
-            desc[u] = j < Q ? d : 0ull;
+            for (int u = 0; u < PU; u++) {
+                const uint4 v = pb.raw[u].v;
+                const rk_compact32::Row r = nib ? rk_compact32::decode_nib(v.x, v.y, v.z, v.w, pb.j[u]) : rk_compact32::decode_byte(v.x, v.y, v.z, v.w, pb.j[u]);
+                rows.unit[u] = r.unit;
+                rows.n[u] = r.n;  // (positions beyond the read: emit_batch)
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < PU; u++) {
+                const u32 j = pos + u * G + li;
+                const u64 d = lookup_decode<BITS, TM>(a.db, pb.raw[u], pb.code[u]);
+                rows.desc[u] = j < Q ? d : 0ull;
+            }
         }
     };
 
@@ -1654,14 +1728,13 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
     // prologue: the first tile's inputs and its first batch of descriptors
     u32 c_recw, c_R, c_fin;
     bool c_have;
-    u64 desc0[PU];
+    RowBatch<PU, C32> rows0;
     {
         load_tile(wave_global, c_recw, c_R, c_fin, c_have);
-        u64 code[PU];
-        RawSlot raw[PU];
+        ProbeBatch<PU, C32> pb;
         const u32 Q0 = read_head<BITS>(a, c_R, c_fin, c_have).Q;
-        fetch_batch(c_recw, 0u, Q0, code, raw);
-        decode_batch(code, raw, 0u, Q0, desc0);
+        fetch_batch(c_recw, 0u, Q0, pb);
+        decode_batch(pb, 0u, Q0, rows0);
     }
 
     for (u64 tile = wave_global; tile < n_tiles; tile += wave_count) {
@@ -1685,17 +1758,19 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             wave_lds_fence();
             cnt = 0;
         };
-        // one batch of PU*16 positions: descriptors -> unit items in k-mer order (or, for rows too long for the list, the
+        // one batch of PU*16 positions: rows (first unit, units) -> unit items in k-mer order (or, for rows too long for the list, the
         // row-cursor fallback); identical to place_packed_kernel's emit phase
-        auto emit_batch = [&](const u64 (&desc)[PU], bool more) {
-            u32 nch[PU], excl[PU];
+        auto emit_batch = [&](const RowBatch<PU, C32> &rows, u32 pos, bool more) {
+            u32 nch[PU], excl[PU], rb[PU];
             int total = 0;
             bool wide_rows = false;
 #pragma unroll
             for (int u = 0; u < PU; u++) {
-                const u32 lenp = (u32)desc[u] & DESC_LEN_MASK;
-                nch[u] = (lenp + G - 1) >> 4;
-                wide_rows = wide_rows || nch[u] > 15u;
+                if constexpr (C32) nch[u] = pos + u * G + li < Q ? rows.n[u] : 0u;  // the only gate: an absent k-mer has no units
+                else nch[u] = (((u32)rows.desc[u] & DESC_LEN_MASK) + G - 1) >> 4;  // (decode_batch has cleared the descriptor)
+                if constexpr (C32) rb[u] = rows.unit[u] * 128u;  // byte offset of the row (128-byte units)
+                else rb[u] = (u32)(rows.desc[u] >> DESC_LEN_BITS) * 8u;
+                if (!(C32 && nib)) wide_rows = wide_rows || nch[u] > 15u;  // (a nibble holds no more)
             }
             auto row_scan = [](u32 v) {  // inclusive prefix sum over the 16 lanes of a DPP row (row_shr shifts zeros in)
                 v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
@@ -1740,10 +1815,9 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
                     const u32 room = (u32)(cap_items - cnt);
 #pragma unroll
                     for (int u = 0; u < PU; u++) {
-                        const u32 rb = (u32)(desc[u] >> DESC_LEN_BITS) * 8u;
                         for (u32 c = 0; __any(c < nch[u]); c++) {
                             const u32 x = excl[u] + c - done;  // (wraps for units before the part: then >= room)
-                            if (c < nch[u] && x < room) items[cnt + (int)x] = rb + c * 128u;
+                            if (c < nch[u] && x < room) items[cnt + (int)x] = rb[u] + c * 128u;
                         }
                     }
                     const u32 take = min((u32)total - done, room);
@@ -1758,10 +1832,13 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
 #pragma unroll
                     for (int u = 0; u < PU; u++) {
                         const bool part = u >= u_lo && u < u_lo + per_part;
-                        const bool hit = part && ((u32)desc[u] & DESC_LEN_MASK) != 0;
+                        const bool hit = part && nch[u] != 0;
                         const u64 bal = __ballot(hit);
                         const u64 sub = group_bits<G>(bal, gi);
-                        if (hit) list[rc + count_below<G>(sub, li)] = desc[u];
+                        u64 d;  // (the row cursor walks a 64-bit descriptor)
+                        if constexpr (C32) d = unit_desc(rows.unit[u], nch[u]);
+                        else d = rows.desc[u];
+                        if (hit) list[rc + count_below<G>(sub, li)] = d;
                         rc += __builtin_popcountll(sub);
                     }
                     if (li == 0) list[rc] = 0;
@@ -1772,26 +1849,25 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             } else {
 #pragma unroll
                 for (int u = 0; u < PU; u++) {
-                    const u32 rb = (u32)(desc[u] >> DESC_LEN_BITS) * 8u;  // byte offset of the row (128-byte units)
                     const int base = cnt + (int)excl[u];
-                    if (nch[u] > 0) items[base] = rb;
-                    if (nch[u] > 1) items[base + 1] = rb + 128u;
+                    if (nch[u] > 0) items[base] = rb[u];
+                    if (nch[u] > 1) items[base + 1] = rb[u] + 128u;
                     for (u32 c = 2; __any(c < nch[u]); c++)
-                        if (c < nch[u]) items[base + (int)c] = rb + c * 128u;
+                        if (c < nch[u]) items[base + (int)c] = rb[u] + c * 128u;
                 }
                 cnt += total;
             }
         };
 
         stamps.mark(0);  // tile setup
-        emit_batch(desc0, Q > 0);
+        emit_batch(rows0, 0u, Q > 0);
         for (u32 pos = PU * G; __any(pos < Q); pos += PU * G) {  // reads longer than PU*16 + k - 1 symbols
-            u64 code[PU], desc[PU];
-            RawSlot raw[PU];
-            fetch_batch(c_recw, pos, Q, code, raw);
+            ProbeBatch<PU, C32> pb;
+            RowBatch<PU, C32> rows;
+            fetch_batch(c_recw, pos, Q, pb);
             __builtin_amdgcn_sched_barrier(0);
-            decode_batch(code, raw, pos, Q, desc);
-            emit_batch(desc, pos < Q);
+            decode_batch(pb, pos, Q, rows);
+            emit_batch(rows, pos, pos < Q);
         }
         stamps.mark(2);  // scans + item emission
         // next tile's inputs: in flight during this tile's accumulate phase
@@ -1799,10 +1875,9 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         if (__any(cnt > 0)) flush();
         stamps.mark(4);  // accumulate (incl. its fences)
         // next tile's first batch of table gathers: in flight during this tile's select phase
-        u64 ncode[PU];
-        RawSlot nraw[PU];
+        ProbeBatch<PU, C32> npb;
         const u32 nQ = read_head<BITS>(a, c_R, c_fin, c_have).Q;
-        fetch_batch(c_recw, 0u, nQ, ncode, nraw);
+        fetch_batch(c_recw, 0u, nQ, npb);
         __builtin_amdgcn_sched_barrier(0);
         stamps.mark(1);  // next tile's codes + gather issue
 
@@ -1812,7 +1887,11 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         else numBest = select_topk<G>(S, nb, li, gi, (int)a.keep_at_most, list, (int)a.list_cap, win_key, stamps);
         wave_lds_fence();
         stamps.mark(5);  // select (rest: reset)
-        decode_batch(ncode, nraw, 0u, nQ, desc0);  // (before this tile's stores, so that the wait covers loads only)
+        decode_batch(npb, 0u, nQ, rows0);  // (before this tile's stores, so that the wait covers loads only)
+        if constexpr (C32) {  // (the rows are 32-bit values the next tile reads: left alone, their arithmetic sinks below the stores)
+#pragma unroll
+            for (int u = 0; u < PU; u++) asm volatile("" : "+v"(rows0.unit[u]), "+v"(rows0.n[u]));
+        }
         __builtin_amdgcn_sched_barrier(0);
         stamps.mark(3);  // decode of the next tile's descriptors (waits for its gathers)
         if (have && !deferred(a, h)) weigh_and_store<G>(a, r, li, numBest, win_key, h.flags);
