@@ -360,6 +360,44 @@ int rk_place_packed_device_translated(rk_db *db, const rk_params *p, uint64_t n_
 int rk_place_batch_translated(rk_db *db, const rk_params *p, uint64_t n_reads, const uint8_t *seq_ascii, const uint64_t *seq_off,
                               rk_result *out, uint8_t *frame_out, rk_counters *counters);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Edge masses: the per-branch LWR sums of a result set.  The reference writes one jplace record per read
+ * (src/main_v2/Main_PLACEMENT_v07.java:150-320) and leaves the table most users are after -- how much likelihood weight landed on each
+ * branch -- to the tools behind it; here it is summed where the results are, so a device caller copies 2 * B + 4 words instead of
+ * ~100 bytes a read.  Works on the result set of any placement entry point (plain, strands, translated), either alphabet.
+ *   Mass buffer  2 * B + 4 little-endian 64-bit words for a tree of B = n_branches:
+ *                  [0, B)    mass_q30[x]  sum over the counted rows on branch x of w_r * q(lwr)
+ *                  [B, 2B)   best[x]      sum of w_r over the reads whose row 0 is branch x
+ *                  2B + 0    sum of w_r over all reads of the calls
+ *                  2B + 1    sum of w_r over the reads with at least one counted row
+ *                  2B + 2    sum of w_r * (counted rows of r)
+ *                  2B + 3    rows skipped because their branch id was >= B (not weighted)
+ *   Terms        w_r = weights[r], or 1 when weights is NULL (0 is legal: such a read adds 0 everywhere).  The rows of read r are
+ *                e < min(n_rows[r], keep_at_most); what lies behind them is never looked at.  q(l) = llrint(min(l, 1.0) * 2^30) for
+ *                l >= 0 (ties to even; the product is exact in binary64), 0 for a negative or NaN.  A row with branch >= B is never
+ *                used as an index: it is skipped, counted in word 2B + 3 and adds to no other word (as row 0: nothing to best either)
+ *                -- a bounds check, the engine's own results never meet it.  score and flags of the result are not read and may be
+ *                NULL; n_rows == 0 already says unplaced or gated.
+ *   Exactness    all sums are integers, so they do not depend on the order of the adds: device, host and any split into calls give
+ *                the same words.  One add is below 2^62, so a buffer is exact while the sum of w_r stays below 2^33 (not checked).
+ *   Adding       calls ADD into the buffer; zeroing it is the caller's hipMemsetAsync / memset.  Buffers of chunks, batches, streams
+ *                and GPUs combine by element-wise integer addition.  The result set is read, never written.
+ *   rk_masses_words              words of a mass buffer: 2 * n_branches + 4; 0 for n_branches == 0 or > 65535.
+ *   rk_masses_accumulate_device  device pointers on db's device, B from the handle.  Asynchronous on `stream`, allocates nothing and
+ *                                does not use the handle's per-stream launch scratch: the one-stream rule of rk_place_packed_device
+ *                                does not apply to it.
+ *   rk_masses_accumulate_host    the same words in plain C++: no handle, no GPU.  Every thread sums privately, the partial sums are
+ *                                added at the end; n_threads 0 = automatic, at most 16.
+ * RK_ERR_INVALID (and a message) for a NULL n_rows / branch / lwr / mass buffer, keep_at_most outside 1..16 and n_reads >= 2^32: then
+ * nothing is launched and no byte is written.  n_reads == 0 is RK_OK and touches nothing.  Added without a bump of RK_VERSION (no
+ * struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+uint64_t rk_masses_words(uint32_t n_branches);
+int rk_masses_accumulate_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_res, const uint32_t *d_weights,
+                                uint64_t *d_masses, void *stream);
+int rk_masses_accumulate_host(uint32_t n_branches, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, const uint32_t *weights,
+                              uint64_t *masses, uint32_t n_threads);
+
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the
  * packed kernels place (not BAD_CHAR / TOO_LONG / AMBIGUOUS, at least k symbols); kmers_hit = those with a row in the database

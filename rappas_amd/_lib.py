@@ -126,6 +126,9 @@ EXPORTS = {
                                                     C.c_void_p, C.POINTER(rk_result), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rk_place_batch_translated": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(rk_result), C.c_void_p,
                                             C.POINTER(rk_counters)]),
+    "rk_masses_words": (C.c_uint64, [C.c_uint32]),
+    "rk_masses_accumulate_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rk_masses_accumulate_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_void_p, C.c_uint32]),
     "rk_count_work_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_set_lanes_per_read": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rk_kernel_name": (C.c_char_p, [C.c_void_p]),

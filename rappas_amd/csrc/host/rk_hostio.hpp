@@ -322,6 +322,38 @@ inline Tree parse_newick(const std::string &text) {  // NewickReader.java:46-200
     return t;
 }
 
+// The per-edge table of a mass buffer (include/rappas_place.h: mass_q30[B] | best[B] | four totals, B = the tree's nodes), the text
+// `--masses FILE` writes: tab-separated, one header line, one line per node in id order, a last line `#total` with the four totals.
+// edge_num is the node's jplace edge (-1 for the root, which has none); mass = mass_q30 / 2^30 with nine decimals; the clade columns
+// are the integer sums over the node's subtree, the node included.  The twin of hostio.masses_table (byte-identical).
+inline std::string masses_table(const Tree &t, const uint64_t *m, size_t words) {
+    const size_t B = t.nodes.size();
+    if (words != 2 * B + 4) throw std::runtime_error("masses_table: the buffer holds " + std::to_string(words) + " words, the tree's " + std::to_string(B) + " nodes need " + std::to_string(2 * B + 4));
+    std::vector<uint64_t> cm(m, m + B), cb(m + B, m + 2 * B);
+    std::vector<int> order, stack{t.root};
+    while (!stack.empty()) {
+        const int id = stack.back();
+        stack.pop_back();
+        order.push_back(id);
+        for (int c : t.nodes[id].children) stack.push_back(c);
+    }
+    for (size_t i = order.size(); i-- > 1;) {  // children before parents: every node hands its subtree's sums up
+        const int id = order[i], up = t.nodes[id].parent;
+        if (up >= 0) { cm[up] += cm[id]; cb[up] += cb[id]; }
+    }
+    std::string out = "node_id\tedge_num\tlabel\tbest_reads\tmass_q30\tmass\tclade_best_reads\tclade_mass_q30\tclade_mass\n";
+    char buf[96];
+    auto mass = [&](uint64_t q) { snprintf(buf, sizeof(buf), "%.9f", (double)q / 1073741824.0); return std::string(buf); };
+    for (size_t id = 0; id < B; id++) {
+        const Node &n = t.nodes[id];
+        out += std::to_string(id) + "\t" + std::to_string((int)id == t.root ? -1 : n.jplace_edge) + "\t" + n.label + "\t" + std::to_string(m[B + id]) + "\t" +
+               std::to_string(m[id]) + "\t" + mass(m[id]) + "\t" + std::to_string(cb[id]) + "\t" + std::to_string(cm[id]) + "\t" + mass(cm[id]) + "\n";
+    }
+    out += "#total";
+    for (size_t i = 0; i < 4; i++) out += "\t" + std::to_string(m[2 * B + i]);
+    return out + "\n";
+}
+
 // NumberFormat.getNumberInstance(Locale.UK), exactly 12 fraction digits, grouping commas (NewickWriter.java:61-64)
 inline std::string fmt12(float x) {
     char buf[400];

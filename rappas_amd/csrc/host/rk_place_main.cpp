@@ -29,17 +29,20 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                [--threads N] [--md5-dedup] [--classic-io] [--timing] [--save-dbimage DB.rkimg] [--strand fwd|rev|both]\n"
                  "                (--strand, DNA: the reads as given = the reference's behaviour | their reverse complements | both, the better\n"
                  "                 strand per read; rev / both also write logs/reversed_<query>.tsv)\n"
+                 "                [--masses FILE]  (the per-edge table of the run: one line per tree node with the reads whose best placement is its\n"
+                 "                 edge and the likelihood weight on it, and the same summed over its clade; a read counts once per FASTA record)\n"
                  "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
                  "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
                  "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
                  "       rk_place (--jsondb DB.json | --uniondb DB.union) --save-dbimage DB.rkimg      (no GPU needed)\n"
+                 "       rk_place --masses-table TREE.nwk MASSES.bin OUT.tsv      (a raw little-endian u64 mass buffer as that table; no GPU needed)\n"
                  "       rk_place --emit-tree TREE.nwk | --format-float X | --format-double X | --dedup READS.fa | --md5 TEXT\n";
     return rc;
 }
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd";
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7;
@@ -66,6 +69,7 @@ int main(int argc, char **argv) {
             else if (a == "--amb") amb = val();
             else if (a == "--strand") strand_name = val();
             else if (a == "--translate") translate = true;
+            else if (a == "--masses") masses_path = val();
             else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
             else if (a == "--guppy-compat") guppy = true;
@@ -195,6 +199,17 @@ int main(int argc, char **argv) {
                 of << rkh::jplace_document(t, pl, call, guppy);
                 std::cout << n << " " << ws.placed << " " << (ws.exact_path ? "exact" : "direct") << "\n";
                 return 0;
+            } else if (a == "--masses-table") {  // TREE MASSES OUT: the table writer on its own (compared with the Python twin)
+                const std::string tpath = val(), mpath = val(), opath = val();
+                const rkh::Tree t = rkh::parse_newick(slurp(tpath));
+                const std::string raw = slurp(mpath);
+                if (raw.size() % 8) throw std::runtime_error(mpath + ": not a whole number of 64-bit words");
+                std::vector<uint64_t> m(raw.size() / 8);
+                if (!m.empty()) memcpy(m.data(), raw.data(), raw.size());
+                std::ofstream of(opath, std::ios::binary);
+                if (!of) throw std::runtime_error("cannot write " + opath);
+                of << rkh::masses_table(t, m.data(), m.size());
+                return 0;
             } else if (a == "--ingest-rate") {  // N3 throughput: FASTA parse, MD5 dedup, host-side packing (no device needed)
                 const std::string text = slurp(val());
                 auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -268,6 +283,17 @@ int main(int argc, char **argv) {
             }
             const int rc = strand == RK_STRAND_FORWARD ? rk_place_batch(h, pp, m, sq, so, rs, c) : rk_place_batch_strands(h, pp, strand, m, sq, so, rs, c);
             if (rc != RK_OK) throw std::runtime_error(std::string(strand == RK_STRAND_FORWARD ? "rk_place_batch: " : "rk_place_batch_strands: ") + rk_last_error());
+        };
+        // --masses: the per-edge table of the whole run.  The results are on the host already, so the sums are rk_masses_accumulate_host's;
+        // the weight of a unique read is the number of FASTA records it stands for, so the table speaks of reads
+        auto write_masses = [&](const rkh::Tree &t, uint64_t m, const rk_result *rs, const uint32_t *w, uint32_t n_threads) {
+            std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);
+            if (words.empty()) throw std::runtime_error("--masses: the tree has no nodes, or more than 65535");
+            if (rk_masses_accumulate_host((uint32_t)t.nodes.size(), keep_at_most, m, rs, w, words.data(), n_threads) != RK_OK)
+                throw std::runtime_error(std::string("rk_masses_accumulate_host: ") + rk_last_error());
+            std::ofstream mf(masses_path, std::ios::binary);
+            if (!mf) throw std::runtime_error("cannot write " + masses_path);
+            mf << rkh::masses_table(t, words.data(), words.size());
         };
         auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_start = now();
@@ -384,6 +410,18 @@ int main(int argc, char **argv) {
                 if (!ff) throw std::runtime_error("cannot write the frames log under " + log_dir.string());
                 ff << rkh::frames_log_fast(sc, dd, frame.data());
             }
+            if (!masses_path.empty()) {
+                rkh::RawArray<uint32_t> weight;
+                weight.alloc(n);
+                team.run([&](unsigned t, unsigned T) {
+                    for (size_t u = n * t / T; u < n * (t + 1) / T; u++) {
+                        uint32_t c = 0;
+                        for (uint32_t rec = dd.first_rec[u]; rec != 0xFFFFFFFFu; rec = dd.next_dup[rec]) c++;
+                        weight[u] = c;
+                    }
+                });
+                write_masses(tree, n, &res, weight.data(), team.size());
+            }
             const double t6 = now();
             std::cerr << n << " unique reads, " << ws.placed << " placed -> " << out << "\n";
             if (timing) {  // one JSON line (bench.py's fasta_to_jplace leg reads it): seconds per pass, FASTA bytes in -> jplace bytes out
@@ -438,6 +476,11 @@ int main(int argc, char **argv) {
                 if (!ff) throw std::runtime_error("cannot write the frames log under " + log_dir.string());
                 ff << rkh::frames_log(records, dd, frame.data());
             }
+        }
+        if (!masses_path.empty()) {
+            std::vector<uint32_t> weight(n);
+            for (size_t i = 0; i < n; i++) weight[i] = (uint32_t)names[i].size();
+            write_masses(tree, n, &res, weight.data(), 1);
         }
         std::cerr << n << " unique reads, " << pl.size() << " placed -> " << out << "\n";
         if (timing) std::cout << "{\"reads\": " << records.size() << ", \"unique\": " << n << ", \"db_s\": " << (t_db - t_start) << ", \"fasta_to_jplace_s\": " << (now() - tc0) << ", \"classic\": true}" << std::endl;

@@ -4402,4 +4402,119 @@ __global__ void __launch_bounds__(256) init_frame_kernel(const unsigned char *nr
     for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n_reads; r += (u64)gridDim.x * blockDim.x) frame[r] = nrows[r] ? 0 : (unsigned char)RK_FRAME_NONE;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Edge masses: the per-branch LWR sums of a result set.  out = mass_q30[B] | best[B] | four totals, 64-bit words the
+// call ADDS into.  Every term is an integer -- an LWR enters as q = rint(min(l, 1) * 2^30), times the read's weight -- so the sums do
+// not depend on the order of the atomic adds.  The reference has no counterpart (it writes one jplace record per read).
+//
+// masses_kernel: a histogram with hot spots (a clade-shaped batch puts most rows on a handful of branches).  A wave takes 64 reads,
+// as merge_results_kernel does: a lane loads n_rows and the weight of one read, then the wave walks the 64 * K rows lane after lane
+// along the flattened arrays (the branch and lwr loads coalesce) and takes n_rows and w of the read that owns the row by shuffle.
+//   LDS_BINS   small trees: the block's mass and best live in the LDS (64-bit integer LDS atomics), are flushed once at the end, the
+//              non-zero bins only, one global atomic per bin and block; the grid is a small multiple of the CU count, not a block
+//              per 256 reads, since the flush costs blocks x B.
+//   otherwise  large trees: 64-bit global atomics straight into `out`.
+// A row whose branch is >= B is never an index: it is skipped and counted (word 2B+3), and takes no part in any other word.  That
+// needs the number of skipped rows per READ while the rows sit in other lanes: the wave ballots the skip (all zero on the engine's
+// own results) and, in the rare case, walks the set bits to the lanes that own the reads.  The four totals stay in registers, are
+// reduced across the wave by shuffles and added to four LDS words, which the block flushes with the bins.
+//   COMBINE    equal branches among the lanes of a wave are summed before the atomics (see there).
+// No 64-bit shift by a per-lane count anywhere.
+// ------------------------------------------------------------------------------------------------
+constexpr u32 MASS_NO_BRANCH = 0xFFFFFFFFu;  // a lane without a counted row
+
+template <bool LDS_BINS, bool COMBINE>
+__global__ void __launch_bounds__(256) masses_kernel(u64 n_reads, u32 K, u32 B, const unsigned char *n_rows, const unsigned short *branch,
+                                                     const double *lwr, const u32 *weights, u64 *out) {
+    extern __shared__ u64 mass_lds[];  // LDS_BINS: mass[B] | best[B] | totals[4]; otherwise totals[4]
+    const u32 n_lds = LDS_BINS ? 2u * B + 4u : 4u;
+    for (u32 i = threadIdx.x; i < n_lds; i += 256) mass_lds[i] = 0;
+    __syncthreads();
+    u64 *tot = mass_lds + (n_lds - 4u);
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
+    u64 t_all = 0, t_placed = 0, t_rows = 0, t_skip = 0;
+    for (u64 r0 = wave * 64; r0 < n_reads; r0 += n_waves * 64) {
+        const u64 r = r0 + lane;
+        u32 nr = 0, w = 0;
+        if (r < n_reads) {
+            nr = n_rows[r];
+            nr = nr < K ? nr : K;
+            w = weights ? weights[r] : 1u;
+        }
+        u32 my_skips = 0;  // rows of THIS lane's read with a branch >= B
+        for (u32 e = lane; e < 64u * K; e += 64) {  // (uniform trip count: shuffles and the ballot are executed by the whole wave)
+            const u32 rr = e / K, j = e - rr * K;
+            const u32 nr_e = (u32)__shfl((int)nr, (int)rr, 64), w_e = (u32)__shfl((int)w, (int)rr, 64);
+            bool skipped = false;
+            u32 cx = MASS_NO_BRANCH;  // this lane's add: branch, weighted mass, weight for best (row 0 only)
+            u64 cv = 0, cb = 0;
+            if (j < nr_e) {  // (nr == 0 beyond the batch: no row of such a read is loaded)
+                const u64 g = r0 * K + e;
+                const u32 x = branch[g];
+                if (x < B) {
+                    const double l = lwr[g];
+                    const u32 q = l >= 0.0 ? (u32)__builtin_rint(fmin(l, 1.0) * 1073741824.0) : 0u;  // (NaN: 0)
+                    cx = x;
+                    cv = (u64)w_e * q;
+                    cb = j == 0 ? w_e : 0u;
+                } else {
+                    skipped = true;
+                }
+            }
+            if (COMBINE) {
+                // Row j of consecutive reads sits K lanes apart, and a clade-shaped batch repeats branches there: the lanes of such a
+                // chain are summed pairwise, then by fours, ... wherever neighbours hold the same branch (read rr takes read rr + 2^s
+                // when bit s of rr is clear, so nobody gives and takes in one step); a lane that was taken adds nothing itself.
+                for (u32 s = 0, d = K; d < 64u; s++, d <<= 1) {
+                    const u32 ox = (u32)__shfl_down((int)cx, d, 64);
+                    const u64 ov = __shfl_down(cv, d, 64), ob = __shfl_down(cb, d, 64);
+                    const int take = ((rr >> s) & 1u) == 0u && lane + d < 64u && cx != MASS_NO_BRANCH && ox == cx;
+                    if (take) { cv += ov; cb += ob; }
+                    const int taken = __shfl_up(take, d, 64);
+                    if (lane >= d && taken) cx = MASS_NO_BRANCH;
+                }
+            }
+            if (cx != MASS_NO_BRANCH) {
+                if (LDS_BINS) {
+                    atomicAdd(&mass_lds[cx], cv);
+                    if (cb) atomicAdd(&mass_lds[B + cx], cb);
+                } else {
+                    atomicAdd(&out[cx], cv);
+                    if (cb) atomicAdd(&out[B + cx], cb);
+                }
+            }
+            u64 sk = __ballot(skipped);
+            while (sk) {  // wave-uniform, never entered on the engine's own results
+                const u32 bit = (u32)__ffsll((long long)sk) - 1u;
+                sk &= sk - 1;
+                if (lane == (e - lane + bit) / K) my_skips++;
+            }
+        }
+        const u32 counted = nr - my_skips;
+        t_all += w;  // (w == 0 beyond the batch)
+        if (counted) t_placed += w;
+        t_rows += (u64)w * counted;
+        t_skip += my_skips;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        t_all += __shfl_down(t_all, o, 64);
+        t_placed += __shfl_down(t_placed, o, 64);
+        t_rows += __shfl_down(t_rows, o, 64);
+        t_skip += __shfl_down(t_skip, o, 64);
+    }
+    if (lane == 0) {
+        if (t_all) atomicAdd(&tot[0], t_all);
+        if (t_placed) atomicAdd(&tot[1], t_placed);
+        if (t_rows) atomicAdd(&tot[2], t_rows);
+        if (t_skip) atomicAdd(&tot[3], t_skip);
+    }
+    __syncthreads();
+    u64 *dst = LDS_BINS ? out : out + 2u * (u64)B;
+    for (u32 i = threadIdx.x; i < n_lds; i += 256) {
+        const u64 v = mass_lds[i];
+        if (v) atomicAdd(&dst[i], v);
+    }
+}
+
 }  // namespace rk

@@ -319,6 +319,36 @@ def reset_jplace_edge_ids(tree):
     dfs(tree.root)
 
 
+def masses_table(tree, masses):
+    """the per-edge table of a mass buffer (include/rappas_place.h: mass_q30[B] | best[B] | four totals, B = the tree's nodes), the
+    text `--masses FILE` writes -- the twin of rkh::masses_table (rappas_amd/csrc/host/rk_hostio.hpp), byte-identical: tab-separated,
+    one header line, one line per node in id order, a last line `#total` with the four totals.  edge_num is the node's jplace edge
+    (-1 for the root); mass = mass_q30 / 2^30 with nine decimals; the clade columns are the integer sums (modulo 2^64, as the words
+    themselves) over the node's subtree, the node included."""
+    B = len(tree.nodes)
+    m = [int(x) for x in np.asarray(masses, dtype=np.uint64).reshape(-1)]
+    if len(m) != 2 * B + 4:
+        raise ValueError(f"masses_table: the buffer holds {len(m)} words, the tree's {B} nodes need {2 * B + 4}")
+    cm, cb = m[:B], m[B:2 * B]
+    order, stack = [], [tree.root]
+    while stack:
+        n = stack.pop()
+        order.append(n)
+        stack.extend(n.children)
+    for n in reversed(order[1:]):  # children before parents: every node hands its subtree's sums up
+        if n.parent is not None:
+            cm[n.parent.id] = (cm[n.parent.id] + cm[n.id]) & 0xFFFFFFFFFFFFFFFF
+            cb[n.parent.id] = (cb[n.parent.id] + cb[n.id]) & 0xFFFFFFFFFFFFFFFF
+    out = ["node_id\tedge_num\tlabel\tbest_reads\tmass_q30\tmass\tclade_best_reads\tclade_mass_q30\tclade_mass\n"]
+    for n in tree.nodes:
+        i = n.id
+        edge = -1 if n is tree.root else n.jplace_edge
+        out.append("%d\t%d\t%s\t%d\t%d\t%.9f\t%d\t%d\t%.9f\n" % (i, edge, n.label, m[B + i], m[i], float(m[i]) / 1073741824.0, cb[i], cm[i],
+                                                               float(cm[i]) / 1073741824.0))
+    out.append("#total\t%d\t%d\t%d\t%d\n" % tuple(m[2 * B:]))
+    return "".join(out)
+
+
 def _fmt12(x):
     """NumberFormat.getNumberInstance(Locale.UK) with exactly 12 fraction digits (NewickWriter.java:61-64): grouping commas,
     HALF_EVEN on the exact binary value."""

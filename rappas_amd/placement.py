@@ -82,6 +82,39 @@ def translate_packed_host(dna, frame, lens=None, fixed_len=0, aa_words=None):
     return aa, aa_lens
 
 
+def masses_words(n_branches):
+    """rk_masses_words: 64-bit words of a mass buffer of a tree of n_branches (2 * B + 4; 0 for 0 or more than 65535 branches)"""
+    return int(_lib.load().rk_masses_words(n_branches))
+
+
+def accumulate_masses_host(n_branches, placements, weights=None, masses=None, threads=0):
+    """rk_masses_accumulate_host (no GPU): the per-branch LWR sums of a result set (`placements`: a Placements, or anything with
+    n_rows u8 [n], branch u16 [n, K] and lwr f64 [n, K]) ADDED into `masses`, a uint64 array of masses_words(n_branches) -- mass_q30[B] |
+    best[B] | four totals (include/rappas_place.h) -- made and zeroed when None.  weights: uint32 [n], one per read (None = 1 each)."""
+    lib = _lib.load()
+    words = masses_words(n_branches)
+    if not words:
+        raise ValueError(f"n_branches={n_branches} must be in 1..65535")
+    n_rows = np.ascontiguousarray(placements.n_rows, dtype=np.uint8)
+    branch = np.ascontiguousarray(placements.branch, dtype=np.uint16)
+    lwr = np.ascontiguousarray(placements.lwr, dtype=np.float64)
+    n = n_rows.shape[0]
+    K = branch.shape[1] if branch.ndim == 2 else (branch.size // n if n else 1)
+    if branch.size != n * K or lwr.size != n * K:
+        raise ValueError("branch and lwr must hold n_reads x K rows")
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.uint32)
+        if weights.shape != (n,):
+            raise ValueError("weights must hold one uint32 per read")
+    if masses is None:
+        masses = np.zeros(words, np.uint64)
+    elif masses.dtype != np.uint64 or masses.shape != (words,) or not masses.flags.c_contiguous:
+        raise ValueError(f"masses must be a contiguous uint64 array of {words} words")
+    res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
+    _lib.check(lib.rk_masses_accumulate_host(n_branches, K, n, C.byref(res), None if weights is None else _ptr(weights), _ptr(masses), threads))
+    return masses
+
+
 def host_alloc(shape, dtype):
     """numpy array in page-locked host memory (rk_host_alloc): buffers the DMA reads / writes directly, no staging copies in
     rk_place_batch / rk_place_batch_packed.  The memory lives until the process ends (tests and the bench allocate a handful)."""
@@ -438,6 +471,32 @@ class PlacementProcess:
                                                                dp(flags_in), C.byref(res), out["frame"].data_ptr(), work.data_ptr(),
                                                                work.numel(), C.c_void_p(st)))
         return out
+
+    def accumulate_masses(self, out, weights=None, masses=None, stream=None):
+        """rk_masses_accumulate_device: the per-branch LWR sums of `out` -- the dict of device tensors place_packed / place_translated
+        return -- ADDED into `masses`, an int64 tensor of masses_words(n_branches) words on the same device (the bits are unsigned:
+        .cpu().numpy().view(numpy.uint64)), allocated and zeroed when None.  weights: int32 tensor [n] read as uint32 (None = 1 a
+        read).  Asynchronous on the stream; the results are read, never written."""
+        import torch
+        n, K = out["branch"].shape
+        dev = out["branch"].device
+        words = masses_words(self.db.info.n_branches)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        if masses is None:
+            masses = torch.empty(words, dtype=torch.int64, device=dev)
+            if stream is not None:
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                    masses.zero_()
+            else:
+                masses.zero_()
+        elif masses.dtype != torch.int64 or masses.numel() != words or not masses.is_contiguous() or masses.device != dev:
+            raise ValueError(f"masses must be a contiguous int64 tensor of {words} words on {dev}")
+        if weights is not None and (weights.dtype != torch.int32 or weights.numel() != n or not weights.is_contiguous() or weights.device != dev):
+            raise ValueError(f"weights must be a contiguous int32 tensor of {n} words on {dev}")
+        res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), None, out["lwr"].data_ptr(), None)
+        _lib.check(self._lib.rk_masses_accumulate_device(self.db.handle, K, n, C.byref(res), None if weights is None else weights.data_ptr(),
+                                                         masses.data_ptr(), C.c_void_p(st)))
+        return masses
 
     def translate_packed(self, dna, frame, fixed_len=0, lens=None, aa_words=None, stream=None):
         """rk_translate_packed_device: one reading frame of 2-bit DNA records [n, dna_words] -> (amino-acid records [n, aa_words],

@@ -19,12 +19,13 @@ TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds D
 
 
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
-               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False):
+               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
     reversed_<query>.tsv).  translate: DNA reads on an amino-acid database, six reading frames translated on the device and the best
-    one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both"."""
+    one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both".  masses: res.masses is
+    then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for)."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
     if dbimage is not None:
@@ -61,6 +62,11 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     res.notplaced = hostio.notplaced_log(records, unique, (res.flags & 1) != 0)
     res.reversed = hostio.reversed_log(records, unique, res.flags) if strand != "fwd" else None
     res.frames = hostio.frames_log(records, unique, res.frame) if translate else None
+    res.masses = None
+    if masses:
+        from ..placement import accumulate_masses_host
+        weights = np.array([len(nm) for nm in names], dtype=np.uint32)
+        res.masses = hostio.masses_table(tree, accumulate_masses_host(len(tree.nodes), res, weights))
     return hostio.jplace_document(tree, pl, call_string, guppy), res
 
 
@@ -84,6 +90,9 @@ def main(argv=None):
                     help="amino-acid database, DNA reads: translate every read in its six reading frames on the device (standard genetic "
                          "code, longest stop-free run per frame) and report the best frame; also writes logs/frames_<query>.tsv "
                          "(header<TAB>+1|+2|+3|-1|-2|-3); not with --strand rev | both")
+    ap.add_argument("--masses", default=None, metavar="FILE",
+                    help="also write the per-edge table of the run: one line per tree node with the reads whose best placement is its edge and "
+                         "the likelihood weight on it, and the same summed over its clade; a read counts once per FASTA record")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--logs", default=None, help="directory of notplaced_<query>.tsv (default: logs/ next to --out, like the reference's workdir/logs)")
@@ -100,7 +109,7 @@ def main(argv=None):
     try:
         doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
-                              translate=a.translate)
+                              translate=a.translate, masses=a.masses is not None)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA:
             raise
@@ -118,6 +127,9 @@ def main(argv=None):
     if res.frames is not None:
         with open(os.path.join(logs, "frames_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
             f.write(res.frames)
+    if res.masses is not None:
+        with open(a.masses, "w") as f:
+            f.write(res.masses)
     placed = int(np.count_nonzero(res.n_rows))
     print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
     return 0
