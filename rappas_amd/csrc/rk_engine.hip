@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <cstring>
@@ -27,6 +28,7 @@
 #include <mutex>
 #include <tuple>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -202,236 +204,7 @@ static void build_alphabet(uint32_t alphabet, bool convert_uo, Alphabet &A) {
 // ------------------------------------------------------------------------------------------------
 // DB object
 // ------------------------------------------------------------------------------------------------
-namespace {
-struct GrowBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n) {
-        if (n <= cap) return RK_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n + n / 4 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RK_ERR_NOMEM : RK_ERR_HIP, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        cap = want;
-        return RK_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T *as() { return (T *)p; }
-};
-}  // namespace
-
-namespace {
-// The host CPUs next to a GPU (its PCI device's NUMA node, from sysfs), cut to what this process may run on: the staging threads of
-// the host path and the page-locked buffers they fill are kept there (round 3 measured 2.0 - 2.6e8 reads/s for the same call
-// depending on where the scheduler had put them).  `ok` false = unknown / one node / nothing left after the cut: nothing is pinned.
-struct NodeCpus {
-    cpu_set_t set;
-    bool ok = false;
-    int node = -1;
-};
-const NodeCpus &gpu_node_cpus(int device) {
-    static std::mutex mu;
-    static std::map<int, NodeCpus> known;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = known.find(device);
-    if (it != known.end()) return it->second;
-    NodeCpus nc;
-    CPU_ZERO(&nc.set);
-    char bus[64] = "";
-    if (rk_knob("RK_NO_NUMA")) return known.emplace(device, nc).first->second;  // developer knob (A/B)
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), device) == hipSuccess && bus[0]) {
-        for (char *c = bus; *c; c++) *c = (char)tolower((unsigned char)*c);
-        int node = -1;
-        { std::ifstream f(std::string("/sys/bus/pci/devices/") + bus + "/numa_node"); if (f) f >> node; }
-        std::string list;
-        if (node >= 0) { std::ifstream f("/sys/devices/system/node/node" + std::to_string(node) + "/cpulist"); if (f) std::getline(f, list); }
-        cpu_set_t allowed;
-        CPU_ZERO(&allowed);
-        if (!list.empty() && sched_getaffinity(0, sizeof(allowed), &allowed) == 0) {
-            int n_set = 0;
-            const char *q = list.c_str();
-            while (*q) {  // "0-23,96-119"
-                char *e;
-                long a = strtol(q, &e, 10), b = a;
-                if (e == q) break;
-                if (*e == '-') { q = e + 1; b = strtol(q, &e, 10); }
-                for (long c = a; c <= b && c < CPU_SETSIZE; c++)
-                    if (CPU_ISSET((int)c, &allowed)) { CPU_SET((int)c, &nc.set); n_set++; }
-                q = (*e == ',') ? e + 1 : e;
-                if (*e != ',' ) break;
-            }
-            nc.ok = n_set >= 4 && n_set < CPU_COUNT(&allowed);  // (all of the allowed CPUs on that node: nothing to choose)
-            nc.node = node;
-        }
-    } else {
-        (void)hipGetLastError();
-    }
-    return known.emplace(device, nc).first->second;
-}
-void pin_this_thread(const NodeCpus *nc) {
-    if (nc && nc->ok) (void)pthread_setaffinity_np(pthread_self(), sizeof(nc->set), &nc->set);
-}
-
-struct PinBuf {  // page-locked host staging, grow-only
-    void *p = nullptr;
-    size_t cap = 0;
-    // (node: allocated by a short-lived thread that runs next to the GPU, so that the pages -- pinned as they are allocated -- come
-    //  from that node's memory; the caller's own thread is never moved)
-    int reserve(size_t n, const NodeCpus *node = nullptr, int device = 0) {
-        if (n <= cap) return RK_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n + n / 4 + 256;
-        hipError_t e = hipSuccess;
-        bool done = false;
-        if (node && node->ok) {
-            try {
-                std::thread t([&]() {
-                    pin_this_thread(node);
-                    (void)hipSetDevice(device);
-                    e = hipHostMalloc(&p, want, hipHostMallocDefault);
-                });
-                t.join();
-                done = true;
-            } catch (...) {  // no thread to be had: allocate here
-            }
-        }
-        if (!done) e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RK_ERR_NOMEM : RK_ERR_HIP, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-        cap = want;
-        return RK_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-    template <class T> T *as() { return (T *)p; }
-};
-
-// memcpy split over a few host threads: one thread moves ~10 GB/s, the PCIe link five times that
-void parallel_copy(void *dst, const void *src, size_t bytes) {
-    const size_t min_part = 2u << 20;
-    unsigned hw = std::thread::hardware_concurrency();
-    size_t parts = std::min<size_t>(std::min<unsigned>(hw ? hw : 1u, 12u), bytes / min_part);
-    if (parts <= 1) { if (bytes) memcpy(dst, src, bytes); return; }
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < parts; i++) {
-        const size_t a = bytes * i / parts, b = bytes * (i + 1) / parts;
-        th.emplace_back([=]() { memcpy((char *)dst + a, (const char *)src + a, b - a); });
-    }
-    memcpy(dst, src, bytes / parts);
-    for (std::thread &t : th) t.join();
-}
-
-// A few worker threads that live for the duration of ONE host call: run(fn) executes fn(part, parts) on every worker and on the
-// caller and returns when all are done (a chunk of 2^18 reads is packed in under a millisecond -- starting threads per chunk would
-// cost as much as the work).  Joined in the destructor, so no path out of the call leaves a thread behind.
-class ForkJoin {
-  public:
-    explicit ForkJoin(unsigned workers, const NodeCpus *node = nullptr) {  // node: the workers run on the CPUs next to the GPU
-        for (unsigned i = 0; i < workers; i++) th_.emplace_back([this, i, node]() { pin_this_thread(node); loop(i + 1); });
-    }
-    ~ForkJoin() {
-        { std::lock_guard<std::mutex> lk(m_); stop_ = true; gen_.fetch_add(1); }
-        cv_.notify_all();
-        for (std::thread &t : th_) t.join();
-    }
-    unsigned parts() const { return (unsigned)th_.size() + 1; }
-    void run(const std::function<void(unsigned, unsigned)> &fn) {  // the workers and the caller, each one part; returns when all are done
-        if (th_.empty()) { fn(0, 1); return; }
-        post(&fn, 0, parts());
-        fn(0, parts());
-        wait();
-    }
-    // the workers alone, while the caller does something else; wait() before the next start() / run().  Without workers the
-    // function runs in start().
-    void start(std::function<void(unsigned, unsigned)> fn) {
-        if (th_.empty()) { fn(0, 1); return; }
-        own_ = std::move(fn);
-        post(&own_, 1, (unsigned)th_.size());
-    }
-    void wait() {
-        for (int spin = 0; spin < 4000 && left_.load(std::memory_order_acquire) != 0; spin++) cpu_relax();
-        if (left_.load(std::memory_order_acquire) == 0) return;
-        std::unique_lock<std::mutex> lk(m_);
-        done_.wait(lk, [&]() { return left_.load() == 0; });
-    }
-
-  private:
-    static void cpu_relax() {
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    void post(const std::function<void(unsigned, unsigned)> *fn, unsigned base, unsigned parts) {
-        {
-            std::lock_guard<std::mutex> lk(m_);
-            fn_ = fn; base_ = base; parts_ = parts;
-            left_.store((unsigned)th_.size(), std::memory_order_release);
-            gen_.fetch_add(1, std::memory_order_release);
-        }
-        cv_.notify_all();
-    }
-    // A chunk of the host path is staged in well under a millisecond, so a worker that has just finished one job spins for a few
-    // tens of microseconds before it blocks: the next job usually arrives within that time and a futex wake-up costs as much.
-    void loop(unsigned me) {
-        uint64_t seen = 0;
-        while (true) {
-            for (int spin = 0; spin < 3000 && gen_.load(std::memory_order_acquire) == seen; spin++) cpu_relax();  // (~30 us; a hosting JVM has pools of its own to feed)
-            const std::function<void(unsigned, unsigned)> *fn;
-            unsigned part, parts;
-            {
-                std::unique_lock<std::mutex> lk(m_);
-                cv_.wait(lk, [&]() { return gen_.load() != seen; });
-                seen = gen_.load();
-                if (stop_) return;
-                fn = fn_;
-                part = me - base_;
-                parts = parts_;
-            }
-            (*fn)(part, parts);
-            if (left_.fetch_sub(1, std::memory_order_acq_rel) == 1) {
-                std::lock_guard<std::mutex> lk(m_);
-                done_.notify_all();
-            }
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    const std::function<void(unsigned, unsigned)> *fn_ = nullptr;
-    std::function<void(unsigned, unsigned)> own_;
-    std::atomic<uint64_t> gen_{0};
-    std::atomic<unsigned> left_{0};
-    unsigned base_ = 0, parts_ = 1;
-    bool stop_ = false;
-};
-
-// rk_place_batch_multi runs one host call per GPU at the same time: each takes its share of the thread budget
-thread_local unsigned tl_concurrent_calls = 1;
-unsigned host_threads(uint64_t n_reads, unsigned asked) {
-    unsigned hw = std::thread::hardware_concurrency();
-    unsigned T = asked ? asked : std::max(2u, std::min(hw ? hw : 1u, 16u * tl_concurrent_calls) / tl_concurrent_calls);
-    if (!asked && T > 16u) T = 16u;
-    return n_reads < 4096 ? 1u : T;
-}
-}  // namespace
-
-struct rk_workspace {
-    GrowBuf ascii, off, packed, lens, flags, nrows, branch, score, lwr, oflags;
-    GrowBuf strands;  // rk_place_batch_strands: the workspace of rk_place_packed_device_strands for a chunk
-    GrowBuf translated, frames;  // rk_place_batch_translated: the workspace of rk_place_packed_device_translated and the frame bytes
-    // page-locked staging for callers that hand over pageable memory (a JVM heap array, a numpy array): copies to / from
-    // it run on a few host threads, the DMA itself is then asynchronous and overlaps the other workspace's chunk
-    PinBuf h_ascii, h_off, h_packed, h_nrows, h_branch, h_score, h_lwr, h_oflags;
-    bool pending = false;       // results of the last chunk are still in the staging buffers
-    uint64_t pend_r0 = 0, pend_n = 0;
-    hipStream_t stream = nullptr;
-    void release() {
-        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &nrows, &branch, &score, &lwr, &oflags, &strands, &translated, &frames}) b->release();
-        for (PinBuf *b : {&h_ascii, &h_off, &h_packed, &h_nrows, &h_branch, &h_score, &h_lwr, &h_oflags}) b->release();
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
-    }
-};
+#include "rk_hostbuf_impl.h"
 
 // mid-size trees: the score vector of a read is held one window of W branches at a time (place_packed16w_kernel)
 constexpr uint32_t RK_MAX_WINDOWS = 64;  // 6-bit window ids in winspec and in the item tags
@@ -1231,98 +1004,6 @@ extern "C" int rk_db_get_info(const rk_db *db, rk_db_info *info) {
     if (!db || !info) return fail(RK_ERR_INVALID, "rk_db_get_info: null argument");
     *info = db->info;
     return RK_OK;
-}
-
-static int check_params(const rk_params *p);
-
-// one host thread per device handle; contiguous shards; see include/rappas_place.h
-extern "C" int rk_place_batch_multi(rk_db *const *dbs, uint32_t n_dbs, const rk_params *p, uint64_t n_reads,
-                                    const uint8_t *seq_ascii, const uint64_t *seq_off, rk_result *out, rk_counters *counters) {
-    if (!dbs || n_dbs == 0 || !out) return fail(RK_ERR_INVALID, "rk_place_batch_multi: null argument");
-    for (uint32_t g = 0; g < n_dbs; g++)
-        if (!dbs[g]) return fail(RK_ERR_INVALID, "rk_place_batch_multi: dbs[%u] is null", g);
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (n_dbs == 1 || n_reads == 0) return rk_place_batch(dbs[0], p, n_reads, seq_ascii, seq_off, out, counters);
-    if (!seq_ascii || !seq_off) return fail(RK_ERR_INVALID, "rk_place_batch_multi: null reads");
-    if (!out->n_rows || !out->branch || !out->score || !out->lwr || !out->flags) return fail(RK_ERR_INVALID, "rk_place_batch_multi: null result array");
-    const uint32_t K = p->keep_at_most;
-    RK_GUARD_BEGIN
-    std::vector<int> codes(n_dbs, RK_OK);
-    std::vector<std::string> msgs(n_dbs);
-    std::vector<rk_counters> cts(n_dbs);
-    // developer / test knob: the first attempt of this shard reports a device failure (exercises the re-queue below)
-#ifdef RK_DEV_KNOBS
-    const int inject = rk_knob("RK_TEST_FAIL_SHARD") ? atoi(rk_knob("RK_TEST_FAIL_SHARD")) : -1;
-#endif
-    auto run_shard = [&](uint32_t g, uint32_t on, bool first_attempt) {  // shard g of the batch on handle `on`, in the calling thread
-        const uint64_t lo = n_reads * g / n_dbs, hi = n_reads * (g + 1) / n_dbs;
-        cts[g] = rk_counters{};
-        codes[g] = RK_OK;
-        if (hi == lo) return;
-#ifdef RK_DEV_KNOBS
-        if (first_attempt && inject == (int)g) {
-            codes[g] = RK_ERR_HIP;
-            msgs[g] = "injected failure (RK_TEST_FAIL_SHARD)";
-            return;
-        }
-#else
-        (void)first_attempt;
-#endif
-        rk_result r{out->n_rows + lo, out->branch + lo * K, out->score + lo * K, out->lwr + lo * K, out->flags + lo};
-        tl_concurrent_calls = first_attempt ? n_dbs : 1u;  // (this shard's thread: the host threads its call starts are 1 / n_dbs of the budget)
-        codes[g] = rk_place_batch(dbs[on], p, hi - lo, seq_ascii, seq_off + lo, &r, &cts[g]);
-        tl_concurrent_calls = 1;
-        try {
-            if (codes[g] != RK_OK) msgs[g] = rk_last_error();  // the message lives in this thread: hand it over
-        } catch (...) {  // (nothing may leave a thread's function: std::terminate would take the hosting process down)
-        }
-    };
-    struct JoinAll {  // joined on every way out of the scope, a throwing emplace_back included
-        std::vector<std::thread> v;
-        ~JoinAll() { for (std::thread &t : v) if (t.joinable()) t.join(); }
-    };
-    {
-        JoinAll workers;
-        workers.v.reserve(n_dbs);
-        for (uint32_t g = 0; g < n_dbs; g++) workers.v.emplace_back([&, g]() { run_shard(g, g, true); });
-    }
-    // A shard whose device failed (per-GPU failure => shard re-queued on another GPU) is placed again on
-    // the handles that did finish, one after the other, each attempt in a fresh host thread; the process is never restarted.
-    // Argument errors (RK_ERR_INVALID / RK_ERR_UNSUPPORTED) would fail anywhere and are not retried.
-    std::vector<char> healthy(n_dbs);
-    for (uint32_t g = 0; g < n_dbs; g++) healthy[g] = codes[g] == RK_OK;
-    std::string note;
-    for (uint32_t g = 0; g < n_dbs; g++) {
-        if (codes[g] == RK_OK || codes[g] == RK_ERR_INVALID || codes[g] == RK_ERR_UNSUPPORTED) continue;
-        const std::string first_msg = msgs[g];
-        const int first_code = codes[g];
-        for (uint32_t h = 0; h < n_dbs && codes[g] != RK_OK; h++) {
-            if (!healthy[h]) continue;
-            {
-                JoinAll one;
-                one.v.emplace_back([&, g, h]() { run_shard(g, h, false); });
-            }
-            if (codes[g] == RK_OK) {
-                char buf[256];
-                snprintf(buf, sizeof(buf), "shard %u failed on device %d (%d: %.120s) and was placed on device %d; ", g, dbs[g]->info.device,
-                         first_code, first_msg.c_str(), dbs[h]->info.device);
-                note += buf;
-            }
-        }
-        if (codes[g] != RK_OK) { codes[g] = first_code; msgs[g] = first_msg; }
-    }
-    rk_counters total{};
-    for (uint32_t g = 0; g < n_dbs; g++) {
-        if (codes[g] != RK_OK) return fail(codes[g], "rk_place_batch_multi: shard %u (device %d): %s", g, dbs[g]->info.device, msgs[g].c_str());
-        total.reads += cts[g].reads; total.placed += cts[g].placed; total.unplaced += cts[g].unplaced;
-        total.bad_char += cts[g].bad_char; total.too_short += cts[g].too_short; total.ambiguous += cts[g].ambiguous;
-    }
-    if (counters) *counters = total;
-    // success, but the caller can still learn which device dropped out: rk_last_error() carries the note (empty otherwise)
-    (void)fail(RK_OK, "%s", note.c_str());
-    return RK_OK;
-    RK_GUARD_END("rk_place_batch_multi")
 }
 
 extern "C" void *rk_host_alloc(uint64_t bytes) {
@@ -2504,21 +2185,6 @@ extern "C" int rk_count_work_device(rk_db *db, uint64_t n_reads, const uint32_t 
     return RK_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// host-buffer entry point: chunked, two workspaces on two streams so that the upload of chunk c+1 overlaps the
-// kernels / download of chunk c; device buffers are kept (grow-only) in the rk_db between calls
-// ------------------------------------------------------------------------------------------------
-// what the host hands over: ASCII reads (packed on the device) or records already packed on the host (rk_pack_reads_host)
-struct HostInput {
-    const uint8_t *ascii = nullptr;   // concatenated reads; with `packed` set: only consulted for reads flagged AMBIGUOUS
-    const uint64_t *off = nullptr;    // [n + 1]
-    const uint32_t *packed = nullptr; // [n][wpr]
-    uint32_t wpr = 0;
-    const uint32_t *lens = nullptr;   // [n] or NULL (fixed_len)
-    uint32_t fixed_len = 0;
-    const uint32_t *flags = nullptr;  // [n] or NULL
-};
-
 static rk::PackSpec pack_spec(const Alphabet &A, uint32_t alphabet, uint32_t bits, uint32_t k, uint32_t words_per_read) {
     rk::PackSpec P;
     P.table = A.table; P.bits = bits; P.k = k; P.words_per_read = words_per_read;
@@ -2527,469 +2193,7 @@ static rk::PackSpec pack_spec(const Alphabet &A, uint32_t alphabet, uint32_t bit
     return P;
 }
 
-static int place_host(rk_db *db, const rk_params *p, uint64_t n_reads, const HostInput &in, rk_result *out, rk_counters *counters,
-                      const char *who, uint32_t strand = RK_STRAND_FORWARD) {
-    const bool packed_in = in.packed != nullptr;
-    const uint8_t *seq_ascii = in.ascii;
-    const uint64_t *seq_off = in.off;
-    rk_counters ct{};
-    if (n_reads == 0) { if (counters) *counters = ct; return RK_OK; }
-    if (!out->n_rows || !out->branch || !out->score || !out->lwr || !out->flags) return fail(RK_ERR_INVALID, "%s: null result array", who);
-    if (seq_off)
-        for (uint64_t r = 0; r < n_reads; r++)
-            if (seq_off[r + 1] < seq_off[r]) return fail(RK_ERR_INVALID, "%s: seq_off not monotone at read %llu", who, (unsigned long long)r);
-    std::lock_guard<std::mutex> lock(db->host_mutex);  // the two workspaces belong to the db: one host call at a time
-    HIP_TRY(hipSetDevice(db->info.device));
-    const uint32_t K = p->keep_at_most;
-    // chunks of 2^18 reads: the kernel still fills the chip (2^16 tiles for 2 048 waves) and the part of a call that nothing
-    // overlaps -- the first chunk's upload, the last chunk's download and drain -- stays short
-    uint64_t max_chunk_reads = 1ull << 18;
-    if (const char *e = rk_knob("RK_CHUNK_READS")) {  // developer knob
-        const long v = atol(e);
-        if (v >= 1024) max_chunk_reads = (uint64_t)v;
-    }
-    const uint64_t max_chunk_bytes = 128ull << 20;
-    for (rk_workspace &w : db->ws)
-        if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    // Caller buffers from rk_host_alloc (or otherwise page-locked) are the DMA's source / target directly; pageable ones
-    // (the usual case behind JNI) go through page-locked staging with threaded copies
-    auto is_pinned = [](const void *ptr) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
-        return at.type == hipMemoryTypeHost;
-    };
-    const bool in_pinned = packed_in ? is_pinned(in.packed) : is_pinned(seq_ascii);
-    const bool out_pinned = is_pinned(out->n_rows) && is_pinned(out->branch) && is_pinned(out->score) && is_pinned(out->lwr) && is_pinned(out->flags);
-    // pageable characters are packed on the host (rk_pack_host.cpp) by this call's worker threads; page-locked ones go to the
-    // device as they are (no host work at all) and are packed there
-    const bool host_pack = !packed_in && !in_pinned;
-    Alphabet alpha;
-    if (host_pack) build_alphabet(db->info.alphabet, db->convert_uo != 0, alpha);
-    // host threads of this call: staging / packing on one side, result copies on the other (both only for pageable memory)
-    unsigned n_stage = in_pinned ? 0u : std::max(1u, host_threads(n_reads, 0) * 5 / 8), n_drain = out_pinned ? 0u : std::max(1u, host_threads(n_reads, 0) * 3 / 8);
-    if (const char *e = rk_knob("RK_STAGE_THREADS")) n_stage = (unsigned)std::max(1, atoi(e));   // developer knobs
-    if (const char *e = rk_knob("RK_DRAIN_THREADS")) n_drain = (unsigned)std::max(1, atoi(e));
-    const NodeCpus *node = &gpu_node_cpus(db->info.device);  // the CPUs next to the GPU: staging threads and page-locked buffers live there
-    ForkJoin pool(n_stage ? n_stage - 1 : 0, node);
-    auto count_flags = [&](const uint32_t *fl, uint64_t m) {  // per-batch counters, taken chunk by chunk while the flags are cache-hot
-        for (uint64_t r = 0; r < m; r++) {
-            const uint32_t f = fl[r];
-            ct.reads++;
-            if (f & RK_FLAG_PLACED) ct.placed++; else ct.unplaced++;
-            if (f & RK_FLAG_BAD_CHAR) ct.bad_char++;
-            if (f & RK_FLAG_TOO_SHORT) ct.too_short++;
-            if (f & RK_FLAG_AMBIGUOUS) ct.ambiguous++;
-        }
-    };
-    auto drain = [&](rk_workspace &w, ForkJoin &dpool) {  // staged results of the workspace's last chunk -> the caller's arrays
-        if (!w.pending) return;
-        const uint64_t a0 = w.pend_r0, m = w.pend_n;
-        if (!out_pinned) {
-            // the drain thread's workers, each a range of reads over the five arrays (103 bytes per read at K = 7)
-            dpool.run([&](unsigned part, unsigned parts) {
-                const uint64_t lo = m * part / parts, c = m * (part + 1) / parts - lo;
-                if (!c) return;
-                memcpy(out->n_rows + a0 + lo, w.h_nrows.as<uint8_t>() + lo, c);
-                memcpy(out->branch + (a0 + lo) * K, w.h_branch.as<uint16_t>() + lo * K, c * K * 2);
-                memcpy(out->score + (a0 + lo) * K, w.h_score.as<float>() + lo * K, c * K * 4);
-                memcpy(out->lwr + (a0 + lo) * K, w.h_lwr.as<double>() + lo * K, c * K * 8);
-                memcpy(out->flags + a0 + lo, w.h_oflags.as<uint32_t>() + lo, c * 4);
-            });
-        }
-        count_flags(out->flags + a0, m);
-        w.pending = false;
-    };
-    unsigned chunk_no = 0;
-    int status = RK_OK;
-    // developer knob: RK_HOST_TIMING=1 prints where the host thread of this call spent its time (stderr)
-    const bool timing = rk_knob("RK_HOST_TIMING") != nullptr;
-    double t_wait = 0, t_drain = 0, t_stage = 0, t_enq = 0;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    // Four workspaces in flight.  The call's worker threads stage chunk c + 1 (pack its characters / copy its records into
-    // page-locked memory) while this thread enqueues chunk c, and a second host thread waits for the stream of the oldest chunk
-    // and moves its results into the caller's arrays: staging, enqueueing, the GPU's work and the result copies of different
-    // chunks overlap (one host thread doing everything by turns kept the GPU waiting: 1.6e8 reads/s on C2).
-    constexpr unsigned NWS = 4;
-    std::mutex qm;
-    std::condition_variable qcv;
-    std::deque<unsigned> submitted;   // workspace indices in submission order
-    bool ws_busy[NWS] = {false, false, false, false};
-    bool closing = false;
-    int drain_status = RK_OK;
-    std::string drain_msg;
-    const int device = db->info.device;
-    std::thread drainer([&]() {
-        pin_this_thread(node);
-        (void)hipSetDevice(device);
-        std::unique_ptr<ForkJoin> dpool;
-        try {
-            dpool.reset(new ForkJoin(n_drain ? n_drain - 1 : 0, node));
-        } catch (...) {  // no worker threads: this thread copies alone
-        }
-        ForkJoin none(0);
-        while (true) {
-            unsigned wi;
-            {
-                std::unique_lock<std::mutex> lk(qm);
-                qcv.wait(lk, [&]() { return !submitted.empty() || closing; });
-                if (submitted.empty()) return;
-                wi = submitted.front();
-                submitted.pop_front();
-            }
-            rk_workspace &w = db->ws[wi];
-            const double t0 = now();
-            const hipError_t he = hipStreamSynchronize(w.stream);
-            const double t1 = now();
-            if (he != hipSuccess) {
-                std::lock_guard<std::mutex> lk(qm);
-                if (drain_status == RK_OK) { drain_status = RK_ERR_HIP; drain_msg = std::string("hipStreamSynchronize failed: ") + hipGetErrorString(he); }
-                w.pending = false;
-            } else {
-                bool ok;
-                { std::lock_guard<std::mutex> lk(qm); ok = drain_status == RK_OK; }
-                if (ok) {
-                    try {
-                        drain(w, dpool ? *dpool : none);
-                    } catch (...) {
-                        std::lock_guard<std::mutex> lk(qm);
-                        if (drain_status == RK_OK) { drain_status = RK_ERR_NOMEM; drain_msg = "out of host memory while moving results"; }
-                        w.pending = false;
-                    }
-                } else w.pending = false;
-            }
-            t_wait += t1 - t0; t_drain += now() - t1;
-            {
-                std::lock_guard<std::mutex> lk(qm);
-                ws_busy[wi] = false;
-            }
-            qcv.notify_all();
-        }
-    });
-    // the drainer is joined on EVERY way out of this function, an exception thrown by a container or a thread constructor included
-    // (a joinable std::thread that is destroyed calls std::terminate, which would take the hosting JVM down)
-    struct JoinOnExit {
-        std::function<void()> fn;
-        ~JoinOnExit() { if (fn) fn(); }
-    } join_on_exit;
-    auto finish = [&]() {  // every submitted chunk drained, the thread joined
-        if (!drainer.joinable()) return;
-        { std::lock_guard<std::mutex> lk(qm); closing = true; }
-        qcv.notify_all();
-        drainer.join();
-    };
-    join_on_exit.fn = finish;
-    // A chunk's host side (plan + stage) runs one chunk ahead of its device side (enqueue).
-    struct Plan {
-        uint64_t r0 = 0, r1 = 0, n = 0;
-        uint32_t wpr = 0;
-        unsigned wi = 0;
-        size_t pb = 0;
-        bool staged_async = false;
-        std::atomic<uint32_t> flags{0};   // OR of the flags the host packer set
-    };
-    Plan plans[2];
-    auto plan_chunk = [&](Plan &c, uint64_t from, unsigned no) -> int {  // bounds, record width, workspace (waits until it is free)
-        uint64_t r1 = from, max_len = 0;
-        if (packed_in) {
-            r1 = std::min(n_reads, from + max_chunk_reads);
-        } else {
-            while (r1 < n_reads && r1 - from < max_chunk_reads && (seq_off[r1 + 1] - seq_off[from] <= max_chunk_bytes || r1 == from)) {
-                uint64_t L = seq_off[r1 + 1] - seq_off[r1];
-                if (L > max_len) max_len = L;
-                r1++;
-            }
-        }
-        if (max_len > 0x7FFFFFFFull / 8) return fail(RK_ERR_UNSUPPORTED, "%s: read longer than 2^28 symbols", who);
-        c.r0 = from; c.r1 = r1; c.n = r1 - from;
-        c.wpr = packed_in ? in.wpr : rk_packed_words(db, (uint32_t)max_len);
-        c.wi = no % NWS;
-        c.pb = c.n * c.wpr * 4;
-        c.staged_async = false;
-        c.flags.store(0);
-        // the workspace was last used four chunks ago: its results must have left the staging buffers before it is overwritten
-        std::unique_lock<std::mutex> lk(qm);
-        qcv.wait(lk, [&]() { return !ws_busy[c.wi]; });
-        if (drain_status != RK_OK) return fail(drain_status, "%s", drain_msg.c_str());
-        return RK_OK;
-    };
-    // host work of a chunk that needs no HIP call: started on the worker threads, joined with pool.wait()
-    auto stage_start = [&](Plan &c) -> int {
-        rk_workspace &w = db->ws[c.wi];
-        const uint64_t n = c.n, c0 = c.r0;
-        if (host_pack) {
-            // pageable characters (the usual case behind JNI): packed HERE, by the call's worker threads, straight into the
-            // page-locked staging buffer -- 48 instead of 158 bytes per 150-bp read cross the link, no copy of the characters
-            int rc = w.h_packed.reserve(c.pb + 8 * n, node, device);
-            if (rc) return rc;
-            uint32_t *hp = w.h_packed.as<uint32_t>(), *hl = hp + n * c.wpr, *hf = hl + n;
-            const rk::PackSpec P = pack_spec(alpha, db->info.alphabet, db->info.bits_per_symbol, db->info.k, c.wpr);
-            Plan *pc = &c;
-            pool.start([=](unsigned part, unsigned parts) {
-                pc->flags.fetch_or(rk::pack_reads_range(P, seq_ascii, seq_off, c0 + n * part / parts, c0 + n * (part + 1) / parts, c0, hp, hl, hf));
-            });
-            c.staged_async = true;
-        } else if (packed_in && !in_pinned) {
-            const size_t lb = in.lens ? n * 4 : 0, fb = in.flags ? n * 4 : 0, pb = c.pb;
-            int rc = w.h_packed.reserve(pb + lb + fb, node, device);
-            if (rc) return rc;
-            const char *src = (const char *)(in.packed + c0 * c.wpr);
-            char *dst = (char *)w.h_packed.p;
-            pool.start([=](unsigned part, unsigned parts) {
-                const size_t a = pb * part / parts, b = pb * (part + 1) / parts;
-                if (b > a) memcpy(dst + a, src + a, b - a);
-            });
-            c.staged_async = true;
-        }
-        return RK_OK;
-    };
-    unsigned cur = 0;
-    if (n_reads) {
-        status = plan_chunk(plans[0], 0, 0);
-        if (status == RK_OK) status = stage_start(plans[0]);
-    }
-    while (status == RK_OK) {
-        Plan &c = plans[cur];
-        const uint64_t r0 = c.r0, r1 = c.r1, n = c.n;
-        const uint32_t wpr = c.wpr;
-        const unsigned wi = c.wi;
-        rk_workspace &w = db->ws[wi];
-        hipStream_t s = w.stream;
-        double t2 = now();
-        if (c.staged_async) pool.wait();
-        t_stage += now() - t2;
-        // the next chunk's host side starts now and runs while this chunk is enqueued
-        Plan &nx = plans[cur ^ 1];
-        const bool more = r1 < n_reads;
-#define WS_TRY(expr) do { int rc_ = (expr); if (rc_ != RK_OK) { status = rc_; goto done; } } while (0)
-#define WS_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { status = fail(RK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto done; } } while (0)
-        const size_t pb = c.pb;
-        // packed input: the ASCII of the chunk travels only if one of its reads carries the AMBIGUOUS flag (the ambiguity kernel
-        // works on characters); otherwise 38 instead of 150 bytes per 150-bp read cross the link
-        bool need_ascii = !packed_in && !host_pack;
-        if (host_pack) need_ascii = (c.flags.load() & RK_FLAG_AMBIGUOUS) != 0;
-        if (packed_in && in.flags && seq_ascii && seq_off)
-            for (uint64_t r = r0; r < r1 && !need_ascii; r++) need_ascii = (in.flags[r] & RK_FLAG_AMBIGUOUS) != 0;
-        const uint64_t nbytes = need_ascii ? seq_off[r1] - seq_off[r0] : 0;
-        if (need_ascii && nbytes && !(!packed_in && in_pinned)) {  // (rare: a chunk with ambiguity codes) its characters, staged by every thread
-            WS_TRY(w.h_ascii.reserve(nbytes, node, device));
-            const uint8_t *src = seq_ascii + seq_off[r0];
-            uint8_t *dst = w.h_ascii.as<uint8_t>();
-            pool.run([&](unsigned part, unsigned parts) {
-                const uint64_t a = nbytes * part / parts, b = nbytes * (part + 1) / parts;
-                if (b > a) memcpy(dst + a, src + a, b - a);
-            });
-        }
-        if (more) {
-            WS_TRY(plan_chunk(nx, r1, chunk_no + 1));
-            WS_TRY(stage_start(nx));
-        }
-        t2 = now();
-        WS_TRY(w.packed.reserve(pb));
-        WS_TRY(w.lens.reserve(n * 4));
-        WS_TRY(w.flags.reserve(n * 4));
-        WS_TRY(w.nrows.reserve(n));
-        WS_TRY(w.branch.reserve(n * K * 2));
-        WS_TRY(w.score.reserve(n * K * 4));
-        WS_TRY(w.lwr.reserve(n * K * 8));
-        WS_TRY(w.oflags.reserve(n * 4));
-        if (need_ascii) {
-            WS_TRY(w.ascii.reserve(nbytes));
-            WS_TRY(w.off.reserve((n + 1) * 8));
-            WS_TRY(w.h_off.reserve((n + 1) * 8, node, device));
-            uint64_t *ho = w.h_off.as<uint64_t>();
-            for (uint64_t i = 0; i <= n; i++) ho[i] = seq_off[r0 + i] - seq_off[r0];
-            if (!packed_in && in_pinned) {
-                if (nbytes) WS_HIP(hipMemcpyAsync(w.ascii.p, seq_ascii + seq_off[r0], nbytes, hipMemcpyHostToDevice, s));
-            } else if (nbytes) {
-                WS_HIP(hipMemcpyAsync(w.ascii.p, w.h_ascii.p, nbytes, hipMemcpyHostToDevice, s));
-            }
-            WS_HIP(hipMemcpyAsync(w.off.p, w.h_off.p, (n + 1) * 8, hipMemcpyHostToDevice, s));
-        }
-        if (host_pack) {
-            WS_HIP(hipMemcpyAsync(w.packed.p, w.h_packed.p, pb, hipMemcpyHostToDevice, s));
-            WS_HIP(hipMemcpyAsync(w.lens.p, (char *)w.h_packed.p + pb, n * 4, hipMemcpyHostToDevice, s));
-            WS_HIP(hipMemcpyAsync(w.flags.p, (char *)w.h_packed.p + pb + n * 4, n * 4, hipMemcpyHostToDevice, s));
-        } else if (packed_in) {
-            // packed records (+ lengths, flags): straight from page-locked caller memory, else through the staging buffer
-            const size_t lb = in.lens ? n * 4 : 0, fb = in.flags ? n * 4 : 0;
-            if (in_pinned) WS_HIP(hipMemcpyAsync(w.packed.p, in.packed + r0 * wpr, pb, hipMemcpyHostToDevice, s));
-            else WS_HIP(hipMemcpyAsync(w.packed.p, w.h_packed.p, pb, hipMemcpyHostToDevice, s));
-            // (lengths and flags are small: pageable copies are fine, but they must not be read after this call returns
-            //  -- the staging buffer keeps them when the caller's memory is pageable)
-            if (lb) {
-                if (in_pinned) WS_HIP(hipMemcpyAsync(w.lens.p, in.lens + r0, lb, hipMemcpyHostToDevice, s));
-                else { memcpy((char *)w.h_packed.p + pb, in.lens + r0, lb); WS_HIP(hipMemcpyAsync(w.lens.p, (char *)w.h_packed.p + pb, lb, hipMemcpyHostToDevice, s)); }
-            }
-            if (fb) {
-                if (in_pinned) WS_HIP(hipMemcpyAsync(w.flags.p, in.flags + r0, fb, hipMemcpyHostToDevice, s));
-                else { memcpy((char *)w.h_packed.p + pb + lb, in.flags + r0, fb); WS_HIP(hipMemcpyAsync(w.flags.p, (char *)w.h_packed.p + pb + lb, fb, hipMemcpyHostToDevice, s)); }
-            }
-        } else {
-            WS_TRY(rk_pack_reads_device(db, n, w.ascii.as<uint8_t>(), w.off.as<uint64_t>(), wpr, w.packed.as<uint32_t>(),
-                                        w.lens.as<uint32_t>(), w.flags.as<uint32_t>(), s));
-        }
-        {
-            rk_result dres{w.nrows.as<uint8_t>(), w.branch.as<uint16_t>(), w.score.as<float>(), w.lwr.as<double>(), w.oflags.as<uint32_t>()};
-            const uint32_t *d_lens = (!packed_in || in.lens) ? w.lens.as<uint32_t>() : nullptr;   // (host-packed chunks carry both)
-            const uint32_t *d_flags = (!packed_in || in.flags) ? w.flags.as<uint32_t>() : nullptr;
-            if (strand == RK_STRAND_FORWARD) {
-                WS_TRY(rk_place_packed_device(db, p, n, w.packed.as<uint32_t>(), wpr, d_lens, packed_in ? in.fixed_len : 0, d_flags,
-                                              need_ascii ? w.ascii.as<uint8_t>() : nullptr, need_ascii ? w.off.as<uint64_t>() : nullptr, &dres, s));
-            } else {
-                // the other strand's records, its result set and -- a chunk whose characters travel -- their reverse complement: part
-                // of the workspace (a chunk of empty reads has characters of length 0: one byte of room keeps the call's test quiet)
-                const uint64_t wb = rk_strands_work_bytes(db, n, wpr, K, need_ascii ? std::max<uint64_t>(nbytes, 1) : 0);
-                WS_TRY(w.strands.reserve(wb));
-                WS_TRY(rk_place_packed_device_strands(db, p, strand, n, w.packed.as<uint32_t>(), wpr, d_lens, packed_in ? in.fixed_len : 0, d_flags,
-                                                      need_ascii ? w.ascii.as<uint8_t>() : nullptr, need_ascii ? w.off.as<uint64_t>() : nullptr, &dres,
-                                                      w.strands.p, wb, s));
-            }
-        }
-        if (out_pinned) {
-            WS_HIP(hipMemcpyAsync(out->n_rows + r0, w.nrows.p, n, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(out->branch + r0 * K, w.branch.p, n * K * 2, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(out->score + r0 * K, w.score.p, n * K * 4, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(out->lwr + r0 * K, w.lwr.p, n * K * 8, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(out->flags + r0, w.oflags.p, n * 4, hipMemcpyDeviceToHost, s));
-        } else {
-            WS_TRY(w.h_nrows.reserve(n, node, device));
-            WS_TRY(w.h_branch.reserve(n * K * 2, node, device));
-            WS_TRY(w.h_score.reserve(n * K * 4, node, device));
-            WS_TRY(w.h_lwr.reserve(n * K * 8, node, device));
-            WS_TRY(w.h_oflags.reserve(n * 4, node, device));
-            WS_HIP(hipMemcpyAsync(w.h_nrows.p, w.nrows.p, n, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(w.h_branch.p, w.branch.p, n * K * 2, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(w.h_score.p, w.score.p, n * K * 4, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(w.h_lwr.p, w.lwr.p, n * K * 8, hipMemcpyDeviceToHost, s));
-            WS_HIP(hipMemcpyAsync(w.h_oflags.p, w.oflags.p, n * 4, hipMemcpyDeviceToHost, s));
-        }
-#undef WS_TRY
-#undef WS_HIP
-        w.pending = true; w.pend_r0 = r0; w.pend_n = n;  // (page-locked caller arrays: nothing to copy, the flags are still counted)
-        {
-            std::lock_guard<std::mutex> lk(qm);
-            ws_busy[wi] = true;
-            submitted.push_back(wi);
-        }
-        qcv.notify_all();
-        t_enq += now() - t2;
-        chunk_no++;
-        if (!more) break;
-        cur ^= 1;
-    }
-done:
-    pool.wait();  // (an error may leave the next chunk's staging running: it reads the caller's arrays)
-    finish();
-    for (rk_workspace &w : db->ws) {  // (after an error some streams may still hold work of a half-enqueued chunk)
-        if (w.stream && status != RK_OK) (void)hipStreamSynchronize(w.stream);
-        w.pending = false;
-    }
-    if (timing)
-        fprintf(stderr, "%s: GPU %d on NUMA node %d, %d of this process's CPUs there, staging threads %s; %u staging + %u drain threads\n", who, device, node->node,
-                node->ok ? CPU_COUNT(&node->set) : 0, node->ok ? "kept there" : "not pinned", n_stage, n_drain);
-    if (timing)
-        fprintf(stderr, "%s: %u chunks; submit thread: stage input %.1f ms, stage+enqueue %.1f ms; drain thread: wait for stream %.1f ms, move results %.1f ms\n",
-                who, chunk_no, t_stage * 1e3, t_enq * 1e3, t_wait * 1e3, t_drain * 1e3);
-    if (status == RK_OK && drain_status != RK_OK) status = fail(drain_status, "%s", drain_msg.c_str());
-    if (status != RK_OK) return status;
-    if (counters) *counters = ct;
-    return RK_OK;
-}
-
-// What the first rk_place_batch / rk_place_batch_packed of a handle would set up on its way -- the four workspaces' streams, device
-// buffers and page-locked staging buffers for full chunks of reads of up to max_read_len symbols, the launches' scratch -- done ahead
-// of time (a caller does this while it is still reading its input: ~80 ms that the first batch then does not pay).
-extern "C" int rk_reserve_host_path(rk_db *db, uint32_t keep_at_most, uint32_t max_read_len) {
-    if (!db) return fail(RK_ERR_INVALID, "rk_reserve_host_path: null handle");
-    if (keep_at_most < 1 || keep_at_most > 16) return fail(RK_ERR_INVALID, "keep_at_most=%u outside 1..16", keep_at_most);
-    RK_GUARD_BEGIN
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    struct Restore { int p; ~Restore() { (void)hipSetDevice(p); } } restore{prev};
-    {
-    std::lock_guard<std::mutex> lock(db->host_mutex);
-    HIP_TRY(hipSetDevice(db->info.device));
-    const uint64_t n = 1ull << 18, K = keep_at_most;  // (place_host's chunk)
-    const uint32_t wpr = rk_packed_words(db, max_read_len ? max_read_len : 1);
-    const size_t pb = (size_t)n * wpr * 4;
-    const NodeCpus *node = &gpu_node_cpus(db->info.device);
-    const int device = db->info.device;
-    for (rk_workspace &w : db->ws) {
-        if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-        int rc;
-        if ((rc = w.packed.reserve(pb)) || (rc = w.lens.reserve(n * 4)) || (rc = w.flags.reserve(n * 4)) || (rc = w.nrows.reserve(n)) || (rc = w.branch.reserve(n * K * 2)) ||
-            (rc = w.score.reserve(n * K * 4)) || (rc = w.lwr.reserve(n * K * 8)) || (rc = w.oflags.reserve(n * 4)) || (rc = w.h_packed.reserve(pb + 8 * n, node, device)) ||
-            (rc = w.h_nrows.reserve(n, node, device)) || (rc = w.h_branch.reserve(n * K * 2, node, device)) || (rc = w.h_score.reserve(n * K * 4, node, device)) ||
-            (rc = w.h_lwr.reserve(n * K * 8, node, device)) || (rc = w.h_oflags.reserve(n * 4, node, device)))
-            return rc;
-        (void)launch_scratch(db, w.stream, 1024 + (size_t)n / 4 + 256 + (size_t)n * 5 + 512);
-    }
-    }
-    {
-        // ... and one small batch through the whole path: the runtime loads a kernel's code to the device at its first launch
-        // (tens of milliseconds for the packer, the placement kernel and the tile-order pre-pass together)
-        const uint64_t m = 32768;  // (the pre-pass starts at this many reads)
-        const uint32_t len = std::max<uint32_t>(db->info.k, std::min<uint32_t>(max_read_len ? max_read_len : 1u, 64u));
-        std::vector<uint8_t> seq((size_t)m * len, db->info.alphabet == RK_ALPHABET_DNA ? (uint8_t)'A' : (uint8_t)'R');
-        std::vector<uint64_t> off(m + 1);
-        for (uint64_t i = 0; i <= m; i++) off[i] = i * len;
-        std::vector<uint8_t> n_rows(m);
-        std::vector<uint16_t> branch(m * keep_at_most);
-        std::vector<float> score(m * keep_at_most);
-        std::vector<double> lwr(m * keep_at_most);
-        std::vector<uint32_t> flags(m);
-        rk_result res{n_rows.data(), branch.data(), score.data(), lwr.data(), flags.data()};
-        rk_params p{keep_at_most, 0.01f, RK_AMB_MEAN, -INFINITY};
-        return rk_place_batch(db, &p, m, seq.data(), off.data(), &res, nullptr);
-    }
-    RK_GUARD_END("rk_reserve_host_path")
-}
-
-extern "C" int rk_place_batch(rk_db *db, const rk_params *p, uint64_t n_reads, const uint8_t *seq_ascii,
-                              const uint64_t *seq_off, rk_result *out, rk_counters *counters) {
-    if (!db || !out) return fail(RK_ERR_INVALID, "rk_place_batch: null argument");
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (n_reads && (!seq_ascii || !seq_off)) return fail(RK_ERR_INVALID, "rk_place_batch: null reads");
-    HostInput in;
-    in.ascii = seq_ascii; in.off = seq_off;
-    RK_GUARD_BEGIN
-    return place_host(db, p, n_reads, in, out, counters, "rk_place_batch");
-    RK_GUARD_END("rk_place_batch")
-}
-
-extern "C" int rk_place_batch_strands(rk_db *db, const rk_params *p, uint32_t strand, uint64_t n_reads, const uint8_t *seq_ascii,
-                                      const uint64_t *seq_off, rk_result *out, rk_counters *counters) {
-    int rc = strands_handle(db, "rk_place_batch_strands");
-    if (rc) return rc;
-    if (strand > RK_STRAND_BOTH) return fail(RK_ERR_INVALID, "rk_place_batch_strands: strand=%u (0 forward, 1 reverse, 2 both)", strand);
-    if (!out) return fail(RK_ERR_INVALID, "rk_place_batch_strands: null argument");
-    rc = check_params(p);
-    if (rc) return rc;
-    if (n_reads && (!seq_ascii || !seq_off)) return fail(RK_ERR_INVALID, "rk_place_batch_strands: null reads");
-    HostInput in;
-    in.ascii = seq_ascii; in.off = seq_off;
-    RK_GUARD_BEGIN
-    return place_host(db, p, n_reads, in, out, counters, "rk_place_batch_strands", strand);
-    RK_GUARD_END("rk_place_batch_strands")
-}
-
-extern "C" int rk_place_batch_packed(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *packed, uint32_t words_per_read,
-                                     const uint32_t *lens, uint32_t fixed_len, const uint32_t *flags, const uint8_t *seq_ascii,
-                                     const uint64_t *seq_off, rk_result *out, rk_counters *counters) {
-    if (!db || !out) return fail(RK_ERR_INVALID, "rk_place_batch_packed: null argument");
-    int rc = check_params(p);
-    if (rc) return rc;
-    if (n_reads && (!packed || words_per_read == 0)) return fail(RK_ERR_INVALID, "rk_place_batch_packed: null packed reads");
-    rc = check_fixed_len("rk_place_batch_packed", lens, fixed_len, db->info.bits_per_symbol, words_per_read);
-    if (rc) return rc;
-    if ((seq_ascii == nullptr) != (seq_off == nullptr)) return fail(RK_ERR_INVALID, "rk_place_batch_packed: seq_ascii and seq_off go together");
-    HostInput in;
-    in.ascii = seq_ascii; in.off = seq_off; in.packed = packed; in.wpr = words_per_read; in.lens = lens; in.fixed_len = fixed_len; in.flags = flags;
-    RK_GUARD_BEGIN
-    return place_host(db, p, n_reads, in, out, counters, "rk_place_batch_packed");
-    RK_GUARD_END("rk_place_batch_packed")
-}
+#include "rk_hostpath_impl.h"
 
 // AmbigSequenceKnife.initTables' char -> state part (AmbigSequenceKnife.java:103-130) on the host, for callers that would rather
 // ship 2 / 5 bits per symbol over PCIe than 8: the same records, lengths and flags pack_reads_kernel produces (rk_pack_host.cpp:
@@ -3027,80 +2231,6 @@ extern "C" int rk_pack_reads(uint32_t alphabet, int convert_uo, uint32_t k, uint
     return pack_reads_threads(pack_spec(A, alphabet, alphabet == RK_ALPHABET_DNA ? 2u : 5u, k, words_per_read), n_reads, seq_ascii, seq_off, packed,
                               lens, flags, n_threads);
     RK_GUARD_END("rk_pack_reads")
-}
-
-// DNA characters from the host onto an amino-acid database: packed here (rk_pack_reads), then rk_place_packed_device_translated chunk
-// by chunk through the first workspace of the handle's host path.  One chunk in flight -- six placement passes a chunk are the cost,
-// not the copies around them.
-extern "C" int rk_place_batch_translated(rk_db *db, const rk_params *p, uint64_t n_reads, const uint8_t *seq_ascii, const uint64_t *seq_off,
-                                         rk_result *out, uint8_t *frame_out, rk_counters *counters) {
-    const char *who = "rk_place_batch_translated";
-    int rc = translated_handle(db, who);
-    if (rc) return rc;
-    if (!out) return fail(RK_ERR_INVALID, "%s: null argument", who);
-    rc = check_params(p);
-    if (rc) return rc;
-    if (n_reads && (!seq_ascii || !seq_off)) return fail(RK_ERR_INVALID, "%s: null reads", who);
-    RK_GUARD_BEGIN
-    rk_counters ct{};
-    if (n_reads == 0) { if (counters) *counters = ct; return RK_OK; }
-    if (!out->n_rows || !out->branch || !out->score || !out->lwr || !out->flags || !frame_out) return fail(RK_ERR_INVALID, "%s: null result array", who);
-    uint64_t max_len = 0;
-    for (uint64_t r = 0; r < n_reads; r++) {
-        if (seq_off[r + 1] < seq_off[r]) return fail(RK_ERR_INVALID, "%s: seq_off not monotone at read %llu", who, (unsigned long long)r);
-        max_len = std::max(max_len, seq_off[r + 1] - seq_off[r]);
-    }
-    if (max_len > 0x7FFFFFFFull / 8) return fail(RK_ERR_UNSUPPORTED, "%s: read longer than 2^28 symbols", who);
-    const uint32_t dna_words = (uint32_t)std::max<uint64_t>(1, (max_len * 2 + 31) / 32);  // one record width for the whole batch
-    const uint32_t K = p->keep_at_most;
-    uint64_t max_chunk_reads = 1ull << 18;  // (place_host's chunk)
-    if (const char *e = rk_knob("RK_CHUNK_READS")) {  // developer knob
-        const long v = atol(e);
-        if (v >= 1024) max_chunk_reads = (uint64_t)v;
-    }
-    std::lock_guard<std::mutex> lock(db->host_mutex);  // the workspaces belong to the db: one host call at a time
-    HIP_TRY(hipSetDevice(db->info.device));
-    rk_workspace &w = db->ws[0];
-    if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    hipStream_t s = w.stream;
-    std::vector<uint32_t> h_packed, h_lens, h_flags;
-    for (uint64_t r0 = 0; r0 < n_reads; r0 += max_chunk_reads) {
-        const uint64_t n = std::min(max_chunk_reads, n_reads - r0);
-        h_packed.resize(n * dna_words); h_lens.resize(n); h_flags.resize(n);
-        rc = rk_pack_reads(RK_ALPHABET_DNA, 0, 1, n, seq_ascii, seq_off + r0, dna_words, h_packed.data(), h_lens.data(), h_flags.data(), 0);
-        if (rc) return rc;
-        const uint64_t wb = rk_translated_work_bytes(db, n, dna_words, K);
-        if (!wb) return RK_ERR_INVALID;
-        if ((rc = w.packed.reserve(n * dna_words * 4)) || (rc = w.lens.reserve(n * 4)) || (rc = w.flags.reserve(n * 4)) || (rc = w.nrows.reserve(n)) ||
-            (rc = w.branch.reserve(n * K * 2)) || (rc = w.score.reserve(n * K * 4)) || (rc = w.lwr.reserve(n * K * 8)) || (rc = w.oflags.reserve(n * 4)) ||
-            (rc = w.frames.reserve(n)) || (rc = w.translated.reserve(wb)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(w.packed.p, h_packed.data(), n * dna_words * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w.lens.p, h_lens.data(), n * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w.flags.p, h_flags.data(), n * 4, hipMemcpyHostToDevice, s));
-        const rk_result dres{w.nrows.as<uint8_t>(), w.branch.as<uint16_t>(), w.score.as<float>(), w.lwr.as<double>(), w.oflags.as<uint32_t>()};
-        rc = rk_place_packed_device_translated(db, p, n, w.packed.as<uint32_t>(), dna_words, w.lens.as<uint32_t>(), 0, w.flags.as<uint32_t>(), &dres,
-                                               w.frames.as<uint8_t>(), w.translated.p, wb, s);
-        if (rc) { (void)hipStreamSynchronize(s); return rc; }
-        HIP_TRY(hipMemcpyAsync(out->n_rows + r0, w.nrows.p, n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out->branch + r0 * K, w.branch.p, n * K * 2, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out->score + r0 * K, w.score.p, n * K * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out->lwr + r0 * K, w.lwr.p, n * K * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out->flags + r0, w.oflags.p, n * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(frame_out + r0, w.frames.p, n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));  // (the host vectors are packed again for the next chunk)
-        for (uint64_t r = r0; r < r0 + n; r++) {
-            const uint32_t f = out->flags[r];
-            ct.reads++;
-            if (f & RK_FLAG_PLACED) ct.placed++; else ct.unplaced++;
-            if (f & RK_FLAG_BAD_CHAR) ct.bad_char++;
-            if (f & RK_FLAG_TOO_SHORT) ct.too_short++;
-            if (f & RK_FLAG_AMBIGUOUS) ct.ambiguous++;
-        }
-    }
-    if (counters) *counters = ct;
-    return RK_OK;
-    RK_GUARD_END("rk_place_batch_translated")
 }
 
 #include "rk_synth_impl.h"

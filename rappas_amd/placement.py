@@ -29,6 +29,56 @@ def _strand(strand):
     return int(strand)
 
 
+def _reads(seq, seq_off):
+    """(characters u8, offsets u64 [n + 1], n): the contiguous arrays the C ABI reads"""
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    return np.ascontiguousarray(seq, dtype=np.uint8), seq_off, seq_off.shape[0] - 1
+
+
+def _db_desc(alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets, branch_ids, scores, table_mode, convert_uo, device=0):
+    """(rk_db_desc, the contiguous CSR arrays it points into)"""
+    csr = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((key_codes, np.uint64), (row_offsets, np.uint64), (branch_ids, np.uint16), (scores, np.float32))]
+    return rk_db_desc(alphabet, int(bool(convert_uo)), k, n_branches, float(thr_log10), float(thr), csr[0].shape[0], *map(_ptr, csr), device, table_mode), csr
+
+
+def _host_out(n, K, out):
+    """`out`, or new host arrays for n reads of K rows"""
+    return out if out is not None else Placements(np.zeros(n, np.uint8), np.zeros((n, K), np.uint16), np.zeros((n, K), np.float32),
+                                                  np.zeros((n, K), np.float64), np.zeros(n, np.uint32), {})
+
+
+def _device_out(n, K, dev, out, frame=False):
+    """`out`, or a new dict of device tensors for n reads of K rows; frame: with the "frame" bytes of place_translated"""
+    import torch
+    if out is None:
+        out = {f: torch.empty(shape, dtype=dt, device=dev) for f, shape, dt in (
+            ("n_rows", n, torch.uint8), ("branch", (n, K), torch.int16), ("score", (n, K), torch.float32),
+            ("lwr", (n, K), torch.float64), ("flags", n, torch.int32))}
+    if frame and "frame" not in out:
+        out["frame"] = torch.empty(n, dtype=torch.uint8, device=dev)
+    return out
+
+
+def _result(out):
+    """rk_result over a Placements (host arrays) or over a dict of device tensors"""
+    if isinstance(out, dict):
+        return rk_result(*(out[f].data_ptr() for f in ("n_rows", "branch", "score", "lwr", "flags")))
+    return rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
+
+
+def _stream(dev, stream):
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+
+
+def _dp(t):
+    return None if t is None else t.data_ptr()
+
+
+def _counters(ct):
+    return {f: getattr(ct, f) for f, _ in rk_counters._fields_}
+
+
 @dataclass
 class Placements:
     """Rows best -> worse per read; unused rows are branch 0xFFFF / score -inf / lwr 0."""
@@ -45,9 +95,7 @@ def pack_reads(alphabet, k, seq, seq_off, words_per_read=None, convert_uo=False,
     """rk_pack_reads: the host-side read packer without a database handle (no GPU): ASCII reads -> (packed u32 [n, wpr], lens u32 [n],
     flags u32 [n]), the records the device packer produces (AmbigSequenceKnife.java:103-130 char -> state)."""
     lib = _lib.load()
-    seq = np.ascontiguousarray(seq, dtype=np.uint8)
-    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-    n = seq_off.shape[0] - 1
+    seq, seq_off, n = _reads(seq, seq_off)
     bits = 2 if alphabet == _lib.RK_ALPHABET_DNA else 5
     if words_per_read is None:
         max_len = int((seq_off[1:] - seq_off[:-1]).max()) if n else 0
@@ -131,12 +179,7 @@ def validate_db(alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets,
                 table_mode=RK_TABLE_AUTO, convert_uo=False):
     """rk_db_validate: argument checks + host-side image construction, no device needed. Returns rk_db_info."""
     lib = _lib.load()
-    key_codes = np.ascontiguousarray(key_codes, dtype=np.uint64)
-    row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
-    branch_ids = np.ascontiguousarray(branch_ids, dtype=np.uint16)
-    scores = np.ascontiguousarray(scores, dtype=np.float32)
-    d = rk_db_desc(alphabet, int(bool(convert_uo)), k, n_branches, float(thr_log10), float(thr), key_codes.shape[0],
-                   _ptr(key_codes), _ptr(row_offsets), _ptr(branch_ids), _ptr(scores), 0, table_mode)
+    d, _keep = _db_desc(alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets, branch_ids, scores, table_mode, convert_uo)
     info = rk_db_info()
     _lib.check(lib.rk_db_validate(C.byref(d), C.byref(info)))
     return info
@@ -146,12 +189,7 @@ def save_db_image(path, alphabet, k, n_branches, thr_log10, thr, key_codes, row_
                   convert_uo=False, user=b""):
     """rk_db_save_desc: the image file of a database given as CSR arrays, built on the host (no GPU needed)."""
     lib = _lib.load()
-    key_codes = np.ascontiguousarray(key_codes, dtype=np.uint64)
-    row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
-    branch_ids = np.ascontiguousarray(branch_ids, dtype=np.uint16)
-    scores = np.ascontiguousarray(scores, dtype=np.float32)
-    d = rk_db_desc(alphabet, int(bool(convert_uo)), k, n_branches, float(thr_log10), float(thr), key_codes.shape[0],
-                   _ptr(key_codes), _ptr(row_offsets), _ptr(branch_ids), _ptr(scores), 0, table_mode)
+    d, _keep = _db_desc(alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets, branch_ids, scores, table_mode, convert_uo)
     user = bytes(user)
     _lib.check(lib.rk_db_save_desc(C.byref(d), str(path).encode(), user, len(user)))
 
@@ -173,23 +211,16 @@ class PhyloKmerDB:
                  device=0, table_mode=RK_TABLE_AUTO, convert_uo=False):
         self._lib = _lib.load()
         self._h = C.c_void_p()
-        key_codes = np.ascontiguousarray(key_codes, dtype=np.uint64)
-        row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
-        branch_ids = np.ascontiguousarray(branch_ids, dtype=np.uint16)
-        scores = np.ascontiguousarray(scores, dtype=np.float32)
+        d, (key_codes, row_offsets, branch_ids, scores) = _db_desc(alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets, branch_ids,
+                                                                   scores, table_mode, convert_uo, device)
         if row_offsets.shape[0] != key_codes.shape[0] + 1:
             raise ValueError("row_offsets must have n_keys+1 entries")
         if key_codes.shape[0] and int(row_offsets[-1]) != branch_ids.shape[0]:
             raise ValueError("row_offsets[-1] must equal len(branch_ids)")
         if branch_ids.shape[0] != scores.shape[0]:
             raise ValueError("branch_ids and scores differ in length")
-        d = rk_db_desc(alphabet, int(bool(convert_uo)), k, n_branches, float(thr_log10), float(thr),
-                       key_codes.shape[0], _ptr(key_codes), _ptr(row_offsets), _ptr(branch_ids), _ptr(scores),
-                       device, table_mode)
         _lib.check(self._lib.rk_db_create(C.byref(d), C.byref(self._h)))
-        info = rk_db_info()
-        _lib.check(self._lib.rk_db_get_info(self._h, C.byref(info)))
-        self.info = info
+        self._read_info()
 
     @classmethod
     def synthetic(cls, spec, device=0, table_mode=RK_TABLE_AUTO, convert_uo=False):
@@ -201,10 +232,12 @@ class PhyloKmerDB:
         d = _lib.rk_synth_desc(spec.alphabet, int(bool(convert_uo)), spec.k, spec.n_branches, float(spec.thr_log10), float(spec.thr),
                                int(spec.seed) & 0xFFFFFFFFFFFFFFFF, float(spec.key_fraction), float(spec.mean_row_len), device, table_mode)
         _lib.check(self._lib.rk_db_create_synth(C.byref(d), C.byref(self._h)))
-        info = rk_db_info()
-        _lib.check(self._lib.rk_db_get_info(self._h, C.byref(info)))
-        self.info = info
+        self._read_info()
         return self
+
+    def _read_info(self):
+        self.info = rk_db_info()
+        _lib.check(self._lib.rk_db_get_info(self._h, C.byref(self.info)))
 
     def save(self, path, user=b""):
         """rk_db_save: this handle's HBM image as a file (the reference's SessionNext_v2.storeHash, SessionNext_v2.java:110-154);
@@ -219,9 +252,7 @@ class PhyloKmerDB:
         self._lib = _lib.load()
         self._h = C.c_void_p()
         _lib.check(self._lib.rk_db_load(str(path).encode(), device, C.byref(self._h)))
-        info = rk_db_info()
-        _lib.check(self._lib.rk_db_get_info(self._h, C.byref(info)))
-        self.info = info
+        self._read_info()
         return self
 
     def clone(self, device=0):
@@ -230,9 +261,7 @@ class PhyloKmerDB:
         other._lib = self._lib
         other._h = C.c_void_p()
         _lib.check(self._lib.rk_db_clone(self.handle, device, C.byref(other._h)))
-        info = rk_db_info()
-        _lib.check(self._lib.rk_db_get_info(other._h, C.byref(info)))
-        other.info = info
+        other._read_info()
         return other
 
     def fetch_row(self, code):
@@ -289,6 +318,15 @@ class PlacementProcess:
         amb = RK_AMB_SKIP if not treatAmbiguities else (RK_AMB_MAX if treatAmbiguitiesWithMax else RK_AMB_MEAN)
         return rk_params(keepAtMost, keepFactor, amb, self.ns_bound)
 
+    def _work(self, attr, dev, need):
+        """the device workspace self.<attr>, grow-only (the old block goes back to its stream's allocator in stream order)"""
+        import torch
+        work = getattr(self, attr, None)
+        if work is None or work.device != dev or work.numel() < need:
+            work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+            setattr(self, attr, work)
+        return work
+
     def processQueries(self, seq, seq_off, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
                        treatAmbiguitiesWithMax=False, out=None, strand="forward"):
         """seq: uint8 ASCII of all reads concatenated (no gap stripping, as FASTAPointer(q,false) delivers them);
@@ -296,14 +334,10 @@ class PlacementProcess:
         strand (DNA databases): "forward" = the reads as given (rk_place_batch, the reference's behaviour), "reverse" = their reverse
         complements, "both" = per read the strand with the better best score (rk_place_batch_strands; RK_FLAG_REVERSE marks the
         results that come from the reverse complement)."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        n = seq_off.shape[0] - 1
+        seq, seq_off, n = _reads(seq, seq_off)
         K = keepAtMost
-        if out is None:
-            out = Placements(np.zeros(n, np.uint8), np.zeros((n, K), np.uint16), np.zeros((n, K), np.float32),
-                             np.zeros((n, K), np.float64), np.zeros(n, np.uint32), {})
-        res = rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
+        out = _host_out(n, K, out)
+        res = _result(out)
         p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
         ct = rk_counters()
         st = _strand(strand)
@@ -313,7 +347,7 @@ class PlacementProcess:
         else:
             _lib.check(self._lib.rk_place_batch_strands(self.db.handle, C.byref(p), st, n, _ptr(seq), _ptr(seq_off), C.byref(res),
                                                         C.byref(ct)))
-        out.counters = {f: getattr(ct, f) for f, _ in rk_counters._fields_}
+        out.counters = _counters(ct)
         return out
 
     def processQueriesTranslated(self, seq, seq_off, keepAtMost=7, keepFactor=0.01, out=None):
@@ -321,29 +355,23 @@ class PlacementProcess:
         on the device and placed on the database; per read the frame with the best score is reported.  Returns a Placements with one
         more array, `frame` (u8 [n]: 0..2 forward from base 0, 1, 2; 3..5 the reverse complement; 0xFF = no result).  Reads with an
         ambiguity code or an unsupported character come back unplaced with their flag."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        n = seq_off.shape[0] - 1
+        seq, seq_off, n = _reads(seq, seq_off)
         K = keepAtMost
-        if out is None:
-            out = Placements(np.zeros(n, np.uint8), np.zeros((n, K), np.uint16), np.zeros((n, K), np.float32),
-                             np.zeros((n, K), np.float64), np.zeros(n, np.uint32), {})
+        out = _host_out(n, K, out)
         if getattr(out, "frame", None) is None or out.frame.shape != (n,):
             out.frame = np.full(n, _lib.RK_FRAME_NONE, np.uint8)
-        res = rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
+        res = _result(out)
         p = self._params(keepAtMost, keepFactor, True, False)
         ct = rk_counters()
         _lib.check(self._lib.rk_place_batch_translated(self.db.handle, C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res), _ptr(out.frame),
                                                        C.byref(ct)))
-        out.counters = {f: getattr(ct, f) for f, _ in rk_counters._fields_}
+        out.counters = _counters(ct)
         return out
 
     def pack_reads_host(self, seq, seq_off, max_len=None, threads=0, out=None):
         """rk_pack_reads_host: ASCII reads -> (packed u32 [n, wpr], lens u32 [n], flags u32 [n]) on the host, the records the
         device packer would produce (AmbigSequenceKnife.java:103-130 char -> state).  `out` = (packed, lens, flags) to reuse."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        n = seq_off.shape[0] - 1
+        seq, seq_off, n = _reads(seq, seq_off)
         if max_len is None:
             max_len = int((seq_off[1:] - seq_off[:-1]).max()) if n else 0
         wpr = self.db.packed_words(max_len)
@@ -364,10 +392,8 @@ class PlacementProcess:
         packed = np.ascontiguousarray(packed, dtype=np.uint32)
         n, wpr = packed.shape
         K = keepAtMost
-        if out is None:
-            out = Placements(np.zeros(n, np.uint8), np.zeros((n, K), np.uint16), np.zeros((n, K), np.float32),
-                             np.zeros((n, K), np.float64), np.zeros(n, np.uint32), {})
-        res = rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
+        out = _host_out(n, K, out)
+        res = _result(out)
         p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
         ct = rk_counters()
         keep = [np.ascontiguousarray(a, dtype=dt) if a is not None else None
@@ -375,27 +401,23 @@ class PlacementProcess:
         ptrs = [None if a is None else _ptr(a) for a in keep]
         _lib.check(self._lib.rk_place_batch_packed(self.db.handle, C.byref(p), n, _ptr(packed), wpr, ptrs[0], fixed_len, ptrs[1],
                                                    ptrs[2], ptrs[3], C.byref(res), C.byref(ct)))
-        out.counters = {f: getattr(ct, f) for f, _ in rk_counters._fields_}
+        out.counters = _counters(ct)
         return out
 
     def processQueriesMulti(self, dbs, seq, seq_off, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
                             treatAmbiguitiesWithMax=False, out=None):
         """processQueries over several device handles of the same database from this one process
         (rk_place_batch_multi: contiguous shards, one host thread per handle, no collective)."""
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        n = seq_off.shape[0] - 1
+        seq, seq_off, n = _reads(seq, seq_off)
         K = keepAtMost
-        if out is None:
-            out = Placements(np.zeros(n, np.uint8), np.zeros((n, K), np.uint16), np.zeros((n, K), np.float32),
-                             np.zeros((n, K), np.float64), np.zeros(n, np.uint32), {})
-        res = rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
+        out = _host_out(n, K, out)
+        res = _result(out)
         p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
         ct = rk_counters()
         handles = (C.c_void_p * len(dbs))(*[d.handle for d in dbs])
         _lib.check(self._lib.rk_place_batch_multi(handles, len(dbs), C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res),
                                                   C.byref(ct)))
-        out.counters = {f: getattr(ct, f) for f, _ in rk_counters._fields_}
+        out.counters = _counters(ct)
         return out
 
     # ---- device-resident variant (torch tensors only carry the memory and the stream) ----
@@ -404,37 +426,26 @@ class PlacementProcess:
                      stream=None, strand="forward"):
         """rk_place_packed_device; with strand "reverse" / "both" rk_place_packed_device_strands, whose device workspace (the
         reverse records, a second result set, the reversed characters) is a tensor this object owns and grows as batches ask."""
-        import torch
         n, wpr = packed.shape
         dev = packed.device
         K = keepAtMost
-        if out is None:
-            out = dict(n_rows=torch.empty(n, dtype=torch.uint8, device=dev),
-                       branch=torch.empty((n, K), dtype=torch.int16, device=dev),
-                       score=torch.empty((n, K), dtype=torch.float32, device=dev),
-                       lwr=torch.empty((n, K), dtype=torch.float64, device=dev),
-                       flags=torch.empty(n, dtype=torch.int32, device=dev))
-        res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), out["score"].data_ptr(),
-                        out["lwr"].data_ptr(), out["flags"].data_ptr())
+        out = _device_out(n, K, dev, out)
+        res = _result(out)
         p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        dp = lambda t: None if t is None else t.data_ptr()
+        st = _stream(dev, stream)
         sd = _strand(strand)
         if sd == _lib.RK_STRAND_FORWARD:
-            _lib.check(self._lib.rk_place_packed_device(self.db.handle, C.byref(p), n, packed.data_ptr(), wpr, dp(lens),
-                                                        fixed_len, dp(flags_in), dp(seq_ascii), dp(seq_off),
+            _lib.check(self._lib.rk_place_packed_device(self.db.handle, C.byref(p), n, packed.data_ptr(), wpr, _dp(lens),
+                                                        fixed_len, _dp(flags_in), _dp(seq_ascii), _dp(seq_off),
                                                         C.byref(res), C.c_void_p(st)))
             return out
         chars = seq_ascii is not None and seq_off is not None and flags_in is not None
         need = int(self._lib.rk_strands_work_bytes(self.db.handle, n, wpr, K, max(1, seq_ascii.numel()) if chars else 0))
         if n and not need:
             _lib.check(_lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_DNA else _lib.RK_ERR_UNSUPPORTED)
-        work = getattr(self, "_strand_work", None)
-        if work is None or work.device != dev or work.numel() < need:
-            # (grow-only; the old block goes back to the allocator of the stream it was used on, in stream order)
-            work = self._strand_work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _lib.check(self._lib.rk_place_packed_device_strands(self.db.handle, C.byref(p), sd, n, packed.data_ptr(), wpr, dp(lens),
-                                                            fixed_len, dp(flags_in), dp(seq_ascii), dp(seq_off),
+        work = self._work("_strand_work", dev, need)
+        _lib.check(self._lib.rk_place_packed_device_strands(self.db.handle, C.byref(p), sd, n, packed.data_ptr(), wpr, _dp(lens),
+                                                            fixed_len, _dp(flags_in), _dp(seq_ascii), _dp(seq_off),
                                                             C.byref(res), work.data_ptr(), work.numel(), C.c_void_p(st)))
         return out
 
@@ -443,32 +454,19 @@ class PlacementProcess:
         device, as rk_pack_reads(RK_ALPHABET_DNA) writes them) placed in their six reading frames; `out` gains "frame" (uint8 [n]).
         The device workspace (one frame's amino-acid records and lengths, a second result set) is a tensor this object owns and
         grows as batches ask."""
-        import torch
         n, wpr = dna.shape
         dev = dna.device
         K = keepAtMost
-        if out is None:
-            out = dict(n_rows=torch.empty(n, dtype=torch.uint8, device=dev),
-                       branch=torch.empty((n, K), dtype=torch.int16, device=dev),
-                       score=torch.empty((n, K), dtype=torch.float32, device=dev),
-                       lwr=torch.empty((n, K), dtype=torch.float64, device=dev),
-                       flags=torch.empty(n, dtype=torch.int32, device=dev))
-        if "frame" not in out:
-            out["frame"] = torch.empty(n, dtype=torch.uint8, device=dev)
-        res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), out["score"].data_ptr(),
-                        out["lwr"].data_ptr(), out["flags"].data_ptr())
+        out = _device_out(n, K, dev, out, frame=True)
+        res = _result(out)
         p = self._params(keepAtMost, keepFactor, True, False)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        dp = lambda t: None if t is None else t.data_ptr()
+        st = _stream(dev, stream)
         need = int(self._lib.rk_translated_work_bytes(self.db.handle, n, wpr, K))
         if n and not need:
             _lib.check(_lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_AA else _lib.RK_ERR_UNSUPPORTED)
-        work = getattr(self, "_translated_work", None)
-        if work is None or work.device != dev or work.numel() < need:
-            # (grow-only; the old block goes back to the allocator of the stream it was used on, in stream order)
-            work = self._translated_work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        _lib.check(self._lib.rk_place_packed_device_translated(self.db.handle, C.byref(p), n, dna.data_ptr(), wpr, dp(lens), fixed_len,
-                                                               dp(flags_in), C.byref(res), out["frame"].data_ptr(), work.data_ptr(),
+        work = self._work("_translated_work", dev, need)
+        _lib.check(self._lib.rk_place_packed_device_translated(self.db.handle, C.byref(p), n, dna.data_ptr(), wpr, _dp(lens), fixed_len,
+                                                               _dp(flags_in), C.byref(res), out["frame"].data_ptr(), work.data_ptr(),
                                                                work.numel(), C.c_void_p(st)))
         return out
 
@@ -481,7 +479,7 @@ class PlacementProcess:
         n, K = out["branch"].shape
         dev = out["branch"].device
         words = masses_words(self.db.info.n_branches)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        st = _stream(dev, stream)
         if masses is None:
             masses = torch.empty(words, dtype=torch.int64, device=dev)
             if stream is not None:
@@ -507,8 +505,8 @@ class PlacementProcess:
             aa_words = translated_words(wpr * 16 if lens is not None else fixed_len)
         aa = torch.empty((n, aa_words), dtype=torch.int32, device=dna.device)
         aa_lens = torch.empty(n, dtype=torch.int32, device=dna.device)
-        st = stream if stream is not None else torch.cuda.current_stream(dna.device).cuda_stream
-        _lib.check(self._lib.rk_translate_packed_device(self.db.handle, frame, n, dna.data_ptr(), wpr, None if lens is None else lens.data_ptr(),
+        st = _stream(dna.device, stream)
+        _lib.check(self._lib.rk_translate_packed_device(self.db.handle, frame, n, dna.data_ptr(), wpr, _dp(lens),
                                                         fixed_len, aa.data_ptr(), aa_words, aa_lens.data_ptr(), C.c_void_p(st)))
         return aa, aa_lens
 
@@ -518,8 +516,8 @@ class PlacementProcess:
         import torch
         n, wpr = packed.shape
         out = torch.empty_like(packed)
-        st = stream if stream is not None else torch.cuda.current_stream(packed.device).cuda_stream
-        _lib.check(self._lib.rk_revcomp_packed_device(self.db.handle, n, packed.data_ptr(), wpr, None if lens is None else lens.data_ptr(),
+        st = _stream(packed.device, stream)
+        _lib.check(self._lib.rk_revcomp_packed_device(self.db.handle, n, packed.data_ptr(), wpr, _dp(lens),
                                                       fixed_len, out.data_ptr(), C.c_void_p(st)))
         return out
 
@@ -527,7 +525,7 @@ class PlacementProcess:
         """rk_revcomp_ascii_device: every read's characters reversed and complemented (hostio.revcomp is the numpy twin), same offsets."""
         import torch
         out = torch.empty_like(seq_ascii)
-        st = stream if stream is not None else torch.cuda.current_stream(seq_ascii.device).cuda_stream
+        st = _stream(seq_ascii.device, stream)
         _lib.check(self._lib.rk_revcomp_ascii_device(self.db.handle, seq_off.shape[0] - 1, seq_ascii.data_ptr(), seq_off.data_ptr(),
                                                      out.data_ptr(), C.c_void_p(st)))
         return out
@@ -539,9 +537,8 @@ class PlacementProcess:
         n, wpr = packed.shape
         dev = packed.device
         out = torch.empty(3, dtype=torch.int64, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        dp = lambda t: None if t is None else t.data_ptr()
-        _lib.check(self._lib.rk_count_work_device(self.db.handle, n, packed.data_ptr(), wpr, dp(lens), fixed_len, dp(flags_in), out.data_ptr(), C.c_void_p(st)))
+        st = _stream(dev, stream)
+        _lib.check(self._lib.rk_count_work_device(self.db.handle, n, packed.data_ptr(), wpr, _dp(lens), fixed_len, _dp(flags_in), out.data_ptr(), C.c_void_p(st)))
         if stream is not None:
             torch.cuda.synchronize(dev)
         probed, hit, entries = (int(x) for x in out.tolist())
@@ -555,7 +552,7 @@ class PlacementProcess:
         packed = torch.empty((n, wpr), dtype=torch.int32, device=dev)
         lens = torch.empty(n, dtype=torch.int32, device=dev)
         flags = torch.empty(n, dtype=torch.int32, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        st = _stream(dev, stream)
         _lib.check(self._lib.rk_pack_reads_device(self.db.handle, n, seq_ascii.data_ptr(), seq_off.data_ptr(), wpr,
                                                   packed.data_ptr(), lens.data_ptr(), flags.data_ptr(),
                                                   C.c_void_p(st)))

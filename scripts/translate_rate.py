@@ -3,7 +3,8 @@ database: in one process, after bench.py's warm-up, with HIP events around every
   (a) the translated six-frame call,
   (b) six plain rk_place_packed_device calls over the same six record sets translated beforehand (the existing entry point),
   (c) the translate kernel alone, all six frames,
-  (d) the merge kernel alone, the five merges of a call.
+  (d) the merge kernel alone, the five merges of a call,
+  (e) rk_place_batch_translated over the same reads as characters in pageable host memory (wall clock, not events).
 (a) - (b) is what the new kernels add; it should be explained by (c) + (d).  Reads are uniform random DNA, generated on the device
 into the 2-bit packed layout (seed 1).
 
@@ -14,8 +15,10 @@ import ctypes as C
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
 import torch
 
 import rappas_amd as ra
@@ -112,4 +115,22 @@ def five_merges():
 
 t_d = line("(d) merge_results_kernel alone, five merges (later calls tie)", timed(five_merges))
 print(f"(a) - (b) = {t_a - t_b:.3f} ms per {n} reads; (c) + (d) = {t_c + t_d:.3f} ms; (a) / (b) = {t_a / t_b:.3f}")
+# (e) the host entry point over the same reads as characters in pageable memory: wall clock, the host's packing and PCIe included
+idx = np.arange(rlen)
+seq = np.ascontiguousarray(synth.DNA_LETTERS[(dna.cpu().numpy().view(np.uint32)[:, idx // 16] >> (2 * (idx % 16)).astype(np.uint32)) & 3]).reshape(-1)
+off = np.arange(n + 1, dtype=np.uint64) * rlen
+host_out = None
+
+
+def host_call():
+    global host_out
+    t0 = time.perf_counter()
+    host_out = pp.processQueriesTranslated(seq, off, keepAtMost=K, out=host_out)
+    return (time.perf_counter() - t0) * 1e3
+
+
+for _ in range(1 + a.warmup):
+    host_call()
+line("(e) rk_place_batch_translated, characters from the host", [host_call() for _ in range(a.steps)])
+assert np.array_equal(host_out.frame, out["frame"].cpu().numpy()) and np.array_equal(host_out.n_rows, out["n_rows"].cpu().numpy())
 db.close()

@@ -169,6 +169,44 @@ def test_six_frames_equal_the_oracle_on_every_frame_merged(k, monkeypatch, dev_l
         db.close()
 
 
+def test_host_path_over_five_chunks_equals_the_device_call_and_a_fresh_handle(monkeypatch, dev_lib):
+    """rk_place_batch_translated through the chunk pipeline: 5 000 ragged DNA reads (0..200 bases, ambiguity codes, unsupported
+    characters) in chunks of 1 024 -- five chunks over four workspaces, so the fifth reuses the first -- from pageable arrays and
+    from page-locked ones (characters and results both).  Results, frame bytes and counters are bit-equal to
+    rk_place_packed_device_translated on rk_pack_reads records of the whole batch (one record width for all reads, where the host
+    path's is per chunk) and to the same host call on a fresh handle."""
+    import torch
+    sdb, _, _ = planted_case(3)
+    n, K = 5000, 7
+    seq, off = synth.make_reads(4, n, 200, amb_rate=0.01, bad_rate=0.01, var_len=200)
+    monkeypatch.setenv("RK_CHUNK_READS", "1024")
+    db, fresh = ra.PhyloKmerDB.from_synth(sdb), ra.PhyloKmerDB.from_synth(sdb)
+    try:
+        packed, lens, flags = ra.pack_reads(4, 1, seq, off)
+        want = to_host(ra.PlacementProcess(db).place_translated(
+            torch.from_numpy(packed.view(np.int32)).cuda(), lens=torch.from_numpy(lens.view(np.int32)).cuda(),
+            flags_in=torch.from_numpy(flags.view(np.int32)).cuda(), keepAtMost=K))
+        fl = want.flags
+        counters = dict(reads=n, placed=int((fl & 1 != 0).sum()), unplaced=int((fl & 1 == 0).sum()), bad_char=int((fl & 2 != 0).sum()),
+                        too_short=int((fl & 4 != 0).sum()), ambiguous=int((fl & 8 != 0).sum()))
+        assert counters["placed"] > 0 and counters["bad_char"] > 0 and counters["ambiguous"] > 0 and counters["too_short"] > 0
+        h_seq, h_off = ra.host_alloc(seq.shape, np.uint8), ra.host_alloc(off.shape, np.uint64)
+        h_seq[:], h_off[:] = seq, off
+
+        def locked_out():
+            return ra.Placements(ra.host_alloc(n, np.uint8), ra.host_alloc((n, K), np.uint16), ra.host_alloc((n, K), np.float32),
+                                 ra.host_alloc((n, K), np.float64), ra.host_alloc(n, np.uint32), {}, ra.host_alloc(n, np.uint8))
+
+        for handle in (db, fresh):
+            pp = ra.PlacementProcess(handle)
+            for got in (pp.processQueriesTranslated(seq, off, keepAtMost=K), pp.processQueriesTranslated(h_seq, h_off, keepAtMost=K, out=locked_out())):
+                same_arrays(got, want)
+                assert got.counters == counters
+    finally:
+        db.close()
+        fresh.close()
+
+
 def test_a_bound_gates_every_frame_on_its_own():
     k = 3
     sdb, reads, planted = planted_case(k)
