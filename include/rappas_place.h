@@ -398,6 +398,35 @@ int rk_masses_accumulate_device(rk_db *db, uint32_t keep_at_most, uint64_t n_rea
 int rk_masses_accumulate_host(uint32_t n_branches, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, const uint32_t *weights,
                               uint64_t *masses, uint32_t n_threads);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Profile-only placement: reads from the host in, a mass buffer out, no result set on the host.  Each chunk of the host path is
+ * placed as by the corresponding entry point and summed where its results lie (rk_masses_accumulate_device on the chunk's stream,
+ * into a buffer of the handle's); of a chunk's results only the flags (4 bytes a read) come back.
+ *   rk_place_batch_masses         characters; `step` is RK_STRAND_FORWARD / _REVERSE / _BOTH or RK_STEP_TRANSLATED (six reading frames of
+ *                                 DNA characters on an amino-acid handle).
+ *   rk_place_batch_packed_masses  the arguments of rk_place_batch_packed (forward).
+ * Contract.  Let R be the result set that the corresponding existing entry point -- rk_place_batch, rk_place_batch_strands,
+ * rk_place_batch_translated or rk_place_batch_packed -- returns for the same arguments.  After the call `masses` (host memory,
+ * rk_masses_words(B) words) holds its previous content plus exactly what rk_masses_accumulate_host(B, p->keep_at_most, n_reads, R,
+ * weights, masses, ...) would add; flags_out (optional, [n_reads]) equals R.flags; counters (optional) equal that call's counters.
+ * weights is NULL or [n_reads].  The frame bytes of the translated step do not come back.  The result does not depend on how the
+ * batch is cut into chunks.  Exactness as for the other masses calls: while the sum of the weights stays below 2^33.
+ * The handle keeps one device mass buffer of rk_masses_words(B) * 8 bytes (at most 1 MB), allocated at the first such call (or by
+ * rk_reserve_host_path) and freed by rk_db_destroy; it is zeroed at the start of a call, the chunks' streams add into it side by side
+ * and one copy brings it to the host at the end.  Calls on one handle are serialised, as all host calls are.
+ * Errors.  RK_ERR_INVALID (and a message) for a NULL handle or masses, NULL reads with n_reads > 0, keep_at_most outside 1..16 and
+ * step > 3; RK_ERR_UNSUPPORTED for a strand step other than forward on an amino-acid handle and for the translated step on a DNA
+ * handle: then nothing is launched and no byte of masses or flags_out is written.  An error later in the call leaves masses as it
+ * was.  n_reads == 0 is RK_OK and touches neither.  Added without a bump of RK_VERSION (no struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_STEP_TRANSLATED 3u /* `step` beside RK_STRAND_FORWARD/REVERSE/BOTH: six reading frames, amino-acid handles only */
+int rk_place_batch_masses(rk_db *db, const rk_params *p, uint32_t step, uint64_t n_reads, const uint8_t *seq_ascii,
+                          const uint64_t *seq_off, const uint32_t *weights, uint64_t *masses, uint32_t *flags_out, rk_counters *counters);
+int rk_place_batch_packed_masses(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *packed, uint32_t words_per_read,
+                                 const uint32_t *lens, uint32_t fixed_len, const uint32_t *flags, const uint8_t *seq_ascii,
+                                 const uint64_t *seq_off, const uint32_t *weights, uint64_t *masses, uint32_t *flags_out,
+                                 rk_counters *counters);
+
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the
  * packed kernels place (not BAD_CHAR / TOO_LONG / AMBIGUOUS, at least k symbols); kmers_hit = those with a row in the database

@@ -6,7 +6,7 @@ rappas_amd/csrc/).  This package is the thin host-side mirror used by tests and 
 from . import _lib, build, synth  # noqa: F401
 from ._lib import (RK_ALPHABET_AA, RK_ALPHABET_DNA, RK_AMB_MAX, RK_AMB_MEAN, RK_AMB_SKIP, RK_FLAG_AMBIGUOUS,  # noqa: F401
                    RK_FLAG_BAD_CHAR, RK_FLAG_BELOW_NSBOUND, RK_FLAG_PLACED, RK_FLAG_REVERSE, RK_FLAG_TOO_LONG, RK_FLAG_TOO_SHORT, RK_FRAME_NONE,
-                   RK_STRAND_BOTH, RK_STRAND_FORWARD, RK_STRAND_REVERSE,
+                   RK_STEP_TRANSLATED, RK_STRAND_BOTH, RK_STRAND_FORWARD, RK_STRAND_REVERSE,
                    RK_TABLE_AUTO, RK_TABLE_DIRECT, RK_TABLE_DIRECT8, RK_TABLE_HASH, RkError)
 from .placement import (PhyloKmerDB, PlacementProcess, Placements, accumulate_masses_host, db_image_info, host_alloc, masses_words,  # noqa: F401
                         pack_reads, save_db_image, translate_packed_host, translated_words, validate_db)

@@ -13,6 +13,7 @@ RK_FLAG_PLACED, RK_FLAG_BAD_CHAR, RK_FLAG_TOO_SHORT, RK_FLAG_AMBIGUOUS, RK_FLAG_
 RK_FLAG_REVERSE = 32
 RK_FRAME_NONE = 0xFF  # d_frame of a read without a result (rk_place_*_translated)
 RK_STRAND_FORWARD, RK_STRAND_REVERSE, RK_STRAND_BOTH = 0, 1, 2
+RK_STEP_TRANSLATED = 3  # `step` of rk_place_batch_masses beside the three strands
 STRANDS = {"forward": RK_STRAND_FORWARD, "fwd": RK_STRAND_FORWARD, "reverse": RK_STRAND_REVERSE, "rev": RK_STRAND_REVERSE, "both": RK_STRAND_BOTH}
 RK_OK, RK_ERR_INVALID, RK_ERR_NO_DEVICE, RK_ERR_HIP, RK_ERR_NOMEM, RK_ERR_UNSUPPORTED, RK_ERR_IO = 0, -1, -2, -3, -4, -5, -6
 
@@ -129,6 +130,10 @@ EXPORTS = {
     "rk_masses_words": (C.c_uint64, [C.c_uint32]),
     "rk_masses_accumulate_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_masses_accumulate_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rk_place_batch_masses": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(rk_counters)]),
+    "rk_place_batch_packed_masses": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rk_counters)]),
     "rk_count_work_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_set_lanes_per_read": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rk_kernel_name": (C.c_char_p, [C.c_void_p]),

@@ -31,6 +31,10 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                 strand per read; rev / both also write logs/reversed_<query>.tsv)\n"
                  "                [--masses FILE]  (the per-edge table of the run: one line per tree node with the reads whose best placement is its\n"
                  "                 edge and the likelihood weight on it, and the same summed over its clade; a read counts once per FASTA record)\n"
+                 "                [--masses-only FILE]  (profile-only run: that table to FILE and nothing else but the notplaced and, with --strand\n"
+                 "                 rev | both, the reversed log; the placements are summed on the device and never reach the host, so no jplace is\n"
+                 "                 written and --out may not be given; with --translate the frames log is not written, as the frame bytes do not come\n"
+                 "                 back; not with --masses; --timing prints one JSON line with keys of its own, fasta_to_masses_s among them)\n"
                  "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
                  "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
                  "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
@@ -42,7 +46,7 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7;
@@ -70,6 +74,7 @@ int main(int argc, char **argv) {
             else if (a == "--strand") strand_name = val();
             else if (a == "--translate") translate = true;
             else if (a == "--masses") masses_path = val();
+            else if (a == "--masses-only") masses_only_path = val();
             else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
             else if (a == "--guppy-compat") guppy = true;
@@ -261,8 +266,17 @@ int main(int argc, char **argv) {
             } else return usage();
         }
         const int n_sources = (jsondb.empty() ? 0 : 1) + (uniondb.empty() ? 0 : 1) + (dbimage.empty() ? 0 : 1);
-        const bool only_convert = !save_image.empty() && fasta.empty() && out.empty();
-        if (n_sources != 1 || (!only_convert && (fasta.empty() || out.empty())) || (only_convert && !dbimage.empty())) return usage();
+        const bool masses_only = !masses_only_path.empty();
+        if (masses_only && !masses_path.empty()) {
+            std::cerr << "rk_place: --masses-only writes the table --masses writes, without placing into a jplace: give one of the two\n";
+            return 2;
+        }
+        if (masses_only && !out.empty()) {
+            std::cerr << "rk_place: --masses-only writes no jplace (the placements never reach the host): it cannot be combined with --out\n";
+            return 2;
+        }
+        const bool only_convert = !save_image.empty() && fasta.empty() && out.empty() && !masses_only;
+        if (n_sources != 1 || (!only_convert && (fasta.empty() || (out.empty() && !masses_only))) || (only_convert && !dbimage.empty())) return usage();
         uint32_t amb_mode;
         if (amb == "mean") amb_mode = RK_AMB_MEAN; else if (amb == "max") amb_mode = RK_AMB_MAX; else if (amb == "skip") amb_mode = RK_AMB_SKIP;
         else return usage();
@@ -293,6 +307,18 @@ int main(int argc, char **argv) {
                 throw std::runtime_error(std::string("rk_masses_accumulate_host: ") + rk_last_error());
             std::ofstream mf(masses_path, std::ios::binary);
             if (!mf) throw std::runtime_error("cannot write " + masses_path);
+            mf << rkh::masses_table(t, words.data(), words.size());
+        };
+        // --masses-only: one profile-only call with the multiplicities as weights -- every chunk is summed on the device, the flags
+        // alone come back -- then the table through the same writer
+        auto place_masses_only = [&](rk_db *h, const rk_params *pp, const rkh::Tree &t, uint64_t m, const uint8_t *sq, const uint64_t *so, const uint32_t *w,
+                                     uint32_t *flags_out, rk_counters *c) {
+            std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);
+            if (words.empty()) throw std::runtime_error("--masses-only: the tree has no nodes, or more than 65535");
+            if (rk_place_batch_masses(h, pp, translate ? RK_STEP_TRANSLATED : strand, m, sq, so, w, words.data(), flags_out, c) != RK_OK)
+                throw std::runtime_error(std::string("rk_place_batch_masses: ") + rk_last_error());
+            std::ofstream mf(masses_only_path, std::ios::binary);
+            if (!mf) throw std::runtime_error("cannot write " + masses_only_path);
             mf << rkh::masses_table(t, words.data(), words.size());
         };
         auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -349,7 +375,7 @@ int main(int argc, char **argv) {
         const uint32_t K = keep_at_most;
         rk_params p{K, keep_factor, amb_mode, nsbound};
         namespace fs = std::filesystem;
-        const fs::path log_dir = logs_given ? fs::path(logs) : fs::absolute(fs::path(out)).parent_path() / "logs";
+        const fs::path log_dir = logs_given ? fs::path(logs) : fs::absolute(fs::path(out.empty() ? masses_only_path : out)).parent_path() / "logs";
         const std::string notplaced_name = "notplaced_" + fs::path(fasta).filename().string() + ".tsv";
         const std::string reversed_name = "reversed_" + fs::path(fasta).filename().string() + ".tsv";  // (--strand rev | both only)
         const std::string frames_name = "frames_" + fs::path(fasta).filename().string() + ".tsv";      // (--translate only)
@@ -374,6 +400,52 @@ int main(int argc, char **argv) {
             rkh::RawArray<uint64_t> off;
             rkh::gather_unique(sc, dd, team, seq, off);
             const size_t n = dd.first_rec.size();
+            auto count_weights = [&](rkh::RawArray<uint32_t> &weight) {  // a unique read weighs the FASTA records it stands for
+                weight.alloc(n);
+                team.run([&](unsigned t, unsigned T) {
+                    for (size_t u = n * t / T; u < n * (t + 1) / T; u++) {
+                        uint32_t c = 0;
+                        for (uint32_t rec = dd.first_rec[u]; rec != 0xFFFFFFFFu; rec = dd.next_dup[rec]) c++;
+                        weight[u] = c;
+                    }
+                });
+            };
+            if (masses_only) {
+                rkh::RawArray<uint32_t> weight, flags;
+                count_weights(weight);
+                flags.alloc(n);
+                team.run([&](unsigned t, unsigned T) { memset(flags.data() + n * t / T, 0, (n * (t + 1) / T - n * t / T) * 4); });
+                const double t3 = now();
+                warm.join();
+                const double t3b = now();
+                rk_counters ct{};
+                place_masses_only(db, &p, tree, n, (const uint8_t *)seq.data(), off.data(), weight.data(), flags.data(), &ct);
+                const double t4 = now();
+                fs::create_directories(log_dir);
+                {
+                    std::ofstream nf(log_dir / notplaced_name, std::ios::binary);
+                    if (!nf) throw std::runtime_error("cannot write the notplaced log under " + log_dir.string());
+                    nf << rkh::notplaced_log_fast(sc, dd, flags.data());
+                }
+                if (strand != RK_STRAND_FORWARD) {
+                    std::ofstream rf(log_dir / reversed_name, std::ios::binary);
+                    if (!rf) throw std::runtime_error("cannot write the reversed log under " + log_dir.string());
+                    rf << rkh::flagged_log_fast(sc, dd, flags.data(), RK_FLAG_REVERSE, RK_FLAG_REVERSE);
+                }
+                const double t5 = now();
+                std::cerr << n << " unique reads, " << ct.placed << " placed -> " << masses_only_path << "\n";
+                if (timing) {
+                    char buf[600];
+                    snprintf(buf, sizeof(buf),
+                             "{\"mode\": \"masses_only\", \"reads\": %zu, \"unique\": %zu, \"placed\": %llu, \"fasta_bytes\": %zu, \"threads\": %u, \"db_s\": %.6f, "
+                             "\"engine_warm_up_s\": %.6f, \"scan_s\": %.6f, \"dedup_s\": %.6f, \"gather_s\": %.6f, \"place_and_sum_s\": %.6f, "
+                             "\"place_wait_for_warm_up_s\": %.6f, \"logs_s\": %.6f, \"fasta_to_masses_s\": %.6f}",
+                             sc.recs.size(), n, (unsigned long long)ct.placed, fa.size, team.size(), t_db - t_start, warm_s, t1 - t0, t2 - t1, t3 - t2, t4 - t3,
+                             t3b - t3, t5 - t4, t5 - t0);
+                    std::cout << buf << std::endl;
+                }
+                return 0;
+            }
             rkh::RawArray<uint8_t> n_rows;
             rkh::RawArray<uint16_t> branch;
             rkh::RawArray<float> score;
@@ -412,14 +484,7 @@ int main(int argc, char **argv) {
             }
             if (!masses_path.empty()) {
                 rkh::RawArray<uint32_t> weight;
-                weight.alloc(n);
-                team.run([&](unsigned t, unsigned T) {
-                    for (size_t u = n * t / T; u < n * (t + 1) / T; u++) {
-                        uint32_t c = 0;
-                        for (uint32_t rec = dd.first_rec[u]; rec != 0xFFFFFFFFu; rec = dd.next_dup[rec]) c++;
-                        weight[u] = c;
-                    }
-                });
+                count_weights(weight);
                 write_masses(tree, n, &res, weight.data(), team.size());
             }
             const double t6 = now();
@@ -448,6 +513,24 @@ int main(int argc, char **argv) {
         for (size_t i = 0; i < n; i++) off[i + 1] = off[i] + records[dd.first_rec[i]].seq.size();
         seq.reserve(off[n]);
         for (size_t i = 0; i < n; i++) seq += records[dd.first_rec[i]].seq;
+        if (masses_only) {
+            std::vector<uint32_t> weight(n), flags(n, 0);
+            for (size_t i = 0; i < n; i++) weight[i] = (uint32_t)names[i].size();
+            rk_counters ct{};
+            place_masses_only(db, &p, tree, n, (const uint8_t *)seq.data(), off.data(), weight.data(), flags.data(), &ct);
+            fs::create_directories(log_dir);
+            std::ofstream nf(log_dir / notplaced_name, std::ios::binary);
+            if (!nf) throw std::runtime_error("cannot write the notplaced log under " + log_dir.string());
+            nf << rkh::notplaced_log(records, dd, flags.data());
+            if (strand != RK_STRAND_FORWARD) {
+                std::ofstream rf(log_dir / reversed_name, std::ios::binary);
+                if (!rf) throw std::runtime_error("cannot write the reversed log under " + log_dir.string());
+                rf << rkh::flagged_log(records, dd, flags.data(), RK_FLAG_REVERSE, RK_FLAG_REVERSE);
+            }
+            std::cerr << n << " unique reads, " << ct.placed << " placed -> " << masses_only_path << "\n";
+            if (timing) std::cout << "{\"mode\": \"masses_only\", \"reads\": " << records.size() << ", \"unique\": " << n << ", \"db_s\": " << (t_db - t_start) << ", \"fasta_to_masses_s\": " << (now() - tc0) << ", \"classic\": true}" << std::endl;
+            return 0;
+        }
         std::vector<uint8_t> n_rows(n);
         std::vector<uint16_t> branch(n * K);
         std::vector<float> score(n * K);

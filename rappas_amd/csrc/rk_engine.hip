@@ -323,6 +323,8 @@ struct rk_db {
     hipStream_t stream = nullptr;      // spare stream
     std::mutex host_mutex;             // rk_place_batch (host path) owns the workspaces below
     rk_workspace ws[4];                // device buffers + stream per in-flight chunk (grow-only)
+    GrowBuf d_masses;                  // the masses sink of the host path: 2 * B + 4 words the four streams add into,
+    PinBuf h_masses;                   // and where they arrive on the host (allocated at the first profile-only call)
     std::string kernel_name;
     // Scratch of the launches themselves (the tile order's keys / histogram / permutation, the marks of the tiles one kernel hands to
     // the next): one grow-only block per stream a caller has launched on, owned by the handle -- the library allocates from no pool
@@ -361,6 +363,8 @@ extern "C" void rk_db_destroy(rk_db *db) {
     if (db->d_winspec) (void)hipFree(db->d_winspec);
     if (db->stream) (void)hipStreamDestroy(db->stream);
     for (rk_workspace &w : db->ws) w.release();
+    db->d_masses.release();
+    db->h_masses.release();
     for (rk_db::LaunchScratch &b : db->scratch)
         if (b.p) (void)hipFree(b.p);
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -1876,26 +1880,29 @@ static int masses_args(const char *who, uint32_t K, uint64_t n_reads, const rk_r
     return RK_OK;
 }
 
-// masses_kernel: LDS bins for small trees, global atomics for large ones
+// masses_kernel: LDS bins for small trees; for large ones global atomics behind a per-block LDS cache of the busiest bins
 static int launch_masses(rk_db *db, uint32_t K, uint64_t n_reads, const rk_result *res, const uint32_t *weights, uint64_t *masses, hipStream_t s) {
     const uint32_t B = db->info.n_branches;
     const uint64_t tiles = (n_reads + 255) / 256;  // a block's four waves take 64 reads each per step
     bool lds = B <= RK_MASSES_LDS_MAX_BRANCHES, combine = RK_MASSES_COMBINE;
+    bool cache = !lds;
     uint32_t per_cu = RK_MASSES_LDS_BLOCKS_PER_CU;
-    if (const char *v = rk_knob("RK_MASSES_VARIANT")) {  // developer builds: "lds" | "global", "+combine" behind either (scripts/masses_rate.py)
-        if (strstr(v, "global")) lds = false;
-        if (strstr(v, "lds") && B <= RK_MASSES_LDS_MAX_BRANCHES) lds = true;
-        combine = strstr(v, "combine") != nullptr;
+    if (const char *v = rk_knob("RK_MASSES_VARIANT")) {  // developer builds: "lds" | "global" | "cache", "+combine" behind lds or global (scripts/masses_rate.py)
+        if (strstr(v, "global")) lds = false, cache = false;
+        if (strstr(v, "cache")) lds = false, cache = true;
+        if (strstr(v, "lds") && B <= RK_MASSES_LDS_MAX_BRANCHES) lds = true, cache = false;
+        combine = strstr(v, "combine") != nullptr && !cache;
     }
     if (const char *v = rk_knob("RK_MASSES_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(v));
     const unsigned blocks = lds ? (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)db->cu_count * per_cu)) : strand_blocks(db, n_reads);
-    const size_t lds_bytes = lds ? (size_t)(2 * B + 4) * 8 : 4 * 8;
+    const size_t lds_bytes = lds ? (size_t)(2 * B + 4) * 8 : cache ? (size_t)(2 * MASS_CACHE_SLOTS + 4) * 8 + (size_t)MASS_CACHE_SLOTS * 4 : 4 * 8;
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds_bytes, s, (u64)n_reads, K, B, (const unsigned char *)res->n_rows, (const unsigned short *)res->branch,
                            (const double *)res->lwr, weights, (u64 *)masses);
     };
     if (lds && combine) launch(masses_kernel<true, true>);
     else if (lds) launch(masses_kernel<true, false>);
+    else if (cache) launch(masses_kernel<false, false, true>);
     else if (combine) launch(masses_kernel<false, true>);
     else launch(masses_kernel<false, false>);
     HIP_TRY(hipGetLastError());

@@ -157,6 +157,7 @@ static rk_result result_slice(const rk_result &r, uint64_t r0, uint32_t K) {
 // asynchronous and overlaps the other workspaces' chunks), and the stream all of it runs on.  Grow-only, kept in the rk_db.
 struct rk_workspace {
     GrowBuf ascii, off, packed, lens, flags;
+    GrowBuf weights;              // the chunk's weights (masses sink)
     ResultBufs<GrowBuf> res;      // (with the frame bytes: rk_place_batch_translated)
     GrowBuf strands, translated;  // the workspaces of rk_place_packed_device_strands / _translated for a chunk
     PinBuf h_ascii, h_off, h_packed;
@@ -165,7 +166,7 @@ struct rk_workspace {
     uint64_t pend_r0 = 0, pend_n = 0;
     hipStream_t stream = nullptr;
     void release() {
-        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &strands, &translated}) b->release();
+        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &weights, &strands, &translated}) b->release();
         for (PinBuf *b : {&h_ascii, &h_off, &h_packed}) b->release();
         res.release();
         h_res.release();

@@ -131,6 +131,15 @@ struct HostStep {
     uint8_t *frame_out = nullptr;
 };
 
+// Where a chunk's results go -- orthogonal to HostStep::kind.  Without `masses` the whole result set is downloaded into the caller's
+// arrays.  With it (rk_place_batch*_masses) the chunk is summed where it lies: rk_masses_accumulate_device on the chunk's stream, its
+// device result set, its weights and the handle's device mass buffer; only the flags come back (the counters are taken from them),
+// and `out` holds the caller's flags_out and nothing else.
+struct HostSink {
+    uint64_t *masses = nullptr;         // the caller's buffer: the device buffer's words are ADDED into it after the last chunk
+    const uint32_t *weights = nullptr;  // [n] or NULL
+};
+
 // the chunk's read limit: the one place that reads the developer knob
 static uint64_t chunk_max_reads() {
     if (const char *e = rk_knob("RK_CHUNK_READS")) {
@@ -161,8 +170,8 @@ static int check_host_call(const char *who, const rk_db *db, const rk_params *p,
     RK_TRY(check_params(p));
     return reads_missing ? fail(RK_ERR_INVALID, "%s: %s", who, reads_missing) : RK_OK;
 }
-static int check_host_batch(const char *who, uint64_t n_reads, const HostInput &in, const rk_result *out, const HostStep &step) {
-    if (!result_complete(out) || (step.kind == HostStep::TRANSLATED && !step.frame_out)) return fail(RK_ERR_INVALID, "%s: null result array", who);
+static int check_host_batch(const char *who, uint64_t n_reads, const HostInput &in, const rk_result *out, const HostStep &step, bool masses_sink) {
+    if (!masses_sink && (!result_complete(out) || (step.kind == HostStep::TRANSLATED && !step.frame_out))) return fail(RK_ERR_INVALID, "%s: null result array", who);
     if (in.off)  // (a compare and nothing else: 0.4 ms for 4 000 000 reads; the 2^28 symbol limit is tested chunk by chunk, where next_chunk has the lengths)
         for (uint64_t r = 0; r < n_reads; r++)
             if (in.off[r + 1] < in.off[r]) return fail(RK_ERR_INVALID, "%s: seq_off not monotone at read %llu", who, (unsigned long long)r);
@@ -198,22 +207,27 @@ class HostPath {
     }
 
   public:
-    HostPath(rk_db *db, const rk_params *p, uint64_t n_reads, const HostInput &in, rk_result *out, const HostStep &step, const char *who)
-        : db_(db), p_(p), n_reads_(n_reads), in_(in), out_(out), step_(step), who_(who), K_(p->keep_at_most), device_(db->info.device),
+    HostPath(rk_db *db, const rk_params *p, uint64_t n_reads, const HostInput &in, rk_result *out, const HostStep &step, const char *who,
+             const HostSink &sink = HostSink{})
+        : db_(db), p_(p), n_reads_(n_reads), in_(in), out_(out), step_(step), sink_(sink), who_(who), K_(p->keep_at_most), device_(db->info.device),
           node_(&gpu_node_cpus(db->info.device)), max_reads_(chunk_max_reads()), timing_(rk_knob("RK_HOST_TIMING") != nullptr) {
         // Caller buffers from rk_host_alloc (or otherwise page-locked) are the DMA's source / target directly; pageable ones
         // (the usual case behind JNI) go through page-locked staging with threaded copies
         packed_in_ = in.packed != nullptr;
         in_pinned_ = packed_in_ ? is_pinned(in.packed) : is_pinned(in.ascii);
-        out_pinned_ = is_pinned(out->n_rows) && is_pinned(out->branch) && is_pinned(out->score) && is_pinned(out->lwr) && is_pinned(out->flags) &&
-                      (!translated() || is_pinned(step.frame_out));
+        if (sink_.masses)  // only the flags come back: into the caller's flags_out if it is page-locked, else into the staging flags
+            out_pinned_ = out->flags && is_pinned(out->flags);
+        else
+            out_pinned_ = is_pinned(out->n_rows) && is_pinned(out->branch) && is_pinned(out->score) && is_pinned(out->lwr) && is_pinned(out->flags) &&
+                          (!translated() || is_pinned(step.frame_out));
+        weights_pinned_ = sink_.weights && is_pinned(sink_.weights);
         // pageable characters are packed on the host (rk_pack_host.cpp) by this call's worker threads; page-locked ones go to the
         // device as they are (no host work at all) and are packed there
         host_pack_ = translated() || (!packed_in_ && !in_pinned_);
         if (translated()) build_alphabet(RK_ALPHABET_DNA, false, alpha_), spec_ = pack_spec(alpha_, RK_ALPHABET_DNA, 2, 1, 0);
         else if (host_pack_) build_alphabet(db->info.alphabet, db->convert_uo != 0, alpha_), spec_ = pack_spec(alpha_, db->info.alphabet, db->info.bits_per_symbol, db->info.k, 0);
         // host threads of this call: staging / packing on one side, result copies on the other (both only for pageable memory)
-        const bool stages = host_pack_ || !in_pinned_;
+        const bool stages = host_pack_ || !in_pinned_ || stage_weights();
         n_stage_ = stages ? std::max(1u, host_threads(n_reads, 0) * 5 / 8) : 0u;
         n_drain_ = out_pinned_ ? 0u : std::max(1u, host_threads(n_reads, 0) * 3 / 8);
         if (const char *e = rk_knob("RK_STAGE_THREADS")) n_stage_ = (unsigned)std::max(1, atoi(e));  // developer knobs
@@ -226,6 +240,7 @@ class HostPath {
     ~HostPath() { finish(true); }
 
     int run(rk_counters *counters) {
+        if (sink_.masses) RK_TRY(masses_begin());
         drainer_ = std::thread([this]() { drainer_loop(); });
         int status = plan_chunk(plans_[0], 0, 0);
         if (status == RK_OK) status = stage_start(plans_[0]);
@@ -241,11 +256,41 @@ class HostPath {
                     who_, chunk_no_, t_stage_ * 1e3, t_enq_ * 1e3, t_wait_ * 1e3, t_drain_ * 1e3);
         }
         if (status == RK_OK && drain_status_ != RK_OK) status = fail(drain_status_, "%s", drain_msg_.c_str());
+        if (status == RK_OK && sink_.masses) status = masses_end();
         if (status == RK_OK && counters) *counters = ct_;
         return status;
     }
 
   private:
+    // The masses sink's device buffer, one per handle: zeroed here, and the zeroing waited for, so that it lies before every chunk's
+    // accumulate on all four streams (which then add into it side by side: integer atomics).
+    size_t masses_bytes() const { return (size_t)rk_masses_words(db_->info.n_branches) * 8; }
+    int masses_begin() {
+        hipStream_t s = db_->ws[0].stream;
+        RK_TRY(db_->d_masses.reserve(masses_bytes()));
+        RK_TRY(db_->h_masses.reserve(masses_bytes(), node_, device_));
+        RK_TRY(hip_rc(hipMemsetAsync(db_->d_masses.p, 0, masses_bytes(), s), "hipMemsetAsync"));
+        return hip_rc(hipStreamSynchronize(s), "hipStreamSynchronize");
+    }
+    // every chunk is drained (finish): one copy brings the words to the host, where they are ADDED into the caller's buffer -- the
+    // only place that writes it, reached on success alone
+    int masses_end() {
+        hipStream_t s = db_->ws[0].stream;
+        RK_TRY(hip_rc(hipMemcpyAsync(db_->h_masses.p, db_->d_masses.p, masses_bytes(), hipMemcpyDeviceToHost, s), "hipMemcpyAsync (device to host)"));
+        RK_TRY(hip_rc(hipStreamSynchronize(s), "hipStreamSynchronize"));
+        const uint64_t *src = db_->h_masses.as<uint64_t>();
+        for (size_t i = 0, n = masses_bytes() / 8; i < n; i++) sink_.masses[i] += src[i];
+        return RK_OK;
+    }
+
+    // bytes of the chunk's staging block ahead of its weights (pageable weights lie behind the records, lengths and flags)
+    size_t staged_base(const Plan &c) const {
+        if (host_pack_) return staged_bytes(c.n, c.wpr, true, true);
+        if (packed_in_ && !in_pinned_) return staged_bytes(c.n, c.wpr, in_.lens != nullptr, in_.flags != nullptr);
+        return 0;
+    }
+    bool stage_weights() const { return sink_.weights && !weights_pinned_; }
+
     // bounds, record width, workspace (waits until it is free)
     int plan_chunk(Plan &c, uint64_t from, unsigned no) {
         const rk::Chunk ch = rk::next_chunk(packed_in_ ? nullptr : in_.off, from, n_reads_, max_reads_, rk::CHUNK_MAX_BYTES);
@@ -270,25 +315,44 @@ class HostPath {
         if (host_pack_) {
             // pageable characters (the usual case behind JNI): packed HERE, by the call's worker threads, straight into the
             // page-locked staging buffer -- 48 instead of 158 bytes per 150-bp read cross the link, no copy of the characters
-            RK_TRY(w.h_packed.reserve(staged_bytes(n, c.wpr, true, true), node_, device_));
+            RK_TRY(w.h_packed.reserve(staged_base(c) + (stage_weights() ? n * 4 : 0), node_, device_));
             uint32_t *hp = w.h_packed.as<uint32_t>(), *hl = hp + n * c.wpr, *hf = hl + n;
             rk::PackSpec P = spec_;
             P.words_per_read = c.wpr;
             const uint8_t *seq_ascii = in_.ascii;
             const uint64_t *seq_off = in_.off;
             Plan *pc = &c;
+            const uint32_t *wsrc = stage_weights() ? sink_.weights + c0 : nullptr;  // pageable weights: behind the flags, a range a worker
+            uint32_t *wdst = hf + n;
             pool_->start([=](unsigned part, unsigned parts) {
-                pc->flags.fetch_or(rk::pack_reads_range(P, seq_ascii, seq_off, c0 + n * part / parts, c0 + n * (part + 1) / parts, c0, hp, hl, hf));
+                const uint64_t lo = n * part / parts, hi = n * (part + 1) / parts;
+                pc->flags.fetch_or(rk::pack_reads_range(P, seq_ascii, seq_off, c0 + lo, c0 + hi, c0, hp, hl, hf));
+                if (wsrc && hi > lo) memcpy(wdst + lo, wsrc + lo, (hi - lo) * 4);
             });
             c.staged_async = true;
         } else if (packed_in_ && !in_pinned_) {
             const size_t pb = c.pb;
-            RK_TRY(w.h_packed.reserve(staged_bytes(n, c.wpr, in_.lens != nullptr, in_.flags != nullptr), node_, device_));
+            RK_TRY(w.h_packed.reserve(staged_base(c) + (stage_weights() ? n * 4 : 0), node_, device_));
             const char *src = (const char *)(in_.packed + c0 * c.wpr);
             char *dst = (char *)w.h_packed.p;
+            const char *wsrc = stage_weights() ? (const char *)(sink_.weights + c0) : nullptr;
+            char *wdst = dst + staged_base(c);
+            const size_t wb = n * 4;
             pool_->start([=](unsigned part, unsigned parts) {
                 const size_t a = pb * part / parts, b = pb * (part + 1) / parts;
                 if (b > a) memcpy(dst + a, src + a, b - a);
+                const size_t wa = wb * part / parts, we = wb * (part + 1) / parts;
+                if (wsrc && we > wa) memcpy(wdst + wa, wsrc + wa, we - wa);
+            });
+            c.staged_async = true;
+        } else if (stage_weights()) {  // page-locked reads, pageable weights: the block holds the weights alone
+            RK_TRY(w.h_packed.reserve(n * 4, node_, device_));
+            const char *wsrc = (const char *)(sink_.weights + c0);
+            char *wdst = (char *)w.h_packed.p;
+            const size_t wb = n * 4;
+            pool_->start([=](unsigned part, unsigned parts) {
+                const size_t wa = wb * part / parts, we = wb * (part + 1) / parts;
+                if (we > wa) memcpy(wdst + wa, wsrc + wa, we - wa);
             });
             c.staged_async = true;
         }
@@ -324,13 +388,26 @@ class HostPath {
             RK_TRY(stage_start(next));
         }
         t2 = now();
-        RK_TRY(reserve_chunk(w, c.n, c.wpr, K_, translated(), !out_pinned_, node_, device_));
+        RK_TRY(reserve_chunk(w, c.n, c.wpr, K_, translated(), !out_pinned_ && !sink_.masses, node_, device_));
+        if (sink_.masses) {  // of the page-locked staging set only the flags; the chunk's weights on the device
+            if (!out_pinned_) RK_TRY(w.h_res.flags.reserve(c.n * 4, node_, device_));
+            if (sink_.weights) RK_TRY(w.weights.reserve(c.n * 4));
+        }
         RK_TRY(upload(c, w));
         RK_TRY(place(c, w));
-        // the result set: into page-locked caller arrays as they are, else into the staging set the drainer copies from
-        RK_TRY(hip_rc(out_pinned_ ? w.res.download(w.stream, *out_, step_.frame_out, c.r0, c.n, K_)
-                                  : w.res.download(w.stream, w.h_res.view(), translated() ? w.h_res.frame() : nullptr, 0, c.n, K_),
-                      "hipMemcpyAsync (device to host)"));
+        if (sink_.masses) {
+            // summed where it lies; the flags alone come back (a result set whose other arrays are null: download skips them)
+            const rk_result dres = w.res.view();
+            RK_TRY(rk_masses_accumulate_device(db_, K_, c.n, &dres, sink_.weights ? w.weights.as<uint32_t>() : nullptr, db_->d_masses.as<uint64_t>(), w.stream));
+            const rk_result staged{nullptr, nullptr, nullptr, nullptr, w.h_res.flags.as<uint32_t>()};
+            RK_TRY(hip_rc(out_pinned_ ? w.res.download(w.stream, *out_, nullptr, c.r0, c.n, K_) : w.res.download(w.stream, staged, nullptr, 0, c.n, K_),
+                          "hipMemcpyAsync (device to host)"));
+        } else {
+            // the result set: into page-locked caller arrays as they are, else into the staging set the drainer copies from
+            RK_TRY(hip_rc(out_pinned_ ? w.res.download(w.stream, *out_, step_.frame_out, c.r0, c.n, K_)
+                                      : w.res.download(w.stream, w.h_res.view(), translated() ? w.h_res.frame() : nullptr, 0, c.n, K_),
+                          "hipMemcpyAsync (device to host)"));
+        }
         w.pending = true; w.pend_r0 = c.r0; w.pend_n = c.n;  // (page-locked caller arrays: nothing to copy, the flags are still counted)
         { std::lock_guard<std::mutex> lk(qm_); ws_busy_[c.wi] = true; submitted_.push_back(c.wi); }
         qcv_.notify_all();
@@ -353,6 +430,9 @@ class HostPath {
             RK_TRY(h2d(w.off.p, w.h_off.p, (n + 1) * 8, s));
         }
         char *staged = (char *)w.h_packed.p;
+        if (sink_.weights) {  // 4 bytes a read: from page-locked caller memory as they are, else from the staging block (stage_start)
+            RK_TRY(h2d(w.weights.p, weights_pinned_ ? (const void *)(sink_.weights + r0) : staged + staged_base(c), n * 4, s));
+        }
         if (host_pack_) {
             RK_TRY(h2d(w.packed.p, staged, pb, s));
             RK_TRY(h2d(w.lens.p, staged + pb, n * 4, s));
@@ -409,6 +489,12 @@ class HostPath {
     void drain(rk_workspace &w, ForkJoin &dpool) {
         if (!w.pending) return;
         const uint64_t a0 = w.pend_r0, m = w.pend_n;
+        if (sink_.masses) {  // the flags: counted where they arrived, copied to flags_out when one is given
+            if (!out_pinned_ && out_->flags) memcpy(out_->flags + a0, w.h_res.flags.p, m * 4);
+            rk::count_flags(out_pinned_ ? out_->flags + a0 : w.h_res.flags.as<uint32_t>(), m, ct_);
+            w.pending = false;
+            return;
+        }
         if (!out_pinned_) {
             // the drain thread's workers, each a range of reads over the arrays (103 bytes per read at K = 7)
             dpool.run([&](unsigned part, unsigned parts) {
@@ -488,12 +574,13 @@ class HostPath {
     const HostInput in_;
     rk_result *const out_;
     const HostStep step_;
+    const HostSink sink_;
     const char *const who_;
     const uint32_t K_;
     const int device_;
     const NodeCpus *const node_;  // the CPUs next to the GPU: staging threads and page-locked buffers live there
     const uint64_t max_reads_;
-    bool packed_in_, in_pinned_, out_pinned_, host_pack_;
+    bool packed_in_, in_pinned_, out_pinned_, host_pack_, weights_pinned_;
     Alphabet alpha_;              // host_pack_: the packer's table and its spec (the record width is the chunk's)
     rk::PackSpec spec_{};
     unsigned n_stage_ = 0, n_drain_ = 0;
@@ -516,14 +603,14 @@ class HostPath {
 };
 
 static int place_host(rk_db *db, const rk_params *p, uint64_t n_reads, const HostInput &in, rk_result *out, rk_counters *counters, const char *who,
-                      const HostStep &step = HostStep{}) {
+                      const HostStep &step = HostStep{}, const HostSink &sink = HostSink{}) {
     if (n_reads == 0) { if (counters) *counters = rk_counters{}; return RK_OK; }
-    RK_TRY(check_host_batch(who, n_reads, in, out, step));
+    RK_TRY(check_host_batch(who, n_reads, in, out, step, sink.masses != nullptr));
     std::lock_guard<std::mutex> lock(db->host_mutex);  // the workspaces belong to the db: one host call at a time
     HIP_TRY(hipSetDevice(db->info.device));
     for (rk_workspace &w : db->ws)
         if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    HostPath path(db, p, n_reads, in, out, step, who);
+    HostPath path(db, p, n_reads, in, out, step, who, sink);
     return path.run(counters);
 }
 
@@ -543,6 +630,9 @@ extern "C" int rk_reserve_host_path(rk_db *db, uint32_t keep_at_most, uint32_t m
         const uint64_t n = rk::CHUNK_MAX_READS;
         const uint32_t wpr = rk_packed_words(db, max_read_len ? max_read_len : 1);
         const NodeCpus *node = &gpu_node_cpus(db->info.device);
+        // the masses sink's buffer, device and host side (rk_place_batch*_masses)
+        RK_TRY(db->d_masses.reserve((size_t)rk_masses_words(db->info.n_branches) * 8));
+        RK_TRY(db->h_masses.reserve((size_t)rk_masses_words(db->info.n_branches) * 8, node, db->info.device));
         for (rk_workspace &w : db->ws) {
             if (!w.stream) HIP_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
             RK_TRY(reserve_chunk(w, n, wpr, keep_at_most, false, true, node, db->info.device));
@@ -618,6 +708,57 @@ extern "C" int rk_place_batch_translated(rk_db *db, const rk_params *p, uint64_t
     step.kind = HostStep::TRANSLATED; step.frame_out = frame_out;
     RK_GUARD_BEGIN
     return place_host(db, p, n_reads, in, out, counters, who, step);
+    RK_GUARD_END(who)
+}
+
+// Profile-only placement: the pipeline of the entry point that `step` names with the masses sink behind it (HostSink).  The tests of
+// the arguments come first and in the header's order; until they have passed nothing is launched and nothing is written.
+static int place_host_masses(const char *who, rk_db *db, const rk_params *p, uint32_t step_code, uint64_t n_reads, const HostInput &in,
+                             const char *reads_missing, const uint32_t *weights, uint64_t *masses, uint32_t *flags_out, rk_counters *counters) {
+    RK_TRY(check_params(p));  // (what needs no handle first: a machine without a GPU can test it)
+    if (step_code > RK_STEP_TRANSLATED) return fail(RK_ERR_INVALID, "%s: step=%u (0 forward, 1 reverse, 2 both, 3 translated)", who, step_code);
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    HostStep step;
+    if (step_code == RK_STEP_TRANSLATED) {
+        RK_TRY(translated_handle(db, who));
+        step.kind = HostStep::TRANSLATED;
+    } else if (step_code != RK_STRAND_FORWARD) {
+        RK_TRY(strands_handle(db, who));
+        step.kind = HostStep::STRANDS; step.strand = step_code;
+    }
+    if (reads_missing) return fail(RK_ERR_INVALID, "%s: %s", who, reads_missing);
+    rk_result out{nullptr, nullptr, nullptr, nullptr, flags_out};
+    HostSink sink;
+    sink.masses = masses; sink.weights = weights;
+    return place_host(db, p, n_reads, in, &out, counters, who, step, sink);
+}
+
+extern "C" int rk_place_batch_masses(rk_db *db, const rk_params *p, uint32_t step, uint64_t n_reads, const uint8_t *seq_ascii, const uint64_t *seq_off,
+                                     const uint32_t *weights, uint64_t *masses, uint32_t *flags_out, rk_counters *counters) {
+    const char *who = "rk_place_batch_masses";
+    HostInput in;
+    in.ascii = seq_ascii; in.off = seq_off;
+    RK_GUARD_BEGIN
+    return place_host_masses(who, db, p, step, n_reads, in, n_reads && (!seq_ascii || !seq_off) ? "null reads" : nullptr, weights, masses, flags_out, counters);
+    RK_GUARD_END(who)
+}
+
+extern "C" int rk_place_batch_packed_masses(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *packed, uint32_t words_per_read,
+                                            const uint32_t *lens, uint32_t fixed_len, const uint32_t *flags, const uint8_t *seq_ascii,
+                                            const uint64_t *seq_off, const uint32_t *weights, uint64_t *masses, uint32_t *flags_out,
+                                            rk_counters *counters) {
+    const char *who = "rk_place_batch_packed_masses";
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    RK_TRY(check_params(p));
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (n_reads && (!packed || words_per_read == 0)) return fail(RK_ERR_INVALID, "%s: null packed reads", who);
+    RK_TRY(check_fixed_len(who, lens, fixed_len, db->info.bits_per_symbol, words_per_read));
+    if ((seq_ascii == nullptr) != (seq_off == nullptr)) return fail(RK_ERR_INVALID, "%s: seq_ascii and seq_off go together", who);
+    HostInput in;
+    in.ascii = seq_ascii; in.off = seq_off; in.packed = packed; in.wpr = words_per_read; in.lens = lens; in.fixed_len = fixed_len; in.flags = flags;
+    RK_GUARD_BEGIN
+    return place_host_masses(who, db, p, RK_STRAND_FORWARD, n_reads, in, nullptr, weights, masses, flags_out, counters);
     RK_GUARD_END(who)
 }
 

@@ -4413,7 +4413,19 @@ __global__ void __launch_bounds__(256) init_frame_kernel(const unsigned char *nr
 //   LDS_BINS   small trees: the block's mass and best live in the LDS (64-bit integer LDS atomics), are flushed once at the end, the
 //              non-zero bins only, one global atomic per bin and block; the grid is a small multiple of the CU count, not a block
 //              per 256 reads, since the flush costs blocks x B.
-//   otherwise  large trees: 64-bit global atomics straight into `out`.
+//   CACHE      large trees (B above the LDS limit): 64-bit global atomics into `out`, behind a per-block LDS table of MASS_CACHE_SLOTS
+//              slots {branch key, mass, best} for the busiest bins.  A lane with a counted row of branch x reads the two keys of
+//              the pair of slots mass_cache_slot(x) names: a key that is x is a hit; an empty key is claimed with a 32-bit LDS
+//              compare-and-swap, and the claim counts as a hit when it succeeds or finds x already there.  A hit adds in the LDS;
+//              anything else does the global atomics exactly as the direct variant.  A slot keeps its branch until the block ends
+//              (no eviction), so a key that was read non-empty is final and claim, add and flush need no order between them.  After
+//              the last barrier the block flushes the non-zero words of its claimed slots, one global atomic each.
+//              A row either adds in the LDS or issues the direct variant's atomics, and a non-zero flushed word has had at least
+//              one row that the direct variant would have sent to that very address (which sends the mass word even when it is
+//              zero): on the same grid the cached variant never issues more global atomics than the direct one, on any input.
+//              A wave-uniform hit-rate test after which a wave stops consulting the table was built and measured: it does not help
+//              the uniform batch (DESIGN.md 4.7 has both forms) and is not here.
+//   otherwise  large trees, direct: 64-bit global atomics straight into `out` (developer build: RK_MASSES_VARIANT=global).
 // A row whose branch is >= B is never an index: it is skipped and counted (word 2B+3), and takes no part in any other word.  That
 // needs the number of skipped rows per READ while the rows sit in other lanes: the wave ballots the skip (all zero on the engine's
 // own results) and, in the rare case, walks the set bits to the lanes that own the reads.  The four totals stay in registers, are
@@ -4421,14 +4433,25 @@ __global__ void __launch_bounds__(256) init_frame_kernel(const unsigned char *nr
 //   COMBINE    equal branches among the lanes of a wave are summed before the atomics (see there).
 // No 64-bit shift by a per-lane count anywhere.
 // ------------------------------------------------------------------------------------------------
-constexpr u32 MASS_NO_BRANCH = 0xFFFFFFFFu;  // a lane without a counted row
+constexpr u32 MASS_NO_BRANCH = 0xFFFFFFFFu;  // a lane without a counted row; an empty key of the cache (a branch id is below 65 536)
+// 512 slots of 20 bytes and the totals are 10 272 bytes of LDS: the eight blocks a CU that the wave limit gives the direct variant stay
+constexpr u32 MASS_CACHE_SLOTS = 512;
+// The first slot of x's pair: the top bits of a multiplicative hash, so that the consecutive pre-order ids of a clade neighbourhood,
+// and ids a power of two apart, land in different pairs.
+__device__ __forceinline__ u32 mass_cache_slot(u32 x) { return ((x * 0x9E3779B1u) >> 24) << 1; }
+static_assert(MASS_CACHE_SLOTS == 512, "mass_cache_slot: 8 bits of pair index, two slots a pair");
 
-template <bool LDS_BINS, bool COMBINE>
+template <bool LDS_BINS, bool COMBINE, bool CACHE = false>
 __global__ void __launch_bounds__(256) masses_kernel(u64 n_reads, u32 K, u32 B, const unsigned char *n_rows, const unsigned short *branch,
                                                      const double *lwr, const u32 *weights, u64 *out) {
-    extern __shared__ u64 mass_lds[];  // LDS_BINS: mass[B] | best[B] | totals[4]; otherwise totals[4]
-    const u32 n_lds = LDS_BINS ? 2u * B + 4u : 4u;
+    static_assert(!(LDS_BINS && CACHE), "the cache stands in front of the global atomics");
+    // LDS_BINS: mass[B] | best[B] | totals[4]; CACHE: mass[S] | best[S] | totals[4] | key[S] (32-bit); otherwise totals[4]
+    extern __shared__ u64 mass_lds[];
+    const u32 n_lds = LDS_BINS ? 2u * B + 4u : CACHE ? 2u * MASS_CACHE_SLOTS + 4u : 4u;
     for (u32 i = threadIdx.x; i < n_lds; i += 256) mass_lds[i] = 0;
+    u32 *const key = (u32 *)(mass_lds + n_lds);
+    if (CACHE)
+        for (u32 i = threadIdx.x; i < MASS_CACHE_SLOTS; i += 256) key[i] = MASS_NO_BRANCH;
     __syncthreads();
     u64 *tot = mass_lds + (n_lds - 4u);
     const u32 lane = threadIdx.x & 63;
@@ -4476,9 +4499,31 @@ __global__ void __launch_bounds__(256) masses_kernel(u64 n_reads, u32 K, u32 B, 
                 }
             }
             if (cx != MASS_NO_BRANCH) {
+                u32 slot = MASS_NO_BRANCH;
+                if (CACHE) {
+                    const u32 s0 = mass_cache_slot(cx);
+                    u32 k0 = __hip_atomic_load(&key[s0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    u32 k1 = __hip_atomic_load(&key[s0 + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (k0 == MASS_NO_BRANCH) {
+                        k0 = atomicCAS(&key[s0], MASS_NO_BRANCH, cx);
+                        if (k0 == MASS_NO_BRANCH) k0 = cx;
+                    }
+                    if (k0 == cx) {
+                        slot = s0;
+                    } else {
+                        if (k1 == MASS_NO_BRANCH) {
+                            k1 = atomicCAS(&key[s0 + 1], MASS_NO_BRANCH, cx);
+                            if (k1 == MASS_NO_BRANCH) k1 = cx;
+                        }
+                        if (k1 == cx) slot = s0 + 1;
+                    }
+                }
                 if (LDS_BINS) {
                     atomicAdd(&mass_lds[cx], cv);
                     if (cb) atomicAdd(&mass_lds[B + cx], cb);
+                } else if (CACHE && slot != MASS_NO_BRANCH) {
+                    atomicAdd(&mass_lds[slot], cv);
+                    if (cb) atomicAdd(&mass_lds[MASS_CACHE_SLOTS + slot], cb);
                 } else {
                     atomicAdd(&out[cx], cv);
                     if (cb) atomicAdd(&out[B + cx], cb);
@@ -4510,6 +4555,18 @@ __global__ void __launch_bounds__(256) masses_kernel(u64 n_reads, u32 K, u32 B, 
         if (t_skip) atomicAdd(&tot[3], t_skip);
     }
     __syncthreads();
+    if (CACHE) {  // the claimed slots' non-zero words to their branches, then the totals
+        for (u32 i = threadIdx.x; i < MASS_CACHE_SLOTS; i += 256) {
+            const u32 x = key[i];
+            if (x < B) {  // (a claimed slot holds a counted row's branch: below B)
+                const u64 v = mass_lds[i], b = mass_lds[MASS_CACHE_SLOTS + i];
+                if (v) atomicAdd(&out[x], v);
+                if (b) atomicAdd(&out[B + x], b);
+            }
+        }
+        if (threadIdx.x < 4 && tot[threadIdx.x]) atomicAdd(&out[2u * (u64)B + threadIdx.x], tot[threadIdx.x]);
+        return;
+    }
     u64 *dst = LDS_BINS ? out : out + 2u * (u64)B;
     for (u32 i = threadIdx.x; i < n_lds; i += 256) {
         const u64 v = mass_lds[i];

@@ -404,6 +404,55 @@ class PlacementProcess:
         out.counters = _counters(ct)
         return out
 
+    def _masses_args(self, n, weights, masses, flags_out):
+        """(weights u32 [n] or None, masses u64 [2B + 4], flags u32 [n]) of a profile-only call, checked / made"""
+        words = masses_words(self.db.info.n_branches)
+        if weights is not None and not isinstance(weights, np.ndarray):
+            weights = np.asarray(weights, dtype=np.uint32)
+        if weights is not None and (weights.dtype != np.uint32 or weights.shape != (n,) or not weights.flags.c_contiguous):
+            raise ValueError("weights must be a contiguous uint32 array with one word per read")
+        if masses is None:
+            masses = np.zeros(words, np.uint64)
+        elif masses.dtype != np.uint64 or masses.shape != (words,) or not masses.flags.c_contiguous:
+            raise ValueError(f"masses must be a contiguous uint64 array of {words} words")
+        if flags_out is None:
+            flags_out = np.zeros(n, np.uint32)
+        elif flags_out.dtype != np.uint32 or flags_out.shape != (n,) or not flags_out.flags.c_contiguous:
+            raise ValueError("flags_out must be a contiguous uint32 array with one word per read")
+        return weights, masses, flags_out
+
+    def processQueriesMasses(self, seq, seq_off, weights=None, masses=None, strand="forward", translate=False, keepAtMost=7, keepFactor=0.01,
+                             treatAmbiguities=True, treatAmbiguitiesWithMax=False, flags_out=None):
+        """rk_place_batch_masses: profile-only placement.  The reads are placed as processQueries(strand=...) -- or, with translate=True,
+        processQueriesTranslated -- would place them, but every chunk is summed on the device (accumulate_masses) and only the flags
+        come back: no Placements.  Returns (masses uint64 [2B + 4], flags uint32 [n], counters): `masses` (made and zeroed when None)
+        has received exactly what accumulate_masses_host would add for that call's result set and `weights` (uint32 [n], None = 1 a
+        read); flags and counters are that call's.  The frame bytes of the translated step do not come back."""
+        seq, seq_off, n = _reads(seq, seq_off)
+        weights, masses, flags_out = self._masses_args(n, weights, masses, flags_out)
+        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
+        ct = rk_counters()
+        step = _lib.RK_STEP_TRANSLATED if translate else _strand(strand)
+        _lib.check(self._lib.rk_place_batch_masses(self.db.handle, C.byref(p), step, n, _ptr(seq), _ptr(seq_off),
+                                                   None if weights is None else _ptr(weights), _ptr(masses), _ptr(flags_out), C.byref(ct)))
+        return masses, flags_out, _counters(ct)
+
+    def processQueriesPackedMasses(self, packed, lens=None, fixed_len=0, flags=None, seq=None, seq_off=None, weights=None, masses=None,
+                                   keepAtMost=7, keepFactor=0.01, treatAmbiguities=True, treatAmbiguitiesWithMax=False, flags_out=None):
+        """rk_place_batch_packed_masses: processQueriesMasses for reads already packed on the host (the arguments of
+        processQueriesPacked); the same (masses, flags, counters)."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint32)
+        n, wpr = packed.shape
+        weights, masses, flags_out = self._masses_args(n, weights, masses, flags_out)
+        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
+        ct = rk_counters()
+        keep = [np.ascontiguousarray(a, dtype=dt) if a is not None else None
+                for a, dt in ((lens, np.uint32), (flags, np.uint32), (seq, np.uint8), (seq_off, np.uint64))]
+        ptrs = [None if a is None else _ptr(a) for a in keep]
+        _lib.check(self._lib.rk_place_batch_packed_masses(self.db.handle, C.byref(p), n, _ptr(packed), wpr, ptrs[0], fixed_len, ptrs[1], ptrs[2], ptrs[3],
+                                                          None if weights is None else _ptr(weights), _ptr(masses), _ptr(flags_out), C.byref(ct)))
+        return masses, flags_out, _counters(ct)
+
     def processQueriesMulti(self, dbs, seq, seq_off, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
                             treatAmbiguitiesWithMax=False, out=None):
         """processQueries over several device handles of the same database from this one process

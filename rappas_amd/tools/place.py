@@ -15,6 +15,8 @@ from ..placement import PhyloKmerDB, PlacementProcess
 
 
 TRANSLATE_WITH_STRAND = "--translate places every read in all six reading frames, both strands included: it cannot be combined with --strand rev | both"
+MASSES_ONLY_WITH_OUT = "--masses-only writes no jplace (the placements never reach the host): it cannot be combined with --out"
+MASSES_ONLY_WITH_MASSES = "--masses-only writes the table --masses writes, without placing into a jplace: give one of the two"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
 
 
@@ -28,22 +30,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for)."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
-    if dbimage is not None:
-        from ..placement import db_image_info
-        _, blob = db_image_info(dbimage)
-        tree = hostio.tree_from_blob(blob)
-        db = PhyloKmerDB.load(dbimage, device=device)
-        if db.info.n_branches != len(tree.nodes):
-            raise ValueError("database image: tree and database disagree on the number of branches")
-    else:
-        d = hostio.load_uniondb(db_text) if union else hostio.load_jsondb(db_text)
-        tree = d["tree"]
-        if save_dbimage is not None:
-            from ..placement import save_db_image
-            save_db_image(save_dbimage, d["alphabet"], d["k"], d["n_branches"], d["thr_log10"], d["thr"], d["key_codes"], d["row_offsets"],
-                          d["branch_ids"], d["scores"], convert_uo=d.get("convert_uo", False), user=hostio.tree_to_blob(tree))
-        db = PhyloKmerDB(d["alphabet"], d["k"], d["n_branches"], d["thr_log10"], d["thr"], d["key_codes"], d["row_offsets"],
-                         d["branch_ids"], d["scores"], device=device, convert_uo=d.get("convert_uo", False))
+    db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     try:
         if translate and db.info.alphabet != 20:
             raise ValueError(TRANSLATE_NEEDS_AA)
@@ -70,6 +57,53 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     return hostio.jplace_document(tree, pl, call_string, guppy), res
 
 
+def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), device=0, union=False,
+                     dbimage=None, save_dbimage=None, strand="fwd", translate=False):
+    """`--masses-only FILE`: scan, dedup and gather as place_file, then ONE profile-only call (processQueriesMasses) with the
+    multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
+    table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
+    No jplace and no frames log: the rows and the frame bytes never reach the host."""
+    from types import SimpleNamespace
+    if translate and strand != "fwd":
+        raise ValueError(TRANSLATE_WITH_STRAND)
+    db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
+    try:
+        if translate and db.info.alphabet != 20:
+            raise ValueError(TRANSLATE_NEEDS_AA)
+        records = hostio.read_fasta(fasta_text)
+        unique, names = hostio.dedup_reads(records)
+        seq, off = hostio.pack_batch([s for _, s in unique])
+        weights = np.array([len(nm) for nm in names], dtype=np.uint32)
+        words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(
+            seq, off, weights=weights, strand=strand, translate=translate, keepAtMost=keep_at_most, keepFactor=keep_factor,
+            treatAmbiguities=(amb != "skip"), treatAmbiguitiesWithMax=(amb == "max"))
+    finally:
+        db.close()
+    return SimpleNamespace(masses=hostio.masses_table(tree, words), notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
+                           reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters)
+
+
+def _open_db(db_text, union, dbimage, save_dbimage, device):
+    """(handle, reference tree) of a --jsondb / --uniondb text or of an image file"""
+    if dbimage is not None:
+        from ..placement import db_image_info
+        _, blob = db_image_info(dbimage)
+        tree = hostio.tree_from_blob(blob)
+        db = PhyloKmerDB.load(dbimage, device=device)
+        if db.info.n_branches != len(tree.nodes):
+            raise ValueError("database image: tree and database disagree on the number of branches")
+    else:
+        d = hostio.load_uniondb(db_text) if union else hostio.load_jsondb(db_text)
+        tree = d["tree"]
+        if save_dbimage is not None:
+            from ..placement import save_db_image
+            save_db_image(save_dbimage, d["alphabet"], d["k"], d["n_branches"], d["thr_log10"], d["thr"], d["key_codes"], d["row_offsets"],
+                          d["branch_ids"], d["scores"], convert_uo=d.get("convert_uo", False), user=hostio.tree_to_blob(tree))
+        db = PhyloKmerDB(d["alphabet"], d["k"], d["n_branches"], d["thr_log10"], d["thr"], d["key_codes"], d["row_offsets"],
+                         d["branch_ids"], d["scores"], device=device, convert_uo=d.get("convert_uo", False))
+    return db, tree
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="rappas_amd.tools.place", description=__doc__.splitlines()[0])
     g = ap.add_mutually_exclusive_group(required=True)
@@ -78,7 +112,7 @@ def main(argv=None):
     g.add_argument("--dbimage", help="the engine's own database image (written by --save-dbimage / rk_db_save): mmap + upload, no parse")
     ap.add_argument("--save-dbimage", default=None, help="with --jsondb / --uniondb: also write the database as an image file")
     ap.add_argument("--fasta", required=True, help="query reads (-q)")
-    ap.add_argument("--out", required=True, help="output .jplace")
+    ap.add_argument("--out", default=None, help="output .jplace (required unless --masses-only is given)")
     ap.add_argument("--keep-at-most", type=int, default=7)
     ap.add_argument("--keep-factor", type=float, default=0.01)
     ap.add_argument("--amb", choices=["mean", "max", "skip"], default="mean", help="--ambwithmax / --noamb")
@@ -93,12 +127,24 @@ def main(argv=None):
     ap.add_argument("--masses", default=None, metavar="FILE",
                     help="also write the per-edge table of the run: one line per tree node with the reads whose best placement is its edge and "
                          "the likelihood weight on it, and the same summed over its clade; a read counts once per FASTA record")
+    ap.add_argument("--masses-only", default=None, metavar="FILE",
+                    help="profile-only run: write that table to FILE and nothing else but the notplaced (and, with --strand rev | both, the "
+                         "reversed) log -- the placements are summed on the device and never reach the host, so no jplace is written, "
+                         "--out may not be given, and with --translate the frames log is not written (the frame bytes do not come back); "
+                         "not with --masses")
+    ap.add_argument("--timing", action="store_true", help="--masses-only: one JSON line with the run's wall-clock times on stdout")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--logs", default=None, help="directory of notplaced_<query>.tsv (default: logs/ next to --out, like the reference's workdir/logs)")
     a = ap.parse_args(argv)
     if a.translate and a.strand != "fwd":
         ap.error(TRANSLATE_WITH_STRAND)
+    if a.masses_only is not None and a.masses is not None:
+        ap.error(MASSES_ONLY_WITH_MASSES)
+    if a.masses_only is not None and a.out is not None:
+        ap.error(MASSES_ONLY_WITH_OUT)
+    if a.masses_only is None and a.out is None:
+        ap.error("--out is required (or --masses-only FILE for a profile-only run)")
     db_text = None
     if a.dbimage is None:
         with open(a.jsondb or a.uniondb, "rb") as f:
@@ -106,6 +152,8 @@ def main(argv=None):
     with open(a.fasta, "rb") as f:
         fasta_text = f.read()
     call = "".join(" " + x for x in (argv if argv is not None else sys.argv[1:]))
+    if a.masses_only is not None:
+        return _main_masses_only(a, db_text, fasta_text)
     try:
         doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
@@ -132,6 +180,35 @@ def main(argv=None):
             f.write(res.masses)
     placed = int(np.count_nonzero(res.n_rows))
     print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
+    return 0
+
+
+def _main_masses_only(a, db_text, fasta_text):
+    import json
+    import time
+    t0 = time.perf_counter()
+    try:
+        res = masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.device, union=a.uniondb is not None,
+                               dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate)
+    except ValueError as e:
+        if str(e) != TRANSLATE_NEEDS_AA:
+            raise
+        print("rappas_amd.tools.place: " + TRANSLATE_NEEDS_AA, file=sys.stderr)
+        return 1
+    t1 = time.perf_counter()
+    with open(a.masses_only, "w") as f:
+        f.write(res.masses)
+    logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.masses_only)), "logs")
+    os.makedirs(logs, exist_ok=True)
+    with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
+        f.write(res.notplaced)
+    if res.reversed is not None:
+        with open(os.path.join(logs, "reversed_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
+            f.write(res.reversed)
+    print(f"{len(res.flags)} unique reads, {res.counters['placed']} placed -> {a.masses_only}", file=sys.stderr)
+    if a.timing:
+        print(json.dumps({"mode": "masses_only", "unique_reads": len(res.flags), "db_and_masses_s": round(t1 - t0, 6),
+                          "fasta_to_masses_s": round(time.perf_counter() - t0, 6)}))
     return 0
 
 

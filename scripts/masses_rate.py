@@ -1,13 +1,14 @@
 """Device-side cost of the edge masses (rk_masses_accumulate_device) next to the placement that made the results:
-10^7 reads at keep_at_most 7 on C2's tree (999 branches: the kernel's LDS variant) and on T64k's (65 535: global atomics), uniform
+10^7 reads at keep_at_most 7 on C2's tree (999 branches: the kernel's LDS variant) and on T64k's (65 535: global atomics behind the
+per-block cache of the busiest bins), uniform
 reads (bench.py's: generated on the device into the packed layout, seed 1) and clade-shaped ones (scripts/clade_bench.py's:
 synth.make_clade_db / make_clade_reads, 2 * 10^6 reads cut from the genome, repeated five times), plus the contention case no
 placement produces: every row of every read on one branch.  Per batch: the accumulate call's time, the plain placement call's time
 on the same batch in the same process, and the bytes of the result set the call reads (n_rows, branch, lwr: 1 + 10 K per read)
 divided by its time.  Warm-up, then HIP events around every step, median.
 
---variants switches to the developer build and repeats the accumulate call with the variant forced (RK_MASSES_VARIANT: lds | global,
-+combine; RK_MASSES_BLOCKS_PER_CU), also on T4k's tree (3 999 branches, the largest bench tree below the LDS limit): the runs the
+--variants switches to the developer build and repeats the accumulate call with the variant forced (RK_MASSES_VARIANT: lds | global |
+cache, +combine; RK_MASSES_BLOCKS_PER_CU), also on T4k's tree (3 999 branches, the largest bench tree below the LDS limit): the runs the
 constants RK_MASSES_LDS_MAX_BRANCHES / RK_MASSES_COMBINE / RK_MASSES_LDS_BLOCKS_PER_CU in rk_engine.hip were chosen from.
 
     python scripts/masses_rate.py [--reads 10000000] [--steps 10] [--warmup 10] [--variants] >> profiles/masses_rate.txt
@@ -65,7 +66,7 @@ def report(tag, pp, out, place_ms=None):
     shape = f"{rows / n:.2f} rows a read, busiest best-branch {int(top.max().item()) / max(1, int((out['n_rows'] > 0).sum().item())):.4f} of the placed reads"
     runs = [("", {})]
     if a.variants:
-        runs = [(v, {"RK_MASSES_VARIANT": v}) for v in ("lds", "lds+combine", "global", "global+combine") if B <= 4094 or "lds" not in v]
+        runs = [(v, {"RK_MASSES_VARIANT": v}) for v in ("lds", "lds+combine", "global", "global+combine", "cache") if B <= 4094 or "lds" not in v]
         if B <= 4094:
             runs += [(f"lds, {b} blocks a CU", {"RK_MASSES_VARIANT": "lds", "RK_MASSES_BLOCKS_PER_CU": str(b)}) for b in (1, 2, 8, 16)]
     for name, env in runs:
