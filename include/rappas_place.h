@@ -427,6 +427,60 @@ int rk_place_batch_packed_masses(rk_db *db, const rk_params *p, uint64_t n_reads
                                  const uint64_t *seq_off, const uint32_t *weights, uint64_t *masses, uint32_t *flags_out,
                                  rk_counters *counters);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-sample edge masses from one batch: a membership list per read.  A study pools and deduplicates the reads of many samples,
+ * places each distinct sequence once and hands its abundance back to every sample it occurs in.  A unique read belongs to several
+ * samples with a multiplicity of its own in each, so the input is a sparse list of entries, not one sample per read.
+ *   Membership entry    (read index, sample index, weight), all uint32.  A read may have zero, one or many entries; the same (read,
+ *                       sample) pair may repeat.
+ *   Sample mass buffer  for S samples on a tree of B branches: S * W + 1 little-endian 64-bit words, W = rk_masses_words(B) = 2B + 4.
+ *                         [s * W, (s + 1) * W)  an ordinary mass buffer for sample s: exactly what rk_masses_accumulate_host adds for
+ *                                               the result set gathered by the entries of sample s -- row i of the gathered set is the
+ *                                               result of read member_read[i], its weight member_weight[i].  A read with two entries
+ *                                               in one sample counts twice there, the skipped-row word included.
+ *                         S * W                 entries skipped because sample >= S or read >= n_reads.  Such an entry is never used
+ *                                               as an index and adds to no other word -- a bounds check, as the branch >= B rule is.
+ *   Exactness           every term is an integer: device, host twin and any split into calls, chunks, streams or GPUs give the same
+ *                       words.  Per sample: exact while the sum of its weights stays below 2^33 (not checked).
+ *   Limits              1 <= S <= 65535 and S * W + 1 <= 2^29 words (4 GiB).
+ *   Adding              calls ADD into the buffer; zeroing it is the caller's job.
+ *   rk_masses_samples_words              S * W + 1; 0 on a bad argument or beyond the limit.
+ *   rk_masses_accumulate_samples_device  device pointers on db's device, B from the handle.  d_member_read NULL: entry i is read i
+ *                                        (n_members == n_reads); d_member_weight NULL: 1.  Asynchronous on `stream`, allocates nothing
+ *                                        and does not use the handle's launch scratch.
+ *   rk_masses_accumulate_samples_host    the same words in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16: threads
+ *                                        share the entries and sum privately while the partial buffers stay small, else they share the
+ *                                        samples and need none.
+ *   rk_place_batch_masses_samples        rk_place_batch_masses with the membership in place of `weights`: member_off [n_reads + 1] is
+ *   rk_place_batch_packed_masses_samples a CSR over the reads (read r owns entries member_off[r] .. member_off[r + 1] of member_sample
+ *                                        and member_weight); member_off NULL: one entry per read, entry r is read r.  member_weight
+ *                                        NULL: 1.  `step` and its RK_ERR_UNSUPPORTED cases as in rk_place_batch_masses.  Let R be the
+ *                                        result set of the corresponding existing entry point for the same reads: `masses` (host
+ *                                        memory, rk_masses_samples_words(B, S) words) ends as its previous content plus what
+ *                                        rk_masses_accumulate_samples_host adds over R with the CSR expanded; flags_out and counters
+ *                                        equal that call's.  The result does not depend on the chunking.  The handle's device mass
+ *                                        buffer grows to S * W + 1 words at the first such call; an error later in the call leaves
+ *                                        `masses` as it was.
+ * RK_ERR_INVALID (and a message), before anything is launched or written, for a NULL required pointer, keep_at_most outside 1..16,
+ * n_reads or n_members >= 2^32 (the accumulate calls), S outside its limits, d_member_read == NULL with n_members != n_reads, member_off[0] != 0 or a
+ * decreasing member_off.  n_members == 0 is RK_OK and touches nothing.  Added without a bump of RK_VERSION (no struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+uint64_t rk_masses_samples_words(uint32_t n_branches, uint32_t n_samples);
+int rk_masses_accumulate_samples_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_res, uint32_t n_samples,
+                                        uint64_t n_members, const uint32_t *d_member_read, const uint32_t *d_member_sample,
+                                        const uint32_t *d_member_weight, uint64_t *d_masses, void *stream);
+int rk_masses_accumulate_samples_host(uint32_t n_branches, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, uint32_t n_samples,
+                                      uint64_t n_members, const uint32_t *member_read, const uint32_t *member_sample,
+                                      const uint32_t *member_weight, uint64_t *masses, uint32_t n_threads);
+int rk_place_batch_masses_samples(rk_db *db, const rk_params *p, uint32_t step, uint64_t n_reads, const uint8_t *seq_ascii,
+                                  const uint64_t *seq_off, uint32_t n_samples, const uint64_t *member_off, const uint32_t *member_sample,
+                                  const uint32_t *member_weight, uint64_t *masses, uint32_t *flags_out, rk_counters *counters);
+int rk_place_batch_packed_masses_samples(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *packed, uint32_t words_per_read,
+                                         const uint32_t *lens, uint32_t fixed_len, const uint32_t *flags, const uint8_t *seq_ascii,
+                                         const uint64_t *seq_off, uint32_t n_samples, const uint64_t *member_off,
+                                         const uint32_t *member_sample, const uint32_t *member_weight, uint64_t *masses,
+                                         uint32_t *flags_out, rk_counters *counters);
+
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the
  * packed kernels place (not BAD_CHAR / TOO_LONG / AMBIGUOUS, at least k symbols); kmers_hit = those with a row in the database

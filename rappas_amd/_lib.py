@@ -134,6 +134,16 @@ EXPORTS = {
                                         C.c_void_p, C.POINTER(rk_counters)]),
     "rk_place_batch_packed_masses": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rk_counters)]),
+    "rk_masses_samples_words": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "rk_masses_accumulate_samples_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rk_masses_accumulate_samples_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rk_place_batch_masses_samples": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(rk_counters)]),
+    "rk_place_batch_packed_masses_samples": (C.c_int, [C.c_void_p, C.POINTER(rk_params), C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.POINTER(rk_counters)]),
     "rk_count_work_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_set_lanes_per_read": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rk_kernel_name": (C.c_char_p, [C.c_void_p]),

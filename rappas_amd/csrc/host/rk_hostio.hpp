@@ -10,6 +10,7 @@
 //                     src/tree/NewickReader.java:46-160, src/tree/PhyloTree.java:408-439, src/tree/NewickWriter.java:116-212
 // rappas_amd/hostio.py is the same logic in Python; tests/test_host_cpp.py requires byte-identical output from the two.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <charconv>
 #include <cmath>
@@ -352,6 +353,73 @@ inline std::string masses_table(const Tree &t, const uint64_t *m, size_t words) 
     out += "#total";
     for (size_t i = 0; i < 4; i++) out += "\t" + std::to_string(m[2 * B + i]);
     return out + "\n";
+}
+
+// --sample-sep C: the per-sample tables of one run.  A record's sample is its header up to the first C; the samples are numbered in
+// byte-wise order of their names; a unique read has one membership entry per distinct sample among its records, the count as its
+// weight, in sample order -- the CSR rk_place_batch_masses_samples takes.  The twin of hostio.sample_members / masses_samples_table.
+inline std::string sample_name(const char *hdr, size_t len, char sep) {
+    const void *at = len ? memchr(hdr, sep, len) : nullptr;
+    if (!at) throw std::runtime_error("--sample-sep: the header '" + std::string(hdr, len) + "' does not contain the separator '" + std::string(1, sep) + "'");
+    return std::string(hdr, (size_t)((const char *)at - hdr));
+}
+
+struct SampleMembers {
+    std::vector<std::string> names;       // [S], sorted
+    std::vector<uint64_t> off;            // [n unique + 1]
+    std::vector<uint32_t> sample, weight; // [entries]
+};
+
+// header_of(i) -> (pointer, length) of record i's header; uniq_of_rec[i]: its unique read
+template <class HeaderOf>
+inline SampleMembers sample_members(size_t n_records, size_t n_unique, HeaderOf header_of, const uint32_t *uniq_of_rec, char sep) {
+    SampleMembers sm;
+    std::unordered_map<std::string, uint32_t> seen;
+    std::vector<uint32_t> rec_sample(n_records);
+    for (size_t i = 0; i < n_records; i++) {
+        const std::pair<const char *, size_t> h = header_of(i);
+        auto ins = seen.emplace(sample_name(h.first, h.second, sep), (uint32_t)seen.size());
+        rec_sample[i] = ins.first->second;
+    }
+    for (const auto &kv : seen) sm.names.push_back(kv.first);
+    std::sort(sm.names.begin(), sm.names.end());  // (std::string compares bytes as unsigned char)
+    std::vector<uint32_t> rank(seen.size());
+    for (uint32_t s = 0; s < sm.names.size(); s++) rank[seen[sm.names[s]]] = s;
+    // the records of every unique read, as their samples: counted, placed, sorted, run-length coded
+    std::vector<uint64_t> at(n_unique + 1, 0);
+    for (size_t i = 0; i < n_records; i++) at[uniq_of_rec[i] + 1]++;
+    for (size_t u = 0; u < n_unique; u++) at[u + 1] += at[u];
+    std::vector<uint32_t> by_read(n_records);
+    {
+        std::vector<uint64_t> fill(at.begin(), at.end() - 1);
+        for (size_t i = 0; i < n_records; i++) by_read[fill[uniq_of_rec[i]]++] = rank[rec_sample[i]];
+    }
+    sm.off.assign(n_unique + 1, 0);
+    for (size_t u = 0; u < n_unique; u++) {
+        std::sort(by_read.begin() + at[u], by_read.begin() + at[u + 1]);
+        for (uint64_t e = at[u]; e < at[u + 1]; e++) {
+            if (e > at[u] && by_read[e] == by_read[e - 1]) { sm.weight.back()++; continue; }
+            sm.sample.push_back(by_read[e]);
+            sm.weight.push_back(1);
+        }
+        sm.off[u + 1] = sm.sample.size();
+    }
+    return sm;
+}
+
+// for each sample in order: a line `#sample<TAB>name<TAB>index`, then masses_table of its words; after the last sample a line
+// `#skipped_entries<TAB>n` (the last word of the sample mass buffer)
+inline std::string masses_samples_table(const Tree &t, const std::vector<std::string> &names, const uint64_t *m, size_t words) {
+    const size_t W = 2 * t.nodes.size() + 4;
+    if (words != names.size() * W + 1)
+        throw std::runtime_error("masses_samples_table: the buffer holds " + std::to_string(words) + " words, " + std::to_string(names.size()) + " samples on the tree's " +
+                                 std::to_string(t.nodes.size()) + " nodes need " + std::to_string(names.size() * W + 1));
+    std::string out;
+    for (size_t s = 0; s < names.size(); s++) {
+        out += "#sample\t" + names[s] + "\t" + std::to_string(s) + "\n";
+        out += masses_table(t, m + s * W, W);
+    }
+    return out + "#skipped_entries\t" + std::to_string(m[names.size() * W]) + "\n";
 }
 
 // NumberFormat.getNumberInstance(Locale.UK), exactly 12 fraction digits, grouping commas (NewickWriter.java:61-64)

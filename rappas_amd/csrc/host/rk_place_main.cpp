@@ -35,18 +35,23 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                 rev | both, the reversed log; the placements are summed on the device and never reach the host, so no jplace is\n"
                  "                 written and --out may not be given; with --translate the frames log is not written, as the frame bytes do not come\n"
                  "                 back; not with --masses; --timing prints one JSON line with keys of its own, fasta_to_masses_s among them)\n"
+                 "                [--sample-sep C]  (with --masses or --masses-only: one table per sample in FILE.  A record's sample is its header up\n"
+                 "                 to the first character C -- a header without C is an error --, samples are numbered in byte-wise order of their\n"
+                 "                 names, and a read counts in every sample once per record of that sample; FILE holds, for each sample, a line\n"
+                 "                 #sample<TAB>name<TAB>index and its table, and a last line #skipped_entries<TAB>n)\n"
                  "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
                  "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
                  "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
                  "       rk_place (--jsondb DB.json | --uniondb DB.union) --save-dbimage DB.rkimg      (no GPU needed)\n"
                  "       rk_place --masses-table TREE.nwk MASSES.bin OUT.tsv      (a raw little-endian u64 mass buffer as that table; no GPU needed)\n"
+                 "       rk_place --sample-members READS.fa C | --masses-samples-table TREE.nwk NAMES.txt MASSES.bin OUT.tsv      (no GPU needed)\n"
                  "       rk_place --emit-tree TREE.nwk | --format-float X | --format-double X | --dedup READS.fa | --md5 TEXT\n";
     return rc;
 }
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7;
@@ -75,6 +80,7 @@ int main(int argc, char **argv) {
             else if (a == "--translate") translate = true;
             else if (a == "--masses") masses_path = val();
             else if (a == "--masses-only") masses_only_path = val();
+            else if (a == "--sample-sep") { sample_sep = val(); if (sample_sep.size() != 1) throw std::runtime_error("--sample-sep takes one character"); }
             else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
             else if (a == "--guppy-compat") guppy = true;
@@ -215,6 +221,36 @@ int main(int argc, char **argv) {
                 if (!of) throw std::runtime_error("cannot write " + opath);
                 of << rkh::masses_table(t, m.data(), m.size());
                 return 0;
+            } else if (a == "--sample-members") {  // FASTA C: the samples and the membership CSR of --sample-sep (compared with the Python twin)
+                const std::string path = val(), sep = val();
+                if (sep.size() != 1) throw std::runtime_error("--sample-members takes one separator character");
+                const std::vector<rkh::Fasta> records = rkh::read_fasta(slurp(path));
+                const rkh::Dedup cd = rkh::dedup_index(records);
+                const rkh::SampleMembers sm = rkh::sample_members(records.size(), cd.first_rec.size(),
+                    [&](size_t r) { return std::make_pair(records[r].header.data(), records[r].header.size()); }, cd.uniq_of_rec.data(), sep[0]);
+                for (size_t s = 0; s < sm.names.size(); s++) std::cout << "#sample\t" << sm.names[s] << "\t" << s << "\n";
+                for (size_t u = 0; u + 1 < sm.off.size(); u++) {
+                    std::cout << u;
+                    for (uint64_t e = sm.off[u]; e < sm.off[u + 1]; e++) std::cout << "\t" << sm.sample[e] << ":" << sm.weight[e];
+                    std::cout << "\n";
+                }
+                return 0;
+            } else if (a == "--masses-samples-table") {  // TREE NAMES MASSES OUT: the per-sample table writer on its own (one name a line)
+                const std::string tpath = val(), npath = val(), mpath = val(), opath = val();
+                const rkh::Tree t = rkh::parse_newick(slurp(tpath));
+                std::vector<std::string> names;
+                {
+                    std::istringstream ns(slurp(npath));
+                    for (std::string line; std::getline(ns, line);) names.push_back(line);
+                }
+                const std::string raw = slurp(mpath);
+                if (raw.size() % 8) throw std::runtime_error(mpath + ": not a whole number of 64-bit words");
+                std::vector<uint64_t> m(raw.size() / 8);
+                if (!m.empty()) memcpy(m.data(), raw.data(), raw.size());
+                std::ofstream of(opath, std::ios::binary);
+                if (!of) throw std::runtime_error("cannot write " + opath);
+                of << rkh::masses_samples_table(t, names, m.data(), m.size());
+                return 0;
             } else if (a == "--ingest-rate") {  // N3 throughput: FASTA parse, MD5 dedup, host-side packing (no device needed)
                 const std::string text = slurp(val());
                 auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -275,6 +311,10 @@ int main(int argc, char **argv) {
             std::cerr << "rk_place: --masses-only writes no jplace (the placements never reach the host): it cannot be combined with --out\n";
             return 2;
         }
+        if (!sample_sep.empty() && !masses_only && masses_path.empty()) {
+            std::cerr << "rk_place: --sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only\n";
+            return 2;
+        }
         const bool only_convert = !save_image.empty() && fasta.empty() && out.empty() && !masses_only;
         if (n_sources != 1 || (!only_convert && (fasta.empty() || (out.empty() && !masses_only))) || (only_convert && !dbimage.empty())) return usage();
         uint32_t amb_mode;
@@ -300,7 +340,23 @@ int main(int argc, char **argv) {
         };
         // --masses: the per-edge table of the whole run.  The results are on the host already, so the sums are rk_masses_accumulate_host's;
         // the weight of a unique read is the number of FASTA records it stands for, so the table speaks of reads
-        auto write_masses = [&](const rkh::Tree &t, uint64_t m, const rk_result *rs, const uint32_t *w, uint32_t n_threads) {
+        // (--sample-sep: `sm` holds the samples and the membership entries of the unique reads, and the table is one per sample)
+        auto write_masses = [&](const rkh::Tree &t, uint64_t m, const rk_result *rs, const uint32_t *w, uint32_t n_threads, const rkh::SampleMembers *sm) {
+            if (sm) {
+                const uint32_t S = (uint32_t)sm->names.size();
+                std::vector<uint64_t> words((size_t)rk_masses_samples_words((uint32_t)t.nodes.size(), S), 0);
+                if (words.empty()) throw std::runtime_error("--masses --sample-sep: " + std::to_string(sm->names.size()) + " samples on this tree are beyond the limits of a sample mass buffer");
+                std::vector<uint32_t> reads(sm->sample.size());
+                for (uint64_t r = 0; r < m; r++)
+                    for (uint64_t e = sm->off[r]; e < sm->off[r + 1]; e++) reads[e] = (uint32_t)r;
+                if (rk_masses_accumulate_samples_host((uint32_t)t.nodes.size(), keep_at_most, m, rs, S, reads.size(), reads.data(), sm->sample.data(), sm->weight.data(),
+                                                      words.data(), n_threads) != RK_OK)
+                    throw std::runtime_error(std::string("rk_masses_accumulate_samples_host: ") + rk_last_error());
+                std::ofstream mf(masses_path, std::ios::binary);
+                if (!mf) throw std::runtime_error("cannot write " + masses_path);
+                mf << rkh::masses_samples_table(t, sm->names, words.data(), words.size());
+                return;
+            }
             std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);
             if (words.empty()) throw std::runtime_error("--masses: the tree has no nodes, or more than 65535");
             if (rk_masses_accumulate_host((uint32_t)t.nodes.size(), keep_at_most, m, rs, w, words.data(), n_threads) != RK_OK)
@@ -312,7 +368,19 @@ int main(int argc, char **argv) {
         // --masses-only: one profile-only call with the multiplicities as weights -- every chunk is summed on the device, the flags
         // alone come back -- then the table through the same writer
         auto place_masses_only = [&](rk_db *h, const rk_params *pp, const rkh::Tree &t, uint64_t m, const uint8_t *sq, const uint64_t *so, const uint32_t *w,
-                                     uint32_t *flags_out, rk_counters *c) {
+                                     uint32_t *flags_out, rk_counters *c, const rkh::SampleMembers *sm) {
+            if (sm) {  // --sample-sep: one per-sample call, the membership CSR in place of the weights
+                const uint32_t S = (uint32_t)sm->names.size();
+                std::vector<uint64_t> words((size_t)rk_masses_samples_words((uint32_t)t.nodes.size(), S), 0);
+                if (words.empty()) throw std::runtime_error("--masses-only --sample-sep: " + std::to_string(sm->names.size()) + " samples on this tree are beyond the limits of a sample mass buffer");
+                if (rk_place_batch_masses_samples(h, pp, translate ? RK_STEP_TRANSLATED : strand, m, sq, so, S, sm->off.data(), sm->sample.data(), sm->weight.data(),
+                                                  words.data(), flags_out, c) != RK_OK)
+                    throw std::runtime_error(std::string("rk_place_batch_masses_samples: ") + rk_last_error());
+                std::ofstream mf(masses_only_path, std::ios::binary);
+                if (!mf) throw std::runtime_error("cannot write " + masses_only_path);
+                mf << rkh::masses_samples_table(t, sm->names, words.data(), words.size());
+                return;
+            }
             std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);
             if (words.empty()) throw std::runtime_error("--masses-only: the tree has no nodes, or more than 65535");
             if (rk_place_batch_masses(h, pp, translate ? RK_STEP_TRANSLATED : strand, m, sq, so, w, words.data(), flags_out, c) != RK_OK)
@@ -400,6 +468,11 @@ int main(int argc, char **argv) {
             rkh::RawArray<uint64_t> off;
             rkh::gather_unique(sc, dd, team, seq, off);
             const size_t n = dd.first_rec.size();
+            rkh::SampleMembers members;  // (--sample-sep only)
+            if (!sample_sep.empty())
+                members = rkh::sample_members(sc.recs.size(), n, [&](size_t r) { return std::make_pair((const char *)sc.recs[r].hdr, (size_t)sc.recs[r].hdr_len); },
+                                              dd.uniq_of_rec.data(), sample_sep[0]);
+            const rkh::SampleMembers *sm = sample_sep.empty() ? nullptr : &members;
             auto count_weights = [&](rkh::RawArray<uint32_t> &weight) {  // a unique read weighs the FASTA records it stands for
                 weight.alloc(n);
                 team.run([&](unsigned t, unsigned T) {
@@ -419,7 +492,7 @@ int main(int argc, char **argv) {
                 warm.join();
                 const double t3b = now();
                 rk_counters ct{};
-                place_masses_only(db, &p, tree, n, (const uint8_t *)seq.data(), off.data(), weight.data(), flags.data(), &ct);
+                place_masses_only(db, &p, tree, n, (const uint8_t *)seq.data(), off.data(), weight.data(), flags.data(), &ct, sm);
                 const double t4 = now();
                 fs::create_directories(log_dir);
                 {
@@ -485,7 +558,7 @@ int main(int argc, char **argv) {
             if (!masses_path.empty()) {
                 rkh::RawArray<uint32_t> weight;
                 count_weights(weight);
-                write_masses(tree, n, &res, weight.data(), team.size());
+                write_masses(tree, n, &res, weight.data(), team.size(), sm);
             }
             const double t6 = now();
             std::cerr << n << " unique reads, " << ws.placed << " placed -> " << out << "\n";
@@ -513,11 +586,16 @@ int main(int argc, char **argv) {
         for (size_t i = 0; i < n; i++) off[i + 1] = off[i] + records[dd.first_rec[i]].seq.size();
         seq.reserve(off[n]);
         for (size_t i = 0; i < n; i++) seq += records[dd.first_rec[i]].seq;
+        rkh::SampleMembers members;  // (--sample-sep only)
+        if (!sample_sep.empty())
+            members = rkh::sample_members(records.size(), n, [&](size_t r) { return std::make_pair(records[r].header.data(), records[r].header.size()); },
+                                          dd.uniq_of_rec.data(), sample_sep[0]);
+        const rkh::SampleMembers *sm = sample_sep.empty() ? nullptr : &members;
         if (masses_only) {
             std::vector<uint32_t> weight(n), flags(n, 0);
             for (size_t i = 0; i < n; i++) weight[i] = (uint32_t)names[i].size();
             rk_counters ct{};
-            place_masses_only(db, &p, tree, n, (const uint8_t *)seq.data(), off.data(), weight.data(), flags.data(), &ct);
+            place_masses_only(db, &p, tree, n, (const uint8_t *)seq.data(), off.data(), weight.data(), flags.data(), &ct, sm);
             fs::create_directories(log_dir);
             std::ofstream nf(log_dir / notplaced_name, std::ios::binary);
             if (!nf) throw std::runtime_error("cannot write the notplaced log under " + log_dir.string());
@@ -563,7 +641,7 @@ int main(int argc, char **argv) {
         if (!masses_path.empty()) {
             std::vector<uint32_t> weight(n);
             for (size_t i = 0; i < n; i++) weight[i] = (uint32_t)names[i].size();
-            write_masses(tree, n, &res, weight.data(), 1);
+            write_masses(tree, n, &res, weight.data(), 1, sm);
         }
         std::cerr << n << " unique reads, " << pl.size() << " placed -> " << out << "\n";
         if (timing) std::cout << "{\"reads\": " << records.size() << ", \"unique\": " << n << ", \"db_s\": " << (t_db - t_start) << ", \"fasta_to_jplace_s\": " << (now() - tc0) << ", \"classic\": true}" << std::endl;

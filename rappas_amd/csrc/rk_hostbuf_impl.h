@@ -158,16 +158,17 @@ static rk_result result_slice(const rk_result &r, uint64_t r0, uint32_t K) {
 struct rk_workspace {
     GrowBuf ascii, off, packed, lens, flags;
     GrowBuf weights;              // the chunk's weights (masses sink)
+    GrowBuf members;              // the chunk's membership entries (masses sink, per-sample form): sample | read - lo | weight
     ResultBufs<GrowBuf> res;      // (with the frame bytes: rk_place_batch_translated)
     GrowBuf strands, translated;  // the workspaces of rk_place_packed_device_strands / _translated for a chunk
-    PinBuf h_ascii, h_off, h_packed;
+    PinBuf h_ascii, h_off, h_packed, h_members;
     ResultBufs<PinBuf> h_res;
     bool pending = false;         // results of the last chunk are still in the staging buffers
     uint64_t pend_r0 = 0, pend_n = 0;
     hipStream_t stream = nullptr;
     void release() {
-        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &weights, &strands, &translated}) b->release();
-        for (PinBuf *b : {&h_ascii, &h_off, &h_packed}) b->release();
+        for (GrowBuf *b : {&ascii, &off, &packed, &lens, &flags, &weights, &members, &strands, &translated}) b->release();
+        for (PinBuf *b : {&h_ascii, &h_off, &h_packed, &h_members}) b->release();
         res.release();
         h_res.release();
         if (stream) (void)hipStreamDestroy(stream);

@@ -138,6 +138,13 @@ struct HostStep {
 struct HostSink {
     uint64_t *masses = nullptr;         // the caller's buffer: the device buffer's words are ADDED into it after the last chunk
     const uint32_t *weights = nullptr;  // [n] or NULL
+    // The membership form (rk_place_batch*_masses_samples; n_samples != 0, weights unused): `masses` is a sample mass buffer, a chunk
+    // [lo, hi) stages the entries member_off[lo] .. member_off[hi] as (read - lo, sample, weight) and hands them to
+    // rk_masses_accumulate_samples_device.  member_off NULL: one entry per read, entry r is read r.
+    uint32_t n_samples = 0;
+    const uint64_t *member_off = nullptr;     // [n + 1] or NULL
+    const uint32_t *member_sample = nullptr;  // [entries]
+    const uint32_t *member_weight = nullptr;  // [entries] or NULL
 };
 
 // the chunk's read limit: the one place that reads the developer knob
@@ -264,7 +271,30 @@ class HostPath {
   private:
     // The masses sink's device buffer, one per handle: zeroed here, and the zeroing waited for, so that it lies before every chunk's
     // accumulate on all four streams (which then add into it side by side: integer atomics).
-    size_t masses_bytes() const { return (size_t)rk_masses_words(db_->info.n_branches) * 8; }
+    size_t masses_bytes() const {
+        return (size_t)(sink_.n_samples ? rk_masses_samples_words(db_->info.n_branches, sink_.n_samples) : rk_masses_words(db_->info.n_branches)) * 8;
+    }
+    // The chunk's membership entries: sample | read - lo | weight, three arrays of m words in one page-locked block (filled here, on
+    // the submit thread: 12 bytes an entry), one copy to the device, then the per-sample sums on the chunk's stream.
+    int masses_samples(const Plan &c, rk_workspace &w, const rk_result &dres) {
+        const uint64_t e0 = sink_.member_off ? sink_.member_off[c.r0] : c.r0, e1 = sink_.member_off ? sink_.member_off[c.r1] : c.r1, m = e1 - e0;
+        if (m == 0) return RK_OK;
+        if (m >= (1ull << 32)) return fail(RK_ERR_INVALID, "%s: %llu membership entries in one chunk of reads, at most 2^32 - 1", who_, (unsigned long long)m);
+        const bool reads = sink_.member_off != nullptr, wts = sink_.member_weight != nullptr;
+        const size_t bytes = (size_t)m * 4 * (1 + (reads ? 1 : 0) + (wts ? 1 : 0));
+        RK_TRY(w.h_members.reserve(bytes, node_, device_));
+        RK_TRY(w.members.reserve(bytes));
+        uint32_t *hs = w.h_members.as<uint32_t>(), *hr = hs + m, *hw = hr + (reads ? m : 0);
+        memcpy(hs, sink_.member_sample + e0, m * 4);
+        if (wts) memcpy(hw, sink_.member_weight + e0, m * 4);
+        if (reads)
+            for (uint64_t r = c.r0; r < c.r1; r++)
+                for (uint64_t e = sink_.member_off[r]; e < sink_.member_off[r + 1]; e++) hr[e - e0] = (uint32_t)(r - c.r0);
+        RK_TRY(h2d(w.members.p, hs, bytes, w.stream));
+        const uint32_t *ds = w.members.as<uint32_t>(), *dr = ds + m, *dw = dr + (reads ? m : 0);
+        return rk_masses_accumulate_samples_device(db_, K_, c.n, &dres, sink_.n_samples, m, reads ? dr : nullptr, ds, wts ? dw : nullptr,
+                                                   db_->d_masses.as<uint64_t>(), w.stream);
+    }
     int masses_begin() {
         hipStream_t s = db_->ws[0].stream;
         RK_TRY(db_->d_masses.reserve(masses_bytes()));
@@ -398,7 +428,8 @@ class HostPath {
         if (sink_.masses) {
             // summed where it lies; the flags alone come back (a result set whose other arrays are null: download skips them)
             const rk_result dres = w.res.view();
-            RK_TRY(rk_masses_accumulate_device(db_, K_, c.n, &dres, sink_.weights ? w.weights.as<uint32_t>() : nullptr, db_->d_masses.as<uint64_t>(), w.stream));
+            if (sink_.n_samples) RK_TRY(masses_samples(c, w, dres));
+            else RK_TRY(rk_masses_accumulate_device(db_, K_, c.n, &dres, sink_.weights ? w.weights.as<uint32_t>() : nullptr, db_->d_masses.as<uint64_t>(), w.stream));
             const rk_result staged{nullptr, nullptr, nullptr, nullptr, w.h_res.flags.as<uint32_t>()};
             RK_TRY(hip_rc(out_pinned_ ? w.res.download(w.stream, *out_, nullptr, c.r0, c.n, K_) : w.res.download(w.stream, staged, nullptr, 0, c.n, K_),
                           "hipMemcpyAsync (device to host)"));
@@ -713,8 +744,32 @@ extern "C" int rk_place_batch_translated(rk_db *db, const rk_params *p, uint64_t
 
 // Profile-only placement: the pipeline of the entry point that `step` names with the masses sink behind it (HostSink).  The tests of
 // the arguments come first and in the header's order; until they have passed nothing is launched and nothing is written.
+static HostSink weights_sink(const uint32_t *weights) {
+    HostSink s;
+    s.weights = weights;
+    return s;
+}
+static HostSink members_sink(uint32_t n_samples, const uint64_t *member_off, const uint32_t *member_sample, const uint32_t *member_weight) {
+    HostSink s;
+    s.n_samples = n_samples; s.member_off = member_off; s.member_sample = member_sample; s.member_weight = member_weight;
+    return s;
+}
+// the membership arguments of a host call, in one pass up front
+static int check_members(const char *who, uint32_t B, uint64_t n_reads, const HostSink &sink) {
+    if (!rk_masses_samples_words(B, sink.n_samples))
+        return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches: 1..65535 samples and at most 2^29 words (n_samples * (2 * n_branches + 4) + 1)", who, sink.n_samples, B);
+    if (sink.member_off) {
+        if (sink.member_off[0] != 0) return fail(RK_ERR_INVALID, "%s: member_off[0]=%llu must be 0", who, (unsigned long long)sink.member_off[0]);
+        for (uint64_t r = 0; r < n_reads; r++)
+            if (sink.member_off[r + 1] < sink.member_off[r]) return fail(RK_ERR_INVALID, "%s: member_off not monotone at read %llu", who, (unsigned long long)r);
+    }
+    const uint64_t entries = sink.member_off ? sink.member_off[n_reads] : n_reads;
+    if (entries && !sink.member_sample) return fail(RK_ERR_INVALID, "%s: null member_sample", who);
+    return RK_OK;
+}
+
 static int place_host_masses(const char *who, rk_db *db, const rk_params *p, uint32_t step_code, uint64_t n_reads, const HostInput &in,
-                             const char *reads_missing, const uint32_t *weights, uint64_t *masses, uint32_t *flags_out, rk_counters *counters) {
+                             const char *reads_missing, HostSink sink, uint64_t *masses, uint32_t *flags_out, rk_counters *counters) {
     RK_TRY(check_params(p));  // (what needs no handle first: a machine without a GPU can test it)
     if (step_code > RK_STEP_TRANSLATED) return fail(RK_ERR_INVALID, "%s: step=%u (0 forward, 1 reverse, 2 both, 3 translated)", who, step_code);
     if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
@@ -729,8 +784,8 @@ static int place_host_masses(const char *who, rk_db *db, const rk_params *p, uin
     }
     if (reads_missing) return fail(RK_ERR_INVALID, "%s: %s", who, reads_missing);
     rk_result out{nullptr, nullptr, nullptr, nullptr, flags_out};
-    HostSink sink;
-    sink.masses = masses; sink.weights = weights;
+    if (sink.n_samples) RK_TRY(check_members(who, db->info.n_branches, n_reads, sink));
+    sink.masses = masses;
     return place_host(db, p, n_reads, in, &out, counters, who, step, sink);
 }
 
@@ -740,7 +795,7 @@ extern "C" int rk_place_batch_masses(rk_db *db, const rk_params *p, uint32_t ste
     HostInput in;
     in.ascii = seq_ascii; in.off = seq_off;
     RK_GUARD_BEGIN
-    return place_host_masses(who, db, p, step, n_reads, in, n_reads && (!seq_ascii || !seq_off) ? "null reads" : nullptr, weights, masses, flags_out, counters);
+    return place_host_masses(who, db, p, step, n_reads, in, n_reads && (!seq_ascii || !seq_off) ? "null reads" : nullptr, weights_sink(weights), masses, flags_out, counters);
     RK_GUARD_END(who)
 }
 
@@ -758,7 +813,42 @@ extern "C" int rk_place_batch_packed_masses(rk_db *db, const rk_params *p, uint6
     HostInput in;
     in.ascii = seq_ascii; in.off = seq_off; in.packed = packed; in.wpr = words_per_read; in.lens = lens; in.fixed_len = fixed_len; in.flags = flags;
     RK_GUARD_BEGIN
-    return place_host_masses(who, db, p, RK_STRAND_FORWARD, n_reads, in, nullptr, weights, masses, flags_out, counters);
+    return place_host_masses(who, db, p, RK_STRAND_FORWARD, n_reads, in, nullptr, weights_sink(weights), masses, flags_out, counters);
+    RK_GUARD_END(who)
+}
+
+// Per-sample profile-only placement: the same pipelines with the membership form of the masses sink
+extern "C" int rk_place_batch_masses_samples(rk_db *db, const rk_params *p, uint32_t step, uint64_t n_reads, const uint8_t *seq_ascii,
+                                             const uint64_t *seq_off, uint32_t n_samples, const uint64_t *member_off, const uint32_t *member_sample,
+                                             const uint32_t *member_weight, uint64_t *masses, uint32_t *flags_out, rk_counters *counters) {
+    const char *who = "rk_place_batch_masses_samples";
+    if (n_samples == 0) return fail(RK_ERR_INVALID, "%s: n_samples=0 (1..65535)", who);
+    HostInput in;
+    in.ascii = seq_ascii; in.off = seq_off;
+    RK_GUARD_BEGIN
+    return place_host_masses(who, db, p, step, n_reads, in, n_reads && (!seq_ascii || !seq_off) ? "null reads" : nullptr,
+                             members_sink(n_samples, member_off, member_sample, member_weight), masses, flags_out, counters);
+    RK_GUARD_END(who)
+}
+
+extern "C" int rk_place_batch_packed_masses_samples(rk_db *db, const rk_params *p, uint64_t n_reads, const uint32_t *packed, uint32_t words_per_read,
+                                                    const uint32_t *lens, uint32_t fixed_len, const uint32_t *flags, const uint8_t *seq_ascii,
+                                                    const uint64_t *seq_off, uint32_t n_samples, const uint64_t *member_off,
+                                                    const uint32_t *member_sample, const uint32_t *member_weight, uint64_t *masses,
+                                                    uint32_t *flags_out, rk_counters *counters) {
+    const char *who = "rk_place_batch_packed_masses_samples";
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    RK_TRY(check_params(p));
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (n_samples == 0) return fail(RK_ERR_INVALID, "%s: n_samples=0 (1..65535)", who);
+    if (n_reads && (!packed || words_per_read == 0)) return fail(RK_ERR_INVALID, "%s: null packed reads", who);
+    RK_TRY(check_fixed_len(who, lens, fixed_len, db->info.bits_per_symbol, words_per_read));
+    if ((seq_ascii == nullptr) != (seq_off == nullptr)) return fail(RK_ERR_INVALID, "%s: seq_ascii and seq_off go together", who);
+    HostInput in;
+    in.ascii = seq_ascii; in.off = seq_off; in.packed = packed; in.wpr = words_per_read; in.lens = lens; in.fixed_len = fixed_len; in.flags = flags;
+    RK_GUARD_BEGIN
+    return place_host_masses(who, db, p, RK_STRAND_FORWARD, n_reads, in, nullptr, members_sink(n_samples, member_off, member_sample, member_weight), masses,
+                             flags_out, counters);
     RK_GUARD_END(who)
 }
 

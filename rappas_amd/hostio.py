@@ -349,6 +349,52 @@ def masses_table(tree, masses):
     return "".join(out)
 
 
+def sample_name(header, sep):
+    """`--sample-sep C`: a record's sample is its header up to the first C; a header without C is an error that names it"""
+    cut = header.find(sep)
+    if cut < 0:
+        raise ValueError(f"--sample-sep: the header '{header}' does not contain the separator '{sep}'")
+    return header[:cut]
+
+
+def sample_members(records, unique, sep):
+    """the per-sample membership of the unique reads -- the twin of rkh::sample_members (rappas_amd/csrc/host/rk_hostio.hpp).
+    -> (names, member_off u64 [n + 1], member_sample u32, member_weight u32): the samples in byte-wise order of their names; unique
+    read i owns the entries member_off[i] .. member_off[i + 1], one per distinct sample among its records, the number of those records
+    as its weight, in sample order -- the CSR rk_place_batch_masses_samples takes."""
+    rec_names = [sample_name(header, sep) for header, _ in records]
+    names = sorted(set(rec_names), key=lambda s: s.encode("utf-8", "surrogatepass"))
+    rank = {s: i for i, s in enumerate(names)}
+    index = {hashlib.md5(seq.replace("-", "").encode()).digest(): i for i, (_, seq) in enumerate(unique)}
+    per_read = [{} for _ in unique]
+    for (_, seq), s in zip(records, rec_names):
+        d = per_read[index[hashlib.md5(seq.replace("-", "").encode()).digest()]]
+        d[rank[s]] = d.get(rank[s], 0) + 1
+    off, sample, weight = [0], [], []
+    for d in per_read:
+        for s in sorted(d):
+            sample.append(s)
+            weight.append(d[s])
+        off.append(len(sample))
+    return names, np.array(off, np.uint64), np.array(sample, np.uint32), np.array(weight, np.uint32)
+
+
+def masses_samples_table(tree, names, masses):
+    """the text `--masses FILE` / `--masses-only FILE` write with `--sample-sep`: for each sample in order a line
+    `#sample<TAB>name<TAB>index` and masses_table of its words, then a line `#skipped_entries<TAB>n` (the last word of the sample mass
+    buffer).  The twin of rkh::masses_samples_table, byte-identical."""
+    W = 2 * len(tree.nodes) + 4
+    m = np.asarray(masses, dtype=np.uint64).reshape(-1)
+    if len(m) != len(names) * W + 1:
+        raise ValueError(f"masses_samples_table: the buffer holds {len(m)} words, {len(names)} samples on the tree's {len(tree.nodes)} nodes need {len(names) * W + 1}")
+    out = []
+    for s, name in enumerate(names):
+        out.append(f"#sample\t{name}\t{s}\n")
+        out.append(masses_table(tree, m[s * W:(s + 1) * W]))
+    out.append(f"#skipped_entries\t{int(m[-1])}\n")
+    return "".join(out)
+
+
 def _fmt12(x):
     """NumberFormat.getNumberInstance(Locale.UK) with exactly 12 fraction digits (NewickWriter.java:61-64): grouping commas,
     HALF_EVEN on the exact binary value."""

@@ -163,6 +163,56 @@ def accumulate_masses_host(n_branches, placements, weights=None, masses=None, th
     return masses
 
 
+def masses_samples_words(n_branches, n_samples):
+    """rk_masses_samples_words: 64-bit words of a sample mass buffer, n_samples * masses_words(n_branches) + 1 (0 on a bad argument:
+    n_branches or n_samples outside 1..65535, or more than 2^29 words)"""
+    return int(_lib.load().rk_masses_samples_words(n_branches, n_samples))
+
+
+def _u32_list(a, n, what):
+    """None, or `a` as a contiguous uint32 array of n words"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if a.shape != (n,):
+        raise ValueError(f"{what} must hold {n} uint32 words")
+    return a
+
+
+def _samples_buffer(n_branches, n_samples, masses):
+    words = masses_samples_words(n_branches, n_samples)
+    if not words:
+        raise ValueError(f"n_samples={n_samples} on {n_branches} branches: both in 1..65535 and at most 2^29 words")
+    if masses is None:
+        return np.zeros(words, np.uint64)
+    if masses.dtype != np.uint64 or masses.shape != (words,) or not masses.flags.c_contiguous:
+        raise ValueError(f"masses must be a contiguous uint64 array of {words} words")
+    return masses
+
+
+def accumulate_masses_samples_host(n_branches, placements, n_samples, member_sample, member_read=None, member_weight=None, masses=None, threads=0):
+    """rk_masses_accumulate_samples_host (no GPU): one mass buffer per sample from the membership entries (member_read[i],
+    member_sample[i], member_weight[i]) over a result set, ADDED into `masses`, a uint64 array of masses_samples_words(n_branches,
+    n_samples) -- n_samples buffers of masses_words(n_branches) words and the count of entries skipped for a sample or read out of
+    range -- made and zeroed when None.  member_read None: entry i is read i; member_weight None: 1."""
+    lib = _lib.load()
+    masses = _samples_buffer(n_branches, n_samples, masses)
+    n_rows = np.ascontiguousarray(placements.n_rows, dtype=np.uint8)
+    branch = np.ascontiguousarray(placements.branch, dtype=np.uint16)
+    lwr = np.ascontiguousarray(placements.lwr, dtype=np.float64)
+    n = n_rows.shape[0]
+    K = branch.shape[1] if branch.ndim == 2 else (branch.size // n if n else 1)
+    if branch.size != n * K or lwr.size != n * K:
+        raise ValueError("branch and lwr must hold n_reads x K rows")
+    member_sample = np.ascontiguousarray(member_sample, dtype=np.uint32)
+    m = member_sample.shape[0]
+    member_read, member_weight = _u32_list(member_read, m, "member_read"), _u32_list(member_weight, m, "member_weight")
+    res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
+    _lib.check(lib.rk_masses_accumulate_samples_host(n_branches, K, n, C.byref(res), n_samples, m, None if member_read is None else _ptr(member_read),
+                                                     _ptr(member_sample), None if member_weight is None else _ptr(member_weight), _ptr(masses), threads))
+    return masses
+
+
 def host_alloc(shape, dtype):
     """numpy array in page-locked host memory (rk_host_alloc): buffers the DMA reads / writes directly, no staging copies in
     rk_place_batch / rk_place_batch_packed.  The memory lives until the process ends (tests and the bench allocate a handful)."""
@@ -453,6 +503,56 @@ class PlacementProcess:
                                                           None if weights is None else _ptr(weights), _ptr(masses), _ptr(flags_out), C.byref(ct)))
         return masses, flags_out, _counters(ct)
 
+    def _members_args(self, n, n_samples, member_off, member_sample, member_weight, masses, flags_out):
+        """(member_off u64 [n + 1] or None, member_sample u32, member_weight u32 or None, masses, flags) of a per-sample call"""
+        masses = _samples_buffer(self.db.info.n_branches, n_samples, masses)
+        if member_off is not None:
+            member_off = np.ascontiguousarray(member_off, dtype=np.uint64)
+            if member_off.shape != (n + 1,):
+                raise ValueError("member_off must hold n_reads + 1 uint64 words")
+        m = int(member_off[-1]) if member_off is not None else n
+        member_sample, member_weight = _u32_list(member_sample, m, "member_sample"), _u32_list(member_weight, m, "member_weight")
+        if flags_out is None:
+            flags_out = np.zeros(n, np.uint32)
+        elif flags_out.dtype != np.uint32 or flags_out.shape != (n,) or not flags_out.flags.c_contiguous:
+            raise ValueError("flags_out must be a contiguous uint32 array with one word per read")
+        return member_off, member_sample, member_weight, masses, flags_out
+
+    def processQueriesMassesSamples(self, seq, seq_off, n_samples, member_sample, member_off=None, member_weight=None, masses=None, strand="forward",
+                                    translate=False, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True, treatAmbiguitiesWithMax=False, flags_out=None):
+        """rk_place_batch_masses_samples: processQueriesMasses with one mass buffer per sample.  Read r owns the entries member_off[r] ..
+        member_off[r + 1] of member_sample / member_weight (member_off None: one entry per read; member_weight None: 1).  Returns
+        (masses uint64 [masses_samples_words(B, n_samples)], flags uint32 [n], counters): `masses` (made and zeroed when None) has
+        received what accumulate_masses_samples_host would add for that call's result set with the entries expanded."""
+        seq, seq_off, n = _reads(seq, seq_off)
+        member_off, member_sample, member_weight, masses, flags_out = self._members_args(n, n_samples, member_off, member_sample, member_weight, masses, flags_out)
+        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
+        ct = rk_counters()
+        step = _lib.RK_STEP_TRANSLATED if translate else _strand(strand)
+        _lib.check(self._lib.rk_place_batch_masses_samples(self.db.handle, C.byref(p), step, n, _ptr(seq), _ptr(seq_off), n_samples,
+                                                           None if member_off is None else _ptr(member_off), _ptr(member_sample),
+                                                           None if member_weight is None else _ptr(member_weight), _ptr(masses), _ptr(flags_out), C.byref(ct)))
+        return masses, flags_out, _counters(ct)
+
+    def processQueriesPackedMassesSamples(self, packed, n_samples, member_sample, member_off=None, member_weight=None, lens=None, fixed_len=0, flags=None,
+                                          seq=None, seq_off=None, masses=None, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
+                                          treatAmbiguitiesWithMax=False, flags_out=None):
+        """rk_place_batch_packed_masses_samples: processQueriesMassesSamples for reads already packed on the host (the arguments of
+        processQueriesPacked); the same (masses, flags, counters)."""
+        packed = np.ascontiguousarray(packed, dtype=np.uint32)
+        n, wpr = packed.shape
+        member_off, member_sample, member_weight, masses, flags_out = self._members_args(n, n_samples, member_off, member_sample, member_weight, masses, flags_out)
+        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
+        ct = rk_counters()
+        keep = [np.ascontiguousarray(a, dtype=dt) if a is not None else None
+                for a, dt in ((lens, np.uint32), (flags, np.uint32), (seq, np.uint8), (seq_off, np.uint64))]
+        ptrs = [None if a is None else _ptr(a) for a in keep]
+        _lib.check(self._lib.rk_place_batch_packed_masses_samples(self.db.handle, C.byref(p), n, _ptr(packed), wpr, ptrs[0], fixed_len, ptrs[1], ptrs[2], ptrs[3],
+                                                                  n_samples, None if member_off is None else _ptr(member_off), _ptr(member_sample),
+                                                                  None if member_weight is None else _ptr(member_weight), _ptr(masses), _ptr(flags_out),
+                                                                  C.byref(ct)))
+        return masses, flags_out, _counters(ct)
+
     def processQueriesMulti(self, dbs, seq, seq_off, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
                             treatAmbiguitiesWithMax=False, out=None):
         """processQueries over several device handles of the same database from this one process
@@ -543,6 +643,36 @@ class PlacementProcess:
         res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), None, out["lwr"].data_ptr(), None)
         _lib.check(self._lib.rk_masses_accumulate_device(self.db.handle, K, n, C.byref(res), None if weights is None else weights.data_ptr(),
                                                          masses.data_ptr(), C.c_void_p(st)))
+        return masses
+
+    def accumulate_masses_samples(self, out, n_samples, member_sample, member_read=None, member_weight=None, masses=None, stream=None):
+        """rk_masses_accumulate_samples_device: one mass buffer per sample from the membership entries (int32 tensors read as uint32, on
+        the device of `out`) over `out` -- the dict of device tensors place_packed / place_translated return -- ADDED into `masses`, an
+        int64 tensor of masses_samples_words(n_branches, n_samples) words on the same device, allocated and zeroed when None.
+        member_read None: entry i is read i; member_weight None: 1.  Asynchronous on the stream."""
+        import torch
+        n, K = out["branch"].shape
+        dev = out["branch"].device
+        words = masses_samples_words(self.db.info.n_branches, n_samples)
+        if not words:
+            raise ValueError(f"n_samples={n_samples} on {self.db.info.n_branches} branches: 1..65535 and at most 2^29 words")
+        st = _stream(dev, stream)
+        if masses is None:
+            masses = torch.empty(words, dtype=torch.int64, device=dev)
+            if stream is not None:
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                    masses.zero_()
+            else:
+                masses.zero_()
+        elif masses.dtype != torch.int64 or masses.numel() != words or not masses.is_contiguous() or masses.device != dev:
+            raise ValueError(f"masses must be a contiguous int64 tensor of {words} words on {dev}")
+        m = member_sample.numel()
+        for t, what in ((member_sample, "member_sample"), (member_read, "member_read"), (member_weight, "member_weight")):
+            if t is not None and (t.dtype != torch.int32 or t.numel() != m or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"{what} must be a contiguous int32 tensor of {m} words on {dev}")
+        res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), None, out["lwr"].data_ptr(), None)
+        _lib.check(self._lib.rk_masses_accumulate_samples_device(self.db.handle, K, n, C.byref(res), n_samples, m, _dp(member_read), member_sample.data_ptr(),
+                                                                 _dp(member_weight), masses.data_ptr(), C.c_void_p(st)))
         return masses
 
     def translate_packed(self, dna, frame, fixed_len=0, lens=None, aa_words=None, stream=None):

@@ -17,17 +17,19 @@ from ..placement import PhyloKmerDB, PlacementProcess
 TRANSLATE_WITH_STRAND = "--translate places every read in all six reading frames, both strands included: it cannot be combined with --strand rev | both"
 MASSES_ONLY_WITH_OUT = "--masses-only writes no jplace (the placements never reach the host): it cannot be combined with --out"
 MASSES_ONLY_WITH_MASSES = "--masses-only writes the table --masses writes, without placing into a jplace: give one of the two"
+SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
 
 
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
-               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False):
+               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
     reversed_<query>.tsv).  translate: DNA reads on an amino-acid database, six reading frames translated on the device and the best
     one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both".  masses: res.masses is
-    then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for)."""
+    then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for);
+    with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table)."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
@@ -36,6 +38,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
             raise ValueError(TRANSLATE_NEEDS_AA)
         records = hostio.read_fasta(fasta_text)
         unique, names = hostio.dedup_reads(records)
+        members = hostio.sample_members(records, unique, sample_sep) if masses and sample_sep is not None else None
         seq, off = hostio.pack_batch([s for _, s in unique])
         if translate:
             res = PlacementProcess(db, ns_bound).processQueriesTranslated(seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor)
@@ -50,7 +53,13 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     res.reversed = hostio.reversed_log(records, unique, res.flags) if strand != "fwd" else None
     res.frames = hostio.frames_log(records, unique, res.frame) if translate else None
     res.masses = None
-    if masses:
+    if members is not None:
+        from ..placement import accumulate_masses_samples_host
+        sample_names, m_off, m_sample, m_weight = members
+        m_read = np.repeat(np.arange(len(unique), dtype=np.uint32), np.diff(m_off.astype(np.int64)))
+        words = accumulate_masses_samples_host(len(tree.nodes), res, len(sample_names), m_sample, member_read=m_read, member_weight=m_weight)
+        res.masses = hostio.masses_samples_table(tree, sample_names, words)
+    elif masses:
         from ..placement import accumulate_masses_host
         weights = np.array([len(nm) for nm in names], dtype=np.uint32)
         res.masses = hostio.masses_table(tree, accumulate_masses_host(len(tree.nodes), res, weights))
@@ -58,11 +67,12 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
 
 
 def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), device=0, union=False,
-                     dbimage=None, save_dbimage=None, strand="fwd", translate=False):
+                     dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None):
     """`--masses-only FILE`: scan, dedup and gather as place_file, then ONE profile-only call (processQueriesMasses) with the
     multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
     table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
-    No jplace and no frames log: the rows and the frame bytes never reach the host."""
+    No jplace and no frames log: the rows and the frame bytes never reach the host.  With sample_sep (one character) the one call is
+    processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample."""
     from types import SimpleNamespace
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
@@ -74,12 +84,19 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
         unique, names = hostio.dedup_reads(records)
         seq, off = hostio.pack_batch([s for _, s in unique])
         weights = np.array([len(nm) for nm in names], dtype=np.uint32)
-        words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(
-            seq, off, weights=weights, strand=strand, translate=translate, keepAtMost=keep_at_most, keepFactor=keep_factor,
-            treatAmbiguities=(amb != "skip"), treatAmbiguitiesWithMax=(amb == "max"))
+        common = dict(strand=strand, translate=translate, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
+                      treatAmbiguitiesWithMax=(amb == "max"))
+        if sample_sep is not None:
+            sample_names, m_off, m_sample, m_weight = hostio.sample_members(records, unique, sample_sep)
+            words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMassesSamples(
+                seq, off, len(sample_names), m_sample, member_off=m_off, member_weight=m_weight, **common)
+            table = hostio.masses_samples_table(tree, sample_names, words)
+        else:
+            words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(seq, off, weights=weights, **common)
+            table = hostio.masses_table(tree, words)
     finally:
         db.close()
-    return SimpleNamespace(masses=hostio.masses_table(tree, words), notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
+    return SimpleNamespace(masses=table, notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
                            reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters)
 
 
@@ -132,6 +149,11 @@ def main(argv=None):
                          "reversed) log -- the placements are summed on the device and never reach the host, so no jplace is written, "
                          "--out may not be given, and with --translate the frames log is not written (the frame bytes do not come back); "
                          "not with --masses")
+    ap.add_argument("--sample-sep", default=None, metavar="C",
+                    help="with --masses or --masses-only: one table per sample in FILE.  A record's sample is its header up to the first "
+                         "character C (a header without C is an error), samples are numbered in byte-wise order of their names, and a read "
+                         "counts in every sample once per record of that sample; FILE holds, for each sample, a line "
+                         "#sample<TAB>name<TAB>index and its table, and a last line #skipped_entries<TAB>n")
     ap.add_argument("--timing", action="store_true", help="--masses-only: one JSON line with the run's wall-clock times on stdout")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
@@ -143,6 +165,10 @@ def main(argv=None):
         ap.error(MASSES_ONLY_WITH_MASSES)
     if a.masses_only is not None and a.out is not None:
         ap.error(MASSES_ONLY_WITH_OUT)
+    if a.sample_sep is not None and len(a.sample_sep) != 1:
+        ap.error("--sample-sep takes one character")
+    if a.sample_sep is not None and a.masses is None and a.masses_only is None:
+        ap.error(SAMPLE_SEP_NEEDS_MASSES)
     if a.masses_only is None and a.out is None:
         ap.error("--out is required (or --masses-only FILE for a profile-only run)")
     db_text = None
@@ -157,11 +183,11 @@ def main(argv=None):
     try:
         doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
-                              translate=a.translate, masses=a.masses is not None)
+                              translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep)
     except ValueError as e:
-        if str(e) != TRANSLATE_NEEDS_AA:
+        if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
-        print("rappas_amd.tools.place: " + TRANSLATE_NEEDS_AA, file=sys.stderr)
+        print("rappas_amd.tools.place: " + str(e), file=sys.stderr)
         return 1
     with open(a.out, "w") as f:
         f.write(doc)
@@ -189,11 +215,11 @@ def _main_masses_only(a, db_text, fasta_text):
     t0 = time.perf_counter()
     try:
         res = masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.device, union=a.uniondb is not None,
-                               dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate)
+                               dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate, sample_sep=a.sample_sep)
     except ValueError as e:
-        if str(e) != TRANSLATE_NEEDS_AA:
+        if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
-        print("rappas_amd.tools.place: " + TRANSLATE_NEEDS_AA, file=sys.stderr)
+        print("rappas_amd.tools.place: " + str(e), file=sys.stderr)
         return 1
     t1 = time.perf_counter()
     with open(a.masses_only, "w") as f:
