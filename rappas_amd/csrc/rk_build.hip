@@ -607,7 +607,9 @@ static int build_db_impl(const rk_build_desc *d, rk_built_db *out) {
 
     // ---- node batches: explore -> sort -> max per key, folded into the running set of unique (key, best score) pairs ----
     // (one batch unless the tuple buffer of a single launch would pass ~2.7e8 slots: the sort is handed 32-bit item counts)
-    const unsigned blocks = (unsigned)prop.multiProcessorCount * 3;  // persistent: 12 waves per CU (LDS: 10.5 KB per wave)
+    unsigned blocks = (unsigned)prop.multiProcessorCount * 3;  // persistent: 12 waves per CU (LDS: 10.5 KB per wave)
+    // developer / test knob: a grid of one block makes every lane take many explorers and every wave turn over many chunks
+    if (const char *e = rk_knob("RK_BUILD_BLOCKS")) blocks = (unsigned)std::min(std::max(atoi(e), 1), 1 << 16);
     const u64 chunk_slack = (u64)blocks * BUILD_WAVES_PER_BLOCK * TUPLE_CHUNK;  // every wave may leave one chunk half empty
     // slots one batch may fill: bounded by the 32-bit item counts of the sort and by device memory (12 bytes per slot, twice for
     // the sort's double buffers, plus its scratch) -- with 288 GB of HBM that is normally the whole input in one batch
@@ -650,8 +652,9 @@ static int build_db_impl(const rk_build_desc *d, rk_built_db *out) {
             int inl = 3;
             if (const char *e = rk_knob("RK_BUILD_INLINE_LEVELS")) inl = atoi(e);  // developer knob
             const dim3 grid(blocks), block(64 * BUILD_WAVES_PER_BLOCK);
-            // whole site rows in registers for the two alphabets RAPPAS has (4 / 20 states); anything else: per-visit loads
-            const int vec = rk_knob("RK_BUILD_NO_VEC") ? 0 : (d->n_states == 4 ? 4 : (d->n_states == 20 ? 20 : 0));
+            // whole site rows in registers for the two alphabets RAPPAS has at their full width (4 / 20 states); anything else:
+            // per-visit loads.  The four-state tail writes 2-bit letters: an amino-acid table cut to four ranked states is not its case.
+            const int vec = rk_knob("RK_BUILD_NO_VEC") ? 0 : (d->alphabet == RK_ALPHABET_DNA && d->n_states == 4 ? 4 : (d->n_states == 20 ? 20 : 0));
 #define RK_LAUNCH_EXPLORE(I)                                                                                \
     do {                                                                                                    \
         if (a.do_gap) {                                                                                     \

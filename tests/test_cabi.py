@@ -302,7 +302,7 @@ def test_product_library_reads_no_environment_variable():
     environment to the libraries it loads"""
     product = open(ra.build.ENGINE_SO, "rb").read()
     dev = open(ra.build.DEV_SO, "rb").read()
-    for knob in (b"RK_TEST_FAIL_SHARD", b"RK_WINDOW_ALWAYS", b"RK_WG_PASSES", b"RK_NO_WINDOW", b"RK_BUILD_BATCH_NODES", b"RK_CHUNK_READS"):
+    for knob in (b"RK_TEST_FAIL_SHARD", b"RK_WINDOW_ALWAYS", b"RK_WG_PASSES", b"RK_NO_WINDOW", b"RK_BUILD_BATCH_NODES", b"RK_BUILD_BLOCKS", b"RK_CHUNK_READS"):
         assert knob not in product, knob
         assert knob in dev, knob
     # (the library's one remaining getenv reference is rocPRIM's own ROCPRIM_USE_ATOMIC_BLOCK_ID, in rocprim/device/detail/ordered_block_id.hpp)
