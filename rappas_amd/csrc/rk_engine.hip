@@ -5,8 +5,6 @@
 #include "rk_internal.h"
 #include "rk_pack_host.h"
 #include "rk_translate_host.h"
-#include "rk_masses_host.h"
-#include "rk_masses_samples_host.h"
 #include "rk_plan.h"
 
 #include <cmath>
@@ -1859,215 +1857,7 @@ extern "C" int rk_merge_strands_device(rk_db *db, uint32_t keep_at_most, uint64_
     return launch_merge(db, keep_at_most, n_reads, d_fwd, nullptr, d_rev, RK_FLAG_REVERSE, 0, (hipStream_t)stream);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Edge masses: the per-branch LWR sums of a result set, added into a caller-owned buffer of 2 * B + 4 words.  Works on
-// the result of any placement entry point; touches no placement kernel, no handle state and no launch scratch.
-// ------------------------------------------------------------------------------------------------
-// Trees of up to this many branches keep mass[B] | best[B] | totals[4] in the LDS of every block: (2 * 4094 + 4) * 8 = 64 KB, so that
-// two blocks still share a CU.  Above it the kernel adds straight into the buffer (DESIGN.md 4.7 holds the runs behind the value).
-constexpr uint32_t RK_MASSES_LDS_MAX_BRANCHES = 4094;
-constexpr uint32_t RK_MASSES_LDS_BLOCKS_PER_CU = 4;  // the flush costs blocks x B global atomics: a fixed multiple of the CU count
-constexpr bool RK_MASSES_COMBINE = false;             // equal branches among the lanes of a wave summed before the atomics
-
-extern "C" uint64_t rk_masses_words(uint32_t n_branches) { return n_branches >= 1 && n_branches <= 65535 ? 2ull * n_branches + 4 : 0; }
-
-// the argument tests the device and the host call share (score and flags are not read: they may be NULL)
-static int masses_args(const char *who, uint32_t K, uint64_t n_reads, const rk_result *res, const uint64_t *masses) {
-    if (K < 1 || K > 16) return fail(RK_ERR_INVALID, "%s: keep_at_most=%u outside 1..16", who, K);
-    if (n_reads >= (1ull << 32)) return fail(RK_ERR_INVALID, "%s: n_reads=%llu, at most 2^32 - 1 per call (the buffers of several calls add up)", who, (unsigned long long)n_reads);
-    if (n_reads == 0) return RK_OK;
-    if (!res || !res->n_rows || !res->branch || !res->lwr) return fail(RK_ERR_INVALID, "%s: null result array (n_rows, branch and lwr are read)", who);
-    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
-    return RK_OK;
-}
-
-// masses_kernel: LDS bins for small trees; for large ones global atomics behind a per-block LDS cache of the busiest bins
-static int launch_masses(rk_db *db, uint32_t K, uint64_t n_reads, const rk_result *res, const uint32_t *weights, uint64_t *masses, hipStream_t s) {
-    const uint32_t B = db->info.n_branches;
-    const uint64_t tiles = (n_reads + 255) / 256;  // a block's four waves take 64 reads each per step
-    bool lds = B <= RK_MASSES_LDS_MAX_BRANCHES, combine = RK_MASSES_COMBINE;
-    bool cache = !lds;
-    uint32_t per_cu = RK_MASSES_LDS_BLOCKS_PER_CU;
-    if (const char *v = rk_knob("RK_MASSES_VARIANT")) {  // developer builds: "lds" | "global" | "cache", "+combine" behind lds or global (scripts/masses_rate.py)
-        if (strstr(v, "global")) lds = false, cache = false;
-        if (strstr(v, "cache")) lds = false, cache = true;
-        if (strstr(v, "lds") && B <= RK_MASSES_LDS_MAX_BRANCHES) lds = true, cache = false;
-        combine = strstr(v, "combine") != nullptr && !cache;
-    }
-    if (const char *v = rk_knob("RK_MASSES_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(v));
-    const unsigned blocks = lds ? (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)db->cu_count * per_cu)) : strand_blocks(db, n_reads);
-    const size_t lds_bytes = lds ? (size_t)(2 * B + 4) * 8 : cache ? (size_t)(2 * MASS_CACHE_SLOTS + 4) * 8 + (size_t)MASS_CACHE_SLOTS * 4 : 4 * 8;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds_bytes, s, (u64)n_reads, K, B, (const unsigned char *)res->n_rows, (const unsigned short *)res->branch,
-                           (const double *)res->lwr, weights, (u64 *)masses);
-    };
-    if (lds && combine) launch(masses_kernel<true, true>);
-    else if (lds) launch(masses_kernel<true, false>);
-    else if (cache) launch(masses_kernel<false, false, true>);
-    else if (combine) launch(masses_kernel<false, true>);
-    else launch(masses_kernel<false, false>);
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
-}
-
-extern "C" int rk_masses_accumulate_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_res, const uint32_t *d_weights,
-                                           uint64_t *d_masses, void *stream) {
-    if (!db) return fail(RK_ERR_INVALID, "rk_masses_accumulate_device: null handle");
-    int rc = masses_args("rk_masses_accumulate_device", keep_at_most, n_reads, d_res, d_masses);
-    if (rc || n_reads == 0) return rc;
-    HIP_TRY(hipSetDevice(db->info.device));
-    return launch_masses(db, keep_at_most, n_reads, d_res, d_weights, d_masses, (hipStream_t)stream);
-}
-
-extern "C" int rk_masses_accumulate_host(uint32_t n_branches, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, const uint32_t *weights,
-                                         uint64_t *masses, uint32_t n_threads) {
-    if (n_branches < 1 || n_branches > 65535) return fail(RK_ERR_INVALID, "rk_masses_accumulate_host: n_branches=%u must be in 1..65535", n_branches);
-    int rc = masses_args("rk_masses_accumulate_host", keep_at_most, n_reads, res, masses);
-    if (rc || n_reads == 0) return rc;
-    const uint64_t words = 2ull * n_branches + 4;
-    unsigned hw = std::thread::hardware_concurrency();
-    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
-    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 256, (n_reads + 4095) / 4096}));  // (a thread pays for a buffer of its own)
-    if (T == 1) {
-        rk::masses_range(n_branches, keep_at_most, 0, n_reads, res->n_rows, res->branch, res->lwr, weights, masses);
-        return RK_OK;
-    }
-    // every thread sums into words of its own; the partial sums are added at the end (integers: any order gives the same words)
-    std::vector<uint64_t> part;
-    try {
-        part.assign(T * words, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(RK_ERR_NOMEM, "rk_masses_accumulate_host: no memory for %llu partial buffers", (unsigned long long)T);
-    }
-    struct JoinAll {
-        std::vector<std::thread> v;
-        ~JoinAll() { for (std::thread &t : v) if (t.joinable()) t.join(); }
-    } th;
-    try {
-        for (uint64_t t = 1; t < T; t++)
-            th.v.emplace_back([&, t]() { rk::masses_range(n_branches, keep_at_most, n_reads * t / T, n_reads * (t + 1) / T, res->n_rows, res->branch, res->lwr, weights, part.data() + t * words); });
-    } catch (const std::exception &) {
-        for (std::thread &t : th.v) t.join();
-        th.v.clear();
-        return fail(RK_ERR_NOMEM, "rk_masses_accumulate_host: cannot start the worker threads");
-    }
-    rk::masses_range(n_branches, keep_at_most, 0, n_reads / T, res->n_rows, res->branch, res->lwr, weights, part.data());
-    for (std::thread &t : th.v) t.join();
-    th.v.clear();
-    for (uint64_t t = 0; t < T; t++)
-        for (uint64_t i = 0; i < words; i++) masses[i] += part[t * words + i];
-    return RK_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Per-sample edge masses: one mass buffer per sample from a membership list of (read, sample, weight) entries, added
-// into a caller-owned buffer of S * (2B + 4) + 1 words.  A kernel of its own (masses_samples_kernel): rk_masses_accumulate_device
-// launches what it always did.
-// ------------------------------------------------------------------------------------------------
-constexpr uint64_t RK_MASSES_SAMPLES_MAX_WORDS = 1ull << 29;  // 4 GiB: a word index is a 32-bit value inside the kernel
-constexpr uint64_t RK_MASSES_SAMPLES_LDS_WORDS = 8192;        // the 64 KB of masses_kernel's LDS variant
-
-extern "C" uint64_t rk_masses_samples_words(uint32_t n_branches, uint32_t n_samples) {
-    const uint64_t W = rk_masses_words(n_branches);
-    if (!W || n_samples < 1 || n_samples > 65535) return 0;
-    const uint64_t words = (uint64_t)n_samples * W + 1;
-    return words <= RK_MASSES_SAMPLES_MAX_WORDS ? words : 0;
-}
-
-// the argument tests the device and the host call share, after masses_args' (whose n_reads == 0 does not end these calls)
-static int masses_samples_args(const char *who, uint32_t B, uint32_t K, uint64_t n_reads, const rk_result *res, uint32_t S, uint64_t n_members,
-                               const uint32_t *member_read, const uint32_t *member_sample, const uint64_t *masses) {
-    if (K < 1 || K > 16) return fail(RK_ERR_INVALID, "%s: keep_at_most=%u outside 1..16", who, K);
-    if (n_reads >= (1ull << 32)) return fail(RK_ERR_INVALID, "%s: n_reads=%llu, at most 2^32 - 1 per call", who, (unsigned long long)n_reads);
-    if (n_members >= (1ull << 32)) return fail(RK_ERR_INVALID, "%s: n_members=%llu, at most 2^32 - 1 per call (the buffers of several calls add up)", who, (unsigned long long)n_members);
-    if (!rk_masses_samples_words(B, S))
-        return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches: 1..65535 samples and at most 2^29 words (n_samples * (2 * n_branches + 4) + 1)", who, S, B);
-    if (!member_read && n_members != n_reads)
-        return fail(RK_ERR_INVALID, "%s: without member_read entry i is read i: n_members=%llu must equal n_reads=%llu", who, (unsigned long long)n_members, (unsigned long long)n_reads);
-    if (n_members == 0) return RK_OK;
-    if (!res || !res->n_rows || !res->branch || !res->lwr) return fail(RK_ERR_INVALID, "%s: null result array (n_rows, branch and lwr are read)", who);
-    if (!member_sample) return fail(RK_ERR_INVALID, "%s: null member_sample", who);
-    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
-    return RK_OK;
-}
-
-extern "C" int rk_masses_accumulate_samples_device(rk_db *db, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_res, uint32_t n_samples,
-                                                   uint64_t n_members, const uint32_t *d_member_read, const uint32_t *d_member_sample,
-                                                   const uint32_t *d_member_weight, uint64_t *d_masses, void *stream) {
-    const char *who = "rk_masses_accumulate_samples_device";
-    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
-    const uint32_t B = db->info.n_branches;
-    int rc = masses_samples_args(who, B, keep_at_most, n_reads, d_res, n_samples, n_members, d_member_read, d_member_sample, d_masses);
-    if (rc || n_members == 0) return rc;
-    HIP_TRY(hipSetDevice(db->info.device));
-    const uint64_t words = rk_masses_samples_words(B, n_samples), tiles = (n_members + 255) / 256;  // a block's four waves take 64 entries each per step
-    const bool lds = words <= RK_MASSES_SAMPLES_LDS_WORDS;
-    const unsigned blocks = lds ? (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)db->cu_count * RK_MASSES_LDS_BLOCKS_PER_CU)) : strand_blocks(db, n_members);
-    const size_t lds_bytes = lds ? (size_t)words * 8 : (size_t)(2 * MASS_CACHE_SLOTS + 2 + 4 * MASS_TOTAL_SLOTS) * 8 + (size_t)(MASS_CACHE_SLOTS + MASS_TOTAL_SLOTS) * 4;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), lds_bytes, (hipStream_t)stream, (u32)n_reads, (u64)n_members, keep_at_most, B, n_samples,
-                           (const unsigned char *)d_res->n_rows, (const unsigned short *)d_res->branch, (const double *)d_res->lwr, d_member_read, d_member_sample,
-                           d_member_weight, (u64 *)d_masses);
-    };
-    if (lds) launch(masses_samples_kernel<true>);
-    else launch(masses_samples_kernel<false>);
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
-}
-
-// Threads take ranges of entries and sum into words of their own while T buffers stay small; beyond that they take ranges of SAMPLES,
-// every thread walks the whole list and adds its samples' entries straight into the caller's words (no partial buffers).
-extern "C" int rk_masses_accumulate_samples_host(uint32_t n_branches, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, uint32_t n_samples,
-                                                 uint64_t n_members, const uint32_t *member_read, const uint32_t *member_sample,
-                                                 const uint32_t *member_weight, uint64_t *masses, uint32_t n_threads) {
-    const char *who = "rk_masses_accumulate_samples_host";
-    if (n_branches < 1 || n_branches > 65535) return fail(RK_ERR_INVALID, "%s: n_branches=%u must be in 1..65535", who, n_branches);
-    int rc = masses_samples_args(who, n_branches, keep_at_most, n_reads, res, n_samples, n_members, member_read, member_sample, masses);
-    if (rc || n_members == 0) return rc;
-    const uint32_t B = n_branches, K = keep_at_most, S = n_samples;
-    const uint64_t words = rk_masses_samples_words(B, S);
-    unsigned hw = std::thread::hardware_concurrency();
-    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
-    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, (n_members + 4095) / 4096}));
-    auto range = [&](uint64_t lo, uint64_t hi, uint32_t s_lo, uint32_t s_hi, bool count_bad, uint64_t *m) {
-        rk::masses_samples_range(B, K, S, n_reads, res->n_rows, res->branch, res->lwr, lo, hi, member_read, member_sample, member_weight, s_lo, s_hi, count_bad, m);
-    };
-    const bool by_sample = T * words > (1ull << 21);  // partial buffers of 16 MB at the most
-    if (by_sample) T = std::min<uint64_t>(T, S);
-    if (T == 1) {
-        range(0, n_members, 0, S, true, masses);
-        return RK_OK;
-    }
-    std::vector<uint64_t> part;
-    if (!by_sample) {
-        try {
-            part.assign(T * words, 0);
-        } catch (const std::bad_alloc &) {
-            return fail(RK_ERR_NOMEM, "%s: no memory for %llu partial buffers", who, (unsigned long long)T);
-        }
-    }
-    auto work = [&](uint64_t t) {
-        if (by_sample) range(0, n_members, (uint32_t)(S * t / T), (uint32_t)(S * (t + 1) / T), t == 0, masses);
-        else range(n_members * t / T, n_members * (t + 1) / T, 0, S, true, part.data() + t * words);
-    };
-    struct JoinAll {
-        std::vector<std::thread> v;
-        ~JoinAll() { for (std::thread &t : v) if (t.joinable()) t.join(); }
-    } th;
-    try {
-        th.v.reserve(T);
-        for (uint64_t t = 1; t < T; t++) th.v.emplace_back([&, t]() { work(t); });
-    } catch (const std::exception &) {  // a thread that would not start: its share is done here (a sample range may already be in `masses`)
-    }
-    work(0);
-    for (uint64_t t = th.v.size() + 1; t < T; t++) work(t);
-    for (std::thread &t : th.v) t.join();
-    th.v.clear();
-    if (!by_sample)
-        for (uint64_t t = 0; t < T; t++)
-            for (uint64_t i = 0; i < words; i++) masses[i] += part[t * words + i];
-    return RK_OK;
-}
+#include "rk_masses_impl.h"  // the edge-mass entry points
 
 // A second result set in a workspace, from byte offset `at` on: n_rows | branch | score | lwr | flags, each on a 256-byte boundary of
 // the block.  Returns the offset behind it and, given a block, the arrays at those offsets of it.

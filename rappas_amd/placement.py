@@ -135,6 +135,30 @@ def masses_words(n_branches):
     return int(_lib.load().rk_masses_words(n_branches))
 
 
+def _host_masses(words, masses):
+    """the mass buffer of a host call: made and zeroed when None, else checked -- a contiguous uint64 array of `words` words"""
+    if masses is None:
+        return np.zeros(words, np.uint64)
+    if masses.dtype != np.uint64 or masses.shape != (words,) or not masses.flags.c_contiguous:
+        raise ValueError(f"masses must be a contiguous uint64 array of {words} words")
+    return masses
+
+
+def _device_masses(words, masses, dev, stream):
+    """the mass buffer of a device call: an int64 tensor of `words` words on `dev`, made and zeroed on the call's stream when None"""
+    import torch
+    if masses is None:
+        masses = torch.empty(words, dtype=torch.int64, device=dev)
+        if stream is not None:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                masses.zero_()
+        else:
+            masses.zero_()
+    elif masses.dtype != torch.int64 or masses.numel() != words or not masses.is_contiguous() or masses.device != dev:
+        raise ValueError(f"masses must be a contiguous int64 tensor of {words} words on {dev}")
+    return masses
+
+
 def accumulate_masses_host(n_branches, placements, weights=None, masses=None, threads=0):
     """rk_masses_accumulate_host (no GPU): the per-branch LWR sums of a result set (`placements`: a Placements, or anything with
     n_rows u8 [n], branch u16 [n, K] and lwr f64 [n, K]) ADDED into `masses`, a uint64 array of masses_words(n_branches) -- mass_q30[B] |
@@ -154,10 +178,7 @@ def accumulate_masses_host(n_branches, placements, weights=None, masses=None, th
         weights = np.ascontiguousarray(weights, dtype=np.uint32)
         if weights.shape != (n,):
             raise ValueError("weights must hold one uint32 per read")
-    if masses is None:
-        masses = np.zeros(words, np.uint64)
-    elif masses.dtype != np.uint64 or masses.shape != (words,) or not masses.flags.c_contiguous:
-        raise ValueError(f"masses must be a contiguous uint64 array of {words} words")
+    masses = _host_masses(words, masses)
     res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
     _lib.check(lib.rk_masses_accumulate_host(n_branches, K, n, C.byref(res), None if weights is None else _ptr(weights), _ptr(masses), threads))
     return masses
@@ -183,11 +204,7 @@ def _samples_buffer(n_branches, n_samples, masses):
     words = masses_samples_words(n_branches, n_samples)
     if not words:
         raise ValueError(f"n_samples={n_samples} on {n_branches} branches: both in 1..65535 and at most 2^29 words")
-    if masses is None:
-        return np.zeros(words, np.uint64)
-    if masses.dtype != np.uint64 or masses.shape != (words,) or not masses.flags.c_contiguous:
-        raise ValueError(f"masses must be a contiguous uint64 array of {words} words")
-    return masses
+    return _host_masses(words, masses)
 
 
 def accumulate_masses_samples_host(n_branches, placements, n_samples, member_sample, member_read=None, member_weight=None, masses=None, threads=0):
@@ -461,10 +478,7 @@ class PlacementProcess:
             weights = np.asarray(weights, dtype=np.uint32)
         if weights is not None and (weights.dtype != np.uint32 or weights.shape != (n,) or not weights.flags.c_contiguous):
             raise ValueError("weights must be a contiguous uint32 array with one word per read")
-        if masses is None:
-            masses = np.zeros(words, np.uint64)
-        elif masses.dtype != np.uint64 or masses.shape != (words,) or not masses.flags.c_contiguous:
-            raise ValueError(f"masses must be a contiguous uint64 array of {words} words")
+        masses = _host_masses(words, masses)
         if flags_out is None:
             flags_out = np.zeros(n, np.uint32)
         elif flags_out.dtype != np.uint32 or flags_out.shape != (n,) or not flags_out.flags.c_contiguous:
@@ -629,15 +643,7 @@ class PlacementProcess:
         dev = out["branch"].device
         words = masses_words(self.db.info.n_branches)
         st = _stream(dev, stream)
-        if masses is None:
-            masses = torch.empty(words, dtype=torch.int64, device=dev)
-            if stream is not None:
-                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-                    masses.zero_()
-            else:
-                masses.zero_()
-        elif masses.dtype != torch.int64 or masses.numel() != words or not masses.is_contiguous() or masses.device != dev:
-            raise ValueError(f"masses must be a contiguous int64 tensor of {words} words on {dev}")
+        masses = _device_masses(words, masses, dev, stream)
         if weights is not None and (weights.dtype != torch.int32 or weights.numel() != n or not weights.is_contiguous() or weights.device != dev):
             raise ValueError(f"weights must be a contiguous int32 tensor of {n} words on {dev}")
         res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), None, out["lwr"].data_ptr(), None)
@@ -657,15 +663,7 @@ class PlacementProcess:
         if not words:
             raise ValueError(f"n_samples={n_samples} on {self.db.info.n_branches} branches: 1..65535 and at most 2^29 words")
         st = _stream(dev, stream)
-        if masses is None:
-            masses = torch.empty(words, dtype=torch.int64, device=dev)
-            if stream is not None:
-                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
-                    masses.zero_()
-            else:
-                masses.zero_()
-        elif masses.dtype != torch.int64 or masses.numel() != words or not masses.is_contiguous() or masses.device != dev:
-            raise ValueError(f"masses must be a contiguous int64 tensor of {words} words on {dev}")
+        masses = _device_masses(words, masses, dev, stream)
         m = member_sample.numel()
         for t, what in ((member_sample, "member_sample"), (member_read, "member_read"), (member_weight, "member_weight")):
             if t is not None and (t.dtype != torch.int32 or t.numel() != m or not t.is_contiguous() or t.device != dev):

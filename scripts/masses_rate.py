@@ -8,8 +8,9 @@ on the same batch in the same process, and the bytes of the result set the call 
 divided by its time.  Warm-up, then HIP events around every step, median.
 
 --variants switches to the developer build and repeats the accumulate call with the variant forced (RK_MASSES_VARIANT: lds | global |
-cache, +combine; RK_MASSES_BLOCKS_PER_CU), also on T4k's tree (3 999 branches, the largest bench tree below the LDS limit): the runs the
-constants RK_MASSES_LDS_MAX_BRANCHES / RK_MASSES_COMBINE / RK_MASSES_LDS_BLOCKS_PER_CU in rk_engine.hip were chosen from.
+cache; RK_MASSES_BLOCKS_PER_CU), also on T4k's tree (3 999 branches, the largest bench tree below the LDS limit): the runs the
+constants RK_MASSES_LDS_MAX_BRANCHES / RK_MASSES_LDS_BLOCKS_PER_CU in rk_masses_impl.h were chosen from.  (The "+combine" lines of
+profiles/masses_rate.txt are of a variant that was measured, rejected and removed: DESIGN.md 4.7.)
 
     python scripts/masses_rate.py [--reads 10000000] [--steps 10] [--warmup 10] [--variants] >> profiles/masses_rate.txt
 """
@@ -66,7 +67,7 @@ def report(tag, pp, out, place_ms=None):
     shape = f"{rows / n:.2f} rows a read, busiest best-branch {int(top.max().item()) / max(1, int((out['n_rows'] > 0).sum().item())):.4f} of the placed reads"
     runs = [("", {})]
     if a.variants:
-        runs = [(v, {"RK_MASSES_VARIANT": v}) for v in ("lds", "lds+combine", "global", "global+combine", "cache") if B <= 4094 or "lds" not in v]
+        runs = [(v, {"RK_MASSES_VARIANT": v}) for v in ("lds", "global", "cache") if B <= 4094 or "lds" not in v]
         if B <= 4094:
             runs += [(f"lds, {b} blocks a CU", {"RK_MASSES_VARIANT": "lds", "RK_MASSES_BLOCKS_PER_CU": str(b)}) for b in (1, 2, 8, 16)]
     for name, env in runs:

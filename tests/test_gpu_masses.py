@@ -117,6 +117,46 @@ def test_every_row_on_one_branch(handles, B):
     assert unchanged(out, before)
 
 
+# ---- 2b. where the variant choice and the LDS sizing decide: the last tree whose bins fit the LDS and the first behind the cache ----
+LIMIT_TREES = (4094, 4095)  # 2 * 4094 + 4 = 8192 words are exactly 64 KB of LDS
+
+
+def limit_db(B):
+    return ra.PhyloKmerDB.from_synth(synth.make_db(4, 6, B, 300, 1500, seed=B))
+
+
+@pytest.mark.parametrize("K", [1, 7, 16])
+@pytest.mark.parametrize("B", LIMIT_TREES)
+def test_the_lds_limit_equals_the_reference_and_the_host_call(B, K):
+    s, w, refs = case(B, K, 5000)
+    assert refs[1][2 * B + 3] > 0 and refs[1][B + B - 1] > 0  # the planted rows are there
+    db = limit_db(B)
+    try:
+        got = words(ra.PlacementProcess(db).accumulate_masses(upload(s), weights=dev_weights(w)))
+    finally:
+        db.close()
+    assert got.shape == (2 * B + 4,)
+    assert np.array_equal(got, refs[1]), np.flatnonzero(got != refs[1])[:8]
+    assert np.array_equal(got, ra.accumulate_masses_host(B, s, w))
+
+
+@pytest.mark.parametrize("K", [1, 7, 16])
+@pytest.mark.parametrize("B", LIMIT_TREES)
+def test_the_lds_limit_forced_variants_give_the_same_words(B, K, monkeypatch, dev_lib):
+    """developer build: RK_MASSES_VARIANT=global and =cache on both trees, the one that takes the LDS variant by default included"""
+    s, w, refs = case(B, K, 5000)
+    db = limit_db(B)
+    try:
+        pp = ra.PlacementProcess(db)
+        out, dw = upload(s), dev_weights(w)
+        for variant in ("global", "cache"):
+            monkeypatch.setenv("RK_MASSES_VARIANT", variant)
+            got = words(pp.accumulate_masses(out, weights=dw))
+            assert np.array_equal(got, refs[1]), (variant, np.flatnonzero(got != refs[1])[:8])
+    finally:
+        db.close()
+
+
 # ---- 3. calls add up: on one stream, and over two streams ----
 @pytest.mark.parametrize("B", TREES)
 def test_calls_accumulate_on_one_stream_and_over_two(handles, B):

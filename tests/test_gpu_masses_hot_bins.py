@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 TREES = (4095, 20001, 65535)
 KS = (1, 7, 16)
-SLOTS = 512  # MASS_CACHE_SLOTS in rappas_amd/csrc/rk_kernels.hip: the slots of a block's table
+SLOTS = 512  # MASS_CACHE_SLOTS in rappas_amd/csrc/rk_masses.h: the slots of a block's table
 HOT = (1, 7, SLOTS - 1, SLOTS, SLOTS + 1, 4 * SLOTS)
 STRIDES = (1, 1 << 10, 1 << 11, 1 << 12, "random")
 SMALL = (1, 63, 65)

@@ -21,15 +21,16 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 300
 SHAPES = [(999, 4), (999, 5), (5, 300), (20001, 40), (65535, 3)]
+LIMIT_SHAPES = [(1363, 3), (2046, 2), (999, 130)]  # the last LDS shape, the first cached one, more samples than MASS_TOTAL_SLOTS
 N, M = 5000, 20000  # reads of a hand-made set, entries of a membership list over it
-SLOTS = 512         # MASS_CACHE_SLOTS in rappas_amd/csrc/rk_kernels.hip
+SLOTS = 512         # MASS_CACHE_SLOTS in rappas_amd/csrc/rk_masses.h
 POISON = np.uint64(0xA5A5A5A5DEADBEEF)
 
 
 @pytest.fixture(scope="module")
 def handles():
     """tiny hand-made databases: only their number of branches matters here"""
-    dbs = {B: ra.PhyloKmerDB.from_synth(synth.make_db(4, 6, B, 300, 1500, seed=B)) for B in sorted({b for b, _ in SHAPES})}
+    dbs = {B: ra.PhyloKmerDB.from_synth(synth.make_db(4, 6, B, 300, 1500, seed=B)) for B in sorted({b for b, _ in SHAPES + LIMIT_SHAPES})}
     yield dbs
     for db in dbs.values():
         db.close()
@@ -82,6 +83,30 @@ def test_device_call_equals_the_reference(handles, B, S, K):
             assert np.array_equal(got, want), (kind, wk, np.flatnonzero(got != want)[:8])
             assert want[-1] == mem.n_planted > 0
             assert np.array_equal(got, ra.accumulate_masses_samples_host(B, s, S, mem.sample, member_read=mem.read, member_weight=w))
+
+
+@pytest.mark.parametrize("K", [1, 7, 16])
+@pytest.mark.parametrize("B,S", LIMIT_SHAPES)
+def test_device_call_at_the_lds_limit_and_with_more_samples_than_total_slots(handles, B, S, K):
+    """(1363, 3): 8 191 words, the LDS form; (2046, 2): 8 193 words, the cached form; (999, 130): the cached form with more samples
+    than the totals' table has slots -- the interleaved list puts 130 samples on the 64 slots of the first block, so a sample that
+    does not hold its slot adds its totals to global memory"""
+    assert SR.words(B, S) == {(1363, 3): 8191, (2046, 2): 8193, (999, 130): 260261}[B, S]
+    pp = ra.PlacementProcess(handles[B])
+    s = result_set(B, K)
+    out = upload(s)
+    for kind in SR.KINDS:
+        mem = SR.make_members(kind, N, M, S, seed=K)
+        SR.assert_not_trivial(mem, N, S)
+        if kind == "interleaved" and S == 130:  # the first block's 256 entries name every sample: two and more to a slot of the totals' table
+            assert len(np.unique(mem.sample[:256][mem.sample[:256] < S])) == S > 64
+        w = MR.make_weights(len(mem.sample), "mixed", seed=K)
+        want = SR.masses_samples_ref(B, S, s, mem.sample, mem.read, w)
+        got = words(device_call(pp, out, S, mem, w))
+        assert got.shape == (SR.words(B, S),)
+        assert np.array_equal(got, want), (kind, np.flatnonzero(got != want)[:8])
+        assert want[-1] == mem.n_planted > 0
+        assert np.array_equal(got, ra.accumulate_masses_samples_host(B, s, S, mem.sample, member_read=mem.read, member_weight=w))
 
 
 @pytest.mark.parametrize("B,S", [(999, 4), (20001, 40)])
