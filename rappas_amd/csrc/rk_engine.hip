@@ -6,6 +6,7 @@
 #include "rk_pack_host.h"
 #include "rk_translate_host.h"
 #include "rk_plan.h"
+#include "rk_geometry.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -37,22 +38,6 @@
 
 using namespace rk;
 
-#ifndef RK_WG_MIN_BRANCHES
-#define RK_WG_MIN_BRANCHES 8192u  // above this a single-wave score vector leaves <= 4 waves per CU: use place_wg_kernel
-#endif
-#ifndef RK_WG_MIN_MEAN_ROW
-#define RK_WG_MIN_MEAN_ROW 320.0    // ... for rows at least this long on average (scripts/long_rows_big_tree.py: up to ~300 entries the windowed kernel is ahead:
-                                    // 15 999 branches, mean row 70 / 150 / 300: 54 / 36 / 19 against 22 / 19 / 17 Mreads/s) ...
-#endif
-#ifndef RK_WG_ALWAYS_BRANCHES
-#define RK_WG_ALWAYS_BRANCHES 65535u  // ... or, whatever the rows, above this many branches (none: the windowed kernel's 64 windows of 1 024 cover every tree)
-#endif
-#ifndef RK_WINDOW_MIN_BRANCHES
-#define RK_WINDOW_MIN_BRANCHES 1276u  // the dense 16-lane geometry keeps eight waves per CU up to 1 116 branches and seven up to 1 276; the switch sits where the seventh wave goes (round 3, scripts/tree_size_sweep.py, dense against windowed Mreads/s: 1 117 branches 291 / 247, 1 200: 257 / ~245, 1 290 (six waves): 219 / 242, 1 400: 218 / 242, 2 800: 110 / 188)
-#endif
-#ifndef RK_RING
-#define RK_RING 8  // depth of the row-chunk register ring (chunks in flight per lane)
-#endif
 #ifndef RK_WG_RING
 #define RK_WG_RING 20  // the same for the large-tree kernel, whose waves stream long row slices from HBM: what counts there is bytes in flight
                        // (C5s: rings of 8 / 12 / 16 / 20 / 24 / 32 give 0.72 / 0.76 / 0.77 / 0.79 / 0.78 / 0.77 of the byte roofline;
@@ -60,9 +45,6 @@ using namespace rk;
 #endif
 #ifndef RK_WRING
 #define RK_WRING RK_RING  // the same for the windowed kernel
-#endif
-#ifndef RK_RING64
-#define RK_RING64 8  // ... and for the 64-lane geometry (one wave per read: large trees with long rows, one or two waves per SIMD)
 #endif
 #ifndef RK_HRING
 #define RK_HRING 2  // ... and for the hash-accumulator kernel (place_hash64_kernel: steps of RK_HNPL entries per lane = 4 * RK_HNPL row units)
@@ -108,35 +90,41 @@ extern "C" const char *rk_last_error(void) { return g_err; }
 // the grid's stride.  The slots are what the runtime says fit (registers, the LDS allocation granule), not LDS size / LDS
 // per block: a grid one block per CU too large runs a second round and costs up to 2 x (seen: 23 360 B of LDS per block, seven
 // by division, six resident; 32-lane geometry with 11 by division, 8 by registers).
-template <typename K>
-static int resident_blocks(K kern, int block_threads, size_t lds, uint64_t by_lds, uint64_t &out) {
+struct Grid {
+    int threads; size_t lds;        // per block: threads and dynamic LDS
+    uint64_t want_per_cu, work;     // blocks a CU holds by LDS size; blocks the batch has work for
+    bool whole_simds = false;       // optional clamp: nine to eleven resident blocks become eight (launch_variant)
+};
+// One launch of a persistent grid on `stream`: nothing is allocated and nothing synchronises (stream capture keeps working); an empty
+// grid launches nothing and asks the runtime nothing.
+template <typename K, typename... Args>
+static int launch_grid(int cu_count, K kern, const Grid &g, hipStream_t stream, const Args &...args) {
+    if (g.work == 0) return RK_OK;
+    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
     int n = 0;
     {  // (asked once per kernel, block size, LDS size and device: the query is not free next to a small launch)
         static std::mutex mu;
         static std::map<std::tuple<const void *, int, size_t, int>, int> known;
         int dev = 0;
         HIP_TRY(hipGetDevice(&dev));
-        const auto key = std::make_tuple((const void *)kern, block_threads, lds, dev);
+        const auto key = std::make_tuple((const void *)kern, g.threads, g.lds, dev);
         std::lock_guard<std::mutex> lock(mu);
         auto it = known.find(key);
         if (it != known.end()) {
             n = it->second;
         } else {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kern, block_threads, lds));
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)kern, g.threads, g.lds));
             known.emplace(key, n);
         }
     }
-    if (n < 1) return fail(RK_ERR_UNSUPPORTED, "internal: kernel does not fit a CU (%d threads, %zu B of LDS per block)", block_threads, lds);
-    out = by_lds < (uint64_t)n ? by_lds : (uint64_t)n;
-    // The LDS is handed out in granules of 512 bytes, which the occupancy query does not count in: 23 232 B per block -- seven by
-    // division and by the query -- are 23 552 B each, and six are resident (round 3, scripts/tree_size_sweep.py at 1 290 branches:
-    // the seventh block of every CU ran in a second round, 140 instead of 250 Mreads/s).
-    if (lds) {
-        const uint64_t by_granule = (160ull * 1024) / ((lds + 511) & ~(size_t)511);
-        if (by_granule >= 1 && by_granule < out) out = by_granule;
-    }
+    if (n < 1) return fail(RK_ERR_UNSUPPORTED, "internal: kernel does not fit a CU (%d threads, %zu B of LDS per block)", g.threads, g.lds);
+    uint64_t per_cu = rk_geom::resident_per_cu(g.want_per_cu, (uint64_t)n, g.lds);
     static const bool trace = rk_knob("RK_TRACE_GRID") != nullptr;  // developer knob
-    if (trace) fprintf(stderr, "[rk] grid: %d threads, %zu B LDS per block -> %d resident per CU (by LDS size %llu)\n", block_threads, lds, n, (unsigned long long)by_lds);
+    if (trace) fprintf(stderr, "[rk] grid: %d threads, %zu B LDS per block -> %d resident per CU (by LDS size %llu)\n", g.threads, g.lds, n, (unsigned long long)g.want_per_cu);
+    if (g.whole_simds && per_cu > 8 && per_cu < 12) per_cu = 8;
+    const uint64_t blocks = rk_geom::grid_blocks(cu_count, per_cu, g.work);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)g.threads), g.lds, stream, args...);
+    HIP_TRY(hipGetLastError());
     return RK_OK;
 }
 extern "C" int rk_version(void) { return RK_VERSION; }
@@ -205,98 +193,15 @@ static void build_alphabet(uint32_t alphabet, bool convert_uo, Alphabet &A) {
 // ------------------------------------------------------------------------------------------------
 #include "rk_hostbuf_impl.h"
 
-// mid-size trees: the score vector of a read is held one window of W branches at a time (place_packed16w_kernel)
-constexpr uint32_t RK_MAX_WINDOWS = 64;  // 6-bit window ids in winspec and in the item tags
-// winspec byte of a row that reaches the windows first .. last: first | span << 6, span 3 = "at least three more: to the last window"
-static inline unsigned char winspec_byte(uint32_t first, uint32_t last) {
-    const uint32_t span = last - first;
-    return (unsigned char)(first | ((span < 3u ? span : 3u) << 6));
+using namespace rk_geom;  // (its types and constants; its functions are called by their full names: the engine's own are db_geometry, db_wg_geometry)
+static_assert(rk_geom::ROW_ENTRIES == ROW_UNIT, "rk_geometry.h repeats this constant of the device code");
+static int knob_int(const char *name, int unset) {
+    const char *e = rk_knob(name);
+    return e ? atoi(e) : unset;
 }
-constexpr uint64_t RK_WINDOW_MAX_BLOB = 1ull << 31;  // list items carry a 24-bit index of 128-byte units
-// The windowed kernel holds a read's row units in a list of a few hundred items: beyond ~2.2 units per k-mer code (a 150-bp read
-// then brings ~300) a read is emitted in many window ranges and the dense kernels are ahead (scripts/row_length_sweep.py, 3 999
-// branches, mean row 100 / 250 entries: 113 / 35 against 87 / 49 Mreads/s) -- unless the tree is so large that they hold one read
-// in two or three waves per CU (beyond 8 192 branches; scripts/dense_rows_mid_tree.py, every k-mer present with rows of 30 / 60
-// entries: 9 001 branches 66 / 45 against 41 / 36, 15 999: 49 / 36 against 17 / 15; longer rows there take the large-tree image)
-static inline bool windows_pay(uint32_t nb, uint64_t blob_units, uint64_t space) {
-    if (rk_knob("RK_WINDOW_ALWAYS")) return true;  // developer / test knob: the windowed kernel whatever the row density
-    return 5 * blob_units <= 11 * space || nb > RK_WG_MIN_BRANCHES;
-}
-struct WindowPlan {
-    uint32_t W = 0, n_win = 0, s_stride = 0, main_cap = 0, work_cap = 0;
-    bool stream = false;          // place_packed16s_kernel first (decided when the image is built: its windows are narrower)
-    double units_per_code = 0.0;  // row units / k-mer codes of the alphabet: what a read's k-mer brings on average
-};
-
-// The dense 16-lane geometry keeps eight waves per CU up to 1 116 branches (choose_geometry); beyond that -- and up to the
-// 65 535 branches of the reference -- the tree is cut into windows of <= 1 024 branches, at most 64 of them
-// (6-bit window ids in winspec and in the item tags), sized so that a wave's four reads fit 20 KB of LDS: 8 waves per CU again.
-#ifndef RK_WSTREAM_MIN_BRANCHES
-#define RK_WSTREAM_MIN_BRANCHES 4500u
-#endif
-// (RK_WSTREAM_MAX_UNITS: rk_plan.h)
-static bool wstream_tree(uint32_t nb, uint32_t bits, double units_per_code, double units_per_row) {  // images whose tiles go to place_packed16s_kernel first
-    if (rk_knob("RK_WSTREAM_ALWAYS")) return true;  // developer / test knob: the sorted-stream kernel on every windowed tree
-    if (150.0 * units_per_code > RK_WSTREAM_MAX_UNITS) return false;
-    // rows of several units (70 entries: 5) put few, long runs of slots into a window -- three or four rounds at its end -- and few
-    // units per window and read, so that most of the list is padding: 9 001 / 15 999 / 25 001 branches 73 / 44 / 28 Mreads/s against
-    // 77 / 53 / 39 (same profile); short rows only
-    if (units_per_row > 2.5) return false;
-    // amino acids: every windowed tree (the first kernel runs with register spills to keep two waves per SIMD: 274 / 248 / 194
-    // Mreads/s at 1 400 / 1 999 / 3 999 branches against 280 / 272 / 241, C4-like rows; profiles/r03_wstream_crossover.txt)
-    return bits == 5 || nb > RK_WSTREAM_MIN_BRANCHES;
-}
-static bool window_plan(uint32_t nb, uint32_t bits, double units_per_code, double units_per_row, WindowPlan &wp) {
-    if (nb <= RK_WINDOW_MIN_BRANCHES || nb > RK_WG_ALWAYS_BRANCHES) return false;
-    // up to ~4 500 branches place_packed16w_kernel is ahead (windows of <= 1 024 branches, as few as possible: it pays per window);
-    // beyond, place_packed16s_kernel (round 3: a window's cost follows what the read touches in it, so more and smaller windows --
-    // about 500 branches, one bitmap word a lane -- cost little and leave the LDS to the list).  At most 64 windows: up to 1 024
-    // branches each on the largest trees.  scripts/wstream_crossover.py, Mreads/s at 3 999 / 4 999 / 5 999 / 7 999 branches:
-    // 164 / 147 / 132 / 113 with the first kernel, 159 / 150 / 144 / 135 with the second (profiles/r03_wstream_crossover.txt)
-    wp.stream = wstream_tree(nb, bits, units_per_code, units_per_row);
-    wp.units_per_code = units_per_code;
-    uint32_t n_win = wp.stream ? (nb + 511) / 512 : (nb + 895) / 896;
-    if (n_win > RK_MAX_WINDOWS) n_win = RK_MAX_WINDOWS;
-    wp.n_win = n_win;
-    wp.W = ((nb + n_win - 1) / n_win + 3) & ~3u;
-    wp.s_stride = wp.W + 4;
-    const uint32_t per_group_words = 160 * 1024 / 8 / 4 / 4;  // 1280 u32 words per read = eight waves per CU
-    // place_packed16w_kernel: the main list has to hold a whole read (C2-like reads: 145 row units on average, 250 at the tail); what
-    // is left goes to the per-window work list, so that a window is normally applied in one accumulate call
-    const uint32_t avail = per_group_words - wp.s_stride;
-    // (88 words = the 44 keys the exact select of a window needs as scratch)
-    uint32_t work = avail > 256 + 88 ? avail - 256 : 88;
-    if (work > 200) work = 200;
-    wp.work_cap = work & ~1u;
-    wp.main_cap = (avail - wp.work_cap) & ~1u;
-    if (wp.main_cap > 640) wp.main_cap = 640;
-    return wp.main_cap >= 160;
-}
-
-// Which image a database gets, from its row lengths alone (slot_units = sum of ceil(len / 16) + 1, max_len, mean_len):
-//   windowed (slot-offset rows + winspec, place_packed16w_kernel) when window_plan has a plan, the compact table applies (DIRECT or
-//     AUTO over a small enough key space, no row beyond 255 units), the blob stays below 2 GB and windows_pay says so;
-//   large-tree (indexed rows, place_wg_kernel) beyond 8 192 branches when the rows are long (mean >= RK_WG_MIN_MEAN_ROW), or when
-//     no windowed image is possible beyond 16 000 branches (there the dense kernels hold one read per CU, or none at all beyond
-//     ~39 000);
-//   the plain slot-offset image of the dense kernels otherwise.
-struct ImageKind { bool indexed, windowable; };
-static ImageKind image_kind(uint32_t nb, uint32_t bits, uint32_t table_mode, uint64_t space, bool space_ok, uint64_t slot_units, uint32_t max_len, double mean_len) {
-    WindowPlan wp;
-    const bool direct = table_mode == RK_TABLE_DIRECT || (table_mode == RK_TABLE_AUTO && space_ok && space <= (1ull << 28));
-    // Just beyond 8 192 branches the dense 64-lane kernel (one wave per read, the whole score vector in the LDS) still holds three or
-    // four reads per CU, and with rows of a few hundred entries it is ahead of both its neighbours (scripts/long_rows_big_tree.py,
-    // scripts/long_rows_lanes64.py, profiles/r03_long_rows_big_tree.txt; Mreads/s, dense against the other):
-    //   the windowed kernel, rows of 150 / 300: 9 001 branches 46.7 / 36.3 against 45.6 / 20.6; 13 001: 30.4 / 24.5 against 39.3 / 19.1;
-    //   the workgroup-per-read kernel between its two regimes (slices of a row shorter than a turn of the ring), rows of 400 / 1 000:
-    //   9 001 branches 31.0 / 14.3 against 16.2 / 12.3; 11 001: 22.2 / 11.0 against 16.0 / 12.1; 13 001: 21.3 / 10.7 against 15.9 / 12.1;
-    //   15 999: 13.5 / 7.2 against 15.8 / 11.9
-    const bool dense64_ahead = nb > RK_WG_MIN_BRANCHES && ((nb <= 9900u && mean_len >= 200.0 && mean_len < 1200.0) || (nb <= 13300u && mean_len >= 250.0 && mean_len < 750.0));
-    const bool windowable = (!dense64_ahead || rk_knob("RK_WINDOW_ALWAYS")) && window_plan(nb, bits, space ? (double)slot_units / (double)space : 0.0, mean_len / ROW_UNIT + 0.5, wp) && direct &&
-                            (max_len + ROW_UNIT - 1) / ROW_UNIT <= 255 && slot_units * 128 < RK_WINDOW_MAX_BLOB && windows_pay(nb, slot_units, space);
-    const bool long_rows = mean_len >= RK_WG_MIN_MEAN_ROW;
-    const bool indexed = nb > RK_WG_MIN_BRANCHES && ((long_rows && !dense64_ahead) || (!windowable && !dense64_ahead && nb > 16000u));
-    return {indexed, windowable && !indexed};
+static rk_geom::Knobs geom_knobs() {  // (developer knobs, read where the geometry is asked for: the product library reads none)
+    return {(uint32_t)knob_int("RK_LIST_CAP", 0), (uint32_t)knob_int("RK_WAVES_PER_CU", 0), knob_int("RK_WG_PASSES", 1), (uint32_t)knob_int("RK_HASH_WAVES", -1),
+            rk_knob("RK_WINDOW_ALWAYS") != nullptr, rk_knob("RK_WSTREAM_ALWAYS") != nullptr};
 }
 
 struct rk_db {
@@ -315,7 +220,6 @@ struct rk_db {
     uint64_t dense_rows_bytes = 0;
     WindowPlan wp;
     uint32_t lanes_per_read = 0;       // 0 = auto
-    uint32_t waves_per_block = 1;
     bool indexed = false;              // rows carry an index line (large trees, place_wg_kernel)
     int cu_count = 256;
     size_t lds_per_cu = 160 * 1024;
@@ -737,12 +641,12 @@ static int build_image(const rk_db_desc *d, DbImage &img) {
         slot_units += (len + ROW_UNIT - 1) / ROW_UNIT;
         if (len > longest) longest = (uint32_t)(len > 0xFFFFFFFFull ? 0xFFFFFFFFull : len);
     }
-    const ImageKind kind = image_kind(d->n_branches, bits, d->table_mode, space, space_ok, slot_units, longest, mean_len);
+    const ImageKind kind = rk_geom::image_kind(d->n_branches, bits, mode == RK_TABLE_DIRECT, space, slot_units, longest, mean_len, geom_knobs());  // (AUTO is resolved by now)
     const bool indexed = kind.indexed;
     img.indexed = indexed;
     std::vector<uint64_t> desc(n_keys);  // by key number
     WindowPlan wp;
-    const bool want_windows = kind.windowable && window_plan(d->n_branches, bits, space ? (double)slot_units / (double)space : 0.0, mean_len / ROW_UNIT + 0.5, wp);
+    const bool want_windows = kind.windowable && rk_geom::window_plan(d->n_branches, bits, space ? (double)slot_units / (double)space : 0.0, mean_len / ROW_UNIT + 0.5, geom_knobs(), wp);
     // Images the dense kernels serve get the same byte per k-mer code with the tree cut into 64 equal ranges: not for any window
     // -- the kernels hold the whole score vector -- but as the position a batch's reads are grouped by (reads of one clade read the
     // same rows: taken together they find them in the L2; scripts/clade_sorted_probe.py: 283 -> 406 Mreads/s on C2's shape)
@@ -1043,61 +947,23 @@ extern "C" int rk_set_lanes_per_read(rk_db *db, uint32_t lanes) {
 // ------------------------------------------------------------------------------------------------
 // launch geometry
 // ------------------------------------------------------------------------------------------------
-struct Geometry {
-    uint32_t G, NG, s_stride, list_cap, pu;
-    size_t lds_per_wave;
-    uint32_t waves_per_cu;
-};
-
-// PU*G >= 144 positions per probe batch.  Amino acids through the 16-lane kernels: a packed record of <= 16 words holds <= 102
-// residues, so seven rounds of sixteen are a whole read (nine made C4 look up 48 k-mers per read that do not exist)
-static uint32_t probe_unroll(uint32_t G, uint32_t bits) { return G <= 16 ? (bits == 5 && G == 16 ? 7 : 9) : (G == 32 ? 5 : 3); }
-
-static int choose_geometry(const rk_db *db, uint32_t keep_at_most, Geometry &g) {
-    const uint32_t nb = db->info.n_branches;
-    const uint32_t s_stride = (nb + 4) & ~3u;  // >= nb + 1 (word nb is the scratch slot of apply_entry), multiple of 4 (b128 scans)
-    const size_t target = db->lds_per_cu / 8;  // aim for >= 8 waves per CU
-    const size_t fixed = (size_t)s_stride * 4;  // per read, besides the hit list
-    auto bytes_for = [&](uint32_t G, uint32_t cap) { return (size_t)(64 / G) * (fixed + (size_t)cap * 8); };
-    uint32_t G = db->lanes_per_read;
-    if (G == 0) {
-        // Throughput follows the reads in flight per CU (LDS capacity / score-vector size) and, at equal reads in flight, prefers
-        // narrower groups as long as enough waves remain to hide latency.  Measured on C2-like DBs (scripts/tree_size_sweep.py):
-        // 999 branches: 16 lanes (8 waves) 335 Mreads/s; 1300 / 1500: 16 lanes (6 waves) 219 / 214 vs 32 lanes (11 / 10 waves) 156 / 141;
-        // 1999: 32 lanes (8 waves) 199 vs 16 lanes (4 waves) 165 vs 64 lanes 120; 3999: 32 lanes (4 waves) 88 vs 64 lanes (9 waves) 62;
-        // 7999: 64 lanes (4 waves) 46 vs 32 lanes (2 waves) 35.  (Between 1 117 and 16 000 branches these dense geometries only serve
-        // what the windowed kernel does not take: records of more than 16 words, a forced lane width.)
-        G = 64;
-        if (keep_at_most <= 16 && bytes_for(16, 16 + 3 * RK_RING + 40) <= db->lds_per_cu / 6) G = 16;
-        else if (keep_at_most <= 32 && bytes_for(32, 32 + 3 * RK_RING + 40) <= db->lds_per_cu / 4) G = 32;
+// (the arithmetic: rk_geometry.h)  What a geometry refuses, as the error codes and texts of the C ABI
+static int geometry_error(rk_geom::Status st, const rk_db *db, uint32_t keep_at_most = 0, size_t lds_per_read = 0) {
+    switch (st) {
+    case rk_geom::GEOM_OK: return RK_OK;
+    case rk_geom::KEEP_NEEDS_LANES: return fail(RK_ERR_INVALID, "keep_at_most=%u needs lanes_per_read >= %u", keep_at_most, keep_at_most);
+    case rk_geom::READ_EXCEEDS_LDS: return fail(RK_ERR_UNSUPPORTED, "n_branches=%u needs %zu B of LDS per read, more than one CU has (%zu B)", db->info.n_branches, lds_per_read, db->lds_per_cu);
+    case rk_geom::NO_WG_WINDOW: return fail(RK_ERR_UNSUPPORTED, "n_branches=%u: no score-vector window fits one CU's LDS (%zu B)", db->info.n_branches, db->lds_per_cu);
+    case rk_geom::WINDOWED_NO_FIT: return fail(RK_ERR_UNSUPPORTED, "internal: windowed geometry does not fit the LDS");
+    default: return fail(RK_ERR_INVALID, "internal: ambiguity kernel launched without a score-vector geometry");
     }
-    if (G < keep_at_most) return fail(RK_ERR_INVALID, "keep_at_most=%u needs lanes_per_read >= %u", keep_at_most, keep_at_most);
-    const uint32_t NG = 64 / G, pu = probe_unroll(G, db->info.bits_per_symbol);
-    const uint32_t min_cap = G + 3 * (G == 64 ? RK_RING64 : RK_RING) + 40;  // one sub-batch of rows + sentinel, ring slack, 16 winner slots + margin
-    // list capacity: whatever is left of the per-wave LDS target, clamped to [min_cap, 256]
-    size_t per_group_target = target / NG;
-    uint32_t cap = min_cap;
-    if (per_group_target > fixed + (size_t)min_cap * 8) {
-        size_t c = (per_group_target - fixed) / 8;
-        cap = (uint32_t)(c > 256 ? 256 : c);
-        if (cap < min_cap) cap = min_cap;
-    }
-    if (const char *e = rk_knob("RK_LIST_CAP")) {  // developer knob: trade hit-list room for occupancy
-        uint32_t v = (uint32_t)atoi(e);
-        if (v >= min_cap && v <= 4096) cap = v;
-    }
-    cap &= ~1u;  // keeps every group's score vector 16-byte aligned
-    g.G = G; g.NG = NG; g.s_stride = s_stride; g.list_cap = cap; g.pu = pu;
-    g.lds_per_wave = bytes_for(G, cap);
-    if (g.lds_per_wave > db->lds_per_cu)
-        return fail(RK_ERR_UNSUPPORTED, "n_branches=%u needs %zu B of LDS per read, more than one CU has (%zu B)", nb, g.lds_per_wave, db->lds_per_cu);
-    uint32_t w = (uint32_t)(db->lds_per_cu / g.lds_per_wave);
-    g.waves_per_cu = w > 32 ? 32 : w;
-    if (const char *e = rk_knob("RK_WAVES_PER_CU")) {  // developer knob for occupancy experiments
-        uint32_t v = (uint32_t)atoi(e);
-        if (v >= 1 && v < g.waves_per_cu) g.waves_per_cu = v;
-    }
-    return RK_OK;
+}
+static int db_geometry(const rk_db *db, uint32_t keep_at_most, Geometry &g) {
+    const rk_geom::Status st = rk_geom::choose_geometry(db->info.n_branches, db->info.bits_per_symbol, db->lds_per_cu, db->lanes_per_read, keep_at_most, geom_knobs(), g);
+    return geometry_error(st, db, keep_at_most, st == rk_geom::READ_EXCEEDS_LDS ? g.lds_per_wave : 0);
+}
+static int db_wg_geometry(const rk_db *db, WgGeometry &g, uint32_t keep_at_most = 16) {
+    return geometry_error(rk_geom::choose_wg_geometry(db->info.n_branches, db->lds_per_cu, keep_at_most, geom_knobs(), g), db);
 }
 
 // 16 lanes per read, direct table, 32-bit row offsets, packed record of <= 16 words: the tile-pipelined kernel
@@ -1108,7 +974,7 @@ static bool use_pipelined16(const rk_db *db, const Geometry &g, const PlaceArgs 
 
 template <int G, int BITS, int TM, bool WIDE>
 static int launch_variant(const rk_db *db, const Geometry &g, const PlaceArgs &args, hipStream_t stream) {
-    constexpr int PU = G <= 16 ? (BITS == 5 && G == 16 ? 7 : 9) : (G == 32 ? 5 : 3);  // (= probe_unroll)
+    constexpr int PU = rk_geom::probe_unroll(G, BITS);
     constexpr int U = G == 64 ? RK_RING64 : RK_RING;
     auto kern = place_packed_kernel<G, BITS, TM, WIDE, U, PU>;
     decltype(kern) clade_kern = nullptr;
@@ -1147,46 +1013,22 @@ static int launch_variant(const rk_db *db, const Geometry &g, const PlaceArgs &a
             }
         }
     }
-    const uint32_t wpb = db->waves_per_block;
-    const size_t lds = g.lds_per_wave * wpb;
-    const uint64_t n_tiles = (args.n_reads + g.NG - 1) / g.NG;
-    auto go = [&](decltype(kern) k, const PlaceArgs &pa) -> int {
-        HIP_TRY(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        uint64_t per_cu = 0;
-        if (int rc = resident_blocks(k, 64 * (int)wpb, lds, (g.waves_per_cu + wpb - 1) / wpb, per_cu)) return rc;
-        if (whole_simds && wpb == 1 && per_cu > 8 && per_cu < 12) per_cu = 8;
-        uint64_t blocks = (uint64_t)db->cu_count * per_cu;
-        const uint64_t need = (n_tiles + wpb - 1) / wpb;
-        if (blocks > need) blocks = need;
-        if (blocks == 0) return RK_OK;
-        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, pa);
-        HIP_TRY(hipGetLastError());
-        return RK_OK;
-    };
-    if (int rc = go(kern, la)) return rc;
+    const Grid grid{64, g.lds_per_wave, g.waves_per_cu, (args.n_reads + g.NG - 1) / g.NG, whole_simds};
+    if (int rc = launch_grid(db->cu_count, kern, grid, stream, la)) return rc;
     if (!clade_kern) return RK_OK;
     PlaceArgs ca = args;
     ca.only_if = 4u;  // bit 2: reads of a clade
-    return go(clade_kern, ca);
+    return launch_grid(db->cu_count, clade_kern, grid, stream, ca);
 }
 
-template <int G, int BITS, int TM>
-static int launch_w(const rk_db *db, const Geometry &g, const PlaceArgs &a, hipStream_t s) {
-    // 32-bit row offsets whenever the row blob is < 4 GiB
-    return db->info.rows_bytes < ROWS_FIT32_LIMIT ? launch_variant<G, BITS, TM, false>(db, g, a, s)
-                                              : launch_variant<G, BITS, TM, true>(db, g, a, s);
-}
 template <int G, int BITS>
 static int launch_t(const rk_db *db, const Geometry &g, const PlaceArgs &a, hipStream_t s) {
+    const bool wide = db->info.rows_bytes >= ROWS_FIT32_LIMIT;  // 32-bit row offsets whenever the row blob is < 4 GiB
     switch (db->info.table_mode) {
-    case RK_TABLE_DIRECT: return launch_w<G, BITS, TM_COMPACT>(db, g, a, s);
-    case RK_TABLE_DIRECT8: return launch_w<G, BITS, TM_DIRECT8>(db, g, a, s);
-    default: return launch_w<G, BITS, TM_HASH>(db, g, a, s);
+    case RK_TABLE_DIRECT: return wide ? launch_variant<G, BITS, TM_COMPACT, true>(db, g, a, s) : launch_variant<G, BITS, TM_COMPACT, false>(db, g, a, s);
+    case RK_TABLE_DIRECT8: return wide ? launch_variant<G, BITS, TM_DIRECT8, true>(db, g, a, s) : launch_variant<G, BITS, TM_DIRECT8, false>(db, g, a, s);
+    default: return wide ? launch_variant<G, BITS, TM_HASH, true>(db, g, a, s) : launch_variant<G, BITS, TM_HASH, false>(db, g, a, s);
     }
-}
-template <int G>
-static int launch_b(const rk_db *db, const Geometry &g, const PlaceArgs &a, hipStream_t s) {
-    return db->info.bits_per_symbol == 2 ? launch_t<G, 2>(db, g, a, s) : launch_t<G, 5>(db, g, a, s);
 }
 // mid-size trees: the windowed kernel whenever the image carries window spans, nobody forced a lane-group width, the K best
 // of the tree fit one 16-lane row (keep_at_most <= 16) and the packed record fits one word per lane
@@ -1307,8 +1149,6 @@ struct TileOrder {
     }
 };
 
-// place_hash64_kernel's geometry (rk_plan.h: RK_HASH_LOG_SLOTS, RK_HASH_KEY_SLACK): a list of 320 items a lane
-constexpr uint32_t RK_HASH_MAIN_CAP = 320;
 using rk_plan::F_NONE;
 using rk_plan::F_SORTED;
 using rk_plan::F_HASH_BIG;
@@ -1321,10 +1161,10 @@ static rk_plan::Knobs plan_knobs() {  // (developer knobs: the product library r
     kn.hash_clade_small = rk_knob("RK_HASH_CLADE_SMALL") != nullptr;
     kn.wstream_always = rk_knob("RK_WSTREAM_ALWAYS") != nullptr;
     kn.no_wstream = rk_knob("RK_NO_WSTREAM") != nullptr;
-    if (const char *e = rk_knob("RK_HASH_KEY_SLACK")) kn.key_slack = (uint32_t)atoi(e);
+    kn.key_slack = (uint32_t)knob_int("RK_HASH_KEY_SLACK", (int)kn.key_slack);
     return kn;
 }
-static uint32_t hash_key_limit(uint32_t log_slots = RK_HASH_LOG_SLOTS) { return rk_plan::hash_key_limit(plan_knobs(), log_slots); }
+static uint32_t hash_key_limit(uint32_t log_slots) { return rk_plan::hash_key_limit(plan_knobs(), log_slots); }
 static bool hash_capable(const rk_db *db) {  // images whose tiles can go to place_hash64_kernel first
     if (rk_knob("RK_NO_HASH") || rk_knob("RK_NO_WSTREAM") || db->info.rows_bytes >= ROWS_FIT32_LIMIT) return false;
     return rk_knob("RK_HASH_ALWAYS") || db->wp.stream;
@@ -1344,7 +1184,7 @@ static rk_plan::In plan_in(const rk_db *db, const rk_plan::ReadShape &rs, uint32
 }
 
 static int launch_windowed(const rk_db *db, PlaceArgs a, hipStream_t stream) {
-    WindowPlan wp = db->wp;
+    const WindowPlan &wp = db->wp;
     const uint64_t n_tiles = (a.n_reads + 3) / 4;
     if (!n_tiles) return RK_OK;
     // (the reads of this batch may be longer than the 150 symbols the image was judged for: rk_plan::read_shape)
@@ -1360,28 +1200,17 @@ static int launch_windowed(const rk_db *db, PlaceArgs a, hipStream_t stream) {
     // (PlaceArgs::marked_if).  Without the verdicts (small batches) one rule serves all.
     in.verdict = a.perm != nullptr;
     const rk_plan::Plan plan = rk_plan::launch_plan(in);
+    const bool dna = db->info.bits_per_symbol == 2;
+    auto go = [&](auto kern, const WaveGeometry &w, PlaceArgs b) {  // one kernel on the batch's tiles, with its LDS layout
+        b.s_stride = w.s_stride; b.main_cap = w.main_cap; b.work_cap = w.work_cap; b.list_cap = w.list_cap;
+        return launch_grid(db->cu_count, kern, Grid{64, w.lds_wave, w.waves_cu, n_tiles}, stream, b);
+    };
     auto launch_hash = [&](uint32_t log_slots, uint32_t only_if, uint32_t only_marked) -> int {
+        const WaveGeometry w = rk_geom::hash_geometry(log_slots, hash_key_limit(log_slots), db->lds_per_cu, geom_knobs());
         PlaceArgs b = a;
-        b.only_if = only_if;
-        b.s_stride = 1u << log_slots; b.main_cap = RK_HASH_MAIN_CAP; b.work_cap = hash_key_limit(log_slots); b.list_cap = 0; b.only_marked = only_marked;
-        const size_t lds_wave = (size_t)(2 * b.s_stride + 64 + b.main_cap) * 4;
-        auto launch = [&](auto kern) -> int {
-            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
-            uint64_t per_cu = 0;
-            uint64_t want = db->lds_per_cu / lds_wave;
-            if (const char *e = rk_knob("RK_HASH_WAVES")) want = std::min<uint64_t>(want, (uint64_t)atoi(e));  // developer knob
-            if (int rc = resident_blocks(kern, 64, lds_wave, want, per_cu)) return rc;
-            uint64_t blocks = (uint64_t)db->cu_count * per_cu;
-            if (blocks > n_tiles) blocks = n_tiles;
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds_wave, stream, b);
-            return RK_OK;
-        };
-        int rc;
-        if (log_slots != RK_HASH_LOG_SLOTS) rc = db->info.bits_per_symbol == 2 ? launch(place_hash64_kernel<2, RK_HRING, RK_HNPL, 3, RK_HASH_LOG_SLOTS - 1>) : launch(place_hash64_kernel<5, RK_HRING, RK_HNPL, 2, RK_HASH_LOG_SLOTS - 1>);
-        else rc = db->info.bits_per_symbol == 2 ? launch(place_hash64_kernel<2, RK_HRING, RK_HNPL, 3, RK_HASH_LOG_SLOTS>) : launch(place_hash64_kernel<5, RK_HRING, RK_HNPL, 2, RK_HASH_LOG_SLOTS>);
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
-        return RK_OK;
+        b.only_if = only_if; b.only_marked = only_marked;
+        if (log_slots != RK_HASH_LOG_SLOTS) return dna ? go(place_hash64_kernel<2, RK_HRING, RK_HNPL, 3, RK_HASH_LOG_SLOTS - 1>, w, b) : go(place_hash64_kernel<5, RK_HRING, RK_HNPL, 2, RK_HASH_LOG_SLOTS - 1>, w, b);
+        return dna ? go(place_hash64_kernel<2, RK_HRING, RK_HNPL, 3, RK_HASH_LOG_SLOTS>, w, b) : go(place_hash64_kernel<5, RK_HRING, RK_HNPL, 2, RK_HASH_LOG_SLOTS>, w, b);
     };
     auto compact_marks = [&]() -> int {  // the marked tiles as a list + the queue's counters, for the next launch
         if (!a.marked_list) return RK_OK;
@@ -1399,242 +1228,76 @@ static int launch_windowed(const rk_db *db, PlaceArgs a, hipStream_t stream) {
         if (int rc = compact_marks()) return rc;
         if (int rc = launch_hash(RK_HASH_LOG_SLOTS, plan.hash_behind.only_if, 1u)) return rc;
     }
-    if (plan.sorted.run) {
-        // ---- place_packed16s_kernel: the sorted list of a tile's four reads + their touched bitmaps.  Seven waves per CU on
-        //      the largest windows, eight otherwise; the list holds a C2-like read (145 units, 250 at the tail) with the padding of
-        //      its window segments ----
+    if (plan.sorted.run) {  // place_packed16s_kernel
+        WaveGeometry w;
+        if (int rc = geometry_error(rk_geom::sorted_geometry(wp, db->lds_per_cu, w), db)) return rc;
         PlaceArgs b = a;
-        b.only_if = plan.sorted.only_if;  // (when another kernel takes batches of the other shape)
-        const uint32_t work_min = 96u;  // scratch of the second pass: 48 candidate keys
-        // ring of row loads: eight deep, a window's segment padded to half turns of it (four deep it left the stream waiting
-        // on HBM: ~280 cycles a step; segments padded to whole turns of eight made the largest trees' lists half filler)
-        const uint32_t ring = 8u;
-        uint32_t work = std::max(work_min, 64u + 3u * ring);  // (also: the 64 window counters of the emit, the touched bitmap of the stream)
-        work = (work + 1) & ~1u;
-        // the list: a C2-like read's 145 units (250 at the tail) + the padding of its window segments to the tile's longest
-        const uint32_t need = 200 + 5 * wp.n_win + 3 * ring;
-        const uint32_t s_str = wp.W + 16;  // a scratch word per lane in front of the window's slots
-        uint32_t budget = 0;
-        // two waves per SIMD (182 registers for DNA, 255 for amino acids).  Tried: three (167 registers, 28 bytes of scratch) and
-        // the nine to eleven waves per CU the LDS then allows -- T8k 137 -> 97, T20k 102 -> 93 Mreads/s: the kernel is bound by
-        // instruction issue, not by latency
-        const uint32_t max_waves = 8u;
-        for (uint32_t waves = max_waves; waves >= 5u; waves--) {
-            budget = (160 * 1024 / waves / 512 * 512) / 4 / 4;  // (whole 512-byte granules per wave: see resident_blocks)
-            if (budget >= s_str + work + need) break;
-        }
-        uint32_t mainc = budget - s_str - work;
-        if (mainc > 640) mainc = 640;
-        mainc &= ~3u;  // (the list is read four items at a time)
-        b.s_stride = s_str; b.main_cap = mainc; b.work_cap = work; b.list_cap = work / 2; b.only_marked = 0;
-        const size_t lds_wave = (size_t)4 * (b.s_stride + b.main_cap + b.work_cap) * 4;
-        uint32_t waves_cu = (uint32_t)(db->lds_per_cu / lds_wave);
-        if (waves_cu < 1) return fail(RK_ERR_UNSUPPORTED, "internal: windowed geometry does not fit the LDS");
-        if (waves_cu > max_waves) waves_cu = max_waves;
-        auto launch = [&](auto kern) -> int {
-            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
-            uint64_t per_cu = 0;
-            if (int rc = resident_blocks(kern, 64, lds_wave, waves_cu, per_cu)) return rc;
-            uint64_t blocks = (uint64_t)db->cu_count * per_cu;
-            if (blocks > n_tiles) blocks = n_tiles;
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds_wave, stream, b);
-            return RK_OK;
-        };
-        int rc;
-        const bool wide = wp.W > 512;  // two bitmap words a lane
-        if (db->info.bits_per_symbol == 2) rc = wide ? launch(place_packed16s_kernel<2, 8, 9, true>) : launch(place_packed16s_kernel<2, 8, 9, false>);
-        else rc = wide ? launch(place_packed16s_kernel<5, 8, 7, true>) : launch(place_packed16s_kernel<5, 8, 7, false>);  // (<= 102 residues in 16 words)
-        if (rc) return rc;
-        HIP_TRY(hipGetLastError());
+        b.only_if = plan.sorted.only_if; b.only_marked = 0;  // (only_if: when another kernel takes batches of the other shape)
+        if (int rc = dna ? (w.wide ? go(place_packed16s_kernel<2, 8, 9, true>, w, b) : go(place_packed16s_kernel<2, 8, 9, false>, w, b))
+                         : (w.wide ? go(place_packed16s_kernel<5, 8, 7, true>, w, b) : go(place_packed16s_kernel<5, 8, 7, false>, w, b)))  // (<= 102 residues in 16 words)
+            return rc;
     }
     // ---- place_packed16w_kernel: every tile (records of more than 16 words), or the tiles the first kernel handed over ----
     a.only_marked = plan.only_marked ? 1u : 0u;
     a.marked_if = plan.marked_if;
     if (a.only_marked)
         if (int rc = compact_marks()) return rc;
-    // 88 words = the 44 keys the exact select of a window needs as scratch for keep_at_most <= 8 (K + 16 candidates + 16 winners); 96 beyond
-    const uint32_t work_min = a.keep_at_most > 8 ? 96u : 88u;
-    if (wp.work_cap < work_min) {
-        wp.main_cap -= work_min - wp.work_cap;
-        wp.work_cap = work_min;
-    }
-    if (a.words_per_read > 10 && wp.work_cap > work_min) {  // reads beyond ~160 bases: a whole read in the main list matters more than one accumulate call per window
-        wp.main_cap += wp.work_cap - work_min;
-        wp.work_cap = work_min;
-    }
-    a.s_stride = wp.s_stride; a.main_cap = wp.main_cap; a.work_cap = wp.work_cap; a.list_cap = wp.work_cap / 2;
-    const size_t lds_wave = (size_t)4 * (wp.s_stride + wp.main_cap + wp.work_cap) * 4;
-    uint32_t waves_cu = (uint32_t)(db->lds_per_cu / lds_wave);
-    if (waves_cu < 1) return fail(RK_ERR_UNSUPPORTED, "internal: windowed geometry does not fit the LDS");
-    if (waves_cu > 8) waves_cu = 8;  // two waves per SIMD: the kernel's register budget
-    auto launch = [&](auto kern) -> int {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_wave));
-        uint64_t per_cu = 0;
-        if (int rc = resident_blocks(kern, 64, lds_wave, waves_cu, per_cu)) return rc;
-        uint64_t blocks = (uint64_t)db->cu_count * per_cu;
-        if (blocks > n_tiles) blocks = n_tiles;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds_wave, stream, a);
-        return RK_OK;
-    };
-    if (int rc = db->info.bits_per_symbol == 2 ? launch(place_packed16w_kernel<2, RK_WRING, 9>) : launch(place_packed16w_kernel<5, RK_WRING, 9>)) return rc;
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
+    WaveGeometry w;
+    if (int rc = geometry_error(rk_geom::windowed_geometry(wp, a.keep_at_most, a.words_per_read, db->lds_per_cu, w), db)) return rc;
+    return dna ? go(place_packed16w_kernel<2, RK_WRING, 9>, w, a) : go(place_packed16w_kernel<5, RK_WRING, 9>, w, a);
 }
 
-static int launch_place(const rk_db *db, const Geometry &g, const PlaceArgs &a_in, hipStream_t s) {
+static int launch_place(const rk_db *db, const Geometry &g, PlaceArgs a, hipStream_t s) {
     // (reads of one clade read the same rows: taken together they find them in the L2 -- scripts/clade_sorted_probe.py)
-    PlaceArgs a = a_in;
     TileOrder order;
     if (int rc = order.prepare(db, a, s, false)) return rc;
+    const bool dna = db->info.bits_per_symbol == 2;
     switch (g.G) {
-    case 8: return launch_b<8>(db, g, a, s);
-    case 16: return launch_b<16>(db, g, a, s);
-    case 32: return launch_b<32>(db, g, a, s);
-    default: return launch_b<64>(db, g, a, s);
+    case 8: return dna ? launch_t<8, 2>(db, g, a, s) : launch_t<8, 5>(db, g, a, s);
+    case 16: return dna ? launch_t<16, 2>(db, g, a, s) : launch_t<16, 5>(db, g, a, s);
+    case 32: return dna ? launch_t<32, 2>(db, g, a, s) : launch_t<32, 5>(db, g, a, s);
+    default: return dna ? launch_t<64, 2>(db, g, a, s) : launch_t<64, 5>(db, g, a, s);
     }
-}
-
-// ---- large trees: one workgroup per read ----
-struct WgGeometry {
-    uint32_t nw, s_stride, list_cap, wgs_per_cu, n_pass;
-    size_t lds;
-};
-
-// The score vector of one read (4 bytes per branch) is shared by the NW waves of a workgroup.  While it fits, one pass:
-// two workgroups of 8 waves per CU when two vectors fit (C5: 19 999 branches = 80 KB), else one of 16 waves.  Trees beyond one
-// CU's LDS (about 39 000 branches; the reference's limit is the 16-bit id: 65 534) take 2 or 4 branch-range passes per read.
-static int choose_wg_geometry(const rk_db *db, WgGeometry &g, uint32_t keep_at_most = 16) {
-    const uint32_t nb = db->info.n_branches;
-    uint32_t min_pass = 1;
-    if (const char *e = rk_knob("RK_WG_PASSES")) min_pass = (uint32_t)atoi(e);  // developer / test knob: force 2 or 4 passes on a tree that fits in one
-    for (uint32_t P : {1u, 2u, 4u}) {
-        if (P < min_pass) continue;
-        const uint32_t span = 32 / P;
-        uint32_t win = 0;
-        for (uint32_t p = 0; p < P; p++) {
-            const uint32_t lo = (uint32_t)(((uint64_t)p * span * nb) / 32), hi = (uint32_t)(((uint64_t)(p + 1) * span * nb) / 32);
-            win = std::max(win, hi - lo);
-        }
-        const uint32_t s_stride = (win + 4) & ~3u;  // >= win + 1 (word win is the scratch slot), multiple of 4 (b128 scans)
-        const size_t s_bytes = (size_t)s_stride * 4;
-        for (uint32_t wgs : {2u, 1u}) {
-            if (P > 1 && wgs == 2) continue;  // (a tree that needs passes with 8 waves fits whole with 16)
-            const uint32_t nw = wgs == 2 ? 8 : 16;
-            const size_t budget = db->lds_per_cu / wgs;
-            // P == 1: the wave winners of the level-1 select go to the hit list (free once every wave has its slices of the batch's rows);
-            // P > 1: a region of their own.  (C5's two workgroups of 80 000-byte score vectors per CU leave ~1.9 KB)
-            const size_t cand = P > 1 ? (size_t)(P * nw * keep_at_most + 16 + 2) * 8 : 0;
-            const size_t extra = 256 + cand;  // per-wave hit counters
-            const size_t min_list = P > 1 ? 66 : std::max<size_t>(66, (size_t)nw * keep_at_most + 18);
-            if (budget < s_bytes + extra + min_list * 8) continue;
-            size_t cap = (budget - s_bytes - extra) / 8;
-            if (cap > 512) cap = 512;
-            g.list_cap = (uint32_t)cap & ~1u;
-            g.wgs_per_cu = wgs;
-            g.nw = nw;
-            g.n_pass = P;
-            g.s_stride = s_stride;
-            g.lds = s_bytes + (size_t)g.list_cap * 8 + extra;
-            return RK_OK;
-        }
-    }
-    return fail(RK_ERR_UNSUPPORTED, "n_branches=%u: no score-vector window fits one CU's LDS (%zu B)", nb, db->lds_per_cu);
 }
 
 static int check_launchable(const rk_db *db) {
     if (db->windowed) return RK_OK;  // (the windowed and the ambiguity kernel hold windows of any tree; a forced dense geometry is checked at launch)
     if (db->indexed) {
         WgGeometry wg;
-        return choose_wg_geometry(db, wg);
+        return db_wg_geometry(db, wg);
     }
     Geometry g;
-    return choose_geometry(db, 7, g);
+    return db_geometry(db, 7, g);
 }
 
-template <int BITS, int TM>
-static int launch_wg_v(const rk_db *db, const WgGeometry &g, PlaceArgs a, hipStream_t stream) {
-    a.s_stride = g.s_stride;
-    a.list_cap = g.list_cap;
-    a.n_pass = g.n_pass;
-    if (!a.n_reads) return RK_OK;
-    auto launch = [&](auto kern) -> int {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
-        uint64_t per_cu = 0;
-        if (int rc = resident_blocks(kern, 64 * (int)g.nw, g.lds, g.wgs_per_cu, per_cu)) return rc;
-        uint64_t blocks = (uint64_t)db->cu_count * per_cu;
-        if (blocks > a.n_reads) blocks = a.n_reads;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * g.nw), g.lds, stream, a);
-        return RK_OK;
-    };
-    if (int rc = db->info.rows_bytes < ROWS_FIT32_LIMIT ? launch(place_wg_kernel<BITS, TM, false, RK_WG_RING>) : launch(place_wg_kernel<BITS, TM, true, RK_WG_RING>)) return rc;
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
+// ---- large trees: one workgroup per read ----
+static int launch_wg(const rk_db *db, const WgGeometry &g, PlaceArgs a, hipStream_t stream) {
+    a.s_stride = g.s_stride; a.list_cap = g.list_cap; a.n_pass = g.n_pass;
+    auto go = [&](auto kern) { return launch_grid(db->cu_count, kern, Grid{64 * (int)g.nw, g.lds, g.wgs_per_cu, a.n_reads}, stream, a); };
+    const bool dna = db->info.bits_per_symbol == 2, wide = db->info.rows_bytes >= ROWS_FIT32_LIMIT;
+    if (db->info.table_mode == RK_TABLE_HASH) {
+        if (dna) return wide ? go(place_wg_kernel<2, TM_HASH, true, RK_WG_RING>) : go(place_wg_kernel<2, TM_HASH, false, RK_WG_RING>);
+        return wide ? go(place_wg_kernel<5, TM_HASH, true, RK_WG_RING>) : go(place_wg_kernel<5, TM_HASH, false, RK_WG_RING>);
+    }
+    if (dna) return wide ? go(place_wg_kernel<2, TM_DIRECT8, true, RK_WG_RING>) : go(place_wg_kernel<2, TM_DIRECT8, false, RK_WG_RING>);
+    return wide ? go(place_wg_kernel<5, TM_DIRECT8, true, RK_WG_RING>) : go(place_wg_kernel<5, TM_DIRECT8, false, RK_WG_RING>);
 }
 
-static int launch_wg(const rk_db *db, const WgGeometry &g, const PlaceArgs &a, hipStream_t s) {
-    const bool dna = db->info.bits_per_symbol == 2;
-    if (db->info.table_mode == RK_TABLE_HASH) return dna ? launch_wg_v<2, TM_HASH>(db, g, a, s) : launch_wg_v<5, TM_HASH>(db, g, a, s);
-    return dna ? launch_wg_v<2, TM_DIRECT8>(db, g, a, s) : launch_wg_v<5, TM_DIRECT8>(db, g, a, s);
-}
-
-template <int BITS, int TM>
+// ---- the ambiguity kernel: the score vector, or a window of it, and the Samb / Camb windows (rk_geom::amb_geometry) ----
+template <int BITS>
 static int launch_ascii_v(const rk_db *db, PlaceArgs args, AmbArgs m, hipStream_t stream) {
-    // LDS: S[s_stride] + candidate list + Samb/Camb windows of `chunk` branches.  S holds the whole tree while that leaves room
-    // for the list and a minimal Samb/Camb window (then large trees take several ambiguity passes over the alternatives);
-    // beyond that (about 39 000 branches) S itself becomes a window of the tree and the read is walked once per window.
-    const uint32_t nb = db->info.n_branches;
-    const size_t list_bytes = (size_t)ASCII_LIST_CAP * 8 + ASCII_TABLE_BYTES;  // (+ the alphabet's tables, behind Camb)
-    uint32_t s_win = nb;
-    size_t chunk;
-    const bool force_windows = db->indexed && rk_knob("RK_WG_PASSES") && atoi(rk_knob("RK_WG_PASSES")) > 1;  // same test knob
-    if (!force_windows && (size_t)((nb + 4) & ~3u) * 4 + list_bytes + 8 * 64 <= db->lds_per_cu) {
-        args.s_stride = (nb + 4) & ~3u;
-        const size_t fixed = (size_t)args.s_stride * 4 + list_bytes;
-        chunk = args.s_stride;
-        const size_t budget = 64 * 1024;  // prefer several waves per CU; grow only if a single pass would not fit
-        if (fixed + 8 * chunk > budget) {
-            size_t avail = (fixed + 8 * 64 <= budget ? budget : db->lds_per_cu) - fixed;
-            chunk = avail / 8;
-            if (chunk > args.s_stride) chunk = args.s_stride;
-        }
-    } else {
-        // 12 bytes per branch of the window (S + Samb + Camb): the window is as large as one CU allows, split evenly
-        const size_t per = (db->lds_per_cu - list_bytes - 64) / 12;
-        uint32_t n_win = (uint32_t)((nb + per - 1) / per);
-        if (force_windows && n_win < 3) n_win = 3;
-        s_win = ((nb + n_win - 1) / n_win + 3) & ~3u;
-        args.s_stride = s_win + 4;
-        chunk = s_win;
-    }
-    if (chunk == 0 || args.s_stride == 0) return fail(RK_ERR_INVALID, "internal: ambiguity kernel launched without a score-vector geometry");
-    m.amb_chunk = (uint32_t)chunk;
-    m.s_win = s_win;
-    const size_t lds = (size_t)args.s_stride * 4 + list_bytes + 8 * chunk;  // S | list | Samb | Camb | tables
-    const uint64_t groups = (args.n_reads + 63) / 64;
-    uint64_t waves_cu = db->lds_per_cu / lds;
-    if (waves_cu > 32) waves_cu = 32;
-    if (!groups) return RK_OK;
-    auto launch = [&](auto kern) -> int {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        uint64_t per_cu = 0;
-        if (int rc = resident_blocks(kern, 64, lds, waves_cu, per_cu)) return rc;
-        uint64_t blocks = (uint64_t)db->cu_count * per_cu;
-        if (blocks > groups) blocks = groups;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64), lds, stream, args, m);
-        return RK_OK;
-    };
-    if (int rc = db->indexed ? launch(place_ascii_kernel<BITS, TM, true>) : launch(place_ascii_kernel<BITS, TM, false>)) return rc;
-    HIP_TRY(hipGetLastError());
-    return RK_OK;
-}
-
-static int launch_ascii(const rk_db *db, const PlaceArgs &a, const AmbArgs &m, hipStream_t s) {
-    const bool dna = db->info.bits_per_symbol == 2;
+    AmbGeometry g;
+    if (int rc = geometry_error(rk_geom::amb_geometry(db->info.n_branches, db->lds_per_cu, db->indexed, (size_t)ASCII_LIST_CAP * 8 + ASCII_TABLE_BYTES, geom_knobs(), g), db)) return rc;
+    args.s_stride = g.s_stride; m.amb_chunk = g.amb_chunk; m.s_win = g.s_win;
+    auto go = [&](auto kern) { return launch_grid(db->cu_count, kern, Grid{64, g.lds, g.waves_cu, (args.n_reads + 63) / 64}, stream, args, m); };
     switch (db->info.table_mode) {
-    case RK_TABLE_DIRECT: return dna ? launch_ascii_v<2, TM_COMPACT>(db, a, m, s) : launch_ascii_v<5, TM_COMPACT>(db, a, m, s);
-    case RK_TABLE_DIRECT8: return dna ? launch_ascii_v<2, TM_DIRECT8>(db, a, m, s) : launch_ascii_v<5, TM_DIRECT8>(db, a, m, s);
-    default: return dna ? launch_ascii_v<2, TM_HASH>(db, a, m, s) : launch_ascii_v<5, TM_HASH>(db, a, m, s);
+    case RK_TABLE_DIRECT: return db->indexed ? go(place_ascii_kernel<BITS, TM_COMPACT, true>) : go(place_ascii_kernel<BITS, TM_COMPACT, false>);
+    case RK_TABLE_DIRECT8: return db->indexed ? go(place_ascii_kernel<BITS, TM_DIRECT8, true>) : go(place_ascii_kernel<BITS, TM_DIRECT8, false>);
+    default: return db->indexed ? go(place_ascii_kernel<BITS, TM_HASH, true>) : go(place_ascii_kernel<BITS, TM_HASH, false>);
     }
+}
+static int launch_ascii(const rk_db *db, const PlaceArgs &a, const AmbArgs &m, hipStream_t s) {
+    return db->info.bits_per_symbol == 2 ? launch_ascii_v<2>(db, a, m, s) : launch_ascii_v<5>(db, a, m, s);
 }
 
 static int check_params(const rk_params *p) {
@@ -1654,16 +1317,15 @@ static bool result_complete(const rk_result *r) { return r && r->n_rows && r->br
 extern "C" const char *rk_kernel_name(const rk_db *db) {
     if (!db) return "";
     Geometry g;
-    rk_db *m = const_cast<rk_db *>(db);
     char buf[800];
+    auto named = [&]() { return (const_cast<rk_db *>(db)->kernel_name = buf).c_str(); };
     if (db->indexed && db->lanes_per_read == 0) {
         WgGeometry wg;
-        if (choose_wg_geometry(db, wg, 7) != RK_OK) return "";
+        if (db_wg_geometry(db, wg, 7) != RK_OK) return "";
         snprintf(buf, sizeof(buf), "place_wg_kernel<BITS=%u,%s,%s,U=%d> waves/WG=%u lds/WG=%zuB rows/batch=%u WGs/CU=%u passes=%u",
                  db->info.bits_per_symbol, db->info.table_mode == RK_TABLE_HASH ? "HASH" : "DIRECT8",
                  db->info.rows_bytes < ROWS_FIT32_LIMIT ? "OFF32" : "OFF64", RK_WG_RING, wg.nw, wg.lds, wg.list_cap, wg.wgs_per_cu, wg.n_pass);
-        m->kernel_name = buf;
-        return m->kernel_name.c_str();
+        return named();
     }
     if (use_windowed(db, 7, 16)) {
         // (for the reads of BASELINE's configs -- 150 bases / 100 residues -- and a batch large enough for the pre-pass's verdicts)
@@ -1676,29 +1338,26 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
         const rk_plan::FirstPlan pl = rk_plan::first_kernel_plan(in, rk_plan::plan_fit(in));
         auto what = [](rk_plan::First f) { return f == F_HASH_SMALL ? "place_hash64_kernel with 1 024 slots (the 2 048-slot one behind it)" : f == F_HASH_BIG ? "place_hash64_kernel" : f == F_SORTED ? "place_packed16s_kernel" : "place_packed16w_kernel"; };
         const rk_plan::First shown = pl.for_uniform == F_HASH_BIG || pl.for_uniform == F_HASH_SMALL ? pl.for_uniform : (pl.for_sparse == F_HASH_SMALL || pl.for_clade == F_HASH_SMALL || pl.for_clade == F_HASH_BIG) && pl.for_uniform == F_NONE ? pl.for_clade : pl.for_uniform;
-        if (shown == F_HASH_BIG || shown == F_HASH_SMALL) {
+        const bool hash_shown = shown == F_HASH_BIG || shown == F_HASH_SMALL, sparse_too = !hash_shown || pl.for_sparse != pl.for_uniform;
+        char other[360] = "";  // the classes of batch that get another first kernel
+        if (pl.for_clade != pl.for_uniform || pl.for_sparse != pl.for_uniform)
+            snprintf(other, sizeof(other), "; batches of 32 768 reads or more, judged on the device: clade-shaped -> %s%s%s", what(pl.for_clade),
+                     sparse_too ? ", uniform and sparse-hit -> " : "", sparse_too ? what(pl.for_sparse) : "");
+        if (hash_shown) {
             const uint32_t ls = shown == F_HASH_SMALL ? RK_HASH_LOG_SLOTS - 1 : RK_HASH_LOG_SLOTS;
-            char other[360] = "";
-            if (pl.for_clade != pl.for_uniform || pl.for_sparse != pl.for_uniform)
-                snprintf(other, sizeof(other), "; batches of 32 768 reads or more, judged on the device: clade-shaped -> %s%s%s", what(pl.for_clade),
-                         pl.for_sparse != pl.for_uniform ? ", uniform and sparse-hit -> " : "", pl.for_sparse != pl.for_uniform ? what(pl.for_sparse) : "");
+            const WaveGeometry hw = rk_geom::hash_geometry(ls, hash_key_limit(ls), db->lds_per_cu, geom_knobs());
             snprintf(buf, sizeof(buf), "place_hash64_kernel<BITS=%u,U=%d,NPL=%d,PU=%d,LOGS=%u> %u slots, <= %u keys a read%s (+ place_packed16w_kernel for the tiles it hands over; windows=%u x %u branches)",
-                     db->info.bits_per_symbol, RK_HRING, RK_HNPL, db->info.bits_per_symbol == 5 ? 2 : 3, ls, 1u << ls, hash_key_limit(ls), other, db->wp.n_win, db->wp.W);
+                     db->info.bits_per_symbol, RK_HRING, RK_HNPL, db->info.bits_per_symbol == 5 ? 2 : 3, ls, hw.s_stride, hw.work_cap, other, db->wp.n_win, db->wp.W);
         } else if (pl.for_uniform == F_SORTED) {
-            char other[360] = "";
-            if (pl.for_clade != pl.for_uniform || pl.for_sparse != pl.for_uniform)
-                snprintf(other, sizeof(other), "; batches of 32 768 reads or more, judged on the device: clade-shaped -> %s, uniform and sparse-hit -> %s", what(pl.for_clade), what(pl.for_sparse));
             snprintf(buf, sizeof(buf), "place_packed16s_kernel<BITS=%u,U=8,PU=%d,WIDE=%d> windows=%u x %u branches%s (+ place_packed16w_kernel for the tiles it hands over)",
-                     db->info.bits_per_symbol, db->info.bits_per_symbol == 5 ? 7 : 9, db->wp.W > 512 ? 1 : 0, db->wp.n_win, db->wp.W, other);
+                     db->info.bits_per_symbol, db->info.bits_per_symbol == 5 ? 7 : 9, rk_geom::sorted_wide(db->wp) ? 1 : 0, db->wp.n_win, db->wp.W, other);
+        } else {  // (the image's plan: a launch re-balances its two lists, rk_geom::windowed_geometry)
+            snprintf(buf, sizeof(buf), "place_packed16w_kernel<BITS=%u,U=%d,PU=9> windows=%u x %u branches lds/wave=%zuB main=%u work=%u", db->info.bits_per_symbol, RK_WRING,
+                     db->wp.n_win, db->wp.W, rk_geom::lds_of_four_reads(db->wp.s_stride, db->wp.main_cap, db->wp.work_cap), db->wp.main_cap, db->wp.work_cap);
         }
-        else
-        snprintf(buf, sizeof(buf), "place_packed16w_kernel<BITS=%u,U=%d,PU=9> windows=%u x %u branches lds/wave=%zuB main=%u work=%u",
-                 db->info.bits_per_symbol, RK_WRING, db->wp.n_win, db->wp.W, (size_t)16 * (db->wp.s_stride + db->wp.main_cap + db->wp.work_cap),
-                 db->wp.main_cap, db->wp.work_cap);
-        m->kernel_name = buf;
-        return m->kernel_name.c_str();
+        return named();
     }
-    if (choose_geometry(db, 7, g) != RK_OK) return "";
+    if (db_geometry(db, 7, g) != RK_OK) return "";
     PlaceArgs probe{};
     probe.words_per_read = 16;
     // (the tile-pipelined variant serves packed records of <= 16 words, i.e. reads of <= 256 bases / 102 residues; longer
@@ -1708,8 +1367,7 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
              pipe ? "place_packed16_kernel" : "place_packed_kernel", g.G, db->info.bits_per_symbol, db->info.table_mode == RK_TABLE_DIRECT ? (db->compact_nib ? "DIRECT4" : "DIRECT") : (db->info.table_mode == RK_TABLE_DIRECT8 ? "DIRECT8" : "HASH"),
              pipe && db->d_dense_rows ? "ROW24," : "", db->info.rows_bytes < ROWS_FIT32_LIMIT ? "ITEM32" : "ITEM64", g.G == 64 ? RK_RING64 : RK_RING, g.pu, g.lds_per_wave, g.list_cap, g.waves_per_cu,
              pipe && db->d_dense_rows && db->view.winspec ? "; batches of 32 768 reads or more that the device judges clade-shaped: 16-entry units" : "");
-    m->kernel_name = buf;
-    return m->kernel_name.c_str();
+    return named();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1754,7 +1412,7 @@ extern "C" int rk_place_packed_device(rk_db *db, const rk_params *p, uint64_t n_
     const bool use_win = !use_wg && use_windowed(db, p->keep_at_most, words_per_read);
     Geometry g{};
     WgGeometry wg{};
-    rc = use_wg ? choose_wg_geometry(db, wg, p->keep_at_most) : (use_win ? RK_OK : choose_geometry(db, p->keep_at_most, g));  // (the windowed launch has its own plan)
+    rc = use_wg ? db_wg_geometry(db, wg, p->keep_at_most) : (use_win ? RK_OK : db_geometry(db, p->keep_at_most, g));  // (the windowed launch has its own plan)
     if (rc) return rc;
     HIP_TRY(hipSetDevice(db->info.device));
     hipStream_t s = (hipStream_t)stream;

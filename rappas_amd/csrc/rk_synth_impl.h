@@ -160,7 +160,7 @@ extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
     const uint32_t sym_bits = d->alphabet == RK_ALPHABET_DNA ? 2u : 5u;
     // (used only when the image turns out not to be an indexed one; the rows are not drawn yet: their density from the spec)
     const double upc_spec = ((double)sp.key_thresh / 4294967296.0) * (d->mean_row_len / (double)ROW_UNIT + 0.5);
-    const bool want_windows = window_plan(d->n_branches, sym_bits, upc_spec, d->mean_row_len / (double)ROW_UNIT + 0.5, wp);
+    const bool want_windows = rk_geom::window_plan(d->n_branches, sym_bits, upc_spec, d->mean_row_len / (double)ROW_UNIT + 0.5, geom_knobs(), wp);
     std::vector<unsigned char> winspec;  // [space] winspec_byte(first, last window) of every row (rows are branch runs)
     if (want_windows) {
         try { winspec.assign(space, 0); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create_synth: host OOM"); }
@@ -210,7 +210,7 @@ extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
     const double mean_len = n_keys ? (double)n_entries / (double)n_keys : 0.0;
     uint64_t slot_units = 1;
     for (uint64_t i = 0; i < n_keys; i++) slot_units += (lens32[i] + ROW_UNIT - 1) / ROW_UNIT;
-    const ImageKind kind = image_kind(d->n_branches, sym_bits, d->table_mode, space, true, slot_units, max_len, mean_len);
+    const ImageKind kind = rk_geom::image_kind(d->n_branches, sym_bits, mode == RK_TABLE_DIRECT, space, slot_units, max_len, mean_len, geom_knobs());  // (AUTO is resolved by now)
     const bool indexed = kind.indexed;
     const uint64_t unit_bytes = indexed ? 64 : ROW_UNIT * 8;
     uint64_t blob_units = 1, max_units = 0;

@@ -270,7 +270,7 @@ class Workgroup(Family):
 
 
 def window_plan(nb, bits, stream):
-    """(windows, branches a window) of a windowed image (rk_engine.hip: window_plan); stream: the image was built for
+    """(windows, branches a window) of a windowed image (rk_geometry.h: window_plan); stream: the image was built for
     place_packed16s_kernel first (DNA beyond 4 500 branches with short rows, every windowed amino-acid tree, RK_WSTREAM_ALWAYS)"""
     n_win = min(64, (nb + 511) // 512 if stream else (nb + 895) // 896)
     return n_win, ((nb + n_win - 1) // n_win + 3) & ~3

@@ -25,7 +25,7 @@ def test_every_shape_is_met(name, route, Ks, amb):
 
 @pytest.mark.parametrize("name", TREES_USED)
 def test_the_window_rows_follow_the_image_windows(name):
-    """the windows planted_db cut the tree into are those rk_engine.hip's window_plan gives the image"""
+    """the windows planted_db cut the tree into are those rk_geometry.h's window_plan gives the image"""
     alphabet, _, nb, _, _, _, kw, _ = P.TREES[name]
     if "window" in kw:
         bits = 5 if alphabet == 20 else 2
