@@ -481,6 +481,63 @@ int rk_place_batch_packed_masses_samples(rk_db *db, const rk_params *p, uint64_t
                                          const uint32_t *member_sample, const uint32_t *member_weight, uint64_t *masses,
                                          uint32_t *flags_out, rk_counters *counters);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Sample-level output: clade masses and the pairwise Kantorovich-Rubinstein (earth mover's, "phylogenetic KR") distances between
+ * the samples of a sample mass buffer (what `guppy kr` / `gappa krd` compute from jplace files).  The reference has no counterpart.
+ *   Tree handle         rk_tree_create uploads the shape of a tree of B = n_branches nodes (1..65535, the B of the mass buffers):
+ *                       parent[x] = node id of x's parent, -1 for the one root (branch id = node id, as everywhere here; the ids need
+ *                       not be in pre-order); branch_len[x] = length of the edge above x, the root's entry ignored and taken as 0.
+ *                       The host walks the tree once, iteratively, children in ascending id.  rk_tree_validate: the same checks
+ *                       without a device.  RK_ERR_INVALID and a message, before any device is touched, for a NULL pointer, B out of
+ *                       range, no root or more than one, a parent >= B or equal to x, a node that does not reach the root (a cycle),
+ *                       a length that is negative, NaN or infinite.  rk_tree_destroy(NULL) is a no-op; it is the only thing that
+ *                       frees.  A handle is read-only after creation: any number of calls on any streams may share it.
+ *   Clade masses        `masses` is a sample mass buffer as rk_masses_samples_words(B, S) lays it out (S blocks of W = 2B + 4 words and
+ *                       the skipped-entries word, which is never read: with S = 1 an ordinary mass buffer of W words is accepted as it
+ *                       is).  clade[s * B + x] = the sum of mass_q30 of sample s over x's subtree, x included: the clade_mass_q30
+ *                       column of the per-edge table.  Integers: device, host twin and the table agree word for word (exact while a
+ *                       sample's total stays below 2^63, which sum of weights < 2^33 gives).  The output is WRITTEN, not added into.
+ *                       rk_clade_masses_device is asynchronous on `stream`, allocates nothing and uses no scratch of any handle.
+ *   KR distance         RAPPAS gives no position along an edge: a branch's mass sits at the midpoint of its edge, mass on the root at
+ *                       the root node.  For sample s: m_s(x) = mass_q30[x], c_s(x) its clade sum, T_s = c_s(root), h[x] =
+ *                       (double)branch_len[x] * 0.5 (h[root] = 0).  The KR integral of |P_s(y) - P_t(y)| over the tree, P(y) the share
+ *                       of the mass on the distal side of y, splits every edge into a proximal half (distal mass c) and a distal half
+ *                       (distal mass c - m):
+ *                           u_s(x) = (double)c_s(x) / (double)T_s        v_s(x) = (double)(c_s(x) - m_s(x)) / (double)T_s
+ *                           term1  = h[x] * fabs(u_s(x) - u_t(x))        term2  = h[x] * fabs(v_s(x) - v_t(x))
+ *                       all in binary64 with IEEE conversions and division, no contraction.
+ *   Order of the sum    fixed, so that every implementation gives the same bits: nodes in ascending id, in chunks of RK_KR_CHUNK ids;
+ *                       a chunk's partial p_c starts at +0.0 and takes acc = (acc + term1) + term2 node after node; D[s][t] = p_0,
+ *                       then + p_1, + p_2, ... in chunk order (B <= RK_KR_CHUNK: one sequential sum).
+ *   Consequences        D is bitwise symmetric.  D[s][s] is +0.0 for a non-empty sample.  A sample with T_s = 0 has u = v = 0 / 0 =
+ *                       NaN: its whole row and column, the diagonal included, are NaN (no special case).  The result does not depend
+ *                       on grid, tile shape or stream.
+ *   rk_kr_work_bytes        bytes of the caller-owned device workspace for S samples (the clade sums, the profiles, per-chunk partials
+ *                           when the matrix is small); 0 and a message on a bad argument or when it would pass 2^40 bytes.
+ *   rk_kr_distances_device  d_out [S * S] doubles, row-major, written.  d_work 16-byte aligned, work_bytes >= rk_kr_work_bytes: too
+ *                           small (or a NULL pointer) is RK_ERR_INVALID and nothing is launched.  1 <= S <= 65535.  Asynchronous on
+ *                           `stream`; calls that share a workspace must be ordered by the caller.
+ *   rk_kr_distances_host    the same bits in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16.
+ *   rk_kr_distances_batch   the drivers' call: host buffer in, host matrix out, through rk_kr_distances_device on db's device (the tree
+ *                           must be on it and have the database's B).  masses NULL: the buffer the last per-sample profile-only call
+ *                           (rk_place_batch_masses_samples / _packed_masses_samples, the same S) left on the device in the handle.
+ *                           Allocates and frees its workspace; returns when `out` is filled.
+ * Added without a bump of RK_VERSION (no struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_KR_CHUNK 2048u
+typedef struct rk_tree rk_tree;
+int rk_tree_create(int32_t device, uint32_t n_branches, const int32_t *parent, const float *branch_len, rk_tree **out);
+int rk_tree_validate(uint32_t n_branches, const int32_t *parent, const float *branch_len);
+void rk_tree_destroy(rk_tree *t);
+int rk_clade_masses_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint64_t *d_clade, void *stream);
+int rk_clade_masses_host(uint32_t n_branches, const int32_t *parent, uint32_t n_samples, const uint64_t *masses, uint64_t *clade);
+uint64_t rk_kr_work_bytes(const rk_tree *t, uint32_t n_samples);
+int rk_kr_distances_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, double *d_out, void *d_work, uint64_t work_bytes,
+                           void *stream);
+int rk_kr_distances_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses,
+                         double *out, uint32_t n_threads);
+int rk_kr_distances_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, double *out);
+
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the
  * packed kernels place (not BAD_CHAR / TOO_LONG / AMBIGUOUS, at least k symbols); kmers_hit = those with a row in the database

@@ -422,6 +422,28 @@ inline std::string masses_samples_table(const Tree &t, const std::vector<std::st
     return out + "#skipped_entries\t" + std::to_string(m[names.size() * W]) + "\n";
 }
 
+// The text `--kr FILE` writes: a line `#kr<TAB>S`, one line per sample in sample order -- its name and the S distances of its row,
+// `%.17g` (a NaN as `nan`, whatever its sign), tab-separated --, and a last line `#samples_without_mass<TAB>n`, n the samples whose
+// diagonal is NaN.  The twin of hostio.kr_table (byte-identical).
+inline std::string kr_table(const std::vector<std::string> &names, const double *D) {
+    const size_t S = names.size();
+    std::string out = "#kr\t" + std::to_string(S) + "\n";
+    char buf[64];
+    size_t empty = 0;
+    for (size_t s = 0; s < S; s++) {
+        out += names[s];
+        for (size_t t = 0; t < S; t++) {
+            const double d = D[s * S + t];
+            if (d != d) { out += "\tnan"; continue; }
+            snprintf(buf, sizeof(buf), "\t%.17g", d);
+            out += buf;
+        }
+        out += "\n";
+        if (D[s * S + s] != D[s * S + s]) empty++;
+    }
+    return out + "#samples_without_mass\t" + std::to_string(empty) + "\n";
+}
+
 // NumberFormat.getNumberInstance(Locale.UK), exactly 12 fraction digits, grouping commas (NewickWriter.java:61-64)
 inline std::string fmt12(float x) {
     char buf[400];

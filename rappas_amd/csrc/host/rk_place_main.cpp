@@ -39,6 +39,9 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                 to the first character C -- a header without C is an error --, samples are numbered in byte-wise order of their\n"
                  "                 names, and a read counts in every sample once per record of that sample; FILE holds, for each sample, a line\n"
                  "                 #sample<TAB>name<TAB>index and its table, and a last line #skipped_entries<TAB>n)\n"
+                 "                [--kr FILE]  (with --sample-sep: the pairwise Kantorovich-Rubinstein distances between the samples' edge masses,\n"
+                 "                 summed on the device: a line #kr<TAB>S, a line per sample with its name and S distances (%.17g), and a last line\n"
+                 "                 #samples_without_mass<TAB>n; a sample without mass has nan in its row and column)\n"
                  "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
                  "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
                  "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
@@ -51,7 +54,7 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7;
@@ -80,6 +83,7 @@ int main(int argc, char **argv) {
             else if (a == "--translate") translate = true;
             else if (a == "--masses") masses_path = val();
             else if (a == "--masses-only") masses_only_path = val();
+            else if (a == "--kr") kr_path = val();
             else if (a == "--sample-sep") { sample_sep = val(); if (sample_sep.size() != 1) throw std::runtime_error("--sample-sep takes one character"); }
             else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
@@ -315,6 +319,10 @@ int main(int argc, char **argv) {
             std::cerr << "rk_place: --sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only\n";
             return 2;
         }
+        if (!kr_path.empty() && sample_sep.empty()) {
+            std::cerr << "rk_place: --kr compares the samples of one run: it needs --sample-sep (with --masses or --masses-only)\n";
+            return 2;
+        }
         const bool only_convert = !save_image.empty() && fasta.empty() && out.empty() && !masses_only;
         if (n_sources != 1 || (!only_convert && (fasta.empty() || (out.empty() && !masses_only))) || (only_convert && !dbimage.empty())) return usage();
         uint32_t amb_mode;
@@ -338,6 +346,24 @@ int main(int argc, char **argv) {
             const int rc = strand == RK_STRAND_FORWARD ? rk_place_batch(h, pp, m, sq, so, rs, c) : rk_place_batch_strands(h, pp, strand, m, sq, so, rs, c);
             if (rc != RK_OK) throw std::runtime_error(std::string(strand == RK_STRAND_FORWARD ? "rk_place_batch: " : "rk_place_batch_strands: ") + rk_last_error());
         };
+        // --kr: the samples' distance matrix from the sample mass buffer -- `words` on the host, or nullptr: where the per-sample
+        // profile-only call left it on the device -- over the database's tree, through rk_kr_distances_batch
+        rk_db *kr_db = nullptr;  // (the handle, once it is open)
+        auto write_kr = [&](const rkh::Tree &t, const rkh::SampleMembers &sm, const uint64_t *words) {
+            if (kr_path.empty()) return;
+            const uint32_t B = (uint32_t)t.nodes.size(), S = (uint32_t)sm.names.size();
+            std::vector<int32_t> parent(B);
+            std::vector<float> bl(B);
+            for (uint32_t x = 0; x < B; x++) { parent[x] = t.nodes[x].parent; bl[x] = t.nodes[x].bl; }
+            rk_tree *kt = nullptr;
+            if (rk_tree_create(device, B, parent.data(), bl.data(), &kt) != RK_OK) throw std::runtime_error(std::string("rk_tree_create: ") + rk_last_error());
+            struct TreeGuard { rk_tree *p; ~TreeGuard() { rk_tree_destroy(p); } } tree_guard{kt};
+            std::vector<double> D((size_t)S * S);
+            if (rk_kr_distances_batch(kr_db, kt, S, words, D.data()) != RK_OK) throw std::runtime_error(std::string("rk_kr_distances_batch: ") + rk_last_error());
+            std::ofstream kf(kr_path, std::ios::binary);
+            if (!kf) throw std::runtime_error("cannot write " + kr_path);
+            kf << rkh::kr_table(sm.names, D.data());
+        };
         // --masses: the per-edge table of the whole run.  The results are on the host already, so the sums are rk_masses_accumulate_host's;
         // the weight of a unique read is the number of FASTA records it stands for, so the table speaks of reads
         // (--sample-sep: `sm` holds the samples and the membership entries of the unique reads, and the table is one per sample)
@@ -355,6 +381,7 @@ int main(int argc, char **argv) {
                 std::ofstream mf(masses_path, std::ios::binary);
                 if (!mf) throw std::runtime_error("cannot write " + masses_path);
                 mf << rkh::masses_samples_table(t, sm->names, words.data(), words.size());
+                write_kr(t, *sm, words.data());
                 return;
             }
             std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);
@@ -379,6 +406,7 @@ int main(int argc, char **argv) {
                 std::ofstream mf(masses_only_path, std::ios::binary);
                 if (!mf) throw std::runtime_error("cannot write " + masses_only_path);
                 mf << rkh::masses_samples_table(t, sm->names, words.data(), words.size());
+                write_kr(t, *sm, nullptr);  // (the buffer is still on the device in the handle)
                 return;
             }
             std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);
@@ -433,6 +461,7 @@ int main(int argc, char **argv) {
             if (rk_db_create(&d, &db) != RK_OK) throw std::runtime_error(std::string("rk_db_create: ") + rk_last_error());
         }
         struct DbGuard { rk_db *p; ~DbGuard() { if (p) rk_db_destroy(p); } } db_guard{db};
+        kr_db = db;
         if (translate) {
             rk_db_info info;
             if (rk_db_get_info(db, &info) != RK_OK) throw std::runtime_error(std::string("rk_db_get_info: ") + rk_last_error());

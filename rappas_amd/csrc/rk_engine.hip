@@ -228,6 +228,7 @@ struct rk_db {
     rk_workspace ws[4];                // device buffers + stream per in-flight chunk (grow-only)
     GrowBuf d_masses;                  // the masses sink of the host path: 2 * B + 4 words the four streams add into,
     PinBuf h_masses;                   // and where they arrive on the host (allocated at the first profile-only call)
+    uint32_t masses_samples = 0;       // the samples whose buffers the last profile-only call left in d_masses (0: one whole-batch buffer, or none)
     std::string kernel_name;
     // Scratch of the launches themselves (the tile order's keys / histogram / permutation, the marks of the tiles one kernel hands to
     // the next): one grow-only block per stream a caller has launched on, owned by the handle -- the library allocates from no pool
@@ -1760,6 +1761,7 @@ static rk::PackSpec pack_spec(const Alphabet &A, uint32_t alphabet, uint32_t bit
 }
 
 #include "rk_hostpath_impl.h"
+#include "rk_samples_impl.h"  // the tree handle, clade sums and KR distances
 
 // AmbigSequenceKnife.initTables' char -> state part (AmbigSequenceKnife.java:103-130) on the host, for callers that would rather
 // ship 2 / 5 bits per symbol over PCIe than 8: the same records, lengths and flags pack_reads_kernel produces (rk_pack_host.cpp:

@@ -299,6 +299,7 @@ class HostPath {
         hipStream_t s = db_->ws[0].stream;
         RK_TRY(db_->d_masses.reserve(masses_bytes()));
         RK_TRY(db_->h_masses.reserve(masses_bytes(), node_, device_));
+        db_->masses_samples = sink_.n_samples;  // (rk_kr_distances_batch reads the buffer where it lies)
         RK_TRY(hip_rc(hipMemsetAsync(db_->d_masses.p, 0, masses_bytes(), s), "hipMemsetAsync"));
         return hip_rc(hipStreamSynchronize(s), "hipStreamSynchronize");
     }

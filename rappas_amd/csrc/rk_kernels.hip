@@ -22,6 +22,7 @@
 #include "rk_compact32.h"
 #include "rk_translate.h"
 #include "rk_masses.h"
+#include "rk_samples.h"
 
 #include <type_traits>
 #ifndef RK_ROW_NT

@@ -1,0 +1,137 @@
+// rk_samples_host.h -- the host side of the sample-level calls: the checks and the one walk of a tree behind
+// rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel and kr_pairs_kernel (rk_samples.h) behind
+// rk_clade_masses_host and rk_kr_distances_host.  Header-only, plain C++, like rk_masses_host.h.  Not part of the C ABI.
+//
+// The KR distance is written as include/rappas_place.h defines it, term by term and in the order fixed there, so that the device and
+// this file give the same bits.  The reference has no counterpart: it stops at the jplace it writes.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+namespace rk {
+
+constexpr uint32_t KR_CHUNK = 2048;  // RK_KR_CHUNK: node ids per partial sum
+
+// What one walk of a tree leaves: pre-order position and subtree size of every node, the node at every position.  Children are taken
+// in ascending id, so the walk is a function of the parent array alone.
+struct TreeWalk {
+    uint32_t root = 0;
+    std::vector<uint32_t> pre, size, node_at;
+};
+
+// The checks of rk_tree_validate, then the walk (iterative: a caterpillar is B - 1 deep).  branch_len == nullptr: the lengths are not
+// part of the call (rk_clade_masses_host).  0, or -1 with a message in `msg`; nothing else is written on failure.
+inline int tree_walk(const char *who, uint32_t B, const int32_t *parent, const float *branch_len, bool need_len, TreeWalk &w, char *msg, size_t msg_len) {
+    auto bad = [&](const char *fmt, auto... a) { snprintf(msg, msg_len, fmt, who, a...); return -1; };
+    if (B < 1 || B > 65535) return bad("%s: n_branches=%u must be in 1..65535", B);
+    if (!parent) return bad("%s: null parent array");
+    if (need_len && !branch_len) return bad("%s: null branch_len array");
+    int64_t root = -1;
+    std::vector<uint32_t> first(B + 1, 0);  // children of x, as a CSR filled in id order: ascending
+    for (uint32_t x = 0; x < B; x++) {
+        const int32_t p = parent[x];
+        if (p == -1) {
+            if (root >= 0) return bad("%s: nodes %u and %u both have parent -1: one root, not more", (uint32_t)root, x);
+            root = x;
+        } else if (p < 0 || (uint32_t)p >= B) {
+            return bad("%s: parent[%u]=%d is outside 0..%u", x, p, B - 1);
+        } else if ((uint32_t)p == x) {
+            return bad("%s: parent[%u] is the node itself", x);
+        } else {
+            first[(uint32_t)p + 1]++;
+        }
+    }
+    if (root < 0) return bad("%s: no node has parent -1: the tree has no root");
+    if (branch_len)
+        for (uint32_t x = 0; x < B; x++)
+            if (x != (uint32_t)root && !(branch_len[x] >= 0.0f && std::isfinite(branch_len[x])))
+                return bad("%s: branch_len[%u]=%g must be finite and not negative", x, (double)branch_len[x]);
+    for (uint32_t x = 0; x < B; x++) first[x + 1] += first[x];
+    std::vector<uint32_t> kids(B ? B - 1 : 0), fill(first.begin(), first.end() - 1);
+    for (uint32_t x = 0; x < B; x++)
+        if ((int64_t)x != root) kids[fill[(uint32_t)parent[x]]++] = x;
+    std::vector<uint32_t> pre(B, 0), size(B, 1), node_at(B, 0), next(first.begin(), first.end() - 1), stack;
+    uint32_t n = 0;
+    stack.push_back((uint32_t)root);
+    node_at[0] = (uint32_t)root;
+    n = 1;
+    while (!stack.empty()) {
+        const uint32_t x = stack.back();
+        if (next[x] < first[x + 1]) {
+            const uint32_t c = kids[next[x]++];
+            pre[c] = n;
+            node_at[n++] = c;
+            stack.push_back(c);
+        } else {
+            stack.pop_back();
+            if (!stack.empty()) size[stack.back()] += size[x];
+        }
+    }
+    if (n != B) {  // whoever was not met hangs on a cycle
+        std::vector<char> met(B, 0);
+        for (uint32_t p = 0; p < n; p++) met[node_at[p]] = 1;
+        uint32_t x = 0;
+        while (met[x]) x++;
+        return bad("%s: node %u does not reach the root (a cycle among the parents)", x);
+    }
+    w.root = (uint32_t)root;
+    w.pre.swap(pre);
+    w.size.swap(size);
+    w.node_at.swap(node_at);
+    return 0;
+}
+
+// h[x]: half the length of the edge above x, 0 for the root
+inline double kr_half_length(const float *branch_len, uint32_t x, uint32_t root) { return x == root ? 0.0 : (double)branch_len[x] * 0.5; }
+
+// The clade sums of one sample: c[x] = mass_q30 over x's subtree, x included.  Backwards along the pre-order every node is met after
+// its whole subtree, so it hands a finished sum to its parent.  Integers: exact, any order gives the same words.
+inline void clade_masses_sample(const TreeWalk &w, const int32_t *parent, const uint64_t *mass, uint64_t *c) {
+    const uint32_t B = (uint32_t)w.node_at.size();
+    for (uint32_t x = 0; x < B; x++) c[x] = mass[x];
+    for (uint32_t p = B; p-- > 1;) {
+        const uint32_t x = w.node_at[p];
+        c[(uint32_t)parent[x]] += c[x];
+    }
+}
+
+// The normalised profiles of one sample: u[x] = c(x) / T, v[x] = (c(x) - m(x)) / T, T = c(root).  T == 0: every entry is 0 / 0.
+inline void kr_profiles_sample(uint32_t B, uint32_t root, const uint64_t *mass, const uint64_t *c, double *u, double *v) {
+    const double T = (double)c[root];
+    for (uint32_t x = 0; x < B; x++) {
+        u[x] = (double)c[x] / T;
+        v[x] = (double)(c[x] - mass[x]) / T;
+    }
+}
+
+// D(s, t) from the profiles of the two samples, in the order of the definition: nodes in ascending id, a partial per KR_CHUNK ids
+// that starts at +0.0 and takes (acc + term1) + term2 node after node; the partials are added in chunk order, the first one as it is.
+inline double kr_pair(uint32_t B, const double *h, const double *us, const double *vs, const double *ut, const double *vt) {
+    double d = 0.0;
+    for (uint32_t x0 = 0; x0 < B; x0 += KR_CHUNK) {
+        const uint32_t x1 = x0 + KR_CHUNK < B ? x0 + KR_CHUNK : B;
+        double acc = 0.0;
+        for (uint32_t x = x0; x < x1; x++) {
+            const double term1 = h[x] * std::fabs(us[x] - ut[x]);
+            const double term2 = h[x] * std::fabs(vs[x] - vt[x]);
+            acc = (acc + term1) + term2;
+        }
+        d = x0 == 0 ? acc : d + acc;
+    }
+    return d;
+}
+
+// Rows s = s_lo, s_lo + s_step, ... of the matrix: the pairs (s, t >= s), each written at [s][t] and [t][s].  u and v hold the
+// profiles sample after sample, B doubles each.
+inline void kr_rows(uint32_t B, uint32_t S, const double *h, const double *u, const double *v, uint32_t s_lo, uint32_t s_step, double *out) {
+    for (uint64_t s = s_lo; s < S; s += s_step)
+        for (uint64_t t = s; t < S; t++) {
+            const double d = kr_pair(B, h, u + s * B, v + s * B, u + t * B, v + t * B);
+            out[s * S + t] = d;
+            out[t * S + s] = d;
+        }
+}
+
+}  // namespace rk

@@ -1,0 +1,268 @@
+// rk_samples_impl.h -- #included by rk_engine.hip: the sample-level entry points -- the tree handle (rk_tree_*), the
+// clade sums of sample mass buffers (rk_clade_masses_device / _host) and the KR distance matrix (rk_kr_distances_device / _host /
+// _batch) -- over the kernels of rk_samples.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses
+// call filled; they touch no placement kernel and no launch scratch, and only rk_kr_distances_batch touches a database handle.
+#pragma once
+
+#include "rk_samples_host.h"
+
+static_assert(RK_KR_CHUNK == rk::KR_CHUNK && RK_KR_CHUNK == KR_CHUNK_IDS, "one chunk rule for the header, the host twin and the kernel");
+constexpr uint64_t RK_KR_MAX_WORK_BYTES = 1ull << 40;
+constexpr uint64_t RK_KR_MAX_PART_BYTES = 1ull << 28;  // per-chunk partials while they stay below 256 MiB: beyond, the tiles alone fill the device
+
+struct rk_tree {
+    int32_t device = 0;
+    uint32_t B = 0, root = 0;
+    // one block: node_at[B] | end_at[B] | span_node[n_span] | span_end[n_span] | span_off[chunks + 1] (32-bit), then h[B] (binary64)
+    void *d_block = nullptr;
+    const u32 *node_at = nullptr, *end_at = nullptr, *span_node = nullptr, *span_end = nullptr, *span_off = nullptr;
+    const double *h = nullptr;
+};
+
+extern "C" int rk_tree_validate(uint32_t n_branches, const int32_t *parent, const float *branch_len) {
+    rk::TreeWalk w;
+    return rk::tree_walk("rk_tree_validate", n_branches, parent, branch_len, true, w, g_err, sizeof(g_err)) ? RK_ERR_INVALID : RK_OK;
+}
+
+extern "C" void rk_tree_destroy(rk_tree *t) {
+    if (!t) return;
+    if (t->d_block) {
+        int prev = -1;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(t->device);
+        (void)hipFree(t->d_block);
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+    delete t;
+}
+
+extern "C" int rk_tree_create(int32_t device, uint32_t n_branches, const int32_t *parent, const float *branch_len, rk_tree **out) {
+    const char *who = "rk_tree_create";
+    if (!out) return fail(RK_ERR_INVALID, "%s: null out", who);
+    *out = nullptr;
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    const uint32_t B = n_branches, n_chunks = (B + CLADE_CHUNK - 1) / CLADE_CHUNK;
+    // the nodes whose pre-order interval leaves the chunk it starts in, by the chunk it ends in (clade_masses_kernel)
+    std::vector<uint32_t> end_at(B), span_off(n_chunks + 1, 0);
+    for (uint32_t p = 0; p < B; p++) {
+        end_at[p] = p + w.size[w.node_at[p]];
+        if ((end_at[p] - 1) / CLADE_CHUNK != p / CLADE_CHUNK) span_off[(end_at[p] - 1) / CLADE_CHUNK + 1]++;
+    }
+    for (uint32_t c = 0; c < n_chunks; c++) span_off[c + 1] += span_off[c];
+    const uint32_t n_span = span_off[n_chunks];
+    std::vector<uint32_t> span_node(n_span), span_end(n_span), fill(span_off.begin(), span_off.end() - 1);
+    for (uint32_t p = 0; p < B; p++)
+        if ((end_at[p] - 1) / CLADE_CHUNK != p / CLADE_CHUNK) {
+            const uint32_t k = fill[(end_at[p] - 1) / CLADE_CHUNK]++;
+            span_node[k] = w.node_at[p];
+            span_end[k] = end_at[p];
+        }
+    std::vector<double> h(B);
+    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
+
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return fail(RK_ERR_NO_DEVICE, "%s: no HIP device", who);
+    if (device < 0 || device >= n_dev) return fail(RK_ERR_INVALID, "%s: device %d of %d", who, device, n_dev);
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<rk_tree, void (*)(rk_tree *)> t(new (std::nothrow) rk_tree, rk_tree_destroy);
+    if (!t) return fail(RK_ERR_NOMEM, "%s: no memory", who);
+    t->device = device;
+    t->B = B;
+    t->root = w.root;
+    const size_t n32 = 2 * (size_t)B + 2 * (size_t)n_span + n_chunks + 1, h_at = (n32 * 4 + 15) / 16 * 16;
+    HIP_TRY(hipMalloc(&t->d_block, h_at + (size_t)B * 8));
+    u32 *d32 = (u32 *)t->d_block;
+    t->node_at = d32;
+    t->end_at = d32 + B;
+    t->span_node = d32 + 2 * (size_t)B;
+    t->span_end = t->span_node + n_span;
+    t->span_off = t->span_end + n_span;
+    t->h = (const double *)((char *)t->d_block + h_at);
+    HIP_TRY(hipMemcpy((void *)t->node_at, w.node_at.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((void *)t->end_at, end_at.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    if (n_span) {
+        HIP_TRY(hipMemcpy((void *)t->span_node, span_node.data(), (size_t)n_span * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((void *)t->span_end, span_end.data(), (size_t)n_span * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy((void *)t->span_off, span_off.data(), (size_t)(n_chunks + 1) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((void *)t->h, h.data(), (size_t)B * 8, hipMemcpyHostToDevice));
+    *out = t.release();
+    return RK_OK;
+}
+
+static int samples_args(const char *who, const rk_tree *t, uint32_t S) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (S < 1 || S > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, S);
+    return RK_OK;
+}
+
+extern "C" int rk_clade_masses_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint64_t *d_clade, void *stream) {
+    const char *who = "rk_clade_masses_device";
+    if (int rc = samples_args(who, t, n_samples)) return rc;
+    if (!d_masses || !d_clade) return fail(RK_ERR_INVALID, "%s: null %s", who, d_masses ? "output" : "mass buffer");
+    HIP_TRY(hipSetDevice(t->device));
+    hipLaunchKernelGGL(clade_masses_kernel, dim3(n_samples), dim3(256), 0, (hipStream_t)stream, t->B, (u64)(2ull * t->B + 4), t->node_at, t->end_at, t->span_node,
+                       t->span_end, t->span_off, (const u64 *)d_masses, (u64 *)d_clade);
+    HIP_TRY(hipGetLastError());
+    return RK_OK;
+}
+
+extern "C" int rk_clade_masses_host(uint32_t n_branches, const int32_t *parent, uint32_t n_samples, const uint64_t *masses, uint64_t *clade) {
+    const char *who = "rk_clade_masses_host";
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, nullptr, false, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (n_samples < 1 || n_samples > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, n_samples);
+    if (!masses || !clade) return fail(RK_ERR_INVALID, "%s: null %s", who, masses ? "output" : "mass buffer");
+    const uint64_t B = n_branches, W = 2 * B + 4;
+    for (uint64_t s = 0; s < n_samples; s++) rk::clade_masses_sample(w, parent, masses + s * W, clade + s * B);
+    return RK_OK;
+}
+
+// The workspace of rk_kr_distances_device: clade[S][B] (64-bit) | u[B][S] | v[B][S] | the partials, chunks x S x S, when they are used.
+struct KrPlan {
+    uint32_t n_chunks;
+    bool to_part;
+    uint64_t clade_at, u_at, v_at, part_at, bytes;
+};
+static bool kr_plan(uint32_t B, uint32_t S, KrPlan &p) {
+    const uint64_t sb = (uint64_t)S * B * 8, ss = (uint64_t)S * S * 8;
+    p.n_chunks = (B + RK_KR_CHUNK - 1) / RK_KR_CHUNK;
+    uint64_t part_limit = RK_KR_MAX_PART_BYTES;
+    if (const char *v = rk_knob("RK_KR_PART_BYTES")) part_limit = strtoull(v, nullptr, 10);  // developer builds: both forms on small shapes
+    p.to_part = p.n_chunks > 1 && ss * p.n_chunks <= part_limit;
+    p.clade_at = 0;
+    p.u_at = sb;
+    p.v_at = 2 * sb;
+    p.part_at = 3 * sb;
+    p.bytes = 3 * sb + (p.to_part ? ss * p.n_chunks : 0);
+    return p.bytes <= RK_KR_MAX_WORK_BYTES;
+}
+
+extern "C" uint64_t rk_kr_work_bytes(const rk_tree *t, uint32_t n_samples) {
+    const char *who = "rk_kr_work_bytes";
+    if (samples_args(who, t, n_samples)) return 0;
+    KrPlan p;
+    if (!kr_plan(t->B, n_samples, p)) {
+        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+        return 0;
+    }
+    return p.bytes;
+}
+
+// The launches behind rk_kr_distances_device, each on its own for scripts/kr_rate.py (developer builds time them one by one).
+static int kr_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, double *d_out, void *d_work, const KrPlan &p, hipStream_t s, unsigned steps = 7) {
+    const uint32_t B = t->B;
+    u64 *clade = (u64 *)((char *)d_work + p.clade_at);
+    double *U = (double *)((char *)d_work + p.u_at), *V = (double *)((char *)d_work + p.v_at), *part = (double *)((char *)d_work + p.part_at);
+    if (steps & 1) {
+        hipLaunchKernelGGL(clade_masses_kernel, dim3(S), dim3(256), 0, s, B, (u64)(2ull * B + 4), t->node_at, t->end_at, t->span_node, t->span_end, t->span_off,
+                           (const u64 *)d_masses, clade);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 2) {
+        hipLaunchKernelGGL(kr_profiles_kernel, dim3((B + 31) / 32, (S + 31) / 32), dim3(256), 0, s, B, S, (u64)(2ull * B + 4), t->root, (const u64 *)d_masses,
+                           (const u64 *)clade, U, V);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 4) {
+        const uint32_t side = (S + KR_TILE - 1) / KR_TILE;
+        const uint64_t tiles = (uint64_t)side * (side + 1) / 2;
+        hipLaunchKernelGGL(kr_pairs_kernel, dim3((unsigned)tiles, p.to_part ? p.n_chunks : 1), dim3(256), 0, s, B, S, side, p.to_part ? 1u : p.n_chunks,
+                           p.to_part ? 1u : 0u, (const double *)U, (const double *)V, t->h, d_out, part);
+        HIP_TRY(hipGetLastError());
+        if (p.to_part) {
+            const uint64_t n = (uint64_t)S * S;
+            hipLaunchKernelGGL(kr_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u64)n, p.n_chunks, (const double *)part, d_out);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return RK_OK;
+}
+
+extern "C" int rk_kr_distances_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, double *d_out, void *d_work, uint64_t work_bytes,
+                                      void *stream) {
+    const char *who = "rk_kr_distances_device";
+    if (int rc = samples_args(who, t, n_samples)) return rc;
+    KrPlan p;
+    if (!kr_plan(t->B, n_samples, p)) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+    if (!d_masses || !d_out) return fail(RK_ERR_INVALID, "%s: null %s", who, d_masses ? "output" : "mass buffer");
+    if (!d_work || work_bytes < p.bytes)
+        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_kr_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
+    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    HIP_TRY(hipSetDevice(t->device));
+    unsigned steps = 7;
+    if (const char *v = rk_knob("RK_KR_STEPS")) steps = (unsigned)atoi(v);  // developer builds: bit 0 clade, 1 profiles, 2 pairs (scripts/kr_rate.py)
+    return kr_launch(t, n_samples, d_masses, d_out, d_work, p, (hipStream_t)stream, steps);
+}
+
+extern "C" int rk_kr_distances_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses,
+                                    double *out, uint32_t n_threads) {
+    const char *who = "rk_kr_distances_host";
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (n_samples < 1 || n_samples > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, n_samples);
+    if (!masses || !out) return fail(RK_ERR_INVALID, "%s: null %s", who, masses ? "output" : "mass buffer");
+    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
+    std::vector<uint64_t> clade;
+    std::vector<double> u, v, h;
+    try {
+        clade.resize(S * B);
+        u.resize(S * B);
+        v.resize(S * B);
+        h.resize(B);
+    } catch (const std::bad_alloc &) {
+        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
+    }
+    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
+    unsigned hw = std::thread::hardware_concurrency();
+    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
+    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
+    // samples, then rows of the matrix, dealt round to the threads (row s has S - s pairs: dealt, not cut into ranges)
+    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        for (uint64_t s = th; s < S; s += T) {
+            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
+            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
+        }
+    });
+    if (rc) return rc;
+    return masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        rk::kr_rows((uint32_t)B, (uint32_t)S, h.data(), u.data(), v.data(), (uint32_t)th, (uint32_t)T, out);
+    });
+}
+
+// The drivers' call: the matrix of a sample mass buffer on the host -- or, masses == NULL, of the one the last per-sample profile-only
+// call (rk_place_batch_masses_samples, rk_place_batch_packed_masses_samples) left on the device in the handle -- to the host.
+// Workspace and matrix are allocated for the call and freed; it waits for the result.
+extern "C" int rk_kr_distances_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, double *out) {
+    const char *who = "rk_kr_distances_batch";
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (int rc = samples_args(who, t, n_samples)) return rc;
+    if (!out) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (t->B != db->info.n_branches || t->device != db->info.device)
+        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
+    const uint64_t need = rk_kr_work_bytes(t, n_samples), words = rk_masses_samples_words(t->B, n_samples);
+    if (!need) return RK_ERR_INVALID;
+    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
+    std::lock_guard<std::mutex> lock(db->host_mutex);
+    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
+        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
+    HIP_TRY(hipSetDevice(db->info.device));
+    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
+    hipStream_t s = db->ws[0].stream;
+    GrowBuf work, d_out, d_in;
+    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
+    const uint64_t out_bytes = (uint64_t)n_samples * n_samples * 8;
+    if (int rc = work.reserve(need)) return rc;
+    if (int rc = d_out.reserve(out_bytes)) return rc;
+    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
+    if (masses) {
+        if (int rc = d_in.reserve(words * 8)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
+        d_masses = d_in.as<uint64_t>();
+    }
+    if (int rc = rk_kr_distances_device(t, n_samples, d_masses, d_out.as<double>(), work.p, need, s)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RK_OK;
+}

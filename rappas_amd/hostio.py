@@ -395,6 +395,19 @@ def masses_samples_table(tree, names, masses):
     return "".join(out)
 
 
+def kr_table(names, D):
+    """the text `--kr FILE` writes: a line `#kr<TAB>S`, one line per sample in sample order -- its name and the S distances of its row,
+    `%.17g` (a NaN as `nan`), tab-separated --, and a last line `#samples_without_mass<TAB>n`, n the samples whose diagonal is NaN.
+    The twin of rkh::kr_table (rappas_amd/csrc/host/rk_hostio.hpp), byte-identical."""
+    S = len(names)
+    D = np.asarray(D, dtype=np.float64).reshape(S, S)
+    out = [f"#kr\t{S}\n"]
+    for s, name in enumerate(names):
+        out.append(name + "".join("\tnan" if np.isnan(d) else "\t%.17g" % d for d in D[s]) + "\n")
+    out.append(f"#samples_without_mass\t{int(np.isnan(np.diagonal(D)).sum())}\n")
+    return "".join(out)
+
+
 def _fmt12(x):
     """NumberFormat.getNumberInstance(Locale.UK) with exactly 12 fraction digits (NewickWriter.java:61-64): grouping commas,
     HALF_EVEN on the exact binary value."""

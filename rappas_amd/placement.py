@@ -734,3 +734,133 @@ class PlacementProcess:
                                                   packed.data_ptr(), lens.data_ptr(), flags.data_ptr(),
                                                   C.c_void_p(st)))
         return packed, lens, flags
+
+
+# ------------------------------------------------------------------------------------------------
+# Sample-level output: clade masses and pairwise KR distances of a sample mass buffer (include/rappas_place.h)
+# ------------------------------------------------------------------------------------------------
+def _tree_arrays(parent, branch_len=None):
+    parent = np.ascontiguousarray(parent, dtype=np.int32).reshape(-1)
+    if branch_len is not None:
+        branch_len = np.ascontiguousarray(branch_len, dtype=np.float32).reshape(-1)
+        if branch_len.shape != parent.shape:
+            raise ValueError(f"branch_len holds {branch_len.shape[0]} lengths, parent {parent.shape[0]} nodes")
+    return parent, branch_len
+
+
+def _samples_in(n_branches, n_samples, masses):
+    """a host sample mass buffer as the sample-level calls read it: n_samples * (2B + 4) words, the skipped-entries word optional"""
+    masses = np.ascontiguousarray(masses, dtype=np.uint64).reshape(-1)
+    W = 2 * n_branches + 4
+    if masses.shape[0] not in (n_samples * W, n_samples * W + 1):
+        raise ValueError(f"masses holds {masses.shape[0]} words, {n_samples} samples on {n_branches} branches have {n_samples * W} (+ 1)")
+    return masses
+
+
+def tree_validate(parent, branch_len):
+    """rk_tree_validate (no GPU): the checks of EdgeTree on a parent array (-1 = the root) and the lengths of the edges above the nodes;
+    raises RkError (RK_ERR_INVALID and the message) for a tree the sample-level calls refuse"""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    _lib.check(_lib.load().rk_tree_validate(parent.shape[0], _ptr(parent), _ptr(branch_len)))
+
+
+def clade_masses_host(parent, masses, n_samples):
+    """rk_clade_masses_host (no GPU): uint64 [n_samples, B], the sum of mass_q30 over every node's subtree for each sample of a sample
+    mass buffer (with n_samples = 1 an ordinary mass buffer) -- the clade_mass_q30 column of hostio.masses_table"""
+    parent, _ = _tree_arrays(parent)
+    B = parent.shape[0]
+    masses = _samples_in(B, n_samples, masses)
+    clade = np.zeros((n_samples, B), np.uint64)
+    _lib.check(_lib.load().rk_clade_masses_host(B, _ptr(parent), n_samples, _ptr(masses), _ptr(clade)))
+    return clade
+
+
+def kr_distances_host(parent, branch_len, masses, n_samples, threads=0):
+    """rk_kr_distances_host (no GPU): float64 [n_samples, n_samples], the pairwise Kantorovich-Rubinstein distances between the samples
+    of a sample mass buffer on the tree (parent, branch_len) -- the bits EdgeTree.kr_distances gives on the device.  A sample without
+    mass has a NaN row and column."""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    B = parent.shape[0]
+    masses = _samples_in(B, n_samples, masses)
+    out = np.zeros((n_samples, n_samples), np.float64)
+    _lib.check(_lib.load().rk_kr_distances_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), _ptr(out), threads))
+    return out
+
+
+class EdgeTree:
+    """rk_tree: the shape of a reference tree on the device -- parent[x] the node id of x's parent (-1 for the root), branch_len[x] the
+    length of the edge above x -- for the sample-level calls over device mass buffers.  Takes and returns torch device tensors and owns
+    its workspace (grow-only, one a tree: calls on different streams that overlap in time need a tree each)."""
+
+    def __init__(self, parent, branch_len, device=0):
+        parent, branch_len = _tree_arrays(parent, branch_len)
+        self._lib = _lib.load()
+        self.n_branches = parent.shape[0]
+        self.device = device
+        self._h = C.c_void_p()
+        self._work_buf = None
+        _lib.check(self._lib.rk_tree_create(device, self.n_branches, _ptr(parent), _ptr(branch_len), C.byref(self._h)))
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise RuntimeError("EdgeTree is closed")
+        return self._h
+
+    def _masses(self, masses, n_samples):
+        import torch
+        W = 2 * self.n_branches + 4
+        if (masses.dtype != torch.int64 or not masses.is_contiguous() or not masses.is_cuda or masses.device.index != self.device
+                or masses.numel() not in (n_samples * W, n_samples * W + 1)):
+            raise ValueError(f"masses must be a contiguous int64 tensor of {n_samples * W} (+ 1) words on cuda:{self.device}")
+        return masses.device
+
+    def clade_masses(self, masses, n_samples, stream=None):
+        """rk_clade_masses_device: int64 tensor [n_samples, B] (the bits are unsigned), written; asynchronous on the stream"""
+        import torch
+        dev = self._masses(masses, n_samples)
+        clade = torch.empty((n_samples, self.n_branches), dtype=torch.int64, device=dev)
+        _lib.check(self._lib.rk_clade_masses_device(self.handle, n_samples, masses.data_ptr(), clade.data_ptr(), C.c_void_p(_stream(dev, stream))))
+        return clade
+
+    def kr_work_bytes(self, n_samples):
+        need = int(self._lib.rk_kr_work_bytes(self.handle, n_samples))
+        if not need:
+            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
+        return need
+
+    def kr_distances(self, masses, n_samples, stream=None):
+        """rk_kr_distances_device: float64 tensor [n_samples, n_samples], written; asynchronous on the stream"""
+        import torch
+        dev = self._masses(masses, n_samples)
+        need = self.kr_work_bytes(n_samples)
+        if self._work_buf is None or self._work_buf.numel() < need:
+            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        out = torch.empty((n_samples, n_samples), dtype=torch.float64, device=dev)
+        _lib.check(self._lib.rk_kr_distances_device(self.handle, n_samples, masses.data_ptr(), out.data_ptr(), self._work_buf.data_ptr(),
+                                                    self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+        return out
+
+    def kr_distances_batch(self, db, n_samples, masses=None):
+        """rk_kr_distances_batch, the drivers' call: float64 array [n_samples, n_samples] on the host from a host sample mass buffer --
+        or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through
+        rk_kr_distances_device on db's device; returns when the matrix is there"""
+        if masses is not None:
+            masses = _samples_in(self.n_branches, n_samples, masses)
+            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
+                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        out = np.zeros((n_samples, n_samples), np.float64)
+        _lib.check(self._lib.rk_kr_distances_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            self._lib.rk_tree_destroy(self._h)
+            self._h = C.c_void_p()
+        self._work_buf = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
