@@ -61,6 +61,7 @@ struct Stamps {
         t_ = n_;
     }
     __device__ __forceinline__ void add(int slot, unsigned long long n) { st_[slot] += n; }  // (slots used as event counters)
+    __device__ __forceinline__ Stamps *ptr() { return this; }  // for a callee that stamps only when it is handed one
     __device__ __forceinline__ void store(unsigned long long index) const {                   // row `index` of rk_stamp_buf
         for (int i = 0; i < 16; i++) rk_stamp_buf[index * 16 + i] = st_[i];
     }
@@ -69,6 +70,7 @@ struct Stamps {
 struct Stamps {
     __device__ __forceinline__ void mark(int) {}
     __device__ __forceinline__ void add(int, unsigned long long) {}
+    __device__ __forceinline__ Stamps *ptr() { return nullptr; }
     __device__ __forceinline__ void store(unsigned long long) const {}
 };
 #endif
@@ -653,6 +655,125 @@ __device__ __forceinline__ void accumulate_units(u32 *S, const u32 *items, int w
     }
 }
 
+// place_packed16_kernel's form of accumulate_units, cut in two.  The ring of U row units in flight, and the list items of the U steps
+// behind them, are filled by units_issue (the first U gathers of a list and the next U items) and run down by units_run: the kernel
+// fills the ring from inside its emit phase when the head of the list is final early, and from its flush otherwise (DESIGN.md 4.1a
+// "Round 9").  The steps are accumulate_units' steps; the other kernels keep that function as it was, instruction for instruction.
+template <int U>
+struct UnitRing {
+    u32 sb[U], it[U];
+    float sc[U];
+};
+template <int G>
+__device__ __forceinline__ void unit_issue(__amdgpu_buffer_rsrc_t rs, u32 item, u32 li, u32 &b, float &v) {
+    const u32 li8 = li * 8;
+    u32 off = item + li8;  // G == 16: the low bits of an item are zero
+    if (G > 16) off = ((li >> 4) <= (item & 7u)) ? (item & ~127u) + li8 : ITEM_FILLER;  // (li >> 4: which 128-byte unit of the chunk this lane reads)
+    if (RK_ABLATE & 16) off = li8;
+    const v2u32 e = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off, 0, RK_ROW_AUX);
+    b = e.x;  // (left untouched until its step: anything computed from it here would wait for the load and serialise the ring)
+    v = __uint_as_float(e.y);
+}
+template <int G, int U>
+__device__ __forceinline__ void units_issue(UnitRing<U> &r, const u32 *items, u32 li, __amdgpu_buffer_rsrc_t rs) {
+#pragma unroll
+    for (int u = 0; u < U; u++) unit_issue<G>(rs, items[u], li, r.sb[u], r.sc[u]);
+#pragma unroll
+    for (int u = 0; u < U; u++) r.it[u] = items[U + u];
+}
+// TILE: the caller is place_packed16_kernel, whose flush writes fillers up to wcnt + 2U.  Its loop runs whole blocks of U steps only
+// while more than U - 2 steps are left, and ends with one, two or three pairs of steps (wave-uniform: wcnt is scalar) that feed the
+// ring no more: what would follow are fillers, whose loads make no memory request.  The loop's block stays one basic block -- an exit
+// test between the steps of the unrolled body cost 12 % of the kernel (DESIGN.md 5 "Round 9"): the scheduler interleaves steps inside
+// a block only -- and the pairs are nested, not three blocks side by side: the ends of such blocks differ in nothing but the ring
+// places they name, the compiler merges them into one block that indexes the ring by a variable, and the ring goes to scratch memory.
+template <int F, int N, bool B> struct StepBlock { static constexpr int first = F, steps = N; static constexpr bool feed = B; };
+template <int G, int U, bool MONO, bool WIN = false, bool D24 = false, bool TILE = false>
+__device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *items, int wcnt, u32 li, __amdgpu_buffer_rsrc_t rs, float QT, float T,
+                                          u32 wlo4p4 = 4u, u32 w4 = 0xFFFFFFFFu, Stamps *stamps = nullptr) {
+    static_assert(!D24 || (G == 16 && !WIN), "dense units: 16-lane groups, whole trees");
+    static_assert(!TILE || U == 8, "a tail of up to three pairs of steps");
+    static_assert(rk_slots24::SLOT_BITS == SLOT24_BITS, "rk_slots24.h unpacks the slot words rk_device.h defines");
+    const rk_slots24::Shifts sh24 = rk_slots24::lane_shifts(li);  // D24: where this lane's two slots sit in the word the DPP leaves it
+    u32(&sb)[U] = r.sb;
+    u32(&it)[U] = r.it;
+    float(&sc)[U] = r.sc;
+    auto issue = [&](u32 item, u32 &b, float &v) { unit_issue<G>(rs, item, li, b, v); };
+    auto slot_of = [&](u32 b) {  // WIN: S holds one window of the tree -- slot offsets are rebased, everything outside goes to the scratch word
+        if (!WIN) return b;
+        const u32 t = b - wlo4p4;
+        return (t < w4) ? t + 4u : 0u;
+    };
+    // D24, a ring entry is b = w[2li] (d of entry li), v = w[2li + 1] (lanes 0..7: d of entry 16 + li; lanes 8..15: the slot word)
+    auto prepare = [&](float v, u32 *&pa, u32 *&pb) {
+        const int w = (int)__float_as_uint(v);
+        // row_ror:8, bank_mask 0x3 = lanes 0..7 of each row are written, lanes 8..15 keep `old` = their own word: no v_mov 0, no select
+        const u32 r = (u32)__builtin_amdgcn_update_dpp(w, w, 0x128, 0xF, 0x3, false);
+        const rk_slots24::Slots s = rk_slots24::lane_slots(sh24, r);
+        pa = S + s.a;
+        pb = S + s.b;
+    };
+    if (stamps) {  // (stamps build: the wait for the first row unit, on its own)
+        asm volatile("" ::"v"(sc[0]));
+        stamps->mark(7);
+    }
+    int s0 = 0;
+    u32 *pa = S, *pb = S;  // D24: the two words of the step to come
+    if (D24) prepare(sc[0], pa, pb);
+    // steps s0 + first .. s0 + first + steps - 1, from the ring places first ..; feed: each place takes the unit of step + U and the
+    // item of step + 2U
+    auto block = [&](auto kind) __attribute__((always_inline)) {
+        constexpr int F = decltype(kind)::first, N = decltype(kind)::steps;
+        constexpr bool FEED = decltype(kind)::feed;
+#pragma unroll
+        for (int u = F; u < F + N; u++) {
+            if (D24) {
+                u32 *na = pa, *nb = pb;
+                if (RK_ABLATE & 8) {  // timing-only: keep the loads and the unpacking alive, skip the LDS update
+                    asm volatile("" ::"v"(pa), "v"(pb), "v"(sb[u]), "v"(sc[u]));
+                    prepare(sc[(u + 1) % U], na, nb);
+                } else {
+                    // Both words are read before either is written: the two slots of a lane, and those of different lanes, differ
+                    // unless both are the scratch word.
+                    const u32 oa = *pa, ob = *pb;
+                    prepare(sc[(u + 1) % U], na, nb);  // the next step's entry (after the last step: a filler's zeros)
+                    *pa = __float_as_uint(touch_base<MONO>(oa, QT) + __uint_as_float(sb[u]));
+                    *pb = __float_as_uint(touch_base<MONO>(ob, QT) + sc[u]);
+                }
+                pa = na;
+                pb = nb;
+            } else {
+                apply_slot<MONO>(S, slot_of(sb[u]), sc[u], QT, T);
+            }
+            if (FEED) {
+                issue(it[u], sb[u], sc[u]);
+                it[u] = items[s0 + 2 * U + u];
+            }
+        }
+    };
+    if (TILE) {
+        while (wcnt - s0 > U - 2) {
+            block(StepBlock<0, U, true>());
+            s0 += U;
+        }
+        const int left = wcnt - s0;  // <= U - 2
+        if (left > 0) {
+            block(StepBlock<0, 2, false>());
+            if (left > 2) {
+                block(StepBlock<2, 2, false>());
+                if (left > 4) block(StepBlock<4, 2, false>());
+            }
+        }
+        if (stamps) stamps->add(12, (unsigned long long)(s0 + (left > 0 ? (left + 1) & ~1 : 0)));  // (stamps build: the steps taken)
+        return;
+    }
+    while (true) {
+        block(StepBlock<0, U, true>());
+        s0 += U;
+        if (s0 >= wcnt) break;  // what is left in the ring are fillers
+    }
+    if (stamps) stamps->add(12, (unsigned long long)s0);
+}
 // ------------------------------------------------------------------------------------------------
 // select: top-K + LWR + output (A8/A9: PlacementProcess.java:396-451, :974-1025)
 // Order among candidates is the total order of the packed key: score desc (Float.compare), then branch id asc.
@@ -1748,16 +1869,29 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         const float QT = h.QT;
 
         int cnt = 0;  // chunk items waiting in the list
-        auto flush = [&]() {
+        // the row ring of this tile's first flush, when emit_batch has started it (ring_live, wave-uniform); it never outlives the tile:
+        // a started ring means cnt >= 2U in every group, so the flush after the emit phase runs it down at the latest
+        UnitRing<U> ring;
+        bool ring_live = false;
+        constexpr bool EARLY = D24;  // (the canonical units keep their ring start in the flush)
+        // (always_inline: left to its cost model the compiler makes the dense instance's flush a function once the step loop has its tail,
+        // and a kernel that calls one addresses the LDS, the list and PlaceArgs through flat pointers and keeps its arrays in scratch memory)
+        auto flush = [&]() __attribute__((always_inline)) {
             int wcnt = __builtin_amdgcn_readlane(cnt, 0);
             wcnt = max(wcnt, __builtin_amdgcn_readlane(cnt, 32));
             wcnt = max(wcnt, __builtin_amdgcn_readlane(cnt, 16));
             wcnt = max(wcnt, __builtin_amdgcn_readlane(cnt, 48));
-            for (int i = cnt + (int)li; i < wcnt + 2 * U; i += G) items[i] = ITEM_FILLER;
+            for (int i = cnt + (int)li; i < wcnt + 2 * U; i += G) items[i] = ITEM_FILLER;  // (a live ring's groups hold >= 2U items: its 2U items stay)
             wave_lds_fence();
-            if (a.db.mono) accumulate_units<G, U, true, false, D24>(S, items, wcnt, li, rows_rs, QT, T);
-            else accumulate_units<G, U, false, false, D24>(S, items, wcnt, li, rows_rs, QT, T);
+            stamps.mark(10);  // flush outside the ring: fillers, fences (and what the caller did since its last mark)
+            if (!ring_live) units_issue<G, U>(ring, items, li, rows_rs);
+            ring_live = false;
+            stamps.mark(11);  // the ring's U gathers and U item reads
+            if (a.db.mono) units_run<G, U, true, false, D24, true>(ring, S, items, wcnt, li, rows_rs, QT, T, 4u, 0xFFFFFFFFu, stamps.ptr());
+            else units_run<G, U, false, false, D24, true>(ring, S, items, wcnt, li, rows_rs, QT, T, 4u, 0xFFFFFFFFu, stamps.ptr());
+            stamps.mark(4);  // the steps (slot 7, inside: the wait for the first row unit)
             wave_lds_fence();
+            stamps.mark(10);
             cnt = 0;
         };
         // one batch of PU*16 positions: rows (first unit, units) -> unit items in k-mer order (or, for rows too long for the list, the
@@ -1766,6 +1900,7 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             u32 nch[PU], excl[PU], rb[PU];
             int total = 0;
             bool wide_rows = false;
+            bool early = false;  // (wave-uniform) this call has started the ring
 #pragma unroll
             for (int u = 0; u < PU; u++) {
                 if constexpr (C32) nch[u] = pos + u * G + li < Q ? rows.n[u] : 0u;  // the only gate: an absent k-mer has no units
@@ -1780,6 +1915,16 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
                 v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
                 v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
                 return v;
+            };
+            auto write_rows = [&](int u_lo, int u_hi) {  // the unit items of positions u_lo .. u_hi - 1, behind the cnt items of the list
+#pragma unroll
+                for (int u = u_lo; u < u_hi; u++) {
+                    const int base = cnt + (int)excl[u];
+                    if (nch[u] > 0) items[base] = rb[u];
+                    if (nch[u] > 1) items[base + 1] = rb[u] + 128u;
+                    for (u32 c = 2; __any(c < nch[u]); c++)
+                        if (c < nch[u]) items[base + (int)c] = rb[u] + c * 128u;
+                }
             };
             if (!__any(wide_rows)) {
                 // rows of <= 15 units each (240 entries: nearly always): four sub-batches share one scan, one byte each
@@ -1800,6 +1945,19 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
                             total += (int)((tot >> (8 * b)) & 0xFFu);
                         }
                     }
+                    if constexpr (EARLY) {
+                        // Round 9: after the first scan the items of positions 0 .. 63 are final.  When they are at least 2U in every
+                        // group of the wave (so: no missing read, no Q == 0, and the ring's 2U items all lie among them) and fit the
+                        // list, the tile's first U row gathers leave here, and the rest of the emit runs under their round trip.
+                        // First batch of a tile only (pos == 0: the list is empty in every group).
+                        if (u0 == 0 && PU > 4 && pos == 0 && !__any(total < 2 * U || total > cap_items)) {  // (more than the list holds: the parts path decides)
+                            write_rows(0, 4);
+                            wave_lds_fence();
+                            units_issue<G, U>(ring, items, li, rows_rs);
+                            __builtin_amdgcn_sched_barrier(0);  // (the gathers stay in front of the remaining scans)
+                            ring_live = early = true;
+                        }
+                    }
                 }
             } else {
 #pragma unroll
@@ -1809,10 +1967,11 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
                     total += (int)row_bcast32<15>(incl);
                 }
             }
-            if (__any(more && cnt + total > cap_items)) flush();
+            if (!early && __any(more && cnt + total > cap_items)) flush();  // (early: the list held nothing, and its ring is not to run yet)
             if (D24 && __any(more && total > cap_items)) {
                 // the batch's units do not fit an empty list: they go through it in parts, still in k-mer order (a part may
-                // end inside a row); unit c of position u is unit excl[u] + c of the batch
+                // end inside a row); unit c of position u is unit excl[u] + c of the batch.  After an early start the first part
+                // writes the same first items to the same places again (cap_items >= 2U), and its flush runs the ring that is in flight.
                 for (u32 done = 0; __any(done < (u32)total);) {
                     const u32 room = (u32)(cap_items - cnt);
 #pragma unroll
@@ -1849,14 +2008,8 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
                     wave_lds_fence();
                 }
             } else {
-#pragma unroll
-                for (int u = 0; u < PU; u++) {
-                    const int base = cnt + (int)excl[u];
-                    if (nch[u] > 0) items[base] = rb[u];
-                    if (nch[u] > 1) items[base + 1] = rb[u] + 128u;
-                    for (u32 c = 2; __any(c < nch[u]); c++)
-                        if (c < nch[u]) items[base + (int)c] = rb[u] + c * 128u;
-                }
+                if (!early) write_rows(0, PU < 4 ? PU : 4);
+                write_rows(PU < 4 ? PU : 4, PU);
                 cnt += total;
             }
         };

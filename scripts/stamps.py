@@ -47,8 +47,10 @@ lib.rk_debug_read_stamps.argtypes = [C.c_void_p, C.c_int]
 assert lib.rk_debug_read_stamps(buf, nw) == 0
 a = np.frombuffer(buf, dtype=np.uint64).reshape(nw, 16).astype(np.float64)
 tot = a.sum(1)
-names = ["tile setup", "probe (codes+gathers)", "scan+emit items", "pre-accumulate fence", "accumulate", "select (rest: reset)", "weigh+store", "-",
-         "select: scan", "select: rounds"]
+# place_packed16_kernel cuts its accumulate phase up: slot 4 is the steps alone, 7 the wait for the first row unit, 10 the flush around
+# the ring (fillers, fences), 11 the ring's gathers where the flush issues them (an early start issues them inside "scan+emit items")
+names = ["tile setup", "probe (codes+gathers)", "scan+emit items", "pre-accumulate fence", "accumulate (steps)", "select (rest: reset)", "weigh+store",
+         "accumulate: ring fill", "select: scan", "select: rounds", "accumulate: rest of flush", "accumulate: ring issue"]
 windowed = "packed16w" in db.kernel_name()
 if windowed:
     names = ["tile setup", "probe + emit", "window compaction", "window accumulate", "window scan + reset", "rounds", "redo (doubt)", "weigh+store"]
@@ -63,6 +65,8 @@ for i, nm in enumerate(names):
     print(f"  {nm:24s} {100 * np.median(a[:, i] / tot):5.1f} %   {np.median(a[:, i]) / (n / 4 / nw):8.0f} cycles/tile")
 if not windowed:  # select_topk: the locate pass of 16-lane groups, and counters (of the wave's first read / of the wave)
     print(f"  {'select: locate + re-rank':24s} {100 * np.median(a[:, 13] / tot):5.1f} %   {np.median(a[:, 13]) / (n / 4 / nw):8.0f} cycles/tile")
+    if a[:, 12].sum() > 0:  # place_packed16_kernel: slot 12 counts the accumulate steps a wave took
+        print(f"  steps per tile: {np.median(a[:, 12]) / (n / 4 / nw):.2f}")
     print(f"  reads sent to the exact scan: {100 * a[:, 14].sum() / (n / 4):.4f} %   tiles that re-rank equal scores: {100 * a[:, 15].sum() / (n / 4):.4f} %")
 if windowed:
     tiles = n / 4 / nw
