@@ -538,6 +538,52 @@ int rk_kr_distances_host(uint32_t n_branches, const int32_t *parent, const float
                          double *out, uint32_t n_threads);
 int rk_kr_distances_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, double *out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Squash clustering of the samples of a sample mass buffer (what `guppy squash` / `gappa` squash compute from jplace files): a
+ * hierarchical clustering in which a merged cluster is a new mass distribution, the average of its members, whose KR distances to
+ * every other cluster are computed afresh.  The clade profile is linear in the masses, so the profile of an averaged cluster is
+ * the average of the profiles.  The reference has no counterpart.  Fixed so that every implementation gives the same bits:
+ *   Start               u_s, v_s, h and D exactly as the KR block above defines them.  Sample s is a cluster of size n_s = 1; it is
+ *                       active iff T_s != 0.  A sample without mass never takes part: it is only counted.
+ *   Step                while two or more clusters are active: take the active pair a < b with the smallest D[a][b]; on equal
+ *                       distances the smaller a, then the smaller b.  The comparison is plain < on doubles (no NaN and no -0.0
+ *                       occurs among active pairs).
+ *   Merge               the cluster keeps slot a, b becomes inactive.  For every node x, in binary64 without contraction:
+ *                           u_a(x) = ((double)n_a * u_a(x) + (double)n_b * u_b(x)) / (double)(n_a + n_b)
+ *                       and v_a(x) likewise; then n_a += n_b.
+ *   New distances       for every other active t, D[a][t] = D[t][a] = the KR pair sum over the new u_a, v_a and u_t, v_t: the same
+ *                       terms, the same RK_KR_CHUNK rule and the same order as the KR block.
+ *   Output row k        rk_squash_merge {a, b, size, reserved = 0, distance}, 24 bytes: a and b are the smallest sample indices of
+ *                       the two clusters (by induction from a < b), size is n_a after the merge, distance is D[a][b] as picked.
+ *   Row count           n_merges = max(active - 1, 0).  Rows n_merges .. S - 2 are written as {0xFFFFFFFF, 0xFFFFFFFF, 0, 0, +0.0}.
+ *   Monotonicity        the distances need not increase from row to row (an averaged cluster may lie nearer to a third one than
+ *                       either member did).  Nothing is clamped.
+ *   rk_squash_work_bytes  bytes of the caller-owned device workspace: the KR workspace, D, the merged profile, the row partials, the
+ *                         pick scratch, the active flags and the sizes; 0 and a message on a bad argument.
+ *   rk_squash_device      d_merges [S - 1] rows and d_n_merges (one uint32_t), written.  Runs the KR matrix, then S - 1 steps of
+ *                         plain launches in stream order: no host synchronisation, which pair was picked stays on the device.
+ *                         2 <= S <= RK_SQUASH_MAX_SAMPLES (the pick rescans the matrix every step: S^3 beside the S^2 * B of the
+ *                         sums).  Otherwise the argument rules of rk_kr_distances_device: RK_ERR_INVALID and a message, nothing
+ *                         launched.  Asynchronous on `stream`.
+ *   rk_squash_host        the same bits in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16.
+ *   rk_squash_batch       the drivers' call, with the contract of rk_kr_distances_batch: masses NULL = the buffer the last per-sample
+ *                         profile-only call left in the handle.  merges [S - 1] rows and n_merges on the host; returns when they
+ *                         are filled.
+ * Added without a bump of RK_VERSION (no existing struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_SQUASH_MAX_SAMPLES 4096u
+#define RK_SQUASH_NONE 0xFFFFFFFFu
+typedef struct rk_squash_merge {
+    uint32_t a, b, size, reserved;
+    double distance;
+} rk_squash_merge;
+uint64_t rk_squash_work_bytes(const rk_tree *t, uint32_t n_samples);
+int rk_squash_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, rk_squash_merge *d_merges, uint32_t *d_n_merges, void *d_work,
+                     uint64_t work_bytes, void *stream);
+int rk_squash_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses,
+                   rk_squash_merge *merges, uint32_t *n_merges, uint32_t n_threads);
+int rk_squash_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, rk_squash_merge *merges, uint32_t *n_merges);
+
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the
  * packed kernels place (not BAD_CHAR / TOO_LONG / AMBIGUOUS, at least k symbols); kmers_hit = those with a row in the database

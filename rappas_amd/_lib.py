@@ -15,6 +15,7 @@ RK_FRAME_NONE = 0xFF  # d_frame of a read without a result (rk_place_*_translate
 RK_STRAND_FORWARD, RK_STRAND_REVERSE, RK_STRAND_BOTH = 0, 1, 2
 RK_STEP_TRANSLATED = 3  # `step` of rk_place_batch_masses beside the three strands
 STRANDS = {"forward": RK_STRAND_FORWARD, "fwd": RK_STRAND_FORWARD, "reverse": RK_STRAND_REVERSE, "rev": RK_STRAND_REVERSE, "both": RK_STRAND_BOTH}
+RK_SQUASH_MAX_SAMPLES, RK_SQUASH_NONE = 4096, 0xFFFFFFFF
 RK_OK, RK_ERR_INVALID, RK_ERR_NO_DEVICE, RK_ERR_HIP, RK_ERR_NOMEM, RK_ERR_UNSUPPORTED, RK_ERR_IO = 0, -1, -2, -3, -4, -5, -6
 
 
@@ -153,6 +154,10 @@ EXPORTS = {
     "rk_kr_distances_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rk_kr_distances_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rk_kr_distances_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rk_squash_work_bytes": (C.c_uint64, [C.c_void_p, C.c_uint32]),
+    "rk_squash_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rk_squash_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rk_squash_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_count_work_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_set_lanes_per_read": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rk_kernel_name": (C.c_char_p, [C.c_void_p]),

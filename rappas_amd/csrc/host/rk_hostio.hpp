@@ -444,6 +444,59 @@ inline std::string kr_table(const std::vector<std::string> &names, const double 
     return out + "#samples_without_mass\t" + std::to_string(empty) + "\n";
 }
 
+// A row of the squash clustering as the library writes it (rk_squash_merge of include/rappas_place.h, restated: this header does
+// not need the library's)
+struct SquashRow {
+    uint32_t a, b, size, reserved;
+    double distance;
+};
+
+// The text `--squash FILE` writes: `#squash<TAB>S<TAB>n_merges`; per merge `k<TAB>a<TAB>b<TAB>distance<TAB>size` (`%.17g`);
+// `#newick<TAB>tree;` -- leaves named by sample (single-quoted, a quote doubled, where the name holds any of ()[]':;, or white space),
+// an inner node at height distance / 2, a leaf at 0, an edge length height(parent) - height(child) as `%.17g` (negative where the
+// clustering is not monotone), children in the order a, b, no length on the root; one sample with mass gives `name;`, none `;` --;
+// `#inversions<TAB>n`, the negative edge lengths; `#samples_without_mass<TAB>n`.  with_mass: one flag per sample.  The twin of
+// hostio.squash_table (byte-identical).
+inline std::string squash_table(const std::vector<std::string> &names, const SquashRow *merges, uint32_t n_merges, const std::vector<char> &with_mass) {
+    const size_t S = names.size();
+    std::string out = "#squash\t" + std::to_string(S) + "\t" + std::to_string(n_merges) + "\n";
+    std::vector<std::string> sub(S);
+    std::vector<double> height(S, 0.0);
+    size_t n_with = 0, inversions = 0, root = S;
+    for (size_t s = 0; s < S; s++) {
+        if (!with_mass[s]) continue;
+        n_with++;
+        if (n_merges == 0) root = s;  // (one sample with mass: the tree is its name)
+        const std::string &n = names[s];
+        if (n.find_first_of("()[]':;, \t\n\r\v\f") == std::string::npos) { sub[s] = n; continue; }
+        sub[s] = "'";
+        for (char c : n) { sub[s] += c; if (c == '\'') sub[s] += c; }
+        sub[s] += "'";
+    }
+    if (n_merges == 0 && n_with != 1) root = S;
+    char buf[96];
+    for (uint32_t k = 0; k < n_merges; k++) {
+        const SquashRow &m = merges[k];
+        snprintf(buf, sizeof(buf), "%u\t%u\t%u\t%.17g\t%u\n", k, m.a, m.b, m.distance, m.size);
+        out += buf;
+        const double h = m.distance / 2, la = h - height[m.a], lb = h - height[m.b];
+        inversions += (la < 0) + (lb < 0);
+        std::string t = "(" + sub[m.a];
+        snprintf(buf, sizeof(buf), ":%.17g,", la);
+        t += buf;
+        t += sub[m.b];
+        snprintf(buf, sizeof(buf), ":%.17g)", lb);
+        t += buf;
+        sub[m.a].swap(t);
+        sub[m.b].clear();
+        height[m.a] = h;
+        root = m.a;
+    }
+    out += "#newick\t" + (root < S ? sub[root] : std::string()) + ";\n";
+    out += "#inversions\t" + std::to_string(inversions) + "\n";
+    return out + "#samples_without_mass\t" + std::to_string(S - n_with) + "\n";
+}
+
 // NumberFormat.getNumberInstance(Locale.UK), exactly 12 fraction digits, grouping commas (NewickWriter.java:61-64)
 inline std::string fmt12(float x) {
     char buf[400];

@@ -42,6 +42,9 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                [--kr FILE]  (with --sample-sep: the pairwise Kantorovich-Rubinstein distances between the samples' edge masses,\n"
                  "                 summed on the device: a line #kr<TAB>S, a line per sample with its name and S distances (%.17g), and a last line\n"
                  "                 #samples_without_mass<TAB>n; a sample without mass has nan in its row and column)\n"
+                 "                [--squash FILE]  (with --sample-sep: the squash clustering of the samples over those distances, merged on the\n"
+                 "                 device: a line #squash<TAB>S<TAB>n_merges, a line k<TAB>a<TAB>b<TAB>distance<TAB>size per merge, the tree as\n"
+                 "                 #newick<TAB>...; (an inner node at half its distance), #inversions<TAB>n and #samples_without_mass<TAB>n)\n"
                  "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
                  "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
                  "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
@@ -54,7 +57,7 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7;
@@ -84,6 +87,7 @@ int main(int argc, char **argv) {
             else if (a == "--masses") masses_path = val();
             else if (a == "--masses-only") masses_only_path = val();
             else if (a == "--kr") kr_path = val();
+            else if (a == "--squash") squash_path = val();
             else if (a == "--sample-sep") { sample_sep = val(); if (sample_sep.size() != 1) throw std::runtime_error("--sample-sep takes one character"); }
             else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
@@ -323,6 +327,10 @@ int main(int argc, char **argv) {
             std::cerr << "rk_place: --kr compares the samples of one run: it needs --sample-sep (with --masses or --masses-only)\n";
             return 2;
         }
+        if (!squash_path.empty() && sample_sep.empty()) {
+            std::cerr << "rk_place: --squash clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)\n";
+            return 2;
+        }
         const bool only_convert = !save_image.empty() && fasta.empty() && out.empty() && !masses_only;
         if (n_sources != 1 || (!only_convert && (fasta.empty() || (out.empty() && !masses_only))) || (only_convert && !dbimage.empty())) return usage();
         uint32_t amb_mode;
@@ -349,8 +357,9 @@ int main(int argc, char **argv) {
         // --kr: the samples' distance matrix from the sample mass buffer -- `words` on the host, or nullptr: where the per-sample
         // profile-only call left it on the device -- over the database's tree, through rk_kr_distances_batch
         rk_db *kr_db = nullptr;  // (the handle, once it is open)
-        auto write_kr = [&](const rkh::Tree &t, const rkh::SampleMembers &sm, const uint64_t *words) {
-            if (kr_path.empty()) return;
+        // --squash: the same, through rk_squash_batch; `host_words` is the host's copy either way (it tells which samples hold mass)
+        auto write_kr = [&](const rkh::Tree &t, const rkh::SampleMembers &sm, const uint64_t *words, const uint64_t *host_words) {
+            if (kr_path.empty() && squash_path.empty()) return;
             const uint32_t B = (uint32_t)t.nodes.size(), S = (uint32_t)sm.names.size();
             std::vector<int32_t> parent(B);
             std::vector<float> bl(B);
@@ -358,11 +367,26 @@ int main(int argc, char **argv) {
             rk_tree *kt = nullptr;
             if (rk_tree_create(device, B, parent.data(), bl.data(), &kt) != RK_OK) throw std::runtime_error(std::string("rk_tree_create: ") + rk_last_error());
             struct TreeGuard { rk_tree *p; ~TreeGuard() { rk_tree_destroy(p); } } tree_guard{kt};
-            std::vector<double> D((size_t)S * S);
-            if (rk_kr_distances_batch(kr_db, kt, S, words, D.data()) != RK_OK) throw std::runtime_error(std::string("rk_kr_distances_batch: ") + rk_last_error());
-            std::ofstream kf(kr_path, std::ios::binary);
-            if (!kf) throw std::runtime_error("cannot write " + kr_path);
-            kf << rkh::kr_table(sm.names, D.data());
+            if (!kr_path.empty()) {
+                std::vector<double> D((size_t)S * S);
+                if (rk_kr_distances_batch(kr_db, kt, S, words, D.data()) != RK_OK) throw std::runtime_error(std::string("rk_kr_distances_batch: ") + rk_last_error());
+                std::ofstream kf(kr_path, std::ios::binary);
+                if (!kf) throw std::runtime_error("cannot write " + kr_path);
+                kf << rkh::kr_table(sm.names, D.data());
+            }
+            if (!squash_path.empty()) {
+                static_assert(sizeof(rkh::SquashRow) == sizeof(rk_squash_merge), "one row layout");
+                std::vector<rkh::SquashRow> rows(S > 1 ? S - 1 : 0);
+                uint32_t n_merges = 0;
+                if (S > 1 && rk_squash_batch(kr_db, kt, S, words, (rk_squash_merge *)rows.data(), &n_merges) != RK_OK)
+                    throw std::runtime_error(std::string("rk_squash_batch: ") + rk_last_error());
+                std::vector<char> with_mass(S, 0);
+                for (uint32_t s = 0; s < S; s++)
+                    for (uint32_t x = 0; x < B && !with_mass[s]; x++) with_mass[s] = host_words[(size_t)s * (2 * (size_t)B + 4) + x] != 0;
+                std::ofstream qf(squash_path, std::ios::binary);
+                if (!qf) throw std::runtime_error("cannot write " + squash_path);
+                qf << rkh::squash_table(sm.names, rows.data(), n_merges, with_mass);
+            }
         };
         // --masses: the per-edge table of the whole run.  The results are on the host already, so the sums are rk_masses_accumulate_host's;
         // the weight of a unique read is the number of FASTA records it stands for, so the table speaks of reads
@@ -381,7 +405,7 @@ int main(int argc, char **argv) {
                 std::ofstream mf(masses_path, std::ios::binary);
                 if (!mf) throw std::runtime_error("cannot write " + masses_path);
                 mf << rkh::masses_samples_table(t, sm->names, words.data(), words.size());
-                write_kr(t, *sm, words.data());
+                write_kr(t, *sm, words.data(), words.data());
                 return;
             }
             std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);
@@ -406,7 +430,7 @@ int main(int argc, char **argv) {
                 std::ofstream mf(masses_only_path, std::ios::binary);
                 if (!mf) throw std::runtime_error("cannot write " + masses_only_path);
                 mf << rkh::masses_samples_table(t, sm->names, words.data(), words.size());
-                write_kr(t, *sm, nullptr);  // (the buffer is still on the device in the handle)
+                write_kr(t, *sm, nullptr, words.data());  // (the buffer is still on the device in the handle)
                 return;
             }
             std::vector<uint64_t> words((size_t)rk_masses_words((uint32_t)t.nodes.size()), 0);

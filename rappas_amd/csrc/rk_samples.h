@@ -1,5 +1,6 @@
-// rk_samples.h -- #included by rk_kernels.hip: the sample-level kernels -- the clade sums of sample mass buffers over
-// a tree on the device, and the pairwise Kantorovich-Rubinstein distances between the samples.  The launches and the entry points
+// rk_samples.h -- #included by rk_kernels.hip: the sample-level kernels -- the clade sums of sample mass buffers
+// over a tree on the device, the pairwise Kantorovich-Rubinstein distances between the samples, and the squash clustering of the
+// samples over those distances.  The launches and the entry points
 // are in rk_samples_impl.h, the host twins in rk_samples_host.h.  Not part of the C ABI.
 #pragma once
 #include "rk_device.h"
@@ -227,6 +228,213 @@ __global__ void __launch_bounds__(256) kr_reduce_kernel(u64 n, u32 n_chunks, con
     double d = part[i];
     for (u32 c = 1; c < n_chunks; c++) d = d + part[(u64)c * n + i];
     D[i] = d;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Squash clustering (include/rappas_place.h holds the definition).  After the KR matrix the profiles U, V, the half
+// lengths h and D are on the device; S - 1 steps follow, each five plain launches in stream order.  Which pair a step picked stays
+// on the device: squash_pick_finish_kernel writes row k of the output, the kernels behind it read that row, and where it is a
+// filler (fewer than two active clusters) they return at once.  No atomics, no grid-wide wait; every sum has one owner and a fixed
+// order, so the bits depend on neither grid nor block shape.
+//   squash_init_kernel         active[s] = T_s != 0, size[s] = 1, n_merges = max(active - 1, 0)        (one block)
+//   squash_pick_kernel         the minimum of (D[a][b], a, b) over the active pairs a < b of the rows a block owns -> scratch[block]
+//   squash_pick_finish_kernel  the minimum over the blocks; row k, active[b] = 0, size[a] += size[b]   (one block)
+//   squash_merge_kernel        one thread a node: the new column a of U and V, and a contiguous copy ua, va
+//   squash_row_kernel          the hot path: (chunk of KR_CHUNK_IDS ids) x (group of SQUASH_GROUP samples: one wave); a thread owns one t
+//                              and walks its chunk in ascending id -- the 64 lanes take one 512-byte line of U and one of V a node,
+//                              SQUASH_DEPTH - 1 batches of SQUASH_UNROLL nodes in flight while one is summed, h / ua / va of the
+//                              chunk staged in the LDS -- into part[chunk][t]
+//   squash_row_reduce_kernel   D[min(a, t)][max(a, t)] = the partials of t in chunk order, the first one as it is (the pick reads the
+//                              upper triangle only)
+// The (distance, a, b) order is total, so any shape of the reduction finds the same pair.
+// ------------------------------------------------------------------------------------------------
+constexpr u32 SQUASH_FILLER = 0xFFFFFFFFu, SQUASH_GROUP = 64, SQUASH_UNROLL = 8, SQUASH_DEPTH = 4, SQUASH_PICK_BLOCKS = 512;
+
+struct SquashRow {  // rk_squash_merge
+    u32 a, b, size, reserved;
+    double distance;
+};
+struct SquashBest {
+    double d;
+    u32 a, b;
+};
+
+__device__ __forceinline__ void squash_take(SquashBest &best, double d, u32 a, u32 b) {
+    if (d < best.d || (d == best.d && (a < best.a || (a == best.a && b < best.b)))) best = SquashBest{d, a, b};
+}
+
+// the best of the block's 256 candidates, in every thread of it
+__device__ __forceinline__ SquashBest squash_block_best(SquashBest mine) {
+    __shared__ SquashBest cand[256];
+    const u32 tid = threadIdx.x;
+    cand[tid] = mine;
+    for (u32 o = 128; o > 0; o >>= 1) {
+        __syncthreads();
+        if (tid < o) {
+            SquashBest x = cand[tid];
+            const SquashBest y = cand[tid + o];
+            squash_take(x, y.d, y.a, y.b);
+            cand[tid] = x;
+        }
+    }
+    __syncthreads();
+    return cand[0];
+}
+
+__global__ void __launch_bounds__(256) squash_init_kernel(u32 B, u32 S, u32 root, const u64 *clade, u32 *active, u32 *size, u32 *n_merges) {
+    __shared__ u32 count[256];
+    const u32 tid = threadIdx.x;
+    u32 n = 0;
+    for (u32 s = tid; s < S; s += 256) {
+        const u32 on = clade[(u64)s * B + root] != 0 ? 1u : 0u;
+        active[s] = on;
+        size[s] = 1;
+        n += on;
+    }
+    count[tid] = n;
+    for (u32 o = 128; o > 0; o >>= 1) {
+        __syncthreads();
+        if (tid < o) count[tid] += count[tid + o];
+    }
+    if (tid == 0) *n_merges = count[0] ? count[0] - 1 : 0;
+}
+
+__global__ void __launch_bounds__(256) squash_pick_kernel(u32 S, const double *D, const u32 *active, SquashBest *scratch) {
+    SquashBest best{__builtin_inf(), SQUASH_FILLER, SQUASH_FILLER};
+    for (u32 a = blockIdx.x; a + 1 < S; a += gridDim.x) {
+        if (!active[a]) continue;  // (uniform)
+        const double *row = D + (u64)a * S;
+        for (u32 b = a + 1 + threadIdx.x; b < S; b += 256)
+            if (active[b]) squash_take(best, row[b], a, b);
+    }
+    best = squash_block_best(best);
+    if (threadIdx.x == 0) scratch[blockIdx.x] = best;
+}
+
+__global__ void __launch_bounds__(256) squash_pick_finish_kernel(u32 n_scratch, u32 k, const SquashBest *scratch, u32 *active, u32 *size, SquashRow *merges) {
+    SquashBest best{__builtin_inf(), SQUASH_FILLER, SQUASH_FILLER};
+    for (u32 i = threadIdx.x; i < n_scratch; i += 256) {
+        const SquashBest c = scratch[i];
+        squash_take(best, c.d, c.a, c.b);
+    }
+    best = squash_block_best(best);
+    if (threadIdx.x != 0) return;
+    if (best.a == SQUASH_FILLER) {
+        merges[k] = SquashRow{SQUASH_FILLER, SQUASH_FILLER, 0, 0, 0.0};
+        return;
+    }
+    const u32 n = size[best.a] + size[best.b];  // (size[b] stays: the merge kernel reads it)
+    size[best.a] = n;
+    active[best.b] = 0;
+    merges[k] = SquashRow{best.a, best.b, n, 0, best.d};
+}
+
+__global__ void __launch_bounds__(256) squash_merge_kernel(u32 B, u32 S, u32 k, const SquashRow *merges, const u32 *size, double *U, double *V, double *ua, double *va) {
+    const SquashRow row = merges[k];
+    const u32 x = blockIdx.x * 256 + threadIdx.x;
+    if (row.a == SQUASH_FILLER || x >= B) return;
+    const u32 nb = size[row.b], na = row.size - nb;
+    const double wa = (double)na, wb = (double)nb, n = (double)row.size;
+    double *pu = U + (u64)x * S, *pv = V + (u64)x * S;
+    const double u = (wa * pu[row.a] + wb * pu[row.b]) / n;
+    const double v = (wa * pv[row.a] + wb * pv[row.b]) / n;
+    pu[row.a] = u;
+    pv[row.a] = v;
+    ua[x] = u;
+    va[x] = v;
+}
+
+__global__ void __launch_bounds__(SQUASH_GROUP) squash_row_kernel(u32 B, u32 S, u32 k, const SquashRow *merges, const u32 *active, const double *U, const double *V,
+                                                         const double *h, const double *ua, const double *va, double *part) {
+    __shared__ double uni[3][KR_CHUNK_IDS];  // h, ua, va of the chunk: the same for every thread of the block
+    const u32 a = merges[k].a;
+    if (a == SQUASH_FILLER) return;
+    const u32 t = blockIdx.y * SQUASH_GROUP + threadIdx.x;
+    const bool need = t < S && t != a && active[t] != 0;
+    if (!__syncthreads_or(need)) return;  // the block's samples are all inactive or a
+    const u32 x_lo = blockIdx.x * KR_CHUNK_IDS, x_hi = min(x_lo + KR_CHUNK_IDS, B);
+    for (u32 i = threadIdx.x; i < x_hi - x_lo; i += SQUASH_GROUP) {
+        uni[0][i] = h[x_lo + i];
+        uni[1][i] = ua[x_lo + i];
+        uni[2][i] = va[x_lo + i];
+    }
+    __syncthreads();
+    if (__ballot(need) == 0) return;  // (a group of several waves: the wave's 64 samples are all inactive or a; no barrier below)
+    const u32 tc = t < S ? t : S - 1;  // (lanes without a sample of their own read the last one's and write nothing)
+    const double *pu = U + tc, *pv = V + tc;
+    double acc = 0.0;
+    auto load = [&](double(&lu)[SQUASH_UNROLL], double(&lv)[SQUASH_UNROLL], u32 x0) {
+#pragma unroll
+        for (u32 i = 0; i < SQUASH_UNROLL; i++) {
+            lu[i] = pu[(u64)(x0 + i) * S];
+            lv[i] = pv[(u64)(x0 + i) * S];
+        }
+    };
+    struct Uniform {  // h, ua, va of a batch: broadcast reads of the LDS
+        double h[SQUASH_UNROLL], a[SQUASH_UNROLL], b[SQUASH_UNROLL];
+    };
+    auto uniform = [&](Uniform &q, u32 x0) {
+#pragma unroll
+        for (u32 i = 0; i < SQUASH_UNROLL; i++) {
+            q.h[i] = uni[0][x0 - x_lo + i];
+            q.a[i] = uni[1][x0 - x_lo + i];
+            q.b[i] = uni[2][x0 - x_lo + i];
+        }
+    };
+    auto sum = [&](const Uniform &q, const double(&lu)[SQUASH_UNROLL], const double(&lv)[SQUASH_UNROLL]) {
+#pragma unroll
+        for (u32 i = 0; i < SQUASH_UNROLL; i++) {
+            const double term1 = q.h[i] * fabs(q.a[i] - lu[i]);
+            const double term2 = q.h[i] * fabs(q.b[i] - lv[i]);
+            acc = (acc + term1) + term2;
+        }
+    };
+    u32 x = x_lo;
+    // whole groups of SQUASH_DEPTH batches of SQUASH_UNROLL nodes: a ring of register batches, SQUASH_DEPTH - 1 of them in flight while
+    // one is summed (a thread's sum is one dependent chain, so what a wave can hide of the loads' latency is what it has in flight).
+    // The scheduling barriers keep the loads of the batch ahead, and the uniform loads of this one, in front of this one's sum.
+    const u32 n_batches = (x_hi - x_lo) / (SQUASH_UNROLL * SQUASH_DEPTH) * SQUASH_DEPTH;
+    if (n_batches) {
+        double ru[SQUASH_DEPTH][SQUASH_UNROLL], rv[SQUASH_DEPTH][SQUASH_UNROLL];
+#pragma unroll
+        for (u32 d = 0; d + 1 < SQUASH_DEPTH; d++) load(ru[d], rv[d], x_lo + d * SQUASH_UNROLL);
+        for (u32 b0 = 0; b0 < n_batches; b0 += SQUASH_DEPTH) {
+#pragma unroll
+            for (u32 d = 0; d < SQUASH_DEPTH; d++) {
+                const u32 ahead = min(b0 + d + SQUASH_DEPTH - 1, n_batches - 1);  // (the last batches load the last one again: no branch)
+                Uniform q;
+                uniform(q, x_lo + (b0 + d) * SQUASH_UNROLL);
+                load(ru[(d + SQUASH_DEPTH - 1) % SQUASH_DEPTH], rv[(d + SQUASH_DEPTH - 1) % SQUASH_DEPTH], x_lo + ahead * SQUASH_UNROLL);
+                __builtin_amdgcn_sched_barrier(0);
+                sum(q, ru[d], rv[d]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        x = x_lo + n_batches * SQUASH_UNROLL;
+    }
+    for (; x + SQUASH_UNROLL <= x_hi; x += SQUASH_UNROLL) {  // the batches that fill no group
+        double lu[SQUASH_UNROLL], lv[SQUASH_UNROLL];
+        Uniform q;
+        uniform(q, x);
+        load(lu, lv, x);
+        sum(q, lu, lv);
+    }
+    for (; x < x_hi; x++) {
+        const double hx = uni[0][x - x_lo];
+        const double term1 = hx * fabs(uni[1][x - x_lo] - pu[(u64)x * S]);
+        const double term2 = hx * fabs(uni[2][x - x_lo] - pv[(u64)x * S]);
+        acc = (acc + term1) + term2;
+    }
+    if (need) part[(u64)blockIdx.x * S + t] = acc;
+}
+
+__global__ void __launch_bounds__(256) squash_row_reduce_kernel(u32 S, u32 k, u32 n_chunks, const SquashRow *merges, const u32 *active, const double *part, double *D) {
+    const u32 a = merges[k].a;
+    const u32 t = blockIdx.x * 256 + threadIdx.x;
+    if (a == SQUASH_FILLER || t >= S || t == a || !active[t]) return;
+    double d = part[t];
+    for (u32 c = 1; c < n_chunks; c++) d = d + part[(u64)c * S + t];
+    D[(u64)min(a, t) * S + max(a, t)] = d;
 }
 
 }  // namespace rk

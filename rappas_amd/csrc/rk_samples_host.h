@@ -1,6 +1,6 @@
-// rk_samples_host.h -- the host side of the sample-level calls (DESIGN.md 4.9): the checks and the one walk of a tree behind
-// rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel and kr_pairs_kernel (rk_samples.h) behind
-// rk_clade_masses_host and rk_kr_distances_host.  Header-only, plain C++, like rk_masses_host.h.  Not part of the C ABI.
+// rk_samples_host.h -- the host side of the sample-level calls (DESIGN.md 4.9, 4.10): the checks and the one walk of a tree behind
+// rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel, kr_pairs_kernel and the squash kernels (rk_samples.h)
+// behind rk_clade_masses_host, rk_kr_distances_host and rk_squash_host.  Header-only, plain C++, like rk_masses_host.h.  Not part of the C ABI.
 //
 // The KR distance is written as include/rappas_place.h defines it, term by term and in the order fixed there, so that the device and
 // this file give the same bits.  The reference has no counterpart: it stops at the jplace it writes.
@@ -132,6 +132,77 @@ inline void kr_rows(uint32_t B, uint32_t S, const double *h, const double *u, co
             out[s * S + t] = d;
             out[t * S + s] = d;
         }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Squash clustering (include/rappas_place.h holds the definition): the host twin of the squash kernels of rk_samples.h.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t SQUASH_NONE = 0xFFFFFFFFu;  // RK_SQUASH_NONE
+struct SquashMerge {                           // rk_squash_merge
+    uint32_t a, b, size, reserved;
+    double distance;
+};
+
+// The active pair a < b with the smallest D[a][b]; ties to the smaller a, then the smaller b (rows and columns ascending, strict <).
+// false: fewer than two clusters are active.
+inline bool squash_pick(uint32_t S, const double *D, const uint8_t *active, uint32_t &a_out, uint32_t &b_out) {
+    bool found = false;
+    double best = 0.0;
+    for (uint32_t a = 0; a < S; a++) {
+        if (!active[a]) continue;
+        for (uint32_t b = a + 1; b < S; b++)
+            if (active[b] && (!found || D[(uint64_t)a * S + b] < best)) {
+                found = true;
+                best = D[(uint64_t)a * S + b];
+                a_out = a;
+                b_out = b;
+            }
+    }
+    return found;
+}
+
+// Cluster a takes in cluster b: the weighted average of the two profiles, entry by entry
+inline void squash_merge_profiles(uint32_t B, uint32_t na, uint32_t nb, double *ua, double *va, const double *ub, const double *vb) {
+    const double wa = (double)na, wb = (double)nb, n = (double)(na + nb);
+    for (uint32_t x = 0; x < B; x++) {
+        ua[x] = (wa * ua[x] + wb * ub[x]) / n;
+        va[x] = (wa * va[x] + wb * vb[x]) / n;
+    }
+}
+
+// The new distances of cluster a to the active clusters t = t_lo, t_lo + t_step, ...: written at [a][t] and [t][a]
+inline void squash_row(uint32_t B, uint32_t S, const double *h, const double *u, const double *v, const uint8_t *active, uint32_t a, uint32_t t_lo, uint32_t t_step,
+                       double *D) {
+    for (uint64_t t = t_lo; t < S; t += t_step) {
+        if (!active[t] || t == a) continue;
+        const double d = kr_pair(B, h, u + (uint64_t)a * B, v + (uint64_t)a * B, u + t * B, v + t * B);
+        D[(uint64_t)a * S + t] = d;
+        D[t * S + a] = d;
+    }
+}
+
+// The S - 1 steps over profiles u, v (sample after sample, B doubles each; merged in place), the matrix D (updated in place) and the
+// active flags (cleared as clusters are taken in).  row_step(a) fills the row of the merged cluster: squash_row over every t, dealt
+// as the caller likes.  Returns n_merges; the rows behind it are fillers.
+template <class RowStep>
+inline uint32_t squash_steps(uint32_t B, uint32_t S, double *u, double *v, double *D, uint8_t *active, SquashMerge *merges, RowStep &&row_step) {
+    std::vector<uint32_t> size(S, 1);
+    uint32_t n_merges = 0;
+    for (uint32_t k = 0; k + 1 < S; k++) {
+        uint32_t a = 0, b = 0;
+        if (!squash_pick(S, D, active, a, b)) {
+            merges[k] = SquashMerge{SQUASH_NONE, SQUASH_NONE, 0, 0, 0.0};
+            continue;
+        }
+        const double d = D[(uint64_t)a * S + b];
+        squash_merge_profiles(B, size[a], size[b], u + (uint64_t)a * B, v + (uint64_t)a * B, u + (uint64_t)b * B, v + (uint64_t)b * B);
+        size[a] += size[b];
+        active[b] = 0;
+        merges[k] = SquashMerge{a, b, size[a], 0, d};
+        n_merges++;
+        row_step(a);
+    }
+    return n_merges;
 }
 
 }  // namespace rk

@@ -1,7 +1,8 @@
-// rk_samples_impl.h -- #included by rk_engine.hip: the sample-level entry points -- the tree handle (rk_tree_*), the
-// clade sums of sample mass buffers (rk_clade_masses_device / _host) and the KR distance matrix (rk_kr_distances_device / _host /
-// _batch) -- over the kernels of rk_samples.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses
-// call filled; they touch no placement kernel and no launch scratch, and only rk_kr_distances_batch touches a database handle.
+// rk_samples_impl.h -- #included by rk_engine.hip: the sample-level entry points -- the tree handle (rk_tree_*),
+// the clade sums of sample mass buffers (rk_clade_masses_device / _host), the KR distance matrix (rk_kr_distances_device / _host /
+// _batch) and the squash clustering over it (rk_squash_device / _host / _batch) -- over the kernels of rk_samples.h and the host twins
+// of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
+// scratch, and only the two _batch calls touch a database handle.
 #pragma once
 
 #include "rk_samples_host.h"
@@ -263,6 +264,189 @@ extern "C" int rk_kr_distances_batch(rk_db *db, const rk_tree *t, uint32_t n_sam
     }
     if (int rc = rk_kr_distances_device(t, n_samples, d_masses, d_out.as<double>(), work.p, need, s)) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Squash clustering: rk_squash_work_bytes / _device / _host / _batch.
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(rk_squash_merge) == 24 && sizeof(SquashRow) == 24 && sizeof(rk::SquashMerge) == 24 && offsetof(rk_squash_merge, distance) == 16 &&
+                  offsetof(SquashRow, distance) == 16 && offsetof(rk::SquashMerge, distance) == 16,
+              "one row layout for the header, the host twin and the kernels");
+static_assert(RK_SQUASH_NONE == SQUASH_FILLER && RK_SQUASH_NONE == rk::SQUASH_NONE, "one filler word");
+
+// The workspace of rk_squash_device: the KR workspace | D[S][S] | ua[B] | va[B] | part[chunks][S] | the pick scratch | active[S] | size[S]
+struct SquashPlan {
+    KrPlan kr;
+    uint32_t pick_blocks;
+    uint64_t d_at, ua_at, va_at, part_at, scratch_at, active_at, size_at, bytes;
+};
+static bool squash_plan(uint32_t B, uint32_t S, SquashPlan &p) {
+    if (!kr_plan(B, S, p.kr)) return false;
+    auto up = [](uint64_t v) { return (v + 15) / 16 * 16; };
+    p.pick_blocks = std::min<uint32_t>(S - 1, SQUASH_PICK_BLOCKS);
+    p.d_at = up(p.kr.bytes);
+    p.ua_at = p.d_at + (uint64_t)S * S * 8;
+    p.va_at = p.ua_at + (uint64_t)B * 8;
+    p.part_at = p.va_at + (uint64_t)B * 8;
+    p.scratch_at = p.part_at + (uint64_t)p.kr.n_chunks * S * 8;
+    p.active_at = p.scratch_at + (uint64_t)p.pick_blocks * sizeof(SquashBest);
+    p.size_at = p.active_at + (uint64_t)S * 4;
+    p.bytes = up(p.size_at + (uint64_t)S * 4);
+    return p.bytes <= RK_KR_MAX_WORK_BYTES;
+}
+
+static int squash_args(const char *who, const rk_tree *t, uint32_t S) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (S < 2 || S > RK_SQUASH_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, S, RK_SQUASH_MAX_SAMPLES);
+    return RK_OK;
+}
+
+extern "C" uint64_t rk_squash_work_bytes(const rk_tree *t, uint32_t n_samples) {
+    const char *who = "rk_squash_work_bytes";
+    if (squash_args(who, t, n_samples)) return 0;
+    SquashPlan p;
+    if (!squash_plan(t->B, n_samples, p)) {
+        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+        return 0;
+    }
+    return p.bytes;
+}
+
+// The launches behind rk_squash_device.  `steps` (developer builds, scripts/squash_rate.py): bit 0 the KR matrix and the start, 1 the
+// pick, 2 the merge, 3 the row step, 4 its reduce.
+static int squash_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, rk_squash_merge *d_merges, uint32_t *d_n_merges, void *d_work, const SquashPlan &p,
+                         hipStream_t s, unsigned steps = 31) {
+    const uint32_t B = t->B, n_chunks = p.kr.n_chunks;
+    char *w = (char *)d_work;
+    const u64 *clade = (const u64 *)(w + p.kr.clade_at);
+    double *U = (double *)(w + p.kr.u_at), *V = (double *)(w + p.kr.v_at), *D = (double *)(w + p.d_at);
+    double *ua = (double *)(w + p.ua_at), *va = (double *)(w + p.va_at), *part = (double *)(w + p.part_at);
+    SquashBest *scratch = (SquashBest *)(w + p.scratch_at);
+    u32 *active = (u32 *)(w + p.active_at), *size = (u32 *)(w + p.size_at);
+    SquashRow *merges = (SquashRow *)d_merges;
+    if (steps & 1) {
+        if (int rc = kr_launch(t, S, d_masses, D, d_work, p.kr, s)) return rc;
+        hipLaunchKernelGGL(squash_init_kernel, dim3(1), dim3(256), 0, s, B, S, t->root, clade, active, size, (u32 *)d_n_merges);
+        HIP_TRY(hipGetLastError());
+    }
+    const dim3 row_grid(n_chunks, (S + SQUASH_GROUP - 1) / SQUASH_GROUP);
+    for (uint32_t k = 0; k + 1 < S; k++) {
+        if (steps & 2) {
+            hipLaunchKernelGGL(squash_pick_kernel, dim3(p.pick_blocks), dim3(256), 0, s, S, (const double *)D, (const u32 *)active, scratch);
+            hipLaunchKernelGGL(squash_pick_finish_kernel, dim3(1), dim3(256), 0, s, p.pick_blocks, k, (const SquashBest *)scratch, active, size, merges);
+        }
+        if (steps & 4)
+            hipLaunchKernelGGL(squash_merge_kernel, dim3((B + 255) / 256), dim3(256), 0, s, B, S, k, (const SquashRow *)merges, (const u32 *)size, U, V, ua, va);
+        if (steps & 8)
+            hipLaunchKernelGGL(squash_row_kernel, row_grid, dim3(SQUASH_GROUP), 0, s, B, S, k, (const SquashRow *)merges, (const u32 *)active, (const double *)U,
+                               (const double *)V, t->h, (const double *)ua, (const double *)va, part);
+        if (steps & 16)
+            hipLaunchKernelGGL(squash_row_reduce_kernel, dim3((S + 255) / 256), dim3(256), 0, s, S, k, n_chunks, (const SquashRow *)merges, (const u32 *)active,
+                               (const double *)part, D);
+        HIP_TRY(hipGetLastError());
+    }
+    return RK_OK;
+}
+
+extern "C" int rk_squash_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, rk_squash_merge *d_merges, uint32_t *d_n_merges, void *d_work,
+                                uint64_t work_bytes, void *stream) {
+    const char *who = "rk_squash_device";
+    if (int rc = squash_args(who, t, n_samples)) return rc;
+    SquashPlan p;
+    if (!squash_plan(t->B, n_samples, p)) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+    if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!d_merges || !d_n_merges) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if ((uintptr_t)d_merges % 8 || (uintptr_t)d_n_merges % 4) return fail(RK_ERR_INVALID, "%s: the rows must be 8-byte aligned, the count 4-byte aligned", who);
+    if (!d_work || work_bytes < p.bytes)
+        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_squash_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
+    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    HIP_TRY(hipSetDevice(t->device));
+    unsigned steps = 31;
+    if (const char *v = rk_knob("RK_SQUASH_STEPS")) steps = (unsigned)atoi(v);  // developer builds (scripts/squash_rate.py)
+    if (!(steps & 1) || !(steps & 2)) steps &= 1;                               // (the steps behind the pick read the row it writes, the pick the start)
+    return squash_launch(t, n_samples, d_masses, d_merges, d_n_merges, d_work, p, (hipStream_t)stream, steps);
+}
+
+extern "C" int rk_squash_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses,
+                              rk_squash_merge *merges, uint32_t *n_merges, uint32_t n_threads) {
+    const char *who = "rk_squash_host";
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (n_samples < 2 || n_samples > RK_SQUASH_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, n_samples, RK_SQUASH_MAX_SAMPLES);
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!merges || !n_merges) return fail(RK_ERR_INVALID, "%s: null output", who);
+    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
+    std::vector<uint64_t> clade;
+    std::vector<double> u, v, h, D;
+    std::vector<uint8_t> active;
+    try {
+        clade.resize(S * B);
+        u.resize(S * B);
+        v.resize(S * B);
+        h.resize(B);
+        D.resize(S * S);
+        active.resize(S);
+    } catch (const std::bad_alloc &) {
+        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
+    }
+    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
+    unsigned hw = std::thread::hardware_concurrency();
+    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
+    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
+    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        for (uint64_t s = th; s < S; s += T) {
+            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
+            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
+        }
+    });
+    if (rc) return rc;
+    rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        rk::kr_rows((uint32_t)B, (uint32_t)S, h.data(), u.data(), v.data(), (uint32_t)th, (uint32_t)T, D.data());
+    });
+    if (rc) return rc;
+    for (uint64_t s = 0; s < S; s++) active[s] = clade[s * B + w.root] != 0;
+    *n_merges = rk::squash_steps((uint32_t)B, (uint32_t)S, u.data(), v.data(), D.data(), active.data(), (rk::SquashMerge *)merges, [&](uint32_t a) {
+        (void)masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+            rk::squash_row((uint32_t)B, (uint32_t)S, h.data(), u.data(), v.data(), active.data(), a, (uint32_t)th, (uint32_t)T, D.data());
+        });
+    });
+    return RK_OK;
+}
+
+// The drivers' call: as rk_kr_distances_batch, with the rows and their count on the host at the end
+extern "C" int rk_squash_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, rk_squash_merge *merges, uint32_t *n_merges) {
+    const char *who = "rk_squash_batch";
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (int rc = squash_args(who, t, n_samples)) return rc;
+    if (!merges || !n_merges) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (t->B != db->info.n_branches || t->device != db->info.device)
+        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
+    const uint64_t need = rk_squash_work_bytes(t, n_samples), words = rk_masses_samples_words(t->B, n_samples);
+    if (!need) return RK_ERR_INVALID;
+    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
+    std::lock_guard<std::mutex> lock(db->host_mutex);
+    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
+        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
+    HIP_TRY(hipSetDevice(db->info.device));
+    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
+    hipStream_t s = db->ws[0].stream;
+    GrowBuf work, d_out, d_in;
+    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
+    const uint64_t rows_bytes = (uint64_t)(n_samples - 1) * sizeof(rk_squash_merge);  // the rows, then the count
+    if (int rc = work.reserve(need)) return rc;
+    if (int rc = d_out.reserve(rows_bytes + 8)) return rc;
+    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
+    if (masses) {
+        if (int rc = d_in.reserve(words * 8)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
+        d_masses = d_in.as<uint64_t>();
+    }
+    uint32_t *d_count = (uint32_t *)((char *)d_out.p + rows_bytes);
+    if (int rc = rk_squash_device(t, n_samples, d_masses, (rk_squash_merge *)d_out.p, d_count, work.p, need, s)) return rc;
+    HIP_TRY(hipMemcpyAsync(merges, d_out.p, rows_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(n_merges, d_count, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return RK_OK;
 }

@@ -408,6 +408,49 @@ def kr_table(names, D):
     return "".join(out)
 
 
+def _squash_leaf(name):
+    """a sample name as a Newick leaf: single-quoted, a quote doubled, when it holds any of ()[]':;, or white space"""
+    if any(c in "()[]':;, \t\n\r\v\f" for c in name):
+        return "'" + name.replace("'", "''") + "'"
+    return name
+
+
+def squash_table(names, merges, n_merges, with_mass=None):
+    """the text `--squash FILE` writes: a line `#squash<TAB>S<TAB>n_merges`; one line per merge, `k<TAB>a<TAB>b<TAB>distance<TAB>size`
+    (`%.17g`); a line `#newick<TAB>tree;` -- leaves named by sample (quoted where Newick needs it), an inner node at height
+    distance / 2, a leaf at height 0, an edge length height(parent) - height(child) as `%.17g` (negative where the clustering is not
+    monotone), children in the order a, b, no length on the root; one sample with mass gives `name;`, none gives `;` --; a line
+    `#inversions<TAB>n`, the number of negative edge lengths; and a last line `#samples_without_mass<TAB>n`.
+    merges: rows of placement.SQUASH_MERGE (or anything with a, b, size, distance per row).  with_mass: one flag per sample; None: the
+    samples the merges name (which cannot tell one sample with mass from none).  The twin of rkh::squash_table, byte-identical."""
+    S = len(names)
+    out = [f"#squash\t{S}\t{n_merges}\n"]
+    sub, height = {}, {}  # per slot: the subtree's text and its height
+    if with_mass is None:
+        with_mass = [False] * S
+        for k in range(n_merges):
+            with_mass[int(merges[k]["a"])] = with_mass[int(merges[k]["b"])] = True
+    for s in range(S):
+        if with_mass[s]:
+            sub[s], height[s] = _squash_leaf(names[s]), 0.0
+    inversions, root = 0, None
+    for k in range(n_merges):
+        a, b, d, size = int(merges[k]["a"]), int(merges[k]["b"]), float(merges[k]["distance"]), int(merges[k]["size"])
+        out.append("%d\t%d\t%d\t%.17g\t%d\n" % (k, a, b, d, size))
+        h = d / 2
+        la, lb = h - height[a], h - height[b]
+        inversions += (la < 0) + (lb < 0)
+        sub[a] = "(%s:%.17g,%s:%.17g)" % (sub[a], la, sub.pop(b), lb)
+        height[a] = h
+        root = a
+    if root is None and len(sub) == 1:
+        root = next(iter(sub))
+    out.append("#newick\t" + (sub[root] if root is not None else "") + ";\n")
+    out.append(f"#inversions\t{inversions}\n")
+    out.append(f"#samples_without_mass\t{S - sum(1 for f in with_mass if f)}\n")
+    return "".join(out)
+
+
 def _fmt12(x):
     """NumberFormat.getNumberInstance(Locale.UK) with exactly 12 fraction digits (NewickWriter.java:61-64): grouping commas,
     HALF_EVEN on the exact binary value."""

@@ -787,6 +787,24 @@ def kr_distances_host(parent, branch_len, masses, n_samples, threads=0):
     return out
 
 
+# rk_squash_merge: a row of the squash clustering (a and b the smallest sample indices of the two clusters, size after the merge)
+SQUASH_MERGE = np.dtype([("a", "<u4"), ("b", "<u4"), ("size", "<u4"), ("reserved", "<u4"), ("distance", "<f8")])
+assert SQUASH_MERGE.itemsize == 24
+
+
+def squash_host(parent, branch_len, masses, n_samples, threads=0):
+    """rk_squash_host (no GPU): (merges, n_merges) -- the squash clustering of the samples of a sample mass buffer on the tree (parent,
+    branch_len): a SQUASH_MERGE array of n_samples - 1 rows, of which the first n_merges are merges and the rest fillers -- the bits
+    EdgeTree.squash gives on the device.  A sample without mass takes no part."""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    B = parent.shape[0]
+    masses = _samples_in(B, n_samples, masses)
+    merges = np.zeros(max(n_samples - 1, 0), SQUASH_MERGE)
+    n = C.c_uint32(0)
+    _lib.check(_lib.load().rk_squash_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), _ptr(merges), C.byref(n), threads))
+    return merges, int(n.value)
+
+
 class EdgeTree:
     """rk_tree: the shape of a reference tree on the device -- parent[x] the node id of x's parent (-1 for the root), branch_len[x] the
     length of the edge above x -- for the sample-level calls over device mass buffers.  Takes and returns torch device tensors and owns
@@ -852,6 +870,39 @@ class EdgeTree:
         out = np.zeros((n_samples, n_samples), np.float64)
         _lib.check(self._lib.rk_kr_distances_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(out)))
         return out
+
+    def squash_work_bytes(self, n_samples):
+        need = int(self._lib.rk_squash_work_bytes(self.handle, n_samples))
+        if not need:
+            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
+        return need
+
+    def squash(self, masses, n_samples, stream=None):
+        """rk_squash_device: (merges, n_merges) as device tensors, written -- uint8 [n_samples - 1, 24], the rows of SQUASH_MERGE
+        (merges.cpu().numpy().view(SQUASH_MERGE)), and int32 [1]; asynchronous on the stream"""
+        import torch
+        dev = self._masses(masses, n_samples)
+        need = self.squash_work_bytes(n_samples)
+        if self._work_buf is None or self._work_buf.numel() < need:
+            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        merges = torch.empty((n_samples - 1, SQUASH_MERGE.itemsize), dtype=torch.uint8, device=dev)
+        n_merges = torch.empty((1,), dtype=torch.int32, device=dev)
+        _lib.check(self._lib.rk_squash_device(self.handle, n_samples, masses.data_ptr(), merges.data_ptr(), n_merges.data_ptr(), self._work_buf.data_ptr(),
+                                              self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+        return merges, n_merges
+
+    def squash_batch(self, db, n_samples, masses=None):
+        """rk_squash_batch, the drivers' call: (merges, n_merges) on the host, as squash_host gives them, from a host sample mass buffer --
+        or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_squash_device
+        on db's device; returns when the rows are there"""
+        if masses is not None:
+            masses = _samples_in(self.n_branches, n_samples, masses)
+            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
+                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        merges = np.zeros(max(n_samples - 1, 0), SQUASH_MERGE)
+        n = C.c_uint32(0)
+        _lib.check(self._lib.rk_squash_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(merges), C.byref(n)))
+        return merges, int(n.value)
 
     def close(self):
         if self._h:

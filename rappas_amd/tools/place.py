@@ -18,6 +18,7 @@ TRANSLATE_WITH_STRAND = "--translate places every read in all six reading frames
 MASSES_ONLY_WITH_OUT = "--masses-only writes no jplace (the placements never reach the host): it cannot be combined with --out"
 MASSES_ONLY_WITH_MASSES = "--masses-only writes the table --masses writes, without placing into a jplace: give one of the two"
 KR_NEEDS_SAMPLE_SEP = "--kr compares the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
+SQUASH_NEEDS_SAMPLE_SEP = "--squash clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
 
@@ -34,8 +35,29 @@ def kr_text(db, tree, sample_names, words, device=0):
         et.close()
 
 
+def squash_text(db, tree, sample_names, words, host_words, device=0):
+    """`--squash FILE`: the table (hostio.squash_table) of the squash clustering of the samples of a sample mass buffer over the
+    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`; host_words: the host's copy
+    either way (it tells which samples hold mass)"""
+    from ..placement import SQUASH_MERGE, EdgeTree
+    S, B = len(sample_names), len(tree.nodes)
+    W = 2 * B + 4
+    host_words = np.asarray(host_words, dtype=np.uint64).reshape(-1)
+    with_mass = [bool(host_words[s * W:s * W + B].any()) for s in range(S)]
+    if S < 2:
+        return hostio.squash_table(sample_names, np.zeros(0, SQUASH_MERGE), 0, with_mass)
+    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
+    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
+    try:
+        merges, n_merges = et.squash_batch(db, S, words)
+        return hostio.squash_table(sample_names, merges, n_merges, with_mass)
+    finally:
+        et.close()
+
+
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
-               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None, kr=False):
+               call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None, kr=False,
+               squash=False):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
@@ -43,11 +65,13 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both".  masses: res.masses is
     then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for);
     with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table); with kr as well res.kr is
-    the text `--kr FILE` writes (kr_text)."""
+    the text `--kr FILE` writes (kr_text), with squash res.squash the text `--squash FILE` writes (squash_text)."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
     if kr and not (masses and sample_sep is not None):
         raise ValueError(KR_NEEDS_SAMPLE_SEP)
+    if squash and not (masses and sample_sep is not None):
+        raise ValueError(SQUASH_NEEDS_SAMPLE_SEP)
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     sample_words = None
     try:
@@ -63,7 +87,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
             res = PlacementProcess(db, ns_bound).processQueries(
                 seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
                 treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
-        res.kr = None
+        res.kr = res.squash = None
         if members is not None:
             from ..placement import accumulate_masses_samples_host
             sample_names, m_off, m_sample, m_weight = members
@@ -71,6 +95,8 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
             sample_words = accumulate_masses_samples_host(len(tree.nodes), res, len(sample_names), m_sample, member_read=m_read, member_weight=m_weight)
             if kr:
                 res.kr = kr_text(db, tree, sample_names, sample_words, device)
+            if squash:
+                res.squash = squash_text(db, tree, sample_names, sample_words, sample_words, device)
     finally:
         db.close()
     pl = hostio.jplace_placements(tree, names, res.n_rows, res.branch, res.score, res.lwr, guppy)
@@ -88,19 +114,22 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
 
 
 def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), device=0, union=False,
-                     dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None, kr=False):
+                     dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None, kr=False, squash=False):
     """`--masses-only FILE`: scan, dedup and gather as place_file, then ONE profile-only call (processQueriesMasses) with the
     multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
     table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
     No jplace and no frames log: the rows and the frame bytes never reach the host.  With sample_sep (one character) the one call is
     processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample; with kr as well
-    .kr is the text `--kr FILE` writes, from the buffer that call left on the device."""
+    .kr is the text `--kr FILE` writes, from the buffer that call left on the device, and with squash .squash the text `--squash FILE`
+    writes, from the same buffer."""
     from types import SimpleNamespace
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
     if kr and sample_sep is None:
         raise ValueError(KR_NEEDS_SAMPLE_SEP)
-    kr_out = None
+    if squash and sample_sep is None:
+        raise ValueError(SQUASH_NEEDS_SAMPLE_SEP)
+    kr_out = squash_out = None
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     try:
         if translate and db.info.alphabet != 20:
@@ -118,13 +147,16 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
             table = hostio.masses_samples_table(tree, sample_names, words)
             if kr:
                 kr_out = kr_text(db, tree, sample_names, None, device)
+            if squash:
+                squash_out = squash_text(db, tree, sample_names, None, words, device)
         else:
             words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(seq, off, weights=weights, **common)
             table = hostio.masses_table(tree, words)
     finally:
         db.close()
     return SimpleNamespace(masses=table, notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
-                           reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters, kr=kr_out)
+                           reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters, kr=kr_out,
+                           squash=squash_out)
 
 
 def _open_db(db_text, union, dbimage, save_dbimage, device):
@@ -185,6 +217,10 @@ def main(argv=None):
                     help="with --sample-sep: the pairwise Kantorovich-Rubinstein distances between the samples' edge masses, summed on the "
                          "device: a line #kr<TAB>S, a line per sample with its name and S distances (%%.17g), and a last line "
                          "#samples_without_mass<TAB>n; a sample without mass has nan in its row and column")
+    ap.add_argument("--squash", default=None, metavar="FILE",
+                    help="with --sample-sep: the squash clustering of the samples over those distances, merged on the device: a line "
+                         "#squash<TAB>S<TAB>n_merges, a line k<TAB>a<TAB>b<TAB>distance<TAB>size per merge, the tree as #newick<TAB>...; "
+                         "(an inner node at half its distance), #inversions<TAB>n and #samples_without_mass<TAB>n")
     ap.add_argument("--timing", action="store_true", help="--masses-only: one JSON line with the run's wall-clock times on stdout")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
@@ -202,6 +238,8 @@ def main(argv=None):
         ap.error(SAMPLE_SEP_NEEDS_MASSES)
     if a.kr is not None and a.sample_sep is None:
         ap.error(KR_NEEDS_SAMPLE_SEP)
+    if a.squash is not None and a.sample_sep is None:
+        ap.error(SQUASH_NEEDS_SAMPLE_SEP)
     if a.masses_only is None and a.out is None:
         ap.error("--out is required (or --masses-only FILE for a profile-only run)")
     db_text = None
@@ -216,7 +254,8 @@ def main(argv=None):
     try:
         doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
-                              translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep, kr=a.kr is not None)
+                              translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep, kr=a.kr is not None,
+                              squash=a.squash is not None)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -240,6 +279,9 @@ def main(argv=None):
     if res.kr is not None:
         with open(a.kr, "w") as f:
             f.write(res.kr)
+    if res.squash is not None:
+        with open(a.squash, "w") as f:
+            f.write(res.squash)
     placed = int(np.count_nonzero(res.n_rows))
     print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
     return 0
@@ -251,7 +293,8 @@ def _main_masses_only(a, db_text, fasta_text):
     t0 = time.perf_counter()
     try:
         res = masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.device, union=a.uniondb is not None,
-                               dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate, sample_sep=a.sample_sep, kr=a.kr is not None)
+                               dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate, sample_sep=a.sample_sep, kr=a.kr is not None,
+                               squash=a.squash is not None)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -263,6 +306,9 @@ def _main_masses_only(a, db_text, fasta_text):
     if res.kr is not None:
         with open(a.kr, "w") as f:
             f.write(res.kr)
+    if res.squash is not None:
+        with open(a.squash, "w") as f:
+            f.write(res.squash)
     logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.masses_only)), "logs")
     os.makedirs(logs, exist_ok=True)
     with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
