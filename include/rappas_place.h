@@ -584,6 +584,76 @@ int rk_squash_host(uint32_t n_branches, const int32_t *parent, const float *bran
                    rk_squash_merge *merges, uint32_t *n_merges, uint32_t n_threads);
 int rk_squash_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, rk_squash_merge *merges, uint32_t *n_merges);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Edge principal components of the samples of a sample mass buffer (Matsen & Evans; what `guppy epca` / `gappa edgepca` compute
+ * from jplace files): for every edge the difference between the mass on its two sides, per sample, and the principal components of
+ * that S x B matrix -- the projections of the samples and the loadings of the edges.  The reference has no counterpart.  Fixed so
+ * that every implementation gives the same bits.  All arithmetic is binary64 with IEEE conversion, *, +, -, /, no contraction and
+ * no square root on the device: the two roots a caller needs are taken on the host (Finish).
+ *   Sums over nodes     the RK_KR_CHUNK rule of the KR block: ascending id, a partial per RK_KR_CHUNK ids that starts at +0.0, the
+ *                       partials added in chunk order, the first one as it is.
+ *   Sums over samples   the lane rule LS(f): for l = 0..63, p_l = the sequential sum from +0.0 of f(s) over s = l, l + 64, l + 128,
+ *                       ... < S; LS = (((+0.0 + p_0) + p_1) + ...) + p_63.  dot(a, b) = LS(s -> a[s] * b[s]): the product is
+ *                       rounded, then added.
+ *   1 Active samples    u_s(x), v_s(x), T_s as the KR block defines them.  Sample s is active iff T_s != 0; n = the number of active
+ *                       samples; k_eff = min(k, n - 1), 0 when n < 2.  k_eff == 0: every output double is +0.0 and nothing below
+ *                       applies.
+ *   2 Imbalance         for an active s and x != root: X[x][s] = (u_s(x) + v_s(x)) - 1.0 -- the share of the mass strictly below
+ *                       the edge minus the share strictly above it; the edge's own mass is left out.  The root, or an inactive s:
+ *                       X[x][s] = +0.0.
+ *   3 Centring          mean[x] = LS(s -> X[x][s]) / (double)n.  Xc[x][s] = X[x][s] - mean[x] for an active s and x != root,
+ *                       otherwise +0.0.
+ *   4 Gram matrix       G[s][t] = the chunk-rule sum over x of Xc[x][s] * Xc[x][t], as acc = acc + (a * b).  G is bitwise
+ *                       symmetric; rows and columns of inactive samples are +0.0.  trace = LS(s -> G[s][s]).
+ *   5 Start vectors     for j < k_eff: Q[j][s] = (double)(((s * 8 + j + 1) * 2654435761) mod 2^32) / 4294967296.0 - 0.5.
+ *   6 Iteration         `iters` times: Y[j][s] = LS(t -> G[s][t] * Q[j][t]) for every j < k_eff.  Then for j = 0 .. k_eff - 1 in
+ *                       order: let i be the smallest s with the largest fabs(Y[j][s]) (plain >).  If that value is 0, column j
+ *                       becomes all +0.0 and is skipped by the projections below.  Otherwise Y[j][s] = Y[j][s] / Y[j][i] for every
+ *                       s (the divisor is the value before the division: the largest element becomes exactly +1.0, which is also
+ *                       the sign convention); then nn = dot(Y[j], Y[j]) and for every l > j: d = dot(Y[j], Y[l]) / nn,
+ *                       Y[l][s] = Y[l][s] - d * Y[j][s].  Then Q = Y.
+ *   7 Results           Z[j][s] = LS(t -> G[s][t] * Q[j][t]); nn_j = dot(Q[j], Q[j]); lambda_j = dot(Q[j], Z[j]) / nn_j;
+ *                       rr_j = dot(r, r) with r[s] = Z[j][s] - lambda_j * Q[j][s].  A zero column (nn_j == 0) gives nn_j =
+ *                       lambda_j = rr_j = +0.0.  w[j][x] = LS(s -> Xc[x][s] * Q[j][s]).
+ *   8 Raw output        rk_epca_out_doubles(B, S, k) = 1 + k * (3 + S + B) doubles: trace | lambda[k] | nn[k] | rr[k] | q[k][S] |
+ *                       w[k][B]; components j >= k_eff are +0.0.  Two uint32_t: {n_active, k_eff}.
+ *   Finish              rk_epca_finish_host, host only, the one place with a square root: eigenvalue_j = lambda_j (the eigenvalue
+ *                       of G; divide by n - 1 for the covariance's), share_j = lambda_j / trace, residual_j = sqrt(rr_j / nn_j),
+ *                       projection[s][j] = q[j][s] * sqrt(lambda_j / nn_j), loading[x][j] = w[j][x] / sqrt(lambda_j * nn_j) (the
+ *                       unit-norm edge eigenvector).  A component with lambda_j <= 0 or nn_j == 0 is all +0.0.
+ *   Consequences        The result does not depend on grid, tile or stream.  residual_j is |G q - lambda q| for the unit vector q:
+ *                       it tells how far the fixed number of iterations got -- some eigenvalue of G lies within residual_j of
+ *                       eigenvalue_j; nothing is iterated "until converged".  Components come out in descending eigenvalue once
+ *                       converged; they are not sorted.  They are meaningful only up to the rank of G (hence k_eff: a column
+ *                       beyond the rank would turn into noise).  The q entry of an inactive sample is a zero whose sign is that
+ *                       of the divisor of step 6.
+ *   rk_epca_out_doubles   the length of the raw output; 0 for arguments out of range.
+ *   rk_epca_work_bytes    bytes of the caller-owned device workspace: the clade sums, the profiles (the centred matrix takes the
+ *                         place of u), G, its per-chunk partials when the matrix is small, two [k][S] column blocks and the
+ *                         active flags; 0 and a message on a bad argument.
+ *   rk_epca_device        d_raw [rk_epca_out_doubles] and d_info [2], written.  Clade sums and profiles, then plain launches in
+ *                         stream order (two an iteration): no host synchronisation, n_active and k_eff stay on the device.
+ *                         2 <= S <= RK_EPCA_MAX_SAMPLES, 1 <= k <= RK_EPCA_MAX_COMPONENTS, 1 <= iters <= 10000.  Otherwise the
+ *                         argument rules of rk_kr_distances_device: RK_ERR_INVALID and a message, nothing launched.  Asynchronous
+ *                         on `stream`.
+ *   rk_epca_host          the same bits in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16.
+ *   rk_epca_batch         the drivers' call, with the contract of rk_kr_distances_batch: masses NULL = the buffer the last
+ *                         per-sample profile-only call left in the handle.  raw and info on the host; returns when they are filled.
+ *   rk_epca_finish_host   eigenvalue[k], share[k], residual[k], projection[S][k], loading[B][k] from a raw output, all written.
+ * Added without a bump of RK_VERSION (no existing struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_EPCA_MAX_SAMPLES 4096u
+#define RK_EPCA_MAX_COMPONENTS 8u
+uint64_t rk_epca_out_doubles(uint32_t n_branches, uint32_t n_samples, uint32_t k);
+uint64_t rk_epca_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t k);
+int rk_epca_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t k, uint32_t iters, double *d_raw, uint32_t *d_info,
+                   void *d_work, uint64_t work_bytes, void *stream);
+int rk_epca_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t k,
+                 uint32_t iters, double *raw, uint32_t *info, uint32_t n_threads);
+int rk_epca_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t k, uint32_t iters, double *raw, uint32_t *info);
+int rk_epca_finish_host(uint32_t n_branches, uint32_t n_samples, uint32_t k, const double *raw, double *eigenvalue, double *share,
+                        double *residual, double *projection /*[S][k]*/, double *loading /*[B][k]*/);
+
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the
  * packed kernels place (not BAD_CHAR / TOO_LONG / AMBIGUOUS, at least k symbols); kmers_hit = those with a row in the database

@@ -497,6 +497,34 @@ inline std::string squash_table(const std::vector<std::string> &names, const Squ
     return out + "#samples_without_mass\t" + std::to_string(S - n_with) + "\n";
 }
 
+// The text `--epca FILE` writes, every double as `%.17g`: `#epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff<TAB>iters`; the lines
+// `#eigenvalue`, `#share`, `#residual` with k values each; `#projections` and a line per sample (its name and k values); `#loadings`
+// and a line per node id (the id and k values); `#samples_without_mass<TAB>n`.  The arrays are what rk_epca_finish_host leaves:
+// eigenvalue, share, residual [k], projection [S][k], loading [B][k].  The twin of hostio.epca_table (byte-identical).
+inline std::string epca_table(const std::vector<std::string> &names, uint32_t n_branches, uint32_t k, uint32_t iters, uint32_t n_active, uint32_t k_eff,
+                              const double *eigenvalue, const double *share, const double *residual, const double *projection, const double *loading) {
+    const size_t S = names.size();
+    std::string out = "#epca\t" + std::to_string(S) + "\t" + std::to_string(n_branches) + "\t" + std::to_string(k) + "\t" + std::to_string(n_active) + "\t" +
+                      std::to_string(k_eff) + "\t" + std::to_string(iters) + "\n";
+    char buf[64];
+    auto row = [&](const std::string &head, const double *v) {
+        out += head;
+        for (uint32_t j = 0; j < k; j++) {
+            snprintf(buf, sizeof(buf), "\t%.17g", v[j]);
+            out += buf;
+        }
+        out += "\n";
+    };
+    row("#eigenvalue", eigenvalue);
+    row("#share", share);
+    row("#residual", residual);
+    out += "#projections\n";
+    for (size_t s = 0; s < S; s++) row(names[s], projection + s * k);
+    out += "#loadings\n";
+    for (size_t x = 0; x < n_branches; x++) row(std::to_string(x), loading + x * k);
+    return out + "#samples_without_mass\t" + std::to_string(S - n_active) + "\n";
+}
+
 // NumberFormat.getNumberInstance(Locale.UK), exactly 12 fraction digits, grouping commas (NewickWriter.java:61-64)
 inline std::string fmt12(float x) {
     char buf[400];

@@ -45,6 +45,11 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                [--squash FILE]  (with --sample-sep: the squash clustering of the samples over those distances, merged on the\n"
                  "                 device: a line #squash<TAB>S<TAB>n_merges, a line k<TAB>a<TAB>b<TAB>distance<TAB>size per merge, the tree as\n"
                  "                 #newick<TAB>...; (an inner node at half its distance), #inversions<TAB>n and #samples_without_mass<TAB>n)\n"
+                 "                [--epca FILE [--epca-components K] [--epca-iters N]]  (with --sample-sep: the edge principal components of the samples --\n"
+                 "                 the difference between the mass on the two sides of every edge, centred --, found on the device: K components\n"
+                 "                 (1..8, default 5) after N iterations (1..10000, default 200): a line #epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff\n"
+                 "                 <TAB>iters, the lines #eigenvalue, #share, #residual (k values each, %.17g), #projections and a line per sample,\n"
+                 "                 #loadings and a line per node id, and a last line #samples_without_mass<TAB>n)\n"
                  "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
                  "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
                  "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
@@ -57,10 +62,10 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path, epca_path;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
-        uint32_t keep_at_most = 7;
+        uint32_t keep_at_most = 7, epca_k = 5, epca_iters = 200;
         float keep_factor = 0.01f, nsbound = -INFINITY;
         bool guppy = false;
         int device = 0;
@@ -88,6 +93,9 @@ int main(int argc, char **argv) {
             else if (a == "--masses-only") masses_only_path = val();
             else if (a == "--kr") kr_path = val();
             else if (a == "--squash") squash_path = val();
+            else if (a == "--epca") epca_path = val();
+            else if (a == "--epca-components") epca_k = (uint32_t)std::stoul(val());
+            else if (a == "--epca-iters") epca_iters = (uint32_t)std::stoul(val());
             else if (a == "--sample-sep") { sample_sep = val(); if (sample_sep.size() != 1) throw std::runtime_error("--sample-sep takes one character"); }
             else if (a == "--help" || a == "-h") return usage(std::cout, 0);
             else if (a == "--nsbound") nsbound = std::stof(val());
@@ -331,6 +339,14 @@ int main(int argc, char **argv) {
             std::cerr << "rk_place: --squash clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)\n";
             return 2;
         }
+        if (!epca_path.empty() && sample_sep.empty()) {
+            std::cerr << "rk_place: --epca finds the principal components of the samples of one run: it needs --sample-sep (with --masses or --masses-only)\n";
+            return 2;
+        }
+        if (!epca_path.empty() && (epca_k < 1 || epca_k > RK_EPCA_MAX_COMPONENTS || epca_iters < 1 || epca_iters > 10000)) {
+            std::cerr << "rk_place: --epca-components must be in 1..8, --epca-iters in 1..10000\n";
+            return 2;
+        }
         const bool only_convert = !save_image.empty() && fasta.empty() && out.empty() && !masses_only;
         if (n_sources != 1 || (!only_convert && (fasta.empty() || (out.empty() && !masses_only))) || (only_convert && !dbimage.empty())) return usage();
         uint32_t amb_mode;
@@ -358,8 +374,9 @@ int main(int argc, char **argv) {
         // profile-only call left it on the device -- over the database's tree, through rk_kr_distances_batch
         rk_db *kr_db = nullptr;  // (the handle, once it is open)
         // --squash: the same, through rk_squash_batch; `host_words` is the host's copy either way (it tells which samples hold mass)
+        // --epca: the same, through rk_epca_batch and rk_epca_finish_host (one sample alone has no components: it is only counted)
         auto write_kr = [&](const rkh::Tree &t, const rkh::SampleMembers &sm, const uint64_t *words, const uint64_t *host_words) {
-            if (kr_path.empty() && squash_path.empty()) return;
+            if (kr_path.empty() && squash_path.empty() && epca_path.empty()) return;
             const uint32_t B = (uint32_t)t.nodes.size(), S = (uint32_t)sm.names.size();
             std::vector<int32_t> parent(B);
             std::vector<float> bl(B);
@@ -386,6 +403,26 @@ int main(int argc, char **argv) {
                 std::ofstream qf(squash_path, std::ios::binary);
                 if (!qf) throw std::runtime_error("cannot write " + squash_path);
                 qf << rkh::squash_table(sm.names, rows.data(), n_merges, with_mass);
+            }
+            if (!epca_path.empty()) {
+                const uint32_t k = epca_k;
+                uint32_t info[2] = {0, 0};
+                std::vector<double> ev(k, 0.0), share(k, 0.0), res(k, 0.0), proj((size_t)S * k, 0.0), load((size_t)B * k, 0.0);
+                if (S > 1) {
+                    std::vector<double> raw((size_t)rk_epca_out_doubles(B, S, k));
+                    if (rk_epca_batch(kr_db, kt, S, words, k, epca_iters, raw.data(), info) != RK_OK) throw std::runtime_error(std::string("rk_epca_batch: ") + rk_last_error());
+                    if (rk_epca_finish_host(B, S, k, raw.data(), ev.data(), share.data(), res.data(), proj.data(), load.data()) != RK_OK)
+                        throw std::runtime_error(std::string("rk_epca_finish_host: ") + rk_last_error());
+                } else {
+                    for (uint32_t s = 0; s < S; s++) {
+                        bool any = false;
+                        for (uint32_t x = 0; x < B && !any; x++) any = host_words[(size_t)s * (2 * (size_t)B + 4) + x] != 0;
+                        info[0] += any;
+                    }
+                }
+                std::ofstream ef(epca_path, std::ios::binary);
+                if (!ef) throw std::runtime_error("cannot write " + epca_path);
+                ef << rkh::epca_table(sm.names, B, k, epca_iters, info[0], info[1], ev.data(), share.data(), res.data(), proj.data(), load.data());
             }
         };
         // --masses: the per-edge table of the whole run.  The results are on the host already, so the sums are rk_masses_accumulate_host's;

@@ -23,6 +23,7 @@
 #include "rk_translate.h"
 #include "rk_masses.h"
 #include "rk_samples.h"
+#include "rk_epca.h"
 
 #include <type_traits>
 #ifndef RK_ROW_NT

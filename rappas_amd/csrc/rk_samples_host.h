@@ -1,6 +1,7 @@
-// rk_samples_host.h -- the host side of the sample-level calls (DESIGN.md 4.9, 4.10): the checks and the one walk of a tree behind
-// rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel, kr_pairs_kernel and the squash kernels (rk_samples.h)
-// behind rk_clade_masses_host, rk_kr_distances_host and rk_squash_host.  Header-only, plain C++, like rk_masses_host.h.  Not part of the C ABI.
+// rk_samples_host.h -- the host side of the sample-level calls (DESIGN.md 4.9 - 4.11): the checks and the one walk of a tree behind
+// rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel, kr_pairs_kernel, the squash kernels (rk_samples.h) and
+// the edge-PCA kernels (rk_epca.h) behind rk_clade_masses_host, rk_kr_distances_host, rk_squash_host and rk_epca_host.  Header-only,
+// plain C++, like rk_masses_host.h.  Not part of the C ABI.
 //
 // The KR distance is written as include/rappas_place.h defines it, term by term and in the order fixed there, so that the device and
 // this file give the same bits.  The reference has no counterpart: it stops at the jplace it writes.
@@ -8,6 +9,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <utility>
 #include <vector>
 
 namespace rk {
@@ -203,6 +205,152 @@ inline uint32_t squash_steps(uint32_t B, uint32_t S, double *u, double *v, doubl
         row_step(a);
     }
     return n_merges;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Edge principal components (include/rappas_place.h holds the definition, steps 1 - 8): the host twin of the epca kernels of
+// rk_epca.h, and the one finish (the only square roots) behind rk_epca_finish_host.  Profiles and the centred matrix lie sample
+// after sample, B doubles each; the column blocks Q, Y, Z are [k][S]; G is [S][S].
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t EPCA_LANES = 64, EPCA_MAX_SAMPLES = 4096, EPCA_MAX_COMPONENTS = 8, EPCA_MAX_ITERS = 10000;
+
+inline uint64_t epca_out_doubles(uint32_t B, uint32_t S, uint32_t k) { return 1 + (uint64_t)k * (3 + (uint64_t)S + B); }
+
+// LS(f): 64 sequential lane sums from +0.0 over s = l, l + 64, ..., added in ascending lane order onto +0.0
+template <class F>
+inline double lane_sum(uint32_t S, F &&f) {
+    double p[EPCA_LANES];
+    for (uint32_t l = 0; l < EPCA_LANES; l++) {
+        double a = 0.0;
+        for (uint32_t s = l; s < S; s += EPCA_LANES) a = a + f(s);
+        p[l] = a;
+    }
+    double r = 0.0;
+    for (uint32_t l = 0; l < EPCA_LANES; l++) r = r + p[l];
+    return r;
+}
+inline double epca_dot(uint32_t S, const double *a, const double *b) {
+    return lane_sum(S, [&](uint32_t s) { const double t = a[s] * b[s]; return t; });
+}
+
+// Steps 2 and 3 for the nodes x = x_lo, x_lo + x_step, ...: xc[s * B + x] from the profiles and the active flags (n of them set)
+inline void epca_centre(uint32_t B, uint32_t S, uint32_t root, const uint8_t *active, uint32_t n, const double *u, const double *v, uint32_t x_lo, uint32_t x_step,
+                        double *xc) {
+    for (uint64_t x = x_lo; x < B; x += x_step) {
+        auto X = [&](uint32_t s) { return active[s] && x != root ? (u[s * (uint64_t)B + x] + v[s * (uint64_t)B + x]) - 1.0 : 0.0; };
+        const double mean = lane_sum(S, X) / (double)n;
+        for (uint32_t s = 0; s < S; s++) xc[s * (uint64_t)B + x] = active[s] && x != root ? X(s) - mean : 0.0;
+    }
+}
+
+// G[s][t] from the centred rows of the two samples: the chunk rule, acc = acc + (a * b)
+inline double epca_gram_pair(uint32_t B, const double *xs, const double *xt) {
+    double g = 0.0;
+    for (uint32_t x0 = 0; x0 < B; x0 += KR_CHUNK) {
+        const uint32_t x1 = x0 + KR_CHUNK < B ? x0 + KR_CHUNK : B;
+        double acc = 0.0;
+        for (uint32_t x = x0; x < x1; x++) {
+            const double term = xs[x] * xt[x];
+            acc = acc + term;
+        }
+        g = x0 == 0 ? acc : g + acc;
+    }
+    return g;
+}
+
+// Rows s = s_lo, s_lo + s_step, ... of G: the pairs (s, t >= s), each written at [s][t] and [t][s]
+inline void epca_gram_rows(uint32_t B, uint32_t S, const double *xc, uint32_t s_lo, uint32_t s_step, double *G) {
+    for (uint64_t s = s_lo; s < S; s += s_step)
+        for (uint64_t t = s; t < S; t++) {
+            const double g = epca_gram_pair(B, xc + s * B, xc + t * B);
+            G[s * S + t] = g;
+            G[t * S + s] = g;
+        }
+}
+
+inline double epca_start(uint32_t s, uint32_t j) { return (double)((s * 8u + j + 1u) * 2654435761u) / 4294967296.0 - 0.5; }
+
+// out[j][s] = LS(t -> G[s][t] * in[j][t]) for j < k_eff
+inline void epca_multiply(uint32_t S, uint32_t k_eff, const double *G, const double *in, double *out) {
+    for (uint32_t j = 0; j < k_eff; j++)
+        for (uint64_t s = 0; s < S; s++) out[j * (uint64_t)S + s] = epca_dot(S, G + s * S, in + j * (uint64_t)S);
+}
+
+// Step 6 behind the product: the columns of Y scaled by their largest element and made orthogonal, in column order
+inline void epca_orth(uint32_t S, uint32_t k_eff, double *Y) {
+    for (uint32_t j = 0; j < k_eff; j++) {
+        double *yj = Y + j * (uint64_t)S;
+        uint32_t i = 0;
+        double best = std::fabs(yj[0]);
+        for (uint32_t s = 1; s < S; s++)
+            if (std::fabs(yj[s]) > best) {
+                best = std::fabs(yj[s]);
+                i = s;
+            }
+        if (best == 0.0) {
+            for (uint32_t s = 0; s < S; s++) yj[s] = 0.0;
+            continue;
+        }
+        const double pivot = yj[i];
+        for (uint32_t s = 0; s < S; s++) yj[s] = yj[s] / pivot;
+        const double nn = epca_dot(S, yj, yj);
+        for (uint32_t l = j + 1; l < k_eff; l++) {
+            double *yl = Y + l * (uint64_t)S;
+            const double d = epca_dot(S, yj, yl) / nn;
+            for (uint32_t s = 0; s < S; s++) {
+                const double t = d * yj[s];
+                yl[s] = yl[s] - t;
+            }
+        }
+    }
+}
+
+// Steps 5 - 8 over G and the centred matrix: the raw output.  work: 2 * k * S doubles.  k_eff > 0.
+inline void epca_iterate(uint32_t B, uint32_t S, uint32_t k, uint32_t k_eff, uint32_t iters, const double *G, const double *xc, double *work, double *raw) {
+    double *q = work, *y = work + (uint64_t)k * S;
+    for (uint32_t j = 0; j < k_eff; j++)
+        for (uint32_t s = 0; s < S; s++) q[j * (uint64_t)S + s] = epca_start(s, j);
+    for (uint32_t it = 0; it < iters; it++) {
+        epca_multiply(S, k_eff, G, q, y);
+        epca_orth(S, k_eff, y);
+        std::swap(q, y);
+    }
+    double *z = y;
+    epca_multiply(S, k_eff, G, q, z);
+    double *lambda = raw + 1, *nn = lambda + k, *rr = nn + k, *q_out = rr + k, *w_out = q_out + (uint64_t)k * S;
+    raw[0] = lane_sum(S, [&](uint32_t s) { return G[(uint64_t)s * S + s]; });
+    for (uint32_t j = 0; j < k_eff; j++) {
+        const double *qj = q + j * (uint64_t)S, *zj = z + j * (uint64_t)S;
+        nn[j] = epca_dot(S, qj, qj);
+        if (nn[j] == 0.0) {
+            nn[j] = lambda[j] = rr[j] = 0.0;
+        } else {
+            const double lam = epca_dot(S, qj, zj) / nn[j];
+            lambda[j] = lam;
+            rr[j] = lane_sum(S, [&](uint32_t s) {
+                const double t = lam * qj[s], r = zj[s] - t, r2 = r * r;
+                return r2;
+            });
+        }
+        for (uint32_t s = 0; s < S; s++) q_out[j * (uint64_t)S + s] = qj[s];
+        for (uint64_t x = 0; x < B; x++)
+            w_out[j * (uint64_t)B + x] = lane_sum(S, [&](uint32_t s) { const double t = xc[s * (uint64_t)B + x] * qj[s]; return t; });
+    }
+}
+
+// Finish: what a caller reads, from the raw output (rk_epca_finish_host)
+inline void epca_finish(uint32_t B, uint32_t S, uint32_t k, const double *raw, double *eigenvalue, double *share, double *residual, double *projection,
+                        double *loading) {
+    const double trace = raw[0], *lambda = raw + 1, *nn = lambda + k, *rr = nn + k, *q = rr + k, *w = q + (uint64_t)k * S;
+    for (uint32_t j = 0; j < k; j++) {
+        const bool on = lambda[j] > 0.0 && nn[j] != 0.0;
+        eigenvalue[j] = on ? lambda[j] : 0.0;
+        share[j] = on ? lambda[j] / trace : 0.0;
+        residual[j] = on ? std::sqrt(rr[j] / nn[j]) : 0.0;
+        const double ps = on ? std::sqrt(lambda[j] / nn[j]) : 0.0, ls = on ? std::sqrt(lambda[j] * nn[j]) : 1.0;
+        for (uint64_t s = 0; s < S; s++) projection[s * k + j] = on ? q[j * (uint64_t)S + s] * ps : 0.0;
+        for (uint64_t x = 0; x < B; x++) loading[x * k + j] = on ? w[j * (uint64_t)B + x] / ls : 0.0;
+    }
 }
 
 }  // namespace rk

@@ -1,8 +1,8 @@
 // rk_samples_impl.h -- #included by rk_engine.hip: the sample-level entry points -- the tree handle (rk_tree_*),
 // the clade sums of sample mass buffers (rk_clade_masses_device / _host), the KR distance matrix (rk_kr_distances_device / _host /
-// _batch) and the squash clustering over it (rk_squash_device / _host / _batch) -- over the kernels of rk_samples.h and the host twins
-// of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
-// scratch, and only the two _batch calls touch a database handle.
+// _batch), the squash clustering over it (rk_squash_device / _host / _batch) and the edge principal components (rk_epca_device / _host /
+// _batch / _finish_host) -- over the kernels of rk_samples.h and rk_epca.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
+// scratch, and only the _batch calls touch a database handle.
 #pragma once
 
 #include "rk_samples_host.h"
@@ -448,5 +448,224 @@ extern "C" int rk_squash_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, 
     HIP_TRY(hipMemcpyAsync(merges, d_out.p, rows_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(n_merges, d_count, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return RK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Edge principal components: rk_epca_out_doubles / _work_bytes / _device / _host / _batch / _finish_host.
+// ------------------------------------------------------------------------------------------------
+static_assert(RK_EPCA_MAX_SAMPLES == rk::EPCA_MAX_SAMPLES && RK_EPCA_MAX_COMPONENTS == rk::EPCA_MAX_COMPONENTS && RK_EPCA_MAX_COMPONENTS == EPCA_MAX_K,
+              "one set of limits for the header, the host twin and the kernels");
+
+// The workspace of rk_epca_device: the KR workspace without its pair partials (clade | u, which becomes Xc | v) | G[S][S] | the Gram
+// partials, chunks x S x S, when they are used | two column blocks [k][S] (the product reads one and writes the other) | active[S]
+struct EpcaPlan {
+    KrPlan kr;
+    uint64_t g_at, part_at, qa_at, qb_at, active_at, bytes;
+};
+static bool epca_plan(uint32_t B, uint32_t S, uint32_t k, EpcaPlan &p) {
+    if (!kr_plan(B, S, p.kr)) return false;
+    auto up = [](uint64_t v) { return (v + 15) / 16 * 16; };
+    const uint64_t ss = (uint64_t)S * S * 8;
+    p.g_at = up(p.kr.part_at);
+    p.part_at = p.g_at + ss;
+    p.qa_at = p.part_at + (p.kr.to_part ? ss * p.kr.n_chunks : 0);
+    p.qb_at = p.qa_at + (uint64_t)k * S * 8;
+    p.active_at = p.qb_at + (uint64_t)k * S * 8;
+    p.bytes = up(p.active_at + (uint64_t)S * 4);
+    return p.bytes <= RK_KR_MAX_WORK_BYTES;
+}
+
+static int epca_args(const char *who, const rk_tree *t, uint32_t S, uint32_t k, uint32_t iters) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (S < 2 || S > RK_EPCA_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, S, RK_EPCA_MAX_SAMPLES);
+    if (k < 1 || k > RK_EPCA_MAX_COMPONENTS) return fail(RK_ERR_INVALID, "%s: k=%u components must be in 1..%u", who, k, RK_EPCA_MAX_COMPONENTS);
+    if (iters < 1 || iters > rk::EPCA_MAX_ITERS) return fail(RK_ERR_INVALID, "%s: iters=%u must be in 1..%u", who, iters, rk::EPCA_MAX_ITERS);
+    return RK_OK;
+}
+
+extern "C" uint64_t rk_epca_out_doubles(uint32_t n_branches, uint32_t n_samples, uint32_t k) {
+    if (n_branches < 1 || n_branches > 65535 || n_samples < 2 || n_samples > RK_EPCA_MAX_SAMPLES || k < 1 || k > RK_EPCA_MAX_COMPONENTS) return 0;
+    return rk::epca_out_doubles(n_branches, n_samples, k);
+}
+
+extern "C" uint64_t rk_epca_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t k) {
+    const char *who = "rk_epca_work_bytes";
+    if (epca_args(who, t, n_samples, k, 1)) return 0;
+    EpcaPlan p;
+    if (!epca_plan(t->B, n_samples, k, p)) {
+        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+        return 0;
+    }
+    return p.bytes;
+}
+
+// The launches behind rk_epca_device.  `steps` (developer builds, scripts/epca_rate.py): bit 0 clade sums, profiles and the start,
+// 1 the centring pass, 2 the Gram matrix, 3 the iterations, 4 the results and the loadings.  Every kernel keeps to the k columns and
+// the S samples whatever the workspace holds, so any subset is safe to time on a workspace a whole call has used.
+static int epca_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, uint32_t k, uint32_t iters, double *d_raw, uint32_t *d_info, void *d_work,
+                       const EpcaPlan &p, hipStream_t s, unsigned steps = 31) {
+    const uint32_t B = t->B, n_chunks = p.kr.n_chunks;
+    char *w = (char *)d_work;
+    const u64 *clade = (const u64 *)(w + p.kr.clade_at);
+    double *Xc = (double *)(w + p.kr.u_at), *V = (double *)(w + p.kr.v_at), *G = (double *)(w + p.g_at), *part = (double *)(w + p.part_at);
+    double *qa = (double *)(w + p.qa_at), *qb = (double *)(w + p.qb_at);
+    u32 *active = (u32 *)(w + p.active_at);
+    const u32 *info = (const u32 *)d_info;
+    const unsigned rows = (S + EPCA_WAVES - 1) / EPCA_WAVES, nodes = (B + EPCA_WAVES - 1) / EPCA_WAVES;
+    if (steps & 1) {
+        if (int rc = kr_launch(t, S, d_masses, nullptr, d_work, p.kr, s, 3)) return rc;
+        hipLaunchKernelGGL(epca_init_kernel, dim3(1), dim3(256), 0, s, B, S, k, t->root, clade, active, (u32 *)d_info, qa);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 2) {
+        hipLaunchKernelGGL(epca_centre_kernel, dim3(nodes), dim3(64 * EPCA_WAVES), 0, s, B, S, t->root, (const u32 *)active, info, Xc, (const double *)V);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 4) {
+        const uint32_t side = (S + KR_TILE - 1) / KR_TILE;
+        const uint64_t tiles = (uint64_t)side * (side + 1) / 2;
+        hipLaunchKernelGGL(epca_gram_kernel, dim3((unsigned)tiles, p.kr.to_part ? n_chunks : 1), dim3(256), 0, s, B, S, side, p.kr.to_part ? 1u : n_chunks,
+                           p.kr.to_part ? 1u : 0u, (const double *)Xc, G, part);
+        HIP_TRY(hipGetLastError());
+        if (p.kr.to_part) {
+            const uint64_t n = (uint64_t)S * S;
+            hipLaunchKernelGGL(kr_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u64)n, n_chunks, (const double *)part, G);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    double *q = qa, *y = qb;
+    if (steps & 8)
+        for (uint32_t it = 0; it < iters; it++) {
+            hipLaunchKernelGGL(epca_multiply_kernel, dim3(rows), dim3(64 * EPCA_WAVES), 0, s, S, k, info, (const double *)G, (const double *)q, y);
+            hipLaunchKernelGGL(epca_orth_kernel, dim3(1), dim3(64 * EPCA_WAVES), 0, s, S, k, info, y);
+            HIP_TRY(hipGetLastError());
+            std::swap(q, y);
+        }
+    if (steps & 16) {
+        double *w_out = d_raw + 1 + (uint64_t)k * (3 + (uint64_t)S);
+        hipLaunchKernelGGL(epca_multiply_kernel, dim3(rows), dim3(64 * EPCA_WAVES), 0, s, S, k, info, (const double *)G, (const double *)q, y);
+        hipLaunchKernelGGL(epca_results_kernel, dim3(1), dim3(64 * EPCA_WAVES), 0, s, S, k, info, (const double *)G, (const double *)q, (const double *)y, d_raw);
+        hipLaunchKernelGGL(epca_loadings_kernel, dim3(nodes), dim3(64 * EPCA_WAVES), 0, s, B, S, k, info, (const double *)Xc, (const double *)q, w_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return RK_OK;
+}
+
+extern "C" int rk_epca_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t k, uint32_t iters, double *d_raw, uint32_t *d_info,
+                              void *d_work, uint64_t work_bytes, void *stream) {
+    const char *who = "rk_epca_device";
+    if (int rc = epca_args(who, t, n_samples, k, iters)) return rc;
+    EpcaPlan p;
+    if (!epca_plan(t->B, n_samples, k, p)) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+    if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!d_raw || !d_info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if ((uintptr_t)d_raw % 8 || (uintptr_t)d_info % 4) return fail(RK_ERR_INVALID, "%s: the raw output must be 8-byte aligned, the info words 4-byte aligned", who);
+    if (!d_work || work_bytes < p.bytes)
+        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_epca_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
+    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    HIP_TRY(hipSetDevice(t->device));
+    unsigned steps = 31;
+    if (const char *v = rk_knob("RK_EPCA_STEPS")) steps = (unsigned)atoi(v);  // developer builds (scripts/epca_rate.py)
+    return epca_launch(t, n_samples, d_masses, k, iters, d_raw, d_info, d_work, p, (hipStream_t)stream, steps);
+}
+
+extern "C" int rk_epca_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t k,
+                            uint32_t iters, double *raw, uint32_t *info, uint32_t n_threads) {
+    const char *who = "rk_epca_host";
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (n_samples < 2 || n_samples > RK_EPCA_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, n_samples, RK_EPCA_MAX_SAMPLES);
+    if (k < 1 || k > RK_EPCA_MAX_COMPONENTS) return fail(RK_ERR_INVALID, "%s: k=%u components must be in 1..%u", who, k, RK_EPCA_MAX_COMPONENTS);
+    if (iters < 1 || iters > rk::EPCA_MAX_ITERS) return fail(RK_ERR_INVALID, "%s: iters=%u must be in 1..%u", who, iters, rk::EPCA_MAX_ITERS);
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!raw || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
+    std::vector<uint64_t> clade;
+    std::vector<double> u, v, G, cols;  // (u becomes the centred matrix)
+    std::vector<uint8_t> active;
+    try {
+        clade.resize(S * B);
+        u.resize(S * B);
+        v.resize(S * B);
+        G.resize(S * S);
+        cols.resize(2 * (uint64_t)k * S);
+        active.resize(S);
+    } catch (const std::bad_alloc &) {
+        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
+    }
+    unsigned hw = std::thread::hardware_concurrency();
+    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
+    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
+    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        for (uint64_t s = th; s < S; s += T) {
+            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
+            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
+        }
+    });
+    if (rc) return rc;
+    uint32_t n = 0;
+    for (uint64_t s = 0; s < S; s++) n += active[s] = clade[s * B + w.root] != 0;
+    const uint32_t k_eff = n < 2 ? 0u : std::min(k, n - 1);
+    info[0] = n;
+    info[1] = k_eff;
+    const uint64_t n_out = rk::epca_out_doubles(n_branches, n_samples, k);
+    for (uint64_t i = 0; i < n_out; i++) raw[i] = 0.0;
+    if (!k_eff) return RK_OK;
+    // nodes, then rows of G, dealt round to the threads
+    rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        rk::epca_centre((uint32_t)B, (uint32_t)S, w.root, active.data(), n, u.data(), v.data(), (uint32_t)th, (uint32_t)T, u.data());
+    });
+    if (rc) return rc;
+    rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) { rk::epca_gram_rows((uint32_t)B, (uint32_t)S, u.data(), (uint32_t)th, (uint32_t)T, G.data()); });
+    if (rc) return rc;
+    rk::epca_iterate((uint32_t)B, (uint32_t)S, k, k_eff, iters, G.data(), u.data(), cols.data(), raw);
+    return RK_OK;
+}
+
+// The drivers' call: as rk_kr_distances_batch, with the raw output and the two info words on the host at the end
+extern "C" int rk_epca_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t k, uint32_t iters, double *raw, uint32_t *info) {
+    const char *who = "rk_epca_batch";
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (int rc = epca_args(who, t, n_samples, k, iters)) return rc;
+    if (!raw || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (t->B != db->info.n_branches || t->device != db->info.device)
+        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
+    const uint64_t need = rk_epca_work_bytes(t, n_samples, k), words = rk_masses_samples_words(t->B, n_samples);
+    if (!need) return RK_ERR_INVALID;
+    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
+    std::lock_guard<std::mutex> lock(db->host_mutex);
+    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
+        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
+    HIP_TRY(hipSetDevice(db->info.device));
+    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
+    hipStream_t s = db->ws[0].stream;
+    GrowBuf work, d_out, d_in;
+    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
+    const uint64_t raw_bytes = rk::epca_out_doubles(t->B, n_samples, k) * 8;  // the raw output, then the info words
+    if (int rc = work.reserve(need)) return rc;
+    if (int rc = d_out.reserve(raw_bytes + 8)) return rc;
+    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
+    if (masses) {
+        if (int rc = d_in.reserve(words * 8)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
+        d_masses = d_in.as<uint64_t>();
+    }
+    uint32_t *d_info = (uint32_t *)((char *)d_out.p + raw_bytes);
+    if (int rc = rk_epca_device(t, n_samples, d_masses, k, iters, (double *)d_out.p, d_info, work.p, need, s)) return rc;
+    HIP_TRY(hipMemcpyAsync(raw, d_out.p, raw_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(info, d_info, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RK_OK;
+}
+
+extern "C" int rk_epca_finish_host(uint32_t n_branches, uint32_t n_samples, uint32_t k, const double *raw, double *eigenvalue, double *share, double *residual,
+                                   double *projection, double *loading) {
+    const char *who = "rk_epca_finish_host";
+    if (!rk_epca_out_doubles(n_branches, n_samples, k))
+        return fail(RK_ERR_INVALID, "%s: n_branches=%u, n_samples=%u, k=%u: out of 1..65535, 2..%u, 1..%u", who, n_branches, n_samples, k, RK_EPCA_MAX_SAMPLES, RK_EPCA_MAX_COMPONENTS);
+    if (!raw) return fail(RK_ERR_INVALID, "%s: null raw output", who);
+    if (!eigenvalue || !share || !residual || !projection || !loading) return fail(RK_ERR_INVALID, "%s: null output", who);
+    rk::epca_finish(n_branches, n_samples, k, raw, eigenvalue, share, residual, projection, loading);
     return RK_OK;
 }

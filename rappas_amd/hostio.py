@@ -408,6 +408,27 @@ def kr_table(names, D):
     return "".join(out)
 
 
+def epca_table(names, n_branches, k, iters, n_active, k_eff, eigenvalue, share, residual, projection, loading):
+    """the text `--epca FILE` writes, every double as `%.17g`: a line `#epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff<TAB>iters`; the
+    lines `#eigenvalue`, `#share`, `#residual` with k values each; `#projections` and a line per sample (its name and k values);
+    `#loadings` and a line per node id (the id and k values); `#samples_without_mass<TAB>n`.  The arrays are what placement.epca_finish
+    gives: eigenvalue, share, residual [k], projection [S, k], loading [B, k].  The twin of rkh::epca_table, byte-identical."""
+    S = len(names)
+    projection = np.asarray(projection, np.float64).reshape(S, k)
+    loading = np.asarray(loading, np.float64).reshape(n_branches, k)
+
+    def row(head, v):
+        return head + "".join("\t%.17g" % float(v[j]) for j in range(k)) + "\n"
+
+    out = [f"#epca\t{S}\t{n_branches}\t{k}\t{n_active}\t{k_eff}\t{iters}\n", row("#eigenvalue", eigenvalue), row("#share", share),
+           row("#residual", residual), "#projections\n"]
+    out.extend(row(names[s], projection[s]) for s in range(S))
+    out.append("#loadings\n")
+    out.extend(row(str(x), loading[x]) for x in range(n_branches))
+    out.append(f"#samples_without_mass\t{S - n_active}\n")
+    return "".join(out)
+
+
 def _squash_leaf(name):
     """a sample name as a Newick leaf: single-quoted, a quote doubled, when it holds any of ()[]':;, or white space"""
     if any(c in "()[]':;, \t\n\r\v\f" for c in name):

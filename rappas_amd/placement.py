@@ -6,6 +6,7 @@ src/core/algos/PlacementProcess.java:471-483 that reach the hot path (keepAtMost
 treatAmbiguitiesWithMax) and returns, per read, what :974-1025 turns into jplace rows.
 No compute happens in Python and nothing here falls back to a CPU implementation.
 """
+import collections
 import ctypes as C
 from dataclasses import dataclass
 
@@ -805,6 +806,48 @@ def squash_host(parent, branch_len, masses, n_samples, threads=0):
     return merges, int(n.value)
 
 
+# what epca_finish makes of a raw edge-PCA output: eigenvalue, share, residual [k]; projection [S, k]; loading [B, k]; the two info words
+EdgePCA = collections.namedtuple("EdgePCA", "eigenvalue share residual projection loading n_active k_eff")
+
+
+def _epca_out(n_branches, n_samples, k):
+    n = int(_lib.load().rk_epca_out_doubles(n_branches, n_samples, k))
+    if not n:
+        raise _lib.RkError(_lib.RK_ERR_INVALID, f"edge PCA: n_branches={n_branches}, n_samples={n_samples}, k={k}: out of 1..65535, 2..4096, 1..8")
+    return n
+
+
+def epca_host(parent, branch_len, masses, n_samples, k, iters, threads=0):
+    """rk_epca_host (no GPU): (raw, info) -- the raw edge-PCA output of the samples of a sample mass buffer on the tree (parent, branch_len),
+    float64 [1 + k * (3 + S + B)]: trace | lambda[k] | nn[k] | rr[k] | q[k][S] | w[k][B], and uint32 [2]: n_active, k_eff -- the bits
+    EdgeTree.epca gives on the device.  epca_finish turns them into eigenvalues, projections and loadings."""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    B = parent.shape[0]
+    masses = _samples_in(B, n_samples, masses)
+    raw = np.zeros(max(int(_lib.load().rk_epca_out_doubles(B, n_samples, k)), 1), np.float64)
+    info = np.zeros(2, np.uint32)
+    _lib.check(_lib.load().rk_epca_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), k, iters, _ptr(raw), _ptr(info), threads))
+    return raw, info
+
+
+def epca_finish(n_branches, n_samples, k, raw, info=None):
+    """rk_epca_finish_host: an EdgePCA from a raw output (a host array, or a device tensor, which is downloaded) -- the eigenvalues of the
+    Gram matrix of the centred edge imbalances, their shares of its trace, the residuals |G q - lambda q| of the unit vectors, the
+    projections of the samples [S, k] and the unit-norm loadings of the edges [B, k].  The only square roots of the edge PCA are here."""
+    if hasattr(raw, "cpu"):
+        raw = raw.cpu().numpy()
+    if info is not None and hasattr(info, "cpu"):
+        info = info.cpu().numpy()
+    raw = np.ascontiguousarray(raw, dtype=np.float64).reshape(-1)
+    if raw.shape[0] != _epca_out(n_branches, n_samples, k):
+        raise ValueError(f"raw holds {raw.shape[0]} doubles, an edge PCA of {k} components of {n_samples} samples on {n_branches} branches has {_epca_out(n_branches, n_samples, k)}")
+    ev, share, res = np.zeros(k), np.zeros(k), np.zeros(k)
+    proj, load = np.zeros((n_samples, k)), np.zeros((n_branches, k))
+    _lib.check(_lib.load().rk_epca_finish_host(n_branches, n_samples, k, _ptr(raw), _ptr(ev), _ptr(share), _ptr(res), _ptr(proj), _ptr(load)))
+    n_active, k_eff = (None, None) if info is None else (int(np.asarray(info).view(np.uint32)[0]), int(np.asarray(info).view(np.uint32)[1]))
+    return EdgePCA(ev, share, res, proj, load, n_active, k_eff)
+
+
 class EdgeTree:
     """rk_tree: the shape of a reference tree on the device -- parent[x] the node id of x's parent (-1 for the root), branch_len[x] the
     length of the edge above x -- for the sample-level calls over device mass buffers.  Takes and returns torch device tensors and owns
@@ -903,6 +946,39 @@ class EdgeTree:
         n = C.c_uint32(0)
         _lib.check(self._lib.rk_squash_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(merges), C.byref(n)))
         return merges, int(n.value)
+
+    def epca_work_bytes(self, n_samples, k):
+        need = int(self._lib.rk_epca_work_bytes(self.handle, n_samples, k))
+        if not need:
+            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
+        return need
+
+    def epca(self, masses, n_samples, k, iters, stream=None):
+        """rk_epca_device: (raw, info) as device tensors, written -- float64 [1 + k * (3 + S + B)] and int32 [2] (n_active, k_eff), as
+        epca_host gives them; asynchronous on the stream.  epca_finish(B, S, k, raw, info) downloads and finishes them."""
+        import torch
+        dev = self._masses(masses, n_samples)
+        need = self.epca_work_bytes(n_samples, k)
+        if self._work_buf is None or self._work_buf.numel() < need:
+            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        raw = torch.empty((_epca_out(self.n_branches, n_samples, k),), dtype=torch.float64, device=dev)
+        info = torch.empty((2,), dtype=torch.int32, device=dev)
+        _lib.check(self._lib.rk_epca_device(self.handle, n_samples, masses.data_ptr(), k, iters, raw.data_ptr(), info.data_ptr(), self._work_buf.data_ptr(),
+                                            self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+        return raw, info
+
+    def epca_batch(self, db, n_samples, k, iters, masses=None):
+        """rk_epca_batch, the drivers' call: (raw, info) on the host, as epca_host gives them, from a host sample mass buffer -- or, masses
+        None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_epca_device on db's
+        device; returns when they are there"""
+        if masses is not None:
+            masses = _samples_in(self.n_branches, n_samples, masses)
+            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
+                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        raw = np.zeros(max(int(self._lib.rk_epca_out_doubles(self.n_branches, n_samples, k)), 1), np.float64)
+        info = np.zeros(2, np.uint32)
+        _lib.check(self._lib.rk_epca_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), k, iters, _ptr(raw), _ptr(info)))
+        return raw, info
 
     def close(self):
         if self._h:

@@ -19,6 +19,8 @@ MASSES_ONLY_WITH_OUT = "--masses-only writes no jplace (the placements never rea
 MASSES_ONLY_WITH_MASSES = "--masses-only writes the table --masses writes, without placing into a jplace: give one of the two"
 KR_NEEDS_SAMPLE_SEP = "--kr compares the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 SQUASH_NEEDS_SAMPLE_SEP = "--squash clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
+EPCA_NEEDS_SAMPLE_SEP = "--epca finds the principal components of the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
+EPCA_RANGES = "--epca-components must be in 1..8, --epca-iters in 1..10000"
 SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
 
@@ -55,9 +57,30 @@ def squash_text(db, tree, sample_names, words, host_words, device=0):
         et.close()
 
 
+def epca_text(db, tree, sample_names, words, host_words, k, iters, device=0):
+    """`--epca FILE`: the table (hostio.epca_table) of the edge principal components of the samples of a sample mass buffer over the
+    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`; host_words: the host's copy
+    either way (one sample alone has no components: it is only counted)"""
+    from ..placement import EdgeTree, epca_finish
+    S, B = len(sample_names), len(tree.nodes)
+    if S < 2:
+        W = 2 * B + 4
+        host_words = np.asarray(host_words, dtype=np.uint64).reshape(-1)
+        n_active = sum(bool(host_words[s * W:s * W + B].any()) for s in range(S))
+        return hostio.epca_table(sample_names, B, k, iters, n_active, 0, np.zeros(k), np.zeros(k), np.zeros(k), np.zeros((S, k)), np.zeros((B, k)))
+    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
+    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
+    try:
+        raw, info = et.epca_batch(db, S, k, iters, words)
+        f = epca_finish(B, S, k, raw, info)
+        return hostio.epca_table(sample_names, B, k, iters, f.n_active, f.k_eff, f.eigenvalue, f.share, f.residual, f.projection, f.loading)
+    finally:
+        et.close()
+
+
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
                call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None, kr=False,
-               squash=False):
+               squash=False, epca=False, epca_components=5, epca_iters=200):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
@@ -65,9 +88,14 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both".  masses: res.masses is
     then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for);
     with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table); with kr as well res.kr is
-    the text `--kr FILE` writes (kr_text), with squash res.squash the text `--squash FILE` writes (squash_text)."""
+    the text `--kr FILE` writes (kr_text), with squash res.squash the text `--squash FILE` writes (squash_text), with epca res.epca the text
+    `--epca FILE` writes (epca_text) for epca_components components after epca_iters iterations."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
+    if epca and not (masses and sample_sep is not None):
+        raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
+    if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
+        raise ValueError(EPCA_RANGES)
     if kr and not (masses and sample_sep is not None):
         raise ValueError(KR_NEEDS_SAMPLE_SEP)
     if squash and not (masses and sample_sep is not None):
@@ -87,7 +115,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
             res = PlacementProcess(db, ns_bound).processQueries(
                 seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
                 treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
-        res.kr = res.squash = None
+        res.kr = res.squash = res.epca = None
         if members is not None:
             from ..placement import accumulate_masses_samples_host
             sample_names, m_off, m_sample, m_weight = members
@@ -97,6 +125,8 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
                 res.kr = kr_text(db, tree, sample_names, sample_words, device)
             if squash:
                 res.squash = squash_text(db, tree, sample_names, sample_words, sample_words, device)
+            if epca:
+                res.epca = epca_text(db, tree, sample_names, sample_words, sample_words, epca_components, epca_iters, device)
     finally:
         db.close()
     pl = hostio.jplace_placements(tree, names, res.n_rows, res.branch, res.score, res.lwr, guppy)
@@ -114,22 +144,27 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
 
 
 def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), device=0, union=False,
-                     dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None, kr=False, squash=False):
+                     dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None, kr=False, squash=False, epca=False, epca_components=5,
+                     epca_iters=200):
     """`--masses-only FILE`: scan, dedup and gather as place_file, then ONE profile-only call (processQueriesMasses) with the
     multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
     table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
     No jplace and no frames log: the rows and the frame bytes never reach the host.  With sample_sep (one character) the one call is
     processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample; with kr as well
     .kr is the text `--kr FILE` writes, from the buffer that call left on the device, and with squash .squash the text `--squash FILE`
-    writes, from the same buffer."""
+    writes, from the same buffer, and with epca .epca the text `--epca FILE` writes, from the same buffer again."""
     from types import SimpleNamespace
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
+    if epca and sample_sep is None:
+        raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
+    if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
+        raise ValueError(EPCA_RANGES)
     if kr and sample_sep is None:
         raise ValueError(KR_NEEDS_SAMPLE_SEP)
     if squash and sample_sep is None:
         raise ValueError(SQUASH_NEEDS_SAMPLE_SEP)
-    kr_out = squash_out = None
+    kr_out = squash_out = epca_out = None
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     try:
         if translate and db.info.alphabet != 20:
@@ -149,6 +184,8 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
                 kr_out = kr_text(db, tree, sample_names, None, device)
             if squash:
                 squash_out = squash_text(db, tree, sample_names, None, words, device)
+            if epca:
+                epca_out = epca_text(db, tree, sample_names, None, words, epca_components, epca_iters, device)
         else:
             words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(seq, off, weights=weights, **common)
             table = hostio.masses_table(tree, words)
@@ -156,7 +193,7 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
         db.close()
     return SimpleNamespace(masses=table, notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
                            reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters, kr=kr_out,
-                           squash=squash_out)
+                           squash=squash_out, epca=epca_out)
 
 
 def _open_db(db_text, union, dbimage, save_dbimage, device):
@@ -221,6 +258,13 @@ def main(argv=None):
                     help="with --sample-sep: the squash clustering of the samples over those distances, merged on the device: a line "
                          "#squash<TAB>S<TAB>n_merges, a line k<TAB>a<TAB>b<TAB>distance<TAB>size per merge, the tree as #newick<TAB>...; "
                          "(an inner node at half its distance), #inversions<TAB>n and #samples_without_mass<TAB>n")
+    ap.add_argument("--epca", default=None, metavar="FILE",
+                    help="with --sample-sep: the edge principal components of the samples (the difference between the mass on the two sides "
+                         "of every edge, centred), found on the device: a line #epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff<TAB>iters, the "
+                         "lines #eigenvalue, #share, #residual (k values each, %%.17g), #projections and a line per sample, #loadings and a "
+                         "line per node id, and a last line #samples_without_mass<TAB>n")
+    ap.add_argument("--epca-components", type=int, default=5, metavar="K", help="--epca: the number of components, 1..8 (default 5)")
+    ap.add_argument("--epca-iters", type=int, default=200, metavar="N", help="--epca: the fixed number of iterations, 1..10000 (default 200)")
     ap.add_argument("--timing", action="store_true", help="--masses-only: one JSON line with the run's wall-clock times on stdout")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
@@ -240,6 +284,10 @@ def main(argv=None):
         ap.error(KR_NEEDS_SAMPLE_SEP)
     if a.squash is not None and a.sample_sep is None:
         ap.error(SQUASH_NEEDS_SAMPLE_SEP)
+    if a.epca is not None and a.sample_sep is None:
+        ap.error(EPCA_NEEDS_SAMPLE_SEP)
+    if a.epca is not None and not (1 <= a.epca_components <= 8 and 1 <= a.epca_iters <= 10000):
+        ap.error(EPCA_RANGES)
     if a.masses_only is None and a.out is None:
         ap.error("--out is required (or --masses-only FILE for a profile-only run)")
     db_text = None
@@ -255,7 +303,7 @@ def main(argv=None):
         doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
                               translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep, kr=a.kr is not None,
-                              squash=a.squash is not None)
+                              squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -282,6 +330,9 @@ def main(argv=None):
     if res.squash is not None:
         with open(a.squash, "w") as f:
             f.write(res.squash)
+    if res.epca is not None:
+        with open(a.epca, "w") as f:
+            f.write(res.epca)
     placed = int(np.count_nonzero(res.n_rows))
     print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
     return 0
@@ -294,7 +345,7 @@ def _main_masses_only(a, db_text, fasta_text):
     try:
         res = masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.device, union=a.uniondb is not None,
                                dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate, sample_sep=a.sample_sep, kr=a.kr is not None,
-                               squash=a.squash is not None)
+                               squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -309,6 +360,9 @@ def _main_masses_only(a, db_text, fasta_text):
     if res.squash is not None:
         with open(a.squash, "w") as f:
             f.write(res.squash)
+    if res.epca is not None:
+        with open(a.epca, "w") as f:
+            f.write(res.epca)
     logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.masses_only)), "logs")
     os.makedirs(logs, exist_ok=True)
     with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
