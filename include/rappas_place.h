@@ -654,6 +654,53 @@ int rk_epca_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_
 int rk_epca_finish_host(uint32_t n_branches, uint32_t n_samples, uint32_t k, const double *raw, double *eigenvalue, double *share,
                         double *residual, double *projection /*[S][k]*/, double *loading /*[B][k]*/);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * EDPL, the expected distance between placement locations of a read (Matsen et al. 2010; what `guppy edpl` / `gappa examine edpl`
+ * compute from jplace files): the sum over the pairs of a read's placements of LWR x LWR x the tree path between them -- small for
+ * a read whose rows sit on neighbouring edges, large for one whose weight is split between distant clades.  The reference has no
+ * counterpart.  A placement sits at the midpoint of its edge, as in the KR block and as the jplace writers put it (distal_length =
+ * branch_len / 2, pendant_length = 0).  Fixed so that every implementation gives the same bits: all arithmetic is binary64 with
+ * IEEE conversion, *, + and -, no contraction.
+ *   Tree quantities     on the tree of rk_tree_create (parent, branch_len, B nodes): D[root] = +0.0; D[x] = D[parent[x]] +
+ *                       (double)branch_len[x], one add per node from its parent's value; h[x] as in the KR block; pos[x] = D[x] -
+ *                       h[x], the root distance of the midpoint of the edge above x (pos[root] = +0.0).
+ *   Distance            between branches a != b, l their lowest common ancestor (which may be a or b):
+ *                           l == a (a is an ancestor of b)      d(a, b) = pos[b] - pos[a]
+ *                           l == b                              d(a, b) = pos[a] - pos[b]
+ *                           otherwise                           d(a, b) = (pos[a] - D[l]) + (pos[b] - D[l])
+ *                       d(a, a) = +0.0.  Nothing is clamped.  The ancestor cases are not a special form of the third line: the midpoint
+ *                       of a's edge lies above node a, so that line with l = a would be wrong by 2 h[a].  l is unique, so the bits do
+ *                       not depend on how it is found.
+ *   Read r              K = keep_at_most.  The usable rows are e < min(n_rows[r], K) with branch < B and lwr > 0, in row order (a NaN
+ *                       or a weight that is not positive fails the comparison: the row is skipped).  Weights are taken as given, not
+ *                       renormalised.  acc starts at +0.0; for i ascending and, inside it, j > i ascending over the usable rows:
+ *                       acc = acc + ((w_i * w_j) * d(b_i, b_j)).  edpl[r] = 2.0 * acc: the sum over ordered pairs, as the paper has
+ *                       it.  Fewer than two usable rows, an unplaced read included, give +0.0.  score and flags are not read and may
+ *                       be NULL.
+ *   rk_edpl_device        d_res and d_edpl [n_reads] are device pointers on the tree's device; d_edpl is WRITTEN, not added into.
+ *                         Asynchronous on `stream`, allocates nothing and uses no scratch of any handle; the result does not depend on
+ *                         grid, stream or how a batch is split into calls.  The query cost does not grow with the depth of the tree.
+ *   rk_edpl_host          the same bits in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16.
+ *   rk_edpl_batch         the drivers' call: a host result set in, host doubles out, in chunks through rk_edpl_device on db's device
+ *                         (the tree must be on it and have the database's B).  Uploads only n_rows, branch and lwr; allocates and
+ *                         frees its buffers; returns when `edpl` is filled.
+ *   rk_tree_distance_host d[i] = d(a[i], b[i]) for n_pairs pairs, for tests and callers; a branch >= B is RK_ERR_INVALID.
+ *   rk_edpl_lds_bytes     which form of the kernel a tree gets: the bytes of its distance tables when they are copied into the LDS of
+ *                         every block, 0 when they are read from global memory (DESIGN.md 4.12 has the rule).
+ *   Errors                with the rules of rk_masses_accumulate_device: RK_ERR_INVALID and a message for a NULL tree, n_rows, branch,
+ *                         lwr or output, keep_at_most outside 1..RK_EDPL_MAX_KEEP, n_reads >= 2^32; nothing is launched and no byte
+ *                         written.  n_reads == 0 is RK_OK and touches nothing.
+ * Added without a bump of RK_VERSION (no existing struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_EDPL_MAX_KEEP 16u
+int rk_edpl_device(const rk_tree *t, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_res, double *d_edpl, void *stream);
+int rk_edpl_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t keep_at_most, uint64_t n_reads,
+                 const rk_result *res, double *edpl, uint32_t n_threads);
+int rk_edpl_batch(rk_db *db, const rk_tree *t, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, double *edpl);
+int rk_tree_distance_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_pairs, const uint16_t *a,
+                          const uint16_t *b, double *d);
+uint64_t rk_edpl_lds_bytes(const rk_tree *t);
+
 /* Optional diagnostics (round 4): the work a batch of packed reads asks of the database, counted by a kernel of its own -- the
  * placement kernels carry no counters.  kmers_probed = sum of sk.getMerCount() (AmbigSequenceKnife.java:191) over the reads the
  * packed kernels place (not BAD_CHAR / TOO_LONG / AMBIGUOUS, at least k symbols); kmers_hit = those with a row in the database

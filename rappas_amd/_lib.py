@@ -17,6 +17,7 @@ RK_STEP_TRANSLATED = 3  # `step` of rk_place_batch_masses beside the three stran
 STRANDS = {"forward": RK_STRAND_FORWARD, "fwd": RK_STRAND_FORWARD, "reverse": RK_STRAND_REVERSE, "rev": RK_STRAND_REVERSE, "both": RK_STRAND_BOTH}
 RK_SQUASH_MAX_SAMPLES, RK_SQUASH_NONE = 4096, 0xFFFFFFFF
 RK_EPCA_MAX_SAMPLES, RK_EPCA_MAX_COMPONENTS = 4096, 8
+RK_EDPL_MAX_KEEP = 16
 RK_OK, RK_ERR_INVALID, RK_ERR_NO_DEVICE, RK_ERR_HIP, RK_ERR_NOMEM, RK_ERR_UNSUPPORTED, RK_ERR_IO = 0, -1, -2, -3, -4, -5, -6
 
 
@@ -165,6 +166,11 @@ EXPORTS = {
     "rk_epca_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rk_epca_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rk_epca_finish_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rk_edpl_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_void_p]),
+    "rk_edpl_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_uint32]),
+    "rk_edpl_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p]),
+    "rk_tree_distance_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rk_edpl_lds_bytes": (C.c_uint64, [C.c_void_p]),
     "rk_count_work_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_set_lanes_per_read": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rk_kernel_name": (C.c_char_p, [C.c_void_p]),

@@ -525,6 +525,26 @@ inline std::string epca_table(const std::vector<std::string> &names, uint32_t n_
     return out + "#samples_without_mass\t" + std::to_string(S - n_active) + "\n";
 }
 
+// The text `--edpl FILE` writes: `#edpl<TAB>n_lines`, then `header<TAB>edpl` (`%.17g`) with the full header of every FASTA record
+// that has a placement, in file order, every occurrence.  header_of(r) gives (pointer, length) of record r's header, as
+// sample_members takes it; n_rows and edpl are per unique read.  The twin of hostio.edpl_table (byte-identical).
+template <class HeaderOf>
+inline std::string edpl_table(size_t n_records, HeaderOf header_of, const uint32_t *uniq_of_rec, const uint8_t *n_rows, const double *edpl) {
+    std::string body;
+    size_t n_lines = 0;
+    char buf[64];
+    for (size_t r = 0; r < n_records; r++) {
+        const uint32_t u = uniq_of_rec[r];
+        if (!n_rows[u]) continue;
+        const auto h = header_of(r);
+        body.append(h.first, h.second);
+        snprintf(buf, sizeof(buf), "\t%.17g\n", edpl[u]);
+        body += buf;
+        n_lines++;
+    }
+    return "#edpl\t" + std::to_string(n_lines) + "\n" + body;
+}
+
 // NumberFormat.getNumberInstance(Locale.UK), exactly 12 fraction digits, grouping commas (NewickWriter.java:61-64)
 inline std::string fmt12(float x) {
     char buf[400];

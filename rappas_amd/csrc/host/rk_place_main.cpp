@@ -50,6 +50,10 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                 (1..8, default 5) after N iterations (1..10000, default 200): a line #epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff\n"
                  "                 <TAB>iters, the lines #eigenvalue, #share, #residual (k values each, %.17g), #projections and a line per sample,\n"
                  "                 #loadings and a line per node id, and a last line #samples_without_mass<TAB>n)\n"
+                 "                [--edpl FILE]  (with --out: the EDPL of every placed read -- the expected distance between its placement locations,\n"
+                 "                 the sum over the pairs of its rows of LWR x LWR x the tree path between the midpoints of the two edges --, computed\n"
+                 "                 on the device: a line #edpl<TAB>n_lines, then header<TAB>edpl (%.17g) per FASTA record that has a placement, in\n"
+                 "                 input order; not with --masses-only)\n"
                  "                [--translate]  (amino-acid database, DNA reads: the six reading frames of every read are translated on the device\n"
                  "                 -- standard genetic code, longest stop-free run per frame -- and the best frame is reported; also writes\n"
                  "                 logs/frames_<query>.tsv, header<TAB>+1|+2|+3|-1|-2|-3; not with --strand rev | both)\n"
@@ -62,7 +66,7 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path, epca_path;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path, epca_path, edpl_path;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7, epca_k = 5, epca_iters = 200;
@@ -94,6 +98,7 @@ int main(int argc, char **argv) {
             else if (a == "--kr") kr_path = val();
             else if (a == "--squash") squash_path = val();
             else if (a == "--epca") epca_path = val();
+            else if (a == "--edpl") edpl_path = val();
             else if (a == "--epca-components") epca_k = (uint32_t)std::stoul(val());
             else if (a == "--epca-iters") epca_iters = (uint32_t)std::stoul(val());
             else if (a == "--sample-sep") { sample_sep = val(); if (sample_sep.size() != 1) throw std::runtime_error("--sample-sep takes one character"); }
@@ -327,6 +332,10 @@ int main(int argc, char **argv) {
             std::cerr << "rk_place: --masses-only writes no jplace (the placements never reach the host): it cannot be combined with --out\n";
             return 2;
         }
+        if (!edpl_path.empty() && out.empty()) {
+            std::cerr << "rk_place: --edpl reads the placements of a run that writes a jplace: it needs --out (and cannot be combined with --masses-only)\n";
+            return 2;
+        }
         if (!sample_sep.empty() && !masses_only && masses_path.empty()) {
             std::cerr << "rk_place: --sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only\n";
             return 2;
@@ -424,6 +433,23 @@ int main(int argc, char **argv) {
                 if (!ef) throw std::runtime_error("cannot write " + epca_path);
                 ef << rkh::epca_table(sm.names, B, k, epca_iters, info[0], info[1], ev.data(), share.data(), res.data(), proj.data(), load.data());
             }
+        };
+        // --edpl: the EDPL of every unique read from the results on the host, over the database's tree as --epca builds it, through
+        // rk_edpl_batch; a line per FASTA record that has a placement
+        auto write_edpl = [&](const rkh::Tree &t, uint64_t m, const rk_result *rs, size_t n_records, auto header_of, const uint32_t *uniq_of_rec) {
+            if (edpl_path.empty()) return;
+            const uint32_t B = (uint32_t)t.nodes.size();
+            std::vector<int32_t> parent(B);
+            std::vector<float> bl(B);
+            for (uint32_t x = 0; x < B; x++) { parent[x] = t.nodes[x].parent; bl[x] = t.nodes[x].bl; }
+            rk_tree *kt = nullptr;
+            if (rk_tree_create(device, B, parent.data(), bl.data(), &kt) != RK_OK) throw std::runtime_error(std::string("rk_tree_create: ") + rk_last_error());
+            struct TreeGuard { rk_tree *p; ~TreeGuard() { rk_tree_destroy(p); } } tree_guard{kt};
+            std::vector<double> edpl(m, 0.0);
+            if (rk_edpl_batch(kr_db, kt, keep_at_most, m, rs, edpl.data()) != RK_OK) throw std::runtime_error(std::string("rk_edpl_batch: ") + rk_last_error());
+            std::ofstream ef(edpl_path, std::ios::binary);
+            if (!ef) throw std::runtime_error("cannot write " + edpl_path);
+            ef << rkh::edpl_table(n_records, header_of, uniq_of_rec, rs->n_rows, edpl.data());
         };
         // --masses: the per-edge table of the whole run.  The results are on the host already, so the sums are rk_masses_accumulate_host's;
         // the weight of a unique read is the number of FASTA records it stands for, so the table speaks of reads
@@ -650,6 +676,7 @@ int main(int argc, char **argv) {
                 count_weights(weight);
                 write_masses(tree, n, &res, weight.data(), team.size(), sm);
             }
+            write_edpl(tree, n, &res, sc.recs.size(), [&](size_t r) { return std::make_pair((const char *)sc.recs[r].hdr, (size_t)sc.recs[r].hdr_len); }, dd.uniq_of_rec.data());
             const double t6 = now();
             std::cerr << n << " unique reads, " << ws.placed << " placed -> " << out << "\n";
             if (timing) {  // one JSON line (bench.py's fasta_to_jplace leg reads it): seconds per pass, FASTA bytes in -> jplace bytes out
@@ -733,6 +760,7 @@ int main(int argc, char **argv) {
             for (size_t i = 0; i < n; i++) weight[i] = (uint32_t)names[i].size();
             write_masses(tree, n, &res, weight.data(), 1, sm);
         }
+        write_edpl(tree, n, &res, records.size(), [&](size_t r) { return std::make_pair(records[r].header.data(), records[r].header.size()); }, dd.uniq_of_rec.data());
         std::cerr << n << " unique reads, " << pl.size() << " placed -> " << out << "\n";
         if (timing) std::cout << "{\"reads\": " << records.size() << ", \"unique\": " << n << ", \"db_s\": " << (t_db - t_start) << ", \"fasta_to_jplace_s\": " << (now() - tc0) << ", \"classic\": true}" << std::endl;
         return 0;

@@ -24,6 +24,7 @@
 #include "rk_masses.h"
 #include "rk_samples.h"
 #include "rk_epca.h"
+#include "rk_edpl.h"
 
 #include <type_traits>
 #ifndef RK_ROW_NT

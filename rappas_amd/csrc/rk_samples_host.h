@@ -1,6 +1,7 @@
 // rk_samples_host.h -- the host side of the sample-level calls: the checks and the one walk of a tree behind
 // rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel, kr_pairs_kernel, the squash kernels (rk_samples.h) and
-// the edge-PCA kernels (rk_epca.h) behind rk_clade_masses_host, rk_kr_distances_host, rk_squash_host and rk_epca_host.  Header-only,
+// the edge-PCA kernels (rk_epca.h) behind rk_clade_masses_host, rk_kr_distances_host, rk_squash_host and rk_epca_host, and the
+// distance tables of a tree with the twin of edpl_kernel (rk_edpl.h) behind rk_edpl_host and rk_tree_distance_host.  Header-only,
 // plain C++, like rk_masses_host.h.  Not part of the C ABI.
 //
 // The KR distance is written as include/rappas_place.h defines it, term by term and in the order fixed there, so that the device and
@@ -351,6 +352,105 @@ inline void epca_finish(uint32_t B, uint32_t S, uint32_t k, const double *raw, d
         for (uint64_t s = 0; s < S; s++) projection[s * k + j] = on ? q[j * (uint64_t)S + s] * ps : 0.0;
         for (uint64_t x = 0; x < B; x++) loading[x * k + j] = on ? w[j * (uint64_t)B + x] / ls : 0.0;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// EDPL: the distance between two branches and the pair sum of a read, as include/rappas_place.h defines them.  The
+// tables are built once here, for rk_tree_create (which uploads them as they are) and for the host twins alike.
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t EDPL_MAX_K = 16;
+
+// what a row of a read needs of its branch: pos, the root distance of the midpoint of the edge above it, and its pre-order interval
+struct EdplNode {
+    double pos;
+    uint32_t pre, end;
+};
+
+// node[B] by node id; lca: one block of 8-byte words that holds, by pre-order position p,
+//   dpar[B]  binary64: D of the parent of the node at p (the root: +0.0) -- the D[l] of a pair whose shallowest node between them sits at p
+//   depth[B] 16-bit
+//   table[levels][B] 16-bit: table[j][p] = a position of least depth among p .. p + 2^j - 1 (clamped to B - 1); table[0][p] = p
+// levels = floor(log2(B - 1)) + 1 for B >= 2, 0 for B == 1: a range of B - 1 positions is the longest a query has.
+struct TreeDist {
+    uint32_t B = 0, levels = 0;
+    std::vector<EdplNode> node;
+    std::vector<uint64_t> lca;
+    const double *dpar() const { return (const double *)lca.data(); }
+    const uint16_t *depth() const { return (const uint16_t *)(lca.data() + B); }
+    const uint16_t *table() const { return depth() + B; }
+};
+
+inline uint32_t edpl_levels(uint32_t B) {
+    uint32_t levels = 0;
+    while (B >= 2 && (1u << levels) <= B - 1) levels++;
+    return levels;
+}
+// 8-byte words of the block of B positions
+inline uint64_t edpl_lca_words(uint32_t B) { return (uint64_t)B + ((uint64_t)B * 2 * (1 + edpl_levels(B)) + 7) / 8; }
+
+// D[x] = D[parent[x]] + (double)branch_len[x] along the pre-order (a parent is met before its children), pos[x] = D[x] - h[x]
+inline void tree_dist_build(const TreeWalk &w, const int32_t *parent, const float *branch_len, TreeDist &t) {
+    const uint32_t B = (uint32_t)w.node_at.size(), levels = edpl_levels(B);
+    t.B = B;
+    t.levels = levels;
+    t.node.assign(B, EdplNode{0.0, 0, 0});
+    t.lca.assign(edpl_lca_words(B), 0);
+    double *dpar = (double *)t.lca.data();
+    uint16_t *depth = (uint16_t *)(t.lca.data() + B), *table = depth + B;
+    std::vector<double> D(B, 0.0);
+    for (uint32_t p = 0; p < B; p++) {
+        const uint32_t x = w.node_at[p];
+        if (p) {
+            const uint32_t up = (uint32_t)parent[x];
+            D[x] = D[up] + (double)branch_len[x];
+            dpar[p] = D[up];
+            depth[p] = (uint16_t)(depth[w.pre[up]] + 1);
+        }
+        t.node[x] = EdplNode{D[x] - kr_half_length(branch_len, x, w.root), p, p + w.size[x]};
+        table[p] = (uint16_t)p;
+    }
+    for (uint32_t j = 1; j < levels; j++) {
+        const uint16_t *below = table + (uint64_t)(j - 1) * B;
+        uint16_t *row = table + (uint64_t)j * B;
+        for (uint32_t p = 0; p < B; p++) {
+            const uint32_t q = p + (1u << (j - 1)) < B ? p + (1u << (j - 1)) : B - 1;
+            row[p] = depth[below[q]] < depth[below[p]] ? below[q] : below[p];
+        }
+    }
+}
+
+// d(a, b) of two nodes given by their EdplNode: the one met first in the pre-order either holds the other in its interval (it is the
+// ancestor) or the two meet at the parent of a shallowest node among the positions behind the first, up to the second.
+inline double tree_distance(const EdplNode &a, const EdplNode &b, uint32_t B, const double *dpar, const uint16_t *depth, const uint16_t *table) {
+    if (a.pre == b.pre) return 0.0;
+    const EdplNode &f = a.pre < b.pre ? a : b, &s = a.pre < b.pre ? b : a;
+    if (s.pre < f.end) return s.pos - f.pos;
+    const uint32_t len = s.pre - f.pre, j = 31u - (uint32_t)__builtin_clz(len);
+    const uint16_t *row = table + (uint64_t)j * B;
+    const uint32_t c1 = row[f.pre + 1], c2 = row[s.pre + 1 - (1u << j)];
+    const double dl = dpar[depth[c2] < depth[c1] ? c2 : c1];
+    return (a.pos - dl) + (b.pos - dl);
+}
+
+// edpl[r] of one read: its first n rows (n = min(n_rows, K)), the usable ones in row order
+inline double edpl_read(const TreeDist &t, uint32_t n, const uint16_t *branch, const double *lwr) {
+    const double *dpar = t.dpar();
+    const uint16_t *depth = t.depth(), *table = t.table();
+    double acc = 0.0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!(branch[i] < t.B && lwr[i] > 0.0)) continue;
+        for (uint32_t j = i + 1; j < n; j++) {
+            if (!(branch[j] < t.B && lwr[j] > 0.0)) continue;
+            const double ww = lwr[i] * lwr[j], d = tree_distance(t.node[branch[i]], t.node[branch[j]], t.B, dpar, depth, table);
+            const double term = ww * d;
+            acc = acc + term;
+        }
+    }
+    return 2.0 * acc;
+}
+
+inline void edpl_range(const TreeDist &t, uint32_t K, uint64_t r_lo, uint64_t r_hi, const uint8_t *n_rows, const uint16_t *branch, const double *lwr, double *edpl) {
+    for (uint64_t r = r_lo; r < r_hi; r++) edpl[r] = edpl_read(t, n_rows[r] < K ? n_rows[r] : K, branch + r * K, lwr + r * K);
 }
 
 }  // namespace rk

@@ -1,7 +1,8 @@
 // rk_samples_impl.h -- #included by rk_engine.hip: the sample-level entry points -- the tree handle (rk_tree_*),
 // the clade sums of sample mass buffers (rk_clade_masses_device / _host), the KR distance matrix (rk_kr_distances_device / _host /
 // _batch), the squash clustering over it (rk_squash_device / _host / _batch) and the edge principal components (rk_epca_device / _host /
-// _batch / _finish_host) -- over the kernels of rk_samples.h and rk_epca.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
+// _batch / _finish_host) and the per-read EDPL (rk_edpl_device / _host / _batch, rk_tree_distance_host)
+// -- over the kernels of rk_samples.h, rk_epca.h and rk_edpl.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
 // scratch, and only the _batch calls touch a database handle.
 #pragma once
 
@@ -18,6 +19,11 @@ struct rk_tree {
     void *d_block = nullptr;
     const u32 *node_at = nullptr, *end_at = nullptr, *span_node = nullptr, *span_end = nullptr, *span_off = nullptr;
     const double *h = nullptr;
+    // behind h, for the distance between two branches (rk_edpl_device): node[B] (16 bytes each), then the lca_words 8-byte words of
+    // dpar | depth | table as rk::tree_dist_build lays them out
+    const EdplEntry *node = nullptr;
+    const u64 *lca = nullptr;
+    uint32_t lca_words = 0, cu_count = 256;
 };
 
 extern "C" int rk_tree_validate(uint32_t n_branches, const int32_t *parent, const float *branch_len) {
@@ -61,6 +67,8 @@ extern "C" int rk_tree_create(int32_t device, uint32_t n_branches, const int32_t
         }
     std::vector<double> h(B);
     for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
+    rk::TreeDist dist;
+    rk::tree_dist_build(w, parent, branch_len, dist);
 
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0) return fail(RK_ERR_NO_DEVICE, "%s: no HIP device", who);
@@ -72,7 +80,10 @@ extern "C" int rk_tree_create(int32_t device, uint32_t n_branches, const int32_t
     t->B = B;
     t->root = w.root;
     const size_t n32 = 2 * (size_t)B + 2 * (size_t)n_span + n_chunks + 1, h_at = (n32 * 4 + 15) / 16 * 16;
-    HIP_TRY(hipMalloc(&t->d_block, h_at + (size_t)B * 8));
+    const size_t node_at = (h_at + (size_t)B * 8 + 15) / 16 * 16, lca_at = node_at + (size_t)B * sizeof(EdplEntry);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) t->cu_count = (uint32_t)cus;
+    HIP_TRY(hipMalloc(&t->d_block, lca_at + dist.lca.size() * 8));
     u32 *d32 = (u32 *)t->d_block;
     t->node_at = d32;
     t->end_at = d32 + B;
@@ -88,6 +99,11 @@ extern "C" int rk_tree_create(int32_t device, uint32_t n_branches, const int32_t
     }
     HIP_TRY(hipMemcpy((void *)t->span_off, span_off.data(), (size_t)(n_chunks + 1) * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy((void *)t->h, h.data(), (size_t)B * 8, hipMemcpyHostToDevice));
+    t->node = (const EdplEntry *)((char *)t->d_block + node_at);
+    t->lca = (const u64 *)((char *)t->d_block + lca_at);
+    t->lca_words = (uint32_t)dist.lca.size();
+    HIP_TRY(hipMemcpy((void *)t->node, dist.node.data(), (size_t)B * sizeof(EdplEntry), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((void *)t->lca, dist.lca.data(), dist.lca.size() * 8, hipMemcpyHostToDevice));
     *out = t.release();
     return RK_OK;
 }
@@ -667,5 +683,143 @@ extern "C" int rk_epca_finish_host(uint32_t n_branches, uint32_t n_samples, uint
     if (!raw) return fail(RK_ERR_INVALID, "%s: null raw output", who);
     if (!eigenvalue || !share || !residual || !projection || !loading) return fail(RK_ERR_INVALID, "%s: null output", who);
     rk::epca_finish(n_branches, n_samples, k, raw, eigenvalue, share, residual, projection, loading);
+    return RK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// EDPL: rk_edpl_lds_bytes / rk_edpl_device / _host / _batch and rk_tree_distance_host.
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(EdplEntry) == 16 && sizeof(rk::EdplNode) == 16 && offsetof(EdplEntry, pre) == 8 && offsetof(rk::EdplNode, pre) == 8 &&
+                  offsetof(EdplEntry, end) == 12 && offsetof(rk::EdplNode, end) == 12,
+              "one entry layout for the host's builder and the kernel");
+static_assert(RK_EDPL_MAX_KEEP == rk::EDPL_MAX_K, "one limit for the header and the host twin");
+// The tables of a tree go into the LDS of every block while they take at most this many bytes: behind them the 160 KB of a CU still
+// hold the stages of four waves at K = 16 (87 040 bytes) and of ten at K = 7 (8 960 bytes each).
+constexpr uint64_t RK_EDPL_LDS_MAX_BYTES = 65536;
+constexpr uint64_t RK_EDPL_CU_LDS_BYTES = 160 * 1024;
+constexpr uint32_t RK_EDPL_GLOBAL_WAVES = 4;          // without the tables: blocks of four waves, as many a CU as their stages allow
+constexpr uint32_t RK_EDPL_GLOBAL_BLOCKS_PER_CU = 8;
+constexpr uint64_t RK_EDPL_CHUNK_READS = 1ull << 22;  // rk_edpl_batch: reads a chunk (at K = 7, 75 MB up and 32 MB down)
+
+// the rule that picks the form: the byte size of the tables against the limit (developer builds move the limit)
+static bool edpl_tables_in_lds(const rk_tree *t) {
+    uint64_t limit = RK_EDPL_LDS_MAX_BYTES;
+    if (const char *v = rk_knob("RK_EDPL_LDS_BYTES")) limit = strtoull(v, nullptr, 10);  // developer builds: both forms on one small tree
+    limit = std::min<uint64_t>(limit, RK_EDPL_CU_LDS_BYTES - RK_EDPL_GLOBAL_WAVES * edpl_stage_bytes(RK_EDPL_MAX_KEEP));  // (four waves' stages fit at any K)
+    return (uint64_t)t->lca_words * 8 <= limit;
+}
+
+extern "C" uint64_t rk_edpl_lds_bytes(const rk_tree *t) {
+    if (!t) {
+        (void)fail(RK_ERR_INVALID, "rk_edpl_lds_bytes: null tree");
+        return 0;
+    }
+    return edpl_tables_in_lds(t) ? (uint64_t)t->lca_words * 8 : 0;
+}
+
+// the tests of the three calls that read a result set, with the rules of masses_args
+static int edpl_args(const char *who, uint32_t K, uint64_t n_reads, const rk_result *res, const double *edpl) {
+    if (K < 1 || K > RK_EDPL_MAX_KEEP) return fail(RK_ERR_INVALID, "%s: keep_at_most=%u outside 1..16", who, K);
+    if (n_reads >= (1ull << 32)) return fail(RK_ERR_INVALID, "%s: n_reads=%llu, at most 2^32 - 1 per call", who, (unsigned long long)n_reads);
+    if (n_reads == 0) return RK_OK;
+    if (!res || !res->n_rows || !res->branch || !res->lwr) return fail(RK_ERR_INVALID, "%s: null result array (n_rows, branch and lwr are read)", who);
+    if (!edpl) return fail(RK_ERR_INVALID, "%s: null output", who);
+    return RK_OK;
+}
+
+extern "C" int rk_edpl_device(const rk_tree *t, uint32_t keep_at_most, uint64_t n_reads, const rk_result *d_res, double *d_edpl, void *stream) {
+    const char *who = "rk_edpl_device";
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    int rc = edpl_args(who, keep_at_most, n_reads, d_res, d_edpl);
+    if (rc || n_reads == 0) return rc;
+    HIP_TRY(hipSetDevice(t->device));
+    // with the tables: one block a CU, of the waves whose stages fit behind them (at least four: the limit leaves room for them at
+    // any K); without: blocks of four waves, a grid of as many a CU as their stages allow
+    const bool lds = edpl_tables_in_lds(t);
+    const uint64_t stage = edpl_stage_bytes(keep_at_most), tables = lds ? (uint64_t)t->lca_words * 8 : 0;
+    const uint32_t waves = lds ? (uint32_t)std::min<uint64_t>((RK_EDPL_CU_LDS_BYTES - tables) / stage, EDPL_MAX_WAVES) : RK_EDPL_GLOBAL_WAVES;
+    const uint64_t tiles = (n_reads + 64 * waves - 1) / (64 * waves);
+    const uint64_t per_cu = lds ? 1 : std::max<uint64_t>(1, std::min<uint64_t>(RK_EDPL_CU_LDS_BYTES / (waves * stage), RK_EDPL_GLOBAL_BLOCKS_PER_CU));
+    const unsigned blocks = (unsigned)std::min<uint64_t>(tiles, (uint64_t)t->cu_count * per_cu);
+    const size_t lds_bytes = (size_t)(tables + waves * stage);
+    auto launch = [&](auto kernel) -> int {
+        HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * waves), lds_bytes, (hipStream_t)stream, (u64)n_reads, keep_at_most, t->B, t->lca_words,
+                           (const unsigned char *)d_res->n_rows, (const unsigned short *)d_res->branch, (const double *)d_res->lwr, t->node, t->lca, d_edpl);
+        HIP_TRY(hipGetLastError());
+        return RK_OK;
+    };
+    return lds ? launch(edpl_kernel<true>) : launch(edpl_kernel<false>);
+}
+
+extern "C" int rk_edpl_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res,
+                            double *edpl, uint32_t n_threads) {
+    const char *who = "rk_edpl_host";
+    RK_GUARD_BEGIN
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    int rc = edpl_args(who, keep_at_most, n_reads, res, edpl);
+    if (rc || n_reads == 0) return rc;
+    rk::TreeDist dist;
+    rk::tree_dist_build(w, parent, branch_len, dist);
+    unsigned hw = std::thread::hardware_concurrency();
+    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
+    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, (n_reads + 4095) / 4096}));
+    return masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        rk::edpl_range(dist, keep_at_most, n_reads * th / T, n_reads * (th + 1) / T, res->n_rows, res->branch, res->lwr, edpl);
+    });
+    RK_GUARD_END(who)
+}
+
+extern "C" int rk_tree_distance_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_pairs, const uint16_t *a, const uint16_t *b,
+                                     double *d) {
+    const char *who = "rk_tree_distance_host";
+    RK_GUARD_BEGIN
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (n_pairs == 0) return RK_OK;
+    if (!a || !b) return fail(RK_ERR_INVALID, "%s: null branch array", who);
+    if (!d) return fail(RK_ERR_INVALID, "%s: null output", who);
+    for (uint32_t i = 0; i < n_pairs; i++)
+        if (a[i] >= n_branches || b[i] >= n_branches) return fail(RK_ERR_INVALID, "%s: pair %u is (%u, %u), the tree has %u branches", who, i, a[i], b[i], n_branches);
+    rk::TreeDist dist;
+    rk::tree_dist_build(w, parent, branch_len, dist);
+    for (uint32_t i = 0; i < n_pairs; i++) d[i] = rk::tree_distance(dist.node[a[i]], dist.node[b[i]], dist.B, dist.dpar(), dist.depth(), dist.table());
+    return RK_OK;
+    RK_GUARD_END(who)
+}
+
+// The drivers' call: a result set on the host in, one double a read on the host out, in chunks through rk_edpl_device on db's device.
+// Only n_rows, branch and lwr are uploaded; the buffers are allocated for the call and freed; it waits for the result.
+extern "C" int rk_edpl_batch(rk_db *db, const rk_tree *t, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, double *edpl) {
+    const char *who = "rk_edpl_batch";
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    int rc = edpl_args(who, keep_at_most, n_reads, res, edpl);
+    if (rc) return rc;
+    if (t->B != db->info.n_branches || t->device != db->info.device)
+        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
+    if (n_reads == 0) return RK_OK;
+    std::lock_guard<std::mutex> lock(db->host_mutex);
+    HIP_TRY(hipSetDevice(db->info.device));
+    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
+    hipStream_t s = db->ws[0].stream;
+    const uint64_t K = keep_at_most, chunk = std::min<uint64_t>(n_reads, RK_EDPL_CHUNK_READS);
+    GrowBuf d_in, d_out;
+    struct Free { GrowBuf &a, &b; ~Free() { a.release(); b.release(); } } free_all{d_in, d_out};
+    const uint64_t branch_at = up256(chunk), lwr_at = branch_at + up256(chunk * K * 2);  // n_rows | branch | lwr
+    if (int e = d_in.reserve(lwr_at + chunk * K * 8)) return e;
+    if (int e = d_out.reserve(chunk * 8)) return e;
+    char *base = (char *)d_in.p;
+    const rk_result d_res{(uint8_t *)base, (uint16_t *)(base + branch_at), nullptr, (double *)(base + lwr_at), nullptr};
+    for (uint64_t r0 = 0; r0 < n_reads; r0 += chunk) {  // (one stream: a chunk's uploads wait for the kernel of the chunk before)
+        const uint64_t n = std::min(chunk, n_reads - r0);
+        HIP_TRY(hipMemcpyAsync(d_res.n_rows, res->n_rows + r0, n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_res.branch, res->branch + r0 * K, n * K * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_res.lwr, res->lwr + r0 * K, n * K * 8, hipMemcpyHostToDevice, s));
+        if (int e = rk_edpl_device(t, keep_at_most, n, &d_res, d_out.as<double>(), s)) return e;
+        HIP_TRY(hipMemcpyAsync(edpl + r0, d_out.p, n * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
     return RK_OK;
 }

@@ -429,6 +429,19 @@ def epca_table(names, n_branches, k, iters, n_active, k_eff, eigenvalue, share, 
     return "".join(out)
 
 
+def edpl_table(records, unique, n_rows, edpl):
+    """the text `--edpl FILE` writes: a line `#edpl<TAB>n_lines`, then `header<TAB>edpl` (`%.17g`) with the FULL header of every FASTA
+    record that has a placement, in file order, every occurrence (a duplicate follows its representative, the frames log's rules).
+    n_rows[i], edpl[i]: the rows and the EDPL of unique read i.  The twin of rkh::edpl_table, byte-identical."""
+    index = {hashlib.md5(seq.replace("-", "").encode()).digest(): i for i, (_, seq) in enumerate(unique)}
+    lines = []
+    for header, seq in records:
+        u = index[hashlib.md5(seq.replace("-", "").encode()).digest()]
+        if n_rows[u]:
+            lines.append("%s\t%.17g\n" % (header, float(edpl[u])))
+    return f"#edpl\t{len(lines)}\n" + "".join(lines)
+
+
 def _squash_leaf(name):
     """a sample name as a Newick leaf: single-quoted, a quote doubled, when it holds any of ()[]':;, or white space"""
     if any(c in "()[]':;, \t\n\r\v\f" for c in name):

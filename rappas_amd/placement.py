@@ -848,6 +848,42 @@ def epca_finish(n_branches, n_samples, k, raw, info=None):
     return EdgePCA(ev, share, res, proj, load, n_active, k_eff)
 
 
+def _edpl_rows(n_rows, branch, lwr, K):
+    """the three arrays of a host result set that the EDPL reads, as the C ABI takes them: u8 [n], u16 [n * K], f64 [n * K]"""
+    n_rows = np.ascontiguousarray(n_rows, dtype=np.uint8).reshape(-1)
+    branch = np.ascontiguousarray(branch, dtype=np.uint16).reshape(-1)
+    lwr = np.ascontiguousarray(lwr, dtype=np.float64).reshape(-1)
+    n = n_rows.shape[0]
+    if branch.shape[0] != n * K or lwr.shape[0] != n * K:
+        raise ValueError(f"branch and lwr must hold n_reads x K = {n} x {K} rows")
+    return n_rows, branch, lwr, n
+
+
+def edpl_host(parent, branch_len, keep_at_most, n_rows, branch, lwr, threads=0):
+    """rk_edpl_host (no GPU): float64 [n_reads], the expected distance between the placement locations of every read of a result set
+    (n_rows u8 [n], branch u16 [n, K], lwr f64 [n, K]) on the tree (parent, branch_len): 2 * the sum over the pairs of its usable rows of
+    lwr_i * lwr_j * the path between the midpoints of the two edges -- the bits EdgeTree.edpl gives on the device."""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    n_rows, branch, lwr, n = _edpl_rows(n_rows, branch, lwr, keep_at_most)
+    out = np.zeros(n, np.float64)
+    res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
+    _lib.check(_lib.load().rk_edpl_host(parent.shape[0], _ptr(parent), _ptr(branch_len), keep_at_most, n, C.byref(res), _ptr(out), threads))
+    return out
+
+
+def tree_distance_host(parent, branch_len, a, b):
+    """rk_tree_distance_host (no GPU): float64 [n], the path between the midpoints of the edges above a[i] and b[i] on the tree (parent,
+    branch_len), the d(a, b) of the EDPL; the midpoint of the root's edge is the root"""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    a = np.ascontiguousarray(a, dtype=np.uint16).reshape(-1)
+    b = np.ascontiguousarray(b, dtype=np.uint16).reshape(-1)
+    if a.shape != b.shape:
+        raise ValueError("a and b must hold one branch each per pair")
+    d = np.zeros(a.shape[0], np.float64)
+    _lib.check(_lib.load().rk_tree_distance_host(parent.shape[0], _ptr(parent), _ptr(branch_len), a.shape[0], _ptr(a), _ptr(b), _ptr(d)))
+    return d
+
+
 class EdgeTree:
     """rk_tree: the shape of a reference tree on the device -- parent[x] the node id of x's parent (-1 for the root), branch_len[x] the
     length of the edge above x -- for the sample-level calls over device mass buffers.  Takes and returns torch device tensors and owns
@@ -979,6 +1015,35 @@ class EdgeTree:
         info = np.zeros(2, np.uint32)
         _lib.check(self._lib.rk_epca_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), k, iters, _ptr(raw), _ptr(info)))
         return raw, info
+
+    def edpl_lds_bytes(self):
+        """rk_edpl_lds_bytes: the bytes of the distance tables when edpl copies them into the LDS of every block, 0 when it reads them
+        from global memory"""
+        return int(self._lib.rk_edpl_lds_bytes(self.handle))
+
+    def edpl(self, out, keep_at_most, stream=None):
+        """rk_edpl_device: float64 tensor [n_reads], written -- the EDPL of every read of a device result set (`out`: the dict of device
+        tensors a placement call returns; n_rows, branch [n, keep_at_most] and lwr [n, keep_at_most] are read); asynchronous on the stream"""
+        import torch
+        n_rows, branch, lwr = out["n_rows"], out["branch"], out["lwr"]
+        n, K = n_rows.numel(), keep_at_most
+        for t, dt, size, what in ((n_rows, torch.uint8, n, "n_rows"), (branch, torch.int16, n * K, "branch"), (lwr, torch.float64, n * K, "lwr")):
+            if t.dtype != dt or t.numel() != size or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"{what} must be a contiguous {dt} tensor of {size} elements on cuda:{self.device}")
+        dev = n_rows.device
+        edpl = torch.empty((n,), dtype=torch.float64, device=dev)
+        res = rk_result(n_rows.data_ptr(), branch.data_ptr(), None, lwr.data_ptr(), None)
+        _lib.check(self._lib.rk_edpl_device(self.handle, K, n, C.byref(res), edpl.data_ptr(), C.c_void_p(_stream(dev, stream))))
+        return edpl
+
+    def edpl_batch(self, db, keep_at_most, n_rows, branch, lwr):
+        """rk_edpl_batch, the drivers' call: float64 array [n_reads] on the host, as edpl_host gives it, from a host result set, in chunks
+        through rk_edpl_device on db's device; returns when the values are there"""
+        n_rows, branch, lwr, n = _edpl_rows(n_rows, branch, lwr, keep_at_most)
+        edpl = np.zeros(n, np.float64)
+        res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
+        _lib.check(self._lib.rk_edpl_batch(db.handle, self.handle, keep_at_most, n, C.byref(res), _ptr(edpl)))
+        return edpl
 
     def close(self):
         if self._h:

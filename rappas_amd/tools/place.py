@@ -21,6 +21,7 @@ KR_NEEDS_SAMPLE_SEP = "--kr compares the samples of one run: it needs --sample-s
 SQUASH_NEEDS_SAMPLE_SEP = "--squash clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 EPCA_NEEDS_SAMPLE_SEP = "--epca finds the principal components of the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 EPCA_RANGES = "--epca-components must be in 1..8, --epca-iters in 1..10000"
+EDPL_NEEDS_OUT = "--edpl reads the placements of a run that writes a jplace: it needs --out (and cannot be combined with --masses-only)"
 SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
 
@@ -78,9 +79,21 @@ def epca_text(db, tree, sample_names, words, host_words, k, iters, device=0):
         et.close()
 
 
+def edpl_text(db, tree, records, unique, res, keep_at_most, device=0):
+    """`--edpl FILE`: the table (hostio.edpl_table) of the EDPL of every placed read of a result set on the host, over the database's
+    tree as epca_text builds it, through rk_edpl_batch on db's device"""
+    from ..placement import EdgeTree
+    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
+    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
+    try:
+        return hostio.edpl_table(records, unique, res.n_rows, et.edpl_batch(db, keep_at_most, res.n_rows, res.branch, res.lwr))
+    finally:
+        et.close()
+
+
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
                call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None, kr=False,
-               squash=False, epca=False, epca_components=5, epca_iters=200):
+               squash=False, epca=False, epca_components=5, epca_iters=200, edpl=False):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
@@ -89,7 +102,8 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for);
     with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table); with kr as well res.kr is
     the text `--kr FILE` writes (kr_text), with squash res.squash the text `--squash FILE` writes (squash_text), with epca res.epca the text
-    `--epca FILE` writes (epca_text) for epca_components components after epca_iters iterations."""
+    `--epca FILE` writes (epca_text) for epca_components components after epca_iters iterations.  edpl: res.edpl is the text `--edpl FILE`
+    writes (edpl_text), with any strand and with translate."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
     if epca and not (masses and sample_sep is not None):
@@ -116,6 +130,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
                 seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
                 treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
         res.kr = res.squash = res.epca = None
+        res.edpl = edpl_text(db, tree, records, unique, res, keep_at_most, device) if edpl else None
         if members is not None:
             from ..placement import accumulate_masses_samples_host
             sample_names, m_off, m_sample, m_weight = members
@@ -265,6 +280,11 @@ def main(argv=None):
                          "line per node id, and a last line #samples_without_mass<TAB>n")
     ap.add_argument("--epca-components", type=int, default=5, metavar="K", help="--epca: the number of components, 1..8 (default 5)")
     ap.add_argument("--epca-iters", type=int, default=200, metavar="N", help="--epca: the fixed number of iterations, 1..10000 (default 200)")
+    ap.add_argument("--edpl", default=None, metavar="FILE",
+                    help="with --out: the EDPL of every placed read (the expected distance between its placement locations: the sum over the "
+                         "pairs of its rows of LWR x LWR x the tree path between the midpoints of the two edges), computed on the device: a "
+                         "line #edpl<TAB>n_lines, then header<TAB>edpl (%%.17g) per FASTA record that has a placement, in input order; "
+                         "not with --masses-only")
     ap.add_argument("--timing", action="store_true", help="--masses-only: one JSON line with the run's wall-clock times on stdout")
     ap.add_argument("--guppy-compat", action="store_true")
     ap.add_argument("--device", type=int, default=0)
@@ -288,6 +308,8 @@ def main(argv=None):
         ap.error(EPCA_NEEDS_SAMPLE_SEP)
     if a.epca is not None and not (1 <= a.epca_components <= 8 and 1 <= a.epca_iters <= 10000):
         ap.error(EPCA_RANGES)
+    if a.edpl is not None and a.out is None:
+        ap.error(EDPL_NEEDS_OUT)
     if a.masses_only is None and a.out is None:
         ap.error("--out is required (or --masses-only FILE for a profile-only run)")
     db_text = None
@@ -303,7 +325,8 @@ def main(argv=None):
         doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
                               translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep, kr=a.kr is not None,
-                              squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters)
+                              squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters,
+                              edpl=a.edpl is not None)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -333,6 +356,9 @@ def main(argv=None):
     if res.epca is not None:
         with open(a.epca, "w") as f:
             f.write(res.epca)
+    if res.edpl is not None:
+        with open(a.edpl, "w") as f:
+            f.write(res.edpl)
     placed = int(np.count_nonzero(res.n_rows))
     print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
     return 0
