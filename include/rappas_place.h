@@ -585,6 +585,67 @@ int rk_squash_host(uint32_t n_branches, const int32_t *parent, const float *bran
 int rk_squash_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, rk_squash_merge *merges, uint32_t *n_merges);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Phylogenetic k-means of the samples of a sample mass buffer (what `gappa analyze phylogenetic-kmeans` computes from jplace
+ * files): k clusters whose centroids are mass distributions, the averages of their members, with the KR distance between a sample
+ * and a centroid.  The method for many samples and a handful of clusters: S * k * B terms a round and no S x S object.  The
+ * reference has no counterpart.  Fixed so that every implementation gives the same bits; u_s, v_s, h, T_s, the KR pair sum,
+ * RK_KR_CHUNK and the order of the sum are exactly those of the KR block, all binary64 without contraction.
+ *   Limits              1 <= S <= 65535, 1 <= k <= RK_KMEANS_MAX_K, 1 <= max_rounds <= RK_KMEANS_MAX_ROUNDS.
+ *   Active samples      sample s is active iff T_s != 0; an inactive sample never takes part.  n_active = their number.  Without
+ *                       caller seeds k_eff = min(k, n_active); with them k_eff = k.
+ *   Seeds               farthest-first when the caller gives none: seed_0 = the smallest active s; for j = 1 .. k_eff - 1, mind[s] =
+ *                       the minimum over i < j of the KR pair sum between seed_i's profile and sample s, and seed_j = the active s
+ *                       that is not yet a seed with the largest mind[s] under plain >, ties to the smaller s.
+ *   Caller's seeds      `seeds`: a host array of k sample indices, read during the call.  An index >= S or a repeated index is
+ *                       RK_ERR_INVALID on the host and nothing is launched.  Whether a seed has mass is known on the device only:
+ *                       an inactive seed gives status = 1 and every output is written as its filler.
+ *   Start               cluster j's centroid profile cu_j = u_{seed_j}, cv_j = v_{seed_j}; the previous assignment of every sample is
+ *                       RK_KMEANS_NONE.
+ *   Round               1 Distances: for every j < k_eff and active s, Dc[j][s] = the KR pair sum with cu_j, cv_j in the place of the
+ *                       first operand's u, v: the same terms, chunk rule and order.  2 Assignment: assign[s] = the j with the
+ *                       smallest Dc[j][s] under plain <, ties to the smaller j; changed = the number of active s whose assignment
+ *                       differs from the previous one.  3 changed == 0: the run has converged and ends.  Otherwise every cluster
+ *                       gets a new centroid and the next round starts.
+ *   Update              a cluster with n_j >= 1 members: cu_j(x) = sum / (double)n_j, cv_j(x) likewise from v.  sum adds u_s(x) over
+ *                       the members in ascending s with one partial per RK_KMEANS_GROUP sample indices (group = s / 256): a partial
+ *                       starts at +0.0 and adds member after member; the partials of the groups that hold a member are added in
+ *                       group order, the first one as it is.  A cluster that lost every member keeps its profile.
+ *   End                 after the round that found no change, or after max_rounds rounds (the last of those still updates).
+ *                       info = {k_eff, n_active, rounds run (the one that found no change included), converged | status << 1}.
+ *   Outputs             all written, none added into.  assign [S] uint32_t: RK_KMEANS_NONE for an inactive sample.  dist [S]:
+ *                       Dc[assign[s]][s] of the last distance step, +0.0 for an inactive sample.  sizes [k]: the member counts.
+ *                       within [k]: the dist of the members added in ascending s from +0.0.  centroids [k][2][B], optional: cu_j then
+ *                       cv_j as they stand at the end.  Rows j >= k_eff of sizes, within and centroids are 0 / +0.0.
+ *   Fillers             n_active == 0 or status != 0: every assign is RK_KMEANS_NONE, every other output 0 / +0.0, info reports 0
+ *                       rounds and converged = 1.
+ *   rk_kmeans_work_bytes  bytes of the caller-owned device workspace: the clade sums, the profiles, the centroid profiles, the
+ *                         chunk partials [chunks][k][S], the nearest centroid of every sample, the seeding's minima, the active
+ *                         flags and the control words; 0 and a message on a bad argument.
+ *   rk_kmeans_device      plain launches in stream order: no host synchronisation, no grid-wide wait, no cross-block atomics.
+ *                         Whether the run has converged is a word of the workspace: the kernels of the rounds behind it return at
+ *                         once.  Every workspace word is written before it is read.  d_centroids may be NULL.  Otherwise the
+ *                         argument rules of rk_squash_device: RK_ERR_INVALID and a message, nothing launched, nothing written.
+ *                         Asynchronous on `stream`.
+ *   rk_kmeans_host        the same bits in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16.
+ *   rk_kmeans_batch       the drivers' call, with the contract of rk_squash_batch: masses NULL = the buffer the last per-sample
+ *                         profile-only call left in the handle.  The outputs on the host; returns when they are filled.
+ * Added without a bump of RK_VERSION (no existing struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_KMEANS_MAX_K 64u
+#define RK_KMEANS_MAX_ROUNDS 1024u
+#define RK_KMEANS_GROUP 256u
+#define RK_KMEANS_NONE 0xFFFFFFFFu
+uint64_t rk_kmeans_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t k);
+int rk_kmeans_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t k, uint32_t max_rounds, const uint32_t *seeds /* host, may be NULL */,
+                     uint32_t *d_assign, double *d_dist, uint32_t *d_sizes, double *d_within, uint32_t *d_info /*[4]*/, double *d_centroids /* may be NULL */,
+                     void *d_work, uint64_t work_bytes, void *stream);
+int rk_kmeans_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t k,
+                   uint32_t max_rounds, const uint32_t *seeds, uint32_t *assign, double *dist, uint32_t *sizes, double *within, uint32_t *info,
+                   double *centroids, uint32_t n_threads);
+int rk_kmeans_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t k, uint32_t max_rounds, const uint32_t *seeds,
+                    uint32_t *assign, double *dist, uint32_t *sizes, double *within, uint32_t *info, double *centroids);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Edge principal components of the samples of a sample mass buffer (Matsen & Evans; what `guppy epca` / `gappa edgepca` compute
  * from jplace files): for every edge the difference between the mass on its two sides, per sample, and the principal components of
  * that S x B matrix -- the projections of the samples and the loadings of the edges.  The reference has no counterpart.  Fixed so

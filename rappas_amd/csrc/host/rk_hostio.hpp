@@ -497,6 +497,31 @@ inline std::string squash_table(const std::vector<std::string> &names, const Squ
     return out + "#samples_without_mass\t" + std::to_string(S - n_with) + "\n";
 }
 
+// The text `--kmeans FILE` writes: `#kmeans<TAB>S<TAB>k<TAB>k_eff<TAB>n_active<TAB>rounds<TAB>converged`; `#clusters` and a line
+// `j<TAB>size<TAB>within` (`%.17g`) per cluster j < k; `#samples` and a line `name<TAB>cluster<TAB>distance` per sample in sample
+// order, a sample without mass (assign = 0xFFFFFFFF) with the cluster `-` and the distance `0`; `#samples_without_mass<TAB>n`.  The
+// arrays are what rk_kmeans_batch leaves; info = {k_eff, n_active, rounds, converged | status << 1}.  The twin of hostio.kmeans_table
+// (byte-identical).
+inline std::string kmeans_table(const std::vector<std::string> &names, uint32_t k, const uint32_t *assign, const double *dist, const uint32_t *sizes,
+                                const double *within, const uint32_t *info) {
+    const size_t S = names.size();
+    std::string out = "#kmeans\t" + std::to_string(S) + "\t" + std::to_string(k) + "\t" + std::to_string(info[0]) + "\t" + std::to_string(info[1]) + "\t" +
+                      std::to_string(info[2]) + "\t" + std::to_string(info[3] & 1u) + "\n#clusters\n";
+    char buf[96];
+    for (uint32_t j = 0; j < k; j++) {
+        snprintf(buf, sizeof(buf), "%u\t%u\t%.17g\n", j, sizes[j], within[j]);
+        out += buf;
+    }
+    out += "#samples\n";
+    for (size_t s = 0; s < S; s++) {
+        out += names[s];
+        if (assign[s] == 0xFFFFFFFFu) { out += "\t-\t0\n"; continue; }
+        snprintf(buf, sizeof(buf), "\t%u\t%.17g\n", assign[s], dist[s]);
+        out += buf;
+    }
+    return out + "#samples_without_mass\t" + std::to_string(S - info[1]) + "\n";
+}
+
 // The text `--epca FILE` writes, every double as `%.17g`: `#epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff<TAB>iters`; the lines
 // `#eigenvalue`, `#share`, `#residual` with k values each; `#projections` and a line per sample (its name and k values); `#loadings`
 // and a line per node id (the id and k values); `#samples_without_mass<TAB>n`.  The arrays are what rk_epca_finish_host leaves:

@@ -45,6 +45,11 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                [--squash FILE]  (with --sample-sep: the squash clustering of the samples over those distances, merged on the\n"
                  "                 device: a line #squash<TAB>S<TAB>n_merges, a line k<TAB>a<TAB>b<TAB>distance<TAB>size per merge, the tree as\n"
                  "                 #newick<TAB>...; (an inner node at half its distance), #inversions<TAB>n and #samples_without_mass<TAB>n)\n"
+                 "                [--kmeans FILE --kmeans-k K [--kmeans-rounds N]]  (with --sample-sep: the phylogenetic k-means of the samples -- K\n"
+                 "                 clusters (1..64) whose centroids are the averages of their members' mass, KR distances, farthest-first seeds, at\n"
+                 "                 most N rounds (1..1024, default 100) --, found on the device: a line #kmeans<TAB>S<TAB>k<TAB>k_eff<TAB>n_active\n"
+                 "                 <TAB>rounds<TAB>converged, #clusters and a line j<TAB>size<TAB>within per cluster, #samples and a line\n"
+                 "                 name<TAB>cluster<TAB>distance per sample (- and 0 without mass), and a last line #samples_without_mass<TAB>n)\n"
                  "                [--epca FILE [--epca-components K] [--epca-iters N]]  (with --sample-sep: the edge principal components of the samples --\n"
                  "                 the difference between the mass on the two sides of every edge, centred --, found on the device: K components\n"
                  "                 (1..8, default 5) after N iterations (1..10000, default 200): a line #epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff\n"
@@ -66,10 +71,10 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path, epca_path, edpl_path;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path, epca_path, edpl_path, kmeans_path;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
-        uint32_t keep_at_most = 7, epca_k = 5, epca_iters = 200;
+        uint32_t keep_at_most = 7, epca_k = 5, epca_iters = 200, kmeans_k = 0, kmeans_rounds = 100;
         float keep_factor = 0.01f, nsbound = -INFINITY;
         bool guppy = false;
         int device = 0;
@@ -99,6 +104,9 @@ int main(int argc, char **argv) {
             else if (a == "--squash") squash_path = val();
             else if (a == "--epca") epca_path = val();
             else if (a == "--edpl") edpl_path = val();
+            else if (a == "--kmeans") kmeans_path = val();
+            else if (a == "--kmeans-k") kmeans_k = (uint32_t)std::stoul(val());
+            else if (a == "--kmeans-rounds") kmeans_rounds = (uint32_t)std::stoul(val());
             else if (a == "--epca-components") epca_k = (uint32_t)std::stoul(val());
             else if (a == "--epca-iters") epca_iters = (uint32_t)std::stoul(val());
             else if (a == "--sample-sep") { sample_sep = val(); if (sample_sep.size() != 1) throw std::runtime_error("--sample-sep takes one character"); }
@@ -356,6 +364,14 @@ int main(int argc, char **argv) {
             std::cerr << "rk_place: --epca-components must be in 1..8, --epca-iters in 1..10000\n";
             return 2;
         }
+        if (!kmeans_path.empty() && sample_sep.empty()) {
+            std::cerr << "rk_place: --kmeans clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)\n";
+            return 2;
+        }
+        if (!kmeans_path.empty() && (kmeans_k < 1 || kmeans_k > RK_KMEANS_MAX_K || kmeans_rounds < 1 || kmeans_rounds > RK_KMEANS_MAX_ROUNDS)) {
+            std::cerr << "rk_place: --kmeans needs --kmeans-k in 1..64; --kmeans-rounds must be in 1..1024\n";
+            return 2;
+        }
         const bool only_convert = !save_image.empty() && fasta.empty() && out.empty() && !masses_only;
         if (n_sources != 1 || (!only_convert && (fasta.empty() || (out.empty() && !masses_only))) || (only_convert && !dbimage.empty())) return usage();
         uint32_t amb_mode;
@@ -384,8 +400,9 @@ int main(int argc, char **argv) {
         rk_db *kr_db = nullptr;  // (the handle, once it is open)
         // --squash: the same, through rk_squash_batch; `host_words` is the host's copy either way (it tells which samples hold mass)
         // --epca: the same, through rk_epca_batch and rk_epca_finish_host (one sample alone has no components: it is only counted)
+        // --kmeans: the same, through rk_kmeans_batch
         auto write_kr = [&](const rkh::Tree &t, const rkh::SampleMembers &sm, const uint64_t *words, const uint64_t *host_words) {
-            if (kr_path.empty() && squash_path.empty() && epca_path.empty()) return;
+            if (kr_path.empty() && squash_path.empty() && epca_path.empty() && kmeans_path.empty()) return;
             const uint32_t B = (uint32_t)t.nodes.size(), S = (uint32_t)sm.names.size();
             std::vector<int32_t> parent(B);
             std::vector<float> bl(B);
@@ -432,6 +449,17 @@ int main(int argc, char **argv) {
                 std::ofstream ef(epca_path, std::ios::binary);
                 if (!ef) throw std::runtime_error("cannot write " + epca_path);
                 ef << rkh::epca_table(sm.names, B, k, epca_iters, info[0], info[1], ev.data(), share.data(), res.data(), proj.data(), load.data());
+            }
+            if (!kmeans_path.empty()) {
+                const uint32_t k = kmeans_k;
+                std::vector<uint32_t> assign(S), sizes(k);
+                std::vector<double> dist(S), within(k);
+                uint32_t info[4] = {0, 0, 0, 0};
+                if (rk_kmeans_batch(kr_db, kt, S, words, k, kmeans_rounds, nullptr, assign.data(), dist.data(), sizes.data(), within.data(), info, nullptr) != RK_OK)
+                    throw std::runtime_error(std::string("rk_kmeans_batch: ") + rk_last_error());
+                std::ofstream mf(kmeans_path, std::ios::binary);
+                if (!mf) throw std::runtime_error("cannot write " + kmeans_path);
+                mf << rkh::kmeans_table(sm.names, k, assign.data(), dist.data(), sizes.data(), within.data(), info);
             }
         };
         // --edpl: the EDPL of every unique read from the results on the host, over the database's tree as --epca builds it, through

@@ -25,6 +25,7 @@
 #include "rk_samples.h"
 #include "rk_epca.h"
 #include "rk_edpl.h"
+#include "rk_kmeans.h"
 
 #include <type_traits>
 #ifndef RK_ROW_NT

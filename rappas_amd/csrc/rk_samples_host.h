@@ -1,7 +1,8 @@
 // rk_samples_host.h -- the host side of the sample-level calls: the checks and the one walk of a tree behind
 // rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel, kr_pairs_kernel, the squash kernels (rk_samples.h) and
 // the edge-PCA kernels (rk_epca.h) behind rk_clade_masses_host, rk_kr_distances_host, rk_squash_host and rk_epca_host, and the
-// distance tables of a tree with the twin of edpl_kernel (rk_edpl.h) behind rk_edpl_host and rk_tree_distance_host.  Header-only,
+// distance tables of a tree with the twin of edpl_kernel (rk_edpl.h) behind rk_edpl_host and rk_tree_distance_host, and the twin of
+// the k-means kernels (rk_kmeans.h) behind rk_kmeans_host.  Header-only,
 // plain C++, like rk_masses_host.h.  Not part of the C ABI.
 //
 // The KR distance is written as include/rappas_place.h defines it, term by term and in the order fixed there, so that the device and
@@ -451,6 +452,157 @@ inline double edpl_read(const TreeDist &t, uint32_t n, const uint16_t *branch, c
 
 inline void edpl_range(const TreeDist &t, uint32_t K, uint64_t r_lo, uint64_t r_hi, const uint8_t *n_rows, const uint16_t *branch, const double *lwr, double *edpl) {
     for (uint64_t r = r_lo; r < r_hi; r++) edpl[r] = edpl_read(t, n_rows[r] < K ? n_rows[r] : K, branch + r * K, lwr + r * K);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Phylogenetic k-means (include/rappas_place.h holds the definition): the host twin of the kernels of rk_kmeans.h.
+// Profiles lie sample after sample, B doubles each; the centroid profiles cu, cv cluster after cluster, B doubles each; Dc is [k][S].
+// ------------------------------------------------------------------------------------------------
+constexpr uint32_t KMEANS_NONE = 0xFFFFFFFFu, KMEANS_GROUP = 256, KMEANS_MAX_K = 64, KMEANS_MAX_ROUNDS = 1024;
+
+struct KmeansOut {  // the outputs of a run; centroids may be nullptr
+    uint32_t *assign;
+    double *dist;
+    uint32_t *sizes;
+    double *within;
+    uint32_t *info;
+    double *centroids;
+};
+
+// every output as its filler, info = {k_eff, n_active, 0 rounds, converged | status << 1}
+inline void kmeans_fill(uint32_t B, uint32_t S, uint32_t k, uint32_t k_eff, uint32_t n_active, uint32_t status, const KmeansOut &o) {
+    for (uint32_t s = 0; s < S; s++) {
+        o.assign[s] = KMEANS_NONE;
+        o.dist[s] = 0.0;
+    }
+    for (uint32_t j = 0; j < k; j++) {
+        o.sizes[j] = 0;
+        o.within[j] = 0.0;
+    }
+    if (o.centroids)
+        for (uint64_t i = 0; i < (uint64_t)k * 2 * B; i++) o.centroids[i] = 0.0;
+    o.info[0] = k_eff;
+    o.info[1] = n_active;
+    o.info[2] = 0;
+    o.info[3] = 1u | status << 1;
+}
+
+// Dc[j][s] for the centroids j_lo <= j < j_hi and the active samples s = s_lo, s_lo + s_step, ...: the centroid is the first operand
+inline void kmeans_distances(uint32_t B, uint32_t S, const double *h, const double *u, const double *v, const uint8_t *active, const double *cu, const double *cv,
+                             uint32_t j_lo, uint32_t j_hi, uint32_t s_lo, uint32_t s_step, double *Dc) {
+    for (uint64_t j = j_lo; j < j_hi; j++)
+        for (uint64_t s = s_lo; s < S; s += s_step)
+            if (active[s]) Dc[j * S + s] = kr_pair(B, h, cu + j * B, cv + j * B, u + s * B, v + s * B);
+}
+
+// Farthest-first seeds 1 .. k_eff - 1 behind seed_0 = the smallest active sample; every seed's profile becomes its cluster's centroid.
+// dist_step(j_lo, j_hi) fills rows j_lo .. j_hi - 1 of Dc: kmeans_distances over every s, dealt as the caller likes.
+template <class DistStep>
+inline void kmeans_seed(uint32_t B, uint32_t S, uint32_t k_eff, const double *u, const double *v, const uint8_t *active, double *cu, double *cv, const double *Dc,
+                        uint32_t *seeds, DistStep &&dist_step) {
+    std::vector<double> mind(S, 0.0);
+    std::vector<uint8_t> is_seed(S, 0);
+    auto take = [&](uint32_t j, uint32_t s) {
+        seeds[j] = s;
+        is_seed[s] = 1;
+        for (uint64_t x = 0; x < B; x++) {
+            cu[j * (uint64_t)B + x] = u[s * (uint64_t)B + x];
+            cv[j * (uint64_t)B + x] = v[s * (uint64_t)B + x];
+        }
+    };
+    uint32_t s0 = 0;
+    while (!active[s0]) s0++;
+    take(0, s0);
+    for (uint32_t j = 1; j < k_eff; j++) {
+        dist_step(j - 1, j);
+        const double *row = Dc + (uint64_t)(j - 1) * S;
+        uint32_t best = KMEANS_NONE;
+        for (uint32_t s = 0; s < S; s++) {
+            if (!active[s]) continue;
+            mind[s] = (j == 1 || row[s] < mind[s]) ? row[s] : mind[s];
+            if (!is_seed[s] && (best == KMEANS_NONE || mind[s] > mind[best])) best = s;
+        }
+        take(j, best);
+    }
+}
+
+// assign[s] = the nearest centroid of every active s (plain <, ties to the smaller j), dist[s] its distance; returns `changed`
+inline uint32_t kmeans_assign(uint32_t S, uint32_t k_eff, const double *Dc, const uint8_t *active, uint32_t *assign, double *dist) {
+    uint32_t changed = 0;
+    for (uint32_t s = 0; s < S; s++) {
+        if (!active[s]) continue;
+        uint32_t best = 0;
+        for (uint32_t j = 1; j < k_eff; j++)
+            if (Dc[(uint64_t)j * S + s] < Dc[(uint64_t)best * S + s]) best = j;
+        changed += assign[s] != best;
+        assign[s] = best;
+        dist[s] = Dc[(uint64_t)best * S + s];
+    }
+    return changed;
+}
+
+// The new centroids of the clusters j = j_lo, j_lo + j_step, ... < k_eff: the members in ascending s, one partial a group of
+// KMEANS_GROUP sample indices from +0.0, the partials of the groups that hold a member in group order, then the division.  A cluster
+// without members keeps its profile.
+inline void kmeans_update(uint32_t B, uint32_t S, uint32_t k_eff, const double *u, const double *v, const uint32_t *assign, uint32_t j_lo, uint32_t j_step, double *cu,
+                          double *cv) {
+    std::vector<double> pu(B), pv(B), su(B), sv(B);
+    for (uint64_t j = j_lo; j < k_eff; j += j_step) {
+        uint32_t n = 0;
+        for (uint32_t g0 = 0; g0 < S; g0 += KMEANS_GROUP) {
+            uint32_t in_group = 0;
+            for (uint64_t s = g0; s < S && s < g0 + KMEANS_GROUP; s++) {
+                if (assign[s] != j) continue;
+                if (!in_group++)
+                    for (uint32_t x = 0; x < B; x++) pu[x] = pv[x] = 0.0;
+                for (uint32_t x = 0; x < B; x++) {
+                    pu[x] = pu[x] + u[s * B + x];
+                    pv[x] = pv[x] + v[s * B + x];
+                }
+            }
+            if (!in_group) continue;
+            for (uint32_t x = 0; x < B; x++) {
+                su[x] = n ? su[x] + pu[x] : pu[x];
+                sv[x] = n ? sv[x] + pv[x] : pv[x];
+            }
+            n += in_group;
+        }
+        if (!n) continue;
+        const double nn = (double)n;
+        for (uint32_t x = 0; x < B; x++) {
+            cu[j * B + x] = su[x] / nn;
+            cv[j * B + x] = sv[x] / nn;
+        }
+    }
+}
+
+// The rounds behind the start (cu, cv hold the seeds' profiles), then sizes, within, info and the centroids.  dist_step(j_lo, j_hi)
+// as in kmeans_seed; update_step() gives every cluster its new centroid: kmeans_update over every j, dealt as the caller likes.
+template <class DistStep, class UpdateStep>
+inline void kmeans_rounds(uint32_t B, uint32_t S, uint32_t k, uint32_t k_eff, uint32_t n_active, uint32_t max_rounds, const uint8_t *active, const double *cu,
+                          const double *cv, const double *Dc, const KmeansOut &o, DistStep &&dist_step, UpdateStep &&update_step) {
+    kmeans_fill(B, S, k, k_eff, n_active, 0, o);
+    uint32_t rounds = 0, converged = 0;
+    while (rounds < max_rounds && !converged) {
+        dist_step(0, k_eff);
+        const uint32_t changed = kmeans_assign(S, k_eff, Dc, active, o.assign, o.dist);
+        rounds++;
+        if (changed == 0) converged = 1;
+        else update_step();
+    }
+    for (uint32_t s = 0; s < S; s++)
+        if (active[s]) {
+            o.sizes[o.assign[s]]++;
+            o.within[o.assign[s]] = o.within[o.assign[s]] + o.dist[s];
+        }
+    o.info[2] = rounds;
+    o.info[3] = converged;
+    if (o.centroids)
+        for (uint64_t j = 0; j < k_eff; j++)
+            for (uint64_t x = 0; x < B; x++) {
+                o.centroids[(j * 2) * B + x] = cu[j * B + x];
+                o.centroids[(j * 2 + 1) * B + x] = cv[j * B + x];
+            }
 }
 
 }  // namespace rk

@@ -2,7 +2,8 @@
 // the clade sums of sample mass buffers (rk_clade_masses_device / _host), the KR distance matrix (rk_kr_distances_device / _host /
 // _batch), the squash clustering over it (rk_squash_device / _host / _batch) and the edge principal components (rk_epca_device / _host /
 // _batch / _finish_host) and the per-read EDPL (rk_edpl_device / _host / _batch, rk_tree_distance_host)
-// -- over the kernels of rk_samples.h, rk_epca.h and rk_edpl.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
+// and the phylogenetic k-means of the samples (rk_kmeans_device / _host / _batch)
+// -- over the kernels of rk_samples.h, rk_epca.h, rk_edpl.h and rk_kmeans.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
 // scratch, and only the _batch calls touch a database handle.
 #pragma once
 
@@ -463,6 +464,309 @@ extern "C" int rk_squash_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, 
     if (int rc = rk_squash_device(t, n_samples, d_masses, (rk_squash_merge *)d_out.p, d_count, work.p, need, s)) return rc;
     HIP_TRY(hipMemcpyAsync(merges, d_out.p, rows_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(n_merges, d_count, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Phylogenetic k-means: rk_kmeans_work_bytes / _device / _host / _batch.
+// ------------------------------------------------------------------------------------------------
+static_assert(RK_KMEANS_MAX_K == KMEANS_MAX_CENTROIDS && RK_KMEANS_MAX_K == rk::KMEANS_MAX_K && RK_KMEANS_GROUP == KMEANS_UPDATE_GROUP &&
+                  RK_KMEANS_GROUP == rk::KMEANS_GROUP && RK_KMEANS_NONE == KMEANS_FILLER && RK_KMEANS_NONE == rk::KMEANS_NONE &&
+                  RK_KMEANS_MAX_ROUNDS == rk::KMEANS_MAX_ROUNDS,
+              "one set of constants for the header, the host twin and the kernels");
+
+// The workspace of rk_kmeans_device: the KR workspace without its pair partials (clade | U | V) | cu[k][B] | cv[k][B] |
+// part[chunks][k][S] | bestd[S] | mind[S] | best[S] | active[S] | members[k] | the control words
+struct KmeansPlan {
+    KrPlan kr;
+    uint64_t cu_at, cv_at, part_at, bestd_at, mind_at, best_at, active_at, members_at, ctl_at, bytes;
+};
+static bool kmeans_plan(uint32_t B, uint32_t S, uint32_t k, KmeansPlan &p) {
+    const uint64_t sb = (uint64_t)S * B * 8, kb = (uint64_t)k * B * 8;
+    auto up = [](uint64_t v) { return (v + 15) / 16 * 16; };
+    p.kr.n_chunks = (B + RK_KR_CHUNK - 1) / RK_KR_CHUNK;
+    p.kr.to_part = false;
+    p.kr.clade_at = 0;
+    p.kr.u_at = sb;
+    p.kr.v_at = 2 * sb;
+    p.kr.part_at = p.kr.bytes = 3 * sb;
+    p.cu_at = up(3 * sb);
+    p.cv_at = p.cu_at + kb;
+    p.part_at = p.cv_at + kb;
+    p.bestd_at = p.part_at + (uint64_t)p.kr.n_chunks * k * S * 8;
+    p.mind_at = p.bestd_at + (uint64_t)S * 8;
+    p.best_at = p.mind_at + (uint64_t)S * 8;
+    p.active_at = p.best_at + (uint64_t)S * 4;
+    p.members_at = p.active_at + (uint64_t)S * 4;
+    p.ctl_at = p.members_at + (uint64_t)k * 4;
+    p.bytes = up(p.ctl_at + (uint64_t)KM_WORDS * 4);
+    return p.bytes <= RK_KR_MAX_WORK_BYTES;
+}
+
+static int kmeans_args(const char *who, uint32_t S, uint32_t k, uint32_t max_rounds) {
+    if (S < 1 || S > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, S);
+    if (k < 1 || k > RK_KMEANS_MAX_K) return fail(RK_ERR_INVALID, "%s: k=%u clusters must be in 1..%u", who, k, RK_KMEANS_MAX_K);
+    if (max_rounds < 1 || max_rounds > RK_KMEANS_MAX_ROUNDS) return fail(RK_ERR_INVALID, "%s: max_rounds=%u must be in 1..%u", who, max_rounds, RK_KMEANS_MAX_ROUNDS);
+    return RK_OK;
+}
+// the caller's seeds, on the host: k indices below S, no two the same
+static int kmeans_seed_args(const char *who, uint32_t S, uint32_t k, const uint32_t *seeds) {
+    if (!seeds) return RK_OK;
+    for (uint32_t j = 0; j < k; j++) {
+        if (seeds[j] >= S) return fail(RK_ERR_INVALID, "%s: seeds[%u]=%u, the buffer has %u samples", who, j, seeds[j], S);
+        for (uint32_t i = 0; i < j; i++)
+            if (seeds[i] == seeds[j]) return fail(RK_ERR_INVALID, "%s: seeds[%u] and seeds[%u] are both sample %u", who, i, j, seeds[j]);
+    }
+    return RK_OK;
+}
+
+extern "C" uint64_t rk_kmeans_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t k) {
+    const char *who = "rk_kmeans_work_bytes";
+    if (!t) {
+        (void)fail(RK_ERR_INVALID, "%s: null tree", who);
+        return 0;
+    }
+    if (kmeans_args(who, n_samples, k, 1)) return 0;
+    KmeansPlan p;
+    if (!kmeans_plan(t->B, n_samples, k, p)) {
+        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u, k=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, k, t->B);
+        return 0;
+    }
+    return p.bytes;
+}
+
+struct KmeansDeviceOut {
+    uint32_t *assign;
+    double *dist;
+    uint32_t *sizes;
+    double *within;
+    uint32_t *info;
+    double *centroids;
+};
+
+// The rung of kmeans_dist_kernel's ladder for k centroids: the largest -- none beyond the smallest that holds them all -- that still
+// leaves four blocks a CU, and 1 where none does.  A block is one wave whose sums are KC dependent chains: more centroids a block
+// stream U and V fewer times, fewer give more waves to hide the loads behind, and only a grid that fills the device gains from the
+// first (profiles/kmeans_rate.txt: the measured best of every shape there is this rule's choice).
+static uint32_t kmeans_rung(const rk_tree *t, uint32_t S, uint32_t k) {
+    const uint64_t per_group = (uint64_t)((t->B + RK_KR_CHUNK - 1) / RK_KR_CHUNK) * ((S + KMEANS_WAVE - 1) / KMEANS_WAVE);
+    for (uint32_t kc = 8; kc > 1; kc >>= 1)
+        if (kc < 2 * k && per_group * ((k + kc - 1) / kc) >= 4ull * t->cu_count) return kc;
+    return 1;
+}
+
+// The launches behind rk_kmeans_device.  `steps` (developer builds, scripts/kmeans_rate.py): bit 0 clade sums, profiles, the start and
+// the seeding, 1 the distance step, 2 its reduce, 3 the assignment, 4 the update, 5 the centroid output.  `kc`: the rung of the ladder.
+static int kmeans_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, uint32_t k, uint32_t max_rounds, const uint32_t *seeds, const KmeansDeviceOut &o,
+                         void *d_work, const KmeansPlan &p, hipStream_t s, uint32_t kc, unsigned steps = 63) {
+    const uint32_t B = t->B, n_chunks = p.kr.n_chunks;
+    char *w = (char *)d_work;
+    const u64 *clade = (const u64 *)(w + p.kr.clade_at);
+    const double *U = (const double *)(w + p.kr.u_at), *V = (const double *)(w + p.kr.v_at);
+    double *cu = (double *)(w + p.cu_at), *cv = (double *)(w + p.cv_at), *part = (double *)(w + p.part_at);
+    double *bestd = (double *)(w + p.bestd_at), *mind = (double *)(w + p.mind_at);
+    u32 *best = (u32 *)(w + p.best_at), *active = (u32 *)(w + p.active_at), *members = (u32 *)(w + p.members_at), *ctl = (u32 *)(w + p.ctl_at);
+    const unsigned waves = (S + KMEANS_WAVE - 1) / KMEANS_WAVE, s_blocks = (S + 255) / 256, x_blocks = (B + 255) / 256;
+    auto dist = [&](uint32_t rung, uint32_t j_base, uint32_t j_limit) {
+        const dim3 grid(n_chunks, waves, (j_limit - j_base + rung - 1) / rung);
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(KMEANS_WAVE), 0, s, B, S, k, j_base, j_limit, (const u32 *)ctl, (const u32 *)active, U, V, t->h, (const double *)cu,
+                               (const double *)cv, part);
+        };
+        if (rung == 1) go(kmeans_dist_kernel<1>);
+        else if (rung == 2) go(kmeans_dist_kernel<2>);
+        else if (rung == 4) go(kmeans_dist_kernel<4>);
+        else go(kmeans_dist_kernel<8>);
+    };
+    auto reduce = [&](uint32_t j_base, uint32_t j_limit) {
+        hipLaunchKernelGGL(kmeans_reduce_kernel, dim3(s_blocks), dim3(256), 0, s, S, k, n_chunks, j_base, j_limit, (const u32 *)ctl, (const u32 *)active,
+                           (const double *)part, best, bestd);
+    };
+    if (steps & 1) {
+        if (int rc = kr_launch(t, S, d_masses, nullptr, d_work, p.kr, s, 3)) return rc;
+        KmeansSeeds given{};
+        for (uint32_t j = 0; seeds && j < k; j++) given.s[j] = seeds[j];
+        hipLaunchKernelGGL(kmeans_init_kernel, dim3(1), dim3(256), 0, s, B, S, k, t->root, seeds ? 1u : 0u, given, clade, ctl, active, (u32 *)o.assign, o.dist,
+                           (u32 *)o.sizes, o.within, (u32 *)o.info);
+        HIP_TRY(hipGetLastError());
+        // the seeds' profiles as the first centroids; without caller's seeds, farthest-first: seed j from the distances to seed j - 1
+        hipLaunchKernelGGL(kmeans_gather_kernel, dim3(x_blocks, seeds ? k : 1), dim3(256), 0, s, B, S, k, 0u, (const u32 *)ctl, U, V, cu, cv);
+        for (uint32_t j = 1; !seeds && j < k; j++) {
+            dist(1, j - 1, j);
+            reduce(j - 1, j);
+            hipLaunchKernelGGL(kmeans_seed_kernel, dim3(1), dim3(256), 0, s, S, k, j, ctl, active, (const double *)bestd, mind);
+            hipLaunchKernelGGL(kmeans_gather_kernel, dim3(x_blocks, 1), dim3(256), 0, s, B, S, k, j, (const u32 *)ctl, U, V, cu, cv);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    // the update kernel's lanes: 2^kp_log2 >= k clusters a node, and as many nodes a wave as fit while four blocks a CU are left
+    uint32_t kp_log2 = 0;
+    while ((1u << kp_log2) < k) kp_log2++;
+    uint32_t nodes_log2 = 6 - kp_log2;
+    while (nodes_log2 > 0 && (B >> nodes_log2) < 4 * t->cu_count) nodes_log2--;
+    const uint32_t update_nodes = 1u << nodes_log2;
+    for (uint32_t r = 0; r < max_rounds; r++) {
+        if (steps & 2) dist(kc, 0, k);
+        if (steps & 4) reduce(0, k);
+        if (steps & 8)
+            hipLaunchKernelGGL(kmeans_assign_kernel, dim3(1), dim3(256), 0, s, S, k, r, max_rounds, ctl, (const u32 *)active, (const u32 *)best, (const double *)bestd,
+                               (u32 *)o.assign, o.dist, members, (u32 *)o.sizes, o.within, (u32 *)o.info);
+        if (steps & 16)
+            hipLaunchKernelGGL(kmeans_update_kernel, dim3((B + update_nodes - 1) / update_nodes), dim3(KMEANS_WAVE), 0, s, B, S, k, kp_log2, nodes_log2, (const u32 *)ctl,
+                               (const u32 *)o.assign, (const u32 *)members, U, V, cu, cv);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((steps & 32) && o.centroids) {
+        hipLaunchKernelGGL(kmeans_centroids_kernel, dim3(x_blocks, k), dim3(256), 0, s, B, k, (const u32 *)ctl, (const double *)cu, (const double *)cv, o.centroids);
+        HIP_TRY(hipGetLastError());
+    }
+    return RK_OK;
+}
+
+extern "C" int rk_kmeans_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t k, uint32_t max_rounds, const uint32_t *seeds,
+                                uint32_t *d_assign, double *d_dist, uint32_t *d_sizes, double *d_within, uint32_t *d_info, double *d_centroids, void *d_work,
+                                uint64_t work_bytes, void *stream) {
+    const char *who = "rk_kmeans_device";
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = kmeans_args(who, n_samples, k, max_rounds)) return rc;
+    KmeansPlan p;
+    if (!kmeans_plan(t->B, n_samples, k, p))
+        return fail(RK_ERR_INVALID, "%s: n_samples=%u, k=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, k, t->B);
+    if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!d_assign || !d_dist || !d_sizes || !d_within || !d_info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if ((uintptr_t)d_dist % 8 || (uintptr_t)d_within % 8 || (uintptr_t)d_centroids % 8 || (uintptr_t)d_assign % 4 || (uintptr_t)d_sizes % 4 || (uintptr_t)d_info % 4)
+        return fail(RK_ERR_INVALID, "%s: the doubles must be 8-byte aligned, the 32-bit words 4-byte aligned", who);
+    if (!d_work || work_bytes < p.bytes)
+        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_kmeans_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
+    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    if (int rc = kmeans_seed_args(who, n_samples, k, seeds)) return rc;
+    HIP_TRY(hipSetDevice(t->device));
+    unsigned steps = 63;
+    uint32_t kc = kmeans_rung(t, n_samples, k);
+    if (const char *v = rk_knob("RK_KMEANS_STEPS")) steps = (unsigned)atoi(v);  // developer builds (scripts/kmeans_rate.py)
+    if (const char *v = rk_knob("RK_KMEANS_KC")) {                              // developer builds: every rung of the ladder on one shape
+        const uint32_t f = (uint32_t)atoi(v);
+        if (f == 1 || f == 2 || f == 4 || f == 8) kc = f;
+    }
+    const KmeansDeviceOut o{d_assign, d_dist, d_sizes, d_within, d_info, d_centroids};
+    return kmeans_launch(t, n_samples, d_masses, k, max_rounds, seeds, o, d_work, p, (hipStream_t)stream, kc, steps);
+}
+
+extern "C" int rk_kmeans_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t k,
+                              uint32_t max_rounds, const uint32_t *seeds, uint32_t *assign, double *dist, uint32_t *sizes, double *within, uint32_t *info,
+                              double *centroids, uint32_t n_threads) {
+    const char *who = "rk_kmeans_host";
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (int rc = kmeans_args(who, n_samples, k, max_rounds)) return rc;
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!assign || !dist || !sizes || !within || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (int rc = kmeans_seed_args(who, n_samples, k, seeds)) return rc;
+    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
+    std::vector<uint64_t> clade;
+    std::vector<double> u, v, h, cu, cv, Dc;
+    std::vector<uint8_t> active;
+    try {
+        clade.resize(S * B);
+        u.resize(S * B);
+        v.resize(S * B);
+        h.resize(B);
+        cu.resize(k * B);
+        cv.resize(k * B);
+        Dc.resize(k * S);
+        active.resize(S);
+    } catch (const std::bad_alloc &) {
+        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
+    }
+    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
+    unsigned hw = std::thread::hardware_concurrency();
+    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
+    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
+    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        for (uint64_t s = th; s < S; s += T) {
+            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
+            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
+        }
+    });
+    if (rc) return rc;
+    uint32_t n_active = 0, status = 0;
+    for (uint64_t s = 0; s < S; s++) n_active += active[s] = clade[s * B + w.root] != 0;
+    for (uint32_t j = 0; seeds && j < k; j++) status |= !active[seeds[j]];
+    const uint32_t k_eff = seeds ? k : std::min(k, n_active);
+    const rk::KmeansOut o{assign, dist, sizes, within, info, centroids};
+    if (n_active == 0 || status) {
+        rk::kmeans_fill((uint32_t)B, (uint32_t)S, k, k_eff, n_active, status, o);
+        return RK_OK;
+    }
+    // samples, then clusters, dealt round to the threads
+    auto dist_step = [&](uint32_t j_lo, uint32_t j_hi) {
+        (void)masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+            rk::kmeans_distances((uint32_t)B, (uint32_t)S, h.data(), u.data(), v.data(), active.data(), cu.data(), cv.data(), j_lo, j_hi, (uint32_t)th, (uint32_t)T, Dc.data());
+        });
+    };
+    auto update_step = [&]() {
+        (void)masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+            rk::kmeans_update((uint32_t)B, (uint32_t)S, k_eff, u.data(), v.data(), assign, (uint32_t)th, (uint32_t)T, cu.data(), cv.data());
+        });
+    };
+    if (seeds) {
+        for (uint64_t j = 0; j < k; j++)
+            for (uint64_t x = 0; x < B; x++) {
+                cu[j * B + x] = u[seeds[j] * B + x];
+                cv[j * B + x] = v[seeds[j] * B + x];
+            }
+    } else {
+        std::vector<uint32_t> found(k_eff);
+        rk::kmeans_seed((uint32_t)B, (uint32_t)S, k_eff, u.data(), v.data(), active.data(), cu.data(), cv.data(), Dc.data(), found.data(), dist_step);
+    }
+    rk::kmeans_rounds((uint32_t)B, (uint32_t)S, k, k_eff, n_active, max_rounds, active.data(), cu.data(), cv.data(), Dc.data(), o, dist_step, update_step);
+    return RK_OK;
+}
+
+// The drivers' call: as rk_squash_batch, with the outputs on the host at the end
+extern "C" int rk_kmeans_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t k, uint32_t max_rounds, const uint32_t *seeds,
+                               uint32_t *assign, double *dist, uint32_t *sizes, double *within, uint32_t *info, double *centroids) {
+    const char *who = "rk_kmeans_batch";
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = kmeans_args(who, n_samples, k, max_rounds)) return rc;
+    if (!assign || !dist || !sizes || !within || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (t->B != db->info.n_branches || t->device != db->info.device)
+        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
+    const uint64_t need = rk_kmeans_work_bytes(t, n_samples, k), words = rk_masses_samples_words(t->B, n_samples);
+    if (!need) return RK_ERR_INVALID;
+    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
+    std::lock_guard<std::mutex> lock(db->host_mutex);
+    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
+        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
+    HIP_TRY(hipSetDevice(db->info.device));
+    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
+    hipStream_t s = db->ws[0].stream;
+    GrowBuf work, d_out, d_in;
+    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
+    // dist[S] | within[k] | centroids[k][2][B] when wanted | assign[S] | sizes[k] | info[4]
+    const uint64_t S = n_samples, cen_bytes = centroids ? (uint64_t)k * 2 * t->B * 8 : 0;
+    const uint64_t within_at = S * 8, cen_at = within_at + (uint64_t)k * 8, assign_at = cen_at + cen_bytes, sizes_at = assign_at + S * 4, info_at = sizes_at + (uint64_t)k * 4;
+    if (int rc = work.reserve(need)) return rc;
+    if (int rc = d_out.reserve(info_at + 16)) return rc;
+    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
+    if (masses) {
+        if (int rc = d_in.reserve(words * 8)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
+        d_masses = d_in.as<uint64_t>();
+    }
+    char *base = (char *)d_out.p;
+    if (int rc = rk_kmeans_device(t, n_samples, d_masses, k, max_rounds, seeds, (uint32_t *)(base + assign_at), (double *)base, (uint32_t *)(base + sizes_at),
+                                  (double *)(base + within_at), (uint32_t *)(base + info_at), centroids ? (double *)(base + cen_at) : nullptr, work.p, need, s))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(dist, base, S * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(within, base + within_at, (uint64_t)k * 8, hipMemcpyDeviceToHost, s));
+    if (centroids) HIP_TRY(hipMemcpyAsync(centroids, base + cen_at, cen_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(assign, base + assign_at, S * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(sizes, base + sizes_at, (uint64_t)k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(info, base + info_at, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return RK_OK;
 }

@@ -485,6 +485,23 @@ def squash_table(names, merges, n_merges, with_mass=None):
     return "".join(out)
 
 
+def kmeans_table(names, k, assign, dist, sizes, within, info):
+    """the text `--kmeans FILE` writes: a line `#kmeans<TAB>S<TAB>k<TAB>k_eff<TAB>n_active<TAB>rounds<TAB>converged`; `#clusters` and a
+    line `j<TAB>size<TAB>within` (`%.17g`) per cluster j < k; `#samples` and a line `name<TAB>cluster<TAB>distance` per sample in sample
+    order, a sample without mass with the cluster `-` and the distance `0`; a last line `#samples_without_mass<TAB>n`.  The arrays are
+    what kmeans_host and EdgeTree.kmeans_batch give.  The twin of rkh::kmeans_table, byte-identical."""
+    S = len(names)
+    info = [int(w) for w in info]
+    out = ["#kmeans\t%d\t%d\t%d\t%d\t%d\t%d\n" % (S, k, info[0], info[1], info[2], info[3] & 1), "#clusters\n"]
+    out.extend("%d\t%d\t%.17g\n" % (j, int(sizes[j]), float(within[j])) for j in range(k))
+    out.append("#samples\n")
+    for s in range(S):
+        a = int(assign[s])
+        out.append("%s\t-\t0\n" % names[s] if a == 0xFFFFFFFF else "%s\t%d\t%.17g\n" % (names[s], a, float(dist[s])))
+    out.append(f"#samples_without_mass\t{S - info[1]}\n")
+    return "".join(out)
+
+
 def _fmt12(x):
     """NumberFormat.getNumberInstance(Locale.UK) with exactly 12 fraction digits (NewickWriter.java:61-64): grouping commas,
     HALF_EVEN on the exact binary value."""

@@ -806,6 +806,37 @@ def squash_host(parent, branch_len, masses, n_samples, threads=0):
     return merges, int(n.value)
 
 
+# a k-means run: assign uint32 [S] (KMEANS_NONE for a sample without mass), dist float64 [S], sizes uint32 [k], within float64 [k],
+# info uint32 [4] = k_eff, n_active, rounds, converged | status << 1, centroids float64 [k, 2, B] or None
+KMeans = collections.namedtuple("KMeans", "assign dist sizes within info centroids")
+KMEANS_NONE = 0xFFFFFFFF
+
+
+def _kmeans_seeds(seeds, k):
+    if seeds is None:
+        return None
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    if seeds.shape[0] != k:
+        raise ValueError(f"seeds must hold k = {k} sample indices")
+    return seeds
+
+
+def kmeans_host(parent, branch_len, masses, n_samples, k, max_rounds=100, seeds=None, centroids=True, threads=0):
+    """rk_kmeans_host (no GPU): a KMeans of host arrays -- the phylogenetic k-means of the samples of a sample mass buffer on the tree
+    (parent, branch_len), farthest-first seeds unless `seeds` gives k sample indices -- the bits EdgeTree.kmeans gives on the device."""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    B = parent.shape[0]
+    masses = _samples_in(B, n_samples, masses)
+    seeds = _kmeans_seeds(seeds, k)
+    kk = max(k, 0)
+    assign, dist = np.zeros(n_samples, np.uint32), np.zeros(n_samples, np.float64)
+    sizes, within, info = np.zeros(kk, np.uint32), np.zeros(kk, np.float64), np.zeros(4, np.uint32)
+    cen = np.zeros((kk, 2, B), np.float64) if centroids else None
+    _lib.check(_lib.load().rk_kmeans_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), k, max_rounds, None if seeds is None else _ptr(seeds),
+                                          _ptr(assign), _ptr(dist), _ptr(sizes), _ptr(within), _ptr(info), None if cen is None else _ptr(cen), threads))
+    return KMeans(assign, dist, sizes, within, info, cen)
+
+
 # what epca_finish makes of a raw edge-PCA output: eigenvalue, share, residual [k]; projection [S, k]; loading [B, k]; the two info words
 EdgePCA = collections.namedtuple("EdgePCA", "eigenvalue share residual projection loading n_active k_eff")
 
@@ -982,6 +1013,50 @@ class EdgeTree:
         n = C.c_uint32(0)
         _lib.check(self._lib.rk_squash_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(merges), C.byref(n)))
         return merges, int(n.value)
+
+    def kmeans_work_bytes(self, n_samples, k):
+        need = int(self._lib.rk_kmeans_work_bytes(self.handle, n_samples, k))
+        if not need:
+            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
+        return need
+
+    def kmeans(self, masses, n_samples, k, max_rounds=100, seeds=None, centroids=False, stream=None):
+        """rk_kmeans_device: a KMeans of device tensors, written -- assign int32 [S] (the bits are unsigned: -1 is KMEANS_NONE), dist
+        float64 [S], sizes int32 [k], within float64 [k], info int32 [4] and, when asked for, centroids float64 [k, 2, B] --, as
+        kmeans_host gives them; asynchronous on the stream.  `seeds`: k sample indices on the host, read during the call."""
+        import torch
+        dev = self._masses(masses, n_samples)
+        need = self.kmeans_work_bytes(n_samples, k)
+        seeds = _kmeans_seeds(seeds, k)
+        if self._work_buf is None or self._work_buf.numel() < need:
+            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        assign = torch.empty((n_samples,), dtype=torch.int32, device=dev)
+        dist = torch.empty((n_samples,), dtype=torch.float64, device=dev)
+        sizes = torch.empty((k,), dtype=torch.int32, device=dev)
+        within = torch.empty((k,), dtype=torch.float64, device=dev)
+        info = torch.empty((4,), dtype=torch.int32, device=dev)
+        cen = torch.empty((k, 2, self.n_branches), dtype=torch.float64, device=dev) if centroids else None
+        _lib.check(self._lib.rk_kmeans_device(self.handle, n_samples, masses.data_ptr(), k, max_rounds, None if seeds is None else _ptr(seeds), assign.data_ptr(),
+                                              dist.data_ptr(), sizes.data_ptr(), within.data_ptr(), info.data_ptr(), _dp(cen), self._work_buf.data_ptr(),
+                                              self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+        return KMeans(assign, dist, sizes, within, info, cen)
+
+    def kmeans_batch(self, db, n_samples, k, max_rounds=100, masses=None, seeds=None, centroids=False):
+        """rk_kmeans_batch, the drivers' call: a KMeans of host arrays, as kmeans_host gives them, from a host sample mass buffer -- or,
+        masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_kmeans_device on
+        db's device; returns when they are there"""
+        if masses is not None:
+            masses = _samples_in(self.n_branches, n_samples, masses)
+            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
+                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        seeds = _kmeans_seeds(seeds, k)
+        assign, dist = np.zeros(n_samples, np.uint32), np.zeros(n_samples, np.float64)
+        sizes, within, info = np.zeros(k, np.uint32), np.zeros(k, np.float64), np.zeros(4, np.uint32)
+        cen = np.zeros((k, 2, self.n_branches), np.float64) if centroids else None
+        _lib.check(self._lib.rk_kmeans_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), k, max_rounds,
+                                             None if seeds is None else _ptr(seeds), _ptr(assign), _ptr(dist), _ptr(sizes), _ptr(within), _ptr(info),
+                                             None if cen is None else _ptr(cen)))
+        return KMeans(assign, dist, sizes, within, info, cen)
 
     def epca_work_bytes(self, n_samples, k):
         need = int(self._lib.rk_epca_work_bytes(self.handle, n_samples, k))

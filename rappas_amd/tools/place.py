@@ -21,7 +21,9 @@ KR_NEEDS_SAMPLE_SEP = "--kr compares the samples of one run: it needs --sample-s
 SQUASH_NEEDS_SAMPLE_SEP = "--squash clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 EPCA_NEEDS_SAMPLE_SEP = "--epca finds the principal components of the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 EPCA_RANGES = "--epca-components must be in 1..8, --epca-iters in 1..10000"
-EDPL_NEEDS_OUT = "--edpl reads the placements of a run that writes a jplace: it needs --out (and cannot be combined with --masses-only)"
+KMEANS_NEEDS_SAMPLE_SEP = "--kmeans clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
+KMEANS_RANGES = "--kmeans needs --kmeans-k in 1..64; --kmeans-rounds must be in 1..1024"
+EDPL_NEEDS_OUT ="--edpl reads the placements of a run that writes a jplace: it needs --out (and cannot be combined with --masses-only)"
 SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
 
@@ -79,6 +81,26 @@ def epca_text(db, tree, sample_names, words, host_words, k, iters, device=0):
         et.close()
 
 
+def kmeans_text(db, tree, sample_names, words, k, max_rounds, device=0):
+    """`--kmeans FILE`: the table (hostio.kmeans_table) of the phylogenetic k-means of the samples of a sample mass buffer over the
+    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`"""
+    from ..placement import EdgeTree
+    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
+    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
+    try:
+        r = et.kmeans_batch(db, len(sample_names), k, max_rounds, words)
+        return hostio.kmeans_table(sample_names, k, r.assign, r.dist, r.sizes, r.within, r.info)
+    finally:
+        et.close()
+
+
+def _kmeans_check(kmeans, with_samples, k, max_rounds):
+    if kmeans and not with_samples:
+        raise ValueError(KMEANS_NEEDS_SAMPLE_SEP)
+    if kmeans and not (1 <= k <= 64 and 1 <= max_rounds <= 1024):
+        raise ValueError(KMEANS_RANGES)
+
+
 def edpl_text(db, tree, records, unique, res, keep_at_most, device=0):
     """`--edpl FILE`: the table (hostio.edpl_table) of the EDPL of every placed read of a result set on the host, over the database's
     tree as epca_text builds it, through rk_edpl_batch on db's device"""
@@ -93,7 +115,7 @@ def edpl_text(db, tree, records, unique, res, keep_at_most, device=0):
 
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
                call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None, kr=False,
-               squash=False, epca=False, epca_components=5, epca_iters=200, edpl=False):
+               squash=False, epca=False, epca_components=5, epca_iters=200, edpl=False, kmeans=False, kmeans_k=0, kmeans_rounds=100):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
@@ -102,10 +124,12 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for);
     with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table); with kr as well res.kr is
     the text `--kr FILE` writes (kr_text), with squash res.squash the text `--squash FILE` writes (squash_text), with epca res.epca the text
-    `--epca FILE` writes (epca_text) for epca_components components after epca_iters iterations.  edpl: res.edpl is the text `--edpl FILE`
+    `--epca FILE` writes (epca_text) for epca_components components after epca_iters iterations, with kmeans res.kmeans the text
+    `--kmeans FILE` writes (kmeans_text) for kmeans_k clusters and at most kmeans_rounds rounds.  edpl: res.edpl is the text `--edpl FILE`
     writes (edpl_text), with any strand and with translate."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
+    _kmeans_check(kmeans, masses and sample_sep is not None, kmeans_k, kmeans_rounds)
     if epca and not (masses and sample_sep is not None):
         raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
     if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
@@ -129,7 +153,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
             res = PlacementProcess(db, ns_bound).processQueries(
                 seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
                 treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
-        res.kr = res.squash = res.epca = None
+        res.kr = res.squash = res.epca = res.kmeans = None
         res.edpl = edpl_text(db, tree, records, unique, res, keep_at_most, device) if edpl else None
         if members is not None:
             from ..placement import accumulate_masses_samples_host
@@ -142,6 +166,8 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
                 res.squash = squash_text(db, tree, sample_names, sample_words, sample_words, device)
             if epca:
                 res.epca = epca_text(db, tree, sample_names, sample_words, sample_words, epca_components, epca_iters, device)
+            if kmeans:
+                res.kmeans = kmeans_text(db, tree, sample_names, sample_words, kmeans_k, kmeans_rounds, device)
     finally:
         db.close()
     pl = hostio.jplace_placements(tree, names, res.n_rows, res.branch, res.score, res.lwr, guppy)
@@ -160,17 +186,19 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
 
 def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), device=0, union=False,
                      dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None, kr=False, squash=False, epca=False, epca_components=5,
-                     epca_iters=200):
+                     epca_iters=200, kmeans=False, kmeans_k=0, kmeans_rounds=100):
     """`--masses-only FILE`: scan, dedup and gather as place_file, then ONE profile-only call (processQueriesMasses) with the
     multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
     table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
     No jplace and no frames log: the rows and the frame bytes never reach the host.  With sample_sep (one character) the one call is
     processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample; with kr as well
     .kr is the text `--kr FILE` writes, from the buffer that call left on the device, and with squash .squash the text `--squash FILE`
-    writes, from the same buffer, and with epca .epca the text `--epca FILE` writes, from the same buffer again."""
+    writes, from the same buffer, and with epca .epca the text `--epca FILE` writes, from the same buffer again, and with kmeans
+    .kmeans the text `--kmeans FILE` writes, likewise."""
     from types import SimpleNamespace
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
+    _kmeans_check(kmeans, sample_sep is not None, kmeans_k, kmeans_rounds)
     if epca and sample_sep is None:
         raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
     if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
@@ -179,7 +207,7 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
         raise ValueError(KR_NEEDS_SAMPLE_SEP)
     if squash and sample_sep is None:
         raise ValueError(SQUASH_NEEDS_SAMPLE_SEP)
-    kr_out = squash_out = epca_out = None
+    kr_out = squash_out = epca_out = kmeans_out = None
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     try:
         if translate and db.info.alphabet != 20:
@@ -201,6 +229,8 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
                 squash_out = squash_text(db, tree, sample_names, None, words, device)
             if epca:
                 epca_out = epca_text(db, tree, sample_names, None, words, epca_components, epca_iters, device)
+            if kmeans:
+                kmeans_out = kmeans_text(db, tree, sample_names, None, kmeans_k, kmeans_rounds, device)
         else:
             words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(seq, off, weights=weights, **common)
             table = hostio.masses_table(tree, words)
@@ -208,7 +238,7 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
         db.close()
     return SimpleNamespace(masses=table, notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
                            reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters, kr=kr_out,
-                           squash=squash_out, epca=epca_out)
+                           squash=squash_out, epca=epca_out, kmeans=kmeans_out)
 
 
 def _open_db(db_text, union, dbimage, save_dbimage, device):
@@ -280,6 +310,14 @@ def main(argv=None):
                          "line per node id, and a last line #samples_without_mass<TAB>n")
     ap.add_argument("--epca-components", type=int, default=5, metavar="K", help="--epca: the number of components, 1..8 (default 5)")
     ap.add_argument("--epca-iters", type=int, default=200, metavar="N", help="--epca: the fixed number of iterations, 1..10000 (default 200)")
+    ap.add_argument("--kmeans", default=None, metavar="FILE",
+                    help="with --sample-sep and --kmeans-k: the phylogenetic k-means of the samples (clusters whose centroids are the averages "
+                         "of their members' mass, KR distances, farthest-first seeds), found on the device: a line "
+                         "#kmeans<TAB>S<TAB>k<TAB>k_eff<TAB>n_active<TAB>rounds<TAB>converged, #clusters and a line j<TAB>size<TAB>within per "
+                         "cluster, #samples and a line name<TAB>cluster<TAB>distance per sample (- and 0 without mass), and a last line "
+                         "#samples_without_mass<TAB>n")
+    ap.add_argument("--kmeans-k", type=int, default=0, metavar="K", help="--kmeans: the number of clusters, 1..64")
+    ap.add_argument("--kmeans-rounds", type=int, default=100, metavar="N", help="--kmeans: the most rounds run, 1..1024 (default 100)")
     ap.add_argument("--edpl", default=None, metavar="FILE",
                     help="with --out: the EDPL of every placed read (the expected distance between its placement locations: the sum over the "
                          "pairs of its rows of LWR x LWR x the tree path between the midpoints of the two edges), computed on the device: a "
@@ -308,6 +346,10 @@ def main(argv=None):
         ap.error(EPCA_NEEDS_SAMPLE_SEP)
     if a.epca is not None and not (1 <= a.epca_components <= 8 and 1 <= a.epca_iters <= 10000):
         ap.error(EPCA_RANGES)
+    if a.kmeans is not None and a.sample_sep is None:
+        ap.error(KMEANS_NEEDS_SAMPLE_SEP)
+    if a.kmeans is not None and not (1 <= a.kmeans_k <= 64 and 1 <= a.kmeans_rounds <= 1024):
+        ap.error(KMEANS_RANGES)
     if a.edpl is not None and a.out is None:
         ap.error(EDPL_NEEDS_OUT)
     if a.masses_only is None and a.out is None:
@@ -326,7 +368,7 @@ def main(argv=None):
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
                               translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep, kr=a.kr is not None,
                               squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters,
-                              edpl=a.edpl is not None)
+                              edpl=a.edpl is not None, kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -356,6 +398,9 @@ def main(argv=None):
     if res.epca is not None:
         with open(a.epca, "w") as f:
             f.write(res.epca)
+    if res.kmeans is not None:
+        with open(a.kmeans, "w") as f:
+            f.write(res.kmeans)
     if res.edpl is not None:
         with open(a.edpl, "w") as f:
             f.write(res.edpl)
@@ -371,7 +416,8 @@ def _main_masses_only(a, db_text, fasta_text):
     try:
         res = masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.device, union=a.uniondb is not None,
                                dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate, sample_sep=a.sample_sep, kr=a.kr is not None,
-                               squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters)
+                               squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters,
+                               kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -389,6 +435,9 @@ def _main_masses_only(a, db_text, fasta_text):
     if res.epca is not None:
         with open(a.epca, "w") as f:
             f.write(res.epca)
+    if res.kmeans is not None:
+        with open(a.kmeans, "w") as f:
+            f.write(res.kmeans)
     logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.masses_only)), "logs")
     os.makedirs(logs, exist_ok=True)
     with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
