@@ -5,13 +5,22 @@
 // and the phylogenetic k-means of the samples (rk_kmeans_device / _host / _batch)
 // -- over the kernels of rk_samples.h, rk_epca.h, rk_edpl.h and rk_kmeans.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
 // scratch, and only the _batch calls touch a database handle.
+// What the analyses share exists once, ahead of them: the range tests (samples_range, squash_range, kmeans_range, epca_range), which
+// the _host calls and the prepare step of every analysis read; the prepare step (tests, then the workspace plan, carved by Carve and
+// measured by plan_fits), which _work_bytes and _device read; the workspace test of a device call (work_args); the tile grid of the two S x S matrices
+// (launch_tiles); what the four host calls over the KR profiles start from (HostProfiles) and the thread count of every host call
+// (host_threads); the frame of the four _batch calls (samples_batch) over what rk_edpl_batch shares with them (batch_handles,
+// batch_stream, BatchBufs).  An analysis is a plan, a launch function, a host body and a few lines for each of its entry points.
 #pragma once
 
 #include "rk_samples_host.h"
 
 static_assert(RK_KR_CHUNK == rk::KR_CHUNK && RK_KR_CHUNK == KR_CHUNK_IDS, "one chunk rule for the header, the host twin and the kernel");
-constexpr uint64_t RK_KR_MAX_WORK_BYTES = 1ull << 40;
 constexpr uint64_t RK_KR_MAX_PART_BYTES = 1ull << 28;  // per-chunk partials while they stay below 256 MiB: beyond, the tiles alone fill the device
+// A plan beyond this is refused (plan_fits).  Within the limits of the calls none comes near it: clade | U | V of 65535 samples on
+// 65535 branches are 1.03e11 bytes, the partials of an S x S matrix at most RK_KR_MAX_PART_BYTES, and what an analysis adds stays
+// below 2^31 (k-means at k = 64: 1.1e9).  Only a developer build whose RK_KR_PART_BYTES lifts the limit of the partials gets there.
+constexpr uint64_t RK_KR_MAX_WORK_BYTES = 1ull << 40;
 
 struct rk_tree {
     int32_t device = 0;
@@ -28,8 +37,10 @@ struct rk_tree {
 };
 
 extern "C" int rk_tree_validate(uint32_t n_branches, const int32_t *parent, const float *branch_len) {
+    RK_GUARD_BEGIN
     rk::TreeWalk w;
     return rk::tree_walk("rk_tree_validate", n_branches, parent, branch_len, true, w, g_err, sizeof(g_err)) ? RK_ERR_INVALID : RK_OK;
+    RK_GUARD_END("rk_tree_validate")
 }
 
 extern "C" void rk_tree_destroy(rk_tree *t) {
@@ -46,6 +57,7 @@ extern "C" void rk_tree_destroy(rk_tree *t) {
 
 extern "C" int rk_tree_create(int32_t device, uint32_t n_branches, const int32_t *parent, const float *branch_len, rk_tree **out) {
     const char *who = "rk_tree_create";
+    RK_GUARD_BEGIN
     if (!out) return fail(RK_ERR_INVALID, "%s: null out", who);
     *out = nullptr;
     rk::TreeWalk w;
@@ -107,20 +119,141 @@ extern "C" int rk_tree_create(int32_t device, uint32_t n_branches, const int32_t
     HIP_TRY(hipMemcpy((void *)t->lca, dist.lca.data(), dist.lca.size() * 8, hipMemcpyHostToDevice));
     *out = t.release();
     return RK_OK;
+    RK_GUARD_END(who)
 }
 
-static int samples_args(const char *who, const rk_tree *t, uint32_t S) {
-    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+// ------------------------------------------------------------------------------------------------
+// What the sample-level calls share.
+// ------------------------------------------------------------------------------------------------
+static int samples_range(const char *who, uint32_t S) {
     if (S < 1 || S > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, S);
     return RK_OK;
 }
 
+// Hands out the parts of a workspace in order: take(bytes, align) is the offset of the next part, total() the size of the whole
+struct Carve {
+    uint64_t at = 0;
+    uint64_t take(uint64_t bytes, uint64_t align = 8) {
+        const uint64_t here = (at + align - 1) / align * align;
+        at = here + bytes;
+        return here;
+    }
+    uint64_t total() const { return (at + 15) / 16 * 16; }
+};
+
+// the last test of every prepare step: the size of the finished plan
+static int plan_fits(const char *who, const rk_tree *t, uint32_t S, uint64_t bytes) {
+    if (bytes > RK_KR_MAX_WORK_BYTES) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, S, t->B);
+    return RK_OK;
+}
+
+// the workspace test at the end of a device call's tests; `sizer` is the call that tells the size
+static int work_args(const char *who, const char *sizer, const void *d_work, uint64_t work_bytes, uint64_t need) {
+    if (!d_work || work_bytes < need)
+        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (%s)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)need, sizer);
+    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    return RK_OK;
+}
+
+// the threads of a host call: the caller's count, or the CPUs up to 16; never more than 16, nor than the items there are to deal
+static uint64_t host_threads(uint32_t n_threads, uint64_t items) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    const uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
+    return std::max<uint64_t>(1, std::min<uint64_t>({T, 16, items}));
+}
+
+// What the host calls over the KR profiles start from (the caller has tested n_samples): the walk of the tree, the clade sums and the
+// profiles u and v of every sample [S][B], the half lengths h[B], which samples have mass, and the thread count of the call.  The
+// samples are dealt round to the threads.
+struct HostProfiles {
+    rk::TreeWalk w;
+    std::vector<uint64_t> clade;
+    std::vector<double> u, v, h;
+    std::vector<uint8_t> active;
+    uint32_t n_active = 0;
+    uint64_t T = 1;
+    int build(const char *who, uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t n_threads) {
+        if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+        if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+        const uint64_t B = n_branches, S = n_samples, W = rk_masses_words(n_branches);
+        clade.resize(S * B);
+        u.resize(S * B);
+        v.resize(S * B);
+        h.resize(B);
+        active.resize(S);
+        for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
+        T = host_threads(n_threads, S);
+        int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+            for (uint64_t s = th; s < S; s += T) {
+                rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
+                rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
+            }
+        });
+        if (rc) return rc;
+        for (uint64_t s = 0; s < S; s++) n_active += active[s] = clade[s * B + w.root] != 0;
+        return RK_OK;
+    }
+};
+
+// What every _batch call tests first: both handles, and that the tree is the database's
+static int batch_handles(const char *who, const rk_db *db, const rk_tree *t) {
+    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (t->B != db->info.n_branches || t->device != db->info.device)
+        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
+    return RK_OK;
+}
+// the stream of a _batch call, on the database's device (the caller holds host_mutex)
+static int batch_stream(rk_db *db, hipStream_t &s) {
+    HIP_TRY(hipSetDevice(db->info.device));
+    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
+    s = db->ws[0].stream;
+    return RK_OK;
+}
+// the device buffers of a _batch call: allocated for the call, freed on every way out
+struct BatchBufs {
+    GrowBuf work, out, in;
+    ~BatchBufs() { work.release(); out.release(); in.release(); }
+};
+
+// The frame of the four _batch calls over a sample mass buffer (the caller has tested its arguments): the buffer on the host -- or,
+// masses == NULL, the one the last per-sample profile-only call (rk_place_batch_masses_samples, rk_place_batch_packed_masses_samples)
+// left on the device in the handle --, a workspace of `need` bytes and `out_bytes` for the outputs on the device;
+// queue(d_masses, d_out, d_work, stream) queues the device call and the downloads of its outputs, and the frame waits for them.
+template <class Queue>
+static int samples_batch(const char *who, rk_db *db, uint32_t n_samples, const uint64_t *masses, uint64_t need, uint64_t out_bytes, Queue queue) {
+    const uint32_t B = db->info.n_branches;
+    const uint64_t words = rk_masses_samples_words(B, n_samples);
+    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, B);
+    std::lock_guard<std::mutex> lock(db->host_mutex);
+    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
+        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
+    hipStream_t s;
+    if (int rc = batch_stream(db, s)) return rc;
+    BatchBufs b;
+    if (int rc = b.work.reserve(need)) return rc;
+    if (int rc = b.out.reserve(out_bytes)) return rc;
+    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
+    if (masses) {
+        if (int rc = b.in.reserve(words * 8)) return rc;
+        HIP_TRY(hipMemcpyAsync(b.in.p, masses, words * 8, hipMemcpyHostToDevice, s));
+        d_masses = b.in.as<uint64_t>();
+    }
+    if (int rc = queue(d_masses, (char *)b.out.p, b.work.p, s)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return RK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Clade sums and KR distances: rk_clade_masses_device / _host, rk_kr_work_bytes / rk_kr_distances_device / _host / _batch.
+// ------------------------------------------------------------------------------------------------
 extern "C" int rk_clade_masses_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint64_t *d_clade, void *stream) {
     const char *who = "rk_clade_masses_device";
-    if (int rc = samples_args(who, t, n_samples)) return rc;
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = samples_range(who, n_samples)) return rc;
     if (!d_masses || !d_clade) return fail(RK_ERR_INVALID, "%s: null %s", who, d_masses ? "output" : "mass buffer");
     HIP_TRY(hipSetDevice(t->device));
-    hipLaunchKernelGGL(clade_masses_kernel, dim3(n_samples), dim3(256), 0, (hipStream_t)stream, t->B, (u64)(2ull * t->B + 4), t->node_at, t->end_at, t->span_node,
+    hipLaunchKernelGGL(clade_masses_kernel, dim3(n_samples), dim3(256), 0, (hipStream_t)stream, t->B, (u64)rk_masses_words(t->B), t->node_at, t->end_at, t->span_node,
                        t->span_end, t->span_off, (const u64 *)d_masses, (u64 *)d_clade);
     HIP_TRY(hipGetLastError());
     return RK_OK;
@@ -128,44 +261,66 @@ extern "C" int rk_clade_masses_device(const rk_tree *t, uint32_t n_samples, cons
 
 extern "C" int rk_clade_masses_host(uint32_t n_branches, const int32_t *parent, uint32_t n_samples, const uint64_t *masses, uint64_t *clade) {
     const char *who = "rk_clade_masses_host";
+    RK_GUARD_BEGIN
     rk::TreeWalk w;
     if (rk::tree_walk(who, n_branches, parent, nullptr, false, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
-    if (n_samples < 1 || n_samples > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, n_samples);
+    if (int rc = samples_range(who, n_samples)) return rc;
     if (!masses || !clade) return fail(RK_ERR_INVALID, "%s: null %s", who, masses ? "output" : "mass buffer");
-    const uint64_t B = n_branches, W = 2 * B + 4;
+    const uint64_t B = n_branches, W = rk_masses_words(n_branches);
     for (uint64_t s = 0; s < n_samples; s++) rk::clade_masses_sample(w, parent, masses + s * W, clade + s * B);
     return RK_OK;
+    RK_GUARD_END(who)
 }
 
 // The workspace of rk_kr_distances_device: clade[S][B] (64-bit) | u[B][S] | v[B][S] | the partials, chunks x S x S, when they are used.
+// The analyses that start from the profiles carve theirs behind a plan without the pair partials: `to_part` is then the rule alone.
 struct KrPlan {
     uint32_t n_chunks;
     bool to_part;
     uint64_t clade_at, u_at, v_at, part_at, bytes;
 };
-static bool kr_plan(uint32_t B, uint32_t S, KrPlan &p) {
+static KrPlan kr_plan(Carve &c, uint32_t B, uint32_t S, bool pair_partials) {
     const uint64_t sb = (uint64_t)S * B * 8, ss = (uint64_t)S * S * 8;
+    KrPlan p;
     p.n_chunks = (B + RK_KR_CHUNK - 1) / RK_KR_CHUNK;
     uint64_t part_limit = RK_KR_MAX_PART_BYTES;
     if (const char *v = rk_knob("RK_KR_PART_BYTES")) part_limit = strtoull(v, nullptr, 10);  // developer builds: both forms on small shapes
     p.to_part = p.n_chunks > 1 && ss * p.n_chunks <= part_limit;
-    p.clade_at = 0;
-    p.u_at = sb;
-    p.v_at = 2 * sb;
-    p.part_at = 3 * sb;
-    p.bytes = 3 * sb + (p.to_part ? ss * p.n_chunks : 0);
-    return p.bytes <= RK_KR_MAX_WORK_BYTES;
+    p.clade_at = c.take(sb);
+    p.u_at = c.take(sb);
+    p.v_at = c.take(sb);
+    p.part_at = c.take(pair_partials && p.to_part ? ss * p.n_chunks : 0);
+    p.bytes = c.at;
+    return p;
+}
+// the tests of rk_kr_work_bytes and rk_kr_distances_device, and the plan
+static int kr_prepare(const char *who, const rk_tree *t, uint32_t S, KrPlan &p) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = samples_range(who, S)) return rc;
+    Carve c;
+    p = kr_plan(c, t->B, S, true);
+    return plan_fits(who, t, S, p.bytes);
 }
 
 extern "C" uint64_t rk_kr_work_bytes(const rk_tree *t, uint32_t n_samples) {
-    const char *who = "rk_kr_work_bytes";
-    if (samples_args(who, t, n_samples)) return 0;
     KrPlan p;
-    if (!kr_plan(t->B, n_samples, p)) {
-        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
-        return 0;
+    return kr_prepare("rk_kr_work_bytes", t, n_samples, p) ? 0 : p.bytes;
+}
+
+// The triangular grid of tiles over an S x S matrix that kr_pairs_kernel and epca_gram_kernel share: tiles(grid, side, chunks a block,
+// to_part) launches the kernel; where the plan has per-chunk partials a block takes one chunk, and kr_reduce_kernel sums them into `out`.
+template <class Tiles>
+static int launch_tiles(uint32_t S, const KrPlan &p, const double *part, double *out, hipStream_t s, Tiles tiles) {
+    const uint32_t side = (S + KR_TILE - 1) / KR_TILE;
+    const uint64_t n_tiles = (uint64_t)side * (side + 1) / 2;
+    tiles(dim3((unsigned)n_tiles, p.to_part ? p.n_chunks : 1), side, p.to_part ? 1u : p.n_chunks, p.to_part ? 1u : 0u);
+    HIP_TRY(hipGetLastError());
+    if (p.to_part) {
+        const uint64_t n = (uint64_t)S * S;
+        hipLaunchKernelGGL(kr_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u64)n, p.n_chunks, part, out);
+        HIP_TRY(hipGetLastError());
     }
-    return p.bytes;
+    return RK_OK;
 }
 
 // The launches behind rk_kr_distances_device, each on its own for scripts/kr_rate.py (developer builds time them one by one).
@@ -174,40 +329,29 @@ static int kr_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, dou
     u64 *clade = (u64 *)((char *)d_work + p.clade_at);
     double *U = (double *)((char *)d_work + p.u_at), *V = (double *)((char *)d_work + p.v_at), *part = (double *)((char *)d_work + p.part_at);
     if (steps & 1) {
-        hipLaunchKernelGGL(clade_masses_kernel, dim3(S), dim3(256), 0, s, B, (u64)(2ull * B + 4), t->node_at, t->end_at, t->span_node, t->span_end, t->span_off,
+        hipLaunchKernelGGL(clade_masses_kernel, dim3(S), dim3(256), 0, s, B, (u64)rk_masses_words(B), t->node_at, t->end_at, t->span_node, t->span_end, t->span_off,
                            (const u64 *)d_masses, clade);
         HIP_TRY(hipGetLastError());
     }
     if (steps & 2) {
-        hipLaunchKernelGGL(kr_profiles_kernel, dim3((B + 31) / 32, (S + 31) / 32), dim3(256), 0, s, B, S, (u64)(2ull * B + 4), t->root, (const u64 *)d_masses,
+        hipLaunchKernelGGL(kr_profiles_kernel, dim3((B + 31) / 32, (S + 31) / 32), dim3(256), 0, s, B, S, (u64)rk_masses_words(B), t->root, (const u64 *)d_masses,
                            (const u64 *)clade, U, V);
         HIP_TRY(hipGetLastError());
     }
-    if (steps & 4) {
-        const uint32_t side = (S + KR_TILE - 1) / KR_TILE;
-        const uint64_t tiles = (uint64_t)side * (side + 1) / 2;
-        hipLaunchKernelGGL(kr_pairs_kernel, dim3((unsigned)tiles, p.to_part ? p.n_chunks : 1), dim3(256), 0, s, B, S, side, p.to_part ? 1u : p.n_chunks,
-                           p.to_part ? 1u : 0u, (const double *)U, (const double *)V, t->h, d_out, part);
-        HIP_TRY(hipGetLastError());
-        if (p.to_part) {
-            const uint64_t n = (uint64_t)S * S;
-            hipLaunchKernelGGL(kr_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u64)n, p.n_chunks, (const double *)part, d_out);
-            HIP_TRY(hipGetLastError());
-        }
-    }
+    if (steps & 4)
+        return launch_tiles(S, p, part, d_out, s, [&](dim3 grid, uint32_t side, uint32_t chunks, uint32_t to_part) {
+            hipLaunchKernelGGL(kr_pairs_kernel, grid, dim3(256), 0, s, B, S, side, chunks, to_part, (const double *)U, (const double *)V, t->h, d_out, part);
+        });
     return RK_OK;
 }
 
 extern "C" int rk_kr_distances_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, double *d_out, void *d_work, uint64_t work_bytes,
                                       void *stream) {
     const char *who = "rk_kr_distances_device";
-    if (int rc = samples_args(who, t, n_samples)) return rc;
     KrPlan p;
-    if (!kr_plan(t->B, n_samples, p)) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+    if (int rc = kr_prepare(who, t, n_samples, p)) return rc;
     if (!d_masses || !d_out) return fail(RK_ERR_INVALID, "%s: null %s", who, d_masses ? "output" : "mass buffer");
-    if (!d_work || work_bytes < p.bytes)
-        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_kr_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
-    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    if (int rc = work_args(who, "rk_kr_work_bytes", d_work, work_bytes, p.bytes)) return rc;
     HIP_TRY(hipSetDevice(t->device));
     unsigned steps = 7;
     if (const char *v = rk_knob("RK_KR_STEPS")) steps = (unsigned)atoi(v);  // developer builds: bit 0 clade, 1 profiles, 2 pairs (scripts/kr_rate.py)
@@ -217,72 +361,32 @@ extern "C" int rk_kr_distances_device(const rk_tree *t, uint32_t n_samples, cons
 extern "C" int rk_kr_distances_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses,
                                     double *out, uint32_t n_threads) {
     const char *who = "rk_kr_distances_host";
-    rk::TreeWalk w;
-    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
-    if (n_samples < 1 || n_samples > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, n_samples);
-    if (!masses || !out) return fail(RK_ERR_INVALID, "%s: null %s", who, masses ? "output" : "mass buffer");
-    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
-    std::vector<uint64_t> clade;
-    std::vector<double> u, v, h;
-    try {
-        clade.resize(S * B);
-        u.resize(S * B);
-        v.resize(S * B);
-        h.resize(B);
-    } catch (const std::bad_alloc &) {
-        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
-    }
-    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
-    unsigned hw = std::thread::hardware_concurrency();
-    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
-    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
-    // samples, then rows of the matrix, dealt round to the threads (row s has S - s pairs: dealt, not cut into ranges)
-    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-        for (uint64_t s = th; s < S; s += T) {
-            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
-            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
-        }
+    RK_GUARD_BEGIN
+    if (int rc = samples_range(who, n_samples)) return rc;
+    if (!out) return fail(RK_ERR_INVALID, "%s: null output", who);
+    HostProfiles p;
+    if (int rc = p.build(who, n_branches, parent, branch_len, n_samples, masses, n_threads)) return rc;
+    // rows of the matrix, dealt round to the threads (row s has S - s pairs: dealt, not cut into ranges)
+    return masses_fan_out(who, p.T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        rk::kr_rows(n_branches, n_samples, p.h.data(), p.u.data(), p.v.data(), (uint32_t)th, (uint32_t)p.T, out);
     });
-    if (rc) return rc;
-    return masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-        rk::kr_rows((uint32_t)B, (uint32_t)S, h.data(), u.data(), v.data(), (uint32_t)th, (uint32_t)T, out);
-    });
+    RK_GUARD_END(who)
 }
 
-// The drivers' call: the matrix of a sample mass buffer on the host -- or, masses == NULL, of the one the last per-sample profile-only
-// call (rk_place_batch_masses_samples, rk_place_batch_packed_masses_samples) left on the device in the handle -- to the host.
-// Workspace and matrix are allocated for the call and freed; it waits for the result.
+// The drivers' call: the matrix of a sample mass buffer to the host (samples_batch).  Workspace and matrix are allocated for the call
+// and freed; it waits for the result.
 extern "C" int rk_kr_distances_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, double *out) {
     const char *who = "rk_kr_distances_batch";
-    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
-    if (int rc = samples_args(who, t, n_samples)) return rc;
+    if (int rc = batch_handles(who, db, t)) return rc;
+    KrPlan p;
+    if (int rc = kr_prepare(who, t, n_samples, p)) return rc;
     if (!out) return fail(RK_ERR_INVALID, "%s: null output", who);
-    if (t->B != db->info.n_branches || t->device != db->info.device)
-        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
-    const uint64_t need = rk_kr_work_bytes(t, n_samples), words = rk_masses_samples_words(t->B, n_samples);
-    if (!need) return RK_ERR_INVALID;
-    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
-    std::lock_guard<std::mutex> lock(db->host_mutex);
-    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
-        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
-    HIP_TRY(hipSetDevice(db->info.device));
-    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
-    hipStream_t s = db->ws[0].stream;
-    GrowBuf work, d_out, d_in;
-    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
     const uint64_t out_bytes = (uint64_t)n_samples * n_samples * 8;
-    if (int rc = work.reserve(need)) return rc;
-    if (int rc = d_out.reserve(out_bytes)) return rc;
-    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
-    if (masses) {
-        if (int rc = d_in.reserve(words * 8)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
-        d_masses = d_in.as<uint64_t>();
-    }
-    if (int rc = rk_kr_distances_device(t, n_samples, d_masses, d_out.as<double>(), work.p, need, s)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return RK_OK;
+    return samples_batch(who, db, n_samples, masses, p.bytes, out_bytes, [&](const uint64_t *d_masses, char *d_out, void *d_work, hipStream_t s) -> int {
+        if (int rc = rk_kr_distances_device(t, n_samples, d_masses, (double *)d_out, d_work, p.bytes, s)) return rc;
+        HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+        return RK_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -299,36 +403,32 @@ struct SquashPlan {
     uint32_t pick_blocks;
     uint64_t d_at, ua_at, va_at, part_at, scratch_at, active_at, size_at, bytes;
 };
-static bool squash_plan(uint32_t B, uint32_t S, SquashPlan &p) {
-    if (!kr_plan(B, S, p.kr)) return false;
-    auto up = [](uint64_t v) { return (v + 15) / 16 * 16; };
-    p.pick_blocks = std::min<uint32_t>(S - 1, SQUASH_PICK_BLOCKS);
-    p.d_at = up(p.kr.bytes);
-    p.ua_at = p.d_at + (uint64_t)S * S * 8;
-    p.va_at = p.ua_at + (uint64_t)B * 8;
-    p.part_at = p.va_at + (uint64_t)B * 8;
-    p.scratch_at = p.part_at + (uint64_t)p.kr.n_chunks * S * 8;
-    p.active_at = p.scratch_at + (uint64_t)p.pick_blocks * sizeof(SquashBest);
-    p.size_at = p.active_at + (uint64_t)S * 4;
-    p.bytes = up(p.size_at + (uint64_t)S * 4);
-    return p.bytes <= RK_KR_MAX_WORK_BYTES;
-}
-
-static int squash_args(const char *who, const rk_tree *t, uint32_t S) {
-    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+static int squash_range(const char *who, uint32_t S) {
     if (S < 2 || S > RK_SQUASH_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, S, RK_SQUASH_MAX_SAMPLES);
     return RK_OK;
 }
+// the tests of rk_squash_work_bytes and rk_squash_device, and the plan
+static int squash_prepare(const char *who, const rk_tree *t, uint32_t S, SquashPlan &p) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = squash_range(who, S)) return rc;
+    const uint64_t B = t->B;
+    Carve c;
+    p.kr = kr_plan(c, t->B, S, true);
+    p.pick_blocks = std::min<uint32_t>(S - 1, SQUASH_PICK_BLOCKS);
+    p.d_at = c.take((uint64_t)S * S * 8, 16);
+    p.ua_at = c.take(B * 8);
+    p.va_at = c.take(B * 8);
+    p.part_at = c.take((uint64_t)p.kr.n_chunks * S * 8);
+    p.scratch_at = c.take((uint64_t)p.pick_blocks * sizeof(SquashBest));
+    p.active_at = c.take((uint64_t)S * 4, 4);
+    p.size_at = c.take((uint64_t)S * 4, 4);
+    p.bytes = c.total();
+    return plan_fits(who, t, S, p.bytes);
+}
 
 extern "C" uint64_t rk_squash_work_bytes(const rk_tree *t, uint32_t n_samples) {
-    const char *who = "rk_squash_work_bytes";
-    if (squash_args(who, t, n_samples)) return 0;
     SquashPlan p;
-    if (!squash_plan(t->B, n_samples, p)) {
-        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
-        return 0;
-    }
-    return p.bytes;
+    return squash_prepare("rk_squash_work_bytes", t, n_samples, p) ? 0 : p.bytes;
 }
 
 // The launches behind rk_squash_device.  `steps` (developer builds, scripts/squash_rate.py): bit 0 the KR matrix and the start, 1 the
@@ -370,15 +470,12 @@ static int squash_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses,
 extern "C" int rk_squash_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, rk_squash_merge *d_merges, uint32_t *d_n_merges, void *d_work,
                                 uint64_t work_bytes, void *stream) {
     const char *who = "rk_squash_device";
-    if (int rc = squash_args(who, t, n_samples)) return rc;
     SquashPlan p;
-    if (!squash_plan(t->B, n_samples, p)) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+    if (int rc = squash_prepare(who, t, n_samples, p)) return rc;
     if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
     if (!d_merges || !d_n_merges) return fail(RK_ERR_INVALID, "%s: null output", who);
     if ((uintptr_t)d_merges % 8 || (uintptr_t)d_n_merges % 4) return fail(RK_ERR_INVALID, "%s: the rows must be 8-byte aligned, the count 4-byte aligned", who);
-    if (!d_work || work_bytes < p.bytes)
-        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_squash_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
-    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    if (int rc = work_args(who, "rk_squash_work_bytes", d_work, work_bytes, p.bytes)) return rc;
     HIP_TRY(hipSetDevice(t->device));
     unsigned steps = 31;
     if (const char *v = rk_knob("RK_SQUASH_STEPS")) steps = (unsigned)atoi(v);  // developer builds (scripts/squash_rate.py)
@@ -389,83 +486,41 @@ extern "C" int rk_squash_device(const rk_tree *t, uint32_t n_samples, const uint
 extern "C" int rk_squash_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses,
                               rk_squash_merge *merges, uint32_t *n_merges, uint32_t n_threads) {
     const char *who = "rk_squash_host";
-    rk::TreeWalk w;
-    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
-    if (n_samples < 2 || n_samples > RK_SQUASH_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, n_samples, RK_SQUASH_MAX_SAMPLES);
-    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    RK_GUARD_BEGIN
+    if (int rc = squash_range(who, n_samples)) return rc;
     if (!merges || !n_merges) return fail(RK_ERR_INVALID, "%s: null output", who);
-    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
-    std::vector<uint64_t> clade;
-    std::vector<double> u, v, h, D;
-    std::vector<uint8_t> active;
-    try {
-        clade.resize(S * B);
-        u.resize(S * B);
-        v.resize(S * B);
-        h.resize(B);
-        D.resize(S * S);
-        active.resize(S);
-    } catch (const std::bad_alloc &) {
-        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
-    }
-    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
-    unsigned hw = std::thread::hardware_concurrency();
-    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
-    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
+    HostProfiles p;
+    if (int rc = p.build(who, n_branches, parent, branch_len, n_samples, masses, n_threads)) return rc;
+    const uint32_t B = n_branches, S = n_samples, T = (uint32_t)p.T;
+    std::vector<double> D((uint64_t)S * S);
     int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-        for (uint64_t s = th; s < S; s += T) {
-            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
-            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
-        }
+        rk::kr_rows(B, S, p.h.data(), p.u.data(), p.v.data(), (uint32_t)th, T, D.data());
     });
     if (rc) return rc;
-    rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-        rk::kr_rows((uint32_t)B, (uint32_t)S, h.data(), u.data(), v.data(), (uint32_t)th, (uint32_t)T, D.data());
-    });
-    if (rc) return rc;
-    for (uint64_t s = 0; s < S; s++) active[s] = clade[s * B + w.root] != 0;
-    *n_merges = rk::squash_steps((uint32_t)B, (uint32_t)S, u.data(), v.data(), D.data(), active.data(), (rk::SquashMerge *)merges, [&](uint32_t a) {
+    *n_merges = rk::squash_steps(B, S, p.u.data(), p.v.data(), D.data(), p.active.data(), (rk::SquashMerge *)merges, [&](uint32_t a) {
         (void)masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-            rk::squash_row((uint32_t)B, (uint32_t)S, h.data(), u.data(), v.data(), active.data(), a, (uint32_t)th, (uint32_t)T, D.data());
+            rk::squash_row(B, S, p.h.data(), p.u.data(), p.v.data(), p.active.data(), a, (uint32_t)th, T, D.data());
         });
     });
     return RK_OK;
+    RK_GUARD_END(who)
 }
 
 // The drivers' call: as rk_kr_distances_batch, with the rows and their count on the host at the end
 extern "C" int rk_squash_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, rk_squash_merge *merges, uint32_t *n_merges) {
     const char *who = "rk_squash_batch";
-    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
-    if (int rc = squash_args(who, t, n_samples)) return rc;
+    if (int rc = batch_handles(who, db, t)) return rc;
+    SquashPlan p;
+    if (int rc = squash_prepare(who, t, n_samples, p)) return rc;
     if (!merges || !n_merges) return fail(RK_ERR_INVALID, "%s: null output", who);
-    if (t->B != db->info.n_branches || t->device != db->info.device)
-        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
-    const uint64_t need = rk_squash_work_bytes(t, n_samples), words = rk_masses_samples_words(t->B, n_samples);
-    if (!need) return RK_ERR_INVALID;
-    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
-    std::lock_guard<std::mutex> lock(db->host_mutex);
-    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
-        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
-    HIP_TRY(hipSetDevice(db->info.device));
-    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
-    hipStream_t s = db->ws[0].stream;
-    GrowBuf work, d_out, d_in;
-    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
     const uint64_t rows_bytes = (uint64_t)(n_samples - 1) * sizeof(rk_squash_merge);  // the rows, then the count
-    if (int rc = work.reserve(need)) return rc;
-    if (int rc = d_out.reserve(rows_bytes + 8)) return rc;
-    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
-    if (masses) {
-        if (int rc = d_in.reserve(words * 8)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
-        d_masses = d_in.as<uint64_t>();
-    }
-    uint32_t *d_count = (uint32_t *)((char *)d_out.p + rows_bytes);
-    if (int rc = rk_squash_device(t, n_samples, d_masses, (rk_squash_merge *)d_out.p, d_count, work.p, need, s)) return rc;
-    HIP_TRY(hipMemcpyAsync(merges, d_out.p, rows_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(n_merges, d_count, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return RK_OK;
+    return samples_batch(who, db, n_samples, masses, p.bytes, rows_bytes + 8, [&](const uint64_t *d_masses, char *d_out, void *d_work, hipStream_t s) -> int {
+        uint32_t *d_count = (uint32_t *)(d_out + rows_bytes);
+        if (int rc = rk_squash_device(t, n_samples, d_masses, (rk_squash_merge *)d_out, d_count, d_work, p.bytes, s)) return rc;
+        HIP_TRY(hipMemcpyAsync(merges, d_out, rows_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(n_merges, d_count, 4, hipMemcpyDeviceToHost, s));
+        return RK_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -482,30 +537,8 @@ struct KmeansPlan {
     KrPlan kr;
     uint64_t cu_at, cv_at, part_at, bestd_at, mind_at, best_at, active_at, members_at, ctl_at, bytes;
 };
-static bool kmeans_plan(uint32_t B, uint32_t S, uint32_t k, KmeansPlan &p) {
-    const uint64_t sb = (uint64_t)S * B * 8, kb = (uint64_t)k * B * 8;
-    auto up = [](uint64_t v) { return (v + 15) / 16 * 16; };
-    p.kr.n_chunks = (B + RK_KR_CHUNK - 1) / RK_KR_CHUNK;
-    p.kr.to_part = false;
-    p.kr.clade_at = 0;
-    p.kr.u_at = sb;
-    p.kr.v_at = 2 * sb;
-    p.kr.part_at = p.kr.bytes = 3 * sb;
-    p.cu_at = up(3 * sb);
-    p.cv_at = p.cu_at + kb;
-    p.part_at = p.cv_at + kb;
-    p.bestd_at = p.part_at + (uint64_t)p.kr.n_chunks * k * S * 8;
-    p.mind_at = p.bestd_at + (uint64_t)S * 8;
-    p.best_at = p.mind_at + (uint64_t)S * 8;
-    p.active_at = p.best_at + (uint64_t)S * 4;
-    p.members_at = p.active_at + (uint64_t)S * 4;
-    p.ctl_at = p.members_at + (uint64_t)k * 4;
-    p.bytes = up(p.ctl_at + (uint64_t)KM_WORDS * 4);
-    return p.bytes <= RK_KR_MAX_WORK_BYTES;
-}
-
-static int kmeans_args(const char *who, uint32_t S, uint32_t k, uint32_t max_rounds) {
-    if (S < 1 || S > 65535) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..65535", who, S);
+static int kmeans_range(const char *who, uint32_t S, uint32_t k, uint32_t max_rounds) {
+    if (int rc = samples_range(who, S)) return rc;
     if (k < 1 || k > RK_KMEANS_MAX_K) return fail(RK_ERR_INVALID, "%s: k=%u clusters must be in 1..%u", who, k, RK_KMEANS_MAX_K);
     if (max_rounds < 1 || max_rounds > RK_KMEANS_MAX_ROUNDS) return fail(RK_ERR_INVALID, "%s: max_rounds=%u must be in 1..%u", who, max_rounds, RK_KMEANS_MAX_ROUNDS);
     return RK_OK;
@@ -521,19 +554,29 @@ static int kmeans_seed_args(const char *who, uint32_t S, uint32_t k, const uint3
     return RK_OK;
 }
 
+// the tests of rk_kmeans_work_bytes and rk_kmeans_device, and the plan
+static int kmeans_prepare(const char *who, const rk_tree *t, uint32_t S, uint32_t k, uint32_t max_rounds, KmeansPlan &p) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = kmeans_range(who, S, k, max_rounds)) return rc;
+    const uint64_t kb = (uint64_t)k * t->B * 8;
+    Carve c;
+    p.kr = kr_plan(c, t->B, S, false);
+    p.cu_at = c.take(kb, 16);
+    p.cv_at = c.take(kb);
+    p.part_at = c.take((uint64_t)p.kr.n_chunks * k * S * 8);
+    p.bestd_at = c.take((uint64_t)S * 8);
+    p.mind_at = c.take((uint64_t)S * 8);
+    p.best_at = c.take((uint64_t)S * 4, 4);
+    p.active_at = c.take((uint64_t)S * 4, 4);
+    p.members_at = c.take((uint64_t)k * 4, 4);
+    p.ctl_at = c.take((uint64_t)KM_WORDS * 4, 4);
+    p.bytes = c.total();
+    return plan_fits(who, t, S, p.bytes);
+}
+
 extern "C" uint64_t rk_kmeans_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t k) {
-    const char *who = "rk_kmeans_work_bytes";
-    if (!t) {
-        (void)fail(RK_ERR_INVALID, "%s: null tree", who);
-        return 0;
-    }
-    if (kmeans_args(who, n_samples, k, 1)) return 0;
     KmeansPlan p;
-    if (!kmeans_plan(t->B, n_samples, k, p)) {
-        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u, k=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, k, t->B);
-        return 0;
-    }
-    return p.bytes;
+    return kmeans_prepare("rk_kmeans_work_bytes", t, n_samples, k, 1, p) ? 0 : p.bytes;
 }
 
 struct KmeansDeviceOut {
@@ -629,18 +672,13 @@ extern "C" int rk_kmeans_device(const rk_tree *t, uint32_t n_samples, const uint
                                 uint32_t *d_assign, double *d_dist, uint32_t *d_sizes, double *d_within, uint32_t *d_info, double *d_centroids, void *d_work,
                                 uint64_t work_bytes, void *stream) {
     const char *who = "rk_kmeans_device";
-    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
-    if (int rc = kmeans_args(who, n_samples, k, max_rounds)) return rc;
     KmeansPlan p;
-    if (!kmeans_plan(t->B, n_samples, k, p))
-        return fail(RK_ERR_INVALID, "%s: n_samples=%u, k=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, k, t->B);
+    if (int rc = kmeans_prepare(who, t, n_samples, k, max_rounds, p)) return rc;
     if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
     if (!d_assign || !d_dist || !d_sizes || !d_within || !d_info) return fail(RK_ERR_INVALID, "%s: null output", who);
     if ((uintptr_t)d_dist % 8 || (uintptr_t)d_within % 8 || (uintptr_t)d_centroids % 8 || (uintptr_t)d_assign % 4 || (uintptr_t)d_sizes % 4 || (uintptr_t)d_info % 4)
         return fail(RK_ERR_INVALID, "%s: the doubles must be 8-byte aligned, the 32-bit words 4-byte aligned", who);
-    if (!d_work || work_bytes < p.bytes)
-        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_kmeans_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
-    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    if (int rc = work_args(who, "rk_kmeans_work_bytes", d_work, work_bytes, p.bytes)) return rc;
     if (int rc = kmeans_seed_args(who, n_samples, k, seeds)) return rc;
     HIP_TRY(hipSetDevice(t->device));
     unsigned steps = 63;
@@ -658,41 +696,18 @@ extern "C" int rk_kmeans_host(uint32_t n_branches, const int32_t *parent, const 
                               uint32_t max_rounds, const uint32_t *seeds, uint32_t *assign, double *dist, uint32_t *sizes, double *within, uint32_t *info,
                               double *centroids, uint32_t n_threads) {
     const char *who = "rk_kmeans_host";
-    rk::TreeWalk w;
-    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
-    if (int rc = kmeans_args(who, n_samples, k, max_rounds)) return rc;
-    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    RK_GUARD_BEGIN
+    if (int rc = kmeans_range(who, n_samples, k, max_rounds)) return rc;
     if (!assign || !dist || !sizes || !within || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
     if (int rc = kmeans_seed_args(who, n_samples, k, seeds)) return rc;
-    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
-    std::vector<uint64_t> clade;
-    std::vector<double> u, v, h, cu, cv, Dc;
-    std::vector<uint8_t> active;
-    try {
-        clade.resize(S * B);
-        u.resize(S * B);
-        v.resize(S * B);
-        h.resize(B);
-        cu.resize(k * B);
-        cv.resize(k * B);
-        Dc.resize(k * S);
-        active.resize(S);
-    } catch (const std::bad_alloc &) {
-        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
-    }
-    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
-    unsigned hw = std::thread::hardware_concurrency();
-    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
-    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
-    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-        for (uint64_t s = th; s < S; s += T) {
-            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
-            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
-        }
-    });
-    if (rc) return rc;
-    uint32_t n_active = 0, status = 0;
-    for (uint64_t s = 0; s < S; s++) n_active += active[s] = clade[s * B + w.root] != 0;
+    HostProfiles p;
+    if (int rc = p.build(who, n_branches, parent, branch_len, n_samples, masses, n_threads)) return rc;
+    const uint64_t B = n_branches, S = n_samples, T = p.T;
+    const std::vector<double> &u = p.u, &v = p.v, &h = p.h;
+    const std::vector<uint8_t> &active = p.active;
+    std::vector<double> cu(k * B), cv(k * B), Dc(k * S);
+    const uint32_t n_active = p.n_active;
+    uint32_t status = 0;
     for (uint32_t j = 0; seeds && j < k; j++) status |= !active[seeds[j]];
     const uint32_t k_eff = seeds ? k : std::min(k, n_active);
     const rk::KmeansOut o{assign, dist, sizes, within, info, centroids};
@@ -723,52 +738,35 @@ extern "C" int rk_kmeans_host(uint32_t n_branches, const int32_t *parent, const 
     }
     rk::kmeans_rounds((uint32_t)B, (uint32_t)S, k, k_eff, n_active, max_rounds, active.data(), cu.data(), cv.data(), Dc.data(), o, dist_step, update_step);
     return RK_OK;
+    RK_GUARD_END(who)
 }
 
 // The drivers' call: as rk_squash_batch, with the outputs on the host at the end
 extern "C" int rk_kmeans_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t k, uint32_t max_rounds, const uint32_t *seeds,
                                uint32_t *assign, double *dist, uint32_t *sizes, double *within, uint32_t *info, double *centroids) {
     const char *who = "rk_kmeans_batch";
-    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
-    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
-    if (int rc = kmeans_args(who, n_samples, k, max_rounds)) return rc;
+    if (int rc = batch_handles(who, db, t)) return rc;
+    KmeansPlan p;
+    if (int rc = kmeans_prepare(who, t, n_samples, k, max_rounds, p)) return rc;
     if (!assign || !dist || !sizes || !within || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
-    if (t->B != db->info.n_branches || t->device != db->info.device)
-        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
-    const uint64_t need = rk_kmeans_work_bytes(t, n_samples, k), words = rk_masses_samples_words(t->B, n_samples);
-    if (!need) return RK_ERR_INVALID;
-    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
-    std::lock_guard<std::mutex> lock(db->host_mutex);
-    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
-        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
-    HIP_TRY(hipSetDevice(db->info.device));
-    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
-    hipStream_t s = db->ws[0].stream;
-    GrowBuf work, d_out, d_in;
-    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
     // dist[S] | within[k] | centroids[k][2][B] when wanted | assign[S] | sizes[k] | info[4]
+    Carve c;
     const uint64_t S = n_samples, cen_bytes = centroids ? (uint64_t)k * 2 * t->B * 8 : 0;
-    const uint64_t within_at = S * 8, cen_at = within_at + (uint64_t)k * 8, assign_at = cen_at + cen_bytes, sizes_at = assign_at + S * 4, info_at = sizes_at + (uint64_t)k * 4;
-    if (int rc = work.reserve(need)) return rc;
-    if (int rc = d_out.reserve(info_at + 16)) return rc;
-    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
-    if (masses) {
-        if (int rc = d_in.reserve(words * 8)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
-        d_masses = d_in.as<uint64_t>();
-    }
-    char *base = (char *)d_out.p;
-    if (int rc = rk_kmeans_device(t, n_samples, d_masses, k, max_rounds, seeds, (uint32_t *)(base + assign_at), (double *)base, (uint32_t *)(base + sizes_at),
-                                  (double *)(base + within_at), (uint32_t *)(base + info_at), centroids ? (double *)(base + cen_at) : nullptr, work.p, need, s))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(dist, base, S * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(within, base + within_at, (uint64_t)k * 8, hipMemcpyDeviceToHost, s));
-    if (centroids) HIP_TRY(hipMemcpyAsync(centroids, base + cen_at, cen_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(assign, base + assign_at, S * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(sizes, base + sizes_at, (uint64_t)k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(info, base + info_at, 16, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return RK_OK;
+    const uint64_t dist_at = c.take(S * 8), within_at = c.take((uint64_t)k * 8), cen_at = c.take(cen_bytes);
+    const uint64_t assign_at = c.take(S * 4, 4), sizes_at = c.take((uint64_t)k * 4, 4), info_at = c.take(16, 4);
+    return samples_batch(who, db, n_samples, masses, p.bytes, c.at, [&](const uint64_t *d_masses, char *base, void *d_work, hipStream_t s) -> int {
+        if (int rc = rk_kmeans_device(t, n_samples, d_masses, k, max_rounds, seeds, (uint32_t *)(base + assign_at), (double *)(base + dist_at),
+                                      (uint32_t *)(base + sizes_at), (double *)(base + within_at), (uint32_t *)(base + info_at),
+                                      centroids ? (double *)(base + cen_at) : nullptr, d_work, p.bytes, s))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(dist, base + dist_at, S * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(within, base + within_at, (uint64_t)k * 8, hipMemcpyDeviceToHost, s));
+        if (centroids) HIP_TRY(hipMemcpyAsync(centroids, base + cen_at, cen_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(assign, base + assign_at, S * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(sizes, base + sizes_at, (uint64_t)k * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(info, base + info_at, 16, hipMemcpyDeviceToHost, s));
+        return RK_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -783,25 +781,26 @@ struct EpcaPlan {
     KrPlan kr;
     uint64_t g_at, part_at, qa_at, qb_at, active_at, bytes;
 };
-static bool epca_plan(uint32_t B, uint32_t S, uint32_t k, EpcaPlan &p) {
-    if (!kr_plan(B, S, p.kr)) return false;
-    auto up = [](uint64_t v) { return (v + 15) / 16 * 16; };
-    const uint64_t ss = (uint64_t)S * S * 8;
-    p.g_at = up(p.kr.part_at);
-    p.part_at = p.g_at + ss;
-    p.qa_at = p.part_at + (p.kr.to_part ? ss * p.kr.n_chunks : 0);
-    p.qb_at = p.qa_at + (uint64_t)k * S * 8;
-    p.active_at = p.qb_at + (uint64_t)k * S * 8;
-    p.bytes = up(p.active_at + (uint64_t)S * 4);
-    return p.bytes <= RK_KR_MAX_WORK_BYTES;
-}
-
-static int epca_args(const char *who, const rk_tree *t, uint32_t S, uint32_t k, uint32_t iters) {
-    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+static int epca_range(const char *who, uint32_t S, uint32_t k, uint32_t iters) {
     if (S < 2 || S > RK_EPCA_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, S, RK_EPCA_MAX_SAMPLES);
     if (k < 1 || k > RK_EPCA_MAX_COMPONENTS) return fail(RK_ERR_INVALID, "%s: k=%u components must be in 1..%u", who, k, RK_EPCA_MAX_COMPONENTS);
     if (iters < 1 || iters > rk::EPCA_MAX_ITERS) return fail(RK_ERR_INVALID, "%s: iters=%u must be in 1..%u", who, iters, rk::EPCA_MAX_ITERS);
     return RK_OK;
+}
+// the tests of rk_epca_work_bytes and rk_epca_device, and the plan
+static int epca_prepare(const char *who, const rk_tree *t, uint32_t S, uint32_t k, uint32_t iters, EpcaPlan &p) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = epca_range(who, S, k, iters)) return rc;
+    const uint64_t ss = (uint64_t)S * S * 8;
+    Carve c;
+    p.kr = kr_plan(c, t->B, S, false);
+    p.g_at = c.take(ss, 16);
+    p.part_at = c.take(p.kr.to_part ? ss * p.kr.n_chunks : 0);
+    p.qa_at = c.take((uint64_t)k * S * 8);
+    p.qb_at = c.take((uint64_t)k * S * 8);
+    p.active_at = c.take((uint64_t)S * 4, 4);
+    p.bytes = c.total();
+    return plan_fits(who, t, S, p.bytes);
 }
 
 extern "C" uint64_t rk_epca_out_doubles(uint32_t n_branches, uint32_t n_samples, uint32_t k) {
@@ -810,14 +809,8 @@ extern "C" uint64_t rk_epca_out_doubles(uint32_t n_branches, uint32_t n_samples,
 }
 
 extern "C" uint64_t rk_epca_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t k) {
-    const char *who = "rk_epca_work_bytes";
-    if (epca_args(who, t, n_samples, k, 1)) return 0;
     EpcaPlan p;
-    if (!epca_plan(t->B, n_samples, k, p)) {
-        (void)fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
-        return 0;
-    }
-    return p.bytes;
+    return epca_prepare("rk_epca_work_bytes", t, n_samples, k, 1, p) ? 0 : p.bytes;
 }
 
 // The launches behind rk_epca_device.  `steps` (developer builds, scripts/epca_rate.py): bit 0 clade sums, profiles and the start,
@@ -825,7 +818,7 @@ extern "C" uint64_t rk_epca_work_bytes(const rk_tree *t, uint32_t n_samples, uin
 // the S samples whatever the workspace holds, so any subset is safe to time on a workspace a whole call has used.
 static int epca_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, uint32_t k, uint32_t iters, double *d_raw, uint32_t *d_info, void *d_work,
                        const EpcaPlan &p, hipStream_t s, unsigned steps = 31) {
-    const uint32_t B = t->B, n_chunks = p.kr.n_chunks;
+    const uint32_t B = t->B;
     char *w = (char *)d_work;
     const u64 *clade = (const u64 *)(w + p.kr.clade_at);
     double *Xc = (double *)(w + p.kr.u_at), *V = (double *)(w + p.kr.v_at), *G = (double *)(w + p.g_at), *part = (double *)(w + p.part_at);
@@ -843,16 +836,10 @@ static int epca_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, u
         HIP_TRY(hipGetLastError());
     }
     if (steps & 4) {
-        const uint32_t side = (S + KR_TILE - 1) / KR_TILE;
-        const uint64_t tiles = (uint64_t)side * (side + 1) / 2;
-        hipLaunchKernelGGL(epca_gram_kernel, dim3((unsigned)tiles, p.kr.to_part ? n_chunks : 1), dim3(256), 0, s, B, S, side, p.kr.to_part ? 1u : n_chunks,
-                           p.kr.to_part ? 1u : 0u, (const double *)Xc, G, part);
-        HIP_TRY(hipGetLastError());
-        if (p.kr.to_part) {
-            const uint64_t n = (uint64_t)S * S;
-            hipLaunchKernelGGL(kr_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (u64)n, n_chunks, (const double *)part, G);
-            HIP_TRY(hipGetLastError());
-        }
+        int rc = launch_tiles(S, p.kr, part, G, s, [&](dim3 grid, uint32_t side, uint32_t chunks, uint32_t to_part) {
+            hipLaunchKernelGGL(epca_gram_kernel, grid, dim3(256), 0, s, B, S, side, chunks, to_part, (const double *)Xc, G, part);
+        });
+        if (rc) return rc;
     }
     double *q = qa, *y = qb;
     if (steps & 8)
@@ -875,15 +862,12 @@ static int epca_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, u
 extern "C" int rk_epca_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t k, uint32_t iters, double *d_raw, uint32_t *d_info,
                               void *d_work, uint64_t work_bytes, void *stream) {
     const char *who = "rk_epca_device";
-    if (int rc = epca_args(who, t, n_samples, k, iters)) return rc;
     EpcaPlan p;
-    if (!epca_plan(t->B, n_samples, k, p)) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches needs a workspace beyond 2^40 bytes", who, n_samples, t->B);
+    if (int rc = epca_prepare(who, t, n_samples, k, iters, p)) return rc;
     if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
     if (!d_raw || !d_info) return fail(RK_ERR_INVALID, "%s: null output", who);
     if ((uintptr_t)d_raw % 8 || (uintptr_t)d_info % 4) return fail(RK_ERR_INVALID, "%s: the raw output must be 8-byte aligned, the info words 4-byte aligned", who);
-    if (!d_work || work_bytes < p.bytes)
-        return fail(RK_ERR_INVALID, "%s: workspace of %llu bytes, %llu needed (rk_epca_work_bytes)", who, (unsigned long long)(d_work ? work_bytes : 0), (unsigned long long)p.bytes);
-    if ((uintptr_t)d_work % 16) return fail(RK_ERR_INVALID, "%s: the workspace must be 16-byte aligned", who);
+    if (int rc = work_args(who, "rk_epca_work_bytes", d_work, work_bytes, p.bytes)) return rc;
     HIP_TRY(hipSetDevice(t->device));
     unsigned steps = 31;
     if (const char *v = rk_knob("RK_EPCA_STEPS")) steps = (unsigned)atoi(v);  // developer builds (scripts/epca_rate.py)
@@ -893,39 +877,15 @@ extern "C" int rk_epca_device(const rk_tree *t, uint32_t n_samples, const uint64
 extern "C" int rk_epca_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t k,
                             uint32_t iters, double *raw, uint32_t *info, uint32_t n_threads) {
     const char *who = "rk_epca_host";
-    rk::TreeWalk w;
-    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
-    if (n_samples < 2 || n_samples > RK_EPCA_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 2..%u", who, n_samples, RK_EPCA_MAX_SAMPLES);
-    if (k < 1 || k > RK_EPCA_MAX_COMPONENTS) return fail(RK_ERR_INVALID, "%s: k=%u components must be in 1..%u", who, k, RK_EPCA_MAX_COMPONENTS);
-    if (iters < 1 || iters > rk::EPCA_MAX_ITERS) return fail(RK_ERR_INVALID, "%s: iters=%u must be in 1..%u", who, iters, rk::EPCA_MAX_ITERS);
-    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    RK_GUARD_BEGIN
+    if (int rc = epca_range(who, n_samples, k, iters)) return rc;
     if (!raw || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
-    const uint64_t B = n_branches, S = n_samples, W = 2 * B + 4;
-    std::vector<uint64_t> clade;
-    std::vector<double> u, v, G, cols;  // (u becomes the centred matrix)
-    std::vector<uint8_t> active;
-    try {
-        clade.resize(S * B);
-        u.resize(S * B);
-        v.resize(S * B);
-        G.resize(S * S);
-        cols.resize(2 * (uint64_t)k * S);
-        active.resize(S);
-    } catch (const std::bad_alloc &) {
-        return fail(RK_ERR_NOMEM, "%s: no memory for the profiles of %u samples on %u branches", who, n_samples, n_branches);
-    }
-    unsigned hw = std::thread::hardware_concurrency();
-    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
-    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, S}));
-    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-        for (uint64_t s = th; s < S; s += T) {
-            rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
-            rk::kr_profiles_sample((uint32_t)B, w.root, masses + s * W, clade.data() + s * B, u.data() + s * B, v.data() + s * B);
-        }
-    });
-    if (rc) return rc;
-    uint32_t n = 0;
-    for (uint64_t s = 0; s < S; s++) n += active[s] = clade[s * B + w.root] != 0;
+    HostProfiles p;
+    if (int rc = p.build(who, n_branches, parent, branch_len, n_samples, masses, n_threads)) return rc;
+    const uint64_t B = n_branches, S = n_samples, T = p.T;
+    std::vector<double> &u = p.u;  // (u becomes the centred matrix)
+    std::vector<double> G(S * S), cols(2 * (uint64_t)k * S);
+    const uint32_t n = p.n_active;
     const uint32_t k_eff = n < 2 ? 0u : std::min(k, n - 1);
     info[0] = n;
     info[1] = k_eff;
@@ -933,50 +893,32 @@ extern "C" int rk_epca_host(uint32_t n_branches, const int32_t *parent, const fl
     for (uint64_t i = 0; i < n_out; i++) raw[i] = 0.0;
     if (!k_eff) return RK_OK;
     // nodes, then rows of G, dealt round to the threads
-    rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
-        rk::epca_centre((uint32_t)B, (uint32_t)S, w.root, active.data(), n, u.data(), v.data(), (uint32_t)th, (uint32_t)T, u.data());
+    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        rk::epca_centre((uint32_t)B, (uint32_t)S, p.w.root, p.active.data(), n, u.data(), p.v.data(), (uint32_t)th, (uint32_t)T, u.data());
     });
     if (rc) return rc;
     rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) { rk::epca_gram_rows((uint32_t)B, (uint32_t)S, u.data(), (uint32_t)th, (uint32_t)T, G.data()); });
     if (rc) return rc;
     rk::epca_iterate((uint32_t)B, (uint32_t)S, k, k_eff, iters, G.data(), u.data(), cols.data(), raw);
     return RK_OK;
+    RK_GUARD_END(who)
 }
 
 // The drivers' call: as rk_kr_distances_batch, with the raw output and the two info words on the host at the end
 extern "C" int rk_epca_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t k, uint32_t iters, double *raw, uint32_t *info) {
     const char *who = "rk_epca_batch";
-    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
-    if (int rc = epca_args(who, t, n_samples, k, iters)) return rc;
+    if (int rc = batch_handles(who, db, t)) return rc;
+    EpcaPlan p;
+    if (int rc = epca_prepare(who, t, n_samples, k, iters, p)) return rc;
     if (!raw || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
-    if (t->B != db->info.n_branches || t->device != db->info.device)
-        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
-    const uint64_t need = rk_epca_work_bytes(t, n_samples, k), words = rk_masses_samples_words(t->B, n_samples);
-    if (!need) return RK_ERR_INVALID;
-    if (!words) return fail(RK_ERR_INVALID, "%s: n_samples=%u on %u branches is beyond the limits of a sample mass buffer", who, n_samples, t->B);
-    std::lock_guard<std::mutex> lock(db->host_mutex);
-    if (!masses && (db->masses_samples != n_samples || !db->d_masses.p))
-        return fail(RK_ERR_INVALID, "%s: the handle holds the buffer of %u samples, not of %u (the last per-sample profile-only call leaves it)", who, db->masses_samples, n_samples);
-    HIP_TRY(hipSetDevice(db->info.device));
-    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
-    hipStream_t s = db->ws[0].stream;
-    GrowBuf work, d_out, d_in;
-    struct Free { GrowBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } free_all{work, d_out, d_in};
     const uint64_t raw_bytes = rk::epca_out_doubles(t->B, n_samples, k) * 8;  // the raw output, then the info words
-    if (int rc = work.reserve(need)) return rc;
-    if (int rc = d_out.reserve(raw_bytes + 8)) return rc;
-    const uint64_t *d_masses = db->d_masses.as<uint64_t>();
-    if (masses) {
-        if (int rc = d_in.reserve(words * 8)) return rc;
-        HIP_TRY(hipMemcpyAsync(d_in.p, masses, words * 8, hipMemcpyHostToDevice, s));
-        d_masses = d_in.as<uint64_t>();
-    }
-    uint32_t *d_info = (uint32_t *)((char *)d_out.p + raw_bytes);
-    if (int rc = rk_epca_device(t, n_samples, d_masses, k, iters, (double *)d_out.p, d_info, work.p, need, s)) return rc;
-    HIP_TRY(hipMemcpyAsync(raw, d_out.p, raw_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(info, d_info, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return RK_OK;
+    return samples_batch(who, db, n_samples, masses, p.bytes, raw_bytes + 8, [&](const uint64_t *d_masses, char *d_out, void *d_work, hipStream_t s) -> int {
+        uint32_t *d_info = (uint32_t *)(d_out + raw_bytes);
+        if (int rc = rk_epca_device(t, n_samples, d_masses, k, iters, (double *)d_out, d_info, d_work, p.bytes, s)) return rc;
+        HIP_TRY(hipMemcpyAsync(raw, d_out, raw_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(info, d_info, 8, hipMemcpyDeviceToHost, s));
+        return RK_OK;
+    });
 }
 
 extern "C" int rk_epca_finish_host(uint32_t n_branches, uint32_t n_samples, uint32_t k, const double *raw, double *eigenvalue, double *share, double *residual,
@@ -1066,9 +1008,7 @@ extern "C" int rk_edpl_host(uint32_t n_branches, const int32_t *parent, const fl
     if (rc || n_reads == 0) return rc;
     rk::TreeDist dist;
     rk::tree_dist_build(w, parent, branch_len, dist);
-    unsigned hw = std::thread::hardware_concurrency();
-    uint64_t T = n_threads ? n_threads : std::min(hw ? hw : 1u, 16u);
-    T = std::max<uint64_t>(1, std::min<uint64_t>({T, 16, (n_reads + 4095) / 4096}));
+    const uint64_t T = host_threads(n_threads, (n_reads + 4095) / 4096);
     return masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
         rk::edpl_range(dist, keep_at_most, n_reads * th / T, n_reads * (th + 1) / T, res->n_rows, res->branch, res->lwr, edpl);
     });
@@ -1097,20 +1037,15 @@ extern "C" int rk_tree_distance_host(uint32_t n_branches, const int32_t *parent,
 // Only n_rows, branch and lwr are uploaded; the buffers are allocated for the call and freed; it waits for the result.
 extern "C" int rk_edpl_batch(rk_db *db, const rk_tree *t, uint32_t keep_at_most, uint64_t n_reads, const rk_result *res, double *edpl) {
     const char *who = "rk_edpl_batch";
-    if (!db) return fail(RK_ERR_INVALID, "%s: null handle", who);
-    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = batch_handles(who, db, t)) return rc;
     int rc = edpl_args(who, keep_at_most, n_reads, res, edpl);
-    if (rc) return rc;
-    if (t->B != db->info.n_branches || t->device != db->info.device)
-        return fail(RK_ERR_INVALID, "%s: the tree has %u branches on device %d, the database %u on device %d", who, t->B, t->device, db->info.n_branches, db->info.device);
-    if (n_reads == 0) return RK_OK;
+    if (rc || n_reads == 0) return rc;
     std::lock_guard<std::mutex> lock(db->host_mutex);
-    HIP_TRY(hipSetDevice(db->info.device));
-    if (!db->ws[0].stream) HIP_TRY(hipStreamCreateWithFlags(&db->ws[0].stream, hipStreamNonBlocking));
-    hipStream_t s = db->ws[0].stream;
+    hipStream_t s;
+    if (int e = batch_stream(db, s)) return e;
     const uint64_t K = keep_at_most, chunk = std::min<uint64_t>(n_reads, RK_EDPL_CHUNK_READS);
-    GrowBuf d_in, d_out;
-    struct Free { GrowBuf &a, &b; ~Free() { a.release(); b.release(); } } free_all{d_in, d_out};
+    BatchBufs b;
+    GrowBuf &d_in = b.in, &d_out = b.out;
     const uint64_t branch_at = up256(chunk), lwr_at = branch_at + up256(chunk * K * 2);  // n_rows | branch | lwr
     if (int e = d_in.reserve(lwr_at + chunk * K * 8)) return e;
     if (int e = d_out.reserve(chunk * 8)) return e;

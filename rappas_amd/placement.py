@@ -758,6 +758,13 @@ def _samples_in(n_branches, n_samples, masses):
     return masses
 
 
+def _host_samples(parent, branch_len, masses, n_samples):
+    """what the sample-level host calls take in: (parent, branch_len, B, masses) as the C ABI reads them"""
+    parent, branch_len = _tree_arrays(parent, branch_len)
+    B = parent.shape[0]
+    return parent, branch_len, B, _samples_in(B, n_samples, masses)
+
+
 def tree_validate(parent, branch_len):
     """rk_tree_validate (no GPU): the checks of EdgeTree on a parent array (-1 = the root) and the lengths of the edges above the nodes;
     raises RkError (RK_ERR_INVALID and the message) for a tree the sample-level calls refuse"""
@@ -768,9 +775,7 @@ def tree_validate(parent, branch_len):
 def clade_masses_host(parent, masses, n_samples):
     """rk_clade_masses_host (no GPU): uint64 [n_samples, B], the sum of mass_q30 over every node's subtree for each sample of a sample
     mass buffer (with n_samples = 1 an ordinary mass buffer) -- the clade_mass_q30 column of hostio.masses_table"""
-    parent, _ = _tree_arrays(parent)
-    B = parent.shape[0]
-    masses = _samples_in(B, n_samples, masses)
+    parent, _, B, masses = _host_samples(parent, None, masses, n_samples)
     clade = np.zeros((n_samples, B), np.uint64)
     _lib.check(_lib.load().rk_clade_masses_host(B, _ptr(parent), n_samples, _ptr(masses), _ptr(clade)))
     return clade
@@ -780,9 +785,7 @@ def kr_distances_host(parent, branch_len, masses, n_samples, threads=0):
     """rk_kr_distances_host (no GPU): float64 [n_samples, n_samples], the pairwise Kantorovich-Rubinstein distances between the samples
     of a sample mass buffer on the tree (parent, branch_len) -- the bits EdgeTree.kr_distances gives on the device.  A sample without
     mass has a NaN row and column."""
-    parent, branch_len = _tree_arrays(parent, branch_len)
-    B = parent.shape[0]
-    masses = _samples_in(B, n_samples, masses)
+    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
     out = np.zeros((n_samples, n_samples), np.float64)
     _lib.check(_lib.load().rk_kr_distances_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), _ptr(out), threads))
     return out
@@ -797,9 +800,7 @@ def squash_host(parent, branch_len, masses, n_samples, threads=0):
     """rk_squash_host (no GPU): (merges, n_merges) -- the squash clustering of the samples of a sample mass buffer on the tree (parent,
     branch_len): a SQUASH_MERGE array of n_samples - 1 rows, of which the first n_merges are merges and the rest fillers -- the bits
     EdgeTree.squash gives on the device.  A sample without mass takes no part."""
-    parent, branch_len = _tree_arrays(parent, branch_len)
-    B = parent.shape[0]
-    masses = _samples_in(B, n_samples, masses)
+    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
     merges = np.zeros(max(n_samples - 1, 0), SQUASH_MERGE)
     n = C.c_uint32(0)
     _lib.check(_lib.load().rk_squash_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), _ptr(merges), C.byref(n), threads))
@@ -824,9 +825,7 @@ def _kmeans_seeds(seeds, k):
 def kmeans_host(parent, branch_len, masses, n_samples, k, max_rounds=100, seeds=None, centroids=True, threads=0):
     """rk_kmeans_host (no GPU): a KMeans of host arrays -- the phylogenetic k-means of the samples of a sample mass buffer on the tree
     (parent, branch_len), farthest-first seeds unless `seeds` gives k sample indices -- the bits EdgeTree.kmeans gives on the device."""
-    parent, branch_len = _tree_arrays(parent, branch_len)
-    B = parent.shape[0]
-    masses = _samples_in(B, n_samples, masses)
+    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
     seeds = _kmeans_seeds(seeds, k)
     kk = max(k, 0)
     assign, dist = np.zeros(n_samples, np.uint32), np.zeros(n_samples, np.float64)
@@ -852,9 +851,7 @@ def epca_host(parent, branch_len, masses, n_samples, k, iters, threads=0):
     """rk_epca_host (no GPU): (raw, info) -- the raw edge-PCA output of the samples of a sample mass buffer on the tree (parent, branch_len),
     float64 [1 + k * (3 + S + B)]: trace | lambda[k] | nn[k] | rr[k] | q[k][S] | w[k][B], and uint32 [2]: n_active, k_eff -- the bits
     EdgeTree.epca gives on the device.  epca_finish turns them into eigenvalues, projections and loadings."""
-    parent, branch_len = _tree_arrays(parent, branch_len)
-    B = parent.shape[0]
-    masses = _samples_in(B, n_samples, masses)
+    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
     raw = np.zeros(max(int(_lib.load().rk_epca_out_doubles(B, n_samples, k)), 1), np.float64)
     info = np.zeros(2, np.uint32)
     _lib.check(_lib.load().rk_epca_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), k, iters, _ptr(raw), _ptr(info), threads))
@@ -951,74 +948,78 @@ class EdgeTree:
         _lib.check(self._lib.rk_clade_masses_device(self.handle, n_samples, masses.data_ptr(), clade.data_ptr(), C.c_void_p(_stream(dev, stream))))
         return clade
 
-    def kr_work_bytes(self, n_samples):
-        need = int(self._lib.rk_kr_work_bytes(self.handle, n_samples))
+    def _need(self, fn, *args):
+        """the answer of a _work_bytes call, or the RkError of the shape it refuses"""
+        need = int(fn(self.handle, *args))
         if not need:
             raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
         return need
+
+    def _work(self, need, dev):
+        """the device workspace, grow-only"""
+        import torch
+        if self._work_buf is None or self._work_buf.numel() < need:
+            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        return self._work_buf
+
+    def _batch_masses(self, n_samples, masses):
+        """the host buffer of a _batch call as the C ABI reads it -- whole, the skipped-entries word with it -- or None: the one in the handle"""
+        if masses is None:
+            return None
+        masses = _samples_in(self.n_branches, n_samples, masses)
+        if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
+            raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        return masses
+
+    def kr_work_bytes(self, n_samples):
+        return self._need(self._lib.rk_kr_work_bytes, n_samples)
 
     def kr_distances(self, masses, n_samples, stream=None):
         """rk_kr_distances_device: float64 tensor [n_samples, n_samples], written; asynchronous on the stream"""
         import torch
         dev = self._masses(masses, n_samples)
-        need = self.kr_work_bytes(n_samples)
-        if self._work_buf is None or self._work_buf.numel() < need:
-            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        work = self._work(self.kr_work_bytes(n_samples), dev)
         out = torch.empty((n_samples, n_samples), dtype=torch.float64, device=dev)
-        _lib.check(self._lib.rk_kr_distances_device(self.handle, n_samples, masses.data_ptr(), out.data_ptr(), self._work_buf.data_ptr(),
-                                                    self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+        _lib.check(self._lib.rk_kr_distances_device(self.handle, n_samples, masses.data_ptr(), out.data_ptr(), work.data_ptr(),
+                                                    work.numel(), C.c_void_p(_stream(dev, stream))))
         return out
 
     def kr_distances_batch(self, db, n_samples, masses=None):
         """rk_kr_distances_batch, the drivers' call: float64 array [n_samples, n_samples] on the host from a host sample mass buffer --
         or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through
         rk_kr_distances_device on db's device; returns when the matrix is there"""
-        if masses is not None:
-            masses = _samples_in(self.n_branches, n_samples, masses)
-            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
-                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        masses = self._batch_masses(n_samples, masses)
         out = np.zeros((n_samples, n_samples), np.float64)
         _lib.check(self._lib.rk_kr_distances_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(out)))
         return out
 
     def squash_work_bytes(self, n_samples):
-        need = int(self._lib.rk_squash_work_bytes(self.handle, n_samples))
-        if not need:
-            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
-        return need
+        return self._need(self._lib.rk_squash_work_bytes, n_samples)
 
     def squash(self, masses, n_samples, stream=None):
         """rk_squash_device: (merges, n_merges) as device tensors, written -- uint8 [n_samples - 1, 24], the rows of SQUASH_MERGE
         (merges.cpu().numpy().view(SQUASH_MERGE)), and int32 [1]; asynchronous on the stream"""
         import torch
         dev = self._masses(masses, n_samples)
-        need = self.squash_work_bytes(n_samples)
-        if self._work_buf is None or self._work_buf.numel() < need:
-            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        work = self._work(self.squash_work_bytes(n_samples), dev)
         merges = torch.empty((n_samples - 1, SQUASH_MERGE.itemsize), dtype=torch.uint8, device=dev)
         n_merges = torch.empty((1,), dtype=torch.int32, device=dev)
-        _lib.check(self._lib.rk_squash_device(self.handle, n_samples, masses.data_ptr(), merges.data_ptr(), n_merges.data_ptr(), self._work_buf.data_ptr(),
-                                              self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+        _lib.check(self._lib.rk_squash_device(self.handle, n_samples, masses.data_ptr(), merges.data_ptr(), n_merges.data_ptr(), work.data_ptr(),
+                                              work.numel(), C.c_void_p(_stream(dev, stream))))
         return merges, n_merges
 
     def squash_batch(self, db, n_samples, masses=None):
         """rk_squash_batch, the drivers' call: (merges, n_merges) on the host, as squash_host gives them, from a host sample mass buffer --
         or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_squash_device
         on db's device; returns when the rows are there"""
-        if masses is not None:
-            masses = _samples_in(self.n_branches, n_samples, masses)
-            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
-                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        masses = self._batch_masses(n_samples, masses)
         merges = np.zeros(max(n_samples - 1, 0), SQUASH_MERGE)
         n = C.c_uint32(0)
         _lib.check(self._lib.rk_squash_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(merges), C.byref(n)))
         return merges, int(n.value)
 
     def kmeans_work_bytes(self, n_samples, k):
-        need = int(self._lib.rk_kmeans_work_bytes(self.handle, n_samples, k))
-        if not need:
-            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
-        return need
+        return self._need(self._lib.rk_kmeans_work_bytes, n_samples, k)
 
     def kmeans(self, masses, n_samples, k, max_rounds=100, seeds=None, centroids=False, stream=None):
         """rk_kmeans_device: a KMeans of device tensors, written -- assign int32 [S] (the bits are unsigned: -1 is KMEANS_NONE), dist
@@ -1028,8 +1029,7 @@ class EdgeTree:
         dev = self._masses(masses, n_samples)
         need = self.kmeans_work_bytes(n_samples, k)
         seeds = _kmeans_seeds(seeds, k)
-        if self._work_buf is None or self._work_buf.numel() < need:
-            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        work = self._work(need, dev)
         assign = torch.empty((n_samples,), dtype=torch.int32, device=dev)
         dist = torch.empty((n_samples,), dtype=torch.float64, device=dev)
         sizes = torch.empty((k,), dtype=torch.int32, device=dev)
@@ -1037,18 +1037,15 @@ class EdgeTree:
         info = torch.empty((4,), dtype=torch.int32, device=dev)
         cen = torch.empty((k, 2, self.n_branches), dtype=torch.float64, device=dev) if centroids else None
         _lib.check(self._lib.rk_kmeans_device(self.handle, n_samples, masses.data_ptr(), k, max_rounds, None if seeds is None else _ptr(seeds), assign.data_ptr(),
-                                              dist.data_ptr(), sizes.data_ptr(), within.data_ptr(), info.data_ptr(), _dp(cen), self._work_buf.data_ptr(),
-                                              self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+                                              dist.data_ptr(), sizes.data_ptr(), within.data_ptr(), info.data_ptr(), _dp(cen), work.data_ptr(),
+                                              work.numel(), C.c_void_p(_stream(dev, stream))))
         return KMeans(assign, dist, sizes, within, info, cen)
 
     def kmeans_batch(self, db, n_samples, k, max_rounds=100, masses=None, seeds=None, centroids=False):
         """rk_kmeans_batch, the drivers' call: a KMeans of host arrays, as kmeans_host gives them, from a host sample mass buffer -- or,
         masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_kmeans_device on
         db's device; returns when they are there"""
-        if masses is not None:
-            masses = _samples_in(self.n_branches, n_samples, masses)
-            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
-                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        masses = self._batch_masses(n_samples, masses)
         seeds = _kmeans_seeds(seeds, k)
         assign, dist = np.zeros(n_samples, np.uint32), np.zeros(n_samples, np.float64)
         sizes, within, info = np.zeros(k, np.uint32), np.zeros(k, np.float64), np.zeros(4, np.uint32)
@@ -1059,33 +1056,25 @@ class EdgeTree:
         return KMeans(assign, dist, sizes, within, info, cen)
 
     def epca_work_bytes(self, n_samples, k):
-        need = int(self._lib.rk_epca_work_bytes(self.handle, n_samples, k))
-        if not need:
-            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
-        return need
+        return self._need(self._lib.rk_epca_work_bytes, n_samples, k)
 
     def epca(self, masses, n_samples, k, iters, stream=None):
         """rk_epca_device: (raw, info) as device tensors, written -- float64 [1 + k * (3 + S + B)] and int32 [2] (n_active, k_eff), as
         epca_host gives them; asynchronous on the stream.  epca_finish(B, S, k, raw, info) downloads and finishes them."""
         import torch
         dev = self._masses(masses, n_samples)
-        need = self.epca_work_bytes(n_samples, k)
-        if self._work_buf is None or self._work_buf.numel() < need:
-            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        work = self._work(self.epca_work_bytes(n_samples, k), dev)
         raw = torch.empty((_epca_out(self.n_branches, n_samples, k),), dtype=torch.float64, device=dev)
         info = torch.empty((2,), dtype=torch.int32, device=dev)
-        _lib.check(self._lib.rk_epca_device(self.handle, n_samples, masses.data_ptr(), k, iters, raw.data_ptr(), info.data_ptr(), self._work_buf.data_ptr(),
-                                            self._work_buf.numel(), C.c_void_p(_stream(dev, stream))))
+        _lib.check(self._lib.rk_epca_device(self.handle, n_samples, masses.data_ptr(), k, iters, raw.data_ptr(), info.data_ptr(), work.data_ptr(),
+                                            work.numel(), C.c_void_p(_stream(dev, stream))))
         return raw, info
 
     def epca_batch(self, db, n_samples, k, iters, masses=None):
         """rk_epca_batch, the drivers' call: (raw, info) on the host, as epca_host gives them, from a host sample mass buffer -- or, masses
         None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_epca_device on db's
         device; returns when they are there"""
-        if masses is not None:
-            masses = _samples_in(self.n_branches, n_samples, masses)
-            if masses.shape[0] != masses_samples_words(self.n_branches, n_samples):
-                raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
+        masses = self._batch_masses(n_samples, masses)
         raw = np.zeros(max(int(self._lib.rk_epca_out_doubles(self.n_branches, n_samples, k)), 1), np.float64)
         info = np.zeros(2, np.uint32)
         _lib.check(self._lib.rk_epca_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), k, iters, _ptr(raw), _ptr(info)))
