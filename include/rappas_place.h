@@ -646,6 +646,64 @@ int rk_kmeans_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint6
                     uint32_t *assign, double *dist, uint32_t *sizes, double *within, uint32_t *info, double *centroids);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Per-sample phylogenetic diversity of the samples of a sample mass buffer (what `guppy fpd` computes from jplace files): phylogenetic
+ * diversity (PD), balance-weighted PD, quadratic entropy and phylogenetic entropy of every sample, and the one-parameter families
+ * of McCoy & Matsen.  The reference has no counterpart.  Fixed so that every implementation gives the same bits; c = c_s(x), m =
+ * m_s(x), T = T_s and h[x] are those of the KR block, all binary64 with IEEE conversion, *, +, -, /, no contraction.
+ *   Limits              1 <= S <= 65535, 0 <= n_theta <= RK_DIVERSITY_MAX_THETA, every theta finite and in [0, 8].
+ *   Half-edges          every node x other than the root gives two half-edges of length h[x]: the proximal half with distal mass
+ *                       a = c, the distal half with a = c - m (integers until the one division).  The root contributes nothing
+ *                       (h[root] = 0: its terms are zeros).  For a half-edge:
+ *                           D = (double)a / (double)T        E = 1.0 - D        M = 2.0 * (E < D ? E : D)
+ *   Indicators          tested on the integers ((T - 1) / T rounds to 1.0 once T >= 2^54): rooted = a > 0; split = a > 0 && a < T.
+ *                       A term whose indicator is false is +0.0; it is still added, so no control flow changes the order of the sum.
+ *   Functions           lg(x) = rk_log2(x), pw(x, theta) = rk_exp2(theta * rk_log2(x)) for x > 0: the project's own binary logarithm
+ *                       and exponential (rappas_amd/csrc/rk_divmath.h), written with + - * /, comparisons and integer operations
+ *                       on the bits alone -- the platforms' log and pow round differently.  rk_log2 is exact on powers of two
+ *                       (rk_log2(1.0) = +0.0, rk_log2(0.5) = -1.0); rk_exp2(+-0.0) = 1.0 exactly, so theta = 0 reproduces the plain
+ *                       column.  For x <= 0 -- reachable only for M, where E rounds to 0 -- pw(x, theta) is 1.0 for theta == 0 and
+ *                       +0.0 otherwise (the limit).  Accuracy against exact values: profiles/diversity_math_accuracy.txt.
+ *   Fixed columns       each the sum of its term over both half-edges of every node:
+ *                           0 rooted_pd      rooted ? h : 0
+ *                           1 pd             split ? h : 0                       (unrooted PD)
+ *                           2 bwpd           split ? h * M : 0                   (guppy's awpd; theta = 1 without a transcendental)
+ *                           3 quadratic      split ? h * (D * E) : 0
+ *                           4 phylo_entropy  rooted ? h * (-(D * lg(D)) * RK_LN2) : 0,  RK_LN2 = 0x1.62e42fefa39efp-1
+ *   Columns per theta   for i < n_theta:  5 + 2i rooted_pd_theta = rooted ? h * pw(D, theta_i) : 0;  6 + 2i bwpd_theta = split ? h *
+ *                       pw(M, theta_i) : 0.
+ *   Output              [S][RK_DIVERSITY_FIXED + 2 * n_theta] doubles, WRITTEN, not added into.
+ *   Order of the sum    a per-sample reduction has no pairs to spread over a device, so the definition carries the parallelism:
+ *                       nodes in chunks of RK_KR_CHUNK ids; within a chunk RK_DIVERSITY_LANES = 256 lane partials, lane j starts
+ *                       at +0.0 and takes the nodes base + j, base + j + 256, ... in ascending order with acc = (acc +
+ *                       term_proximal) + term_distal; the partials are folded by halving, stride 128, 64, ..., 1: p[j] = p[j] +
+ *                       p[j + stride]; a column is chunk_0, then + chunk_1, ... in chunk order.
+ *   Sample without mass T = 0: its whole row is the quiet NaN 0x7FF8000000000000.
+ *   rk_diversity_work_bytes  bytes of the caller-owned device workspace: the clade sums and the chunk partials; 0 and a message on a
+ *                            bad argument.
+ *   rk_diversity_device      the clade sums, the measure kernel, an in-order reduce over the chunks: plain launches in stream order,
+ *                            no atomics, no host synchronisation, no grid-wide wait.  `theta` is a host array, read during the
+ *                            call.  A bad theta (NaN, negative, above 8), n_theta above 8 or a NULL theta with n_theta > 0 is
+ *                            RK_ERR_INVALID on the host.  Otherwise the argument rules of rk_kmeans_device: RK_ERR_INVALID and a
+ *                            message, nothing launched, nothing written.  Asynchronous on `stream`.
+ *   rk_diversity_host        the same bits in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16.
+ *   rk_diversity_batch       the drivers' call, with the contract of rk_kmeans_batch: masses NULL = the buffer the last per-sample
+ *                            profile-only call left in the handle.  The table on the host; returns when it is filled.
+ *   rk_diversity_math_host   for tests: out[i] = rk_log2(x[i]) (op 0), rk_exp2(x[i]) (op 1) or pw(x[i], y[i]) (op 2; y is read by
+ *                            op 2 only).
+ * Added without a bump of RK_VERSION (no existing struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_DIVERSITY_FIXED 5u
+#define RK_DIVERSITY_MAX_THETA 8u
+#define RK_DIVERSITY_LANES 256u
+uint64_t rk_diversity_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t n_theta);
+int rk_diversity_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t n_theta, const double *theta /* host */, double *d_out,
+                        void *d_work, uint64_t work_bytes, void *stream);
+int rk_diversity_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t n_theta,
+                      const double *theta, double *out, uint32_t n_threads);
+int rk_diversity_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t n_theta, const double *theta, double *out);
+int rk_diversity_math_host(uint32_t op /* 0 log2, 1 exp2, 2 pw */, uint64_t n, const double *x, const double *y, double *out);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Edge principal components of the samples of a sample mass buffer (Matsen & Evans; what `guppy epca` / `gappa edgepca` compute
  * from jplace files): for every edge the difference between the mass on its two sides, per sample, and the principal components of
  * that S x B matrix -- the projections of the samples and the loadings of the edges.  The reference has no counterpart.  Fixed so

@@ -167,6 +167,11 @@ EXPORTS = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rk_kmeans_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "rk_diversity_work_bytes": (C.c_uint64, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rk_diversity_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rk_diversity_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rk_diversity_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rk_diversity_math_host": (C.c_int, [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_epca_out_doubles": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "rk_epca_work_bytes": (C.c_uint64, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "rk_epca_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),

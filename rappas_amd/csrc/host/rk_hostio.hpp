@@ -522,6 +522,34 @@ inline std::string kmeans_table(const std::vector<std::string> &names, uint32_t 
     return out + "#samples_without_mass\t" + std::to_string(S - info[1]) + "\n";
 }
 
+// The text `--diversity FILE` writes: `#diversity<TAB>S<TAB>n_theta`; a line `#columns` with rooted_pd, pd, bwpd, quadratic,
+// phylo_entropy and, per theta, rooted_pd_<theta> and bwpd_<theta> (theta as `%.17g`); one line per sample in sample order -- its
+// name and its values, `%.17g` (a NaN as `nan`, whatever its sign), tab-separated --; `#samples_without_mass<TAB>n`, n the samples
+// whose row is NaN.  `values` [S][5 + 2 n_theta] is what rk_diversity_batch leaves.  The twin of hostio.diversity_table (byte-identical).
+inline std::string diversity_table(const std::vector<std::string> &names, const std::vector<double> &theta, const double *values) {
+    const size_t S = names.size(), C = 5 + 2 * theta.size();
+    std::string out = "#diversity\t" + std::to_string(S) + "\t" + std::to_string(theta.size()) + "\n#columns\trooted_pd\tpd\tbwpd\tquadratic\tphylo_entropy";
+    char buf[96];
+    for (double t : theta) {
+        snprintf(buf, sizeof(buf), "\trooted_pd_%.17g\tbwpd_%.17g", t, t);
+        out += buf;
+    }
+    out += "\n";
+    size_t without = 0;
+    for (size_t s = 0; s < S; s++) {
+        out += names[s];
+        for (size_t i = 0; i < C; i++) {
+            const double v = values[s * C + i];
+            if (v != v) { out += "\tnan"; continue; }
+            snprintf(buf, sizeof(buf), "\t%.17g", v);
+            out += buf;
+        }
+        out += "\n";
+        without += values[s * C] != values[s * C];
+    }
+    return out + "#samples_without_mass\t" + std::to_string(without) + "\n";
+}
+
 // The text `--epca FILE` writes, every double as `%.17g`: `#epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff<TAB>iters`; the lines
 // `#eigenvalue`, `#share`, `#residual` with k values each; `#projections` and a line per sample (its name and k values); `#loadings`
 // and a line per node id (the id and k values); `#samples_without_mass<TAB>n`.  The arrays are what rk_epca_finish_host leaves:

@@ -50,6 +50,10 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                 most N rounds (1..1024, default 100) --, found on the device: a line #kmeans<TAB>S<TAB>k<TAB>k_eff<TAB>n_active\n"
                  "                 <TAB>rounds<TAB>converged, #clusters and a line j<TAB>size<TAB>within per cluster, #samples and a line\n"
                  "                 name<TAB>cluster<TAB>distance per sample (- and 0 without mass), and a last line #samples_without_mass<TAB>n)\n"
+                 "                [--diversity FILE [--diversity-theta T1,T2,...]]  (with --sample-sep: the phylogenetic diversity of every sample, what\n"
+                 "                 guppy fpd reports, summed on the device: a line #diversity<TAB>S<TAB>n_theta, a line #columns with rooted_pd, pd,\n"
+                 "                 bwpd, quadratic, phylo_entropy and, per theta (at most 8 exponents in 0..8), rooted_pd_<theta> and bwpd_<theta>, a\n"
+                 "                 line name<TAB>values (%.17g) per sample (nan without mass), and a last line #samples_without_mass<TAB>n)\n"
                  "                [--epca FILE [--epca-components K] [--epca-iters N]]  (with --sample-sep: the edge principal components of the samples --\n"
                  "                 the difference between the mass on the two sides of every edge, centred --, found on the device: K components\n"
                  "                 (1..8, default 5) after N iterations (1..10000, default 200): a line #epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff\n"
@@ -71,7 +75,7 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
 
 int main(int argc, char **argv) {
     try {
-        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path, epca_path, edpl_path, kmeans_path;
+        std::string jsondb, uniondb, dbimage, save_image, fasta, out, amb = "mean", logs, strand_name = "fwd", masses_path, masses_only_path, sample_sep, kr_path, squash_path, epca_path, edpl_path, kmeans_path, diversity_path, diversity_theta;
         bool logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false;
         unsigned threads = 0;
         uint32_t keep_at_most = 7, epca_k = 5, epca_iters = 200, kmeans_k = 0, kmeans_rounds = 100;
@@ -107,6 +111,8 @@ int main(int argc, char **argv) {
             else if (a == "--kmeans") kmeans_path = val();
             else if (a == "--kmeans-k") kmeans_k = (uint32_t)std::stoul(val());
             else if (a == "--kmeans-rounds") kmeans_rounds = (uint32_t)std::stoul(val());
+            else if (a == "--diversity") diversity_path = val();
+            else if (a == "--diversity-theta") diversity_theta = val();
             else if (a == "--epca-components") epca_k = (uint32_t)std::stoul(val());
             else if (a == "--epca-iters") epca_iters = (uint32_t)std::stoul(val());
             else if (a == "--sample-sep") { sample_sep = val(); if (sample_sep.size() != 1) throw std::runtime_error("--sample-sep takes one character"); }
@@ -372,6 +378,25 @@ int main(int argc, char **argv) {
             std::cerr << "rk_place: --kmeans needs --kmeans-k in 1..64; --kmeans-rounds must be in 1..1024\n";
             return 2;
         }
+        if (!diversity_path.empty() && sample_sep.empty()) {
+            std::cerr << "rk_place: --diversity measures the samples of one run: it needs --sample-sep (with --masses or --masses-only)\n";
+            return 2;
+        }
+        std::vector<double> thetas;  // --diversity-theta: numbers separated by commas
+        bool thetas_ok = true;
+        for (size_t at = 0; !diversity_theta.empty() && at <= diversity_theta.size();) {
+            const size_t comma = std::min(diversity_theta.find(',', at), diversity_theta.size());
+            const std::string item = diversity_theta.substr(at, comma - at);
+            char *end = nullptr;
+            const double v = strtod(item.c_str(), &end);
+            thetas_ok = thetas_ok && !item.empty() && *end == 0 && v >= 0.0 && v <= 8.0;
+            thetas.push_back(v);
+            at = comma + 1;
+        }
+        if (!thetas_ok || thetas.size() > RK_DIVERSITY_MAX_THETA) {
+            std::cerr << "rk_place: --diversity-theta takes at most 8 numbers in 0..8, separated by commas\n";
+            return 2;
+        }
         const bool only_convert = !save_image.empty() && fasta.empty() && out.empty() && !masses_only;
         if (n_sources != 1 || (!only_convert && (fasta.empty() || (out.empty() && !masses_only))) || (only_convert && !dbimage.empty())) return usage();
         uint32_t amb_mode;
@@ -401,8 +426,9 @@ int main(int argc, char **argv) {
         // --squash: the same, through rk_squash_batch; `host_words` is the host's copy either way (it tells which samples hold mass)
         // --epca: the same, through rk_epca_batch and rk_epca_finish_host (one sample alone has no components: it is only counted)
         // --kmeans: the same, through rk_kmeans_batch
+        // --diversity: the same, through rk_diversity_batch
         auto write_kr = [&](const rkh::Tree &t, const rkh::SampleMembers &sm, const uint64_t *words, const uint64_t *host_words) {
-            if (kr_path.empty() && squash_path.empty() && epca_path.empty() && kmeans_path.empty()) return;
+            if (kr_path.empty() && squash_path.empty() && epca_path.empty() && kmeans_path.empty() && diversity_path.empty()) return;
             const uint32_t B = (uint32_t)t.nodes.size(), S = (uint32_t)sm.names.size();
             std::vector<int32_t> parent(B);
             std::vector<float> bl(B);
@@ -460,6 +486,14 @@ int main(int argc, char **argv) {
                 std::ofstream mf(kmeans_path, std::ios::binary);
                 if (!mf) throw std::runtime_error("cannot write " + kmeans_path);
                 mf << rkh::kmeans_table(sm.names, k, assign.data(), dist.data(), sizes.data(), within.data(), info);
+            }
+            if (!diversity_path.empty()) {
+                std::vector<double> values((size_t)S * (RK_DIVERSITY_FIXED + 2 * thetas.size()));
+                if (rk_diversity_batch(kr_db, kt, S, words, (uint32_t)thetas.size(), thetas.empty() ? nullptr : thetas.data(), values.data()) != RK_OK)
+                    throw std::runtime_error(std::string("rk_diversity_batch: ") + rk_last_error());
+                std::ofstream df(diversity_path, std::ios::binary);
+                if (!df) throw std::runtime_error("cannot write " + diversity_path);
+                df << rkh::diversity_table(sm.names, thetas, values.data());
             }
         };
         // --edpl: the EDPL of every unique read from the results on the host, over the database's tree as --epca builds it, through

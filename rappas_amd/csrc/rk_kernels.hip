@@ -26,6 +26,7 @@
 #include "rk_epca.h"
 #include "rk_edpl.h"
 #include "rk_kmeans.h"
+#include "rk_diversity.h"
 
 #include <type_traits>
 #ifndef RK_ROW_NT

@@ -2,7 +2,8 @@
 // rk_tree_validate / rk_tree_create, and the host twins of clade_masses_kernel, kr_pairs_kernel, the squash kernels (rk_samples.h) and
 // the edge-PCA kernels (rk_epca.h) behind rk_clade_masses_host, rk_kr_distances_host, rk_squash_host and rk_epca_host, and the
 // distance tables of a tree with the twin of edpl_kernel (rk_edpl.h) behind rk_edpl_host and rk_tree_distance_host, and the twin of
-// the k-means kernels (rk_kmeans.h) behind rk_kmeans_host.  Header-only,
+// the k-means kernels (rk_kmeans.h) behind rk_kmeans_host, and the twin of the diversity kernels (rk_diversity.h;
+// DESIGN.md 4.14) behind rk_diversity_host.  Header-only,
 // plain C++, like rk_masses_host.h.  Not part of the C ABI.
 //
 // The KR distance is written as include/rappas_place.h defines it, term by term and in the order fixed there, so that the device and
@@ -13,6 +14,8 @@
 #include <cstdio>
 #include <utility>
 #include <vector>
+
+#include "rk_divmath.h"
 
 namespace rk {
 
@@ -603,6 +606,63 @@ inline void kmeans_rounds(uint32_t B, uint32_t S, uint32_t k, uint32_t k_eff, ui
                 o.centroids[(j * 2) * B + x] = cu[j * B + x];
                 o.centroids[(j * 2 + 1) * B + x] = cv[j * B + x];
             }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-sample diversity measures (include/rappas_place.h holds the definition): the host twin of the kernels of
+// rk_diversity.h.  The terms are those of rk_divmath.h, the text the kernel compiles; the order of the sum is written out here.
+// ------------------------------------------------------------------------------------------------
+// The row of one sample from its masses and clade sums: per chunk of KR_CHUNK ids DIVERSITY_LANES lane partials, lane j over the
+// nodes base + j, base + j + 256, ..., folded by halving; the chunks in order, the first one as it is.  T == 0: the NaN row.
+template <uint32_t NT>
+inline void diversity_row(uint32_t B, uint32_t root, const uint64_t *mass, const uint64_t *c, const double *h, const double *theta, double *out) {
+    constexpr uint32_t C = DIVERSITY_FIXED + 2 * NT;
+    const uint64_t T = c[root];
+    if (T == 0) {
+        for (uint32_t i = 0; i < C; i++) out[i] = divmath_double(DIVERSITY_NAN);
+        return;
+    }
+    std::vector<double> lanes((size_t)DIVERSITY_LANES * C);
+    for (uint32_t x0 = 0; x0 < B; x0 += KR_CHUNK) {
+        const uint32_t x1 = x0 + KR_CHUNK < B ? x0 + KR_CHUNK : B;
+        for (uint32_t j = 0; j < DIVERSITY_LANES; j++) {
+            double *acc = lanes.data() + (size_t)j * C;
+            for (uint32_t i = 0; i < C; i++) acc[i] = 0.0;
+            for (uint32_t x = x0 + j; x < x1; x += DIVERSITY_LANES) diversity_node<NT>(c[x], mass[x], T, h[x], theta, acc);
+        }
+        for (uint32_t stride = DIVERSITY_LANES / 2; stride > 0; stride >>= 1)
+            for (uint32_t j = 0; j < stride; j++)
+                for (uint32_t i = 0; i < C; i++) lanes[(size_t)j * C + i] = lanes[(size_t)j * C + i] + lanes[(size_t)(j + stride) * C + i];
+        for (uint32_t i = 0; i < C; i++) out[i] = x0 == 0 ? lanes[i] : out[i] + lanes[i];
+    }
+}
+
+inline void diversity_sample(uint32_t B, uint32_t root, const uint64_t *mass, const uint64_t *c, const double *h, uint32_t n_theta, const double *theta, double *out) {
+    switch (n_theta) {
+    case 0: return diversity_row<0>(B, root, mass, c, h, theta, out);
+    case 1: return diversity_row<1>(B, root, mass, c, h, theta, out);
+    case 2: return diversity_row<2>(B, root, mass, c, h, theta, out);
+    case 3: return diversity_row<3>(B, root, mass, c, h, theta, out);
+    case 4: return diversity_row<4>(B, root, mass, c, h, theta, out);
+    case 5: return diversity_row<5>(B, root, mass, c, h, theta, out);
+    case 6: return diversity_row<6>(B, root, mass, c, h, theta, out);
+    case 7: return diversity_row<7>(B, root, mass, c, h, theta, out);
+    default: return diversity_row<8>(B, root, mass, c, h, theta, out);
+    }
+}
+
+// what every diversity call tests of its thetas; 0, or -1 with a message
+inline int diversity_theta_args(const char *who, uint32_t n_theta, const double *theta, char *msg, size_t msg_len) {
+    if (n_theta && !theta) {
+        snprintf(msg, msg_len, "%s: null theta array with n_theta=%u", who, n_theta);
+        return -1;
+    }
+    for (uint32_t i = 0; i < n_theta; i++)
+        if (!(theta[i] >= 0.0 && theta[i] <= 8.0)) {
+            snprintf(msg, msg_len, "%s: theta[%u]=%g must be in 0..8", who, i, theta[i]);
+            return -1;
+        }
+    return 0;
 }
 
 }  // namespace rk

@@ -3,13 +3,14 @@
 // _batch), the squash clustering over it (rk_squash_device / _host / _batch) and the edge principal components (rk_epca_device / _host /
 // _batch / _finish_host) and the per-read EDPL (rk_edpl_device / _host / _batch, rk_tree_distance_host)
 // and the phylogenetic k-means of the samples (rk_kmeans_device / _host / _batch)
-// -- over the kernels of rk_samples.h, rk_epca.h, rk_edpl.h and rk_kmeans.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
+// and the per-sample diversity measures (rk_diversity_device / _host / _batch, rk_diversity_math_host)
+// -- over the kernels of rk_samples.h, rk_epca.h, rk_edpl.h, rk_kmeans.h and rk_diversity.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
 // scratch, and only the _batch calls touch a database handle.
-// What the analyses share exists once, ahead of them: the range tests (samples_range, squash_range, kmeans_range, epca_range), which
+// What the analyses share exists once, ahead of them: the range tests (samples_range, squash_range, kmeans_range, diversity_range, epca_range), which
 // the _host calls and the prepare step of every analysis read; the prepare step (tests, then the workspace plan, carved by Carve and
 // measured by plan_fits), which _work_bytes and _device read; the workspace test of a device call (work_args); the tile grid of the two S x S matrices
 // (launch_tiles); what the four host calls over the KR profiles start from (HostProfiles) and the thread count of every host call
-// (host_threads); the frame of the four _batch calls (samples_batch) over what rk_edpl_batch shares with them (batch_handles,
+// (host_threads); the frame of the five _batch calls (samples_batch) over what rk_edpl_batch shares with them (batch_handles,
 // batch_stream, BatchBufs).  An analysis is a plan, a launch function, a host body and a few lines for each of its entry points.
 #pragma once
 
@@ -216,7 +217,7 @@ struct BatchBufs {
     ~BatchBufs() { work.release(); out.release(); in.release(); }
 };
 
-// The frame of the four _batch calls over a sample mass buffer (the caller has tested its arguments): the buffer on the host -- or,
+// The frame of the five _batch calls over a sample mass buffer (the caller has tested its arguments): the buffer on the host -- or,
 // masses == NULL, the one the last per-sample profile-only call (rk_place_batch_masses_samples, rk_place_batch_packed_masses_samples)
 // left on the device in the handle --, a workspace of `need` bytes and `out_bytes` for the outputs on the device;
 // queue(d_masses, d_out, d_work, stream) queues the device call and the downloads of its outputs, and the frame waits for them.
@@ -767,6 +768,152 @@ extern "C" int rk_kmeans_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, 
         HIP_TRY(hipMemcpyAsync(info, base + info_at, 16, hipMemcpyDeviceToHost, s));
         return RK_OK;
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-sample diversity measures: rk_diversity_work_bytes / _device / _host / _batch, rk_diversity_math_host.
+// ------------------------------------------------------------------------------------------------
+static_assert(RK_DIVERSITY_FIXED == rk::DIVERSITY_FIXED && RK_DIVERSITY_MAX_THETA == rk::DIVERSITY_MAX_THETA && RK_DIVERSITY_LANES == rk::DIVERSITY_LANES,
+              "one set of constants for the header, the host twin and the kernels");
+
+// The workspace of rk_diversity_device: clade[S][B] (64-bit) | part[S][chunks][5 + 2 n_theta]
+struct DiversityPlan {
+    uint32_t n_chunks, n_cols;
+    uint64_t clade_at, part_at, bytes;
+};
+static int diversity_range(const char *who, uint32_t S, uint32_t n_theta) {
+    if (int rc = samples_range(who, S)) return rc;
+    if (n_theta > RK_DIVERSITY_MAX_THETA) return fail(RK_ERR_INVALID, "%s: n_theta=%u must be in 0..%u", who, n_theta, RK_DIVERSITY_MAX_THETA);
+    return RK_OK;
+}
+// the caller's thetas, on the host: finite and in 0..8
+static int diversity_theta_args(const char *who, uint32_t n_theta, const double *theta) {
+    return rk::diversity_theta_args(who, n_theta, theta, g_err, sizeof(g_err)) ? RK_ERR_INVALID : RK_OK;
+}
+// the tests of rk_diversity_work_bytes and rk_diversity_device, and the plan
+static int diversity_prepare(const char *who, const rk_tree *t, uint32_t S, uint32_t n_theta, DiversityPlan &p) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = diversity_range(who, S, n_theta)) return rc;
+    Carve c;
+    p.n_chunks = (t->B + RK_KR_CHUNK - 1) / RK_KR_CHUNK;
+    p.n_cols = RK_DIVERSITY_FIXED + 2 * n_theta;
+    p.clade_at = c.take((uint64_t)S * t->B * 8);
+    p.part_at = c.take((uint64_t)S * p.n_chunks * p.n_cols * 8);
+    p.bytes = c.total();
+    return plan_fits(who, t, S, p.bytes);
+}
+
+extern "C" uint64_t rk_diversity_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t n_theta) {
+    DiversityPlan p;
+    return diversity_prepare("rk_diversity_work_bytes", t, n_samples, n_theta, p) ? 0 : p.bytes;
+}
+
+// The launches behind rk_diversity_device.  `steps` (developer builds, scripts/diversity_rate.py): bit 0 the clade sums, 1 the measure
+// kernel, 2 its reduce.
+static int diversity_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, uint32_t n_theta, const double *theta, double *d_out, void *d_work,
+                            const DiversityPlan &p, hipStream_t s, unsigned steps = 7) {
+    const uint32_t B = t->B;
+    u64 *clade = (u64 *)((char *)d_work + p.clade_at);
+    double *part = (double *)((char *)d_work + p.part_at);
+    const u64 W = (u64)rk_masses_words(B);
+    if (steps & 1) {
+        hipLaunchKernelGGL(clade_masses_kernel, dim3(S), dim3(256), 0, s, B, W, t->node_at, t->end_at, t->span_node, t->span_end, t->span_off, (const u64 *)d_masses, clade);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 2) {
+        DiversityThetas th{};
+        for (uint32_t i = 0; i < n_theta; i++) th.v[i] = theta[i];
+        auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(p.n_chunks, S), dim3(DIVERSITY_LANES), 0, s, B, W, t->root, p.n_chunks, th, (const u64 *)d_masses, (const u64 *)clade, t->h, part);
+        };
+        switch (n_theta) {
+        case 0: go(diversity_kernel<0>); break;
+        case 1: go(diversity_kernel<1>); break;
+        case 2: go(diversity_kernel<2>); break;
+        case 3: go(diversity_kernel<3>); break;
+        case 4: go(diversity_kernel<4>); break;
+        case 5: go(diversity_kernel<5>); break;
+        case 6: go(diversity_kernel<6>); break;
+        case 7: go(diversity_kernel<7>); break;
+        default: go(diversity_kernel<8>); break;
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 4) {
+        const uint64_t n = (uint64_t)S * p.n_cols;
+        hipLaunchKernelGGL(diversity_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, B, S, t->root, p.n_chunks, p.n_cols, (const u64 *)clade,
+                           (const double *)part, d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return RK_OK;
+}
+
+extern "C" int rk_diversity_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t n_theta, const double *theta, double *d_out, void *d_work,
+                                   uint64_t work_bytes, void *stream) {
+    const char *who = "rk_diversity_device";
+    DiversityPlan p;
+    if (int rc = diversity_prepare(who, t, n_samples, n_theta, p)) return rc;
+    if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (!d_out) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if ((uintptr_t)d_out % 8) return fail(RK_ERR_INVALID, "%s: the doubles must be 8-byte aligned", who);
+    if (int rc = work_args(who, "rk_diversity_work_bytes", d_work, work_bytes, p.bytes)) return rc;
+    if (int rc = diversity_theta_args(who, n_theta, theta)) return rc;
+    HIP_TRY(hipSetDevice(t->device));
+    unsigned steps = 7;
+    if (const char *v = rk_knob("RK_DIVERSITY_STEPS")) steps = (unsigned)atoi(v);  // developer builds (scripts/diversity_rate.py)
+    return diversity_launch(t, n_samples, d_masses, n_theta, theta, d_out, d_work, p, (hipStream_t)stream, steps);
+}
+
+extern "C" int rk_diversity_host(uint32_t n_branches, const int32_t *parent, const float *branch_len, uint32_t n_samples, const uint64_t *masses, uint32_t n_theta,
+                                 const double *theta, double *out, uint32_t n_threads) {
+    const char *who = "rk_diversity_host";
+    RK_GUARD_BEGIN
+    if (int rc = diversity_range(who, n_samples, n_theta)) return rc;
+    if (!out) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (int rc = diversity_theta_args(who, n_theta, theta)) return rc;
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, branch_len, true, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    const uint64_t B = n_branches, S = n_samples, W = rk_masses_words(n_branches), C = RK_DIVERSITY_FIXED + 2 * (uint64_t)n_theta;
+    std::vector<double> h(B);
+    for (uint32_t x = 0; x < B; x++) h[x] = rk::kr_half_length(branch_len, x, w.root);
+    const uint64_t T = host_threads(n_threads, S);
+    // samples dealt round to the threads, each with clade sums of its own
+    return masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        std::vector<uint64_t> clade(B);
+        for (uint64_t s = th; s < S; s += T) {
+            rk::clade_masses_sample(w, parent, masses + s * W, clade.data());
+            rk::diversity_sample((uint32_t)B, w.root, masses + s * W, clade.data(), h.data(), n_theta, theta, out + s * C);
+        }
+    });
+    RK_GUARD_END(who)
+}
+
+// The drivers' call: as rk_kmeans_batch, with the table [S][5 + 2 n_theta] on the host at the end
+extern "C" int rk_diversity_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t n_theta, const double *theta, double *out) {
+    const char *who = "rk_diversity_batch";
+    if (int rc = batch_handles(who, db, t)) return rc;
+    DiversityPlan p;
+    if (int rc = diversity_prepare(who, t, n_samples, n_theta, p)) return rc;
+    if (!out) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (int rc = diversity_theta_args(who, n_theta, theta)) return rc;
+    const uint64_t out_bytes = (uint64_t)n_samples * p.n_cols * 8;
+    return samples_batch(who, db, n_samples, masses, p.bytes, out_bytes, [&](const uint64_t *d_masses, char *d_out, void *d_work, hipStream_t s) -> int {
+        if (int rc = rk_diversity_device(t, n_samples, d_masses, n_theta, theta, (double *)d_out, d_work, p.bytes, s)) return rc;
+        HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+        return RK_OK;
+    });
+}
+
+// The functions of rk_divmath.h for the tests: out[i] = rk_log2(x[i]) (op 0), rk_exp2(x[i]) (1), pw(x[i], y[i]) (2)
+extern "C" int rk_diversity_math_host(uint32_t op, uint64_t n, const double *x, const double *y, double *out) {
+    const char *who = "rk_diversity_math_host";
+    if (op > 2) return fail(RK_ERR_INVALID, "%s: op=%u must be 0 (log2), 1 (exp2) or 2 (pw)", who, op);
+    if (n && (!x || !out)) return fail(RK_ERR_INVALID, "%s: null %s", who, x ? "output" : "input");
+    if (n && op == 2 && !y) return fail(RK_ERR_INVALID, "%s: null theta array", who);
+    for (uint64_t i = 0; i < n; i++)
+        out[i] = op == 0 ? rk::rk_log2(x[i]) : op == 1 ? rk::rk_exp2(x[i]) : rk::rk_pw(x[i], rk::rk_log2(x[i]), y[i]);
+    return RK_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -502,6 +502,23 @@ def kmeans_table(names, k, assign, dist, sizes, within, info):
     return "".join(out)
 
 
+def diversity_table(names, theta, values):
+    """the text `--diversity FILE` writes: a line `#diversity<TAB>S<TAB>n_theta`; a line `#columns` with rooted_pd, pd, bwpd, quadratic,
+    phylo_entropy and, per theta, rooted_pd_<theta> and bwpd_<theta> (theta as `%.17g`); one line per sample in sample order -- its
+    name and its values, `%.17g` (a NaN as `nan`), tab-separated --; a last line `#samples_without_mass<TAB>n`, n the samples whose
+    row is NaN.  `values` [S, 5 + 2 n_theta] is what diversity_host and EdgeTree.diversity_batch give.  The twin of
+    rkh::diversity_table, byte-identical."""
+    S, theta = len(names), [float(t) for t in theta]
+    values = np.asarray(values, dtype=np.float64).reshape(S, 5 + 2 * len(theta))
+    out = ["#diversity\t%d\t%d\n" % (S, len(theta)), "#columns\trooted_pd\tpd\tbwpd\tquadratic\tphylo_entropy"]
+    out.extend("\trooted_pd_%.17g\tbwpd_%.17g" % (t, t) for t in theta)
+    out.append("\n")
+    for s, name in enumerate(names):
+        out.append(name + "".join("\tnan" if np.isnan(v) else "\t%.17g" % v for v in values[s]) + "\n")
+    out.append(f"#samples_without_mass\t{int(np.isnan(values[:, 0]).sum())}\n")
+    return "".join(out)
+
+
 def _fmt12(x):
     """NumberFormat.getNumberInstance(Locale.UK) with exactly 12 fraction digits (NewickWriter.java:61-64): grouping commas,
     HALF_EVEN on the exact binary value."""

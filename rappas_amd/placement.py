@@ -836,6 +836,47 @@ def kmeans_host(parent, branch_len, masses, n_samples, k, max_rounds=100, seeds=
     return KMeans(assign, dist, sizes, within, info, cen)
 
 
+# the diversity measures of the samples: values float64 [S, 5 + 2 n_theta] (a NaN row for a sample without mass), columns their names
+Diversity = collections.namedtuple("Diversity", "values columns")
+DIVERSITY_FIXED = ("rooted_pd", "pd", "bwpd", "quadratic", "phylo_entropy")
+
+
+def _diversity_theta(theta):
+    theta = np.ascontiguousarray(() if theta is None else theta, dtype=np.float64).reshape(-1)
+    return theta, None if theta.shape[0] == 0 else _ptr(theta)
+
+
+def diversity_columns(theta):
+    """the column names of a diversity table: the five fixed ones, then rooted_pd_<theta> and bwpd_<theta> per theta (%.17g)"""
+    names = list(DIVERSITY_FIXED)
+    for t in np.asarray(() if theta is None else theta, dtype=np.float64).reshape(-1):
+        names += ["rooted_pd_%.17g" % t, "bwpd_%.17g" % t]
+    return tuple(names)
+
+
+def diversity_host(parent, branch_len, masses, n_samples, theta=(), threads=0):
+    """rk_diversity_host (no GPU): a Diversity of host arrays -- rooted and unrooted phylogenetic diversity, balance-weighted PD,
+    quadratic entropy and phylogenetic entropy of every sample of a sample mass buffer on the tree (parent, branch_len), and
+    rooted_pd_theta / bwpd_theta for every theta in [0, 8] (at most 8) -- the bits EdgeTree.diversity gives on the device."""
+    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
+    theta, tp = _diversity_theta(theta)
+    out = np.zeros((n_samples, len(DIVERSITY_FIXED) + 2 * theta.shape[0]), np.float64)
+    _lib.check(_lib.load().rk_diversity_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), theta.shape[0], tp, _ptr(out), threads))
+    return Diversity(out, diversity_columns(theta))
+
+
+def diversity_math_host(op, x, y=None):
+    """rk_diversity_math_host (no GPU): the diversity measures' own rk_log2 (op 0), rk_exp2 (op 1) or pw(x, y) = x ** y (op 2),
+    elementwise on float64 arrays"""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if y is not None and y.shape != x.shape:
+        raise ValueError("x and y must hold one value each per element")
+    out = np.zeros(x.shape[0], np.float64)
+    _lib.check(_lib.load().rk_diversity_math_host(op, x.shape[0], _ptr(x), None if y is None else _ptr(y), _ptr(out)))
+    return out
+
+
 # what epca_finish makes of a raw edge-PCA output: eigenvalue, share, residual [k]; projection [S, k]; loading [B, k]; the two info words
 EdgePCA = collections.namedtuple("EdgePCA", "eigenvalue share residual projection loading n_active k_eff")
 
@@ -1054,6 +1095,31 @@ class EdgeTree:
                                              None if seeds is None else _ptr(seeds), _ptr(assign), _ptr(dist), _ptr(sizes), _ptr(within), _ptr(info),
                                              None if cen is None else _ptr(cen)))
         return KMeans(assign, dist, sizes, within, info, cen)
+
+    def diversity_work_bytes(self, n_samples, n_theta=0):
+        return self._need(self._lib.rk_diversity_work_bytes, n_samples, n_theta)
+
+    def diversity(self, masses, n_samples, theta=(), stream=None):
+        """rk_diversity_device: a Diversity whose values are a device tensor float64 [S, 5 + 2 n_theta], written, as diversity_host
+        gives them; asynchronous on the stream.  `theta`: at most 8 values in [0, 8] on the host, read during the call."""
+        import torch
+        dev = self._masses(masses, n_samples)
+        theta, tp = _diversity_theta(theta)
+        work = self._work(self.diversity_work_bytes(n_samples, theta.shape[0]), dev)
+        out = torch.empty((n_samples, len(DIVERSITY_FIXED) + 2 * theta.shape[0]), dtype=torch.float64, device=dev)
+        _lib.check(self._lib.rk_diversity_device(self.handle, n_samples, masses.data_ptr(), theta.shape[0], tp, out.data_ptr(), work.data_ptr(), work.numel(),
+                                                 C.c_void_p(_stream(dev, stream))))
+        return Diversity(out, diversity_columns(theta))
+
+    def diversity_batch(self, db, n_samples, theta=(), masses=None):
+        """rk_diversity_batch, the drivers' call: a Diversity of host arrays, as diversity_host gives them, from a host sample mass
+        buffer -- or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through
+        rk_diversity_device on db's device; returns when the table is there"""
+        masses = self._batch_masses(n_samples, masses)
+        theta, tp = _diversity_theta(theta)
+        out = np.zeros((n_samples, len(DIVERSITY_FIXED) + 2 * theta.shape[0]), np.float64)
+        _lib.check(self._lib.rk_diversity_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), theta.shape[0], tp, _ptr(out)))
+        return Diversity(out, diversity_columns(theta))
 
     def epca_work_bytes(self, n_samples, k):
         return self._need(self._lib.rk_epca_work_bytes, n_samples, k)

@@ -23,6 +23,8 @@ EPCA_NEEDS_SAMPLE_SEP = "--epca finds the principal components of the samples of
 EPCA_RANGES = "--epca-components must be in 1..8, --epca-iters in 1..10000"
 KMEANS_NEEDS_SAMPLE_SEP = "--kmeans clusters the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 KMEANS_RANGES = "--kmeans needs --kmeans-k in 1..64; --kmeans-rounds must be in 1..1024"
+DIVERSITY_NEEDS_SAMPLE_SEP = "--diversity measures the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
+DIVERSITY_RANGES = "--diversity-theta takes at most 8 numbers in 0..8, separated by commas"
 EDPL_NEEDS_OUT ="--edpl reads the placements of a run that writes a jplace: it needs --out (and cannot be combined with --masses-only)"
 SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
@@ -94,6 +96,38 @@ def kmeans_text(db, tree, sample_names, words, k, max_rounds, device=0):
         et.close()
 
 
+def diversity_text(db, tree, sample_names, words, theta, device=0):
+    """`--diversity FILE`: the table (hostio.diversity_table) of the diversity measures of the samples of a sample mass buffer over the
+    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`"""
+    from ..placement import EdgeTree
+    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
+    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
+    try:
+        return hostio.diversity_table(sample_names, theta, et.diversity_batch(db, len(sample_names), theta, words).values)
+    finally:
+        et.close()
+
+
+def parse_thetas(text):
+    """the values of `--diversity-theta T1,T2,...` (None or empty: none); ValueError(DIVERSITY_RANGES) for what the engine would refuse"""
+    if text is None or text == "":
+        return ()
+    try:
+        theta = tuple(float(t) for t in text.split(","))
+    except ValueError:
+        raise ValueError(DIVERSITY_RANGES) from None
+    if len(theta) > 8 or not all(0.0 <= t <= 8.0 for t in theta):
+        raise ValueError(DIVERSITY_RANGES)
+    return theta
+
+
+def _diversity_check(diversity, with_samples, theta):
+    if diversity and not with_samples:
+        raise ValueError(DIVERSITY_NEEDS_SAMPLE_SEP)
+    if diversity and (len(theta) > 8 or not all(0.0 <= t <= 8.0 for t in theta)):
+        raise ValueError(DIVERSITY_RANGES)
+
+
 def _kmeans_check(kmeans, with_samples, k, max_rounds):
     if kmeans and not with_samples:
         raise ValueError(KMEANS_NEEDS_SAMPLE_SEP)
@@ -115,7 +149,7 @@ def edpl_text(db, tree, records, unique, res, keep_at_most, device=0):
 
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
                call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None, kr=False,
-               squash=False, epca=False, epca_components=5, epca_iters=200, edpl=False, kmeans=False, kmeans_k=0, kmeans_rounds=100):
+               squash=False, epca=False, epca_components=5, epca_iters=200, edpl=False, kmeans=False, kmeans_k=0, kmeans_rounds=100, diversity=False, diversity_theta=()):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
@@ -125,11 +159,13 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table); with kr as well res.kr is
     the text `--kr FILE` writes (kr_text), with squash res.squash the text `--squash FILE` writes (squash_text), with epca res.epca the text
     `--epca FILE` writes (epca_text) for epca_components components after epca_iters iterations, with kmeans res.kmeans the text
-    `--kmeans FILE` writes (kmeans_text) for kmeans_k clusters and at most kmeans_rounds rounds.  edpl: res.edpl is the text `--edpl FILE`
+    `--kmeans FILE` writes (kmeans_text) for kmeans_k clusters and at most kmeans_rounds rounds, with diversity res.diversity the text
+    `--diversity FILE` writes (diversity_text) with the thetas diversity_theta.  edpl: res.edpl is the text `--edpl FILE`
     writes (edpl_text), with any strand and with translate."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
     _kmeans_check(kmeans, masses and sample_sep is not None, kmeans_k, kmeans_rounds)
+    _diversity_check(diversity, masses and sample_sep is not None, diversity_theta)
     if epca and not (masses and sample_sep is not None):
         raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
     if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
@@ -153,7 +189,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
             res = PlacementProcess(db, ns_bound).processQueries(
                 seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
                 treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
-        res.kr = res.squash = res.epca = res.kmeans = None
+        res.kr = res.squash = res.epca = res.kmeans = res.diversity = None
         res.edpl = edpl_text(db, tree, records, unique, res, keep_at_most, device) if edpl else None
         if members is not None:
             from ..placement import accumulate_masses_samples_host
@@ -168,6 +204,8 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
                 res.epca = epca_text(db, tree, sample_names, sample_words, sample_words, epca_components, epca_iters, device)
             if kmeans:
                 res.kmeans = kmeans_text(db, tree, sample_names, sample_words, kmeans_k, kmeans_rounds, device)
+            if diversity:
+                res.diversity = diversity_text(db, tree, sample_names, sample_words, diversity_theta, device)
     finally:
         db.close()
     pl = hostio.jplace_placements(tree, names, res.n_rows, res.branch, res.score, res.lwr, guppy)
@@ -186,7 +224,7 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
 
 def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), device=0, union=False,
                      dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None, kr=False, squash=False, epca=False, epca_components=5,
-                     epca_iters=200, kmeans=False, kmeans_k=0, kmeans_rounds=100):
+                     epca_iters=200, kmeans=False, kmeans_k=0, kmeans_rounds=100, diversity=False, diversity_theta=()):
     """`--masses-only FILE`: scan, dedup and gather as place_file, then ONE profile-only call (processQueriesMasses) with the
     multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
     table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
@@ -194,11 +232,12 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
     processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample; with kr as well
     .kr is the text `--kr FILE` writes, from the buffer that call left on the device, and with squash .squash the text `--squash FILE`
     writes, from the same buffer, and with epca .epca the text `--epca FILE` writes, from the same buffer again, and with kmeans
-    .kmeans the text `--kmeans FILE` writes, likewise."""
+    .kmeans the text `--kmeans FILE` writes, likewise, and with diversity .diversity the text `--diversity FILE` writes."""
     from types import SimpleNamespace
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
     _kmeans_check(kmeans, sample_sep is not None, kmeans_k, kmeans_rounds)
+    _diversity_check(diversity, sample_sep is not None, diversity_theta)
     if epca and sample_sep is None:
         raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
     if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
@@ -207,7 +246,7 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
         raise ValueError(KR_NEEDS_SAMPLE_SEP)
     if squash and sample_sep is None:
         raise ValueError(SQUASH_NEEDS_SAMPLE_SEP)
-    kr_out = squash_out = epca_out = kmeans_out = None
+    kr_out = squash_out = epca_out = kmeans_out = diversity_out = None
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     try:
         if translate and db.info.alphabet != 20:
@@ -231,6 +270,8 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
                 epca_out = epca_text(db, tree, sample_names, None, words, epca_components, epca_iters, device)
             if kmeans:
                 kmeans_out = kmeans_text(db, tree, sample_names, None, kmeans_k, kmeans_rounds, device)
+            if diversity:
+                diversity_out = diversity_text(db, tree, sample_names, None, diversity_theta, device)
         else:
             words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(seq, off, weights=weights, **common)
             table = hostio.masses_table(tree, words)
@@ -238,7 +279,7 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
         db.close()
     return SimpleNamespace(masses=table, notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
                            reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters, kr=kr_out,
-                           squash=squash_out, epca=epca_out, kmeans=kmeans_out)
+                           squash=squash_out, epca=epca_out, kmeans=kmeans_out, diversity=diversity_out)
 
 
 def _open_db(db_text, union, dbimage, save_dbimage, device):
@@ -318,6 +359,12 @@ def main(argv=None):
                          "#samples_without_mass<TAB>n")
     ap.add_argument("--kmeans-k", type=int, default=0, metavar="K", help="--kmeans: the number of clusters, 1..64")
     ap.add_argument("--kmeans-rounds", type=int, default=100, metavar="N", help="--kmeans: the most rounds run, 1..1024 (default 100)")
+    ap.add_argument("--diversity", default=None, metavar="FILE",
+                    help="with --sample-sep: the phylogenetic diversity of every sample (what guppy fpd reports), summed on the device: a line "
+                         "#diversity<TAB>S<TAB>n_theta, a line #columns with rooted_pd, pd, bwpd, quadratic, phylo_entropy and, per theta, "
+                         "rooted_pd_<theta> and bwpd_<theta>, a line name<TAB>values (%%.17g) per sample (nan without mass), and a last line "
+                         "#samples_without_mass<TAB>n")
+    ap.add_argument("--diversity-theta", default=None, metavar="T1,T2,...", help="--diversity: at most 8 exponents in 0..8 for the one-parameter families")
     ap.add_argument("--edpl", default=None, metavar="FILE",
                     help="with --out: the EDPL of every placed read (the expected distance between its placement locations: the sum over the "
                          "pairs of its rows of LWR x LWR x the tree path between the midpoints of the two edges), computed on the device: a "
@@ -350,6 +397,12 @@ def main(argv=None):
         ap.error(KMEANS_NEEDS_SAMPLE_SEP)
     if a.kmeans is not None and not (1 <= a.kmeans_k <= 64 and 1 <= a.kmeans_rounds <= 1024):
         ap.error(KMEANS_RANGES)
+    if a.diversity is not None and a.sample_sep is None:
+        ap.error(DIVERSITY_NEEDS_SAMPLE_SEP)
+    try:
+        thetas = parse_thetas(a.diversity_theta)
+    except ValueError as e:
+        ap.error(str(e))
     if a.edpl is not None and a.out is None:
         ap.error(EDPL_NEEDS_OUT)
     if a.masses_only is None and a.out is None:
@@ -362,13 +415,14 @@ def main(argv=None):
         fasta_text = f.read()
     call = "".join(" " + x for x in (argv if argv is not None else sys.argv[1:]))
     if a.masses_only is not None:
-        return _main_masses_only(a, db_text, fasta_text)
+        return _main_masses_only(a, db_text, fasta_text, thetas)
     try:
         doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
                               a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
                               translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep, kr=a.kr is not None,
                               squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters,
-                              edpl=a.edpl is not None, kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds)
+                              edpl=a.edpl is not None, kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds,
+                              diversity=a.diversity is not None, diversity_theta=thetas)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -401,6 +455,9 @@ def main(argv=None):
     if res.kmeans is not None:
         with open(a.kmeans, "w") as f:
             f.write(res.kmeans)
+    if res.diversity is not None:
+        with open(a.diversity, "w") as f:
+            f.write(res.diversity)
     if res.edpl is not None:
         with open(a.edpl, "w") as f:
             f.write(res.edpl)
@@ -409,7 +466,7 @@ def main(argv=None):
     return 0
 
 
-def _main_masses_only(a, db_text, fasta_text):
+def _main_masses_only(a, db_text, fasta_text, thetas=()):
     import json
     import time
     t0 = time.perf_counter()
@@ -417,7 +474,8 @@ def _main_masses_only(a, db_text, fasta_text):
         res = masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.device, union=a.uniondb is not None,
                                dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate, sample_sep=a.sample_sep, kr=a.kr is not None,
                                squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters,
-                               kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds)
+                               kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds, diversity=a.diversity is not None,
+                               diversity_theta=thetas)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
@@ -438,6 +496,9 @@ def _main_masses_only(a, db_text, fasta_text):
     if res.kmeans is not None:
         with open(a.kmeans, "w") as f:
             f.write(res.kmeans)
+    if res.diversity is not None:
+        with open(a.diversity, "w") as f:
+            f.write(res.diversity)
     logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.masses_only)), "logs")
     os.makedirs(logs, exist_ok=True)
     with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
