@@ -669,14 +669,41 @@ struct UnitRing {
     float sc[U];
 };
 template <int G>
-__device__ __forceinline__ void unit_issue(__amdgpu_buffer_rsrc_t rs, u32 item, u32 li, u32 &b, float &v) {
+__device__ __forceinline__ u32 unit_offset(u32 item, u32 li) {  // where in the rows this lane reads the unit of `item`
     const u32 li8 = li * 8;
     u32 off = item + li8;  // G == 16: the low bits of an item are zero
     if (G > 16) off = ((li >> 4) <= (item & 7u)) ? (item & ~127u) + li8 : ITEM_FILLER;  // (li >> 4: which 128-byte unit of the chunk this lane reads)
     if (RK_ABLATE & 16) off = li8;
+    return off;
+}
+__device__ __forceinline__ void unit_load(__amdgpu_buffer_rsrc_t rs, u32 off, u32 &b, float &v) {
     const v2u32 e = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off, 0, RK_ROW_AUX);
     b = e.x;  // (left untouched until its step: anything computed from it here would wait for the load and serialise the ring)
     v = __uint_as_float(e.y);
+}
+template <int G>
+__device__ __forceinline__ void unit_issue(__amdgpu_buffer_rsrc_t rs, u32 item, u32 li, u32 &b, float &v) {
+    unit_load(rs, unit_offset<G>(item, li), b, v);
+}
+// The first touch of a word of a dense step, with what the wave needs next handed to it as inputs it does not read: the two LDS
+// addresses of the step to come and, where the step feeds the ring, the offset of its gather.  An input exists before the statement
+// that takes it, and the wait for the step's LDS words stands in front of their first use, which is this statement: so the unpacking
+// of step n + 1 is issued under the LDS round trip of step n, not behind it, where the scheduler puts it when it is left the choice
+// (DESIGN.md 4.1a "Round 10").  Costs no instruction; the result is touch_base's.
+typedef __attribute__((address_space(3))) const u32 *lds_cu32;
+template <bool MONO, bool FEED>
+__device__ __forceinline__ float touch_base_behind(u32 old, float QT, const u32 *na, const u32 *nb, u32 off) {
+    const lds_cu32 la = (lds_cu32)na, lb = (lds_cu32)nb;
+    float base;
+    if (MONO) {
+        if (FEED) asm("v_max_f32 %0, %1, %2" : "=v"(base) : "v"(old), "v"(QT), "v"(la), "v"(lb), "v"(off));
+        else asm("v_max_f32 %0, %1, %2" : "=v"(base) : "v"(old), "v"(QT), "v"(la), "v"(lb));
+    } else {
+        if (FEED) asm("" : "+v"(old) : "v"(la), "v"(lb), "v"(off));
+        else asm("" : "+v"(old) : "v"(la), "v"(lb));
+        base = touch_base<false>(old, QT);
+    }
+    return base;
 }
 template <int G, int U>
 __device__ __forceinline__ void units_issue(UnitRing<U> &r, const u32 *items, u32 li, __amdgpu_buffer_rsrc_t rs) {
@@ -699,6 +726,7 @@ __device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *ite
     static_assert(!TILE || U == 8, "a tail of up to three pairs of steps");
     static_assert(rk_slots24::SLOT_BITS == SLOT24_BITS, "rk_slots24.h unpacks the slot words rk_device.h defines");
     const rk_slots24::Shifts sh24 = rk_slots24::lane_shifts(li);  // D24: where this lane's two slots sit in the word the DPP leaves it
+    const u32 li8 = li * 8;
     u32(&sb)[U] = r.sb;
     u32(&it)[U] = r.it;
     float(&sc)[U] = r.sc;
@@ -709,10 +737,14 @@ __device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *ite
         return (t < w4) ? t + 4u : 0u;
     };
     // D24, a ring entry is b = w[2li] (d of entry li), v = w[2li + 1] (lanes 0..7: d of entry 16 + li; lanes 8..15: the slot word)
+    // accumulate_units' masked DPP (row_ror:8, bank_mask 0x3: lanes 0..7 of each row are written, lanes 8..15 keep their own word) and
+    // the register copy it needs, as one volatile statement: a volatile asm keeps its place among the memory operations, so the copy
+    // stays between the LDS reads of the step before and that step's gather and LDS writes.  Left to the scheduler, the copy of step
+    // n + 2 is lifted into step n, behind its LDS wait.  The compiler pads no DPP hazard inside an asm: the s_nop gives the two wait
+    // states a DPP needs after a VALU write of its source, whatever wrote the ring entry last.
     auto prepare = [&](float v, u32 *&pa, u32 *&pb) {
-        const int w = (int)__float_as_uint(v);
-        // row_ror:8, bank_mask 0x3 = lanes 0..7 of each row are written, lanes 8..15 keep `old` = their own word: no v_mov 0, no select
-        const u32 r = (u32)__builtin_amdgcn_update_dpp(w, w, 0x128, 0xF, 0x3, false);
+        u32 r;
+        asm volatile("v_mov_b32 %0, %1\n\ts_nop 1\n\tv_mov_b32_dpp %0, %1 row_ror:8 row_mask:0xf bank_mask:0x3" : "=&v"(r) : "v"(v));
         const rk_slots24::Slots s = rk_slots24::lane_slots(sh24, r);
         pa = S + s.a;
         pb = S + s.b;
@@ -741,14 +773,22 @@ __device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *ite
                     // unless both are the scratch word.
                     const u32 oa = *pa, ob = *pb;
                     prepare(sc[(u + 1) % U], na, nb);  // the next step's entry (after the last step: a filler's zeros)
-                    *pa = __float_as_uint(touch_base<MONO>(oa, QT) + __uint_as_float(sb[u]));
-                    *pb = __float_as_uint(touch_base<MONO>(ob, QT) + sc[u]);
+                    u32 off = 0u;  // unit_offset<16>; volatile as in prepare: left free, the add of step n + 1 is lifted behind step n's wait
+                    if (FEED && (RK_ABLATE & 16)) off = unit_offset<G>(it[u], li);
+                    else if (FEED) asm volatile("v_add_u32 %0, %1, %2" : "=v"(off) : "v"(it[u]), "v"(li8));
+                    *pa = __float_as_uint(touch_base_behind<MONO, FEED>(oa, QT, na, nb, off) + __uint_as_float(sb[u]));
+                    *pb = __float_as_uint(touch_base_behind<MONO, FEED>(ob, QT, na, nb, off) + sc[u]);  // (whichever word arrives first)
+                    if (FEED) unit_load(rs, off, sb[u], sc[u]);
                 }
                 pa = na;
                 pb = nb;
-            } else {
-                apply_slot<MONO>(S, slot_of(sb[u]), sc[u], QT, T);
+                if (FEED) {
+                    if (RK_ABLATE & 8) issue(it[u], sb[u], sc[u]);
+                    it[u] = items[s0 + 2 * U + u];
+                }
+                continue;
             }
+            apply_slot<MONO>(S, slot_of(sb[u]), sc[u], QT, T);
             if (FEED) {
                 issue(it[u], sb[u], sc[u]);
                 it[u] = items[s0 + 2 * U + u];
