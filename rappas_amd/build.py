@@ -99,7 +99,7 @@ def check_isa(so, verbose=False):
 
 
 HOST_BIN = os.path.join(ROOT, "rappas_amd", "bin", "rk_place")
-HOST_SRC = [os.path.join(CSRC, "host", f) for f in ("rk_place_main.cpp", "rk_hostio.hpp", "rk_javaser.hpp", "rk_fastio.hpp")]
+HOST_SRC = [os.path.join(CSRC, "host", f) for f in ("rk_place_main.cpp", "rk_place_selftest.hpp", "rk_hostio.hpp", "rk_javaser.hpp", "rk_fastio.hpp")]
 
 
 def build_host_tools(force=False, verbose=False):

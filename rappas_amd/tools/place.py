@@ -5,8 +5,10 @@ from the JSON dump `--jsondb` writes (src/main_v2/SessionNext_v2.java:214-270) i
 Only the placement itself runs on the GPU; ingest and the jplace writer are rappas_amd/hostio.py.
 """
 import argparse
+import contextlib
 import os
 import sys
+from collections import namedtuple
 
 import numpy as np
 
@@ -30,82 +32,128 @@ SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
 
 
+@contextlib.contextmanager
+def _edge_tree(tree, device=0, wanted=True):
+    """the database's tree (a hostio tree) on the device, as the reports and --edpl take it; None if no one wants it"""
+    if not wanted:
+        yield None
+        return
+    from ..placement import EdgeTree
+    et = EdgeTree([n.parent.id if n.parent is not None else -1 for n in tree.nodes], [n.bl for n in tree.nodes], device=device)
+    try:
+        yield et
+    finally:
+        et.close()
+
+
+def _with_mass(et, n_samples, host_words):
+    W = 2 * et.n_branches + 4
+    host_words = np.asarray(host_words, dtype=np.uint64).reshape(-1)
+    return [bool(host_words[s * W:s * W + et.n_branches].any()) for s in range(n_samples)]
+
+
+# The sample reports of --sample-sep, a row each: text(edge_tree, db, sample_names, words, host_words, options) over a sample mass buffer
+# and the database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`; host_words: the
+# host's copy either way (it tells which samples hold mass); options: place_file's keywords of the reports
+def _kr_report(et, db, names, words, host_words, o):
+    return hostio.kr_table(names, et.kr_distances_batch(db, len(names), words))
+
+
+def _squash_report(et, db, names, words, host_words, o):
+    from ..placement import SQUASH_MERGE
+    merges, n_merges = et.squash_batch(db, len(names), words) if len(names) > 1 else (np.zeros(0, SQUASH_MERGE), 0)
+    return hostio.squash_table(names, merges, n_merges, _with_mass(et, len(names), host_words))
+
+
+def _epca_report(et, db, names, words, host_words, o):
+    from ..placement import epca_finish
+    S, B, k, iters = len(names), et.n_branches, o["epca_components"], o["epca_iters"]
+    if S < 2:  # one sample alone has no components: it is only counted
+        return hostio.epca_table(names, B, k, iters, sum(_with_mass(et, S, host_words)), 0, np.zeros(k), np.zeros(k), np.zeros(k), np.zeros((S, k)), np.zeros((B, k)))
+    raw, info = et.epca_batch(db, S, k, iters, words)
+    f = epca_finish(B, S, k, raw, info)
+    return hostio.epca_table(names, B, k, iters, f.n_active, f.k_eff, f.eigenvalue, f.share, f.residual, f.projection, f.loading)
+
+
+def _kmeans_report(et, db, names, words, host_words, o):
+    r = et.kmeans_batch(db, len(names), o["kmeans_k"], o["kmeans_rounds"], words)
+    return hostio.kmeans_table(names, o["kmeans_k"], r.assign, r.dist, r.sizes, r.within, r.info)
+
+
+def _diversity_report(et, db, names, words, host_words, o):
+    return hostio.diversity_table(names, o["diversity_theta"], et.diversity_batch(db, len(names), o["diversity_theta"], words).values)
+
+
+def _thetas_in_range(theta):
+    return len(theta) <= 8 and all(0.0 <= t <= 8.0 for t in theta)
+
+
+# name: the option `--name FILE`, the keyword of place_file and the attribute of its result; in_range(options): its own options, if any
+Report = namedtuple("Report", "name needs_sample_sep in_range ranges text")
+SAMPLE_REPORTS = (
+    Report("kr", KR_NEEDS_SAMPLE_SEP, None, None, _kr_report),
+    Report("squash", SQUASH_NEEDS_SAMPLE_SEP, None, None, _squash_report),
+    Report("epca", EPCA_NEEDS_SAMPLE_SEP, lambda o: 1 <= o["epca_components"] <= 8 and 1 <= o["epca_iters"] <= 10000, EPCA_RANGES, _epca_report),
+    Report("kmeans", KMEANS_NEEDS_SAMPLE_SEP, lambda o: 1 <= o["kmeans_k"] <= 64 and 1 <= o["kmeans_rounds"] <= 1024, KMEANS_RANGES, _kmeans_report),
+    Report("diversity", DIVERSITY_NEEDS_SAMPLE_SEP, lambda o: _thetas_in_range(o["diversity_theta"]), DIVERSITY_RANGES, _diversity_report),
+)
+
+
+def _check_reports(requested, with_samples, options):
+    """ValueError with the sentence of the first rule a requested report breaks, in the table's order"""
+    for r in SAMPLE_REPORTS:
+        if requested[r.name] and not with_samples:
+            raise ValueError(r.needs_sample_sep)
+        if requested[r.name] and r.in_range is not None and not r.in_range(options):
+            raise ValueError(r.ranges)
+
+
+def _run_reports(et, db, sample_names, words, host_words, requested, options):
+    """{name: text, or None if not requested} of every report"""
+    return {r.name: r.text(et, db, sample_names, words, host_words, options) if requested[r.name] else None for r in SAMPLE_REPORTS}
+
+
 def kr_text(db, tree, sample_names, words, device=0):
     """`--kr FILE`: the table (hostio.kr_table) of the pairwise KR distances between the samples of a sample mass buffer over the
     database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`"""
-    from ..placement import EdgeTree
-    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
-    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
-    try:
-        return hostio.kr_table(sample_names, et.kr_distances_batch(db, len(sample_names), words))
-    finally:
-        et.close()
+    with _edge_tree(tree, device) as et:
+        return _kr_report(et, db, sample_names, words, None, None)
 
 
 def squash_text(db, tree, sample_names, words, host_words, device=0):
-    """`--squash FILE`: the table (hostio.squash_table) of the squash clustering of the samples of a sample mass buffer over the
-    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`; host_words: the host's copy
-    either way (it tells which samples hold mass)"""
-    from ..placement import SQUASH_MERGE, EdgeTree
-    S, B = len(sample_names), len(tree.nodes)
-    W = 2 * B + 4
-    host_words = np.asarray(host_words, dtype=np.uint64).reshape(-1)
-    with_mass = [bool(host_words[s * W:s * W + B].any()) for s in range(S)]
-    if S < 2:
-        return hostio.squash_table(sample_names, np.zeros(0, SQUASH_MERGE), 0, with_mass)
-    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
-    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
-    try:
-        merges, n_merges = et.squash_batch(db, S, words)
-        return hostio.squash_table(sample_names, merges, n_merges, with_mass)
-    finally:
-        et.close()
+    """`--squash FILE`: the table (hostio.squash_table) of the squash clustering of the samples, as kr_text; host_words: the host's copy
+    of the buffer either way (it tells which samples hold mass)"""
+    with _edge_tree(tree, device) as et:
+        return _squash_report(et, db, sample_names, words, host_words, None)
 
 
 def epca_text(db, tree, sample_names, words, host_words, k, iters, device=0):
-    """`--epca FILE`: the table (hostio.epca_table) of the edge principal components of the samples of a sample mass buffer over the
-    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`; host_words: the host's copy
-    either way (one sample alone has no components: it is only counted)"""
-    from ..placement import EdgeTree, epca_finish
-    S, B = len(sample_names), len(tree.nodes)
-    if S < 2:
-        W = 2 * B + 4
-        host_words = np.asarray(host_words, dtype=np.uint64).reshape(-1)
-        n_active = sum(bool(host_words[s * W:s * W + B].any()) for s in range(S))
-        return hostio.epca_table(sample_names, B, k, iters, n_active, 0, np.zeros(k), np.zeros(k), np.zeros(k), np.zeros((S, k)), np.zeros((B, k)))
-    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
-    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
-    try:
-        raw, info = et.epca_batch(db, S, k, iters, words)
-        f = epca_finish(B, S, k, raw, info)
-        return hostio.epca_table(sample_names, B, k, iters, f.n_active, f.k_eff, f.eigenvalue, f.share, f.residual, f.projection, f.loading)
-    finally:
-        et.close()
+    """`--epca FILE`: the table (hostio.epca_table) of the edge principal components of the samples, as squash_text"""
+    with _edge_tree(tree, device) as et:
+        return _epca_report(et, db, sample_names, words, host_words, dict(epca_components=k, epca_iters=iters))
 
 
 def kmeans_text(db, tree, sample_names, words, k, max_rounds, device=0):
-    """`--kmeans FILE`: the table (hostio.kmeans_table) of the phylogenetic k-means of the samples of a sample mass buffer over the
-    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`"""
-    from ..placement import EdgeTree
-    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
-    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
-    try:
-        r = et.kmeans_batch(db, len(sample_names), k, max_rounds, words)
-        return hostio.kmeans_table(sample_names, k, r.assign, r.dist, r.sizes, r.within, r.info)
-    finally:
-        et.close()
+    """`--kmeans FILE`: the table (hostio.kmeans_table) of the phylogenetic k-means of the samples, as kr_text"""
+    with _edge_tree(tree, device) as et:
+        return _kmeans_report(et, db, sample_names, words, None, dict(kmeans_k=k, kmeans_rounds=max_rounds))
 
 
 def diversity_text(db, tree, sample_names, words, theta, device=0):
-    """`--diversity FILE`: the table (hostio.diversity_table) of the diversity measures of the samples of a sample mass buffer over the
-    database's tree -- words None: the buffer the per-sample profile-only call left on the device in `db`"""
-    from ..placement import EdgeTree
-    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
-    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
-    try:
-        return hostio.diversity_table(sample_names, theta, et.diversity_batch(db, len(sample_names), theta, words).values)
-    finally:
-        et.close()
+    """`--diversity FILE`: the table (hostio.diversity_table) of the diversity measures of the samples, as kr_text"""
+    with _edge_tree(tree, device) as et:
+        return _diversity_report(et, db, sample_names, words, None, dict(diversity_theta=theta))
+
+
+def _edpl_report(et, db, records, unique, res, keep_at_most):
+    return hostio.edpl_table(records, unique, res.n_rows, et.edpl_batch(db, keep_at_most, res.n_rows, res.branch, res.lwr))
+
+
+def edpl_text(db, tree, records, unique, res, keep_at_most, device=0):
+    """`--edpl FILE`: the table (hostio.edpl_table) of the EDPL of every placed read of a result set on the host, over the database's
+    tree, through rk_edpl_batch on db's device"""
+    with _edge_tree(tree, device) as et:
+        return _edpl_report(et, db, records, unique, res, keep_at_most)
 
 
 def parse_thetas(text):
@@ -116,35 +164,9 @@ def parse_thetas(text):
         theta = tuple(float(t) for t in text.split(","))
     except ValueError:
         raise ValueError(DIVERSITY_RANGES) from None
-    if len(theta) > 8 or not all(0.0 <= t <= 8.0 for t in theta):
+    if not _thetas_in_range(theta):
         raise ValueError(DIVERSITY_RANGES)
     return theta
-
-
-def _diversity_check(diversity, with_samples, theta):
-    if diversity and not with_samples:
-        raise ValueError(DIVERSITY_NEEDS_SAMPLE_SEP)
-    if diversity and (len(theta) > 8 or not all(0.0 <= t <= 8.0 for t in theta)):
-        raise ValueError(DIVERSITY_RANGES)
-
-
-def _kmeans_check(kmeans, with_samples, k, max_rounds):
-    if kmeans and not with_samples:
-        raise ValueError(KMEANS_NEEDS_SAMPLE_SEP)
-    if kmeans and not (1 <= k <= 64 and 1 <= max_rounds <= 1024):
-        raise ValueError(KMEANS_RANGES)
-
-
-def edpl_text(db, tree, records, unique, res, keep_at_most, device=0):
-    """`--edpl FILE`: the table (hostio.edpl_table) of the EDPL of every placed read of a result set on the host, over the database's
-    tree as epca_text builds it, through rk_edpl_batch on db's device"""
-    from ..placement import EdgeTree
-    parent = [n.parent.id if n.parent is not None else -1 for n in tree.nodes]
-    et = EdgeTree(parent, [n.bl for n in tree.nodes], device=device)
-    try:
-        return hostio.edpl_table(records, unique, res.n_rows, et.edpl_batch(db, keep_at_most, res.n_rows, res.branch, res.lwr))
-    finally:
-        et.close()
 
 
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
@@ -156,24 +178,16 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     reversed_<query>.tsv).  translate: DNA reads on an amino-acid database, six reading frames translated on the device and the best
     one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both".  masses: res.masses is
     then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for);
-    with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table); with kr as well res.kr is
-    the text `--kr FILE` writes (kr_text), with squash res.squash the text `--squash FILE` writes (squash_text), with epca res.epca the text
-    `--epca FILE` writes (epca_text) for epca_components components after epca_iters iterations, with kmeans res.kmeans the text
-    `--kmeans FILE` writes (kmeans_text) for kmeans_k clusters and at most kmeans_rounds rounds, with diversity res.diversity the text
-    `--diversity FILE` writes (diversity_text) with the thetas diversity_theta.  edpl: res.edpl is the text `--edpl FILE`
-    writes (edpl_text), with any strand and with translate."""
+    with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table), and then for every
+    report of SAMPLE_REPORTS asked for by its name (kr, squash, epca, kmeans, diversity) res.<name> is the text `--<name> FILE`
+    writes, with the report's own keywords (epca_components components after epca_iters iterations; kmeans_k clusters and at most
+    kmeans_rounds rounds; the thetas diversity_theta).  edpl: res.edpl is the text `--edpl FILE` writes (edpl_text), with any strand
+    and with translate."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
-    _kmeans_check(kmeans, masses and sample_sep is not None, kmeans_k, kmeans_rounds)
-    _diversity_check(diversity, masses and sample_sep is not None, diversity_theta)
-    if epca and not (masses and sample_sep is not None):
-        raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
-    if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
-        raise ValueError(EPCA_RANGES)
-    if kr and not (masses and sample_sep is not None):
-        raise ValueError(KR_NEEDS_SAMPLE_SEP)
-    if squash and not (masses and sample_sep is not None):
-        raise ValueError(SQUASH_NEEDS_SAMPLE_SEP)
+    requested = dict(kr=kr, squash=squash, epca=epca, kmeans=kmeans, diversity=diversity)
+    options = dict(epca_components=epca_components, epca_iters=epca_iters, kmeans_k=kmeans_k, kmeans_rounds=kmeans_rounds, diversity_theta=diversity_theta)
+    _check_reports(requested, masses and sample_sep is not None, options)
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     sample_words = None
     try:
@@ -189,25 +203,19 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
             res = PlacementProcess(db, ns_bound).processQueries(
                 seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor, treatAmbiguities=(amb != "skip"),
                 treatAmbiguitiesWithMax=(amb == "max"), strand=strand)
-        res.kr = res.squash = res.epca = res.kmeans = res.diversity = None
-        res.edpl = edpl_text(db, tree, records, unique, res, keep_at_most, device) if edpl else None
-        if members is not None:
-            from ..placement import accumulate_masses_samples_host
-            sample_names, m_off, m_sample, m_weight = members
-            m_read = np.repeat(np.arange(len(unique), dtype=np.uint32), np.diff(m_off.astype(np.int64)))
-            sample_words = accumulate_masses_samples_host(len(tree.nodes), res, len(sample_names), m_sample, member_read=m_read, member_weight=m_weight)
-            if kr:
-                res.kr = kr_text(db, tree, sample_names, sample_words, device)
-            if squash:
-                res.squash = squash_text(db, tree, sample_names, sample_words, sample_words, device)
-            if epca:
-                res.epca = epca_text(db, tree, sample_names, sample_words, sample_words, epca_components, epca_iters, device)
-            if kmeans:
-                res.kmeans = kmeans_text(db, tree, sample_names, sample_words, kmeans_k, kmeans_rounds, device)
-            if diversity:
-                res.diversity = diversity_text(db, tree, sample_names, sample_words, diversity_theta, device)
+        reports = dict.fromkeys(requested)
+        with _edge_tree(tree, device, edpl or any(requested.values())) as et:
+            res.edpl = _edpl_report(et, db, records, unique, res, keep_at_most) if edpl else None
+            if members is not None:
+                from ..placement import accumulate_masses_samples_host
+                sample_names, m_off, m_sample, m_weight = members
+                m_read = np.repeat(np.arange(len(unique), dtype=np.uint32), np.diff(m_off.astype(np.int64)))
+                sample_words = accumulate_masses_samples_host(len(tree.nodes), res, len(sample_names), m_sample, member_read=m_read, member_weight=m_weight)
+                reports = _run_reports(et, db, sample_names, sample_words, sample_words, requested, options)
     finally:
         db.close()
+    for name, text in reports.items():
+        setattr(res, name, text)
     pl = hostio.jplace_placements(tree, names, res.n_rows, res.branch, res.score, res.lwr, guppy)
     res.notplaced = hostio.notplaced_log(records, unique, (res.flags & 1) != 0)
     res.reversed = hostio.reversed_log(records, unique, res.flags) if strand != "fwd" else None
@@ -229,24 +237,16 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
     multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
     table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
     No jplace and no frames log: the rows and the frame bytes never reach the host.  With sample_sep (one character) the one call is
-    processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample; with kr as well
-    .kr is the text `--kr FILE` writes, from the buffer that call left on the device, and with squash .squash the text `--squash FILE`
-    writes, from the same buffer, and with epca .epca the text `--epca FILE` writes, from the same buffer again, and with kmeans
-    .kmeans the text `--kmeans FILE` writes, likewise, and with diversity .diversity the text `--diversity FILE` writes."""
+    processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample; the reports of
+    SAMPLE_REPORTS are then asked for as of place_file (.kr, .squash, .epca, .kmeans, .diversity), each from the buffer that call left
+    on the device."""
     from types import SimpleNamespace
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
-    _kmeans_check(kmeans, sample_sep is not None, kmeans_k, kmeans_rounds)
-    _diversity_check(diversity, sample_sep is not None, diversity_theta)
-    if epca and sample_sep is None:
-        raise ValueError(EPCA_NEEDS_SAMPLE_SEP)
-    if epca and not (1 <= epca_components <= 8 and 1 <= epca_iters <= 10000):
-        raise ValueError(EPCA_RANGES)
-    if kr and sample_sep is None:
-        raise ValueError(KR_NEEDS_SAMPLE_SEP)
-    if squash and sample_sep is None:
-        raise ValueError(SQUASH_NEEDS_SAMPLE_SEP)
-    kr_out = squash_out = epca_out = kmeans_out = diversity_out = None
+    requested = dict(kr=kr, squash=squash, epca=epca, kmeans=kmeans, diversity=diversity)
+    options = dict(epca_components=epca_components, epca_iters=epca_iters, kmeans_k=kmeans_k, kmeans_rounds=kmeans_rounds, diversity_theta=diversity_theta)
+    _check_reports(requested, sample_sep is not None, options)
+    reports = dict.fromkeys(requested)
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     try:
         if translate and db.info.alphabet != 20:
@@ -262,24 +262,15 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
             words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMassesSamples(
                 seq, off, len(sample_names), m_sample, member_off=m_off, member_weight=m_weight, **common)
             table = hostio.masses_samples_table(tree, sample_names, words)
-            if kr:
-                kr_out = kr_text(db, tree, sample_names, None, device)
-            if squash:
-                squash_out = squash_text(db, tree, sample_names, None, words, device)
-            if epca:
-                epca_out = epca_text(db, tree, sample_names, None, words, epca_components, epca_iters, device)
-            if kmeans:
-                kmeans_out = kmeans_text(db, tree, sample_names, None, kmeans_k, kmeans_rounds, device)
-            if diversity:
-                diversity_out = diversity_text(db, tree, sample_names, None, diversity_theta, device)
+            with _edge_tree(tree, device, any(requested.values())) as et:
+                reports = _run_reports(et, db, sample_names, None, words, requested, options)
         else:
             words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMasses(seq, off, weights=weights, **common)
             table = hostio.masses_table(tree, words)
     finally:
         db.close()
     return SimpleNamespace(masses=table, notplaced=hostio.notplaced_log(records, unique, (flags & 1) != 0),
-                           reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters, kr=kr_out,
-                           squash=squash_out, epca=epca_out, kmeans=kmeans_out, diversity=diversity_out)
+                           reversed=hostio.reversed_log(records, unique, flags) if strand != "fwd" else None, flags=flags, counters=counters, **reports)
 
 
 def _open_db(db_text, union, dbimage, save_dbimage, device):
@@ -301,6 +292,20 @@ def _open_db(db_text, union, dbimage, save_dbimage, device):
         db = PhyloKmerDB(d["alphabet"], d["k"], d["n_branches"], d["thr_log10"], d["thr"], d["key_codes"], d["row_offsets"],
                          d["branch_ids"], d["scores"], device=device, convert_uo=d.get("convert_uo", False))
     return db, tree
+
+
+def _write_outputs(a, res, base_path):
+    """every file of a run but the jplace: the per-edge table, the reports, --edpl, and the logs under --logs (default: logs/ next to
+    base_path, like the reference's workdir/logs); a text that is None, or that this kind of run does not have, is not written"""
+    files = [(a.masses if a.masses_only is None else a.masses_only, res.masses), (a.edpl, getattr(res, "edpl", None))]
+    files += [(getattr(a, r.name), getattr(res, r.name)) for r in SAMPLE_REPORTS]
+    logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(base_path)), "logs")
+    os.makedirs(logs, exist_ok=True)
+    files += [(os.path.join(logs, kind + "_" + os.path.basename(a.fasta) + ".tsv"), getattr(res, kind, None)) for kind in ("notplaced", "reversed", "frames")]
+    for path, text in files:
+        if text is not None:
+            with open(path, "w") as f:
+                f.write(text)
 
 
 def main(argv=None):
@@ -375,6 +380,8 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--logs", default=None, help="directory of notplaced_<query>.tsv (default: logs/ next to --out, like the reference's workdir/logs)")
     a = ap.parse_args(argv)
+    requested = {r.name: getattr(a, r.name) is not None for r in SAMPLE_REPORTS}
+    options = dict(epca_components=a.epca_components, epca_iters=a.epca_iters, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds, diversity_theta=())
     if a.translate and a.strand != "fwd":
         ap.error(TRANSLATE_WITH_STRAND)
     if a.masses_only is not None and a.masses is not None:
@@ -385,22 +392,9 @@ def main(argv=None):
         ap.error("--sample-sep takes one character")
     if a.sample_sep is not None and a.masses is None and a.masses_only is None:
         ap.error(SAMPLE_SEP_NEEDS_MASSES)
-    if a.kr is not None and a.sample_sep is None:
-        ap.error(KR_NEEDS_SAMPLE_SEP)
-    if a.squash is not None and a.sample_sep is None:
-        ap.error(SQUASH_NEEDS_SAMPLE_SEP)
-    if a.epca is not None and a.sample_sep is None:
-        ap.error(EPCA_NEEDS_SAMPLE_SEP)
-    if a.epca is not None and not (1 <= a.epca_components <= 8 and 1 <= a.epca_iters <= 10000):
-        ap.error(EPCA_RANGES)
-    if a.kmeans is not None and a.sample_sep is None:
-        ap.error(KMEANS_NEEDS_SAMPLE_SEP)
-    if a.kmeans is not None and not (1 <= a.kmeans_k <= 64 and 1 <= a.kmeans_rounds <= 1024):
-        ap.error(KMEANS_RANGES)
-    if a.diversity is not None and a.sample_sep is None:
-        ap.error(DIVERSITY_NEEDS_SAMPLE_SEP)
     try:
-        thetas = parse_thetas(a.diversity_theta)
+        _check_reports(requested, a.sample_sep is not None, options)  # (the thetas, asked for or not, come after the reports' rules)
+        options["diversity_theta"] = parse_thetas(a.diversity_theta)
     except ValueError as e:
         ap.error(str(e))
     if a.edpl is not None and a.out is None:
@@ -414,98 +408,30 @@ def main(argv=None):
     with open(a.fasta, "rb") as f:
         fasta_text = f.read()
     call = "".join(" " + x for x in (argv if argv is not None else sys.argv[1:]))
-    if a.masses_only is not None:
-        return _main_masses_only(a, db_text, fasta_text, thetas)
-    try:
-        doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call,
-                              a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand,
-                              translate=a.translate, masses=a.masses is not None, sample_sep=a.sample_sep, kr=a.kr is not None,
-                              squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters,
-                              edpl=a.edpl is not None, kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds,
-                              diversity=a.diversity is not None, diversity_theta=thetas)
-    except ValueError as e:
-        if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
-            raise
-        print("rappas_amd.tools.place: " + str(e), file=sys.stderr)
-        return 1
-    with open(a.out, "w") as f:
-        f.write(doc)
-    logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.out)), "logs")
-    os.makedirs(logs, exist_ok=True)
-    with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
-        f.write(res.notplaced)
-    if res.reversed is not None:
-        with open(os.path.join(logs, "reversed_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
-            f.write(res.reversed)
-    if res.frames is not None:
-        with open(os.path.join(logs, "frames_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
-            f.write(res.frames)
-    if res.masses is not None:
-        with open(a.masses, "w") as f:
-            f.write(res.masses)
-    if res.kr is not None:
-        with open(a.kr, "w") as f:
-            f.write(res.kr)
-    if res.squash is not None:
-        with open(a.squash, "w") as f:
-            f.write(res.squash)
-    if res.epca is not None:
-        with open(a.epca, "w") as f:
-            f.write(res.epca)
-    if res.kmeans is not None:
-        with open(a.kmeans, "w") as f:
-            f.write(res.kmeans)
-    if res.diversity is not None:
-        with open(a.diversity, "w") as f:
-            f.write(res.diversity)
-    if res.edpl is not None:
-        with open(a.edpl, "w") as f:
-            f.write(res.edpl)
-    placed = int(np.count_nonzero(res.n_rows))
-    print(f"{len(res.n_rows)} unique reads, {placed} placed -> {a.out}", file=sys.stderr)
-    return 0
-
-
-def _main_masses_only(a, db_text, fasta_text, thetas=()):
     import json
     import time
+    common = dict(device=a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate,
+                  sample_sep=a.sample_sep, **requested, **options)
     t0 = time.perf_counter()
     try:
-        res = masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.device, union=a.uniondb is not None,
-                               dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate, sample_sep=a.sample_sep, kr=a.kr is not None,
-                               squash=a.squash is not None, epca=a.epca is not None, epca_components=a.epca_components, epca_iters=a.epca_iters,
-                               kmeans=a.kmeans is not None, kmeans_k=a.kmeans_k, kmeans_rounds=a.kmeans_rounds, diversity=a.diversity is not None,
-                               diversity_theta=thetas)
+        if a.masses_only is not None:
+            doc, res = None, masses_only_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, **common)
+        else:
+            doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call, masses=a.masses is not None,
+                                  edpl=a.edpl is not None, **common)
     except ValueError as e:
         if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
             raise
         print("rappas_amd.tools.place: " + str(e), file=sys.stderr)
         return 1
     t1 = time.perf_counter()
-    with open(a.masses_only, "w") as f:
-        f.write(res.masses)
-    if res.kr is not None:
-        with open(a.kr, "w") as f:
-            f.write(res.kr)
-    if res.squash is not None:
-        with open(a.squash, "w") as f:
-            f.write(res.squash)
-    if res.epca is not None:
-        with open(a.epca, "w") as f:
-            f.write(res.epca)
-    if res.kmeans is not None:
-        with open(a.kmeans, "w") as f:
-            f.write(res.kmeans)
-    if res.diversity is not None:
-        with open(a.diversity, "w") as f:
-            f.write(res.diversity)
-    logs = a.logs if a.logs is not None else os.path.join(os.path.dirname(os.path.abspath(a.masses_only)), "logs")
-    os.makedirs(logs, exist_ok=True)
-    with open(os.path.join(logs, "notplaced_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
-        f.write(res.notplaced)
-    if res.reversed is not None:
-        with open(os.path.join(logs, "reversed_" + os.path.basename(a.fasta) + ".tsv"), "w") as f:
-            f.write(res.reversed)
+    if doc is not None:
+        with open(a.out, "w") as f:
+            f.write(doc)
+    _write_outputs(a, res, a.masses_only if doc is None else a.out)
+    if doc is not None:
+        print(f"{len(res.n_rows)} unique reads, {int(np.count_nonzero(res.n_rows))} placed -> {a.out}", file=sys.stderr)
+        return 0
     print(f"{len(res.flags)} unique reads, {res.counters['placed']} placed -> {a.masses_only}", file=sys.stderr)
     if a.timing:
         print(json.dumps({"mode": "masses_only", "unique_reads": len(res.flags), "db_and_masses_s": round(t1 - t0, 6),
