@@ -7,8 +7,8 @@
 //                            thread owns 5 + 2 NT running sums in registers and up to 8 nodes; per node two divisions, up to four
 //                            logarithms (reused by every theta) and 4 NT exponentials, all binary64 VALU work.  The lane partials are
 //                            folded by halving in the LDS, every column in the same step -> part[sample][chunk][column]
-//   diversity_reduce_kernel  one thread a (sample, column): the chunks in order, the first one as it is; the NaN row of a sample
-//                            without mass, whose partials were never written and are not read
+//   diversity_reduce_kernel  one thread a (sample, column): the chunk rule of rk_samplemath.h; the NaN row of a sample without
+//                            mass, whose partials were never written and are not read
 // Not part of the C ABI.
 #pragma once
 #include "rk_divmath.h"
@@ -61,9 +61,7 @@ __global__ void __launch_bounds__(256) diversity_reduce_kernel(u32 B, u32 S, u32
         return;
     }
     const double *p = part + (u64)s * n_chunks * n_cols + col;
-    double v = p[0];
-    for (u32 k = 1; k < n_chunks; k++) v = v + p[(u64)k * n_cols];
-    out[i] = v;
+    out[i] = chunk_sum(n_chunks, [&](u32 k) { return p[(u64)k * n_cols]; });
 }
 
 }  // namespace rk

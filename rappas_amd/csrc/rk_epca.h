@@ -105,9 +105,10 @@ __global__ void __launch_bounds__(64 * EPCA_WAVES) epca_centre_kernel(u32 B, u32
 // of 256 threads owns a tile of 64 x 64 sample pairs on or above the diagonal and the chunks [blockIdx.y * chunks_per_block,
 // + chunks_per_block); per stage of EPCA_STAGE nodes the centred values of the tile's 64 row samples and 64 column samples go through
 // the LDS -- one matrix, so a thread loads EPCA_STAGE / 2 values a stage, in flight in registers while the stage before is summed --;
-// a thread keeps the same 4 x 4 micro-tile and walks the nodes in ascending id: acc = acc + r * c, two FP64 operations a term.  The
-// chunk rule, the two forms of the chunk sum (to_part: part[chunk], added by kr_reduce_kernel) and the mirror written by the thread
-// that summed the pair are kr_pairs_kernel's.  A diagonal tile sums both triangles (a * b == b * a: the same bits).
+// a thread keeps the same 4 x 4 micro-tile and walks the nodes in ascending id: acc = acc + r * c (gram_term of rk_samplemath.h), two
+// FP64 operations a term.  The chunk rule (chunk_fold), the two forms of the chunk sum (to_part: part[chunk], added by
+// kr_reduce_kernel) and the mirror written by the thread that summed the pair are kr_pairs_kernel's.  A diagonal tile sums both
+// triangles (a * b == b * a: the same bits).  The two kernels stay two texts: rk_samples.h says why above kr_pairs_kernel.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) epca_gram_kernel(u32 B, u32 S, u32 n_tiles_side, u32 chunks_per_block, u32 to_part, const double *Xc, double *G, double *part) {
     __shared__ __attribute__((aligned(16))) double st[EPCA_STAGE * 128];  // [node][rows | columns][64]
@@ -160,10 +161,7 @@ __global__ void __launch_bounds__(256) epca_gram_kernel(u32 B, u32 S, u32 n_tile
 #pragma unroll
                 for (u32 a = 0; a < 4; a++)
 #pragma unroll
-                    for (u32 bb = 0; bb < 4; bb++) {
-                        const double term = r[a] * c[bb];
-                        acc[a][bb] = acc[a][bb] + term;
-                    }
+                    for (u32 bb = 0; bb < 4; bb++) acc[a][bb] = gram_term(acc[a][bb], r[a], c[bb]);
             }
         }
         if (to_part) {
@@ -182,7 +180,7 @@ __global__ void __launch_bounds__(256) epca_gram_kernel(u32 B, u32 S, u32 n_tile
 #pragma unroll
             for (u32 a = 0; a < 4; a++)
 #pragma unroll
-                for (u32 bb = 0; bb < 4; bb++) d[a][bb] = ch == ch_lo ? acc[a][bb] : d[a][bb] + acc[a][bb];
+                for (u32 bb = 0; bb < 4; bb++) d[a][bb] = chunk_fold(ch == ch_lo, d[a][bb], acc[a][bb]);
         }
     }
     if (!to_part && ch_lo < ch_hi) {

@@ -6,10 +6,10 @@
 //   kmeans_init_kernel       active[s] = T_s != 0, n_active, k_eff, status, seed_0 or the caller's seeds, the fillers   (one block)
 //   kmeans_gather_kernel     cu[j] = U[.][seed_j], cv[j] = V[.][seed_j]: the centroid-major profiles the distance kernel stages
 //   kmeans_dist_kernel<KC>   the hot path: (chunk of KR_CHUNK_IDS ids) x (64 samples: one wave a block) x (group of KC centroids); a
-//                            thread owns one sample and KC running sums, U and V come through a register ring, one 512-byte line
-//                            each per node per wave, h / cu_j / cv_j of a tile of the chunk are staged in the LDS -> part[chunk][j][t]
-//   kmeans_reduce_kernel     one thread a sample: the partials of every centroid in chunk order, the first one as it is, and the
-//                            nearest centroid among them -> best[s], bestd[s]
+//                            thread owns one sample and KC running sums, U and V come through node_ring of rk_samples.h, tile after
+//                            tile of the chunk, h / cu_j / cv_j of a tile are staged in the LDS -> part[chunk][j][t]
+//   kmeans_reduce_kernel     one thread a sample: the partials of every centroid by the chunk rule, and the nearest centroid among
+//                            them -> best[s], bestd[s]
 //   kmeans_seed_kernel       the running minimum mind[s] and the next farthest-first seed                               (one block)
 //   kmeans_assign_kernel     assign, dist, changed, the sizes; in the last round within and info, and the done word     (one block)
 //   kmeans_update_kernel     one wave a block, a lane a (node, cluster): the ordered group sums of U and V over the members, the division
@@ -112,30 +112,16 @@ __global__ void __launch_bounds__(KMEANS_WAVE) kmeans_dist_kernel(u32 B, u32 S, 
     if (!__syncthreads_or(need)) return;  // the block's samples are all inactive
     const u32 x_lo = blockIdx.x * KR_CHUNK_IDS, x_hi = min(x_lo + KR_CHUNK_IDS, B);
     const u32 tc = t < S ? t : S - 1;  // (lanes without a sample of their own read the last one's and write nothing)
-    const double *pu = U + tc, *pv = V + tc;
     double acc[KC];
 #pragma unroll
     for (u32 jj = 0; jj < KC; jj++) acc[jj] = 0.0;
-    auto load = [&](double(&lu)[KMEANS_UNROLL], double(&lv)[KMEANS_UNROLL], u32 x0) {
-#pragma unroll
-        for (u32 i = 0; i < KMEANS_UNROLL; i++) {
-            lu[i] = pu[(u64)(x0 + i) * S];
-            lv[i] = pv[(u64)(x0 + i) * S];
-        }
-    };
-    auto term = [&](u32 i, double u, double v) {  // node i of the tile
+    auto term = [&](u32 i, double u, double v) {  // node i of the tile: the centroid is the first operand
         const double hx = uh[i];
 #pragma unroll
         for (u32 jj = 0; jj < KC; jj++) {
             const double2 c = *(const double2 *)uc[i][jj];
-            const double term1 = hx * fabs(c.x - u);
-            const double term2 = hx * fabs(c.y - v);
-            acc[jj] = (acc[jj] + term1) + term2;
+            acc[jj] = kr_term(acc[jj], hx, c.x, u, c.y, v);
         }
-    };
-    auto sum = [&](u32 i0, const double(&lu)[KMEANS_UNROLL], const double(&lv)[KMEANS_UNROLL]) {
-#pragma unroll
-        for (u32 i = 0; i < KMEANS_UNROLL; i++) term(i0 + i, lu[i], lv[i]);
     };
     for (u32 y_lo = x_lo; y_lo < x_hi; y_lo += TILE) {  // the tiles of the chunk in ascending id: the sums run on across them
         const u32 n = min(TILE, x_hi - y_lo);
@@ -150,31 +136,13 @@ __global__ void __launch_bounds__(KMEANS_WAVE) kmeans_dist_kernel(u32 B, u32 S, 
             }
         }
         __syncthreads();
-        u32 x = y_lo;
-        // squash_row_kernel's ring: KMEANS_DEPTH - 1 batches of KMEANS_UNROLL nodes in flight while one is summed
-        const u32 n_batches = n / (KMEANS_UNROLL * KMEANS_DEPTH) * KMEANS_DEPTH;
-        if (n_batches) {
-            double ru[KMEANS_DEPTH][KMEANS_UNROLL], rv[KMEANS_DEPTH][KMEANS_UNROLL];
+        node_ring<KMEANS_UNROLL, KMEANS_DEPTH>(  // (rk_samples.h; a batch reads nothing beside its loads: the tile's LDS words are read in the sum)
+            U + tc, V + tc, S, y_lo, n, [](u32) { return 0; },
+            [&](int, u32 x0, const double(&lu)[KMEANS_UNROLL], const double(&lv)[KMEANS_UNROLL]) {
 #pragma unroll
-            for (u32 d = 0; d + 1 < KMEANS_DEPTH; d++) load(ru[d], rv[d], y_lo + d * KMEANS_UNROLL);
-            for (u32 b0 = 0; b0 < n_batches; b0 += KMEANS_DEPTH) {
-#pragma unroll
-                for (u32 d = 0; d < KMEANS_DEPTH; d++) {
-                    const u32 ahead = min(b0 + d + KMEANS_DEPTH - 1, n_batches - 1);  // (the last batches load the last one again: no branch)
-                    load(ru[(d + KMEANS_DEPTH - 1) % KMEANS_DEPTH], rv[(d + KMEANS_DEPTH - 1) % KMEANS_DEPTH], y_lo + ahead * KMEANS_UNROLL);
-                    __builtin_amdgcn_sched_barrier(0);
-                    sum((b0 + d) * KMEANS_UNROLL, ru[d], rv[d]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            x = y_lo + n_batches * KMEANS_UNROLL;
-        }
-        for (; x + KMEANS_UNROLL <= y_lo + n; x += KMEANS_UNROLL) {  // the batches that fill no group
-            double lu[KMEANS_UNROLL], lv[KMEANS_UNROLL];
-            load(lu, lv, x);
-            sum(x - y_lo, lu, lv);
-        }
-        for (; x < y_lo + n; x++) term(x - y_lo, pu[(u64)x * S], pv[(u64)x * S]);
+                for (u32 i = 0; i < KMEANS_UNROLL; i++) term(x0 - y_lo + i, lu[i], lv[i]);
+            },
+            [&](u32 x, double u, double v) { term(x - y_lo, u, v); });
     }
     if (!need) return;
 #pragma unroll
@@ -189,8 +157,7 @@ __global__ void __launch_bounds__(256) kmeans_reduce_kernel(u32 S, u32 k, u32 n_
     u32 bj = j_base;
     double bd = 0.0;
     for (u32 j = j_base; j < j_hi; j++) {
-        double d = part[(u64)j * S + s];
-        for (u32 c = 1; c < n_chunks; c++) d = d + part[((u64)c * k + j) * S + s];
+        const double d = chunk_sum(n_chunks, [&](u32 c) { return part[((u64)c * k + j) * S + s]; });
         if (j == j_base || d < bd) {
             bd = d;
             bj = j;

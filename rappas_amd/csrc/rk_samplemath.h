@@ -1,0 +1,43 @@
+// rk_samplemath.h -- the terms and the chunk rule of the sample-level sums (include/rappas_place.h holds the definitions; DESIGN.md
+// 4.9 - 4.11, 4.13, 4.14), one text for the kernels (rk_samples.h, rk_epca.h, rk_kmeans.h, rk_diversity.h) and the host twins
+// (rk_samples_host.h), in the manner of rk_divmath.h.  Each line is one rounding: under -ffp-contract=off, and from a compiler that
+// forms no fma of its own, every implementation gives the same bits.  No libm call beyond fabs.  Not part of the C ABI.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define RK_SAMPLEMATH_FN __host__ __device__ inline
+#else
+#define RK_SAMPLEMATH_FN inline
+#endif
+
+namespace rk {
+
+// The KR term: what one node with half length h adds to the sum between the profiles (us, vs) and (ut, vt) -- a difference, a
+// product and an add for u, then the same for v: three FP64 operations each, every one rounded by itself
+RK_SAMPLEMATH_FN double kr_term(double acc, double h, double us, double ut, double vs, double vt) {
+    const double term1 = h * std::fabs(us - ut);
+    const double term2 = h * std::fabs(vs - vt);
+    return (acc + term1) + term2;
+}
+
+// The Gram term: two roundings
+RK_SAMPLEMATH_FN double gram_term(double acc, double a, double b) {
+    const double term = a * b;
+    return acc + term;
+}
+
+// The chunk rule: a sum over the node ids is one partial per chunk of RK_KR_CHUNK ids, each from +0.0 in ascending id, and the
+// partials are added in chunk order, the first one as it is (not onto +0.0: a partial of -0.0 or NaN stays what it is).
+// chunk_fold is one step of it, for whoever meets the partials one by one; chunk_sum the whole of it over p(0 .. n_chunks - 1).
+RK_SAMPLEMATH_FN double chunk_fold(bool first, double d, double p) { return first ? p : d + p; }
+
+template <class P>
+RK_SAMPLEMATH_FN double chunk_sum(uint32_t n_chunks, P &&p) {
+    double d = chunk_fold(true, 0.0, p(0));
+    for (uint32_t c = 1; c < n_chunks; c++) d = chunk_fold(false, d, p(c));
+    return d;
+}
+
+}  // namespace rk

@@ -4,6 +4,7 @@
 // are in rk_samples_impl.h, the host twins in rk_samples_host.h.  Not part of the C ABI.
 #pragma once
 #include "rk_device.h"
+#include "rk_samplemath.h"
 
 namespace rk {
 
@@ -117,11 +118,14 @@ __global__ void __launch_bounds__(256) kr_profiles_kernel(u32 B, u32 S, u64 W, u
 // samples go through the LDS (the next stage's loads are in flight in registers while this one is summed); a thread keeps a 4 x 4
 // micro-tile of pairs -- rows 2ty, 2ty + 1, 32 + 2ty, 33 + 2ty, columns likewise from tx, so that the 16 lanes of a ds_read_b128
 // group read 256 contiguous bytes of the columns and one or two addresses of the rows -- and walks the nodes in ascending id:
-// acc = (acc + h * |u_s - u_t|) + h * |v_s - v_t|, three FP64 operations a term (no contraction).
-// A chunk's partial starts at +0.0.  With n_part == 0 the block holds every chunk and adds the partials in chunk order into D, the
-// first one as it is; otherwise it writes each partial to part[chunk] (S x S doubles each) and kr_reduce_kernel adds them in chunk
-// order.  Either way an entry and its mirror are written by the one thread that summed the pair: no atomics, and the bits depend on
+// acc = (acc + h * |u_s - u_t|) + h * |v_s - v_t| (kr_term of rk_samplemath.h), three FP64 operations a term (no contraction).
+// A chunk's partial starts at +0.0.  With to_part == 0 the block holds every chunk and folds the partials by the chunk rule
+// (chunk_fold) into D; otherwise it writes each partial to part[chunk] (S x S doubles each) and kr_reduce_kernel adds them by the
+// same rule.  Either way an entry and its mirror are written by the one thread that summed the pair: no atomics, and the bits depend on
 // neither grid nor tile.  A diagonal tile sums both triangles (|a - b| == |b - a|: the same bits) and writes no mirror.
+// epca_gram_kernel (rk_epca.h) is this kernel with one staged matrix.  One frame under both was built and measured
+// (profiles/sample_frames_rates.txt): this kernel ran 5 - 7 % slower through it, with the stage loop's instructions unchanged but
+// for the register numbers, so the two stay two texts until that is understood; the terms and the chunk rule are shared.
 // ------------------------------------------------------------------------------------------------
 constexpr u32 KR_TILE = 64, KR_STAGE = 8, KR_CHUNK_IDS = 2048;
 
@@ -181,11 +185,7 @@ __global__ void __launch_bounds__(256) kr_pairs_kernel(u32 B, u32 S, u32 n_tiles
 #pragma unroll
                 for (u32 a = 0; a < 4; a++)
 #pragma unroll
-                    for (u32 bb = 0; bb < 4; bb++) {
-                        const double term1 = hx * fabs(ru[a] - cu[bb]);
-                        const double term2 = hx * fabs(rv[a] - cv[bb]);
-                        acc[a][bb] = (acc[a][bb] + term1) + term2;
-                    }
+                    for (u32 bb = 0; bb < 4; bb++) acc[a][bb] = kr_term(acc[a][bb], hx, ru[a], cu[bb], rv[a], cv[bb]);
             }
         }
         if (to_part) {
@@ -204,7 +204,7 @@ __global__ void __launch_bounds__(256) kr_pairs_kernel(u32 B, u32 S, u32 n_tiles
 #pragma unroll
             for (u32 a = 0; a < 4; a++)
 #pragma unroll
-                for (u32 bb = 0; bb < 4; bb++) d[a][bb] = ch == ch_lo ? acc[a][bb] : d[a][bb] + acc[a][bb];
+                for (u32 bb = 0; bb < 4; bb++) d[a][bb] = chunk_fold(ch == ch_lo, d[a][bb], acc[a][bb]);
         }
     }
     if (!to_part && ch_lo < ch_hi) {
@@ -221,13 +221,11 @@ __global__ void __launch_bounds__(256) kr_pairs_kernel(u32 B, u32 S, u32 n_tiles
     }
 }
 
-// D[i] = part[0][i], then + part[1][i], ... in chunk order: the entries of both triangles hold the same partials
+// D[i] = the partials of entry i by the chunk rule: the entries of both triangles hold the same partials
 __global__ void __launch_bounds__(256) kr_reduce_kernel(u64 n, u32 n_chunks, const double *part, double *D) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    double d = part[i];
-    for (u32 c = 1; c < n_chunks; c++) d = d + part[(u64)c * n + i];
-    D[i] = d;
+    D[i] = chunk_sum(n_chunks, [&](u32 c) { return part[(u64)c * n + i]; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -241,11 +239,9 @@ __global__ void __launch_bounds__(256) kr_reduce_kernel(u64 n, u32 n_chunks, con
 //   squash_pick_finish_kernel  the minimum over the blocks; row k, active[b] = 0, size[a] += size[b]   (one block)
 //   squash_merge_kernel        one thread a node: the new column a of U and V, and a contiguous copy ua, va
 //   squash_row_kernel          the hot path: (chunk of KR_CHUNK_IDS ids) x (group of SQUASH_GROUP samples: one wave); a thread owns one t
-//                              and walks its chunk in ascending id -- the 64 lanes take one 512-byte line of U and one of V a node,
-//                              SQUASH_DEPTH - 1 batches of SQUASH_UNROLL nodes in flight while one is summed, h / ua / va of the
-//                              chunk staged in the LDS -- into part[chunk][t]
-//   squash_row_reduce_kernel   D[min(a, t)][max(a, t)] = the partials of t in chunk order, the first one as it is (the pick reads the
-//                              upper triangle only)
+//                              and walks its chunk by node_ring (below), h / ua / va of the chunk staged in the LDS and read a batch
+//                              at a time, the KR term with the merged cluster as the first operand -- into part[chunk][t]
+//   squash_row_reduce_kernel   D[min(a, t)][max(a, t)] = the partials of t by the chunk rule (the pick reads the upper triangle only)
 // The (distance, a, b) order is total, so any shape of the reduction finds the same pair.
 // ------------------------------------------------------------------------------------------------
 constexpr u32 SQUASH_FILLER = 0xFFFFFFFFu, SQUASH_GROUP = 64, SQUASH_UNROLL = 8, SQUASH_DEPTH = 4, SQUASH_PICK_BLOCKS = 512;
@@ -344,6 +340,53 @@ __global__ void __launch_bounds__(256) squash_merge_kernel(u32 B, u32 S, u32 k, 
     va[x] = v;
 }
 
+// ------------------------------------------------------------------------------------------------
+// node_ring<UNROLL, DEPTH>: the frame of squash_row_kernel and of kmeans_dist_kernel (rk_kmeans.h) -- a thread's walk in ascending id
+// over the nodes [x_lo, x_lo + n) of its own sample's columns pu, pv of U and V (the 64 lanes of a wave take one 512-byte line of
+// each a node).  Whole groups of DEPTH batches of UNROLL nodes go through a ring of register batches, DEPTH - 1 of them in flight
+// while one is summed (a thread's sum is one dependent chain, so what a wave can hide of the loads' latency is what it has in
+// flight).  A batch at x0 is, in this order: q = uniform(x0), what it reads beside the loads; the loads of the batch ahead; a
+// scheduling barrier; sum(q, x0, u, v); a scheduling barrier -- the barriers keep the loads of the batch ahead, and the uniform
+// reads of this one, in front of this one's sum.  Then the batches that fill no group, and term(x, u, v) for the nodes that fill
+// no batch.
+// ------------------------------------------------------------------------------------------------
+template <u32 UNROLL, u32 DEPTH, class Uniform, class Sum, class Term>
+__device__ __forceinline__ void node_ring(const double *pu, const double *pv, u32 S, u32 x_lo, u32 n, Uniform &&uniform, Sum &&sum, Term &&term) {
+    auto load = [&](double(&lu)[UNROLL], double(&lv)[UNROLL], u32 x0) {
+#pragma unroll
+        for (u32 i = 0; i < UNROLL; i++) {
+            lu[i] = pu[(u64)(x0 + i) * S];
+            lv[i] = pv[(u64)(x0 + i) * S];
+        }
+    };
+    const u32 x_hi = x_lo + n, n_batches = n / (UNROLL * DEPTH) * DEPTH;
+    u32 x = x_lo;
+    if (n_batches) {
+        double ru[DEPTH][UNROLL], rv[DEPTH][UNROLL];
+#pragma unroll
+        for (u32 d = 0; d + 1 < DEPTH; d++) load(ru[d], rv[d], x_lo + d * UNROLL);
+        for (u32 b0 = 0; b0 < n_batches; b0 += DEPTH) {
+#pragma unroll
+            for (u32 d = 0; d < DEPTH; d++) {
+                const u32 x0 = x_lo + (b0 + d) * UNROLL, ahead = min(b0 + d + DEPTH - 1, n_batches - 1);  // (the last batches load the last one again: no branch)
+                const auto q = uniform(x0);
+                load(ru[(d + DEPTH - 1) % DEPTH], rv[(d + DEPTH - 1) % DEPTH], x_lo + ahead * UNROLL);
+                __builtin_amdgcn_sched_barrier(0);
+                sum(q, x0, ru[d], rv[d]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        x = x_lo + n_batches * UNROLL;
+    }
+    for (; x + UNROLL <= x_hi; x += UNROLL) {  // the batches that fill no group
+        double lu[UNROLL], lv[UNROLL];
+        const auto q = uniform(x);
+        load(lu, lv, x);
+        sum(q, x, lu, lv);
+    }
+    for (; x < x_hi; x++) term(x, pu[(u64)x * S], pv[(u64)x * S]);
+}
+
 __global__ void __launch_bounds__(SQUASH_GROUP) squash_row_kernel(u32 B, u32 S, u32 k, const SquashRow *merges, const u32 *active, const double *U, const double *V,
                                                          const double *h, const double *ua, const double *va, double *part) {
     __shared__ double uni[3][KR_CHUNK_IDS];  // h, ua, va of the chunk: the same for every thread of the block
@@ -361,70 +404,27 @@ __global__ void __launch_bounds__(SQUASH_GROUP) squash_row_kernel(u32 B, u32 S, 
     __syncthreads();
     if (__ballot(need) == 0) return;  // (a group of several waves: the wave's 64 samples are all inactive or a; no barrier below)
     const u32 tc = t < S ? t : S - 1;  // (lanes without a sample of their own read the last one's and write nothing)
-    const double *pu = U + tc, *pv = V + tc;
     double acc = 0.0;
-    auto load = [&](double(&lu)[SQUASH_UNROLL], double(&lv)[SQUASH_UNROLL], u32 x0) {
-#pragma unroll
-        for (u32 i = 0; i < SQUASH_UNROLL; i++) {
-            lu[i] = pu[(u64)(x0 + i) * S];
-            lv[i] = pv[(u64)(x0 + i) * S];
-        }
-    };
     struct Uniform {  // h, ua, va of a batch: broadcast reads of the LDS
         double h[SQUASH_UNROLL], a[SQUASH_UNROLL], b[SQUASH_UNROLL];
     };
-    auto uniform = [&](Uniform &q, u32 x0) {
+    node_ring<SQUASH_UNROLL, SQUASH_DEPTH>(
+        U + tc, V + tc, S, x_lo, x_hi - x_lo,
+        [&](u32 x0) {
+            Uniform q;
 #pragma unroll
-        for (u32 i = 0; i < SQUASH_UNROLL; i++) {
-            q.h[i] = uni[0][x0 - x_lo + i];
-            q.a[i] = uni[1][x0 - x_lo + i];
-            q.b[i] = uni[2][x0 - x_lo + i];
-        }
-    };
-    auto sum = [&](const Uniform &q, const double(&lu)[SQUASH_UNROLL], const double(&lv)[SQUASH_UNROLL]) {
-#pragma unroll
-        for (u32 i = 0; i < SQUASH_UNROLL; i++) {
-            const double term1 = q.h[i] * fabs(q.a[i] - lu[i]);
-            const double term2 = q.h[i] * fabs(q.b[i] - lv[i]);
-            acc = (acc + term1) + term2;
-        }
-    };
-    u32 x = x_lo;
-    // whole groups of SQUASH_DEPTH batches of SQUASH_UNROLL nodes: a ring of register batches, SQUASH_DEPTH - 1 of them in flight while
-    // one is summed (a thread's sum is one dependent chain, so what a wave can hide of the loads' latency is what it has in flight).
-    // The scheduling barriers keep the loads of the batch ahead, and the uniform loads of this one, in front of this one's sum.
-    const u32 n_batches = (x_hi - x_lo) / (SQUASH_UNROLL * SQUASH_DEPTH) * SQUASH_DEPTH;
-    if (n_batches) {
-        double ru[SQUASH_DEPTH][SQUASH_UNROLL], rv[SQUASH_DEPTH][SQUASH_UNROLL];
-#pragma unroll
-        for (u32 d = 0; d + 1 < SQUASH_DEPTH; d++) load(ru[d], rv[d], x_lo + d * SQUASH_UNROLL);
-        for (u32 b0 = 0; b0 < n_batches; b0 += SQUASH_DEPTH) {
-#pragma unroll
-            for (u32 d = 0; d < SQUASH_DEPTH; d++) {
-                const u32 ahead = min(b0 + d + SQUASH_DEPTH - 1, n_batches - 1);  // (the last batches load the last one again: no branch)
-                Uniform q;
-                uniform(q, x_lo + (b0 + d) * SQUASH_UNROLL);
-                load(ru[(d + SQUASH_DEPTH - 1) % SQUASH_DEPTH], rv[(d + SQUASH_DEPTH - 1) % SQUASH_DEPTH], x_lo + ahead * SQUASH_UNROLL);
-                __builtin_amdgcn_sched_barrier(0);
-                sum(q, ru[d], rv[d]);
-                __builtin_amdgcn_sched_barrier(0);
+            for (u32 i = 0; i < SQUASH_UNROLL; i++) {
+                q.h[i] = uni[0][x0 - x_lo + i];
+                q.a[i] = uni[1][x0 - x_lo + i];
+                q.b[i] = uni[2][x0 - x_lo + i];
             }
-        }
-        x = x_lo + n_batches * SQUASH_UNROLL;
-    }
-    for (; x + SQUASH_UNROLL <= x_hi; x += SQUASH_UNROLL) {  // the batches that fill no group
-        double lu[SQUASH_UNROLL], lv[SQUASH_UNROLL];
-        Uniform q;
-        uniform(q, x);
-        load(lu, lv, x);
-        sum(q, lu, lv);
-    }
-    for (; x < x_hi; x++) {
-        const double hx = uni[0][x - x_lo];
-        const double term1 = hx * fabs(uni[1][x - x_lo] - pu[(u64)x * S]);
-        const double term2 = hx * fabs(uni[2][x - x_lo] - pv[(u64)x * S]);
-        acc = (acc + term1) + term2;
-    }
+            return q;
+        },
+        [&](const Uniform &q, u32, const double(&lu)[SQUASH_UNROLL], const double(&lv)[SQUASH_UNROLL]) {
+#pragma unroll
+            for (u32 i = 0; i < SQUASH_UNROLL; i++) acc = kr_term(acc, q.h[i], q.a[i], lu[i], q.b[i], lv[i]);
+        },
+        [&](u32 x, double u, double v) { acc = kr_term(acc, uni[0][x - x_lo], uni[1][x - x_lo], u, uni[2][x - x_lo], v); });
     if (need) part[(u64)blockIdx.x * S + t] = acc;
 }
 
@@ -432,9 +432,7 @@ __global__ void __launch_bounds__(256) squash_row_reduce_kernel(u32 S, u32 k, u3
     const u32 a = merges[k].a;
     const u32 t = blockIdx.x * 256 + threadIdx.x;
     if (a == SQUASH_FILLER || t >= S || t == a || !active[t]) return;
-    double d = part[t];
-    for (u32 c = 1; c < n_chunks; c++) d = d + part[(u64)c * S + t];
-    D[(u64)min(a, t) * S + max(a, t)] = d;
+    D[(u64)min(a, t) * S + max(a, t)] = chunk_sum(n_chunks, [&](u32 c) { return part[(u64)c * S + t]; });
 }
 
 }  // namespace rk

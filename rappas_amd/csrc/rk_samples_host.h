@@ -7,7 +7,8 @@
 // plain C++, like rk_masses_host.h.  Not part of the C ABI.
 //
 // The KR distance is written as include/rappas_place.h defines it, term by term and in the order fixed there, so that the device and
-// this file give the same bits.  The reference has no counterpart: it stops at the jplace it writes.
+// this file give the same bits: the KR term, the Gram term and the chunk rule are those of rk_samplemath.h, the text the kernels
+// compile.  The reference has no counterpart: it stops at the jplace it writes.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "rk_divmath.h"
+#include "rk_samplemath.h"
 
 namespace rk {
 
@@ -113,21 +115,21 @@ inline void kr_profiles_sample(uint32_t B, uint32_t root, const uint64_t *mass, 
     }
 }
 
-// D(s, t) from the profiles of the two samples, in the order of the definition: nodes in ascending id, a partial per KR_CHUNK ids
-// that starts at +0.0 and takes (acc + term1) + term2 node after node; the partials are added in chunk order, the first one as it is.
-inline double kr_pair(uint32_t B, const double *h, const double *us, const double *vs, const double *ut, const double *vt) {
-    double d = 0.0;
-    for (uint32_t x0 = 0; x0 < B; x0 += KR_CHUNK) {
-        const uint32_t x1 = x0 + KR_CHUNK < B ? x0 + KR_CHUNK : B;
+// A sum over the node ids in the order of the definitions: nodes in ascending id, a partial per KR_CHUNK ids that starts at +0.0 and
+// takes term(acc, x) node after node; the partials by the chunk rule of rk_samplemath.h.
+template <class Term>
+inline double chunk_walk(uint32_t B, Term &&term) {
+    return chunk_sum((B + KR_CHUNK - 1) / KR_CHUNK, [&](uint32_t c) {
+        const uint32_t x0 = c * KR_CHUNK, x1 = x0 + KR_CHUNK < B ? x0 + KR_CHUNK : B;
         double acc = 0.0;
-        for (uint32_t x = x0; x < x1; x++) {
-            const double term1 = h[x] * std::fabs(us[x] - ut[x]);
-            const double term2 = h[x] * std::fabs(vs[x] - vt[x]);
-            acc = (acc + term1) + term2;
-        }
-        d = x0 == 0 ? acc : d + acc;
-    }
-    return d;
+        for (uint32_t x = x0; x < x1; x++) acc = term(acc, x);
+        return acc;
+    });
+}
+
+// D(s, t) from the profiles of the two samples
+inline double kr_pair(uint32_t B, const double *h, const double *us, const double *vs, const double *ut, const double *vt) {
+    return chunk_walk(B, [&](double acc, uint32_t x) { return kr_term(acc, h[x], us[x], ut[x], vs[x], vt[x]); });
 }
 
 // Rows s = s_lo, s_lo + s_step, ... of the matrix: the pairs (s, t >= s), each written at [s][t] and [t][s].  u and v hold the
@@ -248,19 +250,9 @@ inline void epca_centre(uint32_t B, uint32_t S, uint32_t root, const uint8_t *ac
     }
 }
 
-// G[s][t] from the centred rows of the two samples: the chunk rule, acc = acc + (a * b)
+// G[s][t] from the centred rows of the two samples: the same walk, acc = acc + (a * b)
 inline double epca_gram_pair(uint32_t B, const double *xs, const double *xt) {
-    double g = 0.0;
-    for (uint32_t x0 = 0; x0 < B; x0 += KR_CHUNK) {
-        const uint32_t x1 = x0 + KR_CHUNK < B ? x0 + KR_CHUNK : B;
-        double acc = 0.0;
-        for (uint32_t x = x0; x < x1; x++) {
-            const double term = xs[x] * xt[x];
-            acc = acc + term;
-        }
-        g = x0 == 0 ? acc : g + acc;
-    }
-    return g;
+    return chunk_walk(B, [&](double acc, uint32_t x) { return gram_term(acc, xs[x], xt[x]); });
 }
 
 // Rows s = s_lo, s_lo + s_step, ... of G: the pairs (s, t >= s), each written at [s][t] and [t][s]
@@ -633,7 +625,7 @@ inline void diversity_row(uint32_t B, uint32_t root, const uint64_t *mass, const
         for (uint32_t stride = DIVERSITY_LANES / 2; stride > 0; stride >>= 1)
             for (uint32_t j = 0; j < stride; j++)
                 for (uint32_t i = 0; i < C; i++) lanes[(size_t)j * C + i] = lanes[(size_t)j * C + i] + lanes[(size_t)(j + stride) * C + i];
-        for (uint32_t i = 0; i < C; i++) out[i] = x0 == 0 ? lanes[i] : out[i] + lanes[i];
+        for (uint32_t i = 0; i < C; i++) out[i] = chunk_fold(x0 == 0, out[i], lanes[i]);
     }
 }
 
