@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import rk_build_desc, rk_built_db
+from .placement import _ptr
 
 
 @dataclass
@@ -27,10 +28,6 @@ class BuiltDB:
     visits: int              # explored nodes of the branch-and-bound trees
     explore_ms: float
     reduce_ms: float
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def build_db(alphabet, k, states, pp_log10, node_branch, thr_log10, gap_off=None, gap_len=None, limit_to_1_jump=True, device=0):
@@ -50,7 +47,7 @@ def build_db(alphabet, k, states, pp_log10, node_branch, thr_log10, gap_off=None
         if gap_off.shape != (n_sites + 1,) or int(gap_off[-1]) != gap_len.shape[0]:
             raise ValueError("gap_off must have n_sites+1 entries and end at len(gap_len)")
     d = rk_build_desc(alphabet, k, n_nodes, n_sites, n_states, int(gaps), int(bool(limit_to_1_jump)), float(thr_log10),
-                      _ptr(states), _ptr(pp), _ptr(node_branch), _ptr(gap_off) if gaps else None,
+                      _ptr(states), _ptr(pp), _ptr(node_branch), _ptr(gap_off),
                       _ptr(gap_len) if gaps and gap_len.size else None, device, 0)
     b = rk_built_db()
     _lib.check(lib.rk_build_db(C.byref(d), C.byref(b)))

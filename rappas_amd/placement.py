@@ -5,6 +5,11 @@ scalars stand (src/main_v2/SessionNext_v2.java:43-66); `PlacementProcess.process
 src/core/algos/PlacementProcess.java:471-483 that reach the hot path (keepAtMost, keepFactor, treatAmbiguities,
 treatAmbiguitiesWithMax) and returns, per read, what :974-1025 turns into jplace rows.
 No compute happens in Python and nothing here falls back to a CPU implementation.
+
+Every public call is a written-out def over a few shared steps: the handle base (_Handle), the output allocator with its one
+numpy -> torch dtype map (_alloc), the rows of a result set (_rows), the reads of a packed call (_packed_reads), and, for the five
+sample-level analyses, one description a call (_SAMPLE_CALLS) run by one runner a form (_sample_host, EdgeTree._sample_device,
+EdgeTree._sample_batch).
 """
 import collections
 import ctypes as C
@@ -18,7 +23,54 @@ from ._lib import (RK_ALPHABET_AA, RK_ALPHABET_DNA, RK_AMB_MAX, RK_AMB_MEAN, RK_
 
 
 def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _dp(t):
+    return None if t is None else t.data_ptr()
+
+
+def _torch():
+    """torch, imported when a device form first needs it: the package and its host forms work without"""
+    import torch
+    return torch
+
+
+def _stream(dev, stream):
+    """the stream argument of a device call: `stream` (a raw handle), or the current stream of `dev`"""
+    return C.c_void_p(stream if stream is not None else _torch().cuda.current_stream(dev).cuda_stream)
+
+
+# numpy -> torch, by the dtype's kind and size: torch tensors carry unsigned words as the signed type of the same width
+_TORCH_DTYPE = {"u1": "uint8", "u2": "int16", "u4": "int32", "u8": "int64", "f4": "float32", "f8": "float64"}
+
+
+def _alloc(shape, dtype, dev=None):
+    """an output array of a call: zeroed numpy on the host, or (dev: a torch device) an uninitialised tensor of the matching torch
+    dtype there; a structured dtype becomes uint8 [..., itemsize] on the device"""
+    if dev is None:
+        return np.zeros(shape, dtype)
+    torch, dtype = _torch(), np.dtype(dtype)
+    shape = (shape,) if np.isscalar(shape) else tuple(shape)
+    if dtype.names:
+        return torch.empty(shape + (dtype.itemsize,), dtype=torch.uint8, device=dev)
+    return torch.empty(shape, dtype=getattr(torch, _TORCH_DTYPE[dtype.str[1:]]), device=dev)
+
+
+def _grow(owner, attr, dev, need):
+    """the device workspace owner.<attr>, grow-only (the old block goes back to its stream's allocator in stream order)"""
+    work = getattr(owner, attr, None)
+    if work is None or work.device != dev or work.numel() < need:
+        work = _alloc(max(need, 256), np.uint8, dev)
+        setattr(owner, attr, work)
+    return work
+
+
+def _or_error(lib, need, code=_lib.RK_ERR_INVALID):
+    """the answer of a _work_bytes call -- or, when it is 0, the call's error: an RkError of `code` with the text the call left"""
+    if not need:
+        raise _lib.RkError(code, lib.rk_last_error().decode("utf-8", "replace"))
+    return int(need)
 
 
 def _strand(strand):
@@ -36,44 +88,70 @@ def _reads(seq, seq_off):
     return np.ascontiguousarray(seq, dtype=np.uint8), seq_off, seq_off.shape[0] - 1
 
 
+def _packed_reads(packed, lens, fixed_len, flags, seq, seq_off):
+    """the reads of a *Packed* call: (n, the arguments n .. seq_off as the C ABI takes them, the contiguous arrays those point into)"""
+    keep = [np.ascontiguousarray(packed, dtype=np.uint32)] + [None if a is None else np.ascontiguousarray(a, dtype=dt) for a, dt in (
+        (lens, np.uint32), (flags, np.uint32), (seq, np.uint8), (seq_off, np.uint64))]
+    n, wpr = keep[0].shape
+    at = [_ptr(a) for a in keep]
+    return n, (n, at[0], wpr, at[1], fixed_len, at[2], at[3], at[4]), keep
+
+
+def _packed_out(n, wpr, dev=None):
+    """(packed u32 [n, wpr], lens u32 [n], flags u32 [n]): what a read packer writes"""
+    return _alloc((n, wpr), np.uint32, dev), _alloc(n, np.uint32, dev), _alloc(n, np.uint32, dev)
+
+
 def _db_desc(alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets, branch_ids, scores, table_mode, convert_uo, device=0):
     """(rk_db_desc, the contiguous CSR arrays it points into)"""
     csr = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((key_codes, np.uint64), (row_offsets, np.uint64), (branch_ids, np.uint16), (scores, np.float32))]
     return rk_db_desc(alphabet, int(bool(convert_uo)), k, n_branches, float(thr_log10), float(thr), csr[0].shape[0], *map(_ptr, csr), device, table_mode), csr
 
 
+# the arrays of a result set, in the order of rk_result: (name, per read K entries or one, dtype)
+_RESULT = (("n_rows", False, np.uint8), ("branch", True, np.uint16), ("score", True, np.float32), ("lwr", True, np.float64), ("flags", False, np.uint32))
+
+
 def _host_out(n, K, out):
     """`out`, or new host arrays for n reads of K rows"""
-    return out if out is not None else Placements(np.zeros(n, np.uint8), np.zeros((n, K), np.uint16), np.zeros((n, K), np.float32),
-                                                  np.zeros((n, K), np.float64), np.zeros(n, np.uint32), {})
+    return out if out is not None else Placements(*(_alloc((n, K) if rows else n, dt) for _, rows, dt in _RESULT), {})
 
 
 def _device_out(n, K, dev, out, frame=False):
     """`out`, or a new dict of device tensors for n reads of K rows; frame: with the "frame" bytes of place_translated"""
-    import torch
     if out is None:
-        out = {f: torch.empty(shape, dtype=dt, device=dev) for f, shape, dt in (
-            ("n_rows", n, torch.uint8), ("branch", (n, K), torch.int16), ("score", (n, K), torch.float32),
-            ("lwr", (n, K), torch.float64), ("flags", n, torch.int32))}
+        out = {f: _alloc((n, K) if rows else n, dt, dev) for f, rows, dt in _RESULT}
     if frame and "frame" not in out:
-        out["frame"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        out["frame"] = _alloc(n, np.uint8, dev)
     return out
 
 
 def _result(out):
     """rk_result over a Placements (host arrays) or over a dict of device tensors"""
     if isinstance(out, dict):
-        return rk_result(*(out[f].data_ptr() for f in ("n_rows", "branch", "score", "lwr", "flags")))
-    return rk_result(_ptr(out.n_rows), _ptr(out.branch), _ptr(out.score), _ptr(out.lwr), _ptr(out.flags))
+        return rk_result(*(out[f].data_ptr() for f, _, _ in _RESULT))
+    return rk_result(*(_ptr(getattr(out, f)) for f, _, _ in _RESULT))
 
 
-def _stream(dev, stream):
-    import torch
-    return stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-
-
-def _dp(t):
-    return None if t is None else t.data_ptr()
+def _rows(rows, K=None):
+    """the three arrays of a result set that a sum reads -> (rk_result with score and flags null, n, K, device or None).  `rows`: a
+    dict of device tensors, or anything with n_rows u8 [n], branch u16 [n, K] and lwr f64 [n, K] on the host, which are made contiguous
+    and checked against each other.  K None: from the shape of branch."""
+    if isinstance(rows, dict):
+        n_rows, branch, lwr = rows["n_rows"], rows["branch"], rows["lwr"]
+        n, K = (n_rows.numel(), K) if K is not None else branch.shape
+        return rk_result(n_rows.data_ptr(), branch.data_ptr(), None, lwr.data_ptr(), None), n, K, branch.device
+    n_rows, branch, lwr = (np.ascontiguousarray(getattr(rows, f), dtype=dt) for f, dt in (("n_rows", np.uint8), ("branch", np.uint16), ("lwr", np.float64)))
+    if K is not None:
+        n, what = n_rows.size, f" = {n_rows.size} x {K}"
+    else:
+        n, what = n_rows.shape[0], ""
+        K = branch.shape[1] if branch.ndim == 2 else (branch.size // n if n else 1)
+    if branch.size != n * K or lwr.size != n * K:
+        raise ValueError(f"branch and lwr must hold n_reads x K{what} rows")
+    res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
+    res.keep = (n_rows, branch, lwr)  # the arrays live as long as the addresses
+    return res, n, K, None
 
 
 def _counters(ct):
@@ -101,9 +179,7 @@ def pack_reads(alphabet, k, seq, seq_off, words_per_read=None, convert_uo=False,
     if words_per_read is None:
         max_len = int((seq_off[1:] - seq_off[:-1]).max()) if n else 0
         words_per_read = max(1, (max_len * bits + 31) // 32)
-    packed = np.zeros((n, words_per_read), np.uint32)
-    lens = np.zeros(n, np.uint32)
-    flags = np.zeros(n, np.uint32)
+    packed, lens, flags = _packed_out(n, words_per_read)
     _lib.check(lib.rk_pack_reads(alphabet, int(bool(convert_uo)), k, n, _ptr(seq), _ptr(seq_off), words_per_read, _ptr(packed), _ptr(lens), _ptr(flags), threads))
     return packed, lens, flags
 
@@ -124,10 +200,8 @@ def translate_packed_host(dna, frame, lens=None, fixed_len=0, aa_words=None):
         lens = np.ascontiguousarray(lens, dtype=np.uint32)
     if aa_words is None:
         aa_words = translated_words(dna_words * 16 if lens is not None else fixed_len)
-    aa = np.zeros((n, aa_words), np.uint32)
-    aa_lens = np.zeros(n, np.uint32)
-    _lib.check(lib.rk_translate_packed_host(frame, n, _ptr(dna), dna_words, None if lens is None else _ptr(lens), fixed_len, _ptr(aa), aa_words,
-                                            _ptr(aa_lens)))
+    aa, aa_lens = _alloc((n, aa_words), np.uint32), _alloc(n, np.uint32)
+    _lib.check(lib.rk_translate_packed_host(frame, n, _ptr(dna), dna_words, _ptr(lens), fixed_len, _ptr(aa), aa_words, _ptr(aa_lens)))
     return aa, aa_lens
 
 
@@ -147,9 +221,9 @@ def _host_masses(words, masses):
 
 def _device_masses(words, masses, dev, stream):
     """the mass buffer of a device call: an int64 tensor of `words` words on `dev`, made and zeroed on the call's stream when None"""
-    import torch
+    torch = _torch()
     if masses is None:
-        masses = torch.empty(words, dtype=torch.int64, device=dev)
+        masses = _alloc(words, np.uint64, dev)
         if stream is not None:
             with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
                 masses.zero_()
@@ -160,6 +234,13 @@ def _device_masses(words, masses, dev, stream):
     return masses
 
 
+def _i32_tensor(t, n, dev, what):
+    """None, or `t` checked: a contiguous int32 tensor of n words on `dev`"""
+    if t is not None and (t.dtype != _torch().int32 or t.numel() != n or not t.is_contiguous() or t.device != dev):
+        raise ValueError(f"{what} must be a contiguous int32 tensor of {n} words on {dev}")
+    return t
+
+
 def accumulate_masses_host(n_branches, placements, weights=None, masses=None, threads=0):
     """rk_masses_accumulate_host (no GPU): the per-branch LWR sums of a result set (`placements`: a Placements, or anything with
     n_rows u8 [n], branch u16 [n, K] and lwr f64 [n, K]) ADDED into `masses`, a uint64 array of masses_words(n_branches) -- mass_q30[B] |
@@ -168,20 +249,13 @@ def accumulate_masses_host(n_branches, placements, weights=None, masses=None, th
     words = masses_words(n_branches)
     if not words:
         raise ValueError(f"n_branches={n_branches} must be in 1..65535")
-    n_rows = np.ascontiguousarray(placements.n_rows, dtype=np.uint8)
-    branch = np.ascontiguousarray(placements.branch, dtype=np.uint16)
-    lwr = np.ascontiguousarray(placements.lwr, dtype=np.float64)
-    n = n_rows.shape[0]
-    K = branch.shape[1] if branch.ndim == 2 else (branch.size // n if n else 1)
-    if branch.size != n * K or lwr.size != n * K:
-        raise ValueError("branch and lwr must hold n_reads x K rows")
+    res, n, K, _ = _rows(placements)
     if weights is not None:
         weights = np.ascontiguousarray(weights, dtype=np.uint32)
         if weights.shape != (n,):
             raise ValueError("weights must hold one uint32 per read")
     masses = _host_masses(words, masses)
-    res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
-    _lib.check(lib.rk_masses_accumulate_host(n_branches, K, n, C.byref(res), None if weights is None else _ptr(weights), _ptr(masses), threads))
+    _lib.check(lib.rk_masses_accumulate_host(n_branches, K, n, C.byref(res), _ptr(weights), _ptr(masses), threads))
     return masses
 
 
@@ -215,19 +289,12 @@ def accumulate_masses_samples_host(n_branches, placements, n_samples, member_sam
     range -- made and zeroed when None.  member_read None: entry i is read i; member_weight None: 1."""
     lib = _lib.load()
     masses = _samples_buffer(n_branches, n_samples, masses)
-    n_rows = np.ascontiguousarray(placements.n_rows, dtype=np.uint8)
-    branch = np.ascontiguousarray(placements.branch, dtype=np.uint16)
-    lwr = np.ascontiguousarray(placements.lwr, dtype=np.float64)
-    n = n_rows.shape[0]
-    K = branch.shape[1] if branch.ndim == 2 else (branch.size // n if n else 1)
-    if branch.size != n * K or lwr.size != n * K:
-        raise ValueError("branch and lwr must hold n_reads x K rows")
+    res, n, K, _ = _rows(placements)
     member_sample = np.ascontiguousarray(member_sample, dtype=np.uint32)
     m = member_sample.shape[0]
     member_read, member_weight = _u32_list(member_read, m, "member_read"), _u32_list(member_weight, m, "member_weight")
-    res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
-    _lib.check(lib.rk_masses_accumulate_samples_host(n_branches, K, n, C.byref(res), n_samples, m, None if member_read is None else _ptr(member_read),
-                                                     _ptr(member_sample), None if member_weight is None else _ptr(member_weight), _ptr(masses), threads))
+    _lib.check(lib.rk_masses_accumulate_samples_host(n_branches, K, n, C.byref(res), n_samples, m, _ptr(member_read), _ptr(member_sample),
+                                                     _ptr(member_weight), _ptr(masses), threads))
     return masses
 
 
@@ -237,9 +304,7 @@ def host_alloc(shape, dtype):
     lib = _lib.load()
     shape = (shape,) if np.isscalar(shape) else tuple(shape)
     nbytes = max(1, int(np.prod(shape)) * np.dtype(dtype).itemsize)
-    p = lib.rk_host_alloc(nbytes)
-    if not p:
-        raise _lib.RkError(_lib.RK_ERR_NOMEM, lib.rk_last_error().decode("utf-8", "replace"))
+    p = _or_error(lib, lib.rk_host_alloc(nbytes), _lib.RK_ERR_NOMEM)
     return np.ctypeslib.as_array((C.c_uint8 * nbytes).from_address(p)).view(dtype)[:int(np.prod(shape))].reshape(shape)
 
 
@@ -272,13 +337,47 @@ def db_image_info(path):
     return info, buf.raw[:n.value]
 
 
-class PhyloKmerDB:
+class _Handle:
+    """A handle of the C ABI and its life: made by a create call of the library current at that moment, read through `handle` while it
+    is open, freed by close() or with the object.  A class names its destroy call and the text of its closed-handle error."""
+    _destroy = _closed = None
+
+    @classmethod
+    def _adopt(cls, lib, create, *args):
+        """a new object around the handle that lib.<create>(*args, &handle) makes, without the class's __init__"""
+        self = cls.__new__(cls)
+        self._open(lib, create, *args)
+        return self
+
+    def _open(self, lib, create, *args):
+        self._lib = lib
+        self._h = C.c_void_p()
+        _lib.check(getattr(lib, create)(*args, C.byref(self._h)))
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise RuntimeError(self._closed)
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PhyloKmerDB(_Handle):
     """Phylo-kmer DB resident in one GPU's HBM (open-addressed / direct table + CSR rows)."""
+    _destroy, _closed = "rk_db_destroy", "PhyloKmerDB is closed"
 
     def __init__(self, alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets, branch_ids, scores,
                  device=0, table_mode=RK_TABLE_AUTO, convert_uo=False):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
         d, (key_codes, row_offsets, branch_ids, scores) = _db_desc(alphabet, k, n_branches, thr_log10, thr, key_codes, row_offsets, branch_ids,
                                                                    scores, table_mode, convert_uo, device)
         if row_offsets.shape[0] != key_codes.shape[0] + 1:
@@ -287,25 +386,20 @@ class PhyloKmerDB:
             raise ValueError("row_offsets[-1] must equal len(branch_ids)")
         if branch_ids.shape[0] != scores.shape[0]:
             raise ValueError("branch_ids and scores differ in length")
-        _lib.check(self._lib.rk_db_create(C.byref(d), C.byref(self._h)))
-        self._read_info()
+        self._open(_lib.load(), "rk_db_create", C.byref(d))
+
+    def _open(self, lib, create, *args):
+        super()._open(lib, create, *args)
+        self.info = rk_db_info()
+        _lib.check(self._lib.rk_db_get_info(self._h, C.byref(self.info)))
 
     @classmethod
     def synthetic(cls, spec, device=0, table_mode=RK_TABLE_AUTO, convert_uo=False):
         """The seeded synthetic database of SURVEY 8(d) generated on the device straight into the HBM image
         (rk_db_create_synth); `spec` is a rappas_amd.synth.SynthSpec, whose numpy twin regenerates any row on the host."""
-        self = cls.__new__(cls)
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
         d = _lib.rk_synth_desc(spec.alphabet, int(bool(convert_uo)), spec.k, spec.n_branches, float(spec.thr_log10), float(spec.thr),
                                int(spec.seed) & 0xFFFFFFFFFFFFFFFF, float(spec.key_fraction), float(spec.mean_row_len), device, table_mode)
-        _lib.check(self._lib.rk_db_create_synth(C.byref(d), C.byref(self._h)))
-        self._read_info()
-        return self
-
-    def _read_info(self):
-        self.info = rk_db_info()
-        _lib.check(self._lib.rk_db_get_info(self._h, C.byref(self.info)))
+        return cls._adopt(_lib.load(), "rk_db_create_synth", C.byref(d))
 
     def save(self, path, user=b""):
         """rk_db_save: this handle's HBM image as a file (the reference's SessionNext_v2.storeHash, SessionNext_v2.java:110-154);
@@ -316,21 +410,11 @@ class PhyloKmerDB:
     @classmethod
     def load(cls, path, device=0):
         """rk_db_load: a handle from an image file -- mmap + one upload per section, no rebuild (SessionNext_v2.load, :158-207)."""
-        self = cls.__new__(cls)
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        _lib.check(self._lib.rk_db_load(str(path).encode(), device, C.byref(self._h)))
-        self._read_info()
-        return self
+        return cls._adopt(_lib.load(), "rk_db_load", str(path).encode(), device)
 
     def clone(self, device=0):
         """rk_db_clone: another handle of this database on `device`, copied device to device (no rebuild, no host round trip)."""
-        other = type(self).__new__(type(self))
-        other._lib = self._lib
-        other._h = C.c_void_p()
-        _lib.check(self._lib.rk_db_clone(self.handle, device, C.byref(other._h)))
-        other._read_info()
-        return other
+        return type(self)._adopt(self._lib, "rk_db_clone", self.handle, device)
 
     def fetch_row(self, code):
         """(branch_ids u16[len], scores f32[len]) of one k-mer code as stored in the HBM image; empty arrays if absent
@@ -347,12 +431,6 @@ class PhyloKmerDB:
         return cls(db.alphabet, db.k, db.n_branches, db.thr_log10, db.thr, db.key_codes, db.row_offsets,
                    db.branch_ids, db.scores, **kw)
 
-    @property
-    def handle(self):
-        if not self._h:
-            raise RuntimeError("PhyloKmerDB is closed")
-        return self._h
-
     def set_lanes_per_read(self, lanes):
         _lib.check(self._lib.rk_set_lanes_per_read(self.handle, lanes))
 
@@ -361,17 +439,6 @@ class PhyloKmerDB:
 
     def packed_words(self, max_len):
         return int(self._lib.rk_packed_words(self.handle, max_len))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.rk_db_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class PlacementProcess:
@@ -386,14 +453,23 @@ class PlacementProcess:
         amb = RK_AMB_SKIP if not treatAmbiguities else (RK_AMB_MAX if treatAmbiguitiesWithMax else RK_AMB_MEAN)
         return rk_params(keepAtMost, keepFactor, amb, self.ns_bound)
 
-    def _work(self, attr, dev, need):
-        """the device workspace self.<attr>, grow-only (the old block goes back to its stream's allocator in stream order)"""
-        import torch
-        work = getattr(self, attr, None)
-        if work is None or work.device != dev or work.numel() < need:
-            work = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-            setattr(self, attr, work)
-        return work
+    def _place_into(self, fn, head, reads, n, rule, out, translated=False):
+        """one host placement call with a result set: fn(*head, &params, *reads, &result, [frame,] &counters) into `out` (made when
+        None), the counters left in out.counters.  rule: (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)"""
+        out = _host_out(n, rule[0], out)
+        if translated and (getattr(out, "frame", None) is None or out.frame.shape != (n,)):
+            out.frame = np.full(n, _lib.RK_FRAME_NONE, np.uint8)
+        res, p, ct = _result(out), self._params(*rule), rk_counters()
+        _lib.check(fn(*head, C.byref(p), *reads, C.byref(res), *((_ptr(out.frame),) if translated else ()), C.byref(ct)))
+        out.counters = _counters(ct)
+        return out
+
+    def _place_masses(self, fn, reads, rule, sums):
+        """one profile-only call: fn(handle, &params, *reads, *sums, &counters), where `sums` are host arrays, None or numbers and end
+        with the mass buffer and the flags -> (masses, flags, counters)"""
+        p, ct = self._params(*rule), rk_counters()
+        _lib.check(fn(self.db.handle, C.byref(p), *reads, *(_ptr(a) if isinstance(a, np.ndarray) else a for a in sums), C.byref(ct)))
+        return sums[-2], sums[-1], _counters(ct)
 
     def processQueries(self, seq, seq_off, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
                        treatAmbiguitiesWithMax=False, out=None, strand="forward"):
@@ -403,20 +479,10 @@ class PlacementProcess:
         complements, "both" = per read the strand with the better best score (rk_place_batch_strands; RK_FLAG_REVERSE marks the
         results that come from the reverse complement)."""
         seq, seq_off, n = _reads(seq, seq_off)
-        K = keepAtMost
-        out = _host_out(n, K, out)
-        res = _result(out)
-        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        ct = rk_counters()
-        st = _strand(strand)
+        rule, st = (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax), _strand(strand)
         if st == _lib.RK_STRAND_FORWARD:
-            _lib.check(self._lib.rk_place_batch(self.db.handle, C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res),
-                                                C.byref(ct)))
-        else:
-            _lib.check(self._lib.rk_place_batch_strands(self.db.handle, C.byref(p), st, n, _ptr(seq), _ptr(seq_off), C.byref(res),
-                                                        C.byref(ct)))
-        out.counters = _counters(ct)
-        return out
+            return self._place_into(self._lib.rk_place_batch, (self.db.handle,), (n, _ptr(seq), _ptr(seq_off)), n, rule, out)
+        return self._place_into(self._lib.rk_place_batch_strands, (self.db.handle,), (st, n, _ptr(seq), _ptr(seq_off)), n, rule, out)
 
     def processQueriesTranslated(self, seq, seq_off, keepAtMost=7, keepFactor=0.01, out=None):
         """rk_place_batch_translated (amino-acid databases): DNA reads as characters, every read translated in its six reading frames
@@ -424,17 +490,8 @@ class PlacementProcess:
         more array, `frame` (u8 [n]: 0..2 forward from base 0, 1, 2; 3..5 the reverse complement; 0xFF = no result).  Reads with an
         ambiguity code or an unsupported character come back unplaced with their flag."""
         seq, seq_off, n = _reads(seq, seq_off)
-        K = keepAtMost
-        out = _host_out(n, K, out)
-        if getattr(out, "frame", None) is None or out.frame.shape != (n,):
-            out.frame = np.full(n, _lib.RK_FRAME_NONE, np.uint8)
-        res = _result(out)
-        p = self._params(keepAtMost, keepFactor, True, False)
-        ct = rk_counters()
-        _lib.check(self._lib.rk_place_batch_translated(self.db.handle, C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res), _ptr(out.frame),
-                                                       C.byref(ct)))
-        out.counters = _counters(ct)
-        return out
+        return self._place_into(self._lib.rk_place_batch_translated, (self.db.handle,), (n, _ptr(seq), _ptr(seq_off)), n,
+                                (keepAtMost, keepFactor, True, False), out, translated=True)
 
     def pack_reads_host(self, seq, seq_off, max_len=None, threads=0, out=None):
         """rk_pack_reads_host: ASCII reads -> (packed u32 [n, wpr], lens u32 [n], flags u32 [n]) on the host, the records the
@@ -447,9 +504,7 @@ class PlacementProcess:
             packed, lens, flags = out
             assert packed.shape == (n, wpr) and packed.dtype == np.uint32 and lens.shape == (n,) and flags.shape == (n,)
         else:
-            packed = np.zeros((n, wpr), np.uint32)
-            lens = np.zeros(n, np.uint32)
-            flags = np.zeros(n, np.uint32)
+            packed, lens, flags = _packed_out(n, wpr)
         _lib.check(self._lib.rk_pack_reads_host(self.db.handle, n, _ptr(seq), _ptr(seq_off), wpr, _ptr(packed), _ptr(lens), _ptr(flags), threads))
         return packed, lens, flags
 
@@ -457,20 +512,17 @@ class PlacementProcess:
                              treatAmbiguities=True, treatAmbiguitiesWithMax=False, out=None):
         """rk_place_batch_packed: processQueries for reads already packed on the host (38 instead of 150 bytes per 150-bp read over
         PCIe); seq / seq_off are only needed for reads flagged AMBIGUOUS.  `out`: a Placements whose arrays are reused."""
-        packed = np.ascontiguousarray(packed, dtype=np.uint32)
-        n, wpr = packed.shape
-        K = keepAtMost
-        out = _host_out(n, K, out)
-        res = _result(out)
-        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        ct = rk_counters()
-        keep = [np.ascontiguousarray(a, dtype=dt) if a is not None else None
-                for a, dt in ((lens, np.uint32), (flags, np.uint32), (seq, np.uint8), (seq_off, np.uint64))]
-        ptrs = [None if a is None else _ptr(a) for a in keep]
-        _lib.check(self._lib.rk_place_batch_packed(self.db.handle, C.byref(p), n, _ptr(packed), wpr, ptrs[0], fixed_len, ptrs[1],
-                                                   ptrs[2], ptrs[3], C.byref(res), C.byref(ct)))
-        out.counters = _counters(ct)
-        return out
+        n, reads, _keep = _packed_reads(packed, lens, fixed_len, flags, seq, seq_off)
+        return self._place_into(self._lib.rk_place_batch_packed, (self.db.handle,), reads, n,
+                                (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax), out)
+
+    def _flags_out(self, n, flags_out):
+        """the flags of a profile-only call: made when None, else checked"""
+        if flags_out is None:
+            return np.zeros(n, np.uint32)
+        if flags_out.dtype != np.uint32 or flags_out.shape != (n,) or not flags_out.flags.c_contiguous:
+            raise ValueError("flags_out must be a contiguous uint32 array with one word per read")
+        return flags_out
 
     def _masses_args(self, n, weights, masses, flags_out):
         """(weights u32 [n] or None, masses u64 [2B + 4], flags u32 [n]) of a profile-only call, checked / made"""
@@ -479,12 +531,7 @@ class PlacementProcess:
             weights = np.asarray(weights, dtype=np.uint32)
         if weights is not None and (weights.dtype != np.uint32 or weights.shape != (n,) or not weights.flags.c_contiguous):
             raise ValueError("weights must be a contiguous uint32 array with one word per read")
-        masses = _host_masses(words, masses)
-        if flags_out is None:
-            flags_out = np.zeros(n, np.uint32)
-        elif flags_out.dtype != np.uint32 or flags_out.shape != (n,) or not flags_out.flags.c_contiguous:
-            raise ValueError("flags_out must be a contiguous uint32 array with one word per read")
-        return weights, masses, flags_out
+        return weights, _host_masses(words, masses), self._flags_out(n, flags_out)
 
     def processQueriesMasses(self, seq, seq_off, weights=None, masses=None, strand="forward", translate=False, keepAtMost=7, keepFactor=0.01,
                              treatAmbiguities=True, treatAmbiguitiesWithMax=False, flags_out=None):
@@ -494,32 +541,21 @@ class PlacementProcess:
         has received exactly what accumulate_masses_host would add for that call's result set and `weights` (uint32 [n], None = 1 a
         read); flags and counters are that call's.  The frame bytes of the translated step do not come back."""
         seq, seq_off, n = _reads(seq, seq_off)
-        weights, masses, flags_out = self._masses_args(n, weights, masses, flags_out)
-        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        ct = rk_counters()
+        sums = self._masses_args(n, weights, masses, flags_out)
         step = _lib.RK_STEP_TRANSLATED if translate else _strand(strand)
-        _lib.check(self._lib.rk_place_batch_masses(self.db.handle, C.byref(p), step, n, _ptr(seq), _ptr(seq_off),
-                                                   None if weights is None else _ptr(weights), _ptr(masses), _ptr(flags_out), C.byref(ct)))
-        return masses, flags_out, _counters(ct)
+        return self._place_masses(self._lib.rk_place_batch_masses, (step, n, _ptr(seq), _ptr(seq_off)),
+                            (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax), sums)
 
     def processQueriesPackedMasses(self, packed, lens=None, fixed_len=0, flags=None, seq=None, seq_off=None, weights=None, masses=None,
                                    keepAtMost=7, keepFactor=0.01, treatAmbiguities=True, treatAmbiguitiesWithMax=False, flags_out=None):
         """rk_place_batch_packed_masses: processQueriesMasses for reads already packed on the host (the arguments of
         processQueriesPacked); the same (masses, flags, counters)."""
-        packed = np.ascontiguousarray(packed, dtype=np.uint32)
-        n, wpr = packed.shape
-        weights, masses, flags_out = self._masses_args(n, weights, masses, flags_out)
-        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        ct = rk_counters()
-        keep = [np.ascontiguousarray(a, dtype=dt) if a is not None else None
-                for a, dt in ((lens, np.uint32), (flags, np.uint32), (seq, np.uint8), (seq_off, np.uint64))]
-        ptrs = [None if a is None else _ptr(a) for a in keep]
-        _lib.check(self._lib.rk_place_batch_packed_masses(self.db.handle, C.byref(p), n, _ptr(packed), wpr, ptrs[0], fixed_len, ptrs[1], ptrs[2], ptrs[3],
-                                                          None if weights is None else _ptr(weights), _ptr(masses), _ptr(flags_out), C.byref(ct)))
-        return masses, flags_out, _counters(ct)
+        n, reads, _keep = _packed_reads(packed, lens, fixed_len, flags, seq, seq_off)
+        sums = self._masses_args(n, weights, masses, flags_out)
+        return self._place_masses(self._lib.rk_place_batch_packed_masses, reads, (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax), sums)
 
     def _members_args(self, n, n_samples, member_off, member_sample, member_weight, masses, flags_out):
-        """(member_off u64 [n + 1] or None, member_sample u32, member_weight u32 or None, masses, flags) of a per-sample call"""
+        """(n_samples, member_off u64 [n + 1] or None, member_sample u32, member_weight u32 or None, masses, flags) of a per-sample call"""
         masses = _samples_buffer(self.db.info.n_branches, n_samples, masses)
         if member_off is not None:
             member_off = np.ascontiguousarray(member_off, dtype=np.uint64)
@@ -527,11 +563,7 @@ class PlacementProcess:
                 raise ValueError("member_off must hold n_reads + 1 uint64 words")
         m = int(member_off[-1]) if member_off is not None else n
         member_sample, member_weight = _u32_list(member_sample, m, "member_sample"), _u32_list(member_weight, m, "member_weight")
-        if flags_out is None:
-            flags_out = np.zeros(n, np.uint32)
-        elif flags_out.dtype != np.uint32 or flags_out.shape != (n,) or not flags_out.flags.c_contiguous:
-            raise ValueError("flags_out must be a contiguous uint32 array with one word per read")
-        return member_off, member_sample, member_weight, masses, flags_out
+        return n_samples, member_off, member_sample, member_weight, masses, self._flags_out(n, flags_out)
 
     def processQueriesMassesSamples(self, seq, seq_off, n_samples, member_sample, member_off=None, member_weight=None, masses=None, strand="forward",
                                     translate=False, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True, treatAmbiguitiesWithMax=False, flags_out=None):
@@ -540,49 +572,28 @@ class PlacementProcess:
         (masses uint64 [masses_samples_words(B, n_samples)], flags uint32 [n], counters): `masses` (made and zeroed when None) has
         received what accumulate_masses_samples_host would add for that call's result set with the entries expanded."""
         seq, seq_off, n = _reads(seq, seq_off)
-        member_off, member_sample, member_weight, masses, flags_out = self._members_args(n, n_samples, member_off, member_sample, member_weight, masses, flags_out)
-        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        ct = rk_counters()
+        sums = self._members_args(n, n_samples, member_off, member_sample, member_weight, masses, flags_out)
         step = _lib.RK_STEP_TRANSLATED if translate else _strand(strand)
-        _lib.check(self._lib.rk_place_batch_masses_samples(self.db.handle, C.byref(p), step, n, _ptr(seq), _ptr(seq_off), n_samples,
-                                                           None if member_off is None else _ptr(member_off), _ptr(member_sample),
-                                                           None if member_weight is None else _ptr(member_weight), _ptr(masses), _ptr(flags_out), C.byref(ct)))
-        return masses, flags_out, _counters(ct)
+        return self._place_masses(self._lib.rk_place_batch_masses_samples, (step, n, _ptr(seq), _ptr(seq_off)),
+                            (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax), sums)
 
     def processQueriesPackedMassesSamples(self, packed, n_samples, member_sample, member_off=None, member_weight=None, lens=None, fixed_len=0, flags=None,
                                           seq=None, seq_off=None, masses=None, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
                                           treatAmbiguitiesWithMax=False, flags_out=None):
         """rk_place_batch_packed_masses_samples: processQueriesMassesSamples for reads already packed on the host (the arguments of
         processQueriesPacked); the same (masses, flags, counters)."""
-        packed = np.ascontiguousarray(packed, dtype=np.uint32)
-        n, wpr = packed.shape
-        member_off, member_sample, member_weight, masses, flags_out = self._members_args(n, n_samples, member_off, member_sample, member_weight, masses, flags_out)
-        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        ct = rk_counters()
-        keep = [np.ascontiguousarray(a, dtype=dt) if a is not None else None
-                for a, dt in ((lens, np.uint32), (flags, np.uint32), (seq, np.uint8), (seq_off, np.uint64))]
-        ptrs = [None if a is None else _ptr(a) for a in keep]
-        _lib.check(self._lib.rk_place_batch_packed_masses_samples(self.db.handle, C.byref(p), n, _ptr(packed), wpr, ptrs[0], fixed_len, ptrs[1], ptrs[2], ptrs[3],
-                                                                  n_samples, None if member_off is None else _ptr(member_off), _ptr(member_sample),
-                                                                  None if member_weight is None else _ptr(member_weight), _ptr(masses), _ptr(flags_out),
-                                                                  C.byref(ct)))
-        return masses, flags_out, _counters(ct)
+        n, reads, _keep = _packed_reads(packed, lens, fixed_len, flags, seq, seq_off)
+        sums = self._members_args(n, n_samples, member_off, member_sample, member_weight, masses, flags_out)
+        return self._place_masses(self._lib.rk_place_batch_packed_masses_samples, reads, (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax), sums)
 
     def processQueriesMulti(self, dbs, seq, seq_off, keepAtMost=7, keepFactor=0.01, treatAmbiguities=True,
                             treatAmbiguitiesWithMax=False, out=None):
         """processQueries over several device handles of the same database from this one process
         (rk_place_batch_multi: contiguous shards, one host thread per handle, no collective)."""
         seq, seq_off, n = _reads(seq, seq_off)
-        K = keepAtMost
-        out = _host_out(n, K, out)
-        res = _result(out)
-        p = self._params(keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax)
-        ct = rk_counters()
         handles = (C.c_void_p * len(dbs))(*[d.handle for d in dbs])
-        _lib.check(self._lib.rk_place_batch_multi(handles, len(dbs), C.byref(p), n, _ptr(seq), _ptr(seq_off), C.byref(res),
-                                                  C.byref(ct)))
-        out.counters = _counters(ct)
-        return out
+        return self._place_into(self._lib.rk_place_batch_multi, (handles, len(dbs)), (n, _ptr(seq), _ptr(seq_off)), n,
+                                (keepAtMost, keepFactor, treatAmbiguities, treatAmbiguitiesWithMax), out)
 
     # ---- device-resident variant (torch tensors only carry the memory and the stream) ----
     def place_packed(self, packed, fixed_len=0, lens=None, flags_in=None, seq_ascii=None, seq_off=None, out=None,
@@ -600,17 +611,16 @@ class PlacementProcess:
         sd = _strand(strand)
         if sd == _lib.RK_STRAND_FORWARD:
             _lib.check(self._lib.rk_place_packed_device(self.db.handle, C.byref(p), n, packed.data_ptr(), wpr, _dp(lens),
-                                                        fixed_len, _dp(flags_in), _dp(seq_ascii), _dp(seq_off),
-                                                        C.byref(res), C.c_void_p(st)))
+                                                        fixed_len, _dp(flags_in), _dp(seq_ascii), _dp(seq_off), C.byref(res), st))
             return out
         chars = seq_ascii is not None and seq_off is not None and flags_in is not None
         need = int(self._lib.rk_strands_work_bytes(self.db.handle, n, wpr, K, max(1, seq_ascii.numel()) if chars else 0))
-        if n and not need:
-            _lib.check(_lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_DNA else _lib.RK_ERR_UNSUPPORTED)
-        work = self._work("_strand_work", dev, need)
+        if n:
+            _or_error(self._lib, need, _lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_DNA else _lib.RK_ERR_UNSUPPORTED)
+        work = _grow(self, "_strand_work", dev, need)
         _lib.check(self._lib.rk_place_packed_device_strands(self.db.handle, C.byref(p), sd, n, packed.data_ptr(), wpr, _dp(lens),
                                                             fixed_len, _dp(flags_in), _dp(seq_ascii), _dp(seq_off),
-                                                            C.byref(res), work.data_ptr(), work.numel(), C.c_void_p(st)))
+                                                            C.byref(res), work.data_ptr(), work.numel(), st))
         return out
 
     def place_translated(self, dna, fixed_len=0, lens=None, flags_in=None, out=None, keepAtMost=7, keepFactor=0.01, stream=None):
@@ -626,12 +636,12 @@ class PlacementProcess:
         p = self._params(keepAtMost, keepFactor, True, False)
         st = _stream(dev, stream)
         need = int(self._lib.rk_translated_work_bytes(self.db.handle, n, wpr, K))
-        if n and not need:
-            _lib.check(_lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_AA else _lib.RK_ERR_UNSUPPORTED)
-        work = self._work("_translated_work", dev, need)
+        if n:
+            _or_error(self._lib, need, _lib.RK_ERR_INVALID if self.db.info.alphabet == RK_ALPHABET_AA else _lib.RK_ERR_UNSUPPORTED)
+        work = _grow(self, "_translated_work", dev, need)
         _lib.check(self._lib.rk_place_packed_device_translated(self.db.handle, C.byref(p), n, dna.data_ptr(), wpr, _dp(lens), fixed_len,
                                                                _dp(flags_in), C.byref(res), out["frame"].data_ptr(), work.data_ptr(),
-                                                               work.numel(), C.c_void_p(st)))
+                                                               work.numel(), st))
         return out
 
     def accumulate_masses(self, out, weights=None, masses=None, stream=None):
@@ -639,17 +649,10 @@ class PlacementProcess:
         return -- ADDED into `masses`, an int64 tensor of masses_words(n_branches) words on the same device (the bits are unsigned:
         .cpu().numpy().view(numpy.uint64)), allocated and zeroed when None.  weights: int32 tensor [n] read as uint32 (None = 1 a
         read).  Asynchronous on the stream; the results are read, never written."""
-        import torch
-        n, K = out["branch"].shape
-        dev = out["branch"].device
-        words = masses_words(self.db.info.n_branches)
-        st = _stream(dev, stream)
-        masses = _device_masses(words, masses, dev, stream)
-        if weights is not None and (weights.dtype != torch.int32 or weights.numel() != n or not weights.is_contiguous() or weights.device != dev):
-            raise ValueError(f"weights must be a contiguous int32 tensor of {n} words on {dev}")
-        res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), None, out["lwr"].data_ptr(), None)
-        _lib.check(self._lib.rk_masses_accumulate_device(self.db.handle, K, n, C.byref(res), None if weights is None else weights.data_ptr(),
-                                                         masses.data_ptr(), C.c_void_p(st)))
+        res, n, K, dev = _rows(out)
+        masses = _device_masses(masses_words(self.db.info.n_branches), masses, dev, stream)
+        _i32_tensor(weights, n, dev, "weights")
+        _lib.check(self._lib.rk_masses_accumulate_device(self.db.handle, K, n, C.byref(res), _dp(weights), masses.data_ptr(), _stream(dev, stream)))
         return masses
 
     def accumulate_masses_samples(self, out, n_samples, member_sample, member_read=None, member_weight=None, masses=None, stream=None):
@@ -657,83 +660,65 @@ class PlacementProcess:
         the device of `out`) over `out` -- the dict of device tensors place_packed / place_translated return -- ADDED into `masses`, an
         int64 tensor of masses_samples_words(n_branches, n_samples) words on the same device, allocated and zeroed when None.
         member_read None: entry i is read i; member_weight None: 1.  Asynchronous on the stream."""
-        import torch
-        n, K = out["branch"].shape
-        dev = out["branch"].device
+        res, n, K, dev = _rows(out)
         words = masses_samples_words(self.db.info.n_branches, n_samples)
         if not words:
             raise ValueError(f"n_samples={n_samples} on {self.db.info.n_branches} branches: 1..65535 and at most 2^29 words")
-        st = _stream(dev, stream)
         masses = _device_masses(words, masses, dev, stream)
         m = member_sample.numel()
         for t, what in ((member_sample, "member_sample"), (member_read, "member_read"), (member_weight, "member_weight")):
-            if t is not None and (t.dtype != torch.int32 or t.numel() != m or not t.is_contiguous() or t.device != dev):
-                raise ValueError(f"{what} must be a contiguous int32 tensor of {m} words on {dev}")
-        res = rk_result(out["n_rows"].data_ptr(), out["branch"].data_ptr(), None, out["lwr"].data_ptr(), None)
+            _i32_tensor(t, m, dev, what)
         _lib.check(self._lib.rk_masses_accumulate_samples_device(self.db.handle, K, n, C.byref(res), n_samples, m, _dp(member_read), member_sample.data_ptr(),
-                                                                 _dp(member_weight), masses.data_ptr(), C.c_void_p(st)))
+                                                                 _dp(member_weight), masses.data_ptr(), _stream(dev, stream)))
         return masses
 
     def translate_packed(self, dna, frame, fixed_len=0, lens=None, aa_words=None, stream=None):
         """rk_translate_packed_device: one reading frame of 2-bit DNA records [n, dna_words] -> (amino-acid records [n, aa_words],
         their lengths [n]) as new int32 tensors (translate_packed_host is the host twin)."""
-        import torch
         n, wpr = dna.shape
         if aa_words is None:
             aa_words = translated_words(wpr * 16 if lens is not None else fixed_len)
-        aa = torch.empty((n, aa_words), dtype=torch.int32, device=dna.device)
-        aa_lens = torch.empty(n, dtype=torch.int32, device=dna.device)
-        st = _stream(dna.device, stream)
+        aa, aa_lens = _alloc((n, aa_words), np.uint32, dna.device), _alloc(n, np.uint32, dna.device)
         _lib.check(self._lib.rk_translate_packed_device(self.db.handle, frame, n, dna.data_ptr(), wpr, _dp(lens),
-                                                        fixed_len, aa.data_ptr(), aa_words, aa_lens.data_ptr(), C.c_void_p(st)))
+                                                        fixed_len, aa.data_ptr(), aa_words, aa_lens.data_ptr(), _stream(dna.device, stream)))
         return aa, aa_lens
 
     def revcomp_packed(self, packed, fixed_len=0, lens=None, stream=None):
         """rk_revcomp_packed_device: the reverse complement of 2-bit records [n, wpr] (int32 tensor on the database's device) ->
         a new tensor of the same shape; lengths and flags are the same for both strands."""
-        import torch
         n, wpr = packed.shape
-        out = torch.empty_like(packed)
-        st = _stream(packed.device, stream)
+        out = _torch().empty_like(packed)
         _lib.check(self._lib.rk_revcomp_packed_device(self.db.handle, n, packed.data_ptr(), wpr, _dp(lens),
-                                                      fixed_len, out.data_ptr(), C.c_void_p(st)))
+                                                      fixed_len, out.data_ptr(), _stream(packed.device, stream)))
         return out
 
     def revcomp_ascii(self, seq_ascii, seq_off, stream=None):
         """rk_revcomp_ascii_device: every read's characters reversed and complemented (hostio.revcomp is the numpy twin), same offsets."""
-        import torch
-        out = torch.empty_like(seq_ascii)
-        st = _stream(seq_ascii.device, stream)
+        out = _torch().empty_like(seq_ascii)
         _lib.check(self._lib.rk_revcomp_ascii_device(self.db.handle, seq_off.shape[0] - 1, seq_ascii.data_ptr(), seq_off.data_ptr(),
-                                                     out.data_ptr(), C.c_void_p(st)))
+                                                     out.data_ptr(), _stream(seq_ascii.device, stream)))
         return out
 
     def count_work(self, packed, fixed_len=0, lens=None, flags_in=None, stream=None):
         """k-mers probed / k-mers with a row / row entries walked for a batch of packed reads (rk_count_work_device: a kernel of its own,
         the placement kernels carry no counters) -> dict"""
-        import torch
         n, wpr = packed.shape
         dev = packed.device
-        out = torch.empty(3, dtype=torch.int64, device=dev)
-        st = _stream(dev, stream)
-        _lib.check(self._lib.rk_count_work_device(self.db.handle, n, packed.data_ptr(), wpr, _dp(lens), fixed_len, _dp(flags_in), out.data_ptr(), C.c_void_p(st)))
+        out = _alloc(3, np.uint64, dev)
+        _lib.check(self._lib.rk_count_work_device(self.db.handle, n, packed.data_ptr(), wpr, _dp(lens), fixed_len, _dp(flags_in), out.data_ptr(),
+                                                  _stream(dev, stream)))
         if stream is not None:
-            torch.cuda.synchronize(dev)
+            _torch().cuda.synchronize(dev)
         probed, hit, entries = (int(x) for x in out.tolist())
         return {"kmers_probed": probed, "kmers_hit": hit, "entries": entries}
 
     def pack_reads(self, seq_ascii, seq_off, max_len, stream=None):
-        import torch
         n = seq_off.shape[0] - 1
         dev = seq_ascii.device
         wpr = self.db.packed_words(max_len)
-        packed = torch.empty((n, wpr), dtype=torch.int32, device=dev)
-        lens = torch.empty(n, dtype=torch.int32, device=dev)
-        flags = torch.empty(n, dtype=torch.int32, device=dev)
-        st = _stream(dev, stream)
+        packed, lens, flags = _packed_out(n, wpr, dev)
         _lib.check(self._lib.rk_pack_reads_device(self.db.handle, n, seq_ascii.data_ptr(), seq_off.data_ptr(), wpr,
-                                                  packed.data_ptr(), lens.data_ptr(), flags.data_ptr(),
-                                                  C.c_void_p(st)))
+                                                  packed.data_ptr(), lens.data_ptr(), flags.data_ptr(), _stream(dev, stream)))
         return packed, lens, flags
 
 
@@ -781,36 +766,21 @@ def clade_masses_host(parent, masses, n_samples):
     return clade
 
 
-def kr_distances_host(parent, branch_len, masses, n_samples, threads=0):
-    """rk_kr_distances_host (no GPU): float64 [n_samples, n_samples], the pairwise Kantorovich-Rubinstein distances between the samples
-    of a sample mass buffer on the tree (parent, branch_len) -- the bits EdgeTree.kr_distances gives on the device.  A sample without
-    mass has a NaN row and column."""
-    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
-    out = np.zeros((n_samples, n_samples), np.float64)
-    _lib.check(_lib.load().rk_kr_distances_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), _ptr(out), threads))
-    return out
-
-
 # rk_squash_merge: a row of the squash clustering (a and b the smallest sample indices of the two clusters, size after the merge)
 SQUASH_MERGE = np.dtype([("a", "<u4"), ("b", "<u4"), ("size", "<u4"), ("reserved", "<u4"), ("distance", "<f8")])
 assert SQUASH_MERGE.itemsize == 24
-
-
-def squash_host(parent, branch_len, masses, n_samples, threads=0):
-    """rk_squash_host (no GPU): (merges, n_merges) -- the squash clustering of the samples of a sample mass buffer on the tree (parent,
-    branch_len): a SQUASH_MERGE array of n_samples - 1 rows, of which the first n_merges are merges and the rest fillers -- the bits
-    EdgeTree.squash gives on the device.  A sample without mass takes no part."""
-    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
-    merges = np.zeros(max(n_samples - 1, 0), SQUASH_MERGE)
-    n = C.c_uint32(0)
-    _lib.check(_lib.load().rk_squash_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), _ptr(merges), C.byref(n), threads))
-    return merges, int(n.value)
-
 
 # a k-means run: assign uint32 [S] (KMEANS_NONE for a sample without mass), dist float64 [S], sizes uint32 [k], within float64 [k],
 # info uint32 [4] = k_eff, n_active, rounds, converged | status << 1, centroids float64 [k, 2, B] or None
 KMeans = collections.namedtuple("KMeans", "assign dist sizes within info centroids")
 KMEANS_NONE = 0xFFFFFFFF
+
+# the diversity measures of the samples: values float64 [S, 5 + 2 n_theta] (a NaN row for a sample without mass), columns their names
+Diversity = collections.namedtuple("Diversity", "values columns")
+DIVERSITY_FIXED = ("rooted_pd", "pd", "bwpd", "quadratic", "phylo_entropy")
+
+# what epca_finish makes of a raw edge-PCA output: eigenvalue, share, residual [k]; projection [S, k]; loading [B, k]; the two info words
+EdgePCA = collections.namedtuple("EdgePCA", "eigenvalue share residual projection loading n_active k_eff")
 
 
 def _kmeans_seeds(seeds, k):
@@ -822,28 +792,9 @@ def _kmeans_seeds(seeds, k):
     return seeds
 
 
-def kmeans_host(parent, branch_len, masses, n_samples, k, max_rounds=100, seeds=None, centroids=True, threads=0):
-    """rk_kmeans_host (no GPU): a KMeans of host arrays -- the phylogenetic k-means of the samples of a sample mass buffer on the tree
-    (parent, branch_len), farthest-first seeds unless `seeds` gives k sample indices -- the bits EdgeTree.kmeans gives on the device."""
-    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
-    seeds = _kmeans_seeds(seeds, k)
-    kk = max(k, 0)
-    assign, dist = np.zeros(n_samples, np.uint32), np.zeros(n_samples, np.float64)
-    sizes, within, info = np.zeros(kk, np.uint32), np.zeros(kk, np.float64), np.zeros(4, np.uint32)
-    cen = np.zeros((kk, 2, B), np.float64) if centroids else None
-    _lib.check(_lib.load().rk_kmeans_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), k, max_rounds, None if seeds is None else _ptr(seeds),
-                                          _ptr(assign), _ptr(dist), _ptr(sizes), _ptr(within), _ptr(info), None if cen is None else _ptr(cen), threads))
-    return KMeans(assign, dist, sizes, within, info, cen)
-
-
-# the diversity measures of the samples: values float64 [S, 5 + 2 n_theta] (a NaN row for a sample without mass), columns their names
-Diversity = collections.namedtuple("Diversity", "values columns")
-DIVERSITY_FIXED = ("rooted_pd", "pd", "bwpd", "quadratic", "phylo_entropy")
-
-
 def _diversity_theta(theta):
-    theta = np.ascontiguousarray(() if theta is None else theta, dtype=np.float64).reshape(-1)
-    return theta, None if theta.shape[0] == 0 else _ptr(theta)
+    """the thetas of a diversity call as the C ABI reads them: float64 [n_theta], None for none"""
+    return np.ascontiguousarray(() if theta is None else theta, dtype=np.float64).reshape(-1)
 
 
 def diversity_columns(theta):
@@ -854,15 +805,89 @@ def diversity_columns(theta):
     return tuple(names)
 
 
+def _epca_out(n_branches, n_samples, k):
+    n = int(_lib.load().rk_epca_out_doubles(n_branches, n_samples, k))
+    if not n:
+        raise _lib.RkError(_lib.RK_ERR_INVALID, f"edge PCA: n_branches={n_branches}, n_samples={n_samples}, k={k}: out of 1..65535, 2..4096, 1..8")
+    return n
+
+
+# One description per sample-level analysis, for its three forms rk_<name>_host, rk_<name>_device and rk_<name>_batch.  `p` holds the
+# call's own parameters, those behind n_samples in the public signatures.
+#   work     rk_<work>_work_bytes(tree, n_samples, *args[:1]) sizes the device form's workspace: it depends on the first parameter
+#   args     p -> the parameters as C takes them, in order; a host array among them (seeds, theta) is read during the call
+#   outputs  (B, S, p) -> (name, shape or None for an output that is not asked for, numpy dtype), in the order C takes them
+#   wrap     (outputs by name, p, host) -> the return value; host: host arrays (the _host and _batch forms), else device tensors
+_SampleCall = collections.namedtuple("_SampleCall", "name work args outputs wrap")
+_SAMPLE_CALLS = {c.name: c for c in (
+    _SampleCall("kr_distances", "kr", lambda p: (),
+                lambda B, S, p: (("out", (S, S), np.float64),),
+                lambda o, p, host: o["out"]),
+    # (n_merges: a word the host and batch forms hand back as a number, the device form as the tensor it is)
+    _SampleCall("squash", "squash", lambda p: (),
+                lambda B, S, p: (("merges", (max(S - 1, 0),), SQUASH_MERGE), ("n_merges", (1,), np.uint32)),
+                lambda o, p, host: (o["merges"], int(o["n_merges"][0]) if host else o["n_merges"])),
+    _SampleCall("kmeans", "kmeans", lambda p: (p["k"], p["max_rounds"], _kmeans_seeds(p["seeds"], p["k"])),
+                lambda B, S, p: (("assign", (S,), np.uint32), ("dist", (S,), np.float64), ("sizes", (max(p["k"], 0),), np.uint32),
+                                 ("within", (max(p["k"], 0),), np.float64), ("info", (4,), np.uint32),
+                                 ("centroids", (max(p["k"], 0), 2, B) if p["centroids"] else None, np.float64)),
+                lambda o, p, host: KMeans(**o)),
+    _SampleCall("diversity", "diversity", lambda p: (p["theta"].shape[0], p["theta"] if p["theta"].shape[0] else None),
+                lambda B, S, p: (("values", (S, len(DIVERSITY_FIXED) + 2 * p["theta"].shape[0]), np.float64),),
+                lambda o, p, host: Diversity(o["values"], diversity_columns(p["theta"]))),
+    # (sized with max(.., 0) and max(.., 1) above and here: a k or S out of range reaches the C side, which says so)
+    _SampleCall("epca", "epca", lambda p: (p["k"], p["iters"]),
+                lambda B, S, p: (("raw", (max(int(_lib.load().rk_epca_out_doubles(B, S, p["k"])), 1),), np.float64), ("info", (2,), np.uint32)),
+                lambda o, p, host: (o["raw"], o["info"])),
+)}
+
+
+def _sample_outputs(call, B, S, p, dev=None):
+    """the outputs of a sample-level call by name: zeroed host arrays, or tensors on `dev`; None where one is not asked for"""
+    return {name: None if shape is None else _alloc(shape, dt, dev) for name, shape, dt in call.outputs(B, S, p)}
+
+
+def _address(x):
+    """a parameter or an output as C takes it: the address of a host array or a device tensor, anything else as it is"""
+    return _ptr(x) if isinstance(x, np.ndarray) else x.data_ptr() if hasattr(x, "data_ptr") else x
+
+
+def _sample_host(name, parent, branch_len, masses, n_samples, threads, **p):
+    """the host form of a sample-level call: rk_<name>_host(B, parent, branch_len, n_samples, masses, parameters, outputs, threads)"""
+    call = _SAMPLE_CALLS[name]
+    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
+    args = call.args(p)
+    out = _sample_outputs(call, B, n_samples, p)
+    _lib.check(getattr(_lib.load(), f"rk_{name}_host")(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), *map(_address, args),
+                                                       *map(_address, out.values()), threads))
+    return call.wrap(out, p, True)
+
+
+def kr_distances_host(parent, branch_len, masses, n_samples, threads=0):
+    """rk_kr_distances_host (no GPU): float64 [n_samples, n_samples], the pairwise Kantorovich-Rubinstein distances between the samples
+    of a sample mass buffer on the tree (parent, branch_len) -- the bits EdgeTree.kr_distances gives on the device.  A sample without
+    mass has a NaN row and column."""
+    return _sample_host("kr_distances", parent, branch_len, masses, n_samples, threads)
+
+
+def squash_host(parent, branch_len, masses, n_samples, threads=0):
+    """rk_squash_host (no GPU): (merges, n_merges) -- the squash clustering of the samples of a sample mass buffer on the tree (parent,
+    branch_len): a SQUASH_MERGE array of n_samples - 1 rows, of which the first n_merges are merges and the rest fillers -- the bits
+    EdgeTree.squash gives on the device.  A sample without mass takes no part."""
+    return _sample_host("squash", parent, branch_len, masses, n_samples, threads)
+
+
+def kmeans_host(parent, branch_len, masses, n_samples, k, max_rounds=100, seeds=None, centroids=True, threads=0):
+    """rk_kmeans_host (no GPU): a KMeans of host arrays -- the phylogenetic k-means of the samples of a sample mass buffer on the tree
+    (parent, branch_len), farthest-first seeds unless `seeds` gives k sample indices -- the bits EdgeTree.kmeans gives on the device."""
+    return _sample_host("kmeans", parent, branch_len, masses, n_samples, threads, k=k, max_rounds=max_rounds, seeds=seeds, centroids=centroids)
+
+
 def diversity_host(parent, branch_len, masses, n_samples, theta=(), threads=0):
     """rk_diversity_host (no GPU): a Diversity of host arrays -- rooted and unrooted phylogenetic diversity, balance-weighted PD,
     quadratic entropy and phylogenetic entropy of every sample of a sample mass buffer on the tree (parent, branch_len), and
     rooted_pd_theta / bwpd_theta for every theta in [0, 8] (at most 8) -- the bits EdgeTree.diversity gives on the device."""
-    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
-    theta, tp = _diversity_theta(theta)
-    out = np.zeros((n_samples, len(DIVERSITY_FIXED) + 2 * theta.shape[0]), np.float64)
-    _lib.check(_lib.load().rk_diversity_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), theta.shape[0], tp, _ptr(out), threads))
-    return Diversity(out, diversity_columns(theta))
+    return _sample_host("diversity", parent, branch_len, masses, n_samples, threads, theta=_diversity_theta(theta))
 
 
 def diversity_math_host(op, x, y=None):
@@ -873,30 +898,15 @@ def diversity_math_host(op, x, y=None):
     if y is not None and y.shape != x.shape:
         raise ValueError("x and y must hold one value each per element")
     out = np.zeros(x.shape[0], np.float64)
-    _lib.check(_lib.load().rk_diversity_math_host(op, x.shape[0], _ptr(x), None if y is None else _ptr(y), _ptr(out)))
+    _lib.check(_lib.load().rk_diversity_math_host(op, x.shape[0], _ptr(x), _ptr(y), _ptr(out)))
     return out
-
-
-# what epca_finish makes of a raw edge-PCA output: eigenvalue, share, residual [k]; projection [S, k]; loading [B, k]; the two info words
-EdgePCA = collections.namedtuple("EdgePCA", "eigenvalue share residual projection loading n_active k_eff")
-
-
-def _epca_out(n_branches, n_samples, k):
-    n = int(_lib.load().rk_epca_out_doubles(n_branches, n_samples, k))
-    if not n:
-        raise _lib.RkError(_lib.RK_ERR_INVALID, f"edge PCA: n_branches={n_branches}, n_samples={n_samples}, k={k}: out of 1..65535, 2..4096, 1..8")
-    return n
 
 
 def epca_host(parent, branch_len, masses, n_samples, k, iters, threads=0):
     """rk_epca_host (no GPU): (raw, info) -- the raw edge-PCA output of the samples of a sample mass buffer on the tree (parent, branch_len),
     float64 [1 + k * (3 + S + B)]: trace | lambda[k] | nn[k] | rr[k] | q[k][S] | w[k][B], and uint32 [2]: n_active, k_eff -- the bits
     EdgeTree.epca gives on the device.  epca_finish turns them into eigenvalues, projections and loadings."""
-    parent, branch_len, B, masses = _host_samples(parent, branch_len, masses, n_samples)
-    raw = np.zeros(max(int(_lib.load().rk_epca_out_doubles(B, n_samples, k)), 1), np.float64)
-    info = np.zeros(2, np.uint32)
-    _lib.check(_lib.load().rk_epca_host(B, _ptr(parent), _ptr(branch_len), n_samples, _ptr(masses), k, iters, _ptr(raw), _ptr(info), threads))
-    return raw, info
+    return _sample_host("epca", parent, branch_len, masses, n_samples, threads, k=k, iters=iters)
 
 
 def epca_finish(n_branches, n_samples, k, raw, info=None):
@@ -917,25 +927,13 @@ def epca_finish(n_branches, n_samples, k, raw, info=None):
     return EdgePCA(ev, share, res, proj, load, n_active, k_eff)
 
 
-def _edpl_rows(n_rows, branch, lwr, K):
-    """the three arrays of a host result set that the EDPL reads, as the C ABI takes them: u8 [n], u16 [n * K], f64 [n * K]"""
-    n_rows = np.ascontiguousarray(n_rows, dtype=np.uint8).reshape(-1)
-    branch = np.ascontiguousarray(branch, dtype=np.uint16).reshape(-1)
-    lwr = np.ascontiguousarray(lwr, dtype=np.float64).reshape(-1)
-    n = n_rows.shape[0]
-    if branch.shape[0] != n * K or lwr.shape[0] != n * K:
-        raise ValueError(f"branch and lwr must hold n_reads x K = {n} x {K} rows")
-    return n_rows, branch, lwr, n
-
-
 def edpl_host(parent, branch_len, keep_at_most, n_rows, branch, lwr, threads=0):
     """rk_edpl_host (no GPU): float64 [n_reads], the expected distance between the placement locations of every read of a result set
     (n_rows u8 [n], branch u16 [n, K], lwr f64 [n, K]) on the tree (parent, branch_len): 2 * the sum over the pairs of its usable rows of
     lwr_i * lwr_j * the path between the midpoints of the two edges -- the bits EdgeTree.edpl gives on the device."""
     parent, branch_len = _tree_arrays(parent, branch_len)
-    n_rows, branch, lwr, n = _edpl_rows(n_rows, branch, lwr, keep_at_most)
+    res, n, _, _ = _rows(Placements(n_rows, branch, None, lwr, None, None), keep_at_most)
     out = np.zeros(n, np.float64)
-    res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
     _lib.check(_lib.load().rk_edpl_host(parent.shape[0], _ptr(parent), _ptr(branch_len), keep_at_most, n, C.byref(res), _ptr(out), threads))
     return out
 
@@ -953,55 +951,36 @@ def tree_distance_host(parent, branch_len, a, b):
     return d
 
 
-class EdgeTree:
+class EdgeTree(_Handle):
     """rk_tree: the shape of a reference tree on the device -- parent[x] the node id of x's parent (-1 for the root), branch_len[x] the
     length of the edge above x -- for the sample-level calls over device mass buffers.  Takes and returns torch device tensors and owns
     its workspace (grow-only, one a tree: calls on different streams that overlap in time need a tree each)."""
+    _destroy, _closed = "rk_tree_destroy", "EdgeTree is closed"
 
     def __init__(self, parent, branch_len, device=0):
         parent, branch_len = _tree_arrays(parent, branch_len)
-        self._lib = _lib.load()
         self.n_branches = parent.shape[0]
         self.device = device
-        self._h = C.c_void_p()
         self._work_buf = None
-        _lib.check(self._lib.rk_tree_create(device, self.n_branches, _ptr(parent), _ptr(branch_len), C.byref(self._h)))
-
-    @property
-    def handle(self):
-        if not self._h:
-            raise RuntimeError("EdgeTree is closed")
-        return self._h
+        self._open(_lib.load(), "rk_tree_create", device, self.n_branches, _ptr(parent), _ptr(branch_len))
 
     def _masses(self, masses, n_samples):
-        import torch
         W = 2 * self.n_branches + 4
-        if (masses.dtype != torch.int64 or not masses.is_contiguous() or not masses.is_cuda or masses.device.index != self.device
+        if (masses.dtype != _torch().int64 or not masses.is_contiguous() or not masses.is_cuda or masses.device.index != self.device
                 or masses.numel() not in (n_samples * W, n_samples * W + 1)):
             raise ValueError(f"masses must be a contiguous int64 tensor of {n_samples * W} (+ 1) words on cuda:{self.device}")
         return masses.device
 
     def clade_masses(self, masses, n_samples, stream=None):
         """rk_clade_masses_device: int64 tensor [n_samples, B] (the bits are unsigned), written; asynchronous on the stream"""
-        import torch
         dev = self._masses(masses, n_samples)
-        clade = torch.empty((n_samples, self.n_branches), dtype=torch.int64, device=dev)
-        _lib.check(self._lib.rk_clade_masses_device(self.handle, n_samples, masses.data_ptr(), clade.data_ptr(), C.c_void_p(_stream(dev, stream))))
+        clade = _alloc((n_samples, self.n_branches), np.uint64, dev)
+        _lib.check(self._lib.rk_clade_masses_device(self.handle, n_samples, masses.data_ptr(), clade.data_ptr(), _stream(dev, stream)))
         return clade
 
     def _need(self, fn, *args):
         """the answer of a _work_bytes call, or the RkError of the shape it refuses"""
-        need = int(fn(self.handle, *args))
-        if not need:
-            raise _lib.RkError(_lib.RK_ERR_INVALID, self._lib.rk_last_error().decode("utf-8", "replace"))
-        return need
-
-    def _work(self, need, dev):
-        """the device workspace, grow-only"""
-        import torch
-        if self._work_buf is None or self._work_buf.numel() < need:
-            self._work_buf = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        return self._work_buf
+        return _or_error(self._lib, fn(self.handle, *args))
 
     def _batch_masses(self, n_samples, masses):
         """the host buffer of a _batch call as the C ABI reads it -- whole, the skipped-entries word with it -- or None: the one in the handle"""
@@ -1012,27 +991,38 @@ class EdgeTree:
             raise ValueError("masses must be a whole sample mass buffer (masses_samples_words)")
         return masses
 
+    def _sample_device(self, name, masses, n_samples, stream, **p):
+        """the device form of a sample-level call: rk_<name>_device(tree, n_samples, masses, parameters, outputs, work, work_bytes, stream)"""
+        call = _SAMPLE_CALLS[name]
+        dev = self._masses(masses, n_samples)
+        args = call.args(p)
+        work = _grow(self, "_work_buf", dev, self._need(getattr(self._lib, f"rk_{call.work}_work_bytes"), n_samples, *args[:1]))
+        out = _sample_outputs(call, self.n_branches, n_samples, p, dev)
+        _lib.check(getattr(self._lib, f"rk_{name}_device")(self.handle, n_samples, masses.data_ptr(), *map(_address, args), *map(_address, out.values()),
+                                                           work.data_ptr(), work.numel(), _stream(dev, stream)))
+        return call.wrap(out, p, False)
+
+    def _sample_batch(self, name, db, n_samples, masses, **p):
+        """the drivers' form of a sample-level call: rk_<name>_batch(db, tree, n_samples, masses or NULL, parameters, outputs)"""
+        call = _SAMPLE_CALLS[name]
+        masses = self._batch_masses(n_samples, masses)
+        args = call.args(p)
+        out = _sample_outputs(call, self.n_branches, n_samples, p)
+        _lib.check(getattr(self._lib, f"rk_{name}_batch")(db.handle, self.handle, n_samples, _ptr(masses), *map(_address, args), *map(_address, out.values())))
+        return call.wrap(out, p, True)
+
     def kr_work_bytes(self, n_samples):
         return self._need(self._lib.rk_kr_work_bytes, n_samples)
 
     def kr_distances(self, masses, n_samples, stream=None):
         """rk_kr_distances_device: float64 tensor [n_samples, n_samples], written; asynchronous on the stream"""
-        import torch
-        dev = self._masses(masses, n_samples)
-        work = self._work(self.kr_work_bytes(n_samples), dev)
-        out = torch.empty((n_samples, n_samples), dtype=torch.float64, device=dev)
-        _lib.check(self._lib.rk_kr_distances_device(self.handle, n_samples, masses.data_ptr(), out.data_ptr(), work.data_ptr(),
-                                                    work.numel(), C.c_void_p(_stream(dev, stream))))
-        return out
+        return self._sample_device("kr_distances", masses, n_samples, stream)
 
     def kr_distances_batch(self, db, n_samples, masses=None):
         """rk_kr_distances_batch, the drivers' call: float64 array [n_samples, n_samples] on the host from a host sample mass buffer --
         or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through
         rk_kr_distances_device on db's device; returns when the matrix is there"""
-        masses = self._batch_masses(n_samples, masses)
-        out = np.zeros((n_samples, n_samples), np.float64)
-        _lib.check(self._lib.rk_kr_distances_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(out)))
-        return out
+        return self._sample_batch("kr_distances", db, n_samples, masses)
 
     def squash_work_bytes(self, n_samples):
         return self._need(self._lib.rk_squash_work_bytes, n_samples)
@@ -1040,24 +1030,13 @@ class EdgeTree:
     def squash(self, masses, n_samples, stream=None):
         """rk_squash_device: (merges, n_merges) as device tensors, written -- uint8 [n_samples - 1, 24], the rows of SQUASH_MERGE
         (merges.cpu().numpy().view(SQUASH_MERGE)), and int32 [1]; asynchronous on the stream"""
-        import torch
-        dev = self._masses(masses, n_samples)
-        work = self._work(self.squash_work_bytes(n_samples), dev)
-        merges = torch.empty((n_samples - 1, SQUASH_MERGE.itemsize), dtype=torch.uint8, device=dev)
-        n_merges = torch.empty((1,), dtype=torch.int32, device=dev)
-        _lib.check(self._lib.rk_squash_device(self.handle, n_samples, masses.data_ptr(), merges.data_ptr(), n_merges.data_ptr(), work.data_ptr(),
-                                              work.numel(), C.c_void_p(_stream(dev, stream))))
-        return merges, n_merges
+        return self._sample_device("squash", masses, n_samples, stream)
 
     def squash_batch(self, db, n_samples, masses=None):
         """rk_squash_batch, the drivers' call: (merges, n_merges) on the host, as squash_host gives them, from a host sample mass buffer --
         or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_squash_device
         on db's device; returns when the rows are there"""
-        masses = self._batch_masses(n_samples, masses)
-        merges = np.zeros(max(n_samples - 1, 0), SQUASH_MERGE)
-        n = C.c_uint32(0)
-        _lib.check(self._lib.rk_squash_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), _ptr(merges), C.byref(n)))
-        return merges, int(n.value)
+        return self._sample_batch("squash", db, n_samples, masses)
 
     def kmeans_work_bytes(self, n_samples, k):
         return self._need(self._lib.rk_kmeans_work_bytes, n_samples, k)
@@ -1066,35 +1045,13 @@ class EdgeTree:
         """rk_kmeans_device: a KMeans of device tensors, written -- assign int32 [S] (the bits are unsigned: -1 is KMEANS_NONE), dist
         float64 [S], sizes int32 [k], within float64 [k], info int32 [4] and, when asked for, centroids float64 [k, 2, B] --, as
         kmeans_host gives them; asynchronous on the stream.  `seeds`: k sample indices on the host, read during the call."""
-        import torch
-        dev = self._masses(masses, n_samples)
-        need = self.kmeans_work_bytes(n_samples, k)
-        seeds = _kmeans_seeds(seeds, k)
-        work = self._work(need, dev)
-        assign = torch.empty((n_samples,), dtype=torch.int32, device=dev)
-        dist = torch.empty((n_samples,), dtype=torch.float64, device=dev)
-        sizes = torch.empty((k,), dtype=torch.int32, device=dev)
-        within = torch.empty((k,), dtype=torch.float64, device=dev)
-        info = torch.empty((4,), dtype=torch.int32, device=dev)
-        cen = torch.empty((k, 2, self.n_branches), dtype=torch.float64, device=dev) if centroids else None
-        _lib.check(self._lib.rk_kmeans_device(self.handle, n_samples, masses.data_ptr(), k, max_rounds, None if seeds is None else _ptr(seeds), assign.data_ptr(),
-                                              dist.data_ptr(), sizes.data_ptr(), within.data_ptr(), info.data_ptr(), _dp(cen), work.data_ptr(),
-                                              work.numel(), C.c_void_p(_stream(dev, stream))))
-        return KMeans(assign, dist, sizes, within, info, cen)
+        return self._sample_device("kmeans", masses, n_samples, stream, k=k, max_rounds=max_rounds, seeds=seeds, centroids=centroids)
 
     def kmeans_batch(self, db, n_samples, k, max_rounds=100, masses=None, seeds=None, centroids=False):
         """rk_kmeans_batch, the drivers' call: a KMeans of host arrays, as kmeans_host gives them, from a host sample mass buffer -- or,
         masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_kmeans_device on
         db's device; returns when they are there"""
-        masses = self._batch_masses(n_samples, masses)
-        seeds = _kmeans_seeds(seeds, k)
-        assign, dist = np.zeros(n_samples, np.uint32), np.zeros(n_samples, np.float64)
-        sizes, within, info = np.zeros(k, np.uint32), np.zeros(k, np.float64), np.zeros(4, np.uint32)
-        cen = np.zeros((k, 2, self.n_branches), np.float64) if centroids else None
-        _lib.check(self._lib.rk_kmeans_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), k, max_rounds,
-                                             None if seeds is None else _ptr(seeds), _ptr(assign), _ptr(dist), _ptr(sizes), _ptr(within), _ptr(info),
-                                             None if cen is None else _ptr(cen)))
-        return KMeans(assign, dist, sizes, within, info, cen)
+        return self._sample_batch("kmeans", db, n_samples, masses, k=k, max_rounds=max_rounds, seeds=seeds, centroids=centroids)
 
     def diversity_work_bytes(self, n_samples, n_theta=0):
         return self._need(self._lib.rk_diversity_work_bytes, n_samples, n_theta)
@@ -1102,24 +1059,13 @@ class EdgeTree:
     def diversity(self, masses, n_samples, theta=(), stream=None):
         """rk_diversity_device: a Diversity whose values are a device tensor float64 [S, 5 + 2 n_theta], written, as diversity_host
         gives them; asynchronous on the stream.  `theta`: at most 8 values in [0, 8] on the host, read during the call."""
-        import torch
-        dev = self._masses(masses, n_samples)
-        theta, tp = _diversity_theta(theta)
-        work = self._work(self.diversity_work_bytes(n_samples, theta.shape[0]), dev)
-        out = torch.empty((n_samples, len(DIVERSITY_FIXED) + 2 * theta.shape[0]), dtype=torch.float64, device=dev)
-        _lib.check(self._lib.rk_diversity_device(self.handle, n_samples, masses.data_ptr(), theta.shape[0], tp, out.data_ptr(), work.data_ptr(), work.numel(),
-                                                 C.c_void_p(_stream(dev, stream))))
-        return Diversity(out, diversity_columns(theta))
+        return self._sample_device("diversity", masses, n_samples, stream, theta=_diversity_theta(theta))
 
     def diversity_batch(self, db, n_samples, theta=(), masses=None):
         """rk_diversity_batch, the drivers' call: a Diversity of host arrays, as diversity_host gives them, from a host sample mass
         buffer -- or, masses None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through
         rk_diversity_device on db's device; returns when the table is there"""
-        masses = self._batch_masses(n_samples, masses)
-        theta, tp = _diversity_theta(theta)
-        out = np.zeros((n_samples, len(DIVERSITY_FIXED) + 2 * theta.shape[0]), np.float64)
-        _lib.check(self._lib.rk_diversity_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), theta.shape[0], tp, _ptr(out)))
-        return Diversity(out, diversity_columns(theta))
+        return self._sample_batch("diversity", db, n_samples, masses, theta=_diversity_theta(theta))
 
     def epca_work_bytes(self, n_samples, k):
         return self._need(self._lib.rk_epca_work_bytes, n_samples, k)
@@ -1127,24 +1073,13 @@ class EdgeTree:
     def epca(self, masses, n_samples, k, iters, stream=None):
         """rk_epca_device: (raw, info) as device tensors, written -- float64 [1 + k * (3 + S + B)] and int32 [2] (n_active, k_eff), as
         epca_host gives them; asynchronous on the stream.  epca_finish(B, S, k, raw, info) downloads and finishes them."""
-        import torch
-        dev = self._masses(masses, n_samples)
-        work = self._work(self.epca_work_bytes(n_samples, k), dev)
-        raw = torch.empty((_epca_out(self.n_branches, n_samples, k),), dtype=torch.float64, device=dev)
-        info = torch.empty((2,), dtype=torch.int32, device=dev)
-        _lib.check(self._lib.rk_epca_device(self.handle, n_samples, masses.data_ptr(), k, iters, raw.data_ptr(), info.data_ptr(), work.data_ptr(),
-                                            work.numel(), C.c_void_p(_stream(dev, stream))))
-        return raw, info
+        return self._sample_device("epca", masses, n_samples, stream, k=k, iters=iters)
 
     def epca_batch(self, db, n_samples, k, iters, masses=None):
         """rk_epca_batch, the drivers' call: (raw, info) on the host, as epca_host gives them, from a host sample mass buffer -- or, masses
         None, from the buffer the last processQueriesMassesSamples call on `db` left on the device -- through rk_epca_device on db's
         device; returns when they are there"""
-        masses = self._batch_masses(n_samples, masses)
-        raw = np.zeros(max(int(self._lib.rk_epca_out_doubles(self.n_branches, n_samples, k)), 1), np.float64)
-        info = np.zeros(2, np.uint32)
-        _lib.check(self._lib.rk_epca_batch(db.handle, self.handle, n_samples, None if masses is None else _ptr(masses), k, iters, _ptr(raw), _ptr(info)))
-        return raw, info
+        return self._sample_batch("epca", db, n_samples, masses, k=k, iters=iters)
 
     def edpl_lds_bytes(self):
         """rk_edpl_lds_bytes: the bytes of the distance tables when edpl copies them into the LDS of every block, 0 when it reads them
@@ -1154,35 +1089,24 @@ class EdgeTree:
     def edpl(self, out, keep_at_most, stream=None):
         """rk_edpl_device: float64 tensor [n_reads], written -- the EDPL of every read of a device result set (`out`: the dict of device
         tensors a placement call returns; n_rows, branch [n, keep_at_most] and lwr [n, keep_at_most] are read); asynchronous on the stream"""
-        import torch
-        n_rows, branch, lwr = out["n_rows"], out["branch"], out["lwr"]
-        n, K = n_rows.numel(), keep_at_most
-        for t, dt, size, what in ((n_rows, torch.uint8, n, "n_rows"), (branch, torch.int16, n * K, "branch"), (lwr, torch.float64, n * K, "lwr")):
+        torch = _torch()
+        res, n, K, dev = _rows(out, keep_at_most)
+        for what, dt, size in (("n_rows", torch.uint8, n), ("branch", torch.int16, n * K), ("lwr", torch.float64, n * K)):
+            t = out[what]
             if t.dtype != dt or t.numel() != size or not t.is_contiguous() or not t.is_cuda or t.device.index != self.device:
                 raise ValueError(f"{what} must be a contiguous {dt} tensor of {size} elements on cuda:{self.device}")
-        dev = n_rows.device
-        edpl = torch.empty((n,), dtype=torch.float64, device=dev)
-        res = rk_result(n_rows.data_ptr(), branch.data_ptr(), None, lwr.data_ptr(), None)
-        _lib.check(self._lib.rk_edpl_device(self.handle, K, n, C.byref(res), edpl.data_ptr(), C.c_void_p(_stream(dev, stream))))
+        edpl = _alloc(n, np.float64, out["n_rows"].device)
+        _lib.check(self._lib.rk_edpl_device(self.handle, K, n, C.byref(res), edpl.data_ptr(), _stream(out["n_rows"].device, stream)))
         return edpl
 
     def edpl_batch(self, db, keep_at_most, n_rows, branch, lwr):
         """rk_edpl_batch, the drivers' call: float64 array [n_reads] on the host, as edpl_host gives it, from a host result set, in chunks
         through rk_edpl_device on db's device; returns when the values are there"""
-        n_rows, branch, lwr, n = _edpl_rows(n_rows, branch, lwr, keep_at_most)
+        res, n, _, _ = _rows(Placements(n_rows, branch, None, lwr, None, None), keep_at_most)
         edpl = np.zeros(n, np.float64)
-        res = rk_result(_ptr(n_rows), _ptr(branch), None, _ptr(lwr), None)
         _lib.check(self._lib.rk_edpl_batch(db.handle, self.handle, keep_at_most, n, C.byref(res), _ptr(edpl)))
         return edpl
 
     def close(self):
-        if self._h:
-            self._lib.rk_tree_destroy(self._h)
-            self._h = C.c_void_p()
+        super().close()
         self._work_buf = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
