@@ -725,12 +725,59 @@ int rk_diversity_math_host(uint32_t op /* 0 log2, 1 exp2, 2 pw */, uint64_t n, c
  *   4 Gram matrix       G[s][t] = the chunk-rule sum over x of Xc[x][s] * Xc[x][t], as acc = acc + (a * b).  G is bitwise
  *                       symmetric; rows and columns of inactive samples are +0.0.  trace = LS(s -> G[s][s]).
  *   5 Start vectors     for j < k_eff: Q[j][s] = (double)(((s * 8 + j + 1) * 2654435761) mod 2^32) / 4294967296.0 - 0.5.
- *   6 Iteration         `iters` times: Y[j][s] = LS(t -> G[s][t] * Q[j][t]) for every j < k_eff.  Then for j = 0 .. k_eff - 1 in
- *                       order: let i be the smallest s with the largest fabs(Y[j][s]) (plain >).  If that value is 0, column j
- *                       becomes all +0.0 and is skipped by the projections below.  Otherwise Y[j][s] = Y[j][s] / Y[j][i] for every
- *                       s (the divisor is the value before the division: the largest element becomes exactly +1.0, which is also
- *                       the sign convention); then nn = dot(Y[j], Y[j]) and for every l > j: d = dot(Y[j], Y[l]) / nn,
- *                       Y[l][s] = Y[l][s] - d * Y[j][s].  Then Q = Y.
+ *   6 Iteration         `iters` times: Y[j][s] = LS(t -> G[s][t] * Q[j][t]) for every j < k_eff, and top0_j = the largest
+ *                       fabs(Y[j][s]) of the column as this product delivered it.  Then for j = 0 .. k_eff - 1 in order, with
+ *                       p = the number of columns before j that were not zero columns (the projections column j has been through),
+ *                       but p = 0 throughout the first of the iterations, and scale_j = the largest of top0_j and the top0 of
+ *                       those columns before j that were not zero columns:
+ *                       let i be the smallest s with the largest fabs(Y[j][s]) (plain >), top that value.  If
+ *                       top <= (((double)S * 2^-40) * (double)p) * scale_j -- two exact products, then one rounding; +0.0 for
+ *                       p == 0, where it is the test top == 0 --, column j is a zero column: it becomes all +0.0 and is skipped by
+ *                       the projections below.  Otherwise Y[j][s] = Y[j][s] / Y[j][i] for every s (the divisor is the value before
+ *                       the division: the largest element becomes exactly +1.0, which is also the sign convention); then
+ *                       nn = dot(Y[j], Y[j]) and for every l > j: d = dot(Y[j], Y[l]) / nn, Y[l][s] = Y[l][s] - d * Y[j][s].
+ *                       Then Q = Y.
+ *     The zero rule     A column beyond the rank of G lies, as the product delivers it, in the span of the columns before it, and
+ *                       what its projections leave is their rounding.  Dividing that by its largest element would blow it up to
+ *                       O(1), still with an O(1) share of the leading vector in it, which the projections on it would put back
+ *                       into the later columns: a leading eigenvalue reported twice.  So such a column must be recognised.  Not
+ *                       in the first iteration: its columns are G times the start vectors, and two start vectors can differ by a
+ *                       constant vector, which G of a centred matrix takes to zero (S = 3, all samples active: columns 0 and 1
+ *                       of the first product are the same bits).  A column lost that way must come back, and what the division
+ *                       makes of its rounding is a start vector as good as another; the first product of a rank-deficient G
+ *                       gets the same treatment and is caught one iteration later (with iters == 1 not at all).  From the second
+ *                       iteration on every live column lies in the range of G, orthogonal to the live ones before it, and G is
+ *                       one-to-one there: a column that its projections then reduce to rounding is beyond the rank for good, and
+ *                       a zero column stays one (G times it is zero).  That also holds for a column whose first product is
+ *                       exactly zero although G is not: the start vectors are affine in s between the wraps of the hash, and
+ *                       the G of a few interleaved profiles can take such a vector to +0.0 in every entry.  That column is a
+ *                       zero column for good and the components sit in the columns that are left, in order.
+ *                       The scale: what the division of iteration one makes of a column's rounding lies almost in the null
+ *                       space of G, so every later product delivers it tiny -- top0_j about 2^-53 of the leading column's --
+ *                       with an O(1) share of the range of G in that little.  Measured against its own top0_j alone it would
+ *                       pass for a live column for ever and be reported as a component of about 2^-53 of the leading
+ *                       eigenvalue.  Every live column enters the product with its largest entry 1, so top0 of a live column
+ *                       is |G q|_max for a q of that size: against the largest of them, a delivered column that small is the
+ *                       rounding of the product itself (at most S u sum_t |G[s][t]| an entry), and the same factor covers it.
+ *                       The factor, with u = 2^-53, to first order in u: a = Y[j] after its division (|a[s]| <= 1, one entry 1, so
+ *                       |a|_2 >= 1 and nn >= 1), b = Y[l] before this projection.  A term of a dot goes through one product and at
+ *                       most S - 1 inexact additions of the lane rule (an addition onto +0.0 is exact), so the computed dot(a, b)
+ *                       is off by at most S u |a|_2 |b|_2 and nn by S u |a|_2^2; with the division d is off by at most
+ *                       (2 S + 1) u |b|_2 / |a|_2, and |d| <= |b|_2 / |a|_2 <= |b|_2.  The two roundings of b[s] - d * a[s] add
+ *                       u |d a[s]| + u |b'[s]| <= 2 u |b|_2.  So one projection moves no entry further than (2 S + 3) u |b|_2 from
+ *                       the exact projection, and the whole column no further than sqrt(S) times that in length.  An exact
+ *                       projection lengthens neither the column nor an error it carries, and |b|_2 <= sqrt(S) top0 at the start.
+ *                       After p projections a column whose exact remainder is zero therefore has no entry beyond
+ *                       p sqrt(S) (2 S + 3) u sqrt(S) top0 = p S (2 S + 3) u top0 <= p * S * 2^13 u * top0 for every
+ *                       S <= RK_EPCA_MAX_SAMPLES (2 * 4096 + 3 rounded to the power of two, so that the factor is exact), and
+ *                       top0 <= scale: S * 2^13 * 2^-53 = S * 2^-40 per projection.  A worst case: what was seen on replicate
+ *                       samples is a few times S * 2^-53 per projection (tests/test_replicates_host.py prints it), which
+ *                       includes what the rounding of G itself adds to such a column.  What the rule costs: a component whose
+ *                       eigenvalue is below about p S 2^-40 of the leading one (at most 7 * 4096 * 2^-40 = 2.6e-8, 1e-11 at
+ *                       S = 10) is taken for such a column -- in the early iterations, where what the projections leave of
+ *                       column j is about eigenvalue_j / eigenvalue_0 of it, or later by its top0 against the scale -- and
+ *                       stays zero.  The call claims components down to an eigenvalue ratio of 2^-20 (a share of one in a
+ *                       million) and none below.
  *   7 Results           Z[j][s] = LS(t -> G[s][t] * Q[j][t]); nn_j = dot(Q[j], Q[j]); lambda_j = dot(Q[j], Z[j]) / nn_j;
  *                       rr_j = dot(r, r) with r[s] = Z[j][s] - lambda_j * Q[j][s].  A zero column (nn_j == 0) gives nn_j =
  *                       lambda_j = rr_j = +0.0.  w[j][x] = LS(s -> Xc[x][s] * Q[j][s]).
@@ -743,9 +790,10 @@ int rk_diversity_math_host(uint32_t op /* 0 log2, 1 exp2, 2 pw */, uint64_t n, c
  *   Consequences        The result does not depend on grid, tile or stream.  residual_j is |G q - lambda q| for the unit vector q:
  *                       it tells how far the fixed number of iterations got -- some eigenvalue of G lies within residual_j of
  *                       eigenvalue_j; nothing is iterated "until converged".  Components come out in descending eigenvalue once
- *                       converged; they are not sorted.  They are meaningful only up to the rank of G (hence k_eff: a column
- *                       beyond the rank would turn into noise).  The q entry of an inactive sample is a zero whose sign is that
- *                       of the divisor of step 6.
+ *                       converged; they are not sorted.  They exist only up to the rank of G: hence k_eff, and where the samples
+ *                       hold fewer distinct profiles than that (replicates), the zero rule of step 6 -- a component beyond the
+ *                       rank is all +0.0, eigenvalue, share and residual included, not a second copy of a leading one.  The q
+ *                       entry of an inactive sample is a zero whose sign is that of the divisor of step 6.
  *   rk_epca_out_doubles   the length of the raw output; 0 for arguments out of range.
  *   rk_epca_work_bytes    bytes of the caller-owned device workspace: the clade sums, the profiles (the centred matrix takes the
  *                         place of u), G, its per-chunk partials when the matrix is small, two [k][S] column blocks and the

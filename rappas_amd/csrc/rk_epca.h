@@ -246,11 +246,56 @@ __global__ void __launch_bounds__(64 * EPCA_WAVES) epca_multiply_kernel(u32 S, u
 // block finds the pivot -- the largest fabs, the smallest index among equals: a total order, so the shape of the reduction plays no
 // part --, divides the column, and after a barrier wave w takes the columns l = j + 1 + w, j + 1 + w + EPCA_WAVES, ...: nn (every
 // wave sums it for itself: the same bits), d, and the update of column l.  A barrier closes the column.
-__global__ void __launch_bounds__(64 * EPCA_WAVES) epca_orth_kernel(u32 S, u32 k, const u32 *info, double *Y) {
+// The zero rule: before the first column changes, the block takes the largest fabs of every column as the product delivered it (a
+// maximum: no order in it; a thread holds one value per column, the loads of all columns in flight together, a wave folds them by
+// six __shfl_xor steps into wave_top, and top0 is the largest of the four); at its turn a column whose largest fabs is at most
+// epca_noise_bound(S, applied, the larger of its top0 and the top0 of the live columns before it) -- applied = those live columns,
+// the projections it has been through -- is a zero column.  Nothing has been applied to column 0: the bound is +0.0 and the rule is the plain zero test; so it is for every column
+// of the first iteration (`first`), whose columns come from the start vectors.
+__global__ void __launch_bounds__(64 * EPCA_WAVES) epca_orth_kernel(u32 S, u32 k, u32 first, const u32 *info, double *Y) {
     __shared__ double best_v[64 * EPCA_WAVES];
     __shared__ u32 best_i[64 * EPCA_WAVES];
+    __shared__ double wave_top[EPCA_WAVES][EPCA_MAX_K];
     const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u32 k_eff = min(info[1], k);  // (never beyond the k columns there are)
+    {
+        double m[EPCA_MAX_K];
+#pragma unroll
+        for (u32 j = 0; j < EPCA_MAX_K; j++) m[j] = -1.0;  // (below every fabs)
+        constexpr u32 AHEAD = 4, STEP = 64 * EPCA_WAVES;
+        u32 s = tid;
+        for (; s + STEP * (AHEAD - 1) < S; s += STEP * AHEAD) {  // the loads of AHEAD steps of every column, then the compares
+            double a[AHEAD][EPCA_MAX_K];
+#pragma unroll
+            for (u32 i = 0; i < AHEAD; i++)
+#pragma unroll
+                for (u32 j = 0; j < EPCA_MAX_K; j++) a[i][j] = j < k_eff ? fabs(Y[(u64)j * S + s + STEP * i]) : -1.0;
+#pragma unroll
+            for (u32 i = 0; i < AHEAD; i++)
+#pragma unroll
+                for (u32 j = 0; j < EPCA_MAX_K; j++)
+                    if (a[i][j] > m[j]) m[j] = a[i][j];
+        }
+        for (; s < S; s += STEP) {
+#pragma unroll
+            for (u32 j = 0; j < EPCA_MAX_K; j++) {
+                const double a = j < k_eff ? fabs(Y[(u64)j * S + s]) : -1.0;
+                if (a > m[j]) m[j] = a;
+            }
+        }
+#pragma unroll
+        for (u32 j = 0; j < EPCA_MAX_K; j++) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double m2 = __shfl_xor(m[j], o, 64);
+                if (m2 > m[j]) m[j] = m2;
+            }
+            if (lane == 0) wave_top[wave][j] = m[j];
+        }
+    }
+    __syncthreads();
+    u32 applied = 0;      // (uniform)
+    double scale = 0.0;   // (uniform) the largest top0 of the live columns so far
     for (u32 j = 0; j < k_eff; j++) {
         double *yj = Y + (u64)j * S;
         double bv = -1.0;  // (below every fabs)
@@ -279,10 +324,16 @@ __global__ void __launch_bounds__(64 * EPCA_WAVES) epca_orth_kernel(u32 S, u32 k
         const double top = best_v[0];
         const double pivot = yj[best_i[0]];
         __syncthreads();  // everyone holds the pivot before the column changes; best_v and best_i are free again
-        if (top == 0.0) {  // (uniform) a zero column: written as +0.0, projected on by nobody
+        double top0 = wave_top[0][j];  // the largest fabs of the column as the product delivered it
+#pragma unroll
+        for (u32 w = 1; w < EPCA_WAVES; w++)
+            if (wave_top[w][j] > top0) top0 = wave_top[w][j];
+        if (top <= epca_noise_bound(S, first ? 0u : applied, top0 > scale ? top0 : scale)) {  // (uniform) a zero column: written as +0.0, projected on by nobody
             for (u32 s = tid; s < S; s += 64 * EPCA_WAVES) yj[s] = 0.0;
             continue;
         }
+        applied++;
+        if (top0 > scale) scale = top0;
         for (u32 s = tid; s < S; s += 64 * EPCA_WAVES) yj[s] = yj[s] / pivot;
         __syncthreads();
         if (j + 1 + wave < k_eff) {  // (a whole wave)

@@ -28,6 +28,16 @@ RK_SAMPLEMATH_FN double gram_term(double acc, double a, double b) {
     return acc + term;
 }
 
+// The zero rule of edge PCA's step 6: the largest fabs that a column of S entries may have after its projections on `applied`
+// columns and still count as rounding, against `scale` -- the larger of the largest fabs the product delivered it with and those of
+// the live columns before it.  Per projection
+// S * 2^13 * 2^-53 (include/rappas_place.h derives it): S * 2^-40 and its product with a small integer are exact, so the whole is
+// one rounding.  applied == 0 gives +0.0: the plain zero test.
+RK_SAMPLEMATH_FN double epca_noise_bound(uint32_t S, uint32_t applied, double scale) {
+    const double per_projection = (double)S * 0x1p-40;
+    return (per_projection * (double)applied) * scale;
+}
+
 // The chunk rule: a sum over the node ids is one partial per chunk of RK_KR_CHUNK ids, each from +0.0 in ascending id, and the
 // partials are added in chunk order, the first one as it is (not onto +0.0: a partial of -0.0 or NaN stays what it is).
 // chunk_fold is one step of it, for whoever meets the partials one by one; chunk_sum the whole of it over p(0 .. n_chunks - 1).

@@ -273,21 +273,36 @@ inline void epca_multiply(uint32_t S, uint32_t k_eff, const double *G, const dou
         for (uint64_t s = 0; s < S; s++) out[j * (uint64_t)S + s] = epca_dot(S, G + s * S, in + j * (uint64_t)S);
 }
 
-// Step 6 behind the product: the columns of Y scaled by their largest element and made orthogonal, in column order
-inline void epca_orth(uint32_t S, uint32_t k_eff, double *Y) {
+// the smallest index with the largest fabs of a column (plain >), and that fabs
+inline uint32_t epca_largest(uint32_t S, const double *y, double *best) {
+    uint32_t i = 0;
+    *best = std::fabs(y[0]);
+    for (uint32_t s = 1; s < S; s++)
+        if (std::fabs(y[s]) > *best) {
+            *best = std::fabs(y[s]);
+            i = s;
+        }
+    return i;
+}
+
+// Step 6 behind the product: the columns of Y scaled by their largest element and made orthogonal, in column order; a column that
+// its projections have left with nothing but their rounding (the zero rule of step 6; not in the first iteration, whose columns come
+// from the start vectors) becomes +0.0 and is projected on by nobody
+inline void epca_orth(uint32_t S, uint32_t k_eff, bool first, double *Y) {
+    double top0[EPCA_MAX_COMPONENTS];  // the largest fabs of every column as the product delivered it
+    for (uint32_t j = 0; j < k_eff; j++) epca_largest(S, Y + j * (uint64_t)S, &top0[j]);
+    uint32_t applied = 0;  // the projections column j has been through: the live columns before it
+    double scale = 0.0;    // the largest top0 of those live columns
     for (uint32_t j = 0; j < k_eff; j++) {
         double *yj = Y + j * (uint64_t)S;
-        uint32_t i = 0;
-        double best = std::fabs(yj[0]);
-        for (uint32_t s = 1; s < S; s++)
-            if (std::fabs(yj[s]) > best) {
-                best = std::fabs(yj[s]);
-                i = s;
-            }
-        if (best == 0.0) {
+        double best;
+        const uint32_t i = epca_largest(S, yj, &best);
+        if (best <= epca_noise_bound(S, first ? 0u : applied, top0[j] > scale ? top0[j] : scale)) {
             for (uint32_t s = 0; s < S; s++) yj[s] = 0.0;
             continue;
         }
+        applied++;
+        if (top0[j] > scale) scale = top0[j];
         const double pivot = yj[i];
         for (uint32_t s = 0; s < S; s++) yj[s] = yj[s] / pivot;
         const double nn = epca_dot(S, yj, yj);
@@ -309,7 +324,7 @@ inline void epca_iterate(uint32_t B, uint32_t S, uint32_t k, uint32_t k_eff, uin
         for (uint32_t s = 0; s < S; s++) q[j * (uint64_t)S + s] = epca_start(s, j);
     for (uint32_t it = 0; it < iters; it++) {
         epca_multiply(S, k_eff, G, q, y);
-        epca_orth(S, k_eff, y);
+        epca_orth(S, k_eff, it == 0, y);
         std::swap(q, y);
     }
     double *z = y;

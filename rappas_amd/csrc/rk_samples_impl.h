@@ -992,7 +992,7 @@ static int epca_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, u
     if (steps & 8)
         for (uint32_t it = 0; it < iters; it++) {
             hipLaunchKernelGGL(epca_multiply_kernel, dim3(rows), dim3(64 * EPCA_WAVES), 0, s, S, k, info, (const double *)G, (const double *)q, y);
-            hipLaunchKernelGGL(epca_orth_kernel, dim3(1), dim3(64 * EPCA_WAVES), 0, s, S, k, info, y);
+            hipLaunchKernelGGL(epca_orth_kernel, dim3(1), dim3(64 * EPCA_WAVES), 0, s, S, k, it == 0 ? 1u : 0u, info, y);
             HIP_TRY(hipGetLastError());
             std::swap(q, y);
         }

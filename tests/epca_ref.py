@@ -60,8 +60,18 @@ def multiply(G, Q):
     return LS(G.T[:, None, :] * Q.T[:, :, None])  # axis 0 is t; [t, j, s]
 
 
-def iterate(prep, k, iters):
-    """steps 5 - 8: (raw, info)"""
+def largest(col):
+    """(i, fabs(col[i])) for the smallest i with the largest fabs (plain >)"""
+    i, best = 0, abs(col[0])
+    for s in range(1, len(col)):
+        if abs(col[s]) > best:
+            i, best = s, abs(col[s])
+    return i, best
+
+
+def iterate(prep, k, iters, trace_to=None):
+    """steps 5 - 8: (raw, info).  trace_to: a list that takes, for every column at its turn, (iteration, j, the projections the rule
+    counts, its largest fabs, the scale it is measured against, whether it became a zero column)"""
     B, S, n, Xc, G, trace = prep
     raw = np.zeros(out_doubles(B, S, k), np.float64)
     k_eff = min(k, n - 1) if n >= 2 else 0
@@ -72,16 +82,22 @@ def iterate(prep, k, iters):
     for j in range(k_eff):
         for s in range(S):
             Q[j, s] = float(((s * 8 + j + 1) * 2654435761) % (1 << 32)) / 4294967296.0 - 0.5
-    for _ in range(iters):
+    noise = np.float64(S) * 2.0 ** -40  # the factor of step 6 for one projection (a power of two times S: exact)
+    for it in range(iters):
         Y = multiply(G, Q)
+        top0 = [largest(Y[j])[1] for j in range(k_eff)]  # as the product delivered the columns
+        applied, scale = 0, np.float64(0.0)  # the live columns so far -- the projections a later column has been through -- and their largest top0
         for j in range(k_eff):
-            i, best = 0, abs(Y[j, 0])
-            for s in range(1, S):
-                if abs(Y[j, s]) > best:
-                    i, best = s, abs(Y[j, s])
-            if best == 0:
+            i, best = largest(Y[j])
+            against = top0[j] if top0[j] > scale else scale
+            zero = best <= (noise * np.float64(applied if it else 0)) * against  # the zero rule, from the second iteration on; before it best == 0
+            if trace_to is not None:
+                trace_to.append((it, j, applied if it else 0, best, against, bool(zero)))
+            if zero:
                 Y[j] = 0.0
                 continue
+            applied += 1
+            scale = against
             Y[j] = Y[j] / Y[j, i]
             nn = dot(Y[j], Y[j])
             for l in range(j + 1, k_eff):
