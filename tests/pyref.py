@@ -201,6 +201,12 @@ def place_read(db, read, keep_at_most=7, keep_factor=0.01, amb_mode="mean", ns_b
                     S[x] = f32(S[x] + f32(S_amb[x] - T))                    # :1230
     if not L:
         return dict(rows=[], flags=flags, S=S, L=L, H=H)
+    return dict(rows=select_and_weigh(S, L, flags, keep_at_most, keep_factor, ns_bound), flags=flags, S=S, L=L, H=H)
+
+
+def select_and_weigh(S, L, flags, keep_at_most=7, keep_factor=0.01, ns_bound=float("-inf")):
+    """the select, the weight ratios, the keep-factor cut and the ns_bound gate of place_read for a read that touched the branches L (in
+    that order) with scores S; adds "placed" / "below_nsbound" to flags.  -> [(branch, score f32, lwr float)]"""
     flags.add("placed")
     K = keep_at_most
     num_best = min(K, len(L))
@@ -227,7 +233,7 @@ def place_read(db, read, keep_at_most=7, keep_factor=0.01, amb_mode="mean", ns_b
             total += math.pow(10.0, float(f32(best_list[ii][1] - shift)))   # float subtract then widen (:445-447)
     if not (best_list[K - 1][1] >= f32(ns_bound)):                          # :974
         flags.add("below_nsbound")
-        return dict(rows=[], flags=flags, S=S, L=L, H=H)
+        return []
     best2, lowest2 = best_list[K - 1][1], best_list[K - num_best][1]
     shift2 = best2 if f32(-308.0) >= lowest2 else f32(0.0)                  # :978-980
     rows, best_ratio = [], -1.0
@@ -238,7 +244,7 @@ def place_read(db, read, keep_at_most=7, keep_factor=0.01, amb_mode="mean", ns_b
         if i < K - 1 and ratio < best_ratio * float(f32(keep_factor)):
             break
         rows.append((best_list[i][0], best_list[i][1], ratio))
-    return dict(rows=rows, flags=flags, S=S, L=L, H=H)
+    return rows
 
 
 def db_to_csr(db):

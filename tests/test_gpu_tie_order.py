@@ -54,14 +54,15 @@ KEEP_FACTORS = (0.0, 0.01)
 
 
 @contextlib.contextmanager
-def route_db(name, route, monkeypatch):
-    """the database of planted tree `name`, opened for the kernel of `route`; the route's developer knobs hold while it is open"""
+def route_db(name, route, monkeypatch, sdb=None):
+    """the database of planted tree `name` (or the database sdb: tests/test_gpu_weigh_planted.py), opened for the kernel of `route`; the
+    route's developer knobs hold while it is open"""
     env, lanes, says = ROUTES[route]
     for knob in KNOBS:
         monkeypatch.delenv(knob, raising=False)
     for knob, v in env.items():
         monkeypatch.setenv(knob, v)
-    db = ra.PhyloKmerDB.from_synth(P.tree(name)[0], device=0)
+    db = ra.PhyloKmerDB.from_synth(P.tree(name)[0] if sdb is None else sdb, device=0)
     try:
         db.set_lanes_per_read(lanes)
         assert says in db.kernel_name(), (route, db.kernel_name())
