@@ -989,13 +989,15 @@ static int launch_variant(const rk_db *db, const Geometry &g, const PlaceArgs &a
             // and the batch took 1.45 ms instead of 1.14 -- the 0.25 / 0.30 of the uneven split.  Nine to eleven resident waves of a
             // compact-table instance go back to the eight (two a SIMD) that every such instance had before; nothing else changes.
             whole_simds = TM == TM_COMPACT;
+            constexpr bool D24 = TM == TM_COMPACT;  // (the other tables have no dense view: k24 is k16 there)
+            constexpr int U24 = D24 ? RK_RING_DENSE : U;  // the dense instances' own ring (DESIGN.md 4.1a "Round 11")
             auto k16 = place_packed16_kernel<BITS, TM, U, PU>;
-            auto k24 = place_packed16_kernel<BITS, TM, U, PU, TM == TM_COMPACT>;
+            auto k24 = place_packed16_kernel<BITS, TM, U24, PU, D24>;
             if constexpr (BITS == 5) {
                 // every read of the batch has the same, known length and at most 96 k-mers (C4: 100 residues, k = 5): six rounds
                 if (!args.lens && args.fixed_len >= db->info.k && args.fixed_len - db->info.k + 1 <= 96u) {
                     k16 = place_packed16_kernel<BITS, TM, U, 6>;
-                    k24 = place_packed16_kernel<BITS, TM, U, 6, TM == TM_COMPACT>;
+                    k24 = place_packed16_kernel<BITS, TM, U24, 6, D24>;
                 }
             }
             kern = k16;
@@ -1364,6 +1366,7 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
     // (the tile-pipelined variant serves packed records of <= 16 words, i.e. reads of <= 256 bases / 102 residues; longer
     // records take place_packed_kernel with the same geometry)
     const bool pipe = use_pipelined16(db, g, probe);
+    // (U: the ring the geometry counts with, RK_RING; the ROW24 instances run their own, RK_RING_DENSE, on the same list)
     snprintf(buf, sizeof(buf), "%s<G=%u,BITS=%u,%s,%s%s,U=%d,PU=%u> lds/wave=%zuB cap=%u waves/CU<=%u (LDS; registers may allow fewer)%s",
              pipe ? "place_packed16_kernel" : "place_packed_kernel", g.G, db->info.bits_per_symbol, db->info.table_mode == RK_TABLE_DIRECT ? (db->compact_nib ? "DIRECT4" : "DIRECT") : (db->info.table_mode == RK_TABLE_DIRECT8 ? "DIRECT8" : "HASH"),
              pipe && db->d_dense_rows ? "ROW24," : "", db->info.rows_bytes < ROWS_FIT32_LIMIT ? "ITEM32" : "ITEM64", g.G == 64 ? RK_RING64 : RK_RING, g.pu, g.lds_per_wave, g.list_cap, g.waves_per_cu,

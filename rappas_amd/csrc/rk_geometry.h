@@ -27,6 +27,9 @@
 #ifndef RK_RING64
 #define RK_RING64 8  // ... and for the 64-lane geometry (one wave per read: large trees with long rows, one or two waves per SIMD)
 #endif
+#ifndef RK_RING_DENSE
+#define RK_RING_DENSE 12  // ... and of the dense 24-entry instances of place_packed16_kernel (even, 8 .. 16: a block's items are the 16 lanes of one register; 14 and 16 spill, DESIGN.md 5 "Round 11")
+#endif
 
 namespace rk_geom {
 
@@ -101,6 +104,12 @@ static inline Status choose_geometry(uint32_t nb, uint32_t bits, size_t lds_per_
     if (kn.waves_per_cu >= 1 && kn.waves_per_cu < g.waves_per_cu) g.waves_per_cu = kn.waves_per_cu;  // developer knob for occupancy experiments
     return GEOM_OK;
 }
+// The dense 24-entry instances of place_packed16_kernel (ring of U = RK_RING_DENSE row units, a block's U items in the lanes of one
+// register): the flush of a tile writes fillers behind the longest list as far as the step loop reads items -- two turns of the ring,
+// or the end of the 16-item read of the last whole block, U + 16 -- and a read's list takes items up to what that leaves of its
+// 2 * list_cap words (less one pair).  min_cap above leaves at least 126: more than the 2U an early start asks for.
+static constexpr uint32_t dense_list_fillers(uint32_t U) { return U + 16 > 2 * U ? U + 16 : 2 * U; }
+static constexpr uint32_t dense_cap_items(uint32_t list_cap, uint32_t U) { return 2 * list_cap - dense_list_fillers(U) - 2; }
 
 // ---- windowed images and their kernels ----
 // mid-size trees: the score vector of a read is held one window of W branches at a time (place_packed16w_kernel)

@@ -27,6 +27,7 @@
 #include "rk_edpl.h"
 #include "rk_kmeans.h"
 #include "rk_diversity.h"
+#include "rk_geometry.h"  // (host arithmetic; place_packed16_kernel takes the dense list's room from it, as the host does)
 
 #include <type_traits>
 #ifndef RK_ROW_NT
@@ -663,9 +664,12 @@ __device__ __forceinline__ void accumulate_units(u32 *S, const u32 *items, int w
 // behind them, are filled by units_issue (the first U gathers of a list and the next U items) and run down by units_run: the kernel
 // fills the ring from inside its emit phase when the head of the list is final early, and from its flush otherwise (DESIGN.md 4.1a
 // "Round 9").  The steps are accumulate_units' steps; the other kernels keep that function as it was, instruction for instruction.
-template <int U>
+// ROWIT (the dense instances; DESIGN.md 4.1a "Round 11"): the U items are the lanes of ONE register -- lane u of a read's 16 lanes holds
+// the item of ring place u, read by one ds_read_b32 with per-lane addresses, and the step that feeds place u takes it through DPP
+// row_newbcast:u in its offset add.  it[0]: the items of the block that runs; it[1]: those of the next, read while it runs.
+template <int U, bool ROWIT = false>
 struct UnitRing {
-    u32 sb[U], it[U];
+    u32 sb[U], it[ROWIT ? 2 : U];
     float sc[U];
 };
 template <int G>
@@ -705,30 +709,58 @@ __device__ __forceinline__ float touch_base_behind(u32 old, float QT, const u32 
     }
     return base;
 }
-template <int G, int U>
-__device__ __forceinline__ void units_issue(UnitRing<U> &r, const u32 *items, u32 li, __amdgpu_buffer_rsrc_t rs) {
-#pragma unroll
-    for (int u = 0; u < U; u++) unit_issue<G>(rs, items[u], li, r.sb[u], r.sc[u]);
-#pragma unroll
-    for (int u = 0; u < U; u++) r.it[u] = items[U + u];
+// unit_offset<16> of the item that lane `place` of the row holds: the offset add of a step with the item taken through DPP, one
+// instruction as before.  Volatile as the add it replaces (units_run).  `row` is written by an LDS read or by row_items_next, which
+// brings its own wait states: the compiler pads no DPP hazard inside an asm, so no VALU copy of `row` may stand within two wait states
+// in front of this statement (checked in the ISA of every step: DESIGN.md 4.1a "Round 11").
+#define RK_ROW_ITEM_CASE(L) \
+    case L: asm volatile("v_add_u32_dpp %0, %1, %2 row_newbcast:" #L " row_mask:0xf bank_mask:0xf" : "=v"(off) : "v"(row), "v"(li8)); break;
+__device__ __forceinline__ u32 row_item_offset(int place, u32 row, u32 li8) {
+    u32 off = 0u;
+    switch (place) {  // (constant once the step loop is unrolled)
+        RK_ROW_ITEM_CASE(0) RK_ROW_ITEM_CASE(1) RK_ROW_ITEM_CASE(2) RK_ROW_ITEM_CASE(3) RK_ROW_ITEM_CASE(4) RK_ROW_ITEM_CASE(5)
+        RK_ROW_ITEM_CASE(6) RK_ROW_ITEM_CASE(7) RK_ROW_ITEM_CASE(8) RK_ROW_ITEM_CASE(9) RK_ROW_ITEM_CASE(10) RK_ROW_ITEM_CASE(11)
+        RK_ROW_ITEM_CASE(12) RK_ROW_ITEM_CASE(13) RK_ROW_ITEM_CASE(14) RK_ROW_ITEM_CASE(15)
+    }
+    return off;
 }
-// TILE: the caller is place_packed16_kernel, whose flush writes fillers up to wcnt + 2U.  Its loop runs whole blocks of U steps only
-// while more than U - 2 steps are left, and ends with one, two or three pairs of steps (wave-uniform: wcnt is scalar) that feed the
+#undef RK_ROW_ITEM_CASE
+// the next block's items become the running block's: one copy a block, with the two wait states the first step's DPP needs behind it
+__device__ __forceinline__ void row_items_next(u32 &row, u32 next) { asm volatile("v_mov_b32 %0, %1\n\ts_nop 1" : "=v"(row) : "v"(next)); }
+template <int G, int U, bool ROWIT>
+__device__ __forceinline__ void units_issue(UnitRing<U, ROWIT> &r, const u32 *items, u32 li, __amdgpu_buffer_rsrc_t rs) {
+    if constexpr (ROWIT) {
+        static_assert(G == 16 && U <= 16, "a read's 16 lanes hold a block's items");
+        const u32 head = items[li];  // the first 16 items; places 0 .. U - 1 are used
+#pragma unroll
+        for (int u = 0; u < U; u++) unit_load(rs, (RK_ABLATE & 16) ? li * 8 : row_item_offset(u, head, li * 8), r.sb[u], r.sc[u]);
+        r.it[0] = items[U + li];
+    } else {
+#pragma unroll
+        for (int u = 0; u < U; u++) unit_issue<G>(rs, items[u], li, r.sb[u], r.sc[u]);
+#pragma unroll
+        for (int u = 0; u < U; u++) r.it[u] = items[U + u];
+    }
+}
+// TILE: the caller is place_packed16_kernel, whose flush writes fillers up to wcnt + 2U (ROWIT: as far as the 16-item read of the
+// last whole block reaches, rk_geom::dense_list_fillers).  Its loop runs whole blocks of U steps only
+// while more than U - 2 steps are left, and ends with up to (U - 2) / 2 pairs of steps (wave-uniform: wcnt is scalar) that feed the
 // ring no more: what would follow are fillers, whose loads make no memory request.  The loop's block stays one basic block -- an exit
 // test between the steps of the unrolled body cost 12 % of the kernel (DESIGN.md 5 "Round 9"): the scheduler interleaves steps inside
-// a block only -- and the pairs are nested, not three blocks side by side: the ends of such blocks differ in nothing but the ring
+// a block only -- and the pairs are nested, not blocks side by side: the ends of such blocks differ in nothing but the ring
 // places they name, the compiler merges them into one block that indexes the ring by a variable, and the ring goes to scratch memory.
 template <int F, int N, bool B> struct StepBlock { static constexpr int first = F, steps = N; static constexpr bool feed = B; };
-template <int G, int U, bool MONO, bool WIN = false, bool D24 = false, bool TILE = false>
-__device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *items, int wcnt, u32 li, __amdgpu_buffer_rsrc_t rs, float QT, float T,
+template <int G, int U, bool MONO, bool WIN = false, bool D24 = false, bool TILE = false, bool ROWIT = false>
+__device__ __forceinline__ void units_run(UnitRing<U, ROWIT> &r, u32 *S, const u32 *items, int wcnt, u32 li, __amdgpu_buffer_rsrc_t rs, float QT, float T,
                                           u32 wlo4p4 = 4u, u32 w4 = 0xFFFFFFFFu, Stamps *stamps = nullptr) {
     static_assert(!D24 || (G == 16 && !WIN), "dense units: 16-lane groups, whole trees");
-    static_assert(!TILE || U == 8, "a tail of up to three pairs of steps");
+    static_assert(!TILE || (U >= 8 && U <= 16 && U % 2 == 0), "a tail of up to seven pairs of steps");
+    static_assert(!ROWIT || (D24 && TILE), "items in the lanes of a register: the dense instances of place_packed16_kernel");
     static_assert(rk_slots24::SLOT_BITS == SLOT24_BITS, "rk_slots24.h unpacks the slot words rk_device.h defines");
     const rk_slots24::Shifts sh24 = rk_slots24::lane_shifts(li);  // D24: where this lane's two slots sit in the word the DPP leaves it
     const u32 li8 = li * 8;
     u32(&sb)[U] = r.sb;
-    u32(&it)[U] = r.it;
+    u32(&it)[ROWIT ? 2 : U] = r.it;
     float(&sc)[U] = r.sc;
     auto issue = [&](u32 item, u32 &b, float &v) { unit_issue<G>(rs, item, li, b, v); };
     auto slot_of = [&](u32 b) {  // WIN: S holds one window of the tree -- slot offsets are rebased, everything outside goes to the scratch word
@@ -755,6 +787,9 @@ __device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *ite
     }
     int s0 = 0;
     u32 *pa = S, *pb = S;  // D24: the two words of the step to come
+    // (the items' LDS read ends here, under the wait for the first unit: inside the loop the register is written by row_items_next
+    // alone, and a read still counted as pending at the loop's head put an lgkmcnt wait in front of every block's first offset add)
+    if constexpr (ROWIT) asm volatile("" : "+v"(it[0]));
     if (D24) prepare(sc[0], pa, pb);
     // steps s0 + first .. s0 + first + steps - 1, from the ring places first ..; feed: each place takes the unit of step + U and the
     // item of step + 2U
@@ -774,24 +809,36 @@ __device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *ite
                     const u32 oa = *pa, ob = *pb;
                     prepare(sc[(u + 1) % U], na, nb);  // the next step's entry (after the last step: a filler's zeros)
                     u32 off = 0u;  // unit_offset<16>; volatile as in prepare: left free, the add of step n + 1 is lifted behind step n's wait
-                    if (FEED && (RK_ABLATE & 16)) off = unit_offset<G>(it[u], li);
-                    else if (FEED) asm volatile("v_add_u32 %0, %1, %2" : "=v"(off) : "v"(it[u]), "v"(li8));
+                    if constexpr (ROWIT) {
+                        if (FEED) off = (RK_ABLATE & 16) ? li8 : row_item_offset(u, it[0], li8);
+                    } else {
+                        if (FEED && (RK_ABLATE & 16)) off = unit_offset<G>(it[u], li);
+                        else if (FEED) asm volatile("v_add_u32 %0, %1, %2" : "=v"(off) : "v"(it[u]), "v"(li8));
+                    }
                     *pa = __float_as_uint(touch_base_behind<MONO, FEED>(oa, QT, na, nb, off) + __uint_as_float(sb[u]));
                     *pb = __float_as_uint(touch_base_behind<MONO, FEED>(ob, QT, na, nb, off) + sc[u]);  // (whichever word arrives first)
                     if (FEED) unit_load(rs, off, sb[u], sc[u]);
                 }
                 pa = na;
                 pb = nb;
-                if (FEED) {
+                if constexpr (ROWIT) {
+                    if (FEED) {
+                        if (RK_ABLATE & 8) unit_load(rs, (RK_ABLATE & 16) ? li8 : row_item_offset(u, it[0], li8), sb[u], sc[u]);
+                        if (u == F) it[1] = items[s0 + 2 * U + (int)li];  // the next block's items: one read, a block ahead
+                        if (u == F + N - 1) row_items_next(it[0], it[1]);
+                    }
+                } else if (FEED) {
                     if (RK_ABLATE & 8) issue(it[u], sb[u], sc[u]);
                     it[u] = items[s0 + 2 * U + u];
                 }
                 continue;
             }
-            apply_slot<MONO>(S, slot_of(sb[u]), sc[u], QT, T);
-            if (FEED) {
-                issue(it[u], sb[u], sc[u]);
-                it[u] = items[s0 + 2 * U + u];
+            if constexpr (!ROWIT) {
+                apply_slot<MONO>(S, slot_of(sb[u]), sc[u], QT, T);
+                if (FEED) {
+                    issue(it[u], sb[u], sc[u]);
+                    it[u] = items[s0 + 2 * U + u];
+                }
             }
         }
     };
@@ -805,7 +852,19 @@ __device__ __forceinline__ void units_run(UnitRing<U> &r, u32 *S, const u32 *ite
             block(StepBlock<0, 2, false>());
             if (left > 2) {
                 block(StepBlock<2, 2, false>());
-                if (left > 4) block(StepBlock<4, 2, false>());
+                if (left > 4) {
+                    block(StepBlock<4, 2, false>());
+                    if constexpr (U > 8) if (left > 6) {
+                        block(StepBlock<6, 2, false>());
+                        if constexpr (U > 10) if (left > 8) {
+                            block(StepBlock<8, 2, false>());
+                            if constexpr (U > 12) if (left > 10) {
+                                block(StepBlock<10, 2, false>());
+                                if constexpr (U > 14) if (left > 12) block(StepBlock<12, 2, false>());
+                            }
+                        }
+                    }
+                }
             }
         }
         if (stamps) stamps->add(12, (unsigned long long)(s0 + (left > 0 ? (left + 1) & ~1 : 0)));  // (stamps build: the steps taken)
@@ -1809,8 +1868,11 @@ __device__ __forceinline__ u64 unit_desc(u32 unit, u32 n) { return n ? ((u64)(un
 
 // D24: a.db is the image's dense view (rk_device.h: 24-entry units, its own compact table); everything but the accumulate step and
 // the wide-row fallback is the same.
+// (waves_per_eu: the dense instances run two waves a SIMD -- 20 KB of LDS a wave, eight a CU -- and a ring deeper than eight left to the
+// register allocator's own limit, 512 for a block of four waves, takes a few registers more than the 256 that two waves leave each;
+// 1 is what the launch bounds alone say, and leaves the canonical instances' code as it was)
 template <int BITS, int TM, int U, int PU, bool D24 = false>
-__global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(D24 ? 2 : 1))) place_packed16_kernel(PlaceArgs a) {
     constexpr int G = 16, NG = 4;
     static_assert(TM != TM_HASH, "direct tables only");
     static_assert(!D24 || TM == TM_COMPACT, "the dense view carries a compact table");
@@ -1830,7 +1892,10 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
     const u32 k = a.db.k;
     const float T = a.db.T;
     const __amdgpu_buffer_rsrc_t rows_rs = rows_resource(a.db);
-    const int cap_items = (int)(a.list_cap * 2) - 3 * U - 2;
+    // D24: the items of a block of U steps are the lanes of one register (UnitRing, ROWIT), and the list keeps free what the fillers
+    // of a flush need behind it, no more (rk_geometry.h)
+    constexpr int FILLERS = D24 ? (int)rk_geom::dense_list_fillers(U) : 2 * U;
+    const int cap_items = D24 ? (int)rk_geom::dense_cap_items(a.list_cap, U) : (int)(a.list_cap * 2) - 3 * U - 2;
     const int cap_rows = (int)a.list_cap - 1;
     const u32 wpr = a.words_per_read;  // <= 16 (checked by the host)
 
@@ -1915,7 +1980,7 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
         int cnt = 0;  // chunk items waiting in the list
         // the row ring of this tile's first flush, when emit_batch has started it (ring_live, wave-uniform); it never outlives the tile:
         // a started ring means cnt >= 2U in every group, so the flush after the emit phase runs it down at the latest
-        UnitRing<U> ring;
+        UnitRing<U, D24> ring;
         bool ring_live = false;
         constexpr bool EARLY = D24;  // (the canonical units keep their ring start in the flush)
         // (always_inline: left to its cost model the compiler makes the dense instance's flush a function once the step loop has its tail,
@@ -1925,14 +1990,14 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
             wcnt = max(wcnt, __builtin_amdgcn_readlane(cnt, 32));
             wcnt = max(wcnt, __builtin_amdgcn_readlane(cnt, 16));
             wcnt = max(wcnt, __builtin_amdgcn_readlane(cnt, 48));
-            for (int i = cnt + (int)li; i < wcnt + 2 * U; i += G) items[i] = ITEM_FILLER;  // (a live ring's groups hold >= 2U items: its 2U items stay)
+            for (int i = cnt + (int)li; i < wcnt + FILLERS; i += G) items[i] = ITEM_FILLER;  // (a live ring's groups hold >= 2U items: its 2U items stay)
             wave_lds_fence();
             stamps.mark(10);  // flush outside the ring: fillers, fences (and what the caller did since its last mark)
-            if (!ring_live) units_issue<G, U>(ring, items, li, rows_rs);
+            if (!ring_live) units_issue<G, U, D24>(ring, items, li, rows_rs);
             ring_live = false;
             stamps.mark(11);  // the ring's U gathers and U item reads
-            if (a.db.mono) units_run<G, U, true, false, D24, true>(ring, S, items, wcnt, li, rows_rs, QT, T, 4u, 0xFFFFFFFFu, stamps.ptr());
-            else units_run<G, U, false, false, D24, true>(ring, S, items, wcnt, li, rows_rs, QT, T, 4u, 0xFFFFFFFFu, stamps.ptr());
+            if (a.db.mono) units_run<G, U, true, false, D24, true, D24>(ring, S, items, wcnt, li, rows_rs, QT, T, 4u, 0xFFFFFFFFu, stamps.ptr());
+            else units_run<G, U, false, false, D24, true, D24>(ring, S, items, wcnt, li, rows_rs, QT, T, 4u, 0xFFFFFFFFu, stamps.ptr());
             stamps.mark(4);  // the steps (slot 7, inside: the wait for the first row unit)
             wave_lds_fence();
             stamps.mark(10);
@@ -1997,7 +2062,7 @@ __global__ void __launch_bounds__(256) place_packed16_kernel(PlaceArgs a) {
                         if (u0 == 0 && PU > 4 && pos == 0 && !__any(total < 2 * U || total > cap_items)) {  // (more than the list holds: the parts path decides)
                             write_rows(0, 4);
                             wave_lds_fence();
-                            units_issue<G, U>(ring, items, li, rows_rs);
+                            units_issue<G, U, D24>(ring, items, li, rows_rs);
                             __builtin_amdgcn_sched_barrier(0);  // (the gathers stay in front of the remaining scans)
                             ring_live = early = true;
                         }
