@@ -204,23 +204,42 @@ static rk_geom::Knobs geom_knobs() {  // (developer knobs, read where the geomet
             rk_knob("RK_WINDOW_ALWAYS") != nullptr, rk_knob("RK_WSTREAM_ALWAYS") != nullptr};
 }
 
+// What an image is, apart from its bytes.  Every producer makes one (build_image, the synthetic builder, shape_of(ImageHeader), a
+// handle keeps the one it was installed with) and every consumer reads one (info_of, header_of, install).
+struct ImageShape {
+    uint32_t alphabet = 0, convert_uo = 0, k = 0, n_branches = 0;  // the scalars every database carries, whatever built its image
+    float thr_log10 = 0.0f, thr = 0.0f;
+    uint32_t mode = 0, bits = 0, max_len = 0;  // table mode (never AUTO), bits per symbol, longest row
+    bool indexed = false;   // rows carry an index line (large trees, place_wg_kernel)
+    bool mono = true;       // every score >= thr_log10 (true of every database RAPPAS builds: words below the threshold are not stored)
+    bool nib = false;       // the compact table holds 4-bit unit counts
+    bool windowed = false;  // place_packed16w_kernel can serve this image: the third section holds a window span per k-mer code
+    bool has_pos = false;   // not windowed, but the third section holds the rows' position in the tree (64 ranges): the key reads are grouped by
+    uint64_t n_keys = 0, n_entries = 0, slots = 0, hash_mask = 0;
+    WindowPlan wp;          // all zero unless windowed
+    uint64_t table_bytes = 0, rows_bytes = 0, winspec_bytes = 0;  // the three sections; winspec_bytes = sigma^k when windowed || has_pos, else 0
+};
+
+static void info_of(const ImageShape &s, int device, rk_db_info *info) {
+    memset(info, 0, sizeof(*info));
+    info->alphabet = s.alphabet; info->k = s.k; info->n_branches = s.n_branches; info->table_mode = s.mode;
+    info->thr_log10 = s.thr_log10; info->thr = s.thr; info->n_keys = s.n_keys; info->n_entries = s.n_entries;
+    info->table_slots = s.slots; info->table_bytes = s.table_bytes; info->rows_bytes = s.rows_bytes;
+    info->bits_per_symbol = s.bits; info->max_row_len = s.max_len; info->device = device;
+}
+
 struct rk_db {
+    ImageShape shape;                  // what install() was given; info and view below are derived from it in finish_db
     rk_db_info info{};
-    uint32_t convert_uo = 0;
     DbView view{};
     void *d_table = nullptr;
     void *d_rows = nullptr;
     unsigned char *d_alpha = nullptr;  // table[256] | alts[320] | alt_count[16]
-    unsigned char *d_winspec = nullptr;  // [sigma^k] window span per k-mer (windowed images only)
-    bool windowed = false;
-    bool has_pos = false;              // d_winspec holds position keys only (dense kernels)
-    bool compact_nib = false;          // the compact table holds 4-bit unit counts
+    unsigned char *d_winspec = nullptr;  // [sigma^k] window span or position key per k-mer (shape.windowed || shape.has_pos)
     void *d_dense_table = nullptr;     // dense view (rk_device.h, ROW_UNIT24) for place_packed16_kernel, or nullptr: build_dense_view
     void *d_dense_rows = nullptr;
     uint64_t dense_rows_bytes = 0;
-    WindowPlan wp;
     uint32_t lanes_per_read = 0;       // 0 = auto
-    bool indexed = false;              // rows carry an index line (large trees, place_wg_kernel)
     int cu_count = 256;
     size_t lds_per_cu = 160 * 1024;
     hipStream_t stream = nullptr;      // spare stream
@@ -275,46 +294,22 @@ extern "C" void rk_db_destroy(rk_db *db) {
     delete db;
 }
 
-// scalars every database carries, whatever built its image
-struct DbMeta {
-    uint32_t alphabet, convert_uo, k, n_branches;
-    float thr_log10, thr;
-};
-
-// device selection, properties, spare stream and the alphabet tables; the caller restores the current device
-static int open_db(const DbMeta &m, int device, rk_db **out) {
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(RK_ERR_NO_DEVICE, "rk_db_create: no HIP device available (this engine has no CPU fallback)");
-    if (device < 0 || device >= ndev)
-        return fail(RK_ERR_INVALID, "rk_db_create: device %d out of range (0..%d)", device, ndev - 1);
-    rk_db *db = new (std::nothrow) rk_db();
-    if (!db) return fail(RK_ERR_NOMEM, "rk_db_create: host OOM");
-    db->info.device = device;
-#define OPEN_TRY(expr)                                                                            \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            int c_ = fail(e_ == hipErrorOutOfMemory ? RK_ERR_NOMEM : RK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rk_db_destroy(db);                                                                    \
-            return c_;                                                                            \
-        }                                                                                         \
-    } while (0)
-    OPEN_TRY(hipSetDevice(device));
+// device selection, properties, spare stream and the alphabet tables of a handle whose shape and device are set; install() owns the
+// handle and restores the current device
+static int open_db(rk_db *db) {
+    const int device = db->info.device;
+    HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    OPEN_TRY(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     db->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     db->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor ? (size_t)prop.maxSharedMemoryPerMultiProcessor : 64 * 1024;
-    OPEN_TRY(hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
-    OPEN_TRY(hipMalloc((void **)&db->d_alpha, 256 + 320 + 16));
+    HIP_TRY(hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
+    HIP_TRY(hipMalloc((void **)&db->d_alpha, 256 + 320 + 16));
     Alphabet A;
-    build_alphabet(m.alphabet, m.convert_uo != 0, A);
-    OPEN_TRY(hipMemcpy(db->d_alpha, A.table, 256, hipMemcpyHostToDevice));
-    OPEN_TRY(hipMemcpy(db->d_alpha + 256, A.alts, 320, hipMemcpyHostToDevice));
-    OPEN_TRY(hipMemcpy(db->d_alpha + 576, A.alt_count, 16, hipMemcpyHostToDevice));
-#undef OPEN_TRY
-    *out = db;
+    build_alphabet(db->shape.alphabet, db->shape.convert_uo != 0, A);
+    HIP_TRY(hipMemcpy(db->d_alpha, A.table, 256, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db->d_alpha + 256, A.alts, 320, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db->d_alpha + 576, A.alt_count, 16, hipMemcpyHostToDevice));
     return RK_OK;
 }
 
@@ -400,7 +395,7 @@ __global__ void dense_fill_kernel(const uint4 *ctab, uint4 *dtab, u64 n_blocks, 
 // device memory, or the developer knob RK_NO_DENSE_UNITS, read per handle, for A/B runs and tests).  Needs the canonical image complete
 // on the current device.
 static void build_dense_view(rk_db *db) {
-    if (db->info.table_mode != RK_TABLE_DIRECT || db->info.n_branches > SLOT24_MAX || db->indexed || db->windowed ||
+    if (db->info.table_mode != RK_TABLE_DIRECT || db->info.n_branches > SLOT24_MAX || db->shape.indexed || db->shape.windowed ||
         db->info.rows_bytes >= ROWS_FIT32_LIMIT || db->info.table_bytes < 16 || rk_knob("RK_NO_DENSE_UNITS"))
         return;
     // ... where rows stream (the nibble form's rule, build_table): a dense step costs more VALU and LDS work per unit, which only fewer row
@@ -408,7 +403,7 @@ static void build_dense_view(rk_db *db) {
     // against 3.66e8
     if (2 * (db->info.rows_bytes / 128) < db->info.table_slots) return;
     const u64 n_blocks = db->info.table_bytes / 16;
-    const u32 per = db->compact_nib ? 2 * COMPACT_KMERS : COMPACT_KMERS;
+    const u32 per = db->shape.nib ? 2 * COMPACT_KMERS : COMPACT_KMERS;
     const unsigned grid = (unsigned)std::min<u64>((n_blocks + 255) / 256, (u64)db->cu_count * 8);
     u32 *d_sums = nullptr;
     bool ok = false;
@@ -416,7 +411,7 @@ static void build_dense_view(rk_db *db) {
         std::vector<u32> sums(n_blocks);
         if (hipMalloc((void **)&d_sums, n_blocks * 4) != hipSuccess || hipMalloc(&db->d_dense_table, n_blocks * 16) != hipSuccess) break;
         hipLaunchKernelGGL(dense_count_kernel, dim3(grid), dim3(256), 0, db->stream, (const uint4 *)db->d_table, (uint4 *)db->d_dense_table,
-                           (u64)n_blocks, per, db->compact_nib, (const Entry *)db->d_rows, d_sums);
+                           (u64)n_blocks, per, db->shape.nib, (const Entry *)db->d_rows, d_sums);
         if (hipGetLastError() != hipSuccess || hipMemcpyAsync(sums.data(), d_sums, n_blocks * 4, hipMemcpyDeviceToHost, db->stream) != hipSuccess ||
             hipStreamSynchronize(db->stream) != hipSuccess)
             break;
@@ -432,7 +427,7 @@ static void build_dense_view(rk_db *db) {
             hipMemcpyAsync(d_sums, sums.data(), n_blocks * 4, hipMemcpyHostToDevice, db->stream) != hipSuccess)
             break;
         hipLaunchKernelGGL(dense_fill_kernel, dim3(grid), dim3(256), 0, db->stream, (const uint4 *)db->d_table, (uint4 *)db->d_dense_table,
-                           (u64)n_blocks, per, db->compact_nib, (const Entry *)db->d_rows, (const u32 *)d_sums, db->info.thr_log10,
+                           (u64)n_blocks, per, db->shape.nib, (const Entry *)db->d_rows, (const u32 *)d_sums, db->info.thr_log10,
                            (uint4 *)db->d_dense_rows);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(db->stream) != hipSuccess) break;
         db->dense_rows_bytes = bytes;
@@ -448,35 +443,61 @@ static void build_dense_view(rk_db *db) {
     }
 }
 
-// info + device view once d_table / d_rows hold the image
-static void finish_db(rk_db *db, const DbMeta &m, uint32_t mode, bool indexed, bool mono, uint64_t n_keys, uint64_t n_entries,
-                      uint64_t slots, uint64_t hash_mask, uint64_t table_bytes, uint64_t blob_bytes, uint32_t max_len) {
-    const uint32_t bits = m.alphabet == RK_ALPHABET_DNA ? 2 : 5;
-    db->convert_uo = m.convert_uo;
-    db->indexed = indexed;
-    db->info.alphabet = m.alphabet; db->info.k = m.k; db->info.n_branches = m.n_branches;
-    db->info.table_mode = mode; db->info.thr_log10 = m.thr_log10; db->info.thr = m.thr;
-    db->info.n_keys = n_keys; db->info.n_entries = n_entries; db->info.table_slots = slots;
-    db->info.table_bytes = table_bytes; db->info.rows_bytes = blob_bytes; db->info.bits_per_symbol = bits;
-    db->info.max_row_len = max_len;
-    db->view.direct = mode == RK_TABLE_DIRECT8 ? (const u64 *)db->d_table : nullptr;
-    db->view.compact = mode == RK_TABLE_DIRECT ? (const uint4 *)db->d_table : nullptr;
-    db->view.compact_nib = db->compact_nib ? 1u : 0u;
-    db->view.slots = mode == RK_TABLE_HASH ? (const uint4 *)db->d_table : nullptr;
-    db->view.hash_mask = hash_mask;
+// info, device view and dense view from the shape, once d_table / d_rows / d_winspec hold the image: the one place they are derived
+static void finish_db(rk_db *db) {
+    const ImageShape &s = db->shape;
+    info_of(s, db->info.device, &db->info);
+    db->view.direct = s.mode == RK_TABLE_DIRECT8 ? (const u64 *)db->d_table : nullptr;
+    db->view.compact = s.mode == RK_TABLE_DIRECT ? (const uint4 *)db->d_table : nullptr;
+    db->view.compact_nib = s.nib ? 1u : 0u;
+    db->view.slots = s.mode == RK_TABLE_HASH ? (const uint4 *)db->d_table : nullptr;
+    db->view.hash_mask = s.hash_mask;
     db->view.rows = (const unsigned char *)db->d_rows;
-    db->view.rows_bytes = db->info.rows_bytes;
-    db->view.k = m.k; db->view.bits = bits; db->view.n_branches = m.n_branches; db->view.alphabet = m.alphabet;
-    db->view.T = m.thr_log10; db->view.P = m.thr; db->view.convert_uo = m.convert_uo;
-    db->view.soa = indexed ? 1u : 0u;
-    db->view.mono = mono ? 1u : 0u;
-    db->view.winspec = (db->windowed || db->has_pos) ? db->d_winspec : nullptr;
-    db->view.win_w = db->windowed ? db->wp.W : 0u;
-    db->view.n_win = db->windowed ? db->wp.n_win : 0u;
+    db->view.rows_bytes = s.rows_bytes;
+    db->view.k = s.k; db->view.bits = s.bits; db->view.n_branches = s.n_branches; db->view.alphabet = s.alphabet;
+    db->view.T = s.thr_log10; db->view.P = s.thr; db->view.convert_uo = s.convert_uo;
+    db->view.soa = s.indexed ? 1u : 0u;
+    db->view.mono = s.mono ? 1u : 0u;
+    db->view.winspec = (s.windowed || s.has_pos) ? db->d_winspec : nullptr;
+    db->view.win_w = s.windowed ? s.wp.W : 0u;
+    db->view.n_win = s.windowed ? s.wp.n_win : 0u;
     build_dense_view(db);
 }
 
 static int check_launchable(const rk_db *db);
+
+// The one way a handle is made: a handle of `shape` on `device`, its three sections allocated from the shape's sizes and filled by
+// fill(db, section, dst, bytes) -> RK_* (IMG_TABLE, IMG_ROWS, then IMG_WINSPEC where the image has one; `device` is current).  What the
+// four entry points differ in is their fill.  Any failure destroys the handle; the caller's current device is restored on every path.
+enum { IMG_TABLE, IMG_ROWS, IMG_WINSPEC };
+template <class Fill>
+static int install(const ImageShape &shape, int device, Fill fill, rk_db **out) {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    struct Restore { int p; ~Restore() { (void)hipSetDevice(p); } } restore{prev};
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(RK_ERR_NO_DEVICE, "rk_db_create: no HIP device available (this engine has no CPU fallback)");
+    if (device < 0 || device >= ndev)
+        return fail(RK_ERR_INVALID, "rk_db_create: device %d out of range (0..%d)", device, ndev - 1);
+    std::unique_ptr<rk_db, void (*)(rk_db *)> db(new (std::nothrow) rk_db(), rk_db_destroy);
+    if (!db) return fail(RK_ERR_NOMEM, "rk_db_create: host OOM");
+    db->shape = shape;
+    db->info.device = device;
+    if (int rc = open_db(db.get())) return rc;
+    HIP_TRY(hipMalloc(&db->d_table, shape.table_bytes ? shape.table_bytes : 8));
+    HIP_TRY(hipMalloc(&db->d_rows, shape.rows_bytes));
+    if (shape.windowed || shape.has_pos) HIP_TRY(hipMalloc((void **)&db->d_winspec, shape.winspec_bytes));
+    if (int rc = fill(*db, IMG_TABLE, db->d_table, shape.table_bytes)) return rc;
+    if (int rc = fill(*db, IMG_ROWS, db->d_rows, shape.rows_bytes)) return rc;
+    if (db->d_winspec)
+        if (int rc = fill(*db, IMG_WINSPEC, (void *)db->d_winspec, shape.winspec_bytes)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    finish_db(db.get());
+    if (int rc = check_launchable(db.get())) return rc;  // a tree whose score vector no kernel geometry can hold is refused here, not at the first batch
+    *out = db.release();
+    return RK_OK;
+}
 
 // ---- k-mer -> row descriptor table, keys given in ascending dense-index order through the accessors ----
 // DIRECT  : compact blocks, 16 bytes per 12 consecutive k-mers {u32 first row unit, 12 x u8 units per row}: 1.33 bytes
@@ -544,17 +565,10 @@ static int build_table(uint32_t &mode, uint64_t space, uint64_t n_keys, bool ind
 
 // Validation + host-side construction of the HBM image (no HIP call in here: rk_db_validate runs it without a device).
 struct DbImage {
-    uint32_t mode = 0, bits = 0, max_len = 0;
-    bool indexed = false;
-    bool mono = true;  // every score >= thr_log10 (true of every database RAPPAS builds: words below the threshold are not stored)
-    uint64_t n_keys = 0, n_entries = 0, blob_bytes = 0, slots = 0, hash_mask = 0;
-    std::vector<Entry> blob;
+    ImageShape shape;
     std::vector<uint64_t> table;
-    bool nib = false;                   // compact table in its 4-bit form
-    bool windowed = false;              // place_packed16w_kernel can serve this image
-    bool has_pos = false;               // not windowed, but winspec holds the rows' position in the tree (64 ranges): the key reads are grouped by
-    WindowPlan wp;
-    std::vector<unsigned char> winspec;  // [sigma^k]
+    std::vector<Entry> blob;
+    std::vector<unsigned char> winspec;  // [sigma^k], or empty
 };
 
 static int build_image(const rk_db_desc *d, DbImage &img) {
@@ -577,11 +591,14 @@ static int build_image(const rk_db_desc *d, DbImage &img) {
     if (n_entries && (!d->branch_ids || !d->scores)) return fail(RK_ERR_INVALID, "rk_db_create: null entry arrays");
     if (n_keys && d->row_offsets[0] != 0) return fail(RK_ERR_INVALID, "rk_db_create: row_offsets[0] must be 0");
 
-    img.bits = bits; img.n_keys = n_keys; img.n_entries = n_entries;
+    ImageShape &shape = img.shape;
+    shape.alphabet = d->alphabet; shape.convert_uo = d->convert_uo; shape.k = d->k; shape.n_branches = d->n_branches;
+    shape.thr_log10 = d->thr_log10; shape.thr = d->thr;
+    shape.bits = bits; shape.n_keys = n_keys; shape.n_entries = n_entries;
     // ---- table mode ----
     uint64_t space = 0;
     const bool space_ok = ipow_fits(d->alphabet, d->k, 1ull << 40, space);
-    uint32_t &mode = img.mode;
+    uint32_t &mode = shape.mode;
     mode = d->table_mode;
     if (mode == RK_TABLE_AUTO) {
         // Direct addressing whenever all sigma^k codes fit 2^28 slots; DIRECT = compact 2-byte-per-k-mer blocks that
@@ -644,7 +661,7 @@ static int build_image(const rk_db_desc *d, DbImage &img) {
     }
     const ImageKind kind = rk_geom::image_kind(d->n_branches, bits, mode == RK_TABLE_DIRECT, space, slot_units, longest, mean_len, geom_knobs());  // (AUTO is resolved by now)
     const bool indexed = kind.indexed;
-    img.indexed = indexed;
+    shape.indexed = indexed;
     std::vector<uint64_t> desc(n_keys);  // by key number
     WindowPlan wp;
     const bool want_windows = kind.windowable && rk_geom::window_plan(d->n_branches, bits, space ? (double)slot_units / (double)space : 0.0, mean_len / ROW_UNIT + 0.5, geom_knobs(), wp);
@@ -760,29 +777,28 @@ static int build_image(const rk_db_desc *d, DbImage &img) {
             return fail(RK_ERR_INVALID, "rk_db_create: non-finite score in row %llu", (unsigned long long)first->r);
         }
         for (char mflag : monos)
-            if (!mflag) img.mono = false;
+            if (!mflag) shape.mono = false;
     }
 
     // ---- table ----
     {
-        int rc = build_table(img.mode, space, n_keys, indexed, max_units, blob_units,
+        int rc = build_table(shape.mode, space, n_keys, indexed, max_units, blob_units,
                              [&](uint64_t i) { return order[i].first; }, [&](uint64_t i) { return desc[order[i].second]; },
-                             [&](uint64_t i) { return d->key_codes[order[i].second]; }, img.table, img.slots, img.hash_mask, img.nib);
+                             [&](uint64_t i) { return d->key_codes[order[i].second]; }, img.table, shape.slots, shape.hash_mask, shape.nib);
         if (rc) return rc;
     }
 
-    img.blob_bytes = blob_bytes;
-    img.max_len = max_len;
+    shape.table_bytes = img.table.size() * sizeof(uint64_t);
+    shape.rows_bytes = blob_bytes;
+    shape.max_len = max_len;
     // windows need the compact table (rows of <= 255 units) and 32-bit row offsets
-    if (want_windows && img.mode == RK_TABLE_DIRECT && blob_bytes < RK_WINDOW_MAX_BLOB) {
+    shape.windowed = want_windows && shape.mode == RK_TABLE_DIRECT && blob_bytes < RK_WINDOW_MAX_BLOB;
+    shape.has_pos = !shape.windowed && (want_windows || want_pos) && (shape.mode == RK_TABLE_DIRECT || shape.mode == RK_TABLE_DIRECT8);
+    if (shape.windowed) shape.wp = wp;
+    if (shape.windowed || shape.has_pos) {
         try { img.winspec.assign(space, 0); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create: host OOM"); }
         for (uint64_t i = 0; i < n_keys; i++) img.winspec[order[i].first] = ws_by_key[order[i].second];
-        img.windowed = true;
-        img.wp = wp;
-    } else if ((want_windows || want_pos) && (img.mode == RK_TABLE_DIRECT || img.mode == RK_TABLE_DIRECT8)) {
-        try { img.winspec.assign(space, 0); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create: host OOM"); }
-        for (uint64_t i = 0; i < n_keys; i++) img.winspec[order[i].first] = ws_by_key[order[i].second];
-        img.has_pos = true;
+        shape.winspec_bytes = space;
     }
     return RK_OK;
 }
@@ -792,13 +808,7 @@ extern "C" int rk_db_validate(const rk_db_desc *d, rk_db_info *info) {
     DbImage img;
     int rc = build_image(d, img);
     if (rc) return rc;
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->alphabet = d->alphabet; info->k = d->k; info->n_branches = d->n_branches; info->table_mode = img.mode;
-        info->thr_log10 = d->thr_log10; info->thr = d->thr; info->n_keys = img.n_keys; info->n_entries = img.n_entries;
-        info->table_slots = img.slots; info->table_bytes = img.table.size() * sizeof(uint64_t); info->rows_bytes = img.blob_bytes;
-        info->bits_per_symbol = img.bits; info->max_row_len = img.max_len; info->device = -1;
-    }
+    if (info) info_of(img.shape, -1, info);
     return RK_OK;
     RK_GUARD_END("rk_db_validate")
 }
@@ -808,52 +818,12 @@ extern "C" int rk_db_create(const rk_db_desc *d, rk_db **out) {
     if (!d || !out) return fail(RK_ERR_INVALID, "rk_db_create: null argument");
     *out = nullptr;
     DbImage img;
-    {
-        int rc = build_image(d, img);  // argument errors are reported before the device is looked at
-        if (rc) return rc;
-    }
-    const uint32_t mode = img.mode, max_len = img.max_len;
-    const bool indexed = img.indexed;
-    const uint64_t n_keys = img.n_keys, n_entries = img.n_entries, blob_bytes = img.blob_bytes, slots = img.slots, hash_mask = img.hash_mask;
-    std::vector<Entry> &blob = img.blob;
-    std::vector<uint64_t> &table = img.table;
-
-    // ---- upload ----
-    rk_db *db = nullptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    struct Restore { int p; ~Restore() { (void)hipSetDevice(p); } } restore{prev};
-    DbMeta meta{d->alphabet, d->convert_uo, d->k, d->n_branches, d->thr_log10, d->thr};
-    int rc = open_db(meta, d->device, &db);
-    if (rc) return rc;
-#define DB_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            int c_ = fail(e_ == hipErrorOutOfMemory ? RK_ERR_NOMEM : RK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rk_db_destroy(db);                                                                    \
-            return c_;                                                                            \
-        }                                                                                         \
-    } while (0)
-    const size_t table_bytes = table.size() * sizeof(uint64_t);
-    DB_TRY(hipMalloc(&db->d_table, table_bytes ? table_bytes : 8));
-    DB_TRY(hipMalloc(&db->d_rows, blob_bytes));
-    if (table_bytes) DB_TRY(hipMemcpy(db->d_table, table.data(), table_bytes, hipMemcpyHostToDevice));
-    DB_TRY(hipMemcpy(db->d_rows, blob.data(), blob_bytes, hipMemcpyHostToDevice));
-    if (img.windowed || img.has_pos) {
-        DB_TRY(hipMalloc((void **)&db->d_winspec, img.winspec.size()));
-        DB_TRY(hipMemcpy(db->d_winspec, img.winspec.data(), img.winspec.size(), hipMemcpyHostToDevice));
-        db->windowed = img.windowed;
-        db->has_pos = img.has_pos;
-        if (img.windowed) db->wp = img.wp;
-    }
-#undef DB_TRY
-    db->compact_nib = img.nib;
-    finish_db(db, meta, mode, indexed, img.mono, n_keys, n_entries, slots, hash_mask, table_bytes, blob_bytes, max_len);
-    rc = check_launchable(db);  // a tree whose score vector no kernel geometry can hold is refused here, not at the first batch
-    if (rc) { rk_db_destroy(db); return rc; }
-    *out = db;
-    return RK_OK;
+    if (int rc = build_image(d, img)) return rc;  // argument errors are reported before the device is looked at
+    const void *from[3] = {img.table.data(), img.blob.data(), img.winspec.data()};
+    return install(img.shape, d->device, [&](const rk_db &, int sec, void *dst, uint64_t bytes) -> int {
+        if (bytes) HIP_TRY(hipMemcpy(dst, from[sec], bytes, hipMemcpyHostToDevice));
+        return RK_OK;
+    }, out);
     RK_GUARD_END("rk_db_create")
 }
 
@@ -863,48 +833,16 @@ extern "C" int rk_db_clone(const rk_db *src, int32_t device, rk_db **out) {
     RK_GUARD_BEGIN
     if (!src || !out) return fail(RK_ERR_INVALID, "rk_db_clone: null argument");
     *out = nullptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    struct Restore { int p; ~Restore() { (void)hipSetDevice(p); } } restore{prev};
-    DbMeta meta{src->info.alphabet, src->convert_uo, src->info.k, src->info.n_branches, src->info.thr_log10, src->info.thr};
-    rk_db *db = nullptr;
-    int rc = open_db(meta, device, &db);
-    if (rc) return rc;
-#define CL_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            int c_ = fail(e_ == hipErrorOutOfMemory ? RK_ERR_NOMEM : RK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rk_db_destroy(db);                                                                    \
-            return c_;                                                                            \
-        }                                                                                         \
-    } while (0)
-    const size_t table_bytes = src->info.table_bytes, blob_bytes = src->info.rows_bytes;
+    const void *from[3] = {src->d_table, src->d_rows, src->d_winspec};
     const int sdev = src->info.device;
-    auto copy = [&](void *dst, const void *from, size_t bytes) {
-        return device == sdev ? hipMemcpy(dst, from, bytes, hipMemcpyDeviceToDevice) : hipMemcpyPeer(dst, device, from, sdev, bytes);
-    };
-    CL_TRY(hipMalloc(&db->d_table, table_bytes ? table_bytes : 8));
-    CL_TRY(hipMalloc(&db->d_rows, blob_bytes));
-    if (table_bytes) CL_TRY(copy(db->d_table, src->d_table, table_bytes));
-    CL_TRY(copy(db->d_rows, src->d_rows, blob_bytes));
-    if (src->windowed || src->has_pos) {
-        uint64_t space = 0;
-        (void)ipow_fits(src->info.alphabet, src->info.k, 1ull << 40, space);
-        CL_TRY(hipMalloc((void **)&db->d_winspec, space));
-        CL_TRY(copy(db->d_winspec, src->d_winspec, space));
-        db->windowed = src->windowed;
-        db->has_pos = src->has_pos;
-        db->wp = src->wp;
-    }
-    CL_TRY(hipDeviceSynchronize());
-#undef CL_TRY
-    db->compact_nib = src->compact_nib;
-    finish_db(db, meta, src->info.table_mode, src->indexed, src->view.mono != 0, src->info.n_keys, src->info.n_entries, src->info.table_slots,
-              src->view.hash_mask, table_bytes, blob_bytes, src->info.max_row_len);
-    db->lanes_per_read = src->lanes_per_read;
-    *out = db;
-    return RK_OK;
+    int rc = install(src->shape, device, [&](const rk_db &, int sec, void *dst, uint64_t bytes) -> int {
+        if (!bytes) return RK_OK;
+        if (device == sdev) HIP_TRY(hipMemcpy(dst, from[sec], bytes, hipMemcpyDeviceToDevice));
+        else HIP_TRY(hipMemcpyPeer(dst, device, from[sec], sdev, bytes));
+        return RK_OK;
+    }, out);
+    if (rc == RK_OK) (*out)->lanes_per_read = src->lanes_per_read;
+    return rc;
     RK_GUARD_END("rk_db_clone")
 }
 
@@ -939,7 +877,7 @@ extern "C" int rk_set_lanes_per_read(rk_db *db, uint32_t lanes) {
     if (!db) return fail(RK_ERR_INVALID, "rk_set_lanes_per_read: null db");
     if (lanes != 0 && lanes != 8 && lanes != 16 && lanes != 32 && lanes != 64)
         return fail(RK_ERR_INVALID, "rk_set_lanes_per_read: lanes must be 0 (auto), 8, 16, 32 or 64");
-    if (lanes != 0 && db->indexed)
+    if (lanes != 0 && db->shape.indexed)
         return fail(RK_ERR_UNSUPPORTED, "rk_set_lanes_per_read: this database uses the large-tree image (n_branches > %u, long rows): always the workgroup-per-read kernel", RK_WG_MIN_BRANCHES);
     db->lanes_per_read = lanes;
     return RK_OK;
@@ -1044,7 +982,7 @@ static bool use_windowed(const rk_db *db, uint32_t keep_at_most, uint32_t words_
     // 18.3 / 20.6 / 22.0; 7 999: 450 / 600 / 1000 bp: 17.5 / 15.2 / 10.8 against 11.8 / 12.7 / 14.4; 15 999: 1000 bp 9.7 against 6.8)
     const uint64_t max_symbols = (uint64_t)words_per_read * 32 / db->info.bits_per_symbol;
     const bool fits = words_per_read <= 16 || max_symbols * 9 <= db->info.n_branches || db->info.n_branches > 16000;  // (25 001 branches: 10.2 against 3.3 at 1000 bp)
-    return !off && db->windowed && db->lanes_per_read == 0 && keep_at_most <= 16 && fits;
+    return !off && db->shape.windowed && db->lanes_per_read == 0 && keep_at_most <= 16 && fits;
 }
 
 // ---- scratch of a launch: owned by the handle, one grow-only block per stream a caller launches on.  Nothing is taken from (and no
@@ -1170,7 +1108,7 @@ static rk_plan::Knobs plan_knobs() {  // (developer knobs: the product library r
 static uint32_t hash_key_limit(uint32_t log_slots) { return rk_plan::hash_key_limit(plan_knobs(), log_slots); }
 static bool hash_capable(const rk_db *db) {  // images whose tiles can go to place_hash64_kernel first
     if (rk_knob("RK_NO_HASH") || rk_knob("RK_NO_WSTREAM") || db->info.rows_bytes >= ROWS_FIT32_LIMIT) return false;
-    return rk_knob("RK_HASH_ALWAYS") || db->wp.stream;
+    return rk_knob("RK_HASH_ALWAYS") || db->shape.wp.stream;
 }
 // the plan's inputs for reads of this shape on this image (the launch's own: verdict, first_ok, marked_list, left false)
 static rk_plan::In plan_in(const rk_db *db, const rk_plan::ReadShape &rs, uint32_t words_per_read) {
@@ -1181,13 +1119,13 @@ static rk_plan::In plan_in(const rk_db *db, const rk_plan::ReadShape &rs, uint32
     in.hash_capable = hash_capable(db);
     in.words_per_read = words_per_read;
     in.one_batch = rs.one_batch;
-    in.stream = db->wp.stream;
+    in.stream = db->shape.wp.stream;
     in.knobs = plan_knobs();
     return in;
 }
 
 static int launch_windowed(const rk_db *db, PlaceArgs a, hipStream_t stream) {
-    const WindowPlan &wp = db->wp;
+    const WindowPlan &wp = db->shape.wp;
     const uint64_t n_tiles = (a.n_reads + 3) / 4;
     if (!n_tiles) return RK_OK;
     // (the reads of this batch may be longer than the 150 symbols the image was judged for: rk_plan::read_shape)
@@ -1264,8 +1202,8 @@ static int launch_place(const rk_db *db, const Geometry &g, PlaceArgs a, hipStre
 }
 
 static int check_launchable(const rk_db *db) {
-    if (db->windowed) return RK_OK;  // (the windowed and the ambiguity kernel hold windows of any tree; a forced dense geometry is checked at launch)
-    if (db->indexed) {
+    if (db->shape.windowed) return RK_OK;  // (the windowed and the ambiguity kernel hold windows of any tree; a forced dense geometry is checked at launch)
+    if (db->shape.indexed) {
         WgGeometry wg;
         return db_wg_geometry(db, wg);
     }
@@ -1290,13 +1228,13 @@ static int launch_wg(const rk_db *db, const WgGeometry &g, PlaceArgs a, hipStrea
 template <int BITS>
 static int launch_ascii_v(const rk_db *db, PlaceArgs args, AmbArgs m, hipStream_t stream) {
     AmbGeometry g;
-    if (int rc = geometry_error(rk_geom::amb_geometry(db->info.n_branches, db->lds_per_cu, db->indexed, (size_t)ASCII_LIST_CAP * 8 + ASCII_TABLE_BYTES, geom_knobs(), g), db)) return rc;
+    if (int rc = geometry_error(rk_geom::amb_geometry(db->info.n_branches, db->lds_per_cu, db->shape.indexed, (size_t)ASCII_LIST_CAP * 8 + ASCII_TABLE_BYTES, geom_knobs(), g), db)) return rc;
     args.s_stride = g.s_stride; m.amb_chunk = g.amb_chunk; m.s_win = g.s_win;
     auto go = [&](auto kern) { return launch_grid(db->cu_count, kern, Grid{64, g.lds, g.waves_cu, (args.n_reads + 63) / 64}, stream, args, m); };
     switch (db->info.table_mode) {
-    case RK_TABLE_DIRECT: return db->indexed ? go(place_ascii_kernel<BITS, TM_COMPACT, true>) : go(place_ascii_kernel<BITS, TM_COMPACT, false>);
-    case RK_TABLE_DIRECT8: return db->indexed ? go(place_ascii_kernel<BITS, TM_DIRECT8, true>) : go(place_ascii_kernel<BITS, TM_DIRECT8, false>);
-    default: return db->indexed ? go(place_ascii_kernel<BITS, TM_HASH, true>) : go(place_ascii_kernel<BITS, TM_HASH, false>);
+    case RK_TABLE_DIRECT: return db->shape.indexed ? go(place_ascii_kernel<BITS, TM_COMPACT, true>) : go(place_ascii_kernel<BITS, TM_COMPACT, false>);
+    case RK_TABLE_DIRECT8: return db->shape.indexed ? go(place_ascii_kernel<BITS, TM_DIRECT8, true>) : go(place_ascii_kernel<BITS, TM_DIRECT8, false>);
+    default: return db->shape.indexed ? go(place_ascii_kernel<BITS, TM_HASH, true>) : go(place_ascii_kernel<BITS, TM_HASH, false>);
     }
 }
 static int launch_ascii(const rk_db *db, const PlaceArgs &a, const AmbArgs &m, hipStream_t s) {
@@ -1322,7 +1260,7 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
     Geometry g;
     char buf[800];
     auto named = [&]() { return (const_cast<rk_db *>(db)->kernel_name = buf).c_str(); };
-    if (db->indexed && db->lanes_per_read == 0) {
+    if (db->shape.indexed && db->lanes_per_read == 0) {
         WgGeometry wg;
         if (db_wg_geometry(db, wg, 7) != RK_OK) return "";
         snprintf(buf, sizeof(buf), "place_wg_kernel<BITS=%u,%s,%s,U=%d> waves/WG=%u lds/WG=%zuB rows/batch=%u WGs/CU=%u passes=%u",
@@ -1334,7 +1272,7 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
         // (for the reads of BASELINE's configs -- 150 bases / 100 residues -- and a batch large enough for the pre-pass's verdicts)
         const uint32_t syms_name = db->info.bits_per_symbol == 5 ? 100u : 150u;
         const uint32_t wpr_name = (syms_name * db->info.bits_per_symbol + 31) / 32;
-        rk_plan::ReadShape rs = rk_plan::read_shape(db->info.bits_per_symbol, db->info.k, wpr_name, false, syms_name, db->wp.units_per_code);
+        rk_plan::ReadShape rs = rk_plan::read_shape(db->info.bits_per_symbol, db->info.k, wpr_name, false, syms_name, db->shape.wp.units_per_code);
         rs.one_batch = true;  // (reads of these lengths in records of their own length: the probe batch is the record's)
         rk_plan::In in = plan_in(db, rs, wpr_name);
         in.verdict = true;
@@ -1350,13 +1288,13 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
             const uint32_t ls = shown == F_HASH_SMALL ? RK_HASH_LOG_SLOTS - 1 : RK_HASH_LOG_SLOTS;
             const WaveGeometry hw = rk_geom::hash_geometry(ls, hash_key_limit(ls), db->lds_per_cu, geom_knobs());
             snprintf(buf, sizeof(buf), "place_hash64_kernel<BITS=%u,U=%d,NPL=%d,PU=%d,LOGS=%u> %u slots, <= %u keys a read%s (+ place_packed16w_kernel for the tiles it hands over; windows=%u x %u branches)",
-                     db->info.bits_per_symbol, RK_HRING, RK_HNPL, db->info.bits_per_symbol == 5 ? 2 : 3, ls, hw.s_stride, hw.work_cap, other, db->wp.n_win, db->wp.W);
+                     db->info.bits_per_symbol, RK_HRING, RK_HNPL, db->info.bits_per_symbol == 5 ? 2 : 3, ls, hw.s_stride, hw.work_cap, other, db->shape.wp.n_win, db->shape.wp.W);
         } else if (pl.for_uniform == F_SORTED) {
             snprintf(buf, sizeof(buf), "place_packed16s_kernel<BITS=%u,U=8,PU=%d,WIDE=%d> windows=%u x %u branches%s (+ place_packed16w_kernel for the tiles it hands over)",
-                     db->info.bits_per_symbol, db->info.bits_per_symbol == 5 ? 7 : 9, rk_geom::sorted_wide(db->wp) ? 1 : 0, db->wp.n_win, db->wp.W, other);
+                     db->info.bits_per_symbol, db->info.bits_per_symbol == 5 ? 7 : 9, rk_geom::sorted_wide(db->shape.wp) ? 1 : 0, db->shape.wp.n_win, db->shape.wp.W, other);
         } else {  // (the image's plan: a launch re-balances its two lists, rk_geom::windowed_geometry)
             snprintf(buf, sizeof(buf), "place_packed16w_kernel<BITS=%u,U=%d,PU=9> windows=%u x %u branches lds/wave=%zuB main=%u work=%u", db->info.bits_per_symbol, RK_WRING,
-                     db->wp.n_win, db->wp.W, rk_geom::lds_of_four_reads(db->wp.s_stride, db->wp.main_cap, db->wp.work_cap), db->wp.main_cap, db->wp.work_cap);
+                     db->shape.wp.n_win, db->shape.wp.W, rk_geom::lds_of_four_reads(db->shape.wp.s_stride, db->shape.wp.main_cap, db->shape.wp.work_cap), db->shape.wp.main_cap, db->shape.wp.work_cap);
         }
         return named();
     }
@@ -1368,7 +1306,7 @@ extern "C" const char *rk_kernel_name(const rk_db *db) {
     const bool pipe = use_pipelined16(db, g, probe);
     // (U: the ring the geometry counts with, RK_RING; the ROW24 instances run their own, RK_RING_DENSE, on the same list)
     snprintf(buf, sizeof(buf), "%s<G=%u,BITS=%u,%s,%s%s,U=%d,PU=%u> lds/wave=%zuB cap=%u waves/CU<=%u (LDS; registers may allow fewer)%s",
-             pipe ? "place_packed16_kernel" : "place_packed_kernel", g.G, db->info.bits_per_symbol, db->info.table_mode == RK_TABLE_DIRECT ? (db->compact_nib ? "DIRECT4" : "DIRECT") : (db->info.table_mode == RK_TABLE_DIRECT8 ? "DIRECT8" : "HASH"),
+             pipe ? "place_packed16_kernel" : "place_packed_kernel", g.G, db->info.bits_per_symbol, db->info.table_mode == RK_TABLE_DIRECT ? (db->shape.nib ? "DIRECT4" : "DIRECT") : (db->info.table_mode == RK_TABLE_DIRECT8 ? "DIRECT8" : "HASH"),
              pipe && db->d_dense_rows ? "ROW24," : "", db->info.rows_bytes < ROWS_FIT32_LIMIT ? "ITEM32" : "ITEM64", g.G == 64 ? RK_RING64 : RK_RING, g.pu, g.lds_per_wave, g.list_cap, g.waves_per_cu,
              pipe && db->d_dense_rows && db->view.winspec ? "; batches of 32 768 reads or more that the device judges clade-shaped: 16-entry units" : "");
     return named();
@@ -1412,7 +1350,7 @@ extern "C" int rk_place_packed_device(rk_db *db, const rk_params *p, uint64_t n_
     if (!result_complete(d_out)) return fail(RK_ERR_INVALID, "rk_place_packed_device: null result array");
     rc = check_fixed_len("rk_place_packed_device", d_lens, fixed_len, db->info.bits_per_symbol, words_per_read);
     if (rc) return rc;
-    const bool use_wg = db->indexed && db->lanes_per_read == 0;  // an explicit lanes_per_read forces the single-wave kernel
+    const bool use_wg = db->shape.indexed && db->lanes_per_read == 0;  // an explicit lanes_per_read forces the single-wave kernel
     const bool use_win = !use_wg && use_windowed(db, p->keep_at_most, words_per_read);
     Geometry g{};
     WgGeometry wg{};
@@ -1784,7 +1722,7 @@ extern "C" int rk_pack_reads_host(const rk_db *db, uint64_t n_reads, const uint8
     if (n_reads && !seq_ascii && seq_off[n_reads]) return fail(RK_ERR_INVALID, "rk_pack_reads_host: null reads");
     RK_GUARD_BEGIN
     Alphabet A;
-    build_alphabet(db->info.alphabet, db->convert_uo != 0, A);
+    build_alphabet(db->info.alphabet, db->shape.convert_uo != 0, A);
     return pack_reads_threads(pack_spec(A, db->info.alphabet, db->info.bits_per_symbol, db->info.k, words_per_read), n_reads, seq_ascii, seq_off,
                               packed, lens, flags, n_threads);
     RK_GUARD_END("rk_pack_reads_host")

@@ -232,7 +232,7 @@ class HostPath {
         // device as they are (no host work at all) and are packed there
         host_pack_ = translated() || (!packed_in_ && !in_pinned_);
         if (translated()) build_alphabet(RK_ALPHABET_DNA, false, alpha_), spec_ = pack_spec(alpha_, RK_ALPHABET_DNA, 2, 1, 0);
-        else if (host_pack_) build_alphabet(db->info.alphabet, db->convert_uo != 0, alpha_), spec_ = pack_spec(alpha_, db->info.alphabet, db->info.bits_per_symbol, db->info.k, 0);
+        else if (host_pack_) build_alphabet(db->info.alphabet, db->shape.convert_uo != 0, alpha_), spec_ = pack_spec(alpha_, db->info.alphabet, db->info.bits_per_symbol, db->info.k, 0);
         // host threads of this call: staging / packing on one side, result copies on the other (both only for pageable memory)
         const bool stages = host_pack_ || !in_pinned_ || stage_weights();
         n_stage_ = stages ? std::max(1u, host_threads(n_reads, 0) * 5 / 8) : 0u;

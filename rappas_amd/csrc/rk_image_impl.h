@@ -40,7 +40,7 @@ struct ImageHeader {
     uint64_t payload_hash;
     uint64_t header_hash;  // of every byte above
 };
-static_assert(sizeof(ImageHeader) <= RK_IMAGE_ALIGN, "header fits its page");
+static_assert(sizeof(ImageHeader) == 192, "the layout of version 1 files: a change here needs a new RK_IMAGE_VERSION");
 
 inline uint64_t align_up(uint64_t v) { return (v + RK_IMAGE_ALIGN - 1) & ~(uint64_t)(RK_IMAGE_ALIGN - 1); }
 
@@ -151,15 +151,35 @@ int write_image(const char *path, ImageHeader h, const Section (&sec)[4], int de
     return RK_OK;
 }
 
-void header_common(ImageHeader &h, uint32_t alphabet, uint32_t convert_uo, uint32_t k, uint32_t n_branches, float thr_log10, float thr) {
+// The header of an image of shape `s` (the two checksums are write_image's) and the shape a checked header describes: the only
+// places the two forms meet.  A shape's plan is all zero unless the image is windowed, and so are the header's plan fields.
+ImageHeader header_of(const ImageShape &s, uint64_t user_bytes) {
+    ImageHeader h;
     memset(&h, 0, sizeof(h));
     h.magic = RK_IMAGE_MAGIC; h.version = RK_IMAGE_VERSION; h.header_bytes = (uint32_t)sizeof(ImageHeader); h.endian_tag = 0x01020304u;
     h.engine_version = RK_VERSION;
-    h.alphabet = alphabet; h.convert_uo = convert_uo; h.k = k; h.n_branches = n_branches; h.thr_log10 = thr_log10; h.thr = thr;
+    h.alphabet = s.alphabet; h.convert_uo = s.convert_uo; h.k = s.k; h.n_branches = s.n_branches; h.thr_log10 = s.thr_log10; h.thr = s.thr;
+    h.table_mode = s.mode; h.bits_per_symbol = s.bits; h.max_row_len = s.max_len;
+    h.indexed = s.indexed; h.mono = s.mono; h.compact_nib = s.nib; h.windowed = s.windowed; h.has_pos = s.has_pos;
+    h.n_keys = s.n_keys; h.n_entries = s.n_entries; h.table_slots = s.slots; h.hash_mask = s.hash_mask;
+    h.wp_W = s.wp.W; h.wp_n_win = s.wp.n_win; h.wp_s_stride = s.wp.s_stride; h.wp_main_cap = s.wp.main_cap; h.wp_work_cap = s.wp.work_cap;
+    h.wp_stream = s.wp.stream ? 1u : 0u; h.wp_units_per_code = s.wp.units_per_code;
+    h.table_bytes = s.table_bytes; h.rows_bytes = s.rows_bytes; h.winspec_bytes = s.winspec_bytes; h.user_bytes = user_bytes;
+    return h;
 }
-void header_plan(ImageHeader &h, const WindowPlan &wp) {
-    h.wp_W = wp.W; h.wp_n_win = wp.n_win; h.wp_s_stride = wp.s_stride; h.wp_main_cap = wp.main_cap; h.wp_work_cap = wp.work_cap;
-    h.wp_stream = wp.stream ? 1u : 0u; h.wp_units_per_code = wp.units_per_code;
+ImageShape shape_of(const ImageHeader &h) {
+    ImageShape s;
+    s.alphabet = h.alphabet; s.convert_uo = h.convert_uo; s.k = h.k; s.n_branches = h.n_branches; s.thr_log10 = h.thr_log10; s.thr = h.thr;
+    s.mode = h.table_mode; s.bits = h.bits_per_symbol; s.max_len = h.max_row_len;
+    s.indexed = h.indexed != 0; s.mono = h.mono != 0; s.nib = h.compact_nib != 0; s.windowed = h.windowed != 0; s.has_pos = h.has_pos != 0;
+    s.n_keys = h.n_keys; s.n_entries = h.n_entries; s.slots = h.table_slots; s.hash_mask = h.hash_mask;
+    if (s.windowed) {
+        s.wp.W = h.wp_W; s.wp.n_win = h.wp_n_win; s.wp.s_stride = h.wp_s_stride; s.wp.main_cap = h.wp_main_cap; s.wp.work_cap = h.wp_work_cap;
+        s.wp.stream = h.wp_stream != 0; s.wp.units_per_code = h.wp_units_per_code;
+    }
+    s.table_bytes = h.table_bytes; s.rows_bytes = h.rows_bytes;
+    s.winspec_bytes = (s.windowed || s.has_pos) ? h.winspec_bytes : 0;
+    return s;
 }
 
 // A mapped image file whose header, size and (optionally) payload checksum have been checked.
@@ -232,28 +252,13 @@ struct MappedImage {
     }
 };
 
-void info_from_header(const ImageHeader &h, rk_db_info *info, int device) {
-    memset(info, 0, sizeof(*info));
-    info->alphabet = h.alphabet; info->k = h.k; info->n_branches = h.n_branches; info->table_mode = h.table_mode;
-    info->thr_log10 = h.thr_log10; info->thr = h.thr; info->n_keys = h.n_keys; info->n_entries = h.n_entries;
-    info->table_slots = h.table_slots; info->table_bytes = h.table_bytes; info->rows_bytes = h.rows_bytes;
-    info->bits_per_symbol = h.bits_per_symbol; info->max_row_len = h.max_row_len; info->device = device;
-}
 }  // namespace
 
 extern "C" int rk_db_save(const rk_db *db, const char *path, const void *user, uint64_t user_bytes) {
     RK_GUARD_BEGIN
     if (!db) return fail(RK_ERR_INVALID, "rk_db_save: null handle");
     if (user_bytes && !user) return fail(RK_ERR_INVALID, "rk_db_save: user_bytes without a user blob");
-    ImageHeader h;
-    header_common(h, db->info.alphabet, db->convert_uo, db->info.k, db->info.n_branches, db->info.thr_log10, db->info.thr);
-    h.table_mode = db->info.table_mode; h.bits_per_symbol = db->info.bits_per_symbol; h.max_row_len = db->info.max_row_len;
-    h.indexed = db->indexed; h.mono = db->view.mono; h.compact_nib = db->compact_nib; h.windowed = db->windowed; h.has_pos = db->has_pos;
-    h.n_keys = db->info.n_keys; h.n_entries = db->info.n_entries; h.table_slots = db->info.table_slots; h.hash_mask = db->view.hash_mask;
-    header_plan(h, db->wp);
-    uint64_t space = 0;
-    if (db->windowed || db->has_pos) (void)ipow_fits(db->info.alphabet, db->info.k, 1ull << 40, space);
-    h.table_bytes = db->info.table_bytes; h.rows_bytes = db->info.rows_bytes; h.winspec_bytes = space; h.user_bytes = user_bytes;
+    const ImageHeader h = header_of(db->shape, user_bytes);
     Section sec[4];
     sec[0].dev = db->d_table; sec[0].bytes = h.table_bytes;
     sec[1].dev = db->d_rows; sec[1].bytes = h.rows_bytes;
@@ -276,14 +281,7 @@ extern "C" int rk_db_save_desc(const rk_db_desc *d, const char *path, const void
     if (user_bytes && !user) return fail(RK_ERR_INVALID, "rk_db_save_desc: user_bytes without a user blob");
     DbImage img;
     if (int rc = build_image(d, img)) return rc;
-    ImageHeader h;
-    header_common(h, d->alphabet, d->convert_uo, d->k, d->n_branches, d->thr_log10, d->thr);
-    h.table_mode = img.mode; h.bits_per_symbol = img.bits; h.max_row_len = img.max_len;
-    h.indexed = img.indexed; h.mono = img.mono; h.compact_nib = img.nib; h.windowed = img.windowed; h.has_pos = img.has_pos;
-    h.n_keys = img.n_keys; h.n_entries = img.n_entries; h.table_slots = img.slots; h.hash_mask = img.hash_mask;
-    if (img.windowed) header_plan(h, img.wp);
-    h.table_bytes = img.table.size() * sizeof(uint64_t); h.rows_bytes = img.blob_bytes;
-    h.winspec_bytes = (img.windowed || img.has_pos) ? img.winspec.size() : 0; h.user_bytes = user_bytes;
+    const ImageHeader h = header_of(img.shape, user_bytes);
     Section sec[4];
     sec[0].host = h.table_bytes ? (const void *)img.table.data() : (const void *)""; sec[0].bytes = h.table_bytes;
     sec[1].host = img.blob.data(); sec[1].bytes = h.rows_bytes;
@@ -297,7 +295,7 @@ extern "C" int rk_db_image_info(const char *path, rk_db_info *info, uint64_t *us
     RK_GUARD_BEGIN
     MappedImage m;
     if (int rc = m.open_file(path, true, "rk_db_image_info")) return rc;
-    if (info) info_from_header(m.h, info, -1);
+    if (info) info_of(shape_of(m.h), -1, info);
     if (user_bytes) *user_bytes = m.h.user_bytes;
     return RK_OK;
     RK_GUARD_END("rk_db_image_info")
@@ -320,49 +318,12 @@ extern "C" int rk_db_load(const char *path, int32_t device, rk_db **out) {
     *out = nullptr;
     MappedImage m;
     if (int rc = m.open_file(path, true, "rk_db_load")) return rc;  // size, header and payload checksums before the device is looked at
-    const ImageHeader &h = m.h;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    struct Restore { int p; ~Restore() { (void)hipSetDevice(p); } } restore{prev};
-    DbMeta meta{h.alphabet, h.convert_uo, h.k, h.n_branches, h.thr_log10, h.thr};
-    rk_db *db = nullptr;
-    if (int rc = open_db(meta, device, &db)) return rc;
-#define LD_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            int c_ = fail(e_ == hipErrorOutOfMemory ? RK_ERR_NOMEM : RK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rk_db_destroy(db);                                                                    \
-            return c_;                                                                            \
-        }                                                                                         \
-    } while (0)
-    auto upload = [&](void *dst, uint64_t off, uint64_t bytes) -> hipError_t {  // in parts: the runtime stages pageable memory itself
-        const uint64_t part = 1ull << 30;
-        for (uint64_t o = 0; o < bytes; o += part) {
-            const hipError_t e = hipMemcpy((unsigned char *)dst + o, m.base + off + o, (size_t)std::min(part, bytes - o), hipMemcpyHostToDevice);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    };
-    LD_TRY(hipMalloc(&db->d_table, h.table_bytes ? h.table_bytes : 8));
-    LD_TRY(hipMalloc(&db->d_rows, h.rows_bytes));
-    LD_TRY(upload(db->d_table, m.off_table, h.table_bytes));
-    LD_TRY(upload(db->d_rows, m.off_rows, h.rows_bytes));
-    if (h.windowed || h.has_pos) {
-        LD_TRY(hipMalloc((void **)&db->d_winspec, h.winspec_bytes));
-        LD_TRY(upload(db->d_winspec, m.off_winspec, h.winspec_bytes));
-        db->windowed = h.windowed != 0;
-        db->has_pos = h.has_pos != 0;
-        if (h.windowed) {
-            db->wp.W = h.wp_W; db->wp.n_win = h.wp_n_win; db->wp.s_stride = h.wp_s_stride; db->wp.main_cap = h.wp_main_cap; db->wp.work_cap = h.wp_work_cap;
-            db->wp.stream = h.wp_stream != 0; db->wp.units_per_code = h.wp_units_per_code;
-        }
-    }
-#undef LD_TRY
-    db->compact_nib = h.compact_nib != 0;
-    finish_db(db, meta, h.table_mode, h.indexed != 0, h.mono != 0, h.n_keys, h.n_entries, h.table_slots, h.hash_mask, h.table_bytes, h.rows_bytes, h.max_row_len);
-    if (int rc = check_launchable(db)) { rk_db_destroy(db); return rc; }
-    *out = db;
-    return RK_OK;
+    const uint64_t off[3] = {m.off_table, m.off_rows, m.off_winspec};
+    return install(shape_of(m.h), device, [&](const rk_db &, int sec, void *dst, uint64_t bytes) -> int {
+        const uint64_t part = 1ull << 30;  // in parts: the runtime stages pageable memory itself
+        for (uint64_t o = 0; o < bytes; o += part)
+            HIP_TRY(hipMemcpy((unsigned char *)dst + o, m.base + off[sec] + o, (size_t)std::min(part, bytes - o), hipMemcpyHostToDevice));
+        return RK_OK;
+    }, out);
     RK_GUARD_END("rk_db_load")
 }

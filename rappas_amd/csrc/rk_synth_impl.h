@@ -229,9 +229,12 @@ extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
     }
     const uint64_t blob_bytes = blob_units * unit_bytes;
     if ((blob_bytes >> 3) >= (1ull << 40)) return fail(RK_ERR_UNSUPPORTED, "rk_db_create_synth: row blob exceeds 8 TiB");
+    ImageShape shape;
+    shape.alphabet = d->alphabet; shape.convert_uo = d->convert_uo; shape.k = d->k; shape.n_branches = d->n_branches;
+    shape.thr_log10 = d->thr_log10; shape.thr = d->thr;
+    shape.bits = sym_bits; shape.max_len = max_len; shape.indexed = indexed; shape.mono = d->thr_log10 <= 0.0f;
+    shape.n_keys = n_keys; shape.n_entries = n_entries;
     std::vector<uint64_t> table;
-    uint64_t slots = 0, hash_mask = 0;
-    bool nib = false;
     {
         const uint32_t alphabet = d->alphabet, k = d->k;
         auto code_of = [&](uint64_t i) -> uint64_t {
@@ -241,66 +244,44 @@ extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
             return code;
         };
         int rc = build_table(mode, space, n_keys, indexed, max_units, blob_units, [&](uint64_t i) { return dense[i]; },
-                             [&](uint64_t i) { return desc[i]; }, code_of, table, slots, hash_mask, nib);
+                             [&](uint64_t i) { return desc[i]; }, code_of, table, shape.slots, shape.hash_mask, shape.nib);
         if (rc) return rc;
     }
+    shape.mode = mode;
+    shape.table_bytes = table.size() * sizeof(uint64_t);
+    shape.rows_bytes = blob_bytes;
+    // windowed under rk_db_create's conditions; a generated image carries no position keys
+    shape.windowed = want_windows && kind.windowable && mode == RK_TABLE_DIRECT && blob_bytes < RK_WINDOW_MAX_BLOB;
+    if (shape.windowed) { shape.wp = wp; shape.winspec_bytes = winspec.size(); }
 
-    // ---- device: table upload, fill kernel ----
-    rk_db *db = nullptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    struct Restore { int p; ~Restore() { (void)hipSetDevice(p); } } restore{prev};
-    DbMeta meta{d->alphabet, d->convert_uo, d->k, d->n_branches, d->thr_log10, d->thr};
-    int rc = open_db(meta, d->device, &db);
-    if (rc) return rc;
-    DevBufS d_dense, d_desc, d_surv;
-#define SY_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            int c_ = fail(e_ == hipErrorOutOfMemory ? RK_ERR_NOMEM : RK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-            rk_db_destroy(db);                                                                    \
-            return c_;                                                                            \
-        }                                                                                         \
-    } while (0)
-    const size_t table_bytes = table.size() * sizeof(uint64_t);
-    SY_TRY(hipMalloc(&db->d_table, table_bytes ? table_bytes : 8));
-    SY_TRY(hipMalloc(&db->d_rows, blob_bytes));
-    if (table_bytes) SY_TRY(hipMemcpy(db->d_table, table.data(), table_bytes, hipMemcpyHostToDevice));
-    SY_TRY(hipMemset(db->d_rows, indexed ? 0xFF : 0, unit_bytes));  // unit 0: the reserved "skip" / scratch pattern
-    if (want_windows && kind.windowable && mode == RK_TABLE_DIRECT && blob_bytes < RK_WINDOW_MAX_BLOB) {
-        SY_TRY(hipMalloc((void **)&db->d_winspec, winspec.size()));
-        SY_TRY(hipMemcpy(db->d_winspec, winspec.data(), winspec.size(), hipMemcpyHostToDevice));
-        db->windowed = true;
-        db->wp = wp;
-    }
-    if (n_keys) {
-        SY_TRY(hipMalloc(&d_dense.p, n_keys * 8));
-        SY_TRY(hipMalloc(&d_desc.p, n_keys * 8));
-        SY_TRY(hipMalloc(&d_surv.p, surv.size() * 8));
-        SY_TRY(hipMemcpy(d_dense.p, dense.data(), n_keys * 8, hipMemcpyHostToDevice));
-        SY_TRY(hipMemcpy(d_desc.p, desc.data(), n_keys * 8, hipMemcpyHostToDevice));
-        SY_TRY(hipMemcpy(d_surv.p, surv.data(), surv.size() * 8, hipMemcpyHostToDevice));
+    // ---- device: table and window spans uploaded, the rows filled by a kernel from the generator's tables ----
+    DevBufS d_dense, d_desc, d_surv;  // (freed after install has synchronised)
+    return install(shape, d->device, [&](const rk_db &db, int sec, void *dst, uint64_t bytes) -> int {
+        if (sec != IMG_ROWS) {
+            if (bytes) HIP_TRY(hipMemcpy(dst, sec == IMG_TABLE ? (const void *)table.data() : (const void *)winspec.data(), bytes, hipMemcpyHostToDevice));
+            return RK_OK;
+        }
+        HIP_TRY(hipMemset(dst, indexed ? 0xFF : 0, unit_bytes));  // unit 0: the reserved "skip" / scratch pattern
+        if (!n_keys) return RK_OK;
+        HIP_TRY(hipMalloc(&d_dense.p, n_keys * 8));
+        HIP_TRY(hipMalloc(&d_desc.p, n_keys * 8));
+        HIP_TRY(hipMalloc(&d_surv.p, surv.size() * 8));
+        HIP_TRY(hipMemcpy(d_dense.p, dense.data(), n_keys * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_desc.p, desc.data(), n_keys * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_surv.p, surv.data(), surv.size() * 8, hipMemcpyHostToDevice));
         SynthParams dsp = sp;
         dsp.surv = (const u64 *)d_surv.p;
-        uint64_t blocks = (uint64_t)db->cu_count * 16;
+        uint64_t blocks = (uint64_t)db.cu_count * 16;
         if (blocks > n_keys) blocks = n_keys;
         if (indexed)
             hipLaunchKernelGGL(synth_fill_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, 0, dsp, (u64)n_keys, (const u64 *)d_dense.p,
-                               (const u64 *)d_desc.p, (unsigned char *)db->d_rows);
+                               (const u64 *)d_desc.p, (unsigned char *)dst);
         else
             hipLaunchKernelGGL(synth_fill_kernel<false>, dim3((unsigned)blocks), dim3(64), 0, 0, dsp, (u64)n_keys, (const u64 *)d_dense.p,
-                               (const u64 *)d_desc.p, (unsigned char *)db->d_rows);
-        SY_TRY(hipGetLastError());
-        SY_TRY(hipDeviceSynchronize());
-    }
-#undef SY_TRY
-    db->compact_nib = nib;
-    finish_db(db, meta, mode, indexed, /*mono=*/d->thr_log10 <= 0.0f, n_keys, n_entries, slots, hash_mask, table_bytes, blob_bytes, max_len);
-    rc = check_launchable(db);
-    if (rc) { rk_db_destroy(db); return rc; }
-    *out = db;
-    return RK_OK;
+                               (const u64 *)d_desc.p, (unsigned char *)dst);
+        HIP_TRY(hipGetLastError());
+        return RK_OK;
+    }, out);
     RK_GUARD_END("rk_db_create_synth")
 }
 

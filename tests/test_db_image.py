@@ -86,19 +86,40 @@ def test_damaged_images_are_refused(tmp_path):
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 def test_saved_and_loaded_database_is_the_same_database(shape, tmp_path):
     """rk_db_save of a handle -> rk_db_load: same info and kernel, every row read back through rk_db_fetch_row equal, placements
-    bit for bit those of the original handle (and the oracle's); the file equals the one rk_db_save_desc writes without a device"""
+    bit for bit those of the original handle (and the oracle's); the file equals the one rk_db_save_desc writes without a device.
+    The file pins everything an image is (mono, nibble form, position keys, hash mask, window plan, section sizes): the loaded
+    handle, a clone of the original and a clone of the loaded handle each save to the same bytes"""
     from oracle import oracle as O
     from tests.util import compare_with_oracle
     alphabet, k, nb, nk, ne, mode = SHAPES[shape]
     sdb = synth.make_db(alphabet, k, nb, nk, ne, seed=11)
     db = ra.PhyloKmerDB.from_synth(sdb, table_mode=mode)
     path = str(tmp_path / "db.rkimg")
+
+    def saves_the_same_file(handle, tag):
+        handle.save(path + tag, user=b"newick;")
+        assert open(path + tag, "rb").read() == first, tag
+
+    def same_database(a, b):
+        for f in ("alphabet", "k", "n_branches", "table_mode", "thr_log10", "thr", "n_keys", "n_entries", "table_slots", "table_bytes",
+                  "rows_bytes", "bits_per_symbol", "max_row_len", "device"):
+            assert getattr(a.info, f) == getattr(b.info, f), f
+        assert a.kernel_name() == b.kernel_name()
+
     try:
         db.save(path, user=b"newick;")
+        first = open(path, "rb").read()
         _save(sdb, path + ".host", mode, user=b"newick;")
-        assert open(path, "rb").read() == open(path + ".host", "rb").read()
+        assert first == open(path + ".host", "rb").read()
+        c0 = db.clone()
+        try:
+            same_database(db, c0)
+            saves_the_same_file(c0, ".clone")
+        finally:
+            c0.close()
         db2 = ra.PhyloKmerDB.load(path)
         try:
+            saves_the_same_file(db2, ".loaded")
             for f in ("alphabet", "k", "n_branches", "table_mode", "n_keys", "n_entries", "table_slots", "table_bytes", "rows_bytes", "max_row_len"):
                 assert getattr(db.info, f) == getattr(db2.info, f), f
             assert db.kernel_name() == db2.kernel_name()
@@ -121,6 +142,8 @@ def test_saved_and_loaded_database_is_the_same_database(shape, tmp_path):
             compare_with_oracle(b, odb.place(seq, off), odb, seq, off)
             c = db2.clone()   # a loaded handle clones like any other
             try:
+                same_database(db2, c)
+                saves_the_same_file(c, ".loaded.clone")
                 cc = ra.PlacementProcess(c).processQueries(seq, off)
                 assert np.array_equal(cc.branch, b.branch)
             finally:

@@ -93,6 +93,44 @@ def test_generated_image_equals_rk_db_create_of_the_same_rows():
         b.close()
 
 
+@pytest.mark.parametrize("shape", ["small_tree", "large_tree", "large_tree_indexed", "protein", "windowed"])
+def test_generated_image_survives_save_load_and_clone(shape, tmp_path):
+    """a generated handle, the handle loaded from its file and a clone all save to the same bytes (the header pins everything the
+    image is, the sections every byte the generator wrote), and the loaded handle and the clone hold the host twin's rows.
+    (The large tree is a windowed image behind the compact table, which is what AUTO resolves to at k = 7, and the indexed
+    large-tree image behind 8-byte descriptors: both are here.)"""
+    large = small_spec(n_branches=19_999, mean=300.0, k=7)
+    spec, table, kind = {"small_tree": (small_spec(), ra.RK_TABLE_AUTO, "dense"),
+                         "large_tree": (large, ra.RK_TABLE_AUTO, "windowed"), "large_tree_indexed": (large, ra.RK_TABLE_DIRECT8, "indexed"),
+                         "protein": (small_spec(alphabet=20, k=3, n_branches=399, mean=9.0, kf=0.4), ra.RK_TABLE_AUTO, "dense"),
+                         "windowed": (small_spec(n_branches=7_999), ra.RK_TABLE_AUTO, "windowed")}[shape]
+    path = str(tmp_path / "synth.rkimg")
+    rng = np.random.default_rng(3)
+    dense = np.unique(np.concatenate([rng.integers(0, spec.space, 60), [0, spec.space - 1]])).astype(np.uint64)
+    db = ra.PhyloKmerDB.synthetic(spec, table_mode=table)
+    try:
+        name = db.kernel_name()
+        assert ("windows=" in name, "place_wg_kernel" in name) == (kind == "windowed", kind == "indexed"), name
+        db.save(path, user=b"tree")
+        first = open(path, "rb").read()
+        clone = db.clone()
+        try:
+            clone.save(path + ".clone", user=b"tree")
+            assert open(path + ".clone", "rb").read() == first
+            check_rows(clone, spec, dense)
+        finally:
+            clone.close()
+        loaded = ra.PhyloKmerDB.load(path)
+        try:
+            loaded.save(path + ".loaded", user=b"tree")
+            assert open(path + ".loaded", "rb").read() == first
+            check_rows(loaded, spec, dense)
+        finally:
+            loaded.close()
+    finally:
+        db.close()
+
+
 def test_argument_errors():
     import ctypes as C
     from rappas_amd import _lib
