@@ -23,6 +23,15 @@ struct __attribute__((aligned(8))) Entry {
     u32 branch;
     float score;
 };
+// How a row's entries are written, for whoever fills an image (the host fill of build_image, synth_fill_kernel): the slot offset of a
+// branch, the padding entry of the slot-offset form -- it updates the scratch word -- and of the large-tree form -- raw id 0xFFFF, which
+// the kernels skip --, and the branch bound of split i = 1..32 of a large-tree row's index line (entries below it belong to the ranges
+// before i).
+__host__ __device__ __forceinline__ u32 slot_offset(u32 branch) { return (branch + 1u) * 4u; }
+__host__ __device__ __forceinline__ Entry slot_padding() { return Entry{0u, 0.0f}; }
+constexpr unsigned short RAW_PAD_BRANCH = 0xFFFFu;
+constexpr float RAW_PAD_SCORE = 0.0f;
+__host__ __device__ __forceinline__ u32 index_bound(u32 i, u32 n_branches) { return (u32)(((u64)i * n_branches) / 32); }
 #ifndef RK_FIT32_LIMIT
 #define RK_FIT32_LIMIT 0xFFFF0000u  // (developer builds lower it to time the 64-bit-offset kernels on small databases)
 #endif

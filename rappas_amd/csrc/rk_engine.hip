@@ -7,6 +7,7 @@
 #include "rk_translate_host.h"
 #include "rk_plan.h"
 #include "rk_geometry.h"
+#include "rk_image_plan.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -204,21 +205,11 @@ static rk_geom::Knobs geom_knobs() {  // (developer knobs, read where the geomet
             rk_knob("RK_WINDOW_ALWAYS") != nullptr, rk_knob("RK_WSTREAM_ALWAYS") != nullptr};
 }
 
-// What an image is, apart from its bytes.  Every producer makes one (build_image, the synthetic builder, shape_of(ImageHeader), a
-// handle keeps the one it was installed with) and every consumer reads one (info_of, header_of, install).
-struct ImageShape {
-    uint32_t alphabet = 0, convert_uo = 0, k = 0, n_branches = 0;  // the scalars every database carries, whatever built its image
-    float thr_log10 = 0.0f, thr = 0.0f;
-    uint32_t mode = 0, bits = 0, max_len = 0;  // table mode (never AUTO), bits per symbol, longest row
-    bool indexed = false;   // rows carry an index line (large trees, place_wg_kernel)
-    bool mono = true;       // every score >= thr_log10 (true of every database RAPPAS builds: words below the threshold are not stored)
-    bool nib = false;       // the compact table holds 4-bit unit counts
-    bool windowed = false;  // place_packed16w_kernel can serve this image: the third section holds a window span per k-mer code
-    bool has_pos = false;   // not windowed, but the third section holds the rows' position in the tree (64 ranges): the key reads are grouped by
-    uint64_t n_keys = 0, n_entries = 0, slots = 0, hash_mask = 0;
-    WindowPlan wp;          // all zero unless windowed
-    uint64_t table_bytes = 0, rows_bytes = 0, winspec_bytes = 0;  // the three sections; winspec_bytes = sigma^k when windowed || has_pos, else 0
-};
+using rk_image::ImageShape;  // (rk_image_plan.h: what an image is, apart from its bytes)
+using rk_image::ipow_fits;
+static_assert(rk_image::ROW_ENTRIES == ROW_UNIT && rk_image::DESC_LEN_BITS == DESC_LEN_BITS && rk_image::COMPACT_KMERS == COMPACT_KMERS,
+              "rk_image_plan.h repeats these constants of the device code");
+static rk_image::Knobs image_knobs() { return {rk_knob("RK_COMPACT_BYTES") != nullptr, rk_knob("RK_COMPACT_NIBBLES") != nullptr}; }  // (developer knobs, as geom_knobs)
 
 static void info_of(const ImageShape &s, int device, rk_db_info *info) {
     memset(info, 0, sizeof(*info));
@@ -257,21 +248,6 @@ struct rk_db {
     mutable std::vector<LaunchScratch> scratch;
     mutable uint64_t scratch_clock = 0;
 };
-
-static uint64_t host_mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return x;
-}
-
-static bool ipow_fits(uint64_t base, uint32_t e, uint64_t limit, uint64_t &out) {
-    uint64_t v = 1;
-    for (uint32_t i = 0; i < e; i++) {
-        if (v > limit / base) return false;
-        v *= base;
-    }
-    out = v;
-    return true;
-}
 
 extern "C" void rk_db_destroy(rk_db *db) {
     if (!db) return;
@@ -499,306 +475,191 @@ static int install(const ImageShape &shape, int device, Fill fill, rk_db **out) 
     return RK_OK;
 }
 
-// ---- k-mer -> row descriptor table, keys given in ascending dense-index order through the accessors ----
-// DIRECT  : compact blocks, 16 bytes per 12 consecutive k-mers {u32 first row unit, 12 x u8 units per row}: 1.33 bytes
-//           per k-mer (1.4 MiB at k=10) -- or per 24 k-mers with 4-bit unit counts (see `nib` below) -- small enough to live in the XCD L2s, one dwordx4 gather per probe; a row's
-//           offset is the block base plus a byte prefix sum.  Needs rows of <= 255 units (4080 entries) and a blob
-//           of < 2^32 units (512 GiB); otherwise DIRECT falls back to DIRECT8.
-// DIRECT8 : one 8-byte descriptor per k-mer.
-// HASH    : open addressing, linear probing, 16-byte slots {key+1, descriptor}, load <= 0.5.
-template <class FDense, class FDesc, class FCode>
-static int build_table(uint32_t &mode, uint64_t space, uint64_t n_keys, bool indexed, uint64_t max_units, uint64_t blob_units,
-                       FDense dense_of, FDesc desc_of, FCode code_of, std::vector<uint64_t> &table, uint64_t &slots, uint64_t &hash_mask,
-                       bool &nib) {
-    if (mode == RK_TABLE_DIRECT && (max_units > 255 || blob_units >= (1ull << 32) || indexed)) mode = RK_TABLE_DIRECT8;
-    slots = 0; hash_mask = 0;
-    // 4-bit unit counts (24 k-mers per block, 0.67 bytes per k-mer) whenever no row exceeds 15 units = 240 entries: half the table
-    // means its lines are re-touched twice as often and survive the rows streaming through the same L2 sets (C2: 15 of a read's 141
-    // probes missed the L2 with the byte form)
-    static const bool bytes_only = rk_knob("RK_COMPACT_BYTES") != nullptr;  // developer knob: A/B against the byte form
-    // ... where rows stream at all: with fewer than one row unit per two k-mer codes (C4: 0.13) the probes outnumber the row lines,
-    // nothing evicts the table and the longer decode is all that is left (C4: 5.37e8 against 5.52e8 reads/s)
-    static const bool nibbles_always = rk_knob("RK_COMPACT_NIBBLES") != nullptr;  // developer knob: the half-size form whatever the density
-    nib = mode == RK_TABLE_DIRECT && max_units <= 15 && (2 * blob_units >= space || nibbles_always) && !bytes_only;
-    try {
-        if (mode == RK_TABLE_DIRECT) {
-            slots = space;
-            const uint64_t per = nib ? 2 * COMPACT_KMERS : COMPACT_KMERS;
-            const uint64_t n_blocks = (space + per - 1) / per;
-            table.assign(n_blocks * 2, 0);
-            unsigned char *tb = (unsigned char *)table.data();
-            uint64_t next_unit = 1, ki = 0;
-            for (uint64_t blk = 0; blk < n_blocks; blk++) {
-                const uint32_t base32 = (uint32_t)next_unit;
-                memcpy(tb + blk * 16, &base32, 4);
-                while (ki < n_keys && dense_of(ki) / per == blk) {
-                    const uint64_t units = ((uint32_t)desc_of(ki) & DESC_LEN_MASK) / ROW_UNIT;
-                    const uint64_t j = dense_of(ki) % per;
-                    if (nib) tb[blk * 16 + 4 + j / 2] |= (unsigned char)(units << (4 * (j & 1)));
-                    else tb[blk * 16 + 4 + j] = (unsigned char)units;
-                    next_unit += units;
-                    ki++;
-                }
-            }
-        } else if (mode == RK_TABLE_DIRECT8) {
-            slots = space;
-            table.assign(slots, 0);
-            for (uint64_t i = 0; i < n_keys; i++) table[dense_of(i)] = desc_of(i);
-        } else {
-            slots = 16;
-            while (slots < 2 * n_keys) slots <<= 1;
-            hash_mask = slots - 1;
-            table.assign(slots * 2, 0);
-            for (uint64_t i = 0; i < n_keys; i++) {
-                const uint64_t code = code_of(i);
-                uint64_t h = host_mix64(code) & hash_mask;
-                while (table[2 * h]) h = (h + 1) & hash_mask;
-                table[2 * h] = code + 1;
-                table[2 * h + 1] = desc_of(i);
-            }
-        }
-    } catch (const std::bad_alloc &) {
-        return fail(RK_ERR_NOMEM, "rk_db_create: host OOM building the k-mer table");
+// ------------------------------------------------------------------------------------------------
+// the HBM image from the caller's CSR arrays (the arithmetic: rk_image_plan.h)
+// ------------------------------------------------------------------------------------------------
+// What a plan refuses, as the error codes and texts of the C ABI; `who` is the entry point's name
+static int image_error(rk_image::Status st, const char *who, uint32_t alphabet, uint32_t k, uint32_t n_branches, uint32_t table_mode) {
+    switch (st) {
+    case rk_image::IMAGE_OK: return RK_OK;
+    case rk_image::BAD_ALPHABET: return fail(RK_ERR_INVALID, "%s: alphabet must be 4 (DNA) or 20 (AA), got %u", who, alphabet);
+    case rk_image::K_OUT_OF_RANGE: return fail(RK_ERR_UNSUPPORTED, "%s: k=%u outside supported range 2..%u for this alphabet", who, k, rk_image::max_k(alphabet));
+    case rk_image::BAD_BRANCHES: return fail(RK_ERR_INVALID, "%s: n_branches=%u must be in 1..65535 (branch ids are 16-bit)", who, n_branches);
+    case rk_image::THRESHOLD_NOT_FINITE: return fail(RK_ERR_INVALID, "%s: thresholds must be finite", who);
+    case rk_image::DIRECT_TOO_LARGE: return fail(RK_ERR_UNSUPPORTED, "%s: direct table needs sigma^k <= 2^31 slots", who);
+    case rk_image::BAD_TABLE_MODE: return fail(RK_ERR_INVALID, "%s: bad table_mode %u", who, table_mode);
+    default: return fail(RK_ERR_UNSUPPORTED, "%s: row blob exceeds 8 TiB", who);
     }
-    return RK_OK;
 }
 
-// Validation + host-side construction of the HBM image (no HIP call in here: rk_db_validate runs it without a device).
+// Validation + host-side construction of the image (no HIP call in here: rk_db_validate runs it without a device): check, order keys,
+// plan layout, fill rows, table, finish.  An allocation that fails leaves through the entry point's guard (RK_ERR_NOMEM).
 struct DbImage {
     ImageShape shape;
     std::vector<uint64_t> table;
     std::vector<Entry> blob;
     std::vector<unsigned char> winspec;  // [sigma^k], or empty
 };
+using KeyOrder = std::vector<std::pair<uint64_t, uint64_t>>;  // (dense index, key number), ascending
+static const char *const CREATE = "rk_db_create";  // (rk_db_validate and rk_db_save_desc report under this name too)
 
-static int build_image(const rk_db_desc *d, DbImage &img) {
+// check: the scalars and arrays of the description, the table mode (AUTO resolved); fills the shape's scalars
+static int check_desc(const rk_db_desc *d, ImageShape &shape, rk_image::TableMode &tm) {
     if (!d) return fail(RK_ERR_INVALID, "rk_db_create: null argument");
-    if (d->alphabet != RK_ALPHABET_DNA && d->alphabet != RK_ALPHABET_AA)
-        return fail(RK_ERR_INVALID, "rk_db_create: alphabet must be 4 (DNA) or 20 (AA), got %u", d->alphabet);
-    const uint32_t bits = d->alphabet == RK_ALPHABET_DNA ? 2 : 5;
-    // DNA: 2 bits per base in a 64-bit code; from k = 16 on the reference allows two ambiguity codes per k-mer
-    // (maxAmbigPerMer = floor(k^(1/4)), AmbigSequenceKnife.java:95), three only from k = 81.  AA: 5 bits per residue.
-    const uint32_t kmax = d->alphabet == RK_ALPHABET_DNA ? 31 : 12;
-    if (d->k < 2 || d->k > kmax)
-        return fail(RK_ERR_UNSUPPORTED, "rk_db_create: k=%u outside supported range 2..%u for this alphabet", d->k, kmax);
-    if (d->n_branches < 1 || d->n_branches > 65535)
-        return fail(RK_ERR_INVALID, "rk_db_create: n_branches=%u must be in 1..65535 (branch ids are 16-bit)", d->n_branches);
-    if (!std::isfinite(d->thr_log10) || !std::isfinite(d->thr))
-        return fail(RK_ERR_INVALID, "rk_db_create: thresholds must be finite");
+    if (int rc = image_error(rk_image::check_scalars(d->alphabet, d->k, d->n_branches, d->thr_log10, d->thr), CREATE, d->alphabet, d->k, d->n_branches, d->table_mode)) return rc;
     if (d->n_keys && (!d->key_codes || !d->row_offsets)) return fail(RK_ERR_INVALID, "rk_db_create: null key arrays");
-    const uint64_t n_keys = d->n_keys;
-    const uint64_t n_entries = n_keys ? d->row_offsets[n_keys] : 0;
+    const uint64_t n_entries = d->n_keys ? d->row_offsets[d->n_keys] : 0;
     if (n_entries && (!d->branch_ids || !d->scores)) return fail(RK_ERR_INVALID, "rk_db_create: null entry arrays");
-    if (n_keys && d->row_offsets[0] != 0) return fail(RK_ERR_INVALID, "rk_db_create: row_offsets[0] must be 0");
-
-    ImageShape &shape = img.shape;
+    if (d->n_keys && d->row_offsets[0] != 0) return fail(RK_ERR_INVALID, "rk_db_create: row_offsets[0] must be 0");
     shape.alphabet = d->alphabet; shape.convert_uo = d->convert_uo; shape.k = d->k; shape.n_branches = d->n_branches;
     shape.thr_log10 = d->thr_log10; shape.thr = d->thr;
-    shape.bits = bits; shape.n_keys = n_keys; shape.n_entries = n_entries;
-    // ---- table mode ----
-    uint64_t space = 0;
-    const bool space_ok = ipow_fits(d->alphabet, d->k, 1ull << 40, space);
-    uint32_t &mode = shape.mode;
-    mode = d->table_mode;
-    if (mode == RK_TABLE_AUTO) {
-        // Direct addressing whenever all sigma^k codes fit 2^28 slots; DIRECT = compact 2-byte-per-k-mer blocks that
-        // stay in the XCD L2s (measured on C2: 2.36e8 reads/s vs 2.18e8 with 8-byte descriptors, whose probes push the
-        // Infinity Fabric to its ~6e10 requests/s ceiling -- scripts/ubench/gather_rate.hip).
-        mode = (space_ok && space <= (1ull << 28)) ? RK_TABLE_DIRECT : RK_TABLE_HASH;
-    }
-    if ((mode == RK_TABLE_DIRECT || mode == RK_TABLE_DIRECT8) && !(space_ok && space <= (1ull << 31)))
-        return fail(RK_ERR_UNSUPPORTED, "rk_db_create: direct table needs sigma^k <= 2^31 slots");
-    if (mode != RK_TABLE_DIRECT && mode != RK_TABLE_DIRECT8 && mode != RK_TABLE_HASH)
-        return fail(RK_ERR_INVALID, "rk_db_create: bad table_mode %u", mode);
+    shape.bits = rk_image::bits_of(d->alphabet); shape.n_keys = d->n_keys; shape.n_entries = n_entries;
+    tm = rk_image::resolve_table_mode(d->table_mode, d->alphabet, d->k, 1ull << 40);
+    shape.mode = tm.mode;
+    return image_error(tm.status, CREATE, d->alphabet, d->k, d->n_branches, tm.mode);
+}
 
-    // ---- validate keys; rows are laid out in dense-index order of their k-mer ----
-    auto code_ok = [&](uint64_t code, uint64_t &dense) -> bool {
-        if (bits == 2) {
-            if (d->k * 2 < 64 && (code >> (2 * d->k))) return false;
-            dense = code;
-            return true;
-        }
-        if (d->k * 5 < 64 && (code >> (5 * d->k))) return false;
-        uint64_t idx = 0, pw = 1;
-        for (uint32_t i = 0; i < d->k; i++) {
-            uint64_t dig = (code >> (5 * i)) & 31;
-            if (dig >= 20) return false;
-            idx += dig * pw;
-            pw *= 20;
-        }
-        dense = idx;
-        return true;
-    };
-    std::vector<std::pair<uint64_t, uint64_t>> order;  // (dense index, key number)
-    try { order.resize(n_keys); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create: host OOM"); }
-    for (uint64_t r = 0; r < n_keys; r++) {
+// order keys: every code a k-mer, none twice; rows are laid out in dense-index order of their k-mer
+static int order_keys(const rk_db_desc *d, uint32_t bits, KeyOrder &order) {
+    order.resize(d->n_keys);
+    for (uint64_t r = 0; r < d->n_keys; r++) {
         uint64_t dense;
-        if (!code_ok(d->key_codes[r], dense)) return fail(RK_ERR_INVALID, "rk_db_create: key %llu has an invalid k-mer code", (unsigned long long)r);
+        if (!rk_image::dense_of_code(bits, d->k, d->key_codes[r], dense)) return fail(RK_ERR_INVALID, "rk_db_create: key %llu has an invalid k-mer code", (unsigned long long)r);
         order[r] = {dense, r};
     }
     std::sort(order.begin(), order.end());
-    for (uint64_t i = 1; i < n_keys; i++)
+    for (uint64_t i = 1; i < d->n_keys; i++)
         if (order[i].first == order[i - 1].first)
             return fail(RK_ERR_INVALID, "rk_db_create: duplicate k-mer code at key %llu", (unsigned long long)order[i].second);
+    return RK_OK;
+}
 
-    // ---- row blob: every row starts on a 128-byte unit and is padded to whole units (16 entries) with zero entries,
-    //      so a row of n entries costs exactly ceil(n/16) aligned 128-byte requests; unit 0 is reserved (all padding) ----
-    // Large trees (n_branches > RK_WG_MIN_BRANCHES): the score vector of one read fills most of a CU's LDS, so a whole
-    // workgroup shares it and every wave owns a branch range (place_wg_kernel).  Rows are then sorted by branch id
-    // and preceded by one 64-byte INDEX line: u16 split[i-1] = number of entries with branch < floor(i * n_branches / 32),
-    // i = 1..32, so a wave finds its slice of a row with two 2-byte loads.  Descriptors still point at the first
-    // entry line; the other kernels never look at the index line.
-    // ... unless the rows are short: a workgroup's eight waves then each scan a sliver of every row, and one wave per read on
-    // a few resident score vectors does better (measured, rows of ~13 entries: 12 001 branches 29 vs 20 Mreads/s; the
-    // workgroup kernel is ahead again from ~16 000 branches on, where two score vectors fill a CU, and always for long rows).
-    const double mean_len = n_keys ? (double)n_entries / (double)n_keys : 0.0;
-    uint64_t slot_units = 1;
-    uint32_t longest = 0;
-    for (uint64_t r = 0; r < n_keys; r++) {
-        const uint64_t len = d->row_offsets[r + 1] - d->row_offsets[r];
-        slot_units += (len + ROW_UNIT - 1) / ROW_UNIT;
-        if (len > longest) longest = (uint32_t)(len > 0xFFFFFFFFull ? 0xFFFFFFFFull : len);
-    }
-    const ImageKind kind = rk_geom::image_kind(d->n_branches, bits, mode == RK_TABLE_DIRECT, space, slot_units, longest, mean_len, geom_knobs());  // (AUTO is resolved by now)
-    const bool indexed = kind.indexed;
-    shape.indexed = indexed;
-    std::vector<uint64_t> desc(n_keys);  // by key number
-    WindowPlan wp;
-    const bool want_windows = kind.windowable && rk_geom::window_plan(d->n_branches, bits, space ? (double)slot_units / (double)space : 0.0, mean_len / ROW_UNIT + 0.5, geom_knobs(), wp);
-    // Images the dense kernels serve get the same byte per k-mer code with the tree cut into 64 equal ranges: not for any window
-    // -- the kernels hold the whole score vector -- but as the position a batch's reads are grouped by (reads of one clade read the
-    // same rows: taken together they find them in the L2; scripts/clade_sorted_probe.py: 283 -> 406 Mreads/s on C2's shape)
-    const bool want_pos = !want_windows && !indexed && space_ok && space <= (1ull << 26);
-    const uint32_t key_w = want_windows ? wp.W : std::max<uint32_t>(1u, (d->n_branches + 63u) / 64u);
-    std::vector<unsigned char> ws_by_key;  // winspec_byte(first window, last window) of every row
-    if (want_windows || want_pos) {
-        try { ws_by_key.assign(n_keys, 0); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create: host OOM"); }
-    }
-    // slot-offset images: 128-byte units (ROW_UNIT = 16 entries), so a chunk of 16 entries is ONE aligned 128-byte request;
-    // raw-id (indexed) images: 64-byte units
-    const uint64_t unit_bytes = indexed ? 64 : ROW_UNIT * 8;
-    uint64_t blob_units = 1;  // unit 0 is reserved (padding pattern)
-    uint32_t max_len = 0;
-    uint64_t max_units = 0;
-    for (uint64_t i = 0; i < n_keys; i++) {
-        const uint64_t r = order[i].second;
-        uint64_t b = d->row_offsets[r], e = d->row_offsets[r + 1];
+// plan layout: the kind of image from the row lengths (the window plan sees the measured density, the image carries position keys),
+// then a descriptor per key number, rows in dense order
+static int plan_layout(const rk_db_desc *d, const KeyOrder &order, uint32_t bits, const rk_image::TableMode &tm, rk_image::KindPlan &kind,
+                       rk_image::RowLayout &lay, std::vector<uint64_t> &desc, uint32_t &max_len) {
+    rk_image::RowStats rs;
+    for (uint64_t r = 0; r < d->n_keys; r++) rs.add(d->row_offsets[r + 1] - d->row_offsets[r]);  // (the offsets themselves are tested below)
+    kind = rk_image::plan_kind(d->n_branches, bits, tm, rs, rk_image::measured_density(rs, tm.space), true, geom_knobs());
+    lay = rk_image::RowLayout(kind.indexed);
+    desc.resize(d->n_keys);
+    max_len = 0;
+    for (uint64_t i = 0; i < d->n_keys; i++) {
+        const uint64_t r = order[i].second, b = d->row_offsets[r], e = d->row_offsets[r + 1];
         if (e < b) return fail(RK_ERR_INVALID, "rk_db_create: row_offsets not monotone at key %llu", (unsigned long long)r);
-        uint64_t len = e - b;
+        const uint64_t len = e - b;
         if (len == 0) return fail(RK_ERR_INVALID, "rk_db_create: key %llu has an empty row", (unsigned long long)r);
         if (len > d->n_branches)
             return fail(RK_ERR_INVALID, "rk_db_create: row %llu has %llu entries (> n_branches)", (unsigned long long)r, (unsigned long long)len);
         if (len > max_len) max_len = (uint32_t)len;
-        uint64_t units = (len + ROW_UNIT - 1) / ROW_UNIT;  // 128-byte units of 16 {slot offset, score} entries
-        uint64_t lenp = units * ROW_UNIT;
-        if (indexed) {
-            // [index line][u16 branch[lenp]][f32 score[lenp]], lenp a multiple of 32 so that the row is whole lines
-            blob_units += 1;
-            lenp = (len + 31) / 32 * 32;
-            units = lenp * 6 / 64;
-        }
-        if (units > max_units) max_units = units;
-        desc[r] = ((blob_units * (unit_bytes / 8)) << DESC_LEN_BITS) | lenp;
-        blob_units += units;
+        desc[r] = lay.add_row(len);
     }
-    const uint64_t blob_bytes = blob_units * unit_bytes;
-    if ((blob_bytes >> 3) >= (1ull << 40)) return fail(RK_ERR_UNSUPPORTED, "rk_db_create: row blob exceeds 8 TiB");
-    std::vector<Entry> &blob = img.blob;
+    return image_error(lay.finish(), CREATE, d->alphabet, d->k, d->n_branches, tm.mode);
+}
+
+// fill rows, one thread's share: the rows of keys r_lo .. r_hi validated and written where their descriptors point; with_keys: their
+// winspec bytes too (windows or 64ths of the tree, key_w branches each).  Stops at the first bad row.
+struct RowErr { int kind = 0; uint64_t r = ~0ull; uint32_t x = 0; };  // 1: branch id out of range, 2: repeated in the row, 3: score not finite
+static void fill_row_range(const rk_db_desc *d, bool indexed, const std::vector<uint64_t> &desc, uint64_t r_lo, uint64_t r_hi, Entry *blob,
+                           unsigned char *ws_by_key, uint32_t key_w, RowErr &err, bool &mono) {
+    std::vector<uint32_t> stamp(d->n_branches, 0xFFFFFFFFu);
+    std::vector<Entry> tmp;
+    for (uint64_t r = r_lo; r < r_hi; r++) {
+        const uint64_t b = d->row_offsets[r], len = d->row_offsets[r + 1] - b;
+        Entry *ep = blob + (desc[r] >> DESC_LEN_BITS);
+        if (indexed) { tmp.resize(len); ep = tmp.data(); }
+        uint32_t xmin = 0xFFFFu, xmax = 0;
+        for (uint64_t i = 0; i < len; i++) {
+            const uint16_t x = d->branch_ids[b + i];
+            xmin = x < xmin ? x : xmin;
+            xmax = x > xmax ? x : xmax;
+            const float v = d->scores[b + i];
+            if (x >= d->n_branches) { err = {1, r, x}; return; }
+            if (stamp[x] == (uint32_t)r) { err = {2, r, x}; return; }
+            stamp[x] = (uint32_t)r;
+            if (!std::isfinite(v)) { err = {3, r, x}; return; }
+            if (!(v >= d->thr_log10)) mono = false;
+            ep[i].branch = indexed ? (uint32_t)x : slot_offset(x);  // raw id (sorted, SoA below) | slot byte offset
+            ep[i].score = v;
+        }
+        if (ws_by_key) ws_by_key[r] = winspec_byte(xmin / key_w, xmax / key_w);
+        if (!indexed) continue;
+        std::sort(ep, ep + len, [](const Entry &p, const Entry &q) { return p.branch < q.branch; });
+        unsigned char *row = (unsigned char *)(blob + (desc[r] >> DESC_LEN_BITS));
+        const uint64_t lenp = (uint32_t)desc[r] & DESC_LEN_MASK;
+        uint16_t *split = (uint16_t *)(row - 64);  // the 64-byte line in front of the row
+        uint16_t *bp = (uint16_t *)row;
+        float *sp = (float *)(row + 2 * lenp);
+        uint64_t e = 0;
+        for (uint32_t i = 1; i <= 32; i++) {
+            const uint32_t bound = index_bound(i, d->n_branches);
+            while (e < len && ep[e].branch < bound) e++;
+            split[i - 1] = (uint16_t)e;
+        }
+        for (uint64_t i = 0; i < lenp; i++) {
+            bp[i] = i < len ? (uint16_t)ep[i].branch : RAW_PAD_BRANCH;
+            sp[i] = i < len ? ep[i].score : RAW_PAD_SCORE;
+        }
+    }
+}
+
+// fill rows: rows are independent, so a few host threads take contiguous key ranges of (roughly) equal entry counts (6e8 entries took
+// 14 s on one); the error reported is that of the first bad row by key number
+static int fill_rows(const rk_db_desc *d, const rk_image::KindPlan &kind, const rk_image::RowLayout &lay, const std::vector<uint64_t> &desc,
+                     std::vector<Entry> &blob, std::vector<unsigned char> &ws_by_key, bool &mono) {
+    const uint64_t n_keys = d->n_keys, n_entries = n_keys ? d->row_offsets[n_keys] : 0;
     // padding / reserved line 0: raw-id images (large trees) skip on 0xFFFF, slot-offset images update scratch slot 0
-    try { blob.assign(blob_bytes / 8, indexed ? Entry{0xFFFFFFFFu, 0.0f} : Entry{0u, 0.0f}); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create: host OOM for %llu-byte row blob", (unsigned long long)blob_bytes); }
-    {
-        // validation + fill, rows are independent: a few host threads over contiguous key ranges (6e8 entries took 14 s on one)
-        struct RowErr { int kind = 0; uint64_t r = ~0ull; uint32_t x = 0; };
-        auto fill = [&](uint64_t r_lo, uint64_t r_hi, RowErr &err, bool &mono) {
-            std::vector<uint32_t> stamp(d->n_branches, 0xFFFFFFFFu);
-            std::vector<Entry> tmp;
-            for (uint64_t r = r_lo; r < r_hi; r++) {
-                uint64_t b = d->row_offsets[r], len = d->row_offsets[r + 1] - b;
-                Entry *ep = blob.data() + (desc[r] >> DESC_LEN_BITS);
-                if (indexed) { tmp.resize(len); ep = tmp.data(); }
-                uint32_t xmin = 0xFFFFu, xmax = 0;
-                for (uint64_t i = 0; i < len; i++) {
-                    uint16_t x = d->branch_ids[b + i];
-                    xmin = x < xmin ? x : xmin;
-                    xmax = x > xmax ? x : xmax;
-                    float v = d->scores[b + i];
-                    if (x >= d->n_branches) { err = {1, r, x}; return; }
-                    if (stamp[x] == (uint32_t)r) { err = {2, r, x}; return; }
-                    stamp[x] = (uint32_t)r;
-                    if (!std::isfinite(v)) { err = {3, r, x}; return; }
-                    if (!(v >= d->thr_log10)) mono = false;
-                    ep[i].branch = indexed ? (uint32_t)x : ((uint32_t)x + 1u) * 4u;  // raw id (sorted, SoA below) | slot byte offset
-                    ep[i].score = v;
-                }
-                if (want_windows || want_pos) ws_by_key[r] = winspec_byte(xmin / key_w, xmax / key_w);
-                if (indexed) {
-                    std::sort(ep, ep + len, [](const Entry &p, const Entry &q) { return p.branch < q.branch; });
-                    unsigned char *row = (unsigned char *)(blob.data() + (desc[r] >> DESC_LEN_BITS));
-                    const uint64_t lenp = (uint32_t)desc[r] & DESC_LEN_MASK;
-                    uint16_t *split = (uint16_t *)(row - 64);  // the 64-byte line in front of the row
-                    uint16_t *bp = (uint16_t *)row;
-                    float *sp = (float *)(row + 2 * lenp);
-                    uint64_t e = 0;
-                    for (uint32_t i = 1; i <= 32; i++) {
-                        const uint32_t bound = (uint32_t)(((uint64_t)i * d->n_branches) / 32);
-                        while (e < len && ep[e].branch < bound) e++;
-                        split[i - 1] = (uint16_t)e;
-                    }
-                    for (uint64_t i = 0; i < lenp; i++) {
-                        bp[i] = i < len ? (uint16_t)ep[i].branch : (uint16_t)0xFFFFu;  // padding = skip entries
-                        sp[i] = i < len ? ep[i].score : 0.0f;
-                    }
-                }
-            }
+    blob.assign(lay.blob_bytes / 8, lay.indexed ? Entry{0xFFFFFFFFu, RAW_PAD_SCORE} : slot_padding());
+    if (kind.want_windows || kind.want_pos) ws_by_key.assign(n_keys, 0);
+    unsigned hw = std::thread::hardware_concurrency();
+    const unsigned T = n_entries > (1u << 22) ? std::max(1u, std::min(hw ? hw : 1u, 16u)) : 1u;
+    std::vector<RowErr> errs(T);
+    std::vector<char> monos(T, 1);
+    std::vector<std::thread> th;
+    std::vector<uint64_t> cut(T + 1, n_keys);
+    cut[0] = 0;
+    for (unsigned t = 1; t < T; t++)
+        cut[t] = (uint64_t)(std::lower_bound(d->row_offsets, d->row_offsets + n_keys, n_entries * t / T) - d->row_offsets);
+    for (unsigned t = 0; t < T; t++) {
+        auto job = [&, t]() {
+            bool m = true;
+            fill_row_range(d, lay.indexed, desc, cut[t], cut[t + 1], blob.data(), ws_by_key.empty() ? nullptr : ws_by_key.data(), kind.key_w, errs[t], m);
+            monos[t] = m ? 1 : 0;
         };
-        unsigned hw = std::thread::hardware_concurrency();
-        const unsigned T = n_entries > (1u << 22) ? std::max(1u, std::min(hw ? hw : 1u, 16u)) : 1u;
-        std::vector<RowErr> errs(T);
-        std::vector<char> monos(T, 1);
-        std::vector<std::thread> th;
-        // ranges of (roughly) equal entry counts
-        std::vector<uint64_t> cut(T + 1, n_keys);
-        cut[0] = 0;
-        for (unsigned t = 1; t < T; t++) {
-            const uint64_t want = n_entries * t / T;
-            cut[t] = (uint64_t)(std::lower_bound(d->row_offsets, d->row_offsets + n_keys, want) - d->row_offsets);
-        }
-        for (unsigned t = 0; t < T; t++) {
-            auto job = [&, t]() { bool mono = true; fill(cut[t], cut[t + 1], errs[t], mono); monos[t] = mono ? 1 : 0; };
-            if (t + 1 < T) th.emplace_back(job); else job();
-        }
-        for (std::thread &x : th) x.join();
-        const RowErr *first = nullptr;
-        for (const RowErr &e : errs)
-            if (e.kind && (!first || e.r < first->r)) first = &e;
-        if (first) {
-            if (first->kind == 1) return fail(RK_ERR_INVALID, "rk_db_create: branch id %u >= n_branches in row %llu", first->x, (unsigned long long)first->r);
-            if (first->kind == 2) return fail(RK_ERR_INVALID, "rk_db_create: branch id %u repeated inside row %llu", first->x, (unsigned long long)first->r);
-            return fail(RK_ERR_INVALID, "rk_db_create: non-finite score in row %llu", (unsigned long long)first->r);
-        }
-        for (char mflag : monos)
-            if (!mflag) shape.mono = false;
+        if (t + 1 < T) th.emplace_back(job); else job();
     }
-
-    // ---- table ----
-    {
-        int rc = build_table(shape.mode, space, n_keys, indexed, max_units, blob_units,
-                             [&](uint64_t i) { return order[i].first; }, [&](uint64_t i) { return desc[order[i].second]; },
-                             [&](uint64_t i) { return d->key_codes[order[i].second]; }, img.table, shape.slots, shape.hash_mask, shape.nib);
-        if (rc) return rc;
+    for (std::thread &x : th) x.join();
+    const RowErr *first = nullptr;
+    for (const RowErr &e : errs)
+        if (e.kind && (!first || e.r < first->r)) first = &e;
+    if (first) {
+        if (first->kind == 1) return fail(RK_ERR_INVALID, "rk_db_create: branch id %u >= n_branches in row %llu", first->x, (unsigned long long)first->r);
+        if (first->kind == 2) return fail(RK_ERR_INVALID, "rk_db_create: branch id %u repeated inside row %llu", first->x, (unsigned long long)first->r);
+        return fail(RK_ERR_INVALID, "rk_db_create: non-finite score in row %llu", (unsigned long long)first->r);
     }
+    mono = std::find(monos.begin(), monos.end(), 0) == monos.end();
+    return RK_OK;
+}
 
-    shape.table_bytes = img.table.size() * sizeof(uint64_t);
-    shape.rows_bytes = blob_bytes;
-    shape.max_len = max_len;
-    // windows need the compact table (rows of <= 255 units) and 32-bit row offsets
-    shape.windowed = want_windows && shape.mode == RK_TABLE_DIRECT && blob_bytes < RK_WINDOW_MAX_BLOB;
-    shape.has_pos = !shape.windowed && (want_windows || want_pos) && (shape.mode == RK_TABLE_DIRECT || shape.mode == RK_TABLE_DIRECT8);
-    if (shape.windowed) shape.wp = wp;
-    if (shape.windowed || shape.has_pos) {
-        try { img.winspec.assign(space, 0); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create: host OOM"); }
-        for (uint64_t i = 0; i < n_keys; i++) img.winspec[order[i].first] = ws_by_key[order[i].second];
-        shape.winspec_bytes = space;
+static int build_image(const rk_db_desc *d, DbImage &img) {
+    ImageShape &shape = img.shape;
+    rk_image::TableMode tm{};
+    if (int rc = check_desc(d, shape, tm)) return rc;
+    KeyOrder order;
+    if (int rc = order_keys(d, shape.bits, order)) return rc;
+    rk_image::KindPlan kind;
+    rk_image::RowLayout lay(false);
+    std::vector<uint64_t> desc;  // by key number
+    uint32_t max_len = 0;
+    if (int rc = plan_layout(d, order, shape.bits, tm, kind, lay, desc, max_len)) return rc;
+    std::vector<unsigned char> ws_by_key;  // winspec_byte(first window, last window) of every row, or empty
+    if (int rc = fill_rows(d, kind, lay, desc, img.blob, ws_by_key, shape.mono)) return rc;
+    rk_image::build_table(shape, tm.space, lay, [&](uint64_t i) { return order[i].first; }, [&](uint64_t i) { return desc[order[i].second]; },
+                          [&](uint64_t i) { return d->key_codes[order[i].second]; }, image_knobs(), img.table);
+    rk_image::finish_shape(shape, lay, kind, img.table.size(), max_len, tm.space);
+    if (shape.winspec_bytes) {
+        img.winspec.assign(tm.space, 0);
+        for (uint64_t i = 0; i < shape.n_keys; i++) img.winspec[order[i].first] = ws_by_key[order[i].second];
     }
     return RK_OK;
 }

@@ -70,22 +70,17 @@ __global__ void __launch_bounds__(256) synth_fill_kernel(SynthParams sp, u64 n_k
             float *scp = (float *)(row + 2 * (size_t)lenp);
             if (threadIdx.x < 32) {
                 const u32 i = threadIdx.x + 1;
-                const u32 bound = (u32)(((u64)i * sp.n_branches) / 32);
+                const u32 bound = index_bound(i, sp.n_branches);
                 const u32 below = bound > b0 ? bound - b0 : 0u;  // entries with branch < bound
                 ((unsigned short *)(row - 64))[threadIdx.x] = (unsigned short)(below < len ? below : len);
             }
             for (u32 i = threadIdx.x; i < lenp; i += blockDim.x) {
-                bp[i] = i < len ? (unsigned short)(b0 + i) : (unsigned short)0xFFFFu;
-                scp[i] = i < len ? synth_score(sp, h0, i) : 0.0f;
+                bp[i] = i < len ? (unsigned short)(b0 + i) : RAW_PAD_BRANCH;
+                scp[i] = i < len ? synth_score(sp, h0, i) : RAW_PAD_SCORE;
             }
         } else {
             Entry *ep = (Entry *)row;
-            for (u32 i = threadIdx.x; i < lenp; i += blockDim.x) {
-                Entry e;
-                e.branch = i < len ? (b0 + i + 1u) * 4u : 0u;
-                e.score = i < len ? synth_score(sp, h0, i) : 0.0f;
-                ep[i] = e;
-            }
+            for (u32 i = threadIdx.x; i < lenp; i += blockDim.x) ep[i] = i < len ? Entry{slot_offset(b0 + i), synth_score(sp, h0, i)} : slot_padding();
         }
     }
 }
@@ -119,25 +114,21 @@ struct DevBufS {
 
 extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
     RK_GUARD_BEGIN
+    static const char *const who = "rk_db_create_synth";
     if (!d || !out) return fail(RK_ERR_INVALID, "rk_db_create_synth: null argument");
     *out = nullptr;
-    if (d->alphabet != RK_ALPHABET_DNA && d->alphabet != RK_ALPHABET_AA)
-        return fail(RK_ERR_INVALID, "rk_db_create_synth: alphabet must be 4 (DNA) or 20 (AA), got %u", d->alphabet);
-    const uint32_t kmax = d->alphabet == RK_ALPHABET_DNA ? 31 : 12;
-    if (d->k < 2 || d->k > kmax) return fail(RK_ERR_UNSUPPORTED, "rk_db_create_synth: k=%u outside supported range 2..%u", d->k, kmax);
-    if (d->n_branches < 1 || d->n_branches > 65535) return fail(RK_ERR_INVALID, "rk_db_create_synth: n_branches=%u must be in 1..65535", d->n_branches);
-    if (!std::isfinite(d->thr_log10) || !std::isfinite(d->thr)) return fail(RK_ERR_INVALID, "rk_db_create_synth: thresholds must be finite");
+    if (int rc = image_error(rk_image::check_scalars(d->alphabet, d->k, d->n_branches, d->thr_log10, d->thr), who, d->alphabet, d->k, d->n_branches, d->table_mode)) return rc;
     if (!(d->key_fraction > 0.0 && d->key_fraction <= 1.0)) return fail(RK_ERR_INVALID, "rk_db_create_synth: key_fraction must be in (0, 1]");
     if (!(d->mean_row_len >= 1.0 && d->mean_row_len <= 65535.0)) return fail(RK_ERR_INVALID, "rk_db_create_synth: mean_row_len must be in [1, 65535]");
-    uint64_t space = 0;
-    if (!ipow_fits(d->alphabet, d->k, 1ull << 32, space))
-        return fail(RK_ERR_UNSUPPORTED, "rk_db_create_synth: sigma^k must be <= 2^32 (every code is visited once)");
-    uint32_t mode = d->table_mode;
-    if (mode == RK_TABLE_AUTO) mode = space <= (1ull << 28) ? RK_TABLE_DIRECT : RK_TABLE_HASH;
-    if ((mode == RK_TABLE_DIRECT || mode == RK_TABLE_DIRECT8) && space > (1ull << 31))
-        return fail(RK_ERR_UNSUPPORTED, "rk_db_create_synth: direct table needs sigma^k <= 2^31 slots");
-    if (mode != RK_TABLE_DIRECT && mode != RK_TABLE_DIRECT8 && mode != RK_TABLE_HASH)
-        return fail(RK_ERR_INVALID, "rk_db_create_synth: bad table_mode %u", mode);
+    const rk_image::TableMode tm = rk_image::resolve_table_mode(d->table_mode, d->alphabet, d->k, 1ull << 32);
+    if (!tm.space_ok) return fail(RK_ERR_UNSUPPORTED, "rk_db_create_synth: sigma^k must be <= 2^32 (every code is visited once)");
+    if (int rc = image_error(tm.status, who, d->alphabet, d->k, d->n_branches, tm.mode)) return rc;
+    const uint64_t space = tm.space;
+    ImageShape shape;
+    shape.alphabet = d->alphabet; shape.convert_uo = d->convert_uo; shape.k = d->k; shape.n_branches = d->n_branches;
+    shape.thr_log10 = d->thr_log10; shape.thr = d->thr;
+    shape.bits = rk_image::bits_of(d->alphabet); shape.mode = tm.mode;
+    shape.mono = d->thr_log10 <= 0.0f;  // (scores are T * u, 0 <= u < 1)
 
     // ---- generator tables ----
     SynthParams sp{};
@@ -156,17 +147,15 @@ extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
     sp.surv = surv.data();
     sp.surv_n = (uint32_t)surv.size();
 
+    // The pass below writes a row's window span as it meets the row, so the window width is needed before a row is drawn: the plan is
+    // asked with the spec's density here, and plan_kind below, given the same density, keeps or drops these very windows
+    const rk_image::RowDensity density = rk_image::spec_density((double)sp.key_thresh / 4294967296.0, d->mean_row_len);
     WindowPlan wp;
-    const uint32_t sym_bits = d->alphabet == RK_ALPHABET_DNA ? 2u : 5u;
-    // (used only when the image turns out not to be an indexed one; the rows are not drawn yet: their density from the spec)
-    const double upc_spec = ((double)sp.key_thresh / 4294967296.0) * (d->mean_row_len / (double)ROW_UNIT + 0.5);
-    const bool want_windows = rk_geom::window_plan(d->n_branches, sym_bits, upc_spec, d->mean_row_len / (double)ROW_UNIT + 0.5, geom_knobs(), wp);
+    const bool may_window = rk_geom::window_plan(d->n_branches, shape.bits, density.units_per_code, density.units_per_row, geom_knobs(), wp);
     std::vector<unsigned char> winspec;  // [space] winspec_byte(first, last window) of every row (rows are branch runs)
-    if (want_windows) {
-        try { winspec.assign(space, 0); } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create_synth: host OOM"); }
-    }
+    if (may_window) winspec.assign(space, 0);
     // ---- pass 1 (host): which codes carry a row and how long it is; rows are laid out in dense order ----
-    std::vector<u64> dense, lens32;  // lens32: row length per present key (u64 to share the prefix pass below)
+    std::vector<u64> dense, lens32;  // lens32: row length per present key (u64: they become the descriptors below)
     {
         unsigned hw = std::thread::hardware_concurrency();
         const unsigned T = space > (1u << 20) ? std::max(1u, std::min(hw ? hw : 1u, 16u)) : 1u;
@@ -183,7 +172,7 @@ extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
                         const u32 len = synth_len(sp, h0);
                         dpart[t].push_back(c);
                         lpart[t].push_back(len);
-                        if (want_windows) {
+                        if (may_window) {
                             const u32 b0 = synth_b0(sp, h0, len), f = b0 / wp.W, l = (b0 + len - 1) / wp.W;
                             winspec[c] = winspec_byte(f, l);
                         }
@@ -194,74 +183,37 @@ extern "C" int rk_db_create_synth(const rk_synth_desc *d, rk_db **out) {
         }
         for (std::thread &x : th) x.join();
         if (oom) return fail(RK_ERR_NOMEM, "rk_db_create_synth: host OOM");
-        try {
-            for (unsigned t = 0; t < T; t++) {
-                dense.insert(dense.end(), dpart[t].begin(), dpart[t].end());
-                lens32.insert(lens32.end(), lpart[t].begin(), lpart[t].end());
-                std::vector<u64>().swap(dpart[t]);
-                std::vector<u64>().swap(lpart[t]);
-            }
-        } catch (const std::bad_alloc &) { return fail(RK_ERR_NOMEM, "rk_db_create_synth: host OOM"); }
-    }
-    const uint64_t n_keys = dense.size();
-    uint64_t n_entries = 0;
-    uint32_t max_len = 0;
-    for (uint64_t i = 0; i < n_keys; i++) { n_entries += lens32[i]; if (lens32[i] > max_len) max_len = (uint32_t)lens32[i]; }
-    const double mean_len = n_keys ? (double)n_entries / (double)n_keys : 0.0;
-    uint64_t slot_units = 1;
-    for (uint64_t i = 0; i < n_keys; i++) slot_units += (lens32[i] + ROW_UNIT - 1) / ROW_UNIT;
-    const ImageKind kind = rk_geom::image_kind(d->n_branches, sym_bits, mode == RK_TABLE_DIRECT, space, slot_units, max_len, mean_len, geom_knobs());  // (AUTO is resolved by now)
-    const bool indexed = kind.indexed;
-    const uint64_t unit_bytes = indexed ? 64 : ROW_UNIT * 8;
-    uint64_t blob_units = 1, max_units = 0;
-    std::vector<u64> &desc = lens32;  // lengths become descriptors in place
-    for (uint64_t i = 0; i < n_keys; i++) {
-        const uint64_t len = lens32[i];
-        uint64_t units = (len + ROW_UNIT - 1) / ROW_UNIT, lenp = units * ROW_UNIT;
-        if (indexed) {
-            blob_units += 1;  // the index line
-            lenp = (len + 31) / 32 * 32;
-            units = lenp * 6 / 64;
+        for (unsigned t = 0; t < T; t++) {
+            dense.insert(dense.end(), dpart[t].begin(), dpart[t].end());
+            lens32.insert(lens32.end(), lpart[t].begin(), lpart[t].end());
+            std::vector<u64>().swap(dpart[t]);
+            std::vector<u64>().swap(lpart[t]);
         }
-        if (units > max_units) max_units = units;
-        desc[i] = ((blob_units * (unit_bytes / 8)) << DESC_LEN_BITS) | lenp;
-        blob_units += units;
     }
-    const uint64_t blob_bytes = blob_units * unit_bytes;
-    if ((blob_bytes >> 3) >= (1ull << 40)) return fail(RK_ERR_UNSUPPORTED, "rk_db_create_synth: row blob exceeds 8 TiB");
-    ImageShape shape;
-    shape.alphabet = d->alphabet; shape.convert_uo = d->convert_uo; shape.k = d->k; shape.n_branches = d->n_branches;
-    shape.thr_log10 = d->thr_log10; shape.thr = d->thr;
-    shape.bits = sym_bits; shape.max_len = max_len; shape.indexed = indexed; shape.mono = d->thr_log10 <= 0.0f;
-    shape.n_keys = n_keys; shape.n_entries = n_entries;
+    // ---- the plan: kind of image (no position keys in a generated image), row layout, table ----
+    const uint64_t n_keys = dense.size();
+    rk_image::RowStats rs;
+    for (uint64_t i = 0; i < n_keys; i++) rs.add(lens32[i]);
+    shape.n_keys = n_keys; shape.n_entries = rs.n_entries;
+    const rk_image::KindPlan kind = rk_image::plan_kind(d->n_branches, shape.bits, tm, rs, density, false, geom_knobs());
+    rk_image::RowLayout lay(kind.indexed);
+    std::vector<u64> &desc = lens32;  // lengths become descriptors in place
+    for (uint64_t i = 0; i < n_keys; i++) desc[i] = lay.add_row(lens32[i]);
+    if (int rc = image_error(lay.finish(), who, d->alphabet, d->k, d->n_branches, tm.mode)) return rc;
     std::vector<uint64_t> table;
-    {
-        const uint32_t alphabet = d->alphabet, k = d->k;
-        auto code_of = [&](uint64_t i) -> uint64_t {
-            if (alphabet == RK_ALPHABET_DNA) return dense[i];
-            uint64_t code = 0, rem = dense[i];
-            for (uint32_t j = 0; j < k; j++) { code |= (rem % 20) << (5 * j); rem /= 20; }
-            return code;
-        };
-        int rc = build_table(mode, space, n_keys, indexed, max_units, blob_units, [&](uint64_t i) { return dense[i]; },
-                             [&](uint64_t i) { return desc[i]; }, code_of, table, shape.slots, shape.hash_mask, shape.nib);
-        if (rc) return rc;
-    }
-    shape.mode = mode;
-    shape.table_bytes = table.size() * sizeof(uint64_t);
-    shape.rows_bytes = blob_bytes;
-    // windowed under rk_db_create's conditions; a generated image carries no position keys
-    shape.windowed = want_windows && kind.windowable && mode == RK_TABLE_DIRECT && blob_bytes < RK_WINDOW_MAX_BLOB;
-    if (shape.windowed) { shape.wp = wp; shape.winspec_bytes = winspec.size(); }
+    rk_image::build_table(shape, space, lay, [&](uint64_t i) { return dense[i]; }, [&](uint64_t i) { return desc[i]; },
+                          [&](uint64_t i) { return rk_image::code_of_dense(shape.bits, d->k, dense[i]); }, image_knobs(), table);
+    rk_image::finish_shape(shape, lay, kind, table.size(), rs.longest, space);
 
     // ---- device: table and window spans uploaded, the rows filled by a kernel from the generator's tables ----
+    const bool indexed = lay.indexed;
     DevBufS d_dense, d_desc, d_surv;  // (freed after install has synchronised)
     return install(shape, d->device, [&](const rk_db &db, int sec, void *dst, uint64_t bytes) -> int {
         if (sec != IMG_ROWS) {
             if (bytes) HIP_TRY(hipMemcpy(dst, sec == IMG_TABLE ? (const void *)table.data() : (const void *)winspec.data(), bytes, hipMemcpyHostToDevice));
             return RK_OK;
         }
-        HIP_TRY(hipMemset(dst, indexed ? 0xFF : 0, unit_bytes));  // unit 0: the reserved "skip" / scratch pattern
+        HIP_TRY(hipMemset(dst, indexed ? 0xFF : 0, lay.unit_bytes));  // unit 0: the reserved "skip" / scratch pattern
         if (!n_keys) return RK_OK;
         HIP_TRY(hipMalloc(&d_dense.p, n_keys * 8));
         HIP_TRY(hipMalloc(&d_desc.p, n_keys * 8));
@@ -298,10 +250,9 @@ extern "C" int rk_db_fetch_row(rk_db *db, uint64_t code, uint32_t cap, uint32_t 
     if (!db || !len) return fail(RK_ERR_INVALID, "rk_db_fetch_row: null argument");
     if (cap && (!branch_ids || !scores)) return fail(RK_ERR_INVALID, "rk_db_fetch_row: null output arrays");
     const uint32_t bits = db->info.bits_per_symbol;
-    if (bits * db->info.k < 64 && (code >> (bits * db->info.k))) return fail(RK_ERR_INVALID, "rk_db_fetch_row: code outside the k-mer space");
-    if (bits == 5)
-        for (uint32_t i = 0; i < db->info.k; i++)
-            if (((code >> (5 * i)) & 31) >= 20) return fail(RK_ERR_INVALID, "rk_db_fetch_row: code has a digit >= 20");
+    uint64_t dense;
+    if (!rk_image::code_in_space(bits, db->info.k, code)) return fail(RK_ERR_INVALID, "rk_db_fetch_row: code outside the k-mer space");
+    if (bits == 5 && !rk_image::aa_dense_of_code(code, db->info.k, dense)) return fail(RK_ERR_INVALID, "rk_db_fetch_row: code has a digit >= 20");
     int prev = 0;
     (void)hipGetDevice(&prev);
     struct Restore { int p; ~Restore() { (void)hipSetDevice(p); } } restore{prev};

@@ -10,6 +10,7 @@ import pytest
 import rappas_amd as ra
 from rappas_amd import synth
 from oracle import oracle as O
+from tests import image_shapes
 from tests.util import compare_with_oracle
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +130,64 @@ def test_generated_image_survives_save_load_and_clone(shape, tmp_path):
             loaded.close()
     finally:
         db.close()
+
+
+@pytest.mark.parametrize("table", sorted(image_shapes.MODES))
+@pytest.mark.parametrize("shape", ["small_tree", "large_tree_900", "protein", "windowed"])
+def test_generated_image_header_is_the_recorded_one(shape, table, tmp_path):
+    """the saved header of a generated image -- every field of its shape, a checksum of its sections -- is the one recorded in
+    tests/golden/image_headers.tsv before the synthetic builder took its plan from rk_image_plan.h"""
+    path = str(tmp_path / "synth.rkimg")
+    db = ra.PhyloKmerDB.synthetic(image_shapes.synth_cases()[shape], table_mode=image_shapes.MODES[table])
+    try:
+        assert ("place_wg_kernel" in db.kernel_name()) == (shape == "large_tree_900")
+        db.save(path)
+    finally:
+        db.close()
+    assert image_shapes.header_hex(path) == image_shapes.golden("synth")[(shape, table)]
+
+
+@pytest.fixture(scope="module")
+def host_rows():
+    """the rows of a generated database as CSR arrays (the numpy twin), made once per spec"""
+    made = {}
+
+    def rows(shape):
+        if shape not in made:
+            spec = image_shapes.synth_cases()[shape]
+            made[shape] = spec.subset_db(np.arange(spec.space, dtype=np.uint64))
+        return made[shape]
+    return rows
+
+
+@pytest.mark.parametrize("table", sorted(image_shapes.MODES))
+@pytest.mark.parametrize("shape", ["small_tree", "large_tree_900", "protein", "windowed"])
+def test_one_generated_database_through_both_builders(shape, table, host_rows, tmp_path):
+    """rk_db_create_synth of a spec and rk_db_create of the spec's rows, both saved: the same k-mer table byte for byte in every mode;
+    the same rows, but for the reserved unit 0 of a large-tree image (64 bytes: all 0xFF from the generator, {0xFFFFFFFF, 0.0f} pairs
+    from rk_db_create; no kernel reads it as an entry); the same header fields, but for those the builders differ in on purpose --
+    has_pos / winspec_bytes (a generated image carries no position keys) and the plan's units_per_code (density from the spec) --
+    DESIGN.md, "The image plan".  What was equal before the plan moved is equal now."""
+    spec, mode = image_shapes.synth_cases()[shape], image_shapes.MODES[table]
+    a = ra.PhyloKmerDB.synthetic(spec, table_mode=mode)
+    b = ra.PhyloKmerDB.from_synth(host_rows(shape), table_mode=mode)
+    pa, pb = str(tmp_path / "synth.rkimg"), str(tmp_path / "create.rkimg")
+    try:
+        a.save(pa)
+        b.save(pb)
+    finally:
+        a.close()
+        b.close()
+    ha, hb = bytes.fromhex(image_shapes.header_hex(pa)), bytes.fromhex(image_shapes.header_hex(pb))
+    # (header offsets: scalars ... windowed [24, 76), has_pos 76, n_keys ... wp_stream [80, 136), wp_units_per_code 136, table_bytes and rows_bytes [144, 160))
+    assert ha[24:76] == hb[24:76] and ha[80:136] == hb[80:136] and ha[144:160] == hb[144:160]
+    (ta, ra_, wa), (tb, rb, wb) = image_shapes.sections(pa), image_shapes.sections(pb)
+    indexed = shape == "large_tree_900"
+    assert int.from_bytes(ha[60:64], "little") == indexed
+    assert ta == tb
+    assert ra_[64 if indexed else 0:] == rb[64 if indexed else 0:] and len(ra_) == len(rb)
+    if table == "hash" or (shape, table) == ("windowed", "auto"):   # no third section, or window spans: equal; position keys: rk_db_create only
+        assert wa == wb
 
 
 def test_argument_errors():
