@@ -822,6 +822,85 @@ int rk_epca_finish_host(uint32_t n_branches, uint32_t n_samples, uint32_t k, con
                         double *residual, double *projection /*[S][k]*/, double *loading /*[B][k]*/);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Edge dispersion and edge correlation of the samples of a sample mass buffer (what `gappa analyze dispersion` / `gappa analyze
+ * correlation` compute from jplace files): for every edge how much its share of the mass and its imbalance vary across the samples,
+ * and the Pearson and Spearman correlation of both with every column of sample metadata.  The reference has no counterpart.  Fixed
+ * so that every implementation gives the same bits; the tree handle, the sample mass buffer, c_s(x), m_s(x), T_s, u_s(x), v_s(x)
+ * are those of the KR block; binary64 with IEEE conversion, /, +, -, *, no contraction; no square root outside the Finish.
+ *   Limits              1 <= S <= RK_EDGESTAT_MAX_SAMPLES (an edge's row is ranked inside the LDS of one block; squash and edge PCA
+ *                       have the same limit), 0 <= F <= RK_EDGESTAT_MAX_FEATURES metadata columns.
+ *   Active samples      sample s is active iff T_s != 0; n = the number of active samples.
+ *   Profiles            two quantities per edge x and active sample s:
+ *                           q = 0, mass share    P0[x][s] = (double)m_s(x) / (double)T_s
+ *                           q = 1, imbalance     P1[x][s] = (u_s(x) + v_s(x)) - 1.0        (step 2 of the edge PCA block)
+ *                       P0 is taken from the integers, not from u - v: the difference cancels under a heavy clade, and the ranks
+ *                       must not see ties that are not there.  For the root, or an inactive s, both are +0.0; the root's row is
+ *                       otherwise computed like any other.  Neither formula gives -0.0.
+ *   Metadata            d_meta [F][S] doubles, g_f[s].  Column f is usable iff g_f[s] is finite for every active s -- decided on
+ *                       the device, where alone the activity is known.  An unusable column: every raw word of the column is
+ *                       written as its filler, the quiet NaN 0x7FF8000000000000 for a double and 0 for an integer, and bit f of
+ *                       info[1] is set.  The value of an inactive sample is never used.
+ *   Sums over samples   the lane rule LS of the edge PCA block (64 lane partials, each sequential over s = l, l + 64, ..., folded
+ *                       in lane order from +0.0); a product is rounded, then added (gram_term).
+ *   Moments             per edge x and quantity q, a[s] = Pq[x][s]: mean = LS(s -> a[s]) / (double)n (inactive entries are +0.0);
+ *                       c[s] = a[s] - mean for an active s, +0.0 otherwise; ss = LS(s -> c[s] * c[s]).  Per usable column f,
+ *                       once: gmean_f, gc_f[s], gss_f likewise from g_f (an inactive entry counts as +0.0).  Per edge:
+ *                       cross_{q,f} = LS(s -> c[s] * gc_f[s]).
+ *   Ranks, in integers  for an active s: rank2(a)[s] = 2 * #{active t : a[t] < a[s]} + #{active t : a[t] == a[s]} + 1 -- twice the
+ *                       1-based mid-rank; t = s counts in the second term.  Plain < and == on the doubles (no NaN occurs among
+ *                       active samples; an implementation that sorts bit keys must still treat the values as numbers).
+ *                       d[s] = rank2 - (n + 1) for an active s, 0 otherwise: sum d = 0 and |d| <= n - 1.  rss = sum d[s]^2.
+ *                       Per usable column gd_f, grss_f likewise from g_f; per edge rcross_{q,f} = sum d[s] * gd_f[s].  All int64,
+ *                       exact below 4096^3: no order in it.
+ *   Raw output          rk_edgestat_out_words(B, F) = B * (6 + 4F) + 3F eight-byte words, WRITTEN, not added into.  Row x:
+ *                           mean0 | ss0 | rss0 | mean1 | ss1 | rss1 | then per f: cross_{0,f} | rcross_{0,f} | cross_{1,f} | rcross_{1,f}
+ *                       doubles and int64 as named.  Behind the B rows a row per column f: gmean_f | gss_f | grss_f.
+ *                       info [2] uint32_t = {n, the mask of the unusable columns}.  n == 0: every raw word is 0 / +0.0.
+ *   Finish              rk_edgestat_finish_host, host only, the one place with a square root.  table [B][8 + 4F] doubles:
+ *                           0 mass_mean = mean0   1 mass_var = ss0 / (double)n   2 mass_sd = sqrt(var)   3 mass_cv = sd / mean
+ *                           4 mass_vmr = var / mean   5 imb_mean = mean1   6 imb_var = ss1 / (double)n   7 imb_sd = sqrt(var)
+ *                       then per f: mass_pearson = cross_{0,f} / sqrt(ss0 * gss_f), mass_spearman = (double)rcross_{0,f} /
+ *                       sqrt((double)rss0 * (double)grss_f), imb_pearson, imb_spearman likewise.  feature_table [F][2]: gmean_f,
+ *                       gss_f / (double)n.  The variance is the population form (a caller who wants n - 1 rescales).  Nothing is
+ *                       clamped and the formulas have no special case: a constant row gives 0 / 0 = NaN, an unusable column is
+ *                       NaN.  With n == 0 the raw words are fillers, not sums: both tables are the quiet NaN throughout.  Each
+ *                       stated operation is one rounding.
+ *   Consequences        The result does not depend on grid, block shape or stream.  Spearman's integer words do not change under a
+ *                       strictly increasing transform of a metadata column, nor under one permutation applied to the samples of
+ *                       buffer and metadata.  A row strictly increasing with a column has rcross == rss == grss: Spearman is
+ *                       exactly 1.0 (strictly decreasing: -1.0).
+ *   rk_edgestat_out_words   the length of the raw output; 0 for arguments out of range.
+ *   rk_edgestat_work_bytes  bytes of the caller-owned device workspace: the clade sums, P0 and P1 node-major, gc and gd of every
+ *                           column and the active flags; 0 and a message on a bad argument.
+ *   rk_edgestat_device      d_raw [rk_edgestat_out_words] and d_info [2], written.  Clade sums, profiles, the column prelude and
+ *                           the edge kernel: plain launches in stream order, no host synchronisation, no grid-wide wait, no
+ *                           cross-block atomics; every workspace word is written before it is read.  A row of at most
+ *                           RK_EDGESTAT_COUNT_MAX_SAMPLES samples is ranked by counting, a longer one by a sort in the LDS (the
+ *                           same integers).  RK_ERR_INVALID and a message -- nothing launched, nothing written -- for a NULL
+ *                           pointer, d_meta == NULL with F > 0, S outside 1..4096, F > 8, a short or misaligned workspace.
+ *                           Asynchronous on `stream`; calls on two streams may share a tree handle, each with its own workspace.
+ *   rk_edgestat_host        the same bits in plain C++: no handle, no GPU.  n_threads 0 = automatic, at most 16.
+ *   rk_edgestat_batch       the drivers' call, with the contract of rk_epca_batch: masses NULL = the buffer the last per-sample
+ *                           profile-only call left in the handle.  `meta` is a host array [F][S]; a value that is not finite is
+ *                           RK_ERR_INVALID on the host.  raw and info on the host; returns when they are filled.
+ *   rk_edgestat_finish_host table and feature_table (may be NULL when F == 0) from a raw output and its info words, all written.
+ * Added without a bump of RK_VERSION (no existing struct changed).
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define RK_EDGESTAT_MAX_SAMPLES 4096u
+#define RK_EDGESTAT_MAX_FEATURES 8u
+#define RK_EDGESTAT_COUNT_MAX_SAMPLES 128u
+uint64_t rk_edgestat_out_words(uint32_t n_branches, uint32_t n_features);
+uint64_t rk_edgestat_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t n_features);
+int rk_edgestat_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t n_features, const double *d_meta, uint64_t *d_raw,
+                       uint32_t *d_info, void *d_work, uint64_t work_bytes, void *stream);
+int rk_edgestat_host(uint32_t n_branches, const int32_t *parent, uint32_t n_samples, const uint64_t *masses, uint32_t n_features, const double *meta,
+                     uint64_t *raw, uint32_t *info, uint32_t n_threads);
+int rk_edgestat_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t n_features, const double *meta /* host */,
+                      uint64_t *raw, uint32_t *info);
+int rk_edgestat_finish_host(uint32_t n_branches, uint32_t n_samples, uint32_t n_features, const uint64_t *raw, const uint32_t *info, double *table,
+                            double *feature_table);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * EDPL, the expected distance between placement locations of a read (Matsen et al. 2010; what `guppy edpl` / `gappa examine edpl`
  * compute from jplace files): the sum over the pairs of a read's placements of LWR x LWR x the tree path between them -- small for
  * a read whose rows sit on neighbouring edges, large for one whose weight is split between distant clades.  The reference has no

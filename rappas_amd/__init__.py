@@ -11,3 +11,4 @@ from ._lib import (RK_ALPHABET_AA, RK_ALPHABET_DNA, RK_AMB_MAX, RK_AMB_MEAN, RK_
 from .placement import (EdgeTree, EdgePCA, PhyloKmerDB, PlacementProcess, Placements, accumulate_masses_host, clade_masses_host, kr_distances_host, accumulate_masses_samples_host, db_image_info,  # noqa: F401
                         host_alloc, masses_samples_words, masses_words, pack_reads, save_db_image, epca_finish, epca_host, edpl_host, tree_distance_host, squash_host, SQUASH_MERGE, kmeans_host, KMeans, KMEANS_NONE, diversity_host, diversity_math_host, diversity_columns, Diversity, translate_packed_host, translated_words, validate_db)
 from .dbbuild import BuiltDB, build_db  # noqa: F401
+from .edgestats import EdgeStats, edgestat, edgestat_batch, edgestat_columns, edgestat_finish, edgestat_host  # noqa: F401

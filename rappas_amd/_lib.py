@@ -178,6 +178,12 @@ EXPORTS = {
     "rk_epca_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]),
     "rk_epca_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rk_epca_finish_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rk_edgestat_out_words": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+    "rk_edgestat_work_bytes": (C.c_uint64, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rk_edgestat_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rk_edgestat_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rk_edgestat_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rk_edgestat_finish_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rk_edpl_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_void_p]),
     "rk_edpl_host": (C.c_int, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p, C.c_uint32]),
     "rk_edpl_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(rk_result), C.c_void_p]),

@@ -550,6 +550,123 @@ inline std::string diversity_table(const std::vector<std::string> &names, const 
     return out + "#samples_without_mass\t" + std::to_string(without) + "\n";
 }
 
+// The sample metadata of `--metadata TSV`: a first line `sample<TAB>name_1<TAB>...<TAB>name_F` with F <= 8, then one line per
+// sample -- its name and F finite numbers --; empty lines are skipped.  The twin of hostio.parse_metadata: the same sentences.
+struct Metadata {
+    std::vector<std::string> features;
+    std::map<std::string, std::vector<double>> rows;
+};
+
+// a number of a --metadata file: [+-] digits with an optional point and fraction, an optional exponent, and finite; what strtod
+// accepts beyond that (inf, nan, hex, blanks) is no number here
+inline bool metadata_number(const std::string &t, double &v) {
+    size_t i = 0, digits = 0;
+    auto run = [&]() { size_t n = 0; while (i < t.size() && t[i] >= '0' && t[i] <= '9') { i++; n++; } return n; };
+    if (i < t.size() && (t[i] == '+' || t[i] == '-')) i++;
+    digits = run();
+    if (i < t.size() && t[i] == '.') {
+        i++;
+        const size_t frac = run();
+        if (!digits && !frac) return false;
+    } else if (!digits) {
+        return false;
+    }
+    if (i < t.size() && (t[i] == 'e' || t[i] == 'E')) {
+        i++;
+        if (i < t.size() && (t[i] == '+' || t[i] == '-')) i++;
+        if (!run()) return false;
+    }
+    if (i != t.size()) return false;
+    v = strtod(t.c_str(), nullptr);
+    return std::isfinite(v);
+}
+
+inline Metadata parse_metadata(const std::string &text) {
+    Metadata md;
+    size_t n_fields = 0, no = 0;
+    bool head = false;
+    for (size_t at = 0; at <= text.size();) {
+        const size_t nl = std::min(text.find('\n', at), text.size());
+        std::string line = text.substr(at, nl - at);
+        at = nl + 1;
+        no++;
+        while (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        std::vector<std::string> f;
+        for (size_t b = 0; b <= line.size();) {
+            const size_t tab = std::min(line.find('\t', b), line.size());
+            f.push_back(line.substr(b, tab - b));
+            b = tab + 1;
+        }
+        if (!head) {
+            bool good = f[0] == "sample" && f.size() - 1 <= 8;
+            for (size_t i = 1; i < f.size(); i++) good = good && !f[i].empty();
+            if (!good) break;
+            head = true;
+            n_fields = f.size();
+            md.features.assign(f.begin() + 1, f.end());
+            continue;
+        }
+        const std::string where = "--metadata: line " + std::to_string(no);
+        if (f.size() != n_fields) throw std::runtime_error(where + " has " + std::to_string(f.size()) + " fields, the first line has " + std::to_string(n_fields));
+        std::vector<double> values(n_fields - 1);
+        for (size_t i = 1; i < n_fields; i++)
+            if (!metadata_number(f[i], values[i - 1])) throw std::runtime_error(where + ": '" + f[i] + "' is not a finite number");
+        if (!md.rows.emplace(f[0], values).second) throw std::runtime_error(where + ": the sample '" + f[0] + "' has a line already");
+    }
+    if (!head) throw std::runtime_error("--metadata: the first line must be sample<TAB>name_1<TAB>...<TAB>name_F with at most 8 column names");
+    return md;
+}
+
+// [F][S]: the metadata of the samples of a run, in sample order (md nullptr: no file, F = 0); more than 4096 samples, or a sample of
+// the run without a line, is an error -- lines of other samples are ignored.  The twin of hostio.metadata_of_samples.
+inline std::vector<double> metadata_of_samples(const std::vector<std::string> &names, const Metadata *md) {
+    if (names.size() > 4096) throw std::runtime_error("--edge-stats: the run has " + std::to_string(names.size()) + " samples, at most 4096");
+    if (!md) return {};
+    const size_t S = names.size(), F = md->features.size();
+    std::vector<double> out(F * S);
+    for (size_t s = 0; s < S; s++) {
+        const auto it = md->rows.find(names[s]);
+        if (it == md->rows.end()) throw std::runtime_error("--metadata: the sample '" + names[s] + "' of the run has no line");
+        for (size_t f = 0; f < F; f++) out[f * S + s] = it->second[f];
+    }
+    return out;
+}
+
+// The text `--edge-stats FILE` writes, every double as `%.17g` (a NaN as `nan`, whatever its sign):
+// `#edge_stats<TAB>S<TAB>B<TAB>F<TAB>n_active`; a line `#columns` with node, the eight fixed columns and, per metadata column,
+// mass_pearson_<name>, mass_spearman_<name>, imb_pearson_<name>, imb_spearman_<name>; a line per node id (the id and its values);
+// `#features` and a line per metadata column (its name, its mean and its population variance over the samples with mass);
+// `#samples_without_mass<TAB>n`.  table [B][8 + 4F] and feature_table [F][2] are what rk_edgestat_finish_host leaves.  The twin of
+// hostio.edge_stats_table (byte-identical).
+inline std::string edge_stats_table(const std::vector<std::string> &names, const std::vector<std::string> &features, uint32_t n_active, uint32_t n_branches,
+                                    const double *table, const double *feature_table) {
+    const size_t S = names.size(), F = features.size(), C = 8 + 4 * F;
+    std::string out = "#edge_stats\t" + std::to_string(S) + "\t" + std::to_string(n_branches) + "\t" + std::to_string(F) + "\t" + std::to_string(n_active) +
+                      "\n#columns\tnode\tmass_mean\tmass_var\tmass_sd\tmass_cv\tmass_vmr\timb_mean\timb_var\timb_sd";
+    for (const std::string &n : features) out += "\tmass_pearson_" + n + "\tmass_spearman_" + n + "\timb_pearson_" + n + "\timb_spearman_" + n;
+    out += "\n";
+    char buf[64];
+    auto num = [&](double v) {
+        if (v != v) { out += "\tnan"; return; }
+        snprintf(buf, sizeof(buf), "\t%.17g", v);
+        out += buf;
+    };
+    for (size_t x = 0; x < n_branches; x++) {
+        out += std::to_string(x);
+        for (size_t i = 0; i < C; i++) num(table[x * C + i]);
+        out += "\n";
+    }
+    out += "#features\n";
+    for (size_t f = 0; f < F; f++) {
+        out += features[f];
+        num(feature_table[2 * f]);
+        num(feature_table[2 * f + 1]);
+        out += "\n";
+    }
+    return out + "#samples_without_mass\t" + std::to_string(S - n_active) + "\n";
+}
+
 // The text `--epca FILE` writes, every double as `%.17g`: `#epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff<TAB>iters`; the lines
 // `#eigenvalue`, `#share`, `#residual` with k values each; `#projections` and a line per sample (its name and k values); `#loadings`
 // and a line per node id (the id and k values); `#samples_without_mass<TAB>n`.  The arrays are what rk_epca_finish_host leaves:

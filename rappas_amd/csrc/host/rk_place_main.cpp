@@ -46,6 +46,13 @@ static int usage(std::ostream &os = std::cerr, int rc = 2) {
                  "                 guppy fpd reports, summed on the device: a line #diversity<TAB>S<TAB>n_theta, a line #columns with rooted_pd, pd,\n"
                  "                 bwpd, quadratic, phylo_entropy and, per theta (at most 8 exponents in 0..8), rooted_pd_<theta> and bwpd_<theta>, a\n"
                  "                 line name<TAB>values (%.17g) per sample (nan without mass), and a last line #samples_without_mass<TAB>n)\n"
+                 "                [--edge-stats FILE [--metadata TSV]]  (with --sample-sep: edge dispersion and edge correlation, found on the device: for\n"
+                 "                 every edge the mean, variance, standard deviation, coefficient of variation and variance-to-mean ratio of its mass\n"
+                 "                 share across the samples, mean, variance and standard deviation of its imbalance, and per metadata column the\n"
+                 "                 Pearson and Spearman correlation of both: a line #edge_stats<TAB>S<TAB>B<TAB>F<TAB>n_active, a line #columns, a\n"
+                 "                 line per node id (%.17g, nan), #features and a line name<TAB>mean<TAB>variance per column, and a last line\n"
+                 "                 #samples_without_mass<TAB>n; at most 4096 samples.  TSV: a first line sample<TAB>name_1<TAB>...<TAB>name_F, F <= 8,\n"
+                 "                 and a line per sample with its name and F finite numbers; every sample of the run needs a line)\n"
                  "                [--epca FILE [--epca-components K] [--epca-iters N]]  (with --sample-sep: the edge principal components of the samples --\n"
                  "                 the difference between the mass on the two sides of every edge, centred --, found on the device: K components\n"
                  "                 (1..8, default 5) after N iterations (1..10000, default 200): a line #epca<TAB>S<TAB>B<TAB>k<TAB>n_active<TAB>k_eff\n"
@@ -73,7 +80,7 @@ static void ok(int rc, const char *call) {
 static const uint32_t NO_MODE = 0xFFFFFFFFu;  // (--amb / --strand with a word that is none of theirs)
 
 struct Options {
-    std::string jsondb, uniondb, dbimage, save_image, fasta, out, logs, masses, masses_only, sample_sep, kr, squash, epca, edpl, kmeans, diversity, call;
+    std::string jsondb, uniondb, dbimage, save_image, fasta, out, logs, masses, masses_only, sample_sep, kr, squash, epca, edpl, kmeans, diversity, edge_stats, metadata, call;
     bool sample_sep_given = false, logs_given = false, md5_dedup = false, classic = false, timing = false, translate = false, guppy = false;
     unsigned threads = 0;
     uint32_t keep_at_most = 7, epca_k = 5, epca_iters = 200, kmeans_k = 0, kmeans_rounds = 100, amb_mode = RK_AMB_MEAN, strand = RK_STRAND_FORWARD;
@@ -81,6 +88,7 @@ struct Options {
     int device = 0;
     std::vector<double> thetas;  // --diversity-theta: numbers separated by commas
     bool thetas_ok = true;
+    std::optional<rkh::Metadata> meta;  // --metadata: the file, parsed before the database is opened
 
     int n_sources() const { return (jsondb.empty() ? 0 : 1) + (uniondb.empty() ? 0 : 1) + (dbimage.empty() ? 0 : 1); }
     bool only_convert() const { return !save_image.empty() && fasta.empty() && out.empty() && masses_only.empty(); }
@@ -135,6 +143,8 @@ static int parse_options(int argc, char **argv, Options &o) {
         else if (a == "--kmeans-k") o.kmeans_k = (uint32_t)std::stoul(val());
         else if (a == "--kmeans-rounds") o.kmeans_rounds = (uint32_t)std::stoul(val());
         else if (a == "--diversity") o.diversity = val();
+        else if (a == "--edge-stats") o.edge_stats = val();
+        else if (a == "--metadata") o.metadata = val();
         else if (a == "--diversity-theta") { o.thetas.clear(); o.thetas_ok = true; parse_thetas(val(), o); }
         else if (a == "--epca-components") o.epca_k = (uint32_t)std::stoul(val());
         else if (a == "--epca-iters") o.epca_iters = (uint32_t)std::stoul(val());
@@ -161,6 +171,7 @@ struct ReportCall {
     const std::vector<std::string> &names;
     const uint64_t *words;               // the sample mass buffer on the host, or nullptr: where the per-sample profile-only call left it on the device
     const std::vector<char> &with_mass;  // [S], from the host's copy of the buffer (filled for the rows that ask for it)
+    const std::vector<double> &meta;     // [F][S], the metadata of the run's samples (--edge-stats)
 };
 
 static std::string kr_report(const ReportCall &c) {
@@ -210,6 +221,18 @@ static std::string diversity_report(const ReportCall &c) {
     return rkh::diversity_table(c.names, thetas, values.data());
 }
 
+static std::string edge_stats_report(const ReportCall &c) {
+    static const std::vector<std::string> none;
+    const std::vector<std::string> &features = c.o.meta ? c.o.meta->features : none;
+    const uint32_t S = (uint32_t)c.names.size(), B = c.B, F = (uint32_t)features.size();
+    std::vector<uint64_t> raw((size_t)rk_edgestat_out_words(B, F));
+    uint32_t info[2] = {0, 0};
+    ok(rk_edgestat_batch(c.db, c.tree, S, c.words, F, F ? c.meta.data() : nullptr, raw.data(), info), "rk_edgestat_batch");
+    std::vector<double> table((size_t)B * (8 + 4 * F)), feature_table(2 * (size_t)F);
+    ok(rk_edgestat_finish_host(B, S, F, raw.data(), info, table.data(), F ? feature_table.data() : nullptr), "rk_edgestat_finish_host");
+    return rkh::edge_stats_table(c.names, features, info[0], B, table.data(), feature_table.data());
+}
+
 struct Report {
     const char *name;                        // the option `--name FILE`
     std::string Options::*path;
@@ -230,6 +253,7 @@ static const Report REPORTS[] = {
      [](const Options &o) { return o.kmeans_k < 1 || o.kmeans_k > RK_KMEANS_MAX_K || o.kmeans_rounds < 1 || o.kmeans_rounds > RK_KMEANS_MAX_ROUNDS; },
      "--kmeans needs --kmeans-k in 1..64; --kmeans-rounds must be in 1..1024", false, kmeans_report},
     {"diversity", &Options::diversity, "measures the samples of one run", nullptr, nullptr, false, diversity_report},
+    {"edge-stats", &Options::edge_stats, "relates the edges to the samples of one run", nullptr, nullptr, false, edge_stats_report},
 };
 
 // ---- the rules: the first row that fires is reported, `rk_place: <sentence>` and 2 (a row without a sentence: the usage text) ----
@@ -255,6 +279,8 @@ static std::vector<Rule> rules() {
                      std::string("--") + rep.name + " " + rep.does + ": it needs --sample-sep (with --masses or --masses-only)"});
         if (rep.out_of_range) r.push_back({[&rep](const Options &o) { return !(o.*rep.path).empty() && rep.out_of_range(o); }, rep.range_sentence});
     }
+    r.push_back({[](const Options &o) { return !o.metadata.empty() && o.edge_stats.empty(); },
+                 "--metadata names the sample metadata of the edge statistics: it needs --edge-stats"});
     r.push_back({[](const Options &o) { return !o.thetas_ok || o.thetas.size() > RK_DIVERSITY_MAX_THETA; },
                  "--diversity-theta takes at most 8 numbers in 0..8, separated by commas"});
     r.push_back({[](const Options &o) {
@@ -299,6 +325,7 @@ struct Run {
     rk_params p;
     fs::path log_dir;
     std::optional<DeviceTree> on_device;
+    std::vector<double> sample_meta;  // --edge-stats: the metadata of the run's samples [F][S], looked up behind the FASTA scan
     const rk_tree *device_tree() {  // (built once, and only by a run that asks for a report or --edpl)
         if (!on_device) on_device.emplace(o.device, tree);
         return on_device->p;
@@ -336,7 +363,7 @@ static void write_reports(Run &run, const std::vector<std::string> &names, const
             for (uint32_t s = 0; s < S; s++)
                 for (uint32_t x = 0; x < B && !with_mass[s]; x++) with_mass[s] = host_words[(size_t)s * (2 * (size_t)B + 4) + x] != 0;
         }
-        write_text(path, rep.text(ReportCall{run.o, run.db, run.device_tree(), B, names, words, with_mass}));
+        write_text(path, rep.text(ReportCall{run.o, run.db, run.device_tree(), B, names, words, with_mass, run.sample_meta}));
     }
 }
 
@@ -397,6 +424,7 @@ static Marks run_reads(Run &run, const ReadSet &rs, EngineReady engine_ready, Wr
     rkh::SampleMembers members;
     if (o.sample_sep_given) members = rkh::sample_members(rs.n_records, n, rs.header, rs.uniq_of_rec, o.sample_sep[0]);
     const rkh::SampleMembers *sm = o.sample_sep_given ? &members : nullptr;
+    if (sm && !o.edge_stats.empty()) run.sample_meta = rkh::metadata_of_samples(sm->names, o.meta ? &*o.meta : nullptr);  // (before placing: every sample has its line)
     rkh::RawArray<uint32_t> weight, flags;
     flags.alloc(n);
     auto weigh = [&]() { weight.alloc(n); rs.weights(weight.data()); };
@@ -511,6 +539,7 @@ int main(int argc, char **argv) {
         if (rc >= 0) return rc;
         if ((rc = check_options(o)) != 0) return rc;
         const double t_start = now();
+        if (!o.metadata.empty()) o.meta = rkh::parse_metadata(slurp(o.metadata));  // (its syntax, before the device is opened)
         rkh::Tree tree;
         rk_db *db = open_db(o, tree);
         if (!db) return 0;
@@ -525,7 +554,7 @@ int main(int argc, char **argv) {
         const uint32_t K = o.keep_at_most;
         const bool masses_only = !o.masses_only.empty();
         Run run{o, db, tree, rk_params{K, o.keep_factor, o.amb_mode, o.nsbound},
-                o.logs_given ? fs::path(o.logs) : fs::absolute(fs::path(masses_only ? o.masses_only : o.out)).parent_path() / "logs", std::nullopt};
+                o.logs_given ? fs::path(o.logs) : fs::absolute(fs::path(masses_only ? o.masses_only : o.out)).parent_path() / "logs", std::nullopt, {}};
 
         if (!o.classic) {
             // ---- every host thread on every pass (rk_fastio.hpp) ----

@@ -27,6 +27,7 @@
 #include "rk_edpl.h"
 #include "rk_kmeans.h"
 #include "rk_diversity.h"
+#include "rk_edgestat.h"
 #include "rk_geometry.h"  // (host arithmetic; place_packed16_kernel takes the dense list's room from it, as the host does)
 
 #include <type_traits>

@@ -4,7 +4,8 @@
 // _batch / _finish_host) and the per-read EDPL (rk_edpl_device / _host / _batch, rk_tree_distance_host)
 // and the phylogenetic k-means of the samples (rk_kmeans_device / _host / _batch)
 // and the per-sample diversity measures (rk_diversity_device / _host / _batch, rk_diversity_math_host)
-// -- over the kernels of rk_samples.h, rk_epca.h, rk_edpl.h, rk_kmeans.h and rk_diversity.h and the host twins of rk_samples_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
+// and the edge statistics (rk_edgestat_device / _host / _batch / _finish_host)
+// -- over the kernels of rk_samples.h, rk_epca.h, rk_edpl.h, rk_kmeans.h, rk_diversity.h and rk_edgestat.h and the host twins of rk_samples_host.h and rk_edgestat_host.h.  The calls read mass buffers that any masses call filled; they touch no placement kernel and no launch
 // scratch, and only the _batch calls touch a database handle.
 // What the analyses share exists once, ahead of them: the range tests (samples_range, squash_range, kmeans_range, diversity_range, epca_range), which
 // the _host calls and the prepare step of every analysis read; the prepare step (tests, then the workspace plan, carved by Carve and
@@ -15,6 +16,7 @@
 #pragma once
 
 #include "rk_samples_host.h"
+#include "rk_edgestat_host.h"
 
 static_assert(RK_KR_CHUNK == rk::KR_CHUNK && RK_KR_CHUNK == KR_CHUNK_IDS, "one chunk rule for the header, the host twin and the kernel");
 constexpr uint64_t RK_KR_MAX_PART_BYTES = 1ull << 28;  // per-chunk partials while they stay below 256 MiB: beyond, the tiles alone fill the device
@@ -1076,6 +1078,183 @@ extern "C" int rk_epca_finish_host(uint32_t n_branches, uint32_t n_samples, uint
     if (!raw) return fail(RK_ERR_INVALID, "%s: null raw output", who);
     if (!eigenvalue || !share || !residual || !projection || !loading) return fail(RK_ERR_INVALID, "%s: null output", who);
     rk::epca_finish(n_branches, n_samples, k, raw, eigenvalue, share, residual, projection, loading);
+    return RK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Edge statistics, edge dispersion and edge correlation: rk_edgestat_out_words / _work_bytes / _device / _host /
+// _batch / _finish_host.
+// ------------------------------------------------------------------------------------------------
+static_assert(RK_EDGESTAT_MAX_SAMPLES == rk::EDGESTAT_MAX_SAMPLES && RK_EDGESTAT_MAX_FEATURES == rk::EDGESTAT_MAX_FEATURES && RK_EDGESTAT_MAX_FEATURES == EDGESTAT_MAX_F &&
+                  rk::EDGESTAT_NAN == EDGESTAT_FILLER && RK_EDGESTAT_COUNT_MAX_SAMPLES <= EDGESTAT_COUNT_LIMIT,
+              "one set of constants for the header, the host twin and the kernels");
+
+// The workspace of rk_edgestat_device: clade[S][B] (64-bit) | P0[B][S] | P1[B][S] | gc[F][S] | gd[F][S] (32-bit) | active[S]
+struct EdgestatPlan {
+    uint64_t clade_at, p0_at, p1_at, gc_at, gd_at, active_at, bytes;
+};
+static int edgestat_range(const char *who, uint32_t S, uint32_t F) {
+    if (S < 1 || S > RK_EDGESTAT_MAX_SAMPLES) return fail(RK_ERR_INVALID, "%s: n_samples=%u must be in 1..%u", who, S, RK_EDGESTAT_MAX_SAMPLES);
+    if (F > RK_EDGESTAT_MAX_FEATURES) return fail(RK_ERR_INVALID, "%s: n_features=%u must be in 0..%u", who, F, RK_EDGESTAT_MAX_FEATURES);
+    return RK_OK;
+}
+// the tests of rk_edgestat_work_bytes and rk_edgestat_device, and the plan
+static int edgestat_prepare(const char *who, const rk_tree *t, uint32_t S, uint32_t F, EdgestatPlan &p) {
+    if (!t) return fail(RK_ERR_INVALID, "%s: null tree", who);
+    if (int rc = edgestat_range(who, S, F)) return rc;
+    const uint64_t sb = (uint64_t)S * t->B * 8;
+    Carve c;
+    p.clade_at = c.take(sb);
+    p.p0_at = c.take(sb);
+    p.p1_at = c.take(sb);
+    p.gc_at = c.take((uint64_t)F * S * 8);
+    p.gd_at = c.take((uint64_t)F * S * 4, 4);
+    p.active_at = c.take((uint64_t)S * 4, 4);
+    p.bytes = c.total();
+    return plan_fits(who, t, S, p.bytes);
+}
+
+extern "C" uint64_t rk_edgestat_out_words(uint32_t n_branches, uint32_t n_features) {
+    if (n_branches < 1 || n_branches > 65535 || n_features > RK_EDGESTAT_MAX_FEATURES) return 0;
+    return rk::edgestat_out_words(n_branches, n_features);
+}
+
+extern "C" uint64_t rk_edgestat_work_bytes(const rk_tree *t, uint32_t n_samples, uint32_t n_features) {
+    EdgestatPlan p;
+    return edgestat_prepare("rk_edgestat_work_bytes", t, n_samples, n_features, p) ? 0 : p.bytes;
+}
+
+// The launches behind rk_edgestat_device.  `steps` (developer builds, scripts/edgestat_rate.py): bit 0 the clade sums, 1 the profiles,
+// 2 the start and the column prelude, 3 the edge kernel.  `cross`: rows of at most this many samples are ranked by counting.
+static int edgestat_launch(const rk_tree *t, uint32_t S, const uint64_t *d_masses, uint32_t F, const double *d_meta, uint64_t *d_raw, uint32_t *d_info, void *d_work,
+                           const EdgestatPlan &p, hipStream_t s, uint32_t cross, unsigned steps = 15) {
+    const uint32_t B = t->B;
+    char *w = (char *)d_work;
+    u64 *clade = (u64 *)(w + p.clade_at);
+    double *P0 = (double *)(w + p.p0_at), *P1 = (double *)(w + p.p1_at), *gc = (double *)(w + p.gc_at);
+    int *gd = (int *)(w + p.gd_at);
+    u32 *active = (u32 *)(w + p.active_at);
+    const u64 W = (u64)rk_masses_words(B);
+    const bool sort = S > cross;
+    uint32_t N = 1;  // the sorted keys: S rounded up to a power of two
+    while (N < S) N <<= 1;
+    if (steps & 1) {
+        hipLaunchKernelGGL(clade_masses_kernel, dim3(S), dim3(256), 0, s, B, W, t->node_at, t->end_at, t->span_node, t->span_end, t->span_off, (const u64 *)d_masses, clade);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 2) {
+        hipLaunchKernelGGL(edgestat_profiles_kernel, dim3((B + 31) / 32, (S + 31) / 32), dim3(256), 0, s, B, S, W, t->root, (const u64 *)d_masses, (const u64 *)clade, P0, P1);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 4) {
+        hipLaunchKernelGGL(edgestat_init_kernel, dim3(1), dim3(256), 0, s, B, S, F, t->root, (const u64 *)clade, d_meta, active, (u32 *)d_info);
+        if (F)
+            hipLaunchKernelGGL(edgestat_column_kernel, dim3(F), dim3(EDGESTAT_THREADS), (size_t)(sort ? N : S) * 8, s, B, S, F, N, sort ? 1u : 0u, (const u32 *)d_info,
+                               (const u32 *)active, d_meta, gc, gd, (u64 *)d_raw);
+        HIP_TRY(hipGetLastError());
+    }
+    if (steps & 8) {
+        if (sort)
+            hipLaunchKernelGGL(edgestat_edge_kernel<true>, dim3(2 * B), dim3(EDGESTAT_THREADS), (size_t)N * 8, s, B, S, F, N, (const u32 *)d_info, (const u32 *)active,
+                               (const double *)P0, (const double *)P1, (const double *)gc, (const int *)gd, (u64 *)d_raw);
+        else
+            hipLaunchKernelGGL(edgestat_edge_kernel<false>, dim3((2 * B + EDGESTAT_WAVES - 1) / EDGESTAT_WAVES), dim3(EDGESTAT_THREADS), (size_t)EDGESTAT_WAVES * S * 8, s, B, S,
+                               F, N, (const u32 *)d_info, (const u32 *)active, (const double *)P0, (const double *)P1, (const double *)gc, (const int *)gd, (u64 *)d_raw);
+        HIP_TRY(hipGetLastError());
+    }
+    return RK_OK;
+}
+
+extern "C" int rk_edgestat_device(const rk_tree *t, uint32_t n_samples, const uint64_t *d_masses, uint32_t n_features, const double *d_meta, uint64_t *d_raw,
+                                  uint32_t *d_info, void *d_work, uint64_t work_bytes, void *stream) {
+    const char *who = "rk_edgestat_device";
+    EdgestatPlan p;
+    if (int rc = edgestat_prepare(who, t, n_samples, n_features, p)) return rc;
+    if (!d_masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    if (n_features && !d_meta) return fail(RK_ERR_INVALID, "%s: null metadata with n_features=%u", who, n_features);
+    if (!d_raw || !d_info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if ((uintptr_t)d_raw % 8 || (uintptr_t)d_meta % 8 || (uintptr_t)d_info % 4)
+        return fail(RK_ERR_INVALID, "%s: the raw output and the metadata must be 8-byte aligned, the info words 4-byte aligned", who);
+    if (int rc = work_args(who, "rk_edgestat_work_bytes", d_work, work_bytes, p.bytes)) return rc;
+    HIP_TRY(hipSetDevice(t->device));
+    unsigned steps = 15;
+    uint32_t cross = RK_EDGESTAT_COUNT_MAX_SAMPLES;
+    if (const char *v = rk_knob("RK_EDGESTAT_STEPS")) steps = (unsigned)atoi(v);  // developer builds (scripts/edgestat_rate.py)
+    if (const char *v = rk_knob("RK_EDGESTAT_COUNT_MAX")) cross = std::min<uint32_t>((uint32_t)atoi(v), EDGESTAT_COUNT_LIMIT);  // developer builds: both forms on one shape
+    return edgestat_launch(t, n_samples, d_masses, n_features, d_meta, d_raw, d_info, d_work, p, (hipStream_t)stream, cross, steps);
+}
+
+extern "C" int rk_edgestat_host(uint32_t n_branches, const int32_t *parent, uint32_t n_samples, const uint64_t *masses, uint32_t n_features, const double *meta,
+                                uint64_t *raw, uint32_t *info, uint32_t n_threads) {
+    const char *who = "rk_edgestat_host";
+    RK_GUARD_BEGIN
+    if (int rc = edgestat_range(who, n_samples, n_features)) return rc;
+    if (n_features && !meta) return fail(RK_ERR_INVALID, "%s: null metadata with n_features=%u", who, n_features);
+    if (!raw || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    rk::TreeWalk w;
+    if (rk::tree_walk(who, n_branches, parent, nullptr, false, w, g_err, sizeof(g_err))) return RK_ERR_INVALID;
+    if (!masses) return fail(RK_ERR_INVALID, "%s: null mass buffer", who);
+    const uint64_t B = n_branches, S = n_samples, W = rk_masses_words(n_branches);
+    std::vector<uint64_t> clade(S * B);
+    uint64_t T = host_threads(n_threads, S);
+    int rc = masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        for (uint64_t s = th; s < S; s += T) rk::clade_masses_sample(w, parent, masses + s * W, clade.data() + s * B);
+    });
+    if (rc) return rc;
+    std::vector<uint8_t> active(S);
+    uint32_t n = 0;
+    for (uint64_t s = 0; s < S; s++) n += active[s] = clade[s * B + w.root] != 0;
+    const uint64_t n_out = rk::edgestat_out_words(n_branches, n_features);
+    info[0] = n;
+    info[1] = 0;
+    if (n == 0) {
+        for (uint64_t i = 0; i < n_out; i++) raw[i] = 0;
+        return RK_OK;
+    }
+    rk::EdgestatColumns col;
+    rk::edgestat_columns(n_samples, n, n_features, active.data(), meta, col, raw + B * rk::edgestat_row_words(n_features));
+    info[1] = col.unusable;
+    // edges dealt round to the threads
+    T = host_threads(n_threads, B);
+    return masses_fan_out(who, T, 0, false, nullptr, [&](uint64_t th, uint64_t *) {
+        rk::edgestat_edges(n_branches, n_samples, W, w.root, n, n_features, active.data(), masses, clade.data(), col, (uint32_t)th, (uint32_t)T, raw);
+    });
+    RK_GUARD_END(who)
+}
+
+// The drivers' call: as rk_epca_batch, with the metadata uploaded behind the outputs; a value that is not finite is refused here
+extern "C" int rk_edgestat_batch(rk_db *db, const rk_tree *t, uint32_t n_samples, const uint64_t *masses, uint32_t n_features, const double *meta, uint64_t *raw,
+                                 uint32_t *info) {
+    const char *who = "rk_edgestat_batch";
+    if (int rc = batch_handles(who, db, t)) return rc;
+    EdgestatPlan p;
+    if (int rc = edgestat_prepare(who, t, n_samples, n_features, p)) return rc;
+    if (n_features && !meta) return fail(RK_ERR_INVALID, "%s: null metadata with n_features=%u", who, n_features);
+    if (!raw || !info) return fail(RK_ERR_INVALID, "%s: null output", who);
+    for (uint64_t i = 0; i < (uint64_t)n_features * n_samples; i++)
+        if (!std::isfinite(meta[i]))
+            return fail(RK_ERR_INVALID, "%s: metadata column %u of sample %u is not finite", who, (uint32_t)(i / n_samples), (uint32_t)(i % n_samples));
+    const uint64_t raw_bytes = rk::edgestat_out_words(t->B, n_features) * 8, meta_bytes = (uint64_t)n_features * n_samples * 8;  // raw | meta | info
+    return samples_batch(who, db, n_samples, masses, p.bytes, raw_bytes + meta_bytes + 8, [&](const uint64_t *d_masses, char *d_out, void *d_work, hipStream_t s) -> int {
+        double *d_meta = (double *)(d_out + raw_bytes);
+        uint32_t *d_info = (uint32_t *)(d_out + raw_bytes + meta_bytes);
+        if (meta_bytes) HIP_TRY(hipMemcpyAsync(d_meta, meta, meta_bytes, hipMemcpyHostToDevice, s));
+        if (int rc = rk_edgestat_device(t, n_samples, d_masses, n_features, n_features ? d_meta : nullptr, (uint64_t *)d_out, d_info, d_work, p.bytes, s)) return rc;
+        HIP_TRY(hipMemcpyAsync(raw, d_out, raw_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(info, d_info, 8, hipMemcpyDeviceToHost, s));
+        return RK_OK;
+    });
+}
+
+extern "C" int rk_edgestat_finish_host(uint32_t n_branches, uint32_t n_samples, uint32_t n_features, const uint64_t *raw, const uint32_t *info, double *table,
+                                       double *feature_table) {
+    const char *who = "rk_edgestat_finish_host";
+    if (!rk_edgestat_out_words(n_branches, n_features)) return fail(RK_ERR_INVALID, "%s: n_branches=%u, n_features=%u: out of 1..65535, 0..%u", who, n_branches, n_features, RK_EDGESTAT_MAX_FEATURES);
+    if (int rc = edgestat_range(who, n_samples, n_features)) return rc;
+    if (!raw || !info) return fail(RK_ERR_INVALID, "%s: null raw output", who);
+    if (!table || (n_features && !feature_table)) return fail(RK_ERR_INVALID, "%s: null output", who);
+    if (info[0] > n_samples) return fail(RK_ERR_INVALID, "%s: info says %u active samples of %u", who, info[0], n_samples);
+    rk::edgestat_finish(n_branches, n_features, raw, info, table, feature_table);
     return RK_OK;
 }
 

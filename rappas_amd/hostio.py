@@ -519,6 +519,76 @@ def diversity_table(names, theta, values):
     return "".join(out)
 
 
+def _metadata_number(text):
+    """a number of a --metadata file: [+-] digits with an optional point and fraction, an optional exponent; None for anything else or
+    for a value that is not finite (what strtod and float() accept beyond that -- inf, nan, hex, blanks -- is no number here)"""
+    if not re.fullmatch(r"[+-]?(?:[0-9]+(?:\.[0-9]*)?|\.[0-9]+)(?:[eE][+-]?[0-9]+)?", text):
+        return None
+    v = float(text)
+    return v if math.isfinite(v) else None
+
+
+def parse_metadata(text):
+    """the sample metadata of `--metadata TSV` -- the twin of rkh::parse_metadata (rappas_amd/csrc/host/rk_hostio.hpp), the same
+    sentences.  A first line `sample<TAB>name_1<TAB>...<TAB>name_F` with F <= 8, then one line per sample: its name and F finite
+    numbers; empty lines are skipped.  -> (feature names, {sample name: [F values]}).  ValueError("--metadata: ...") for a header
+    that is none, a line with another number of fields, a field that is no finite number, a sample named twice."""
+    if isinstance(text, bytes):
+        text = text.decode("utf-8", "replace")
+    lines = [(i + 1, ln) for i, ln in enumerate(text.split("\n")) if ln.rstrip("\r") != ""]
+    head = lines[0][1].rstrip("\r").split("\t") if lines else []
+    if not head or head[0] != "sample" or len(head) - 1 > 8 or any(n == "" for n in head[1:]):
+        raise ValueError("--metadata: the first line must be sample<TAB>name_1<TAB>...<TAB>name_F with at most 8 column names")
+    rows = {}
+    for no, ln in lines[1:]:
+        f = ln.rstrip("\r").split("\t")
+        if len(f) != len(head):
+            raise ValueError(f"--metadata: line {no} has {len(f)} fields, the first line has {len(head)}")
+        values = [_metadata_number(v) for v in f[1:]]
+        for v, field in zip(values, f[1:]):
+            if v is None:
+                raise ValueError(f"--metadata: line {no}: '{field}' is not a finite number")
+        if f[0] in rows:
+            raise ValueError(f"--metadata: line {no}: the sample '{f[0]}' has a line already")
+        rows[f[0]] = values
+    return head[1:], rows
+
+
+def metadata_of_samples(sample_names, parsed):
+    """float64 [F, S]: the metadata of the samples of a run, in sample order, from parse_metadata's answer (None: no file, F = 0);
+    ValueError for more than 4096 samples and for a sample of the run without a line -- lines of other samples are ignored"""
+    if len(sample_names) > 4096:
+        raise ValueError(f"--edge-stats: the run has {len(sample_names)} samples, at most 4096")
+    names, rows = parsed if parsed is not None else ([], {})
+    for s in sample_names:
+        if parsed is not None and s not in rows:
+            raise ValueError(f"--metadata: the sample '{s}' of the run has no line")
+    return np.array([[rows[s][f] for s in sample_names] for f in range(len(names))], np.float64).reshape(len(names), len(sample_names))
+
+
+def edge_stats_table(names, feature_names, n_active, table, feature_table):
+    """the text `--edge-stats FILE` writes, every double as `%.17g` (a NaN as `nan`): a line
+    `#edge_stats<TAB>S<TAB>B<TAB>F<TAB>n_active`; a line `#columns` with node, the eight fixed columns and, per metadata column,
+    mass_pearson_<name>, mass_spearman_<name>, imb_pearson_<name>, imb_spearman_<name>; a line per node id (the id and its values);
+    `#features` and a line per metadata column (its name, its mean and its population variance over the samples with mass);
+    `#samples_without_mass<TAB>n`.  table [B, 8 + 4F] and feature_table [F, 2] are what edgestats.edgestat_finish gives.  The twin of
+    rkh::edge_stats_table, byte-identical."""
+    S, F = len(names), len(feature_names)
+    table = np.asarray(table, np.float64)
+    B = table.shape[0]
+    table = table.reshape(B, 8 + 4 * F)
+    feature_table = np.asarray(feature_table, np.float64).reshape(F, 2)
+    num = lambda v: "\tnan" if np.isnan(v) else "\t%.17g" % v
+    out = [f"#edge_stats\t{S}\t{B}\t{F}\t{n_active}\n", "#columns\tnode\tmass_mean\tmass_var\tmass_sd\tmass_cv\tmass_vmr\timb_mean\timb_var\timb_sd"]
+    out.extend(f"\tmass_pearson_{n}\tmass_spearman_{n}\timb_pearson_{n}\timb_spearman_{n}" for n in feature_names)
+    out.append("\n")
+    out.extend(str(x) + "".join(num(v) for v in table[x]) + "\n" for x in range(B))
+    out.append("#features\n")
+    out.extend(feature_names[f] + num(feature_table[f, 0]) + num(feature_table[f, 1]) + "\n" for f in range(F))
+    out.append(f"#samples_without_mass\t{S - n_active}\n")
+    return "".join(out)
+
+
 def _fmt12(x):
     """NumberFormat.getNumberInstance(Locale.UK) with exactly 12 fraction digits (NewickWriter.java:61-64): grouping commas,
     HALF_EVEN on the exact binary value."""

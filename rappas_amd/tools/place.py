@@ -27,6 +27,8 @@ KMEANS_NEEDS_SAMPLE_SEP = "--kmeans clusters the samples of one run: it needs --
 KMEANS_RANGES = "--kmeans needs --kmeans-k in 1..64; --kmeans-rounds must be in 1..1024"
 DIVERSITY_NEEDS_SAMPLE_SEP = "--diversity measures the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
 DIVERSITY_RANGES = "--diversity-theta takes at most 8 numbers in 0..8, separated by commas"
+EDGE_STATS_NEEDS_SAMPLE_SEP = "--edge-stats relates the edges to the samples of one run: it needs --sample-sep (with --masses or --masses-only)"
+METADATA_NEEDS_EDGE_STATS = "--metadata names the sample metadata of the edge statistics: it needs --edge-stats"
 EDPL_NEEDS_OUT ="--edpl reads the placements of a run that writes a jplace: it needs --out (and cannot be combined with --masses-only)"
 SAMPLE_SEP_NEEDS_MASSES = "--sample-sep names the samples of the per-edge tables: it needs --masses or --masses-only"
 TRANSLATE_NEEDS_AA = "--translate needs an amino-acid database (this one holds DNA: DNA reads are placed on it as they are, see --strand)"
@@ -84,6 +86,14 @@ def _diversity_report(et, db, names, words, host_words, o):
     return hostio.diversity_table(names, o["diversity_theta"], et.diversity_batch(db, len(names), o["diversity_theta"], words).values)
 
 
+def _edge_stats_report(et, db, names, words, host_words, o):
+    from .. import edgestats
+    features = o["metadata"][0] if o["metadata"] is not None else []
+    raw, info = edgestats.edgestat_batch(et, db, len(names), o["edge_stats_meta"], words)
+    r = edgestats.edgestat_finish(et.n_branches, len(names), raw, info, features)
+    return hostio.edge_stats_table(names, features, r.n_active, r.table, r.feature_table)
+
+
 def _thetas_in_range(theta):
     return len(theta) <= 8 and all(0.0 <= t <= 8.0 for t in theta)
 
@@ -96,6 +106,7 @@ SAMPLE_REPORTS = (
     Report("epca", EPCA_NEEDS_SAMPLE_SEP, lambda o: 1 <= o["epca_components"] <= 8 and 1 <= o["epca_iters"] <= 10000, EPCA_RANGES, _epca_report),
     Report("kmeans", KMEANS_NEEDS_SAMPLE_SEP, lambda o: 1 <= o["kmeans_k"] <= 64 and 1 <= o["kmeans_rounds"] <= 1024, KMEANS_RANGES, _kmeans_report),
     Report("diversity", DIVERSITY_NEEDS_SAMPLE_SEP, lambda o: _thetas_in_range(o["diversity_theta"]), DIVERSITY_RANGES, _diversity_report),
+    Report("edge_stats", EDGE_STATS_NEEDS_SAMPLE_SEP, None, None, _edge_stats_report),
 )
 
 
@@ -106,6 +117,19 @@ def _check_reports(requested, with_samples, options):
             raise ValueError(r.needs_sample_sep)
         if requested[r.name] and r.in_range is not None and not r.in_range(options):
             raise ValueError(r.ranges)
+
+
+def _parse_metadata(requested, metadata):
+    """the text of `--metadata TSV` parsed (hostio.parse_metadata) before anything is opened; None without one"""
+    if metadata is not None and not requested["edge_stats"]:
+        raise ValueError(METADATA_NEEDS_EDGE_STATS)
+    return hostio.parse_metadata(metadata) if metadata is not None else None
+
+
+def _sample_metadata(requested, options, sample_names):
+    """after the FASTA scan and before placing: the metadata of the run's samples [F, S] -- every sample must have a line"""
+    if requested["edge_stats"]:
+        options["edge_stats_meta"] = hostio.metadata_of_samples(sample_names, options["metadata"])
 
 
 def _run_reports(et, db, sample_names, words, host_words, requested, options):
@@ -145,6 +169,14 @@ def diversity_text(db, tree, sample_names, words, theta, device=0):
         return _diversity_report(et, db, sample_names, words, None, dict(diversity_theta=theta))
 
 
+def edge_stats_text(db, tree, sample_names, words, metadata=None, device=0):
+    """`--edge-stats FILE`: the table (hostio.edge_stats_table) of the edge dispersion of the samples and of the edge correlation with
+    the sample metadata (the text of a `--metadata TSV`, or None), as kr_text"""
+    parsed = hostio.parse_metadata(metadata) if metadata is not None else None
+    with _edge_tree(tree, device) as et:
+        return _edge_stats_report(et, db, sample_names, words, None, dict(metadata=parsed, edge_stats_meta=hostio.metadata_of_samples(sample_names, parsed)))
+
+
 def _edpl_report(et, db, records, unique, res, keep_at_most):
     return hostio.edpl_table(records, unique, res.n_rows, et.edpl_batch(db, keep_at_most, res.n_rows, res.branch, res.lwr))
 
@@ -171,7 +203,8 @@ def parse_thetas(text):
 
 def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), guppy=False,
                call_string="", device=0, union=False, dbimage=None, save_dbimage=None, strand="fwd", translate=False, masses=False, sample_sep=None, kr=False,
-               squash=False, epca=False, epca_components=5, epca_iters=200, edpl=False, kmeans=False, kmeans_k=0, kmeans_rounds=100, diversity=False, diversity_theta=()):
+               squash=False, epca=False, epca_components=5, epca_iters=200, edpl=False, kmeans=False, kmeans_k=0, kmeans_rounds=100, diversity=False, diversity_theta=(), edge_stats=False,
+               metadata=None):
     """db_text: the bytes of a --jsondb dump, or (union=True) of a Java-serialized .union database; or dbimage = the path of the
     engine's own image file (rk_db_load: mmap + upload, the reference tree in its user blob).  strand: "fwd" (the reference's
     behaviour), "rev" or "both" (DNA: reads placed from their reverse complement / on the better strand; res.reversed is then the text of
@@ -179,15 +212,16 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
     one reported per read (res.frames is then the text of frames_<query>.tsv); not together with strand "rev" / "both".  masses: res.masses is
     then the text of the per-edge table `--masses FILE` writes (hostio.masses_table; a read weighs the number of FASTA records it stands for);
     with sample_sep (one character) one table per sample (hostio.sample_members, hostio.masses_samples_table), and then for every
-    report of SAMPLE_REPORTS asked for by its name (kr, squash, epca, kmeans, diversity) res.<name> is the text `--<name> FILE`
-    writes, with the report's own keywords (epca_components components after epca_iters iterations; kmeans_k clusters and at most
-    kmeans_rounds rounds; the thetas diversity_theta).  edpl: res.edpl is the text `--edpl FILE` writes (edpl_text), with any strand
+    report of SAMPLE_REPORTS asked for by its name (kr, squash, epca, kmeans, diversity, edge_stats) res.<name> is the text
+    `--<name> FILE` writes, with the report's own keywords (epca_components components after epca_iters iterations; kmeans_k clusters and
+    at most kmeans_rounds rounds; the thetas diversity_theta; metadata, the text of the `--metadata TSV` of the edge statistics).  edpl: res.edpl is the text `--edpl FILE` writes (edpl_text), with any strand
     and with translate."""
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
-    requested = dict(kr=kr, squash=squash, epca=epca, kmeans=kmeans, diversity=diversity)
+    requested = dict(kr=kr, squash=squash, epca=epca, kmeans=kmeans, diversity=diversity, edge_stats=edge_stats)
     options = dict(epca_components=epca_components, epca_iters=epca_iters, kmeans_k=kmeans_k, kmeans_rounds=kmeans_rounds, diversity_theta=diversity_theta)
     _check_reports(requested, masses and sample_sep is not None, options)
+    options["metadata"] = _parse_metadata(requested, metadata)
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     sample_words = None
     try:
@@ -196,6 +230,8 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
         records = hostio.read_fasta(fasta_text)
         unique, names = hostio.dedup_reads(records)
         members = hostio.sample_members(records, unique, sample_sep) if masses and sample_sep is not None else None
+        if members is not None:
+            _sample_metadata(requested, options, members[0])
         seq, off = hostio.pack_batch([s for _, s in unique])
         if translate:
             res = PlacementProcess(db, ns_bound).processQueriesTranslated(seq, off, keepAtMost=keep_at_most, keepFactor=keep_factor)
@@ -232,20 +268,21 @@ def place_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean"
 
 def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb="mean", ns_bound=float("-inf"), device=0, union=False,
                      dbimage=None, save_dbimage=None, strand="fwd", translate=False, sample_sep=None, kr=False, squash=False, epca=False, epca_components=5,
-                     epca_iters=200, kmeans=False, kmeans_k=0, kmeans_rounds=100, diversity=False, diversity_theta=()):
+                     epca_iters=200, kmeans=False, kmeans_k=0, kmeans_rounds=100, diversity=False, diversity_theta=(), edge_stats=False, metadata=None):
     """`--masses-only FILE`: scan, dedup and gather as place_file, then ONE profile-only call (processQueriesMasses) with the
     multiplicities as weights: the placements are summed on the device and only the flags come back.  -> a namespace with .masses (the
     table's text, what place_file(masses=True) gives), .notplaced, .reversed (strand "rev" / "both", else None), .flags and .counters.
     No jplace and no frames log: the rows and the frame bytes never reach the host.  With sample_sep (one character) the one call is
     processQueriesMassesSamples with the membership of hostio.sample_members, and .masses holds one table per sample; the reports of
-    SAMPLE_REPORTS are then asked for as of place_file (.kr, .squash, .epca, .kmeans, .diversity), each from the buffer that call left
+    SAMPLE_REPORTS are then asked for as of place_file (.kr, .squash, .epca, .kmeans, .diversity, .edge_stats), each from the buffer that call left
     on the device."""
     from types import SimpleNamespace
     if translate and strand != "fwd":
         raise ValueError(TRANSLATE_WITH_STRAND)
-    requested = dict(kr=kr, squash=squash, epca=epca, kmeans=kmeans, diversity=diversity)
+    requested = dict(kr=kr, squash=squash, epca=epca, kmeans=kmeans, diversity=diversity, edge_stats=edge_stats)
     options = dict(epca_components=epca_components, epca_iters=epca_iters, kmeans_k=kmeans_k, kmeans_rounds=kmeans_rounds, diversity_theta=diversity_theta)
     _check_reports(requested, sample_sep is not None, options)
+    options["metadata"] = _parse_metadata(requested, metadata)
     reports = dict.fromkeys(requested)
     db, tree = _open_db(db_text, union, dbimage, save_dbimage, device)
     try:
@@ -259,6 +296,7 @@ def masses_only_file(db_text, fasta_text, keep_at_most=7, keep_factor=0.01, amb=
                       treatAmbiguitiesWithMax=(amb == "max"))
         if sample_sep is not None:
             sample_names, m_off, m_sample, m_weight = hostio.sample_members(records, unique, sample_sep)
+            _sample_metadata(requested, options, sample_names)
             words, flags, counters = PlacementProcess(db, ns_bound).processQueriesMassesSamples(
                 seq, off, len(sample_names), m_sample, member_off=m_off, member_weight=m_weight, **common)
             table = hostio.masses_samples_table(tree, sample_names, words)
@@ -370,6 +408,15 @@ def main(argv=None):
                          "rooted_pd_<theta> and bwpd_<theta>, a line name<TAB>values (%%.17g) per sample (nan without mass), and a last line "
                          "#samples_without_mass<TAB>n")
     ap.add_argument("--diversity-theta", default=None, metavar="T1,T2,...", help="--diversity: at most 8 exponents in 0..8 for the one-parameter families")
+    ap.add_argument("--edge-stats", default=None, metavar="FILE",
+                    help="with --sample-sep: edge dispersion and edge correlation, found on the device: for every edge the mean, variance, "
+                         "standard deviation, coefficient of variation and variance-to-mean ratio of its mass share across the samples, mean, "
+                         "variance and standard deviation of its imbalance, and per metadata column the Pearson and Spearman correlation of "
+                         "both: a line #edge_stats<TAB>S<TAB>B<TAB>F<TAB>n_active, a line #columns, a line per node id (%%.17g, nan), #features "
+                         "and a line name<TAB>mean<TAB>variance per column, and a last line #samples_without_mass<TAB>n; at most 4096 samples")
+    ap.add_argument("--metadata", default=None, metavar="TSV",
+                    help="--edge-stats: the sample metadata, a first line sample<TAB>name_1<TAB>...<TAB>name_F (F <= 8) and a line per sample "
+                         "with its name and F finite numbers; every sample of the run needs a line, lines of other samples are ignored")
     ap.add_argument("--edpl", default=None, metavar="FILE",
                     help="with --out: the EDPL of every placed read (the expected distance between its placement locations: the sum over the "
                          "pairs of its rows of LWR x LWR x the tree path between the midpoints of the two edges), computed on the device: a "
@@ -397,6 +444,8 @@ def main(argv=None):
         options["diversity_theta"] = parse_thetas(a.diversity_theta)
     except ValueError as e:
         ap.error(str(e))
+    if a.metadata is not None and a.edge_stats is None:
+        ap.error(METADATA_NEEDS_EDGE_STATS)
     if a.edpl is not None and a.out is None:
         ap.error(EDPL_NEEDS_OUT)
     if a.masses_only is None and a.out is None:
@@ -407,11 +456,15 @@ def main(argv=None):
             db_text = f.read()
     with open(a.fasta, "rb") as f:
         fasta_text = f.read()
+    metadata = None
+    if a.metadata is not None:
+        with open(a.metadata, "rb") as f:
+            metadata = f.read()
     call = "".join(" " + x for x in (argv if argv is not None else sys.argv[1:]))
     import json
     import time
     common = dict(device=a.device, union=a.uniondb is not None, dbimage=a.dbimage, save_dbimage=a.save_dbimage, strand=a.strand, translate=a.translate,
-                  sample_sep=a.sample_sep, **requested, **options)
+                  sample_sep=a.sample_sep, metadata=metadata, **requested, **options)
     t0 = time.perf_counter()
     try:
         if a.masses_only is not None:
@@ -420,7 +473,7 @@ def main(argv=None):
             doc, res = place_file(db_text, fasta_text, a.keep_at_most, a.keep_factor, a.amb, a.nsbound, a.guppy_compat, call, masses=a.masses is not None,
                                   edpl=a.edpl is not None, **common)
     except ValueError as e:
-        if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith("--sample-sep: "):
+        if str(e) != TRANSLATE_NEEDS_AA and not str(e).startswith(("--sample-sep: ", "--metadata: ", "--edge-stats: ")):
             raise
         print("rappas_amd.tools.place: " + str(e), file=sys.stderr)
         return 1
